@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: joint-timesteps/s of inverse_dynamics_trajectory over B x N rows.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config all|c2|c2f|c3|c4|c4s|c5|c5b] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config all|c2|c2f|c3|c4|c4s|c5|c5b] [--full] [--no-cpu-baseline]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W          (one rank per GPU)
+
+A plain run (no --full) measures the headline only: set-up, the untimed ramp and W warm-up steps, the K timed steps, and the
+line - `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the roofline figures of those K steps.  Everything
+described below beyond that (cold figures, streaming probes, the sampled clock, the single-set loop, PMC figures, CPU baselines and
+parity samples, the other configurations, and at N > 1 the all-gather phases and the strong-scaled entries) runs with --full.
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (see dump_outputs).
 
 A "step" is one pass of the hot path over one batch of synthetic input that is already resident in
 HBM: config c2 (default, the one BASELINE.json's metric is quoted on) = UR5 (6 DOF), B = 4096
@@ -13,7 +20,7 @@ the path has no exchange step, so the timed step has no collective.  The RCCL al
 reassembles the full torque history on every GPU is then measured in a second loop (step + all-gather)
 and reported in the "allgather" object next to `value`.
 
-The default run (`--config all`, one GPU) times c2 as the line's `value` / `roofline` / `cpu_baseline` and then every other
+The --full run (`--config all`, one GPU) times c2 as the line's `value` / `roofline` / `cpu_baseline` and then every other
 BASELINE configuration (c2f, c3, c4, c4s, c5 on the time-major device layout, c5b on the batch-major one) into the line's
 `"configs"` object: ms_per_step, kernel, kernel_ms (+ cold), roofline {frac, traffic, algorithmic bytes}, roofline_valu and a
 `parity_sample` against the pinned C oracle.  Every parity sample is an ASSERTION: the line is still printed, and the
@@ -223,6 +230,38 @@ def emit(result):
         return x
 
     print(json.dumps(strict(result), allow_nan=False), flush=True)
+
+
+DUMP_BYTES = 48 << 20   # --dump-outputs: what one run writes at most, over all ranks
+
+
+def dump_outputs(out_dir, info, ctx, B, arrays):
+    """--dump-outputs: the arrays the last timed step handed its caller, as out_dir/<name>.npy (rank r > 0: <name>_rank<r>.npy).
+    `arrays`: name -> (device buffer holding B trajectories, one trajectory's shape (N, ...), dtype, time-major?); a buffer is
+    (B, N, ...) on the device, or (N, B, n) when time-major.  Written (trajectories, N, ...) in the step's own float type.  When all
+    trajectories do not fit in DUMP_BYTES, a fixed seeded sample of them, ascending, the same one for every array and every run."""
+    from manipulapy_amd import _hip
+
+    traj_bytes = sum(int(np.prod(shape)) * np.dtype(dt).itemsize for _, shape, dt, _ in arrays.values())
+    keep = int(min(B, max(1, DUMP_BYTES // info.world // traj_bytes)))
+    idx = np.arange(B) if keep == B else np.sort(np.random.default_rng(SEED).choice(B, keep, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    files = []
+    for name, (buf, shape, dt, time_major) in arrays.items():
+        if time_major:   # (N, B, n): the whole array, then the kept trajectories' columns
+            out = np.ascontiguousarray(np.swapaxes(buf.download((shape[0], B) + tuple(shape[1:]), dt)[:, idx], 0, 1))
+        elif keep == B:
+            out = buf.download((B,) + tuple(shape), dt)
+        else:            # one contiguous copy per kept trajectory
+            out = np.empty((keep,) + tuple(shape), dt)
+            nb = out[0].nbytes
+            for j, b in enumerate(idx):
+                _hip._check(ctx.lib.mp_memcpy_d2h(ctx.handle, out[j].ctypes.data, buf.offset(int(b) * nb), nb))
+        fname = name + (f"_rank{info.rank}" if info.rank else "") + ".npy"
+        np.save(os.path.join(out_dir, fname), out)
+        files.append(fname)
+    return {"dir": out_dir, "files": files, "trajectories": keep, "of": int(B),
+            "sample": "all" if keep == B else f"seeded (numpy default_rng({SEED})), ascending"}
 
 
 def device_copy_probe(ctx):
@@ -565,9 +604,11 @@ def bench_fd(args, cfg, info, hg, ctx, model, t, props, headline=True):
     def step():
         ctx.fd_trajectory(model, d_th0, d_dth0, d_tau, d_F, B, N, g, 0.01, 1, d_pos, d_vel, d_acc, dtype=np.float32, time_major=tmaj)
 
-    cold = cold_figures(ctx, step, max(1, min(8, args.steps)), not args.no_clock_sample)
-    kern_ms_cold = cold["kernel_ms_cold"]
-    probe = mix_probe(ctx, cfg, n, B * N)   # this box's streaming rate for the roll-out's byte mix, same process (every rank, its own GPU)
+    cold, probe = None, None
+    if args.full:
+        cold = cold_figures(ctx, step, max(1, min(8, args.steps)), not args.no_clock_sample)
+        kern_ms_cold = cold["kernel_ms_cold"]
+        probe = mix_probe(ctx, cfg, n, B * N)   # this box's streaming rate for the roll-out's byte mix, same process (every rank, its own GPU)
     ramp(ctx, step, args.ramp_ms)
     for _ in range(args.warmup):
         step()
@@ -585,7 +626,7 @@ def bench_fd(args, cfg, info, hg, ctx, model, t, props, headline=True):
     hg.barrier()
     elapsed = hg.max(dt)
     kern_ms = b.elapsed_ms_since(a) / args.steps   # average launch period = kernel duration + dispatch gap
-    clock = None if args.no_clock_sample else sampled_clock(ctx, step, args.steps, kern_ms)
+    clock = None if args.no_clock_sample or not args.full else sampled_clock(ctx, step, args.steps, kern_ms)
     alg_bytes = algorithmic_bytes_per_row(cfg, n) * B * N
     achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
     result = {
@@ -599,8 +640,9 @@ def bench_fd(args, cfg, info, hg, ctx, model, t, props, headline=True):
                    "inputs": "gravity-holding torques + 1e-3 disturbance, per-step wrench 0.02 x reference wrench (finite for all N steps)",
                    "sharding": f"batch axis over {world} rank(s), no collective in the timed step"},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                     "traffic": None, "kernel": kernel_name(cfg), "kernel_ms": kern_ms, "kernel_ms_cold": kern_ms_cold,
-                     "frac_cold": alg_bytes / (kern_ms_cold * 1e-3) / 1e9 / HBM_PEAK_GBPS, "cold": cold_with_frac(cold, alg_bytes),
+                     "traffic": None, "kernel": kernel_name(cfg), "kernel_ms": kern_ms,
+                     **({"kernel_ms_cold": kern_ms_cold, "frac_cold": alg_bytes / (kern_ms_cold * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                         "cold": cold_with_frac(cold, alg_bytes)} if cold else {}),
                      "algorithmic_bytes_per_launch": alg_bytes,
                      "kernel_ms_method": "HIP events on the launch stream around the K launches of the timed region, / K",
                      "note": ("sequential in time, one lane per trajectory; every step streams whole lines (64 x 24-byte rows per array), the next step's rows "
@@ -612,14 +654,16 @@ def bench_fd(args, cfg, info, hg, ctx, model, t, props, headline=True):
     }
     if clock is not None:
         result["roofline"]["clock"] = clock
-    attach_counters(result, cfg["name"])
+    if args.full:
+        attach_counters(result, cfg["name"])
     if probe is not None:
         result["roofline"]["probe"] = probe
         if probe.get("GBps"):
             result["roofline"]["frac_of_probe"] = achieved / probe["GBps"]
-    if info.rank == 0 and headline:
+    if args.full and info.rank == 0 and headline:
         result["roofline"]["device_copy"] = device_copy_probe(ctx)
-    if info.rank == 0 and not args.no_cpu_baseline:
+    host_legs = args.full and not args.no_cpu_baseline
+    if info.rank == 0 and host_legs:
         # rank 0 (of any world): its own shard against the roll-out oracle; the other ranks wait in the barrier below
         host = (lambda d: np.ascontiguousarray(np.swapaxes(d.download((N, B, n), np.float32), 0, 1))) if tmaj else (lambda d: d.download((B, N, n), np.float32))
         pos, vel, acc = host(d_pos), host(d_vel), host(d_acc)
@@ -630,8 +674,12 @@ def bench_fd(args, cfg, info, hg, ctx, model, t, props, headline=True):
         result["parity_sample"] = par
         result["roofline"]["parity"] = {"ok": par["ok"], "rows_checked": int(par["trajectories"] * N), "rows_total": int(B * N),
                                         "trajectories_checked": int(par["trajectories"]), "worst_drift_over_scale": par["drift_over_scale"]["max"]}
-    if world > 1 and not args.no_cpu_baseline:
+    if world > 1 and host_legs:
         hg.barrier()
+    if args.dump_outputs and headline:
+        shape = (N, n)
+        result["outputs"] = dump_outputs(args.dump_outputs, info, ctx, B, {k: (d, shape, np.float32, tmaj) for k, d in
+                                                                           (("positions", d_pos), ("velocities", d_vel), ("accelerations", d_acc))})
     for b in bufs:
         b.free()
     return result
@@ -1085,6 +1133,26 @@ def attach_counters(result, config):
                                    "clock_hz_pmc": v["clock_hz"], "simds": v["simds"], "source": v.get("source")}
 
 
+class OneProcess:
+    """sharding.HostGather's answers for a world of one, without its gloo import: torch takes seconds to load and a one-GPU line
+    has no rendezvous."""
+
+    def __init__(self, info):
+        self.info = info
+
+    def barrier(self):
+        pass
+
+    def max(self, value):
+        return float(value)
+
+    def broadcast_bytes(self, payload, nbytes, src=0):
+        return payload or b""
+
+    def allgather(self, local):
+        return local.copy()
+
+
 def self_launch(gpus: int) -> int:
     """`python bench.py --gpus N` started as ONE command: before anything in this process has touched HIP, start N fresh
     worker processes (one per GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment, exactly what
@@ -1133,7 +1201,12 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="all", choices=["all"] + sorted(CONFIGS),
-                    help="all (default): c2 as the line's value plus every other configuration in its \"configs\" object")
+                    help="all (default): c2 as the line's value (with --full, every other configuration in its \"configs\" object)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: cold figures, probes, sampled clock, single-set loop, PMC figures, CPU baseline "
+                         "and parity samples, the other configurations, and at N > 1 the all-gather phases and strong-scaled entries")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy (at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--parity-set0-only", dest="parity_all_sets", action="store_false",
                     help="headline parity sample: only input set 0 (default: every input set the timed steps rotate over, ~10 s each)")
@@ -1168,7 +1241,7 @@ def main():
     world = info.world
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
-    hg = sharding.HostGather(info)  # gloo; no-op for a single process
+    hg = sharding.HostGather(info) if world > 1 else OneProcess(info)  # gloo between ranks
     if world > 1:
         os.environ.setdefault("NCCL_DEBUG", "WARN")  # a collective that cannot start says why on stderr (the line only carries RCCL's one-line error)
     if os.environ.get("MANIPULAPY_BENCH_DRYRUN") == "1":
@@ -1201,7 +1274,7 @@ def main():
     ctx = _hip.HipContext(dev)
     ctx.selftest()
     props = ctx.properties()
-    names = [args.config] if args.config != "all" else ["c2"] + (list(SECONDARY) if world == 1 else [])
+    names = [args.config] if args.config != "all" else ["c2"] + (list(SECONDARY) if world == 1 and args.full else [])
     result, hung = run_config(names[0], args, info, hg, ctx, props, headline=True)
     failed = []
     if not (result.get("parity_sample") or {"ok": True}).get("ok", True):
@@ -1219,7 +1292,8 @@ def main():
             result["configs"][name] = entry
             if "error" in entry or not (entry.get("parity_sample") or {"ok": True}).get("ok", True):
                 failed.append(name)
-    strong_on = args.config == "all" and not hung and (world > 1 or os.environ.get("MANIPULAPY_BENCH_FORCE_GATHER") == "1")
+    gather_on = args.full and (world > 1 or os.environ.get("MANIPULAPY_BENCH_FORCE_GATHER") == "1")
+    strong_on = args.config == "all" and not hung and gather_on
     if strong_on:
         # the configurations BASELINE defines on the 8-GPU split, strong-scaled over the ranks, each with its reassembly
         result.setdefault("configs", {})
@@ -1236,7 +1310,7 @@ def main():
             result["configs"][name + "_strong"] = entry
             if hung or out_of_step:
                 break
-    if world > 1 or os.environ.get("MANIPULAPY_BENCH_FORCE_GATHER") == "1":
+    if gather_on:
         # an N > 1 line whose collectives could not RUN still carries its compute-only figures; say so at the top level, where a
         # reader of the line's first keys sees it: names of the entries whose reassembly raised or timed out
         errs = [k for k, v in [(names[0], result)] + list((result.get("configs") or {}).items())
@@ -1420,6 +1494,7 @@ def bench_id(args, cfg, info, hg, ctx, model, t, props, headline):
         Returns (max-over-ranks wall seconds, mean kernel ms from HIP events on the launch stream)."""
         do = step_fn or step
         ramp(ctx, step, ramp_ms)
+        turn[0] = 0   # the ramp's step count follows the clock: restart the rotation so the sets the K steps use depend on W and K only
         for _ in range(args.warmup):
             do()
             if fn_after_step:
@@ -1478,24 +1553,27 @@ def bench_id(args, cfg, info, hg, ctx, model, t, props, headline):
         return wall, kms
 
     # ---- cold figures (reported beside the sustained ones, never as `value`)
-    cold = cold_figures(ctx, step, max(1, min(5, args.steps)), not args.no_clock_sample)
-    kern_ms_cold = cold["kernel_ms_cold"]
+    cold, probe = None, None
+    if args.full:
+        cold = cold_figures(ctx, step, max(1, min(5, args.steps)), not args.no_clock_sample)
+        kern_ms_cold = cold["kernel_ms_cold"]
 
-    # ---- this box's streaming rate for the configuration's own byte mix and size, right before the timed region
-    if cfg["op"] == "fk_jac_id":
-        ramp(ctx, step, ramp_ms)           # (the probe of a power-capped configuration is taken in the settled state too)
-    probe = mix_probe(ctx, cfg, n, rows)   # (every rank, on its own GPU: the ranks stay in step; rank 0's is reported)
+        # ---- this box's streaming rate for the configuration's own byte mix and size, right before the timed region
+        if cfg["op"] == "fk_jac_id":
+            ramp(ctx, step, ramp_ms)           # (the probe of a power-capped configuration is taken in the settled state too)
+        probe = mix_probe(ctx, cfg, n, rows)   # (every rank, on its own GPU: the ranks stay in step; rank 0's is reported)
 
     # ---- the timed step: every rank evaluates its own shard; the path has no exchange step, so no collective
     elapsed, kern_ms = timed()
+    last = sets[(turn[0] - 1) % nsets]   # the arrays the last timed step wrote (what --dump-outputs writes)
     kern_ms_all = hg.max(kern_ms)
-    clock = None if args.no_clock_sample else sampled_clock(ctx, step, args.steps, kern_ms)   # (K more launches, not part of `value`)
+    clock = None if args.no_clock_sample or not args.full else sampled_clock(ctx, step, args.steps, kern_ms)   # (K more launches, not part of `value`)
 
     # ---- what a caller that reuses ONE set of arrays gets (the reference's usage, planning/trajectory_dynamics.py:31-90: one
     #      trajectory's arrays, evaluated again and again): every launch's arrays overlap the previous launch's parked float64 pass,
     #      so a pass runs behind every launch instead of one per `nsets` launches.  Reported beside the headline, never as `value`.
     single = None
-    if cfg["dtype"] == "f32" and cfg["op"] in ("id", "fused") and nsets > 1 and args.launch == "stream" and not args.no_single_set:
+    if args.full and cfg["dtype"] == "f32" and cfg["op"] in ("id", "fused") and nsets > 1 and args.launch == "stream" and not args.no_single_set:
         def step_single():
             turn[0] = 0
             step()
@@ -1506,7 +1584,7 @@ def bench_id(args, cfg, info, hg, ctx, model, t, props, headline):
     #      measured as a second timed loop (step + all-gather) and reported next to `value`
     allgather = None
     # MANIPULAPY_BENCH_FORCE_GATHER=1 runs the phase on a single GPU too (a one-rank communicator): exercises this code path
-    if headline and (world > 1 or os.environ.get("MANIPULAPY_BENCH_FORCE_GATHER") == "1") and not args.no_gather:
+    if args.full and headline and (world > 1 or os.environ.get("MANIPULAPY_BENCH_FORCE_GATHER") == "1") and not args.no_gather:
         allgather = {"bytes_per_rank": nb, "collective": "ncclAllGather (RCCL), one call per step after the kernel"}
 
         def verify_gather(d_all):
@@ -1609,10 +1687,11 @@ def bench_id(args, cfg, info, hg, ctx, model, t, props, headline):
                    "sharding": f"batch axis over {world} rank(s), no collective in the timed step"},
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBPS, "traffic": None,
-                     "kernel": kernel_name(cfg), "kernel_ms": kern_ms, "kernel_ms_cold": kern_ms_cold,
-                     "frac_cold": alg_bytes / (kern_ms_cold * 1e-3) / 1e9 / HBM_PEAK_GBPS, "cold": cold_with_frac(cold, alg_bytes),
-                     "sustained_vs_cold": "`kernel_ms` / `frac` are the sustained figures of the timed region (after the ramp and warm-up); "
-                                          "`kernel_ms_cold` is the mean of the first launches after 0.5 s of idle (see `cold`)",
+                     "kernel": kernel_name(cfg), "kernel_ms": kern_ms,
+                     **({"kernel_ms_cold": kern_ms_cold,
+                         "frac_cold": alg_bytes / (kern_ms_cold * 1e-3) / 1e9 / HBM_PEAK_GBPS, "cold": cold_with_frac(cold, alg_bytes),
+                         "sustained_vs_cold": "`kernel_ms` / `frac` are the sustained figures of the timed region (after the ramp and warm-up); "
+                                              "`kernel_ms_cold` is the mean of the first launches after 0.5 s of idle (see `cold`)"} if cold else {}),
                      "kernel_ms_max_over_ranks": kern_ms_all, "algorithmic_bytes_per_launch": alg_bytes,
                      "kernel_ms_method": ("HIP event pair around every %d-th launch of the timed region" % args.event_stride)
                      if args.event_stride > 0 else
@@ -1623,7 +1702,8 @@ def bench_id(args, cfg, info, hg, ctx, model, t, props, headline):
     }
     if clock is not None:
         result["roofline"]["clock"] = clock
-    attach_counters(result, cfg["name"])
+    if args.full:
+        attach_counters(result, cfg["name"])
     if probe is not None:
         result["roofline"]["probe"] = probe
         if probe.get("GBps"):
@@ -1633,10 +1713,11 @@ def bench_id(args, cfg, info, hg, ctx, model, t, props, headline):
         result["roofline"]["frac_single_set"] = alg_bytes / (single["kernel_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBPS
         result["roofline"]["single_set"] = ("the same K launches on ONE set of arrays (a caller that reuses its buffers): a float64 pass runs "
                                             "behind every launch; `frac` / `value` rotate over `config.input_sets` sets")
-    if info.rank == 0 and headline:
+    if args.full and info.rank == 0 and headline:
         result["roofline"]["device_copy"] = device_copy_probe(ctx)
 
-    if info.rank == 0 and not args.no_cpu_baseline and not hung:
+    host_legs = args.full and not args.no_cpu_baseline and not hung
+    if info.rank == 0 and host_legs:
         # rank 0 (of any world): ITS shard of the configuration against the pinned C oracle, the oracle timed on this box's cores; at
         # N > 1 within HOST_BUDGET_S while the other ranks wait in the barrier below
         try:
@@ -1661,7 +1742,7 @@ def bench_id(args, cfg, info, hg, ctx, model, t, props, headline):
             result["cpu_baseline"] = {"value": None, "unit": "joint-timesteps/s", "cores": 0, "kind": "port",
                                       "sample": f"not measured: {type(exc).__name__}: {str(exc)[:200]}"}
             result["parity_sample"] = {"ok": False, "error": f"{type(exc).__name__}: {str(exc)[:200]}"}
-    if world > 1 and not args.no_cpu_baseline and not hung:
+    if world > 1 and host_legs:
         hg.barrier()
     if "parity_sample" in result:
         checked_sets = 1 + len(result["parity_sample"].get("other_input_sets", []))
@@ -1672,6 +1753,11 @@ def bench_id(args, cfg, info, hg, ctx, model, t, props, headline):
         result["value_with_allgather"] = allgather.get("value_with_allgather")
         result["value_overlapped"] = (allgather.get("overlapped") or {}).get("value")
         result["verified"] = bool(allgather.get("verified") is True and (allgather.get("overlapped") or {}).get("verified", True) is True)
+    if args.dump_outputs and headline and not hung:
+        # (with --full, later launches on these arrays recompute the same values from the same inputs)
+        outs = {"T": (last["d_T"], (N, 16)), "J": (last["d_J"], (N, 6 * n))} if cfg["op"] == "fk_jac_id" else {}
+        outs["tau"] = (last["d_tau"], (N, n))
+        result["outputs"] = dump_outputs(args.dump_outputs, info, ctx, B, {k: (buf, shape, dt_np, False) for k, (buf, shape) in outs.items()})
     if not hung:
         for b in bufs:
             b.free()

@@ -2583,6 +2583,52 @@ def test_in_place_float64_rows_without_a_list(tables):
 
 
 @pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(ctx, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full: one JSON line with the headline's fields for
+    exactly K timed steps and none of --full's extras, and DIR/tau.npy - the torques the last timed step wrote, for c2's seeded
+    sample of trajectories of the input set that step used - which the library's trajectory generation + the pinned C oracle
+    reproduce under the bench's float32 parity rule."""
+    import json
+    import subprocess
+    import sys
+
+    import bench
+    from manipulapy_amd import _hip, robots
+    from oracle import c_oracle
+
+    K, W = 7, 2
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W),
+                          "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and res.stdout.strip(), f"rc {res.returncode}\n{res.stdout[-1500:]}\n{res.stderr[-3000:]}"
+    line = json.loads(res.stdout.strip().splitlines()[-1])
+    assert line["steps"] == K and line["warmup"] == W and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "joint-timesteps/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["metric"] == "joint-timesteps/sec (NxBxDOF) inverse-dynamics trajectory"
+    assert not {"configs", "cpu_baseline", "parity_sample", "cpu_twin", "roofline_valu"} & set(line)
+    assert not {"kernel_ms_cold", "cold", "probe", "clock", "device_copy", "frac_single_set"} & set(line["roofline"])
+    cfg = bench.CONFIGS["c2"]
+    B, N, n = cfg["B"], cfg["N"], 6
+    out = line["outputs"]
+    assert out["files"] == ["tau.npy"] and out["of"] == B
+    tau = np.load(tmp_path / "tau.npy")
+    assert tau.dtype == np.float32 and tau.shape == (out["trajectories"], N, n) and tau.nbytes <= 64 << 20
+    # which trajectories and which input set: seeded sample; timed step k (0-based) uses set (W + k) % nsets
+    idx = np.sort(np.random.default_rng(bench.SEED).choice(B, out["trajectories"], replace=False))
+    k = (W + K - 1) % line["config"]["input_sets"]
+    t = robots.robot_tables("ur5")
+    lo, hi = t["joint_limits"][:, 0], t["joint_limits"][:, 1]
+    rng = np.random.default_rng(bench.SEED + 2 + 100_000 * k)
+    start, end = rng.uniform(lo, hi, (B, n)).astype(np.float32), rng.uniform(lo, hi, (B, n)).astype(np.float32)
+    pick = np.array([0, 1, len(idx) // 2, len(idx) - 1])
+    model = _hip.HipModel(t["S_list"], t["Mlist_per_link"], t["Glist"], t["M_ee"], t["joint_limits"])
+    p, v, a = ctx.batch_trajectory_host(model, start[idx[pick]], end[idx[pick]], 2.0, N, 5)
+    want, _ = c_oracle.inverse_dynamics_rows(bench.oracle_tables(ref, "ur5"), *(x.reshape(-1, n).astype(np.float64) for x in (p, v, a)))
+    par = bench.parity_rows(tau[pick].reshape(-1, n), want, "f32")
+    assert par["ok"], par
+
+
+@pytest.mark.gpu
 def test_bench_n2_line_end_to_end_with_two_ranks_sharing_the_gpu():
     """The N > 1 bench line has never met a multi-GPU node (the pool gives one GPU; the driver's 8-GPU run decides).  What CAN run
     here is its whole flow with two ranks sharing this GPU (MANIPULAPY_BENCH_SHARE_DEVICE=1; the figures mean nothing, the flow
@@ -2597,7 +2643,7 @@ def test_bench_n2_line_end_to_end_with_two_ranks_sharing_the_gpu():
     env = dict(os.environ, PYTHONPATH=ROOT, MANIPULAPY_BENCH_SHARE_DEVICE="1", MANIPULAPY_BENCH_GATHER_TIMEOUT="90")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2"], env=env,
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--full"], env=env,
                          capture_output=True, text=True, timeout=900)
     assert res.returncode == 0 and res.stdout.strip(), f"rc {res.returncode}\n{res.stdout[-1500:]}\n{res.stderr[-3000:]}"
     line = json.loads(res.stdout.strip().splitlines()[-1])

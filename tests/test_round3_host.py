@@ -415,6 +415,50 @@ def test_bench_parity_rules_and_line_shape():
             assert isinstance(bench.kernel_name(dict(cfg, specialized=spec, dof=6)), str)
 
 
+def test_bench_dump_outputs_sample_and_layouts(tmp_path):
+    """bench.py --dump-outputs on stand-in device buffers (host arrays behind the same copy calls): an output that fits is written
+    whole; a larger one as the same seeded, ascending sample of trajectories for every array and every run, under 64 MB in all;
+    time-major (N, B, n) arrays come out (trajectories, N, n) like batch-major ones."""
+    import ctypes
+    import types
+
+    import bench
+
+    class _Buf:
+        def __init__(self, a): self.a = np.ascontiguousarray(a)
+        def download(self, shape, dt): return self.a.view(dt).reshape(shape).copy()
+        def offset(self, nbytes): assert 0 <= nbytes < self.a.nbytes; return self.a.ctypes.data + nbytes
+
+    def d2h(handle, dst, src, nb):
+        ctypes.memmove(dst, src, nb)
+        return 0
+
+    ctx = types.SimpleNamespace(handle=None, lib=types.SimpleNamespace(mp_memcpy_d2h=d2h))
+    one = types.SimpleNamespace(rank=0, world=1)
+    B, N, n = 64, 10, 6
+    tau = np.arange(B * N * n, dtype=np.float64).reshape(B, N, n)
+    out = bench.dump_outputs(str(tmp_path / "small"), one, ctx, B, {"tau": (_Buf(tau), (N, n), np.float64, False)})
+    assert out["trajectories"] == B and out["files"] == ["tau.npy"]
+    np.testing.assert_array_equal(np.load(tmp_path / "small" / "tau.npy"), tau)
+    # c2's size: 4096 x 1000 x 6 float32 (98 MB) does not fit
+    B, N = 4096, 1000
+    big = np.random.default_rng(0).standard_normal((B, N, n)).astype(np.float32)
+    tm = np.ascontiguousarray(np.swapaxes(big, 0, 1))
+    arrays = {"tau": (_Buf(big), (N, n), np.float32, False), "tm": (_Buf(tm), (N, n), np.float32, True)}
+    outs = [bench.dump_outputs(str(tmp_path / d), one, ctx, B, arrays) for d in ("a", "b")]
+    assert outs[0] == dict(outs[1], dir=outs[0]["dir"]) and 0 < outs[0]["trajectories"] < B
+    a, t, b = (np.load(tmp_path / d / f) for d, f in (("a", "tau.npy"), ("a", "tm.npy"), ("b", "tau.npy")))
+    assert a.dtype == np.float32 and a.shape == (outs[0]["trajectories"], N, n) and a.nbytes + t.nbytes <= 64 << 20
+    np.testing.assert_array_equal(a, b)
+    np.testing.assert_array_equal(a, t)
+    idx = [int(np.flatnonzero((big[:, 0] == row[0]).all(axis=1))[0]) for row in a]
+    assert idx == sorted(set(idx))
+    np.testing.assert_array_equal(a, big[idx])
+    # rank 1 of 2: its own file name, half the bytes
+    r1 = bench.dump_outputs(str(tmp_path / "r"), types.SimpleNamespace(rank=1, world=2), ctx, B, {"tau": arrays["tau"]})
+    assert r1["files"] == ["tau_rank1.npy"] and 0 < r1["trajectories"] * N * n * 4 <= bench.DUMP_BYTES // 2
+
+
 def test_trac_ik_multi_start():
     """manipulapy_amd/trac_ik.py: the batched form (all guesses in one kinematics.inverse launch), the host form on bare
     callables, an unreachable target (best configuration, success False, inside the limits), a 9-joint arm (host form)."""

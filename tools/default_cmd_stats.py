@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel figures of a rocprofv3 kernel trace of the DEFAULT bench command (every configuration in one process): dispatches are
+"""Per-kernel figures of a rocprofv3 kernel trace of the --full bench command (every configuration in one process): dispatches are
 grouped by (kernel name, grid size) - c2, c4 and c4s launch the same symbol from different code objects - and each group's count,
 average, minimum and maximum duration are printed beside the bench line's own figure for the configuration that launches it.
 
@@ -49,7 +49,7 @@ for (name, who), v in buckets.items():
     rows.append({"kernel": name, "config": who, "dispatches": len(v), "avg_us": round(sum(v) / len(v) / 1e3, 2), "median_us": round(v[len(v) // 2] / 1e3, 2),
                  "min_us": round(v[0] / 1e3, 2), "max_us": round(v[-1] / 1e3, 2), "bench_kernel_ms": [round(x, 5) for x in km]})
 rows.sort(key=lambda r: r["config"])
-print(json.dumps({"command": "python3 bench.py --gpus 1 --steps 20 --warmup 5 (under rocprofv3 --kernel-trace --stats)",
+print(json.dumps({"command": "python3 bench.py --gpus 1 --steps 20 --warmup 5 --full (under rocprofv3 --kernel-trace --stats)",
                   "what": "every dispatch of a configuration's kernel in the whole run (cold windows, ramps, warm-up, timed steps, clock pass, single-set loop); "
                           "c4 and c4s launch the same symbol on the same number of rows and cannot be told apart in a trace",
                   "groups": rows}, indent=1))

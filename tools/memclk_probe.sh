@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/${1:-memclk}
 mkdir -p $OUT
-python3 $R/bench.py --config c3 --steps 4000 --no-cpu-baseline --no-single-set > $OUT/c3.json 2>/dev/null &
+python3 $R/bench.py --full --config c3 --steps 4000 --no-cpu-baseline --no-single-set > $OUT/c3.json 2>/dev/null &
 BPID=$!
 sleep 5
 for i in $(seq 1 40); do
