@@ -233,6 +233,22 @@ int mp_forward_dynamics_f64(mp_ctx* ctx, const mp_model* model, const double* d_
 int mp_forward_dynamics_f32(mp_ctx* ctx, const mp_model* model, const float* d_q, const float* d_qd,
                             const float* d_tau, int64_t rows, const double* g, const double* Ftip, float* d_qdd);
 
+/* Analytical first derivatives (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED above that).  No counterpart in this ABI's
+ * reference interface: the reference differentiates its torch / JAX backends with autograd (README "Differentiable");
+ * these are the same Jacobians, computed per row by forward-mode tangents through the Newton-Euler recursion (csrc/mp_deriv.h).
+ * Every (rows,n,n) output holds [row][i][j] = d out_i / d in_j; outputs marked "may be NULL" are skipped when NULL.  A row with a
+ * non-finite input comes back NaN in every output of that row only.  Derivatives are those of the unclipped torque.
+ *   inverse dynamics at (q, qd, qdd):  tau (rows,n, may be NULL), dtau_dq, dtau_dqd (rows,n,n), M = dtau_dqdd (rows,n,n, may be NULL)
+ *   forward dynamics at (q, qd, tau):  qdd (rows,n, may be NULL), dqdd_dq = -M^-1 dtau_dq, dqdd_dqd = -M^-1 dtau_dqd (rows,n,n),
+ *                                      Minv = dqdd_dtau (rows,n,n, may be NULL)
+ * The device forms are asynchronous (no synchronisation: they may be captured into a launch graph). */
+int mp_id_derivatives_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd,
+                          int64_t rows, const double* g, const double* Ftip, double* d_tau, double* d_dtau_dq, double* d_dtau_dqd,
+                          double* d_M);
+int mp_fd_derivatives_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_tau,
+                          int64_t rows, const double* g, const double* Ftip, double* d_qdd, double* d_dqdd_dq, double* d_dqdd_dqd,
+                          double* d_Minv);
+
 /* forward_dynamics_trajectory for B independent trajectories (planning/trajectory_dynamics.py:382-423,
  * :580-708; replaces forward_dynamics_kernel, cuda_kernels/trajectory_kernels.py:604-705): semi-implicit
  * Euler, intRes sub-steps of dt/intRes, positions clipped to the joint limits after every sub-step, row 0 =
@@ -300,6 +316,12 @@ int mp_fk_jac_id_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, c
 int mp_mass_matrix_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, int64_t rows, double* M);
 int mp_forward_dynamics_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd,
                                  const double* tau, int64_t rows, const double* g, const double* Ftip, double* qdd);
+int mp_id_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd,
+                               int64_t rows, const double* g, const double* Ftip, double* tau, double* dtau_dq, double* dtau_dqd,
+                               double* M);
+int mp_fd_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* tau,
+                               int64_t rows, const double* g, const double* Ftip, double* qdd, double* dqdd_dq, double* dqdd_dqd,
+                               double* Minv);
 int mp_fd_trajectory_host_f32(mp_ctx* ctx, const mp_model* model, const float* theta0, const float* dtheta0,
                               const float* taumat, const float* Ftipmat, int64_t B, int64_t N, const double* g,
                               double dt, int intRes, float* pos, float* vel, float* acc);
@@ -352,6 +374,12 @@ int mp_fk_jac_id_cpu_f64(const mp_model* model, const double* q, const double* q
 int mp_mass_matrix_cpu_f64(const mp_model* model, const double* q, int64_t rows, double* M, int nthreads);
 int mp_forward_dynamics_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* tau, int64_t rows,
                                 const double* g, const double* Ftip, double* qdd, int nthreads);
+int mp_id_derivatives_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, int64_t rows,
+                              const double* g, const double* Ftip, double* tau, double* dtau_dq, double* dtau_dqd, double* M,
+                              int nthreads);
+int mp_fd_derivatives_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* tau, int64_t rows,
+                              const double* g, const double* Ftip, double* qdd, double* dqdd_dq, double* dqdd_dqd, double* Minv,
+                              int nthreads);
 int mp_fd_trajectory_cpu_f32(const mp_model* model, const float* theta0, const float* dtheta0, const float* taumat,
                              const float* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, float* pos,
                              float* vel, float* acc, int nthreads);

@@ -102,6 +102,10 @@ SIGNATURES = {
     "mp_transpose_rows": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _vp]),
     "mp_mass_matrix_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _i64, _c_dp]),
     "mp_forward_dynamics_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp]),
+    "mp_id_derivatives_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
+    "mp_fd_derivatives_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
+    "mp_id_derivatives_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_fd_derivatives_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "mp_fd_trajectory_host_f32": (ctypes.c_int, [_vp, _vp, _c_fp, _c_fp, _c_fp, _c_fp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp]),
     "mp_fd_trajectory_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp]),
     "mp_cartesian_trajectory_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp]),
@@ -122,6 +126,8 @@ SIGNATURES = {
     "mp_fk_jac_id_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_mass_matrix_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _i64, _c_dp, ctypes.c_int]),
     "mp_forward_dynamics_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_id_derivatives_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_fd_derivatives_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_fd_trajectory_cpu_f32": (ctypes.c_int, [_vp, _c_fp, _c_fp, _c_fp, _c_fp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp, ctypes.c_int]),
     "mp_fd_trajectory_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp, ctypes.c_int]),
     "mp_inverse_kinematics_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, ctypes.c_int64, _c_dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, _c_dp, _vp, _vp, _vp, ctypes.c_int]),
@@ -562,6 +568,18 @@ class HipContext:
         F = _vec_or_none(Ftip, 6, "Ftip")
         _check(fn(self.handle, model.handle, _p(d_q), _p(d_qd), _p(d_tau), int(rows), _dptr(g), _dptr(F), _p(d_qdd)))
 
+    def id_derivatives(self, model, d_q, d_qd, d_qdd, rows, d_dtau_dq, d_dtau_dqd, d_tau=None, d_M=None, g=None, Ftip=None):
+        """Analytical inverse-dynamics derivatives on device buffers (float64; csrc/mp_deriv.h); asynchronous."""
+        _check(self.lib.mp_id_derivatives_f64(self.handle, model.handle, _p(d_q), _p(d_qd), _p(d_qdd), int(rows),
+                                              _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _p(d_tau),
+                                              _p(d_dtau_dq), _p(d_dtau_dqd), _p(d_M)))
+
+    def fd_derivatives(self, model, d_q, d_qd, d_tau, rows, d_dqdd_dq, d_dqdd_dqd, d_qdd=None, d_Minv=None, g=None, Ftip=None):
+        """Analytical forward-dynamics derivatives on device buffers (float64; csrc/mp_deriv.h); asynchronous."""
+        _check(self.lib.mp_fd_derivatives_f64(self.handle, model.handle, _p(d_q), _p(d_qd), _p(d_tau), int(rows),
+                                              _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _p(d_qdd),
+                                              _p(d_dqdd_dq), _p(d_dqdd_dqd), _p(d_Minv)))
+
     def cartesian_trajectory(self, d_Xstart, d_Xend, B, N, Tf, method, d_pos, d_vel, d_acc, d_orient):
         _check(self.lib.mp_cartesian_trajectory_f32(self.handle, _p(d_Xstart), _p(d_Xend), int(B), int(N), float(Tf), int(method),
                                                     _p(d_pos), _p(d_vel), _p(d_acc), _p(d_orient)))
@@ -726,6 +744,14 @@ class HipContext:
         _check(self.lib.mp_forward_dynamics_host_f64(self.handle, model.handle, _dptr(q), _dptr(qd), _dptr(tau), q.shape[0],
                                                      _dptr(g), _dptr(F), _dptr(out)))
         return out
+
+    def id_derivatives_host(self, model: HipModel, q, qd, qdd, g=None, Ftip=None):
+        """(tau, dtau_dq, dtau_dqd, M) of (rows, n) host rows: [row, i, j] = d tau_i / d x_j; M = dtau_dqdd."""
+        return _derivatives(self.lib.mp_id_derivatives_host_f64, (self.handle,), model, q, qd, qdd, g, Ftip, "qdd")
+
+    def fd_derivatives_host(self, model: HipModel, q, qd, tau, g=None, Ftip=None):
+        """(qdd, dqdd_dq, dqdd_dqd, Minv) of (rows, n) host rows: [row, i, j] = d qdd_i / d x_j; Minv = dqdd_dtau."""
+        return _derivatives(self.lib.mp_fd_derivatives_host_f64, (self.handle,), model, q, qd, tau, g, Ftip, "tau")
 
     def fd_trajectory_host(self, model: HipModel, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64,
                            layout: str = "batch_major", device_layout: str | None = None, out=None):
@@ -900,6 +926,32 @@ def cpu_forward_dynamics(model: "HipModel", q, qd, tau, g=None, Ftip=None, nthre
                                                       _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _dptr(out),
                                                       int(nthreads)))
     return out
+
+
+def _derivatives(fn, lead, model, q, qd, x, g, Ftip, xname, nthreads=None):
+    q = _as_c(q, np.float64, name="q")
+    if q.ndim != 2 or q.shape[1] != model.n:
+        raise ValueError(f"q must be (rows, {model.n}); got {q.shape}")
+    qd, x = _as_c(qd, np.float64, q.shape, "qd"), _as_c(x, np.float64, q.shape, xname)
+    rows, n = q.shape
+    y = np.empty_like(q)
+    dq, dqd, mat = np.empty((rows, n, n)), np.empty((rows, n, n)), np.empty((rows, n, n))
+    args = list(lead) + [model.handle, _dptr(q), _dptr(qd), _dptr(x), rows, _dptr(_vec_or_none(g, 3, "g")),
+                         _dptr(_vec_or_none(Ftip, 6, "Ftip")), _dptr(y), _dptr(dq), _dptr(dqd), _dptr(mat)]
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return y, dq, dqd, mat
+
+
+def cpu_id_derivatives(model: "HipModel", q, qd, qdd, g=None, Ftip=None, nthreads: int = 0):
+    """CPU twin of HipContext.id_derivatives_host: (tau, dtau_dq, dtau_dqd, M)."""
+    return _derivatives(load_library().mp_id_derivatives_cpu_f64, (), model, q, qd, qdd, g, Ftip, "qdd", nthreads)
+
+
+def cpu_fd_derivatives(model: "HipModel", q, qd, tau, g=None, Ftip=None, nthreads: int = 0):
+    """CPU twin of HipContext.fd_derivatives_host: (qdd, dqdd_dq, dqdd_dqd, Minv)."""
+    return _derivatives(load_library().mp_fd_derivatives_cpu_f64, (), model, q, qd, tau, g, Ftip, "tau", nthreads)
 
 
 def _pd_regulation_args(model, theta0, theta_des, Kp, Kd, g, steps):

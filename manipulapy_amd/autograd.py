@@ -1,0 +1,97 @@
+"""torch.autograd access to the analytical dynamics derivatives (csrc/mp_deriv.h).
+
+    from manipulapy_amd import autograd as mpa
+    tau = mpa.inverse_dynamics(dyn, q, qd, qdd, g, Ftip)          # q, qd, qdd: CPU float64 tensors, (n,) or (rows, n)
+    J = torch.autograd.functional.jacobian(lambda q: mpa.inverse_dynamics(dyn, q, qd, qdd, g, Ftip), q)
+
+The forward value is the registered inverse / forward dynamics operation, the backward pass the vector-Jacobian product with the
+registered derivative operation ("dynamics.inverse_derivatives" / "dynamics.fwd_derivatives"): the GPU under the "hip" backend,
+the CPU twin otherwise.  Once differentiable (no second derivatives).  g and Ftip are constants: a tensor among them that
+requires grad is refused.  Imported on demand only - never from the package's __init__ (torch stays optional).
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from .registry import execute_registered_kernel
+
+__all__ = ["inverse_dynamics", "forward_dynamics"]
+
+
+def _const(v, name):
+    if v is None:
+        return None
+    if isinstance(v, torch.Tensor):
+        if v.requires_grad:
+            raise ValueError(f"{name}: gradients with respect to g and Ftip are not provided - pass a tensor without requires_grad")
+        v = v.detach().cpu().numpy()
+    return np.asarray(v, dtype=np.float64)
+
+
+def _rows(t: torch.Tensor, name: str) -> np.ndarray:
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t, dtype=torch.float64)
+    if t.dtype != torch.float64 or t.device.type != "cpu":
+        raise TypeError(f"{name}: expected a CPU float64 tensor, got {t.dtype} on {t.device}")
+    return np.atleast_2d(t.detach().numpy()).astype(np.float64, copy=False)
+
+
+def _derivatives(op, dyn, q, qd, x, g, F):
+    model = dyn._derivative_model(op)
+    return execute_registered_kernel(op, model, q, qd, x, g, F)
+
+
+def _vjp(gy: torch.Tensor, J: np.ndarray, one: bool) -> torch.Tensor:
+    g2 = np.atleast_2d(gy.detach().cpu().numpy().astype(np.float64))
+    out = torch.from_numpy(np.einsum("ri,rij->rj", g2, J))
+    return out[0] if one else out
+
+
+class _InverseDynamics(torch.autograd.Function):
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gtau):
+        dq, dqd, M = ctx.jac
+        return None, _vjp(gtau, dq, ctx.one), _vjp(gtau, dqd, ctx.one), _vjp(gtau, M, ctx.one), None, None
+
+    @staticmethod
+    def forward(ctx, dyn, q, qd, qdd, g, Ftip):
+        one = q.dim() == 1
+        a, b, c = _rows(q, "q"), _rows(qd, "qd"), _rows(qdd, "qdd")
+        tau, dq, dqd, M = _derivatives("dynamics.inverse_derivatives", dyn, a, b, c, g, Ftip)
+        ctx.jac, ctx.one = (dq, dqd, M), one
+        out = torch.from_numpy(tau)
+        return out[0] if one else out
+
+
+class _ForwardDynamics(torch.autograd.Function):
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gqdd):
+        dq, dqd, Minv = ctx.jac
+        return None, _vjp(gqdd, dq, ctx.one), _vjp(gqdd, dqd, ctx.one), _vjp(gqdd, Minv, ctx.one), None, None
+
+    @staticmethod
+    def forward(ctx, dyn, q, qd, tau, g, Ftip):
+        one = q.dim() == 1
+        a, b, c = _rows(q, "q"), _rows(qd, "qd"), _rows(tau, "tau")
+        qdd, dq, dqd, Minv = _derivatives("dynamics.fwd_derivatives", dyn, a, b, c, g, Ftip)
+        ctx.jac, ctx.one = (dq, dqd, Minv), one
+        out = torch.from_numpy(qdd)
+        return out[0] if one else out
+
+
+def _as_tensor(x):
+    return x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x, dtype=np.float64))
+
+
+def inverse_dynamics(dyn, q, qd, qdd, g=None, Ftip=None) -> torch.Tensor:
+    """tau = ID(q, qd, qdd, g, Ftip) of a ManipulatorDynamics (with Mlist_per_link, n <= 8), differentiable in q, qd, qdd.
+    (n,) inputs give (n,), (rows, n) inputs (rows, n); one g / Ftip for every row."""
+    return _InverseDynamics.apply(dyn, _as_tensor(q), _as_tensor(qd), _as_tensor(qdd), _const(g, "g"), _const(Ftip, "Ftip"))
+
+
+def forward_dynamics(dyn, q, qd, tau, g=None, Ftip=None) -> torch.Tensor:
+    """qdd = FD(q, qd, tau, g, Ftip), differentiable in q, qd, tau; shapes as inverse_dynamics."""
+    return _ForwardDynamics.apply(dyn, _as_tensor(q), _as_tensor(qd), _as_tensor(tau), _const(g, "g"), _const(Ftip, "Ftip"))

@@ -885,6 +885,28 @@ static int fdyn_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const T
   return MP_OK;
 }
 
+// analytical derivatives (mp_deriv.h): float64, unrolled models only - a larger model fails here, it is never sent elsewhere
+static int deriv_impl(const char* fn, bool fd, mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd,
+                      const double* d_x, int64_t rows, const double* g, const double* Ftip, double* d_y, double* d_dq, double* d_dqd,
+                      double* d_mat) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (rows == 0) return MP_OK;
+  REQUIRE(d_q && d_qd && d_x && d_dq && d_dqd, "%s: null device pointer", fn);
+  REQUIRE(aligned16(d_q) && aligned16(d_qd) && aligned16(d_x) && aligned16(d_dq) && aligned16(d_dqd) && (!d_y || aligned16(d_y)) &&
+              (!d_mat || aligned16(d_mat)),
+          "%s: device pointers must be 16-byte aligned", fn);
+  MpCall<double> c;
+  make_call<double>(model, g, Ftip, &c);
+  const bool ftip = any_nonzero(Ftip);
+  PROFILE_SCOPE(ctx, fn);
+  if (fd) HIP_TRY(mpk_fd_deriv(ctx->compute, model->d, c, ftip, d_q, d_qd, d_x, d_y, d_dq, d_dqd, d_mat, (long)rows));
+  else HIP_TRY(mpk_id_deriv(ctx->compute, model->d, c, ftip, d_q, d_qd, d_x, d_y, d_dq, d_dqd, d_mat, (long)rows));
+  return MP_OK;
+}
+
 // specialised forward-dynamics roll-out (float32 only): -1 = none available, otherwise the launch's return code
 int launch_fd_spec(mp_ctx* ctx, const mp_model* model, const MpCall<float>& c, const float* th0, const float* dth0,
                     const float* taumat, const float* Fm, long B, long Nt, float h, int intRes, float* pos, float* vel, float* acc,
@@ -2013,6 +2035,16 @@ int mp_forward_dynamics_f32(mp_ctx* ctx, const mp_model* model, const float* d_q
                             int64_t rows, const double* g, const double* Ftip, float* d_qdd) {
   return fdyn_impl<float>("mp_forward_dynamics_f32", ctx, model, d_q, d_qd, d_tau, rows, g, Ftip, d_qdd);
 }
+int mp_id_derivatives_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd,
+                          int64_t rows, const double* g, const double* Ftip, double* d_tau, double* d_dtau_dq, double* d_dtau_dqd,
+                          double* d_M) {
+  return deriv_impl("mp_id_derivatives_f64", false, ctx, model, d_q, d_qd, d_qdd, rows, g, Ftip, d_tau, d_dtau_dq, d_dtau_dqd, d_M);
+}
+int mp_fd_derivatives_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_tau,
+                          int64_t rows, const double* g, const double* Ftip, double* d_qdd, double* d_dqdd_dq, double* d_dqdd_dqd,
+                          double* d_Minv) {
+  return deriv_impl("mp_fd_derivatives_f64", true, ctx, model, d_q, d_qd, d_tau, rows, g, Ftip, d_qdd, d_dqdd_dq, d_dqdd_dqd, d_Minv);
+}
 int mp_fd_trajectory_f32(mp_ctx* ctx, const mp_model* model, const float* d_theta0, const float* d_dtheta0,
                          const float* d_taumat, const float* d_Ftipmat, int64_t B, int64_t N, const double* g, double dt,
                          int intRes, float* d_pos, float* d_vel, float* d_acc) {
@@ -2098,6 +2130,49 @@ int mp_forward_dynamics_host_f64(mp_ctx* ctx, const mp_model* model, const doubl
   D2H(qdd, dout, bytes);
   HIP_TRY(hipStreamSynchronize(ctx->compute));
   return MP_OK;
+}
+
+static int deriv_host_impl(const char* fn, bool fd, mp_ctx* ctx, const mp_model* model, const double* q, const double* qd,
+                           const double* x, int64_t rows, const double* g, const double* Ftip, double* y, double* dq, double* dqd,
+                           double* mat) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (rows == 0) return MP_OK;
+  REQUIRE(q && qd && x && dq && dqd, "%s: null host pointer", fn);
+  const size_t vb = (size_t)rows * (size_t)model->d.n * sizeof(double), mb = vb * (size_t)model->d.n;
+  Scratch sc(ctx);
+  void *dq_in, *dqd_in, *dx, *dy = nullptr, *ddq, *ddqd, *dmat = nullptr;
+  if (int rc = sc.get(vb, &dq_in)) return rc;
+  if (int rc = sc.get(vb, &dqd_in)) return rc;
+  if (int rc = sc.get(vb, &dx)) return rc;
+  if (y) if (int rc = sc.get(vb, &dy)) return rc;
+  if (int rc = sc.get(mb, &ddq)) return rc;
+  if (int rc = sc.get(mb, &ddqd)) return rc;
+  if (mat) if (int rc = sc.get(mb, &dmat)) return rc;
+  H2D(dq_in, q, vb);
+  H2D(dqd_in, qd, vb);
+  H2D(dx, x, vb);
+  if (int rc = deriv_impl(fn, fd, ctx, model, (double*)dq_in, (double*)dqd_in, (double*)dx, rows, g, Ftip, (double*)dy, (double*)ddq,
+                          (double*)ddqd, (double*)dmat))
+    return rc;
+  if (y) D2H(y, dy, vb);
+  D2H(dq, ddq, mb);
+  D2H(dqd, ddqd, mb);
+  if (mat) D2H(mat, dmat, mb);
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+int mp_id_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd,
+                               int64_t rows, const double* g, const double* Ftip, double* tau, double* dtau_dq, double* dtau_dqd,
+                               double* M) {
+  return deriv_host_impl("mp_id_derivatives_host_f64", false, ctx, model, q, qd, qdd, rows, g, Ftip, tau, dtau_dq, dtau_dqd, M);
+}
+int mp_fd_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* tau,
+                               int64_t rows, const double* g, const double* Ftip, double* qdd, double* dqdd_dq, double* dqdd_dqd,
+                               double* Minv) {
+  return deriv_host_impl("mp_fd_derivatives_host_f64", true, ctx, model, q, qd, tau, rows, g, Ftip, qdd, dqdd_dq, dqdd_dqd, Minv);
 }
 
 int mp_pd_regulation_host_f64(mp_ctx* ctx, const mp_model* model, const double* theta0, const double* theta_des, const double* Kp,

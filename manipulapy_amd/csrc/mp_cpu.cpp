@@ -18,6 +18,7 @@
 
 #include "../../include/manipula_hip.h"
 #include "mp_core.h"
+#include "mp_deriv.h"
 #include "mp_dyn.h"
 #include "mp_ik.h"
 #include "mp_handles.h"
@@ -407,6 +408,46 @@ int mp_forward_dynamics_cpu_f64(const mp_model* model, const double* q, const do
   return MP_OK;
 }
 
+// analytical derivatives (mp_deriv.h): the kernels' per-row code over host rows
+static int deriv_cpu(const char* fn, bool fd, const mp_model* model, const double* q, const double* qd, const double* x, int64_t rows,
+                     const double* g, const double* Ftip, double* y, double* dq, double* dqd, double* mat, int nthreads) {
+  char msg[192];
+  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
+  if (model->big) {
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (rows < 0) { std::snprintf(msg, sizeof msg, "%s: negative row count", fn); return fail(msg); }
+  if (rows == 0) return MP_OK;
+  if (!q || !qd || !x || !dq || !dqd) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
+  const MpModel<double>& M = model->d;
+  const MpCall<double> C = make_call<double>(model, g, Ftip);
+  const bool ftip = any_nonzero(Ftip);
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(rows, 64, nthreads, [&](int64_t lo, int64_t hi) {
+      for (int64_t r = lo; r < hi; ++r) {
+        if (fd) {
+          if (ftip) mp_fd_deriv_row<N, true>(M, C, q, qd, x, y, dq, dqd, mat, (long)r);
+          else mp_fd_deriv_row<N, false>(M, C, q, qd, x, y, dq, dqd, mat, (long)r);
+        } else {
+          if (ftip) mp_id_deriv_row<N, true>(M, C, q, qd, x, y, dq, dqd, mat, (long)r);
+          else mp_id_deriv_row<N, false>(M, C, q, qd, x, y, dq, dqd, mat, (long)r);
+        }
+      }
+    });
+  })
+  return MP_OK;
+}
+int mp_id_derivatives_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, int64_t rows,
+                              const double* g, const double* Ftip, double* tau, double* dtau_dq, double* dtau_dqd, double* M,
+                              int nthreads) {
+  return deriv_cpu("mp_id_derivatives_cpu_f64", false, model, q, qd, qdd, rows, g, Ftip, tau, dtau_dq, dtau_dqd, M, nthreads);
+}
+int mp_fd_derivatives_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* tau, int64_t rows,
+                              const double* g, const double* Ftip, double* qdd, double* dqdd_dq, double* dqdd_dqd, double* Minv,
+                              int nthreads) {
+  return deriv_cpu("mp_fd_derivatives_cpu_f64", true, model, q, qd, tau, rows, g, Ftip, qdd, dqdd_dq, dqdd_dqd, Minv, nthreads);
+}
 int mp_fd_trajectory_cpu_f32(const mp_model* model, const float* theta0, const float* dtheta0, const float* taumat,
                              const float* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, float* pos,
                              float* vel, float* acc, int nthreads) {

@@ -35,6 +35,11 @@ hipError_t mpk_mass_matrix(hipStream_t s, const MpModel<T>& M, const T* q, T* Mo
 template <typename T>
 hipError_t mpk_forward_dynamics(hipStream_t s, const MpModel<T>& M, const MpCall<T>& C, bool ftip, const T* q, const T* qd,
                                 const T* tau, T* qdd, long rows);
+// analytical derivatives (csrc/mp_deriv.h), float64, 1..MP_MAX_DOF joints; tau / Mout and qdd / Minv may be null
+hipError_t mpk_id_deriv(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
+                        const double* qdd, double* tau, double* dq, double* dqd, double* Mout, long rows);
+hipError_t mpk_fd_deriv(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
+                        const double* tau, double* qdd, double* dq, double* dqd, double* Minv, long rows);
 // Ftipmat == nullptr: no tip wrench.  h = dt / intRes.  Outputs are float32 (B, Nt, n).
 template <typename T>
 hipError_t mpk_fd_traj(hipStream_t s, const MpModel<T>& M, const MpCall<T>& C, const T* theta0, const T* dtheta0,

@@ -11,6 +11,7 @@
 #include <cstdlib>
 
 #include "mp_bodies.h"
+#include "mp_deriv.h"
 #include "mp_dyn.h"
 #include "mp_ik.h"
 #include "mp_kernels.h"
@@ -236,6 +237,29 @@ __global__ __launch_bounds__(kBlock) void k_forward_dynamics(const MpModel<T> M,
   const long r = (long)blockIdx.x * kBlock + threadIdx.x;
   if (r >= rows) return;
   mp_body_fd<T, N, HAS_FTIP>(M, C, q, qd, tau, qdd, r);
+}
+
+// ------------------------------------------------------- derivatives of inverse / forward dynamics (float64, mp_deriv.h)
+// 64-lane blocks: the per-row state (~20 doubles a link kept for the sweeps) takes most of a lane's registers, and a small block
+// lets the scheduler place the few waves a SIMD then holds anywhere
+constexpr int kDerivBlock = 64;
+template <int N, bool HAS_FTIP>
+__global__ __launch_bounds__(kDerivBlock) void k_id_deriv(const MpModel<double> M, const MpCall<double> C, const double* __restrict__ q,
+                                                          const double* __restrict__ qd, const double* __restrict__ qdd,
+                                                          double* __restrict__ tau, double* __restrict__ dq, double* __restrict__ dqd,
+                                                          double* __restrict__ Mout, long rows) {
+  const long r = (long)blockIdx.x * kDerivBlock + threadIdx.x;
+  if (r >= rows) return;
+  mp_id_deriv_row<N, HAS_FTIP>(M, C, q, qd, qdd, tau, dq, dqd, Mout, r);
+}
+template <int N, bool HAS_FTIP>
+__global__ __launch_bounds__(kDerivBlock) void k_fd_deriv(const MpModel<double> M, const MpCall<double> C, const double* __restrict__ q,
+                                                          const double* __restrict__ qd, const double* __restrict__ tau,
+                                                          double* __restrict__ qdd, double* __restrict__ dq, double* __restrict__ dqd,
+                                                          double* __restrict__ Minv, long rows) {
+  const long r = (long)blockIdx.x * kDerivBlock + threadIdx.x;
+  if (r >= rows) return;
+  mp_fd_deriv_row<N, HAS_FTIP>(M, C, q, qd, tau, qdd, dq, dqd, Minv, r);
 }
 
 // one wave per block: the roll-out's LDS tile is per wave and nothing is shared between waves
@@ -649,6 +673,27 @@ template hipError_t mpk_forward_dynamics<float>(hipStream_t, const MpModel<float
                                                 const float*, const float*, float*, long);
 template hipError_t mpk_forward_dynamics<double>(hipStream_t, const MpModel<double>&, const MpCall<double>&, bool,
                                                  const double*, const double*, const double*, double*, long);
+
+hipError_t mpk_id_deriv(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
+                        const double* qdd, double* tau, double* dq, double* dqd, double* Mout, long rows) {
+  if (rows <= 0) return hipSuccess;
+  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(M.n, {
+    if (ftip) hipLaunchKernelGGL((k_id_deriv<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, qdd, tau, dq, dqd, Mout, rows);
+    else hipLaunchKernelGGL((k_id_deriv<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, qdd, tau, dq, dqd, Mout, rows);
+  })
+  return hipGetLastError();
+}
+hipError_t mpk_fd_deriv(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
+                        const double* tau, double* qdd, double* dq, double* dqd, double* Minv, long rows) {
+  if (rows <= 0) return hipSuccess;
+  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(M.n, {
+    if (ftip) hipLaunchKernelGGL((k_fd_deriv<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, qdd, dq, dqd, Minv, rows);
+    else hipLaunchKernelGGL((k_fd_deriv<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, qdd, dq, dqd, Minv, rows);
+  })
+  return hipGetLastError();
+}
 
 template <typename T>
 hipError_t mpk_fd_traj(hipStream_t s, const MpModel<T>& M, const MpCall<T>& C, const T* theta0, const T* dtheta0,

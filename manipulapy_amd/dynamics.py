@@ -191,6 +191,34 @@ class ManipulatorDynamics(SerialManipulator):
         qdd = execute_registered_kernel("dynamics.forward", self._model_for(q.shape[0]), q, qd, tau, g, Ftip)
         return qdd if np.ndim(thetalist) == 2 else qdd[0]
 
+    # ---- analytical derivatives (float64, n <= 8; csrc/mp_deriv.h)
+    def _derivative_model(self, what: str) -> _hip.HipModel:
+        if self._legacy:
+            raise NotImplementedError(f"{what}: needs Mlist_per_link - the legacy approximation has no analytical derivatives")
+        model = self.hip_model()
+        if model.n > _hip.MP_MAX_DOF:
+            raise NotImplementedError(f"{what}: the analytical derivatives cover models of up to {_hip.MP_MAX_DOF} joints "
+                                      f"(this one has {model.n})")
+        return model
+
+    def _derivatives(self, op, what, q, qd, x, g, Ftip):
+        model = self._derivative_model(what)
+        one = np.ndim(q) == 1
+        q2, qd2, x2 = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (q, qd, x))
+        _, dq, dqd, mat = execute_registered_kernel(op, model, q2, qd2, x2, g, Ftip)
+        return (dq[0], dqd[0], mat[0]) if one else (dq, dqd, mat)
+
+    def inverse_dynamics_derivatives(self, thetalist, dthetalist, ddthetalist, g, Ftip):
+        """(dtau_dq, dtau_dqd, dtau_dqdd = M) of tau = inverse_dynamics(...), [.., i, j] = d tau_i / d x_j: (n, n) each for 1-D
+        inputs, (rows, n, n) for 2-D ones (one g / Ftip for all rows).  Derivatives of the unclipped torque."""
+        return self._derivatives("dynamics.inverse_derivatives", "inverse_dynamics_derivatives", thetalist, dthetalist, ddthetalist,
+                                 g, Ftip)
+
+    def forward_dynamics_derivatives(self, thetalist, dthetalist, taulist, g, Ftip):
+        """(dqdd_dq, dqdd_dqd, dqdd_dtau = M^-1) of qdd = forward_dynamics(...), [.., i, j] = d qdd_i / d x_j: (n, n) each for 1-D
+        inputs, (rows, n, n) for 2-D ones (one g / Ftip for all rows)."""
+        return self._derivatives("dynamics.fwd_derivatives", "forward_dynamics_derivatives", thetalist, dthetalist, taulist, g, Ftip)
+
     def partial_derivative(self, i: int, j: int, k: int, thetalist, epsilon: float = 1e-6) -> float:
         """dM[i, j] / dtheta_k by the reference's central difference (dynamics/cache.py:39-52)."""
         q = np.asarray(thetalist, dtype=np.float64)

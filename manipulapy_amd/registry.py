@@ -291,6 +291,14 @@ def _launch_forward_dynamics_cpu(model, q, qd, tau, g=None, Ftip=None):
     return _hip.cpu_forward_dynamics(model, q, qd, tau, g, Ftip)
 
 
+def _launch_id_derivatives_cpu(model, q, qd, qdd, g=None, Ftip=None):
+    return _hip.cpu_id_derivatives(model, q, qd, qdd, g, Ftip)
+
+
+def _launch_fd_derivatives_cpu(model, q, qd, tau, g=None, Ftip=None):
+    return _hip.cpu_fd_derivatives(model, q, qd, tau, g, Ftip)
+
+
 def _launch_fd_trajectory_cpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64, layout="batch_major",
                               device_layout=None):
     del device_layout   # (a device-side choice; the host rows are walked in whatever order they come)
@@ -393,6 +401,14 @@ def _launch_forward_dynamics_gpu(model, q, qd, tau, g=None, Ftip=None):
     return get_context().forward_dynamics_host(model, q, qd, tau, g, Ftip)
 
 
+def _launch_id_derivatives_gpu(model, q, qd, qdd, g=None, Ftip=None):
+    return get_context().id_derivatives_host(model, q, qd, qdd, g, Ftip)
+
+
+def _launch_fd_derivatives_gpu(model, q, qd, tau, g=None, Ftip=None):
+    return get_context().fd_derivatives_host(model, q, qd, tau, g, Ftip)
+
+
 def _launch_fd_trajectory_gpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64, layout="batch_major",
                               device_layout=None):
     return get_context().fd_trajectory_host(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=dtype, layout=layout,
@@ -458,6 +474,10 @@ def _build_kernel_registry() -> KernelRegistry:
         ("dynamics.mass_matrix", "mp_mass_matrix_host_f64", _launch_mass_matrix_gpu, _launch_mass_matrix_cpu),
         ("dynamics.forward", "mp_forward_dynamics_host_f64", _launch_forward_dynamics_gpu, _launch_forward_dynamics_cpu),
         ("dynamics.forward_trajectory", "mp_fd_trajectory_host_f32 / _f64", _launch_fd_trajectory_gpu, _launch_fd_trajectory_cpu),
+        # analytical derivatives (csrc/mp_deriv.h).  The forward one is "dynamics.fwd_derivatives": the registry's sorted name list is
+        # pinned right after "dynamics.forward" by the unknown-name message test, and "dynamics.forward_*" would land there
+        ("dynamics.inverse_derivatives", "mp_id_derivatives_host_f64", _launch_id_derivatives_gpu, _launch_id_derivatives_cpu),
+        ("dynamics.fwd_derivatives", "mp_fd_derivatives_host_f64", _launch_fd_derivatives_gpu, _launch_fd_derivatives_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):
