@@ -272,6 +272,25 @@ int mp_fd_trajectory_tm_f32(mp_ctx* ctx, const mp_model* model, const float* d_t
 int mp_fd_trajectory_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_theta0, const double* d_dtheta0,
                             const double* d_taumat, const double* d_Ftipmat, int64_t B, int64_t N, const double* g,
                             double dt, int intRes, float* d_pos, float* d_vel, float* d_acc);
+/* Gradients of forward_dynamics_trajectory (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED above that; intRes >= 1): the
+ * vector-Jacobian product of the roll-out above, by a reverse pass through its sub-steps (csrc/mp_rollout_vjp.h).  No counterpart in
+ * this ABI's reference interface, whose torch backend differentiates the roll-out with autograd.  Given the cotangents gpos / gvel /
+ * gacc of the three (N, n) row arrays (each may be NULL = zero) it returns dL/dtheta0, dL/ddtheta0 (B,n) and dL/dtaumat (N rows,
+ * row 0 always zero).  The clip's gradient is torch.clamp's (inclusive limits); derivatives are those of the unclipped torque, the
+ * float32 cast of the rows counts as the identity, and g / Ftipmat are constants.  A trajectory whose inputs or forward state turn
+ * non-finite gets NaN in all of its gradients.
+ *   _tm_f64:   device pointers, time-major taumat / Ftipmat / gpos / gvel / gacc / gtaumat (N,B,*); d_work holds
+ *              mp_fd_trajectory_vjp_workspace_bytes(model, B, N, intRes) = (B N + B intRes) 2n doubles.  Asynchronous (no
+ *              synchronisation, no allocation: it may be captured into a launch graph).
+ *   _host_f64: batch-major host arrays (B,N,*); converted on the device, workspace from the context's pool, the batch cut into
+ *              chunks of whole trajectories whose workspace stays under MANIPULAPY_HIP_VJP_WORK_BYTES (default 1 GiB).
+ *   _cpu_f64:  the CPU twin on batch-major host arrays.
+ * mp_fd_trajectory_vjp_workspace_bytes returns the byte count, or minus an MP_ERR_* code. */
+int64_t mp_fd_trajectory_vjp_workspace_bytes(const mp_model* model, int64_t B, int64_t N, int intRes);
+int mp_fd_trajectory_vjp_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_theta0, const double* d_dtheta0,
+                                const double* d_taumat, const double* d_Ftipmat, int64_t B, int64_t N, const double* g, double dt,
+                                int intRes, const double* d_gpos, const double* d_gvel, const double* d_gacc, void* d_work,
+                                double* d_gtheta0, double* d_gdtheta0, double* d_gtaumat);
 /* d_dst (inner, outer, row_bytes) <- d_src (outer, inner, row_bytes): converts between the batch-major API arrays
  * (B,N,n) and the time-major layout (N,B,n), either way.  row_bytes: a multiple of 4, at most 256 (32 float64 joints). */
 int mp_transpose_rows(mp_ctx* ctx, const void* d_src, int64_t outer, int64_t inner, int64_t row_bytes, void* d_dst);
@@ -314,6 +333,10 @@ int mp_fk_jac_id_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, c
                           double* J, double* tau);
 
 int mp_mass_matrix_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, int64_t rows, double* M);
+int mp_fd_trajectory_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* theta0, const double* dtheta0,
+                                  const double* taumat, const double* Ftipmat, int64_t B, int64_t N, const double* g, double dt,
+                                  int intRes, const double* gpos, const double* gvel, const double* gacc, double* gtheta0,
+                                  double* gdtheta0, double* gtaumat);
 int mp_forward_dynamics_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd,
                                  const double* tau, int64_t rows, const double* g, const double* Ftip, double* qdd);
 int mp_id_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd,
@@ -383,6 +406,10 @@ int mp_fd_derivatives_cpu_f64(const mp_model* model, const double* q, const doub
 int mp_fd_trajectory_cpu_f32(const mp_model* model, const float* theta0, const float* dtheta0, const float* taumat,
                              const float* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, float* pos,
                              float* vel, float* acc, int nthreads);
+int mp_fd_trajectory_vjp_cpu_f64(const mp_model* model, const double* theta0, const double* dtheta0, const double* taumat,
+                                 const double* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, const double* gpos,
+                                 const double* gvel, const double* gacc, double* gtheta0, double* gdtheta0, double* gtaumat,
+                                 int nthreads);
 int mp_fd_trajectory_cpu_f64(const mp_model* model, const double* theta0, const double* dtheta0, const double* taumat,
                              const double* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, float* pos,
                              float* vel, float* acc, int nthreads);

@@ -106,6 +106,9 @@ SIGNATURES = {
     "mp_fd_derivatives_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
     "mp_id_derivatives_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "mp_fd_derivatives_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_fd_trajectory_vjp_workspace_bytes": (ctypes.c_int64, [_vp, _i64, _i64, ctypes.c_int]),
+    "mp_fd_trajectory_vjp_tm_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_fd_trajectory_vjp_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "mp_fd_trajectory_host_f32": (ctypes.c_int, [_vp, _vp, _c_fp, _c_fp, _c_fp, _c_fp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp]),
     "mp_fd_trajectory_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp]),
     "mp_cartesian_trajectory_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp]),
@@ -128,6 +131,7 @@ SIGNATURES = {
     "mp_forward_dynamics_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_id_derivatives_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_fd_derivatives_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_fd_trajectory_vjp_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_fd_trajectory_cpu_f32": (ctypes.c_int, [_vp, _c_fp, _c_fp, _c_fp, _c_fp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp, ctypes.c_int]),
     "mp_fd_trajectory_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp, ctypes.c_int]),
     "mp_inverse_kinematics_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, ctypes.c_int64, _c_dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, _c_dp, _vp, _vp, _vp, ctypes.c_int]),
@@ -825,6 +829,53 @@ class HipContext:
                 b.free()
         return tuple(out)
 
+    def fd_trajectory_vjp(self, model, d_theta0, d_dtheta0, d_taumat, d_Ftipmat, B, N, g, dt, intRes, d_gpos, d_gvel, d_gacc, d_work,
+                          d_gtheta0, d_gdtheta0, d_gtaumat):
+        """Gradients of the roll-out on device buffers (float64, csrc/mp_rollout_vjp.h), time-major taumat / Ftipmat / cotangents /
+        d_gtaumat (N, B, *); d_Ftipmat and the cotangents may be None; d_work holds fd_trajectory_vjp_workspace_bytes(...).
+        Asynchronous (capturable)."""
+        _check(self.lib.mp_fd_trajectory_vjp_tm_f64(self.handle, model.handle, _p(d_theta0), _p(d_dtheta0), _p(d_taumat), _p(d_Ftipmat),
+                                                    int(B), int(N), _dptr(_vec_or_none(g, 3, "g")), float(dt), int(intRes), _p(d_gpos),
+                                                    _p(d_gvel), _p(d_gacc), _p(d_work), _p(d_gtheta0), _p(d_gdtheta0), _p(d_gtaumat)))
+
+    def fd_trajectory_vjp_host(self, model: HipModel, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos=None, gvel=None, gacc=None,
+                               layout: str = "batch_major"):
+        """(dL/dtheta0 (B,n), dL/ddtheta0 (B,n), dL/dtaumat) of host arrays, float64.  layout="batch_major": taumat / Ftipmat /
+        cotangents / dL/dtaumat are (B,N,*) and go through mp_fd_trajectory_vjp_host_f64 (converted on the device, chunked);
+        "time_major": they are (N,B,*) and go straight to the device form."""
+        th, dth, tm, Fm, G = _vjp_arrays(model, theta0, dtheta0, taumat, Ftipmat, gpos, gvel, gacc, layout)
+        gv3 = _vec_or_none(g, 3, "g")
+        B, n = th.shape
+        N = tm.shape[1] if layout == "batch_major" else tm.shape[0]
+        gth, gdth, gtau = np.zeros((B, n)), np.zeros((B, n)), np.zeros(tm.shape)
+        if layout == "batch_major":
+            _check(self.lib.mp_fd_trajectory_vjp_host_f64(self.handle, model.handle, _dptr(th), _dptr(dth), _dptr(tm), _dptr(Fm), B, N,
+                                                          _dptr(gv3), float(dt), int(intRes), *[_dptr(x) for x in G], _dptr(gth),
+                                                          _dptr(gdth), _dptr(gtau)))
+            return gth, gdth, gtau
+        work = fd_trajectory_vjp_workspace_bytes(model, B, N, intRes)
+        if B == 0 or N == 0:
+            return gth, gdth, gtau
+        bufs = []
+        try:
+            def up(a):
+                bufs.append(self.to_device(a) if a is not None else None)
+                return bufs[-1]
+
+            d_in = [up(a) for a in (th, dth, tm, Fm)] + [up(x) for x in G]
+            d_out = [self.alloc(a.nbytes) for a in (gth, gdth, gtau)]
+            bufs.extend(d_out)
+            bufs.append(self.alloc(work))
+            self.fd_trajectory_vjp(model, d_in[0], d_in[1], d_in[2], d_in[3], B, N, gv3, dt, intRes, d_in[4], d_in[5], d_in[6], bufs[-1],
+                                   *d_out)
+            for a, d in zip((gth, gdth, gtau), d_out):
+                _check(self.lib.mp_memcpy_d2h(self.handle, a.ctypes.data, _p(d), a.nbytes))
+        finally:
+            for b in bufs:
+                if b is not None:
+                    b.free()
+        return gth, gdth, gtau
+
     def fd_trajectory(self, model, d_theta0, d_dtheta0, d_taumat, d_Ftipmat, B, N, g, dt, intRes, d_pos, d_vel, d_acc,
                       dtype=np.float32, time_major: bool = False):
         """Device pointers.  time_major=False: taumat (B,N,n), Ftipmat (B,N,6), outputs (B,N,n); True: (N,B,*) throughout."""
@@ -1011,6 +1062,41 @@ def cpu_fd_trajectory(model: "HipModel", theta0, dtheta0, taumat, g, Ftipmat, dt
     _check(fn(model.handle, _ptr(th, dtype), _ptr(dth, dtype), _ptr(tm, dtype), _ptr(Fm, dtype), B, N, _dptr(_vec_or_none(g, 3, "g")),
               float(dt), int(intRes), _fptr(out[0]), _fptr(out[1]), _fptr(out[2]), int(nthreads)))
     return out[0], out[1], out[2]
+
+
+def _vjp_arrays(model, theta0, dtheta0, taumat, Ftipmat, gpos, gvel, gacc, layout="batch_major"):
+    """float64 C-contiguous arrays of one roll-out VJP call; taumat (B,N,n) or, time-major, (N,B,n)."""
+    if layout not in ("batch_major", "time_major"):
+        raise ValueError("layout must be 'batch_major' or 'time_major'")
+    tm = _as_c(taumat, np.float64, name="taumat")
+    if tm.ndim != 3 or tm.shape[2] != model.n:
+        raise ValueError(f"taumat must be {'(B, N, %d)' % model.n if layout == 'batch_major' else '(N, B, %d)' % model.n}; got {tm.shape}")
+    B = tm.shape[0] if layout == "batch_major" else tm.shape[1]
+    th, dth = _as_c(theta0, np.float64, (B, model.n), "theta0"), _as_c(dtheta0, np.float64, (B, model.n), "dtheta0")
+    Fm = None if Ftipmat is None else _as_c(Ftipmat, np.float64, tm.shape[:2] + (6,), "Ftipmat")
+    G = [None if x is None else _as_c(x, np.float64, tm.shape, name) for x, name in ((gpos, "grad_positions"), (gvel, "grad_velocities"),
+                                                                                     (gacc, "grad_accelerations"))]
+    return th, dth, tm, Fm, G
+
+
+def fd_trajectory_vjp_workspace_bytes(model: "HipModel", B: int, N: int, intRes: int) -> int:
+    """Device workspace of mp_fd_trajectory_vjp_tm_f64: (B N + B intRes) 2n doubles."""
+    v = int(load_library().mp_fd_trajectory_vjp_workspace_bytes(model.handle, int(B), int(N), int(intRes)))
+    if v < 0:
+        _check(-v)
+    return v
+
+
+def cpu_fd_trajectory_vjp(model: "HipModel", theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos=None, gvel=None, gacc=None,
+                          nthreads: int = 0):
+    """CPU twin of HipContext.fd_trajectory_vjp_host on batch-major arrays: (dL/dtheta0, dL/ddtheta0, dL/dtaumat), float64."""
+    th, dth, tm, Fm, G = _vjp_arrays(model, theta0, dtheta0, taumat, Ftipmat, gpos, gvel, gacc)
+    B, N, n = tm.shape
+    gth, gdth, gtau = np.zeros((B, n)), np.zeros((B, n)), np.zeros(tm.shape)
+    _check(load_library().mp_fd_trajectory_vjp_cpu_f64(model.handle, _dptr(th), _dptr(dth), _dptr(tm), _dptr(Fm), B, N,
+                                                       _dptr(_vec_or_none(g, 3, "g")), float(dt), int(intRes), *[_dptr(x) for x in G],
+                                                       _dptr(gth), _dptr(gdth), _dptr(gtau), int(nthreads)))
+    return gth, gdth, gtau
 
 
 def cpu_cartesian_trajectory(Xstart, Xend, Tf, N, method, nthreads: int = 0):

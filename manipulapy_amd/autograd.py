@@ -3,10 +3,12 @@
     from manipulapy_amd import autograd as mpa
     tau = mpa.inverse_dynamics(dyn, q, qd, qdd, g, Ftip)          # q, qd, qdd: CPU float64 tensors, (n,) or (rows, n)
     J = torch.autograd.functional.jacobian(lambda q: mpa.inverse_dynamics(dyn, q, qd, qdd, g, Ftip), q)
+    pos, vel, acc = mpa.forward_dynamics_trajectory(planner, theta0, dtheta0, taumat, g, Ftipmat, dt=0.01, intRes=1)
 
 The forward value is the registered inverse / forward dynamics operation, the backward pass the vector-Jacobian product with the
 registered derivative operation ("dynamics.inverse_derivatives" / "dynamics.fwd_derivatives"): the GPU under the "hip" backend,
-the CPU twin otherwise.  Once differentiable (no second derivatives).  g and Ftip are constants: a tensor among them that
+the CPU twin otherwise.  forward_dynamics_trajectory is a planner's roll-out ("dynamics.forward_trajectory") whose backward pass is
+the reverse pass through its sub-steps ("dynamics.forward_trajectory_vjp", csrc/mp_rollout_vjp.h).  Once differentiable (no second derivatives).  g and Ftip are constants: a tensor among them that
 requires grad is refused.  Imported on demand only - never from the package's __init__ (torch stays optional).
 """
 from __future__ import annotations
@@ -16,7 +18,7 @@ import torch
 
 from .registry import execute_registered_kernel
 
-__all__ = ["inverse_dynamics", "forward_dynamics"]
+__all__ = ["inverse_dynamics", "forward_dynamics", "forward_dynamics_trajectory"]
 
 
 def _const(v, name):
@@ -95,3 +97,36 @@ def inverse_dynamics(dyn, q, qd, qdd, g=None, Ftip=None) -> torch.Tensor:
 def forward_dynamics(dyn, q, qd, tau, g=None, Ftip=None) -> torch.Tensor:
     """qdd = FD(q, qd, tau, g, Ftip), differentiable in q, qd, tau; shapes as inverse_dynamics."""
     return _ForwardDynamics.apply(dyn, _as_tensor(q), _as_tensor(qd), _as_tensor(tau), _const(g, "g"), _const(Ftip, "Ftip"))
+
+
+class _ForwardDynamicsTrajectory(torch.autograd.Function):
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gpos, gvel, gacc):
+        planner, th, dth, tm, g, F, dt, intRes = ctx.args
+        cot = [None if x is None else x.detach().cpu().numpy().astype(np.float64).reshape(tm.shape) for x in (gpos, gvel, gacc)]
+        r = planner.batch_forward_dynamics_trajectory_vjp(th, dth, tm, g, F, dt, intRes, *cot)
+        out = [torch.from_numpy(np.ascontiguousarray(r[k], dtype=np.float64)) for k in ("theta0", "dtheta0", "taumat")]
+        if ctx.one:
+            out = [o[0] for o in out]
+        return (None, *out, None, None, None, None)
+
+    @staticmethod
+    def forward(ctx, planner, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes):
+        one = taumat.dim() == 2
+        tm = _rows(taumat, "taumat")
+        tm = tm[None] if one else tm
+        th, dth = (_rows(a, n).reshape(tm.shape[0], tm.shape[2]) for a, n in ((theta0, "theta0"), (dtheta0, "dtheta0")))
+        F = None if Ftipmat is None else Ftipmat.reshape(tm.shape[:2] + (6,))
+        r = planner.batch_forward_dynamics_trajectory(th, dth, tm, g, F, dt, intRes)
+        ctx.args, ctx.one = (planner, th, dth, tm, g, F, dt, intRes), one
+        out = [torch.as_tensor(np.asarray(r[k], dtype=np.float32)) for k in ("positions", "velocities", "accelerations")]
+        return tuple(o[0] for o in out) if one else tuple(out)
+
+
+def forward_dynamics_trajectory(planner, theta0, dtheta0, taumat, g=None, Ftipmat=None, dt: float = 0.01, intRes: int = 1):
+    """(positions, velocities, accelerations) float32 rows of an OptimizedTrajectoryPlanning's forward-dynamics roll-out, differentiable
+    in theta0, dtheta0 and taumat (CPU float64 tensors).  taumat (N, n) with theta0 / dtheta0 (n,), or (B, N, n) with (B, n);
+    Ftipmat (N, 6) / (B, N, 6) or None.  The float32 cast of the rows counts as the identity; g and Ftipmat are constants."""
+    return _ForwardDynamicsTrajectory.apply(planner, _as_tensor(theta0), _as_tensor(dtheta0), _as_tensor(taumat), _const(g, "g"),
+                                            _const(Ftipmat, "Ftipmat"), float(dt), int(intRes))

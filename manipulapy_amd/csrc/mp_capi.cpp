@@ -907,6 +907,94 @@ static int deriv_impl(const char* fn, bool fd, mp_ctx* ctx, const mp_model* mode
   return MP_OK;
 }
 
+// reverse mode through the roll-out (mp_rollout_vjp.h): float64, unrolled models only
+int64_t vjp_work_doubles(int n, int64_t B, int64_t N, int intRes) { return (B * N + B * (int64_t)intRes) * 2 * (int64_t)n; }
+static int fdtraj_vjp_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* d_theta0, const double* d_dtheta0,
+                           const double* d_taumat, const double* d_Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes,
+                           const double* d_gpos, const double* d_gvel, const double* d_gacc, void* d_work, double* d_gtheta0,
+                           double* d_gdtheta0, double* d_gtaumat) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(B >= 0 && N >= 0, "%s: negative B (%lld) or N (%lld)", fn, (long long)B, (long long)N);
+  REQUIRE(intRes >= 1, "%s: intRes must be >= 1 (got %d)", fn, intRes);
+  if (B == 0 || N == 0) return MP_OK;
+  REQUIRE(d_theta0 && d_dtheta0 && d_taumat && d_work && d_gtheta0 && d_gdtheta0 && d_gtaumat, "%s: null device pointer", fn);
+  REQUIRE(aligned16(d_theta0) && aligned16(d_dtheta0) && aligned16(d_taumat) && aligned16(d_Ftipmat) && aligned16(d_gpos) &&
+              aligned16(d_gvel) && aligned16(d_gacc) && aligned16(d_work) && aligned16(d_gtheta0) && aligned16(d_gdtheta0) &&
+              aligned16(d_gtaumat),
+          "%s: device pointers must be 16-byte aligned", fn);
+  MpCall<double> c;
+  make_call<double>(model, g, nullptr, &c);
+  PROFILE_SCOPE(ctx, fn);
+  HIP_TRY(mpk_fd_traj_vjp(ctx->compute, model->d, c, d_theta0, d_dtheta0, d_taumat, d_Ftipmat, (long)B, (long)N, dt / intRes, intRes,
+                          d_gpos, d_gvel, d_gacc, (double*)d_work, d_gtheta0, d_gdtheta0, d_gtaumat));
+  return MP_OK;
+}
+// The host form's workspace cap (MANIPULAPY_HIP_VJP_WORK_BYTES, read at every call; default 1 GiB): the batch is cut into chunks of
+// whole trajectories whose workspace stays under it
+int64_t vjp_work_cap() {
+  const char* e = getenv("MANIPULAPY_HIP_VJP_WORK_BYTES");
+  const long long v = e ? atoll(e) : 0;
+  return v > 0 ? (int64_t)v : (int64_t)1 << 30;
+}
+// batch-major host arrays: per chunk, upload -> (B, N, *) to (N, B, *) on the device -> the time-major VJP -> back -> download
+static int fdtraj_vjp_host_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* theta0, const double* dtheta0,
+                                const double* taumat, const double* Ftipmat, int64_t B, int64_t N, const double* g, double dt,
+                                int intRes, const double* gpos, const double* gvel, const double* gacc, double* gtheta0,
+                                double* gdtheta0, double* gtaumat) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(B >= 0 && N >= 0, "%s: negative B (%lld) or N (%lld)", fn, (long long)B, (long long)N);
+  REQUIRE(intRes >= 1, "%s: intRes must be >= 1 (got %d)", fn, intRes);
+  if (B == 0 || N == 0) return MP_OK;
+  REQUIRE(theta0 && dtheta0 && taumat && gtheta0 && gdtheta0 && gtaumat, "%s: null host pointer", fn);
+  const int n = model->d.n;
+  const int64_t per = vjp_work_doubles(n, 1, N, intRes) * (int64_t)sizeof(double);  // workspace bytes of one trajectory
+  int64_t cb = std::max<int64_t>(1, vjp_work_cap() / per);
+  if (cb >= 64) cb &= ~(int64_t)63;
+  cb = std::min(cb, B);
+  const size_t sr = (size_t)n * sizeof(double), tr = (size_t)N * sr, fr = (size_t)N * 6 * sizeof(double);
+  Scratch sc(ctx);
+  void *d0, *d1, *dtau, *dF = nullptr, *dgp = nullptr, *dgv = nullptr, *dga = nullptr, *dwork, *dg0, *dg1, *dgt, *stage;
+  if (int rc = sc.get(cb * sr, &d0)) return rc;
+  if (int rc = sc.get(cb * sr, &d1)) return rc;
+  if (int rc = sc.get(cb * tr, &dtau)) return rc;
+  if (Ftipmat) if (int rc = sc.get(cb * fr, &dF)) return rc;
+  if (gpos) if (int rc = sc.get(cb * tr, &dgp)) return rc;
+  if (gvel) if (int rc = sc.get(cb * tr, &dgv)) return rc;
+  if (gacc) if (int rc = sc.get(cb * tr, &dga)) return rc;
+  if (int rc = sc.get((size_t)vjp_work_doubles(n, cb, N, intRes) * sizeof(double), &dwork)) return rc;
+  if (int rc = sc.get(cb * sr, &dg0)) return rc;
+  if (int rc = sc.get(cb * sr, &dg1)) return rc;
+  if (int rc = sc.get(cb * tr, &dgt)) return rc;
+  if (int rc = sc.get(cb * std::max(tr, fr), &stage)) return rc;  // batch-major staging, reused in stream order
+  for (int64_t b0 = 0; b0 < B; b0 += cb) {
+    const int64_t nb = std::min(cb, B - b0);
+    auto up_tm = [&](const double* src, size_t row, void* dst) -> int {  // (nb, N, row) host -> (N, nb, row) device
+      H2D(stage, (const char*)src + b0 * row * N, nb * row * N);
+      return mp_transpose_rows(ctx, stage, nb, N, (int64_t)row, dst);
+    };
+    H2D(d0, (const char*)theta0 + b0 * sr, nb * sr);
+    H2D(d1, (const char*)dtheta0 + b0 * sr, nb * sr);
+    if (int rc = up_tm(taumat, sr, dtau)) return rc;
+    if (Ftipmat) if (int rc = up_tm(Ftipmat, 6 * sizeof(double), dF)) return rc;
+    if (gpos) if (int rc = up_tm(gpos, sr, dgp)) return rc;
+    if (gvel) if (int rc = up_tm(gvel, sr, dgv)) return rc;
+    if (gacc) if (int rc = up_tm(gacc, sr, dga)) return rc;
+    if (int rc = fdtraj_vjp_impl(fn, ctx, model, (double*)d0, (double*)d1, (double*)dtau, (double*)dF, nb, N, g, dt, intRes, (double*)dgp,
+                                 (double*)dgv, (double*)dga, dwork, (double*)dg0, (double*)dg1, (double*)dgt))
+      return rc;
+    if (int rc = mp_transpose_rows(ctx, dgt, N, nb, (int64_t)sr, stage)) return rc;
+    D2H((char*)gtheta0 + b0 * sr, dg0, nb * sr);
+    D2H((char*)gdtheta0 + b0 * sr, dg1, nb * sr);
+    D2H((char*)gtaumat + b0 * tr, stage, nb * tr);
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+
 // specialised forward-dynamics roll-out (float32 only): -1 = none available, otherwise the launch's return code
 int launch_fd_spec(mp_ctx* ctx, const mp_model* model, const MpCall<float>& c, const float* th0, const float* dth0,
                     const float* taumat, const float* Fm, long B, long Nt, float h, int intRes, float* pos, float* vel, float* acc,
@@ -2044,6 +2132,26 @@ int mp_fd_derivatives_f64(mp_ctx* ctx, const mp_model* model, const double* d_q,
                           int64_t rows, const double* g, const double* Ftip, double* d_qdd, double* d_dqdd_dq, double* d_dqdd_dqd,
                           double* d_Minv) {
   return deriv_impl("mp_fd_derivatives_f64", true, ctx, model, d_q, d_qd, d_tau, rows, g, Ftip, d_qdd, d_dqdd_dq, d_dqdd_dqd, d_Minv);
+}
+int64_t mp_fd_trajectory_vjp_workspace_bytes(const mp_model* model, int64_t B, int64_t N, int intRes) {
+  if (!model) return -set_err(MP_ERR_INVALID, "mp_fd_trajectory_vjp_workspace_bytes: null model");
+  if (B < 0 || N < 0 || intRes < 1)
+    return -set_err(MP_ERR_INVALID, "mp_fd_trajectory_vjp_workspace_bytes: negative B or N, or intRes < 1");
+  return vjp_work_doubles(model->d.n, B, N, intRes) * (int64_t)sizeof(double);
+}
+int mp_fd_trajectory_vjp_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_theta0, const double* d_dtheta0,
+                                const double* d_taumat, const double* d_Ftipmat, int64_t B, int64_t N, const double* g, double dt,
+                                int intRes, const double* d_gpos, const double* d_gvel, const double* d_gacc, void* d_work,
+                                double* d_gtheta0, double* d_gdtheta0, double* d_gtaumat) {
+  return fdtraj_vjp_impl("mp_fd_trajectory_vjp_tm_f64", ctx, model, d_theta0, d_dtheta0, d_taumat, d_Ftipmat, B, N, g, dt, intRes, d_gpos,
+                         d_gvel, d_gacc, d_work, d_gtheta0, d_gdtheta0, d_gtaumat);
+}
+int mp_fd_trajectory_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* theta0, const double* dtheta0,
+                                  const double* taumat, const double* Ftipmat, int64_t B, int64_t N, const double* g, double dt,
+                                  int intRes, const double* gpos, const double* gvel, const double* gacc, double* gtheta0,
+                                  double* gdtheta0, double* gtaumat) {
+  return fdtraj_vjp_host_impl("mp_fd_trajectory_vjp_host_f64", ctx, model, theta0, dtheta0, taumat, Ftipmat, B, N, g, dt, intRes, gpos,
+                              gvel, gacc, gtheta0, gdtheta0, gtaumat);
 }
 int mp_fd_trajectory_f32(mp_ctx* ctx, const mp_model* model, const float* d_theta0, const float* d_dtheta0,
                          const float* d_taumat, const float* d_Ftipmat, int64_t B, int64_t N, const double* g, double dt,

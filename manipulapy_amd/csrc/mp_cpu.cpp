@@ -23,6 +23,7 @@
 #include "mp_ik.h"
 #include "mp_handles.h"
 #include "mp_model_compile.h"
+#include "mp_rollout_vjp.h"
 
 namespace {
 const double kG[3] = {0.0, 0.0, -9.81};
@@ -447,6 +448,46 @@ int mp_fd_derivatives_cpu_f64(const mp_model* model, const double* q, const doub
                               const double* g, const double* Ftip, double* qdd, double* dqdd_dq, double* dqdd_dqd, double* Minv,
                               int nthreads) {
   return deriv_cpu("mp_fd_derivatives_cpu_f64", true, model, q, qd, tau, rows, g, Ftip, qdd, dqdd_dq, dqdd_dqd, Minv, nthreads);
+}
+// reverse mode through the roll-out (mp_rollout_vjp.h): the kernel's per-trajectory code over batch-major host arrays, each thread
+// with its own workspace of (N + intRes) 2n doubles
+int mp_fd_trajectory_vjp_cpu_f64(const mp_model* model, const double* theta0, const double* dtheta0, const double* taumat,
+                                 const double* Ftipmat, int64_t B, int64_t Nt, const double* g, double dt, int intRes, const double* gpos,
+                                 const double* gvel, const double* gacc, double* gtheta0, double* gdtheta0, double* gtaumat,
+                                 int nthreads) {
+  const char* fn = "mp_fd_trajectory_vjp_cpu_f64";
+  char msg[192];
+  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
+  if (model->big) {
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (B < 0 || Nt < 0) { std::snprintf(msg, sizeof msg, "%s: negative B or N", fn); return fail(msg); }
+  if (intRes < 1) { std::snprintf(msg, sizeof msg, "%s: intRes must be >= 1 (got %d)", fn, intRes); return fail(msg); }
+  if (B == 0 || Nt == 0) return MP_OK;
+  if (!theta0 || !dtheta0 || !taumat || !gtheta0 || !gdtheta0 || !gtaumat) {
+    std::snprintf(msg, sizeof msg, "%s: null pointer", fn);
+    return fail(msg);
+  }
+  const MpModel<double>& M = model->d;
+  const MpCall<double> C = make_call<double>(model, g, nullptr);
+  const double h = dt / intRes;
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(B, 1, nthreads, [&](int64_t lo, int64_t hi) {
+      std::vector<double> work((size_t)(Nt + intRes) * 2 * N);
+      double *ck = work.data(), *sub = ck + (size_t)Nt * 2 * N;
+      for (int64_t b = lo; b < hi; ++b) {
+        const int64_t o = b * Nt * N, s = b * N;  // (B, N, n) row 0 / (B, n) row of trajectory b
+        const double* F = Ftipmat ? Ftipmat + b * Nt * 6 : nullptr;
+        const double *gp = gpos ? gpos + o : nullptr, *gv = gvel ? gvel + o : nullptr, *ga = gacc ? gacc + o : nullptr;
+        if (F) mp_fd_traj_vjp<N, true>(M, C, theta0 + s, dtheta0 + s, taumat + o, F, 1, (long)Nt, h, intRes, gp, gv, ga, ck, 1, sub, 1,
+                                       gtheta0 + s, gdtheta0 + s, gtaumat + o);
+        else mp_fd_traj_vjp<N, false>(M, C, theta0 + s, dtheta0 + s, taumat + o, nullptr, 1, (long)Nt, h, intRes, gp, gv, ga, ck, 1, sub, 1,
+                                      gtheta0 + s, gdtheta0 + s, gtaumat + o);
+      }
+    });
+  })
+  return MP_OK;
 }
 int mp_fd_trajectory_cpu_f32(const mp_model* model, const float* theta0, const float* dtheta0, const float* taumat,
                              const float* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, float* pos,

@@ -40,6 +40,11 @@ hipError_t mpk_id_deriv(hipStream_t s, const MpModel<double>& M, const MpCall<do
                         const double* qdd, double* tau, double* dq, double* dqd, double* Mout, long rows);
 hipError_t mpk_fd_deriv(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
                         const double* tau, double* qdd, double* dq, double* dqd, double* Minv, long rows);
+// reverse mode through the roll-out (csrc/mp_rollout_vjp.h) on the time-major layout: taumat / Ftipmat / gp / gv / ga / gtau (Nt, B, *),
+// theta0 / dtheta0 / gth0 / gdth0 (B, n); Ftipmat and the cotangents may be null; `work` holds (B Nt + B intRes) 2n doubles
+hipError_t mpk_fd_traj_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, const double* theta0, const double* dtheta0,
+                           const double* taumat, const double* Ftipmat, long B, long Nt, double h, int intRes, const double* gp,
+                           const double* gv, const double* ga, double* work, double* gth0, double* gdth0, double* gtau);
 // Ftipmat == nullptr: no tip wrench.  h = dt / intRes.  Outputs are float32 (B, Nt, n).
 template <typename T>
 hipError_t mpk_fd_traj(hipStream_t s, const MpModel<T>& M, const MpCall<T>& C, const T* theta0, const T* dtheta0,

@@ -15,6 +15,7 @@
 #include "mp_dyn.h"
 #include "mp_ik.h"
 #include "mp_kernels.h"
+#include "mp_rollout_vjp.h"
 
 namespace {
 
@@ -260,6 +261,24 @@ __global__ __launch_bounds__(kDerivBlock) void k_fd_deriv(const MpModel<double> 
   const long r = (long)blockIdx.x * kDerivBlock + threadIdx.x;
   if (r >= rows) return;
   mp_fd_deriv_row<N, HAS_FTIP>(M, C, q, qd, tau, qdd, dq, dqd, Minv, r);
+}
+
+// reverse mode through the roll-out (mp_rollout_vjp.h): one lane = one trajectory on the time-major layout, so that the 64 lanes of a
+// wave read and write neighbouring rows at every step; the workspace is time-major too (row i of trajectory b at (i B + b) 2n)
+template <int N, bool HAS_FTIP>
+__global__ __launch_bounds__(kDerivBlock) void k_fd_traj_vjp(const MpModel<double> M, const MpCall<double> C, const double* __restrict__ th0,
+                                                             const double* __restrict__ dth0, const double* __restrict__ taumat,
+                                                             const double* __restrict__ Fm, long B, long Nt, double h, int intRes,
+                                                             const double* __restrict__ gp, const double* __restrict__ gv,
+                                                             const double* __restrict__ ga, double* __restrict__ work,
+                                                             double* __restrict__ gth0, double* __restrict__ gdth0, double* __restrict__ gtau) {
+  const long b = (long)blockIdx.x * kDerivBlock + threadIdx.x;
+  if (b >= B) return;
+  const long o = b * N;
+  double* ck = work + b * (2 * N);
+  double* sub = work + B * Nt * (2 * N) + b * (2 * N);
+  mp_fd_traj_vjp<N, HAS_FTIP>(M, C, th0 + o, dth0 + o, taumat + o, HAS_FTIP ? Fm + b * 6 : nullptr, B, Nt, h, intRes, gp ? gp + o : nullptr,
+                              gv ? gv + o : nullptr, ga ? ga + o : nullptr, ck, B, sub, B, gth0 + o, gdth0 + o, gtau + o);
 }
 
 // one wave per block: the roll-out's LDS tile is per wave and nothing is shared between waves
@@ -691,6 +710,20 @@ hipError_t mpk_fd_deriv(hipStream_t s, const MpModel<double>& M, const MpCall<do
   MP_DISPATCH_N(M.n, {
     if (ftip) hipLaunchKernelGGL((k_fd_deriv<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, qdd, dq, dqd, Minv, rows);
     else hipLaunchKernelGGL((k_fd_deriv<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, qdd, dq, dqd, Minv, rows);
+  })
+  return hipGetLastError();
+}
+
+hipError_t mpk_fd_traj_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, const double* theta0, const double* dtheta0,
+                           const double* taumat, const double* Ftipmat, long B, long Nt, double h, int intRes, const double* gp,
+                           const double* gv, const double* ga, double* work, double* gth0, double* gdth0, double* gtau) {
+  if (B <= 0 || Nt <= 0) return hipSuccess;
+  const unsigned gb = (unsigned)((B + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(M.n, {
+    if (Ftipmat) hipLaunchKernelGGL((k_fd_traj_vjp<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt,
+                                    h, intRes, gp, gv, ga, work, gth0, gdth0, gtau);
+    else hipLaunchKernelGGL((k_fd_traj_vjp<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt,
+                            h, intRes, gp, gv, ga, work, gth0, gdth0, gtau);
   })
   return hipGetLastError();
 }

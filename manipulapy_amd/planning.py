@@ -313,6 +313,58 @@ class OptimizedTrajectoryPlanning:
         b = get_backend()
         return {"positions": b.asarray(pos), "velocities": b.asarray(vel), "accelerations": b.asarray(acc)}
 
+    def _vjp_model(self, what: str):
+        """The compiled model for the roll-out gradients: refused, in the analytical derivatives' words, for legacy dynamics objects and
+        for models of more than MP_MAX_DOF joints."""
+        if getattr(self.dynamics, "_legacy", False):
+            raise NotImplementedError(f"{what}: needs Mlist_per_link - the legacy approximation has no analytical derivatives")
+        model = self._hip_model()
+        if model.n > _hip.MP_MAX_DOF:
+            raise NotImplementedError(f"{what}: the analytical derivatives cover models of up to {_hip.MP_MAX_DOF} joints "
+                                      f"(this one has {model.n})")
+        return model
+
+    def batch_forward_dynamics_trajectory_vjp(self, theta0_batch, dtheta0_batch, taumat_batch, g, Ftipmat_batch, dt, intRes,
+                                              grad_positions=None, grad_velocities=None, grad_accelerations=None,
+                                              layout: str = "batch_major") -> Dict[str, np.ndarray]:
+        """Gradients of batch_forward_dynamics_trajectory: given the cotangents of its positions / velocities / accelerations (each
+        shaped like them, None = zero), returns {"theta0": (B, n), "dtheta0": (B, n), "taumat": shaped like taumat_batch} =
+        dL/d(input) of L = sum(G * rows), float64.  One reverse pass through the sub-steps (csrc/mp_rollout_vjp.h) instead of a roll-out
+        per perturbed input.  The state is float64 (float32 inputs are refused); the clip's gradient is torch.clamp's; the rows' float32
+        cast counts as the identity; g and Ftipmat are constants.  New (the reference differentiates its torch roll-out with autograd).
+        layout="time_major": taumat / Ftipmat / the cotangents / the taumat gradient are (N, B, *)."""
+        what = "batch_forward_dynamics_trajectory_vjp"
+        if layout not in ("batch_major", "time_major"):
+            raise ValueError("layout must be 'batch_major' or 'time_major'")
+        for name, a in (("theta0_batch", theta0_batch), ("dtheta0_batch", dtheta0_batch), ("taumat_batch", taumat_batch)):
+            if np.asarray(a).dtype == np.float32:
+                raise TypeError(f"{what}: {name} is float32 - the roll-out gradients are computed on float64 state only")
+        th = np.asarray(theta0_batch, dtype=np.float64)
+        if th.ndim != 2:
+            raise ValueError(f"initial states must be (B, n); got {th.shape}")
+        if int(intRes) == 0:
+            raise ZeroDivisionError("float division by zero")  # dt_step = dt / intRes, as the forward roll-out
+        if int(intRes) < 0:
+            raise ValueError("intRes must be positive")
+        model = self._vjp_model(what)
+        if g is None:
+            g = np.array([0.0, 0.0, -9.81])
+        gth, gdth, gtau = self._dispatch("dynamics.forward_trajectory_vjp", model, th, dtheta0_batch, taumat_batch, g, Ftipmat_batch, dt,
+                                         int(intRes), grad_positions, grad_velocities, grad_accelerations, layout=layout)
+        return {"theta0": gth, "dtheta0": gdth, "taumat": gtau}
+
+    def forward_dynamics_trajectory_vjp(self, thetalist, dthetalist, taumat, g, Ftipmat, dt, intRes, grad_positions=None,
+                                        grad_velocities=None, grad_accelerations=None) -> Dict[str, np.ndarray]:
+        """Gradients of forward_dynamics_trajectory for ONE trajectory: cotangents (N, n) (None = zero) -> {"theta0": (n,),
+        "dtheta0": (n,), "taumat": (N, n)}, float64; see batch_forward_dynamics_trajectory_vjp."""
+        tm = np.asarray(taumat)
+        if tm.ndim != 2:
+            raise ValueError(f"taumat must be (N, n); got {tm.shape}")
+        one = lambda a: None if a is None else np.asarray(a)[None]  # noqa: E731
+        r = self.batch_forward_dynamics_trajectory_vjp(one(thetalist), one(dthetalist), tm[None], g, one(Ftipmat), dt, intRes,
+                                                       one(grad_positions), one(grad_velocities), one(grad_accelerations))
+        return {k: v[0] for k, v in r.items()}
+
     # ------------------------------------------------------------------ legacy dynamics objects (Mlist_per_link=None)
     # The reference's approximation for such objects is not rigid-body dynamics (dynamics/mass_matrix.py:101-132), so there
     # is no compiled model and no kernel for it: the planner walks the rows on the host exactly as the reference's CPU

@@ -299,6 +299,16 @@ def _launch_fd_derivatives_cpu(model, q, qd, tau, g=None, Ftip=None):
     return _hip.cpu_fd_derivatives(model, q, qd, tau, g, Ftip)
 
 
+def _launch_fd_trajectory_vjp_cpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos=None, gvel=None, gacc=None,
+                                  layout="batch_major"):
+    if layout == "time_major":   # the CPU twin walks batch-major rows: (N, B, *) <-> (B, N, *) on the host
+        bm = (lambda a: None if a is None else np.ascontiguousarray(np.swapaxes(np.asarray(a), 0, 1)))  # noqa: E731
+        gth, gdth, gtau = _hip.cpu_fd_trajectory_vjp(model, theta0, dtheta0, bm(taumat), g, bm(Ftipmat), dt, intRes, bm(gpos), bm(gvel),
+                                                     bm(gacc))
+        return gth, gdth, bm(gtau)
+    return _hip.cpu_fd_trajectory_vjp(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos, gvel, gacc)
+
+
 def _launch_fd_trajectory_cpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64, layout="batch_major",
                               device_layout=None):
     del device_layout   # (a device-side choice; the host rows are walked in whatever order they come)
@@ -409,6 +419,11 @@ def _launch_fd_derivatives_gpu(model, q, qd, tau, g=None, Ftip=None):
     return get_context().fd_derivatives_host(model, q, qd, tau, g, Ftip)
 
 
+def _launch_fd_trajectory_vjp_gpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos=None, gvel=None, gacc=None,
+                                  layout="batch_major"):
+    return get_context().fd_trajectory_vjp_host(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos, gvel, gacc, layout=layout)
+
+
 def _launch_fd_trajectory_gpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64, layout="batch_major",
                               device_layout=None):
     return get_context().fd_trajectory_host(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=dtype, layout=layout,
@@ -474,6 +489,10 @@ def _build_kernel_registry() -> KernelRegistry:
         ("dynamics.mass_matrix", "mp_mass_matrix_host_f64", _launch_mass_matrix_gpu, _launch_mass_matrix_cpu),
         ("dynamics.forward", "mp_forward_dynamics_host_f64", _launch_forward_dynamics_gpu, _launch_forward_dynamics_cpu),
         ("dynamics.forward_trajectory", "mp_fd_trajectory_host_f32 / _f64", _launch_fd_trajectory_gpu, _launch_fd_trajectory_cpu),
+        # gradients of the roll-out (csrc/mp_rollout_vjp.h); the name sorts after "dynamics.forward_trajectory", so the pinned start of the
+        # sorted name list stays as it is
+        ("dynamics.forward_trajectory_vjp", "mp_fd_trajectory_vjp_host_f64 / _tm_f64", _launch_fd_trajectory_vjp_gpu,
+         _launch_fd_trajectory_vjp_cpu),
         # analytical derivatives (csrc/mp_deriv.h).  The forward one is "dynamics.fwd_derivatives": the registry's sorted name list is
         # pinned right after "dynamics.forward" by the unknown-name message test, and "dynamics.forward_*" would land there
         ("dynamics.inverse_derivatives", "mp_id_derivatives_host_f64", _launch_id_derivatives_gpu, _launch_id_derivatives_cpu),
