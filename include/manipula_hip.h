@@ -272,6 +272,27 @@ int mp_fd_trajectory_tm_f32(mp_ctx* ctx, const mp_model* model, const float* d_t
 int mp_fd_trajectory_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_theta0, const double* d_dtheta0,
                             const double* d_taumat, const double* d_Ftipmat, int64_t B, int64_t N, const double* g,
                             double dt, int intRes, float* d_pos, float* d_vel, float* d_acc);
+/* Inverse-dynamics regressor and the normal equations of inertial-parameter identification (float64, models of 1..8 joints -
+ * MP_ERR_UNSUPPORTED above that; csrc/mp_regressor.h).  No counterpart in this ABI's reference interface.  Inverse dynamics is
+ * linear in the ten inertial parameters of every link:  tau = Y(q, qd, qdd, g) pi + tau_ext(q, Ftip),  pi = n x [m, hx, hy, hz,
+ * Ixx, Ixy, Ixz, Iyy, Iyz, Izz] in link i's CoM frame at the home pose (Mlist_per_link[i]), h = m c, I about that frame's origin;
+ * tau_ext is the tip wrench's share.  Torques are the unclipped ones.
+ *   regressor:        Y (rows, n, 10n) as [row][j][10 k + c] (zero for k < j), tau_ext (rows, n, may be NULL).  A row with a
+ *                     non-finite input comes back NaN in its row of Y and tau_ext.
+ *   normal equations: A = sum Y^T Y (10n, 10n, full and symmetric; may be NULL: then only b and rr), b = sum Y^T (rhs - tau_ext)
+ *                     (10n), rr = sum |rhs - tau_ext|^2 (1), over all rows, Y never stored.  With A = NULL, Ftip = NULL and rhs a
+ *                     cotangent of tau, b is the parameter vector-Jacobian product.  A non-finite input in any row (rhs included)
+ *                     makes A, b and rr NaN; rows = 0 gives zeros.  A fixed grid, per-workgroup partials added in a fixed order
+ *                     and no floating-point atomics: repeat calls are bit-identical.
+ * The device forms are asynchronous (no synchronisation, no allocation: they may be captured into a launch graph); d_work holds
+ * mp_id_regressor_normal_workspace_bytes(model, rows) (the byte count, or minus an MP_ERR_* code).  The host forms take their
+ * device memory from the context's pool. */
+int mp_id_regressor_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd, int64_t rows,
+                        const double* g, const double* Ftip, double* d_Y, double* d_tau_ext);
+int64_t mp_id_regressor_normal_workspace_bytes(const mp_model* model, int64_t rows);
+int mp_id_regressor_normal_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd,
+                               const double* d_rhs, int64_t rows, const double* g, const double* Ftip, void* d_work, double* d_A,
+                               double* d_b, double* d_rr);
 /* Gradients of forward_dynamics_trajectory (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED above that; intRes >= 1): the
  * vector-Jacobian product of the roll-out above, by a reverse pass through its sub-steps (csrc/mp_rollout_vjp.h).  No counterpart in
  * this ABI's reference interface, whose torch backend differentiates the roll-out with autograd.  Given the cotangents gpos / gvel /
@@ -333,6 +354,11 @@ int mp_fk_jac_id_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, c
                           double* J, double* tau);
 
 int mp_mass_matrix_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, int64_t rows, double* M);
+int mp_id_regressor_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd, int64_t rows,
+                             const double* g, const double* Ftip, double* Y, double* tau_ext);
+int mp_id_regressor_normal_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd,
+                                    const double* rhs, int64_t rows, const double* g, const double* Ftip, double* A, double* b,
+                                    double* rr);
 int mp_fd_trajectory_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* theta0, const double* dtheta0,
                                   const double* taumat, const double* Ftipmat, int64_t B, int64_t N, const double* g, double dt,
                                   int intRes, const double* gpos, const double* gvel, const double* gacc, double* gtheta0,
@@ -406,6 +432,10 @@ int mp_fd_derivatives_cpu_f64(const mp_model* model, const double* q, const doub
 int mp_fd_trajectory_cpu_f32(const mp_model* model, const float* theta0, const float* dtheta0, const float* taumat,
                              const float* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, float* pos,
                              float* vel, float* acc, int nthreads);
+int mp_id_regressor_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, int64_t rows, const double* g,
+                            const double* Ftip, double* Y, double* tau_ext, int nthreads);
+int mp_id_regressor_normal_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, const double* rhs,
+                                   int64_t rows, const double* g, const double* Ftip, double* A, double* b, double* rr, int nthreads);
 int mp_fd_trajectory_vjp_cpu_f64(const mp_model* model, const double* theta0, const double* dtheta0, const double* taumat,
                                  const double* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, const double* gpos,
                                  const double* gvel, const double* gacc, double* gtheta0, double* gdtheta0, double* gtaumat,

@@ -106,6 +106,11 @@ SIGNATURES = {
     "mp_fd_derivatives_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
     "mp_id_derivatives_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "mp_fd_derivatives_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_id_regressor_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp]),
+    "mp_id_regressor_normal_workspace_bytes": (ctypes.c_int64, [_vp, _i64]),
+    "mp_id_regressor_normal_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
+    "mp_id_regressor_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_id_regressor_normal_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "mp_fd_trajectory_vjp_workspace_bytes": (ctypes.c_int64, [_vp, _i64, _i64, ctypes.c_int]),
     "mp_fd_trajectory_vjp_tm_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_fd_trajectory_vjp_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
@@ -131,6 +136,8 @@ SIGNATURES = {
     "mp_forward_dynamics_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_id_derivatives_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_fd_derivatives_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_id_regressor_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_id_regressor_normal_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_fd_trajectory_vjp_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_fd_trajectory_cpu_f32": (ctypes.c_int, [_vp, _c_fp, _c_fp, _c_fp, _c_fp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp, ctypes.c_int]),
     "mp_fd_trajectory_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp, ctypes.c_int]),
@@ -829,6 +836,37 @@ class HipContext:
                 b.free()
         return tuple(out)
 
+    def id_regressor(self, model, d_q, d_qd, d_qdd, rows, d_Y, d_tau_ext=None, g=None, Ftip=None):
+        """Inverse-dynamics regressor on device buffers (float64, csrc/mp_regressor.h): Y (rows, n, 10n), tau_ext (rows, n) or None.
+        Asynchronous (capturable)."""
+        _check(self.lib.mp_id_regressor_f64(self.handle, model.handle, _p(d_q), _p(d_qd), _p(d_qdd), int(rows),
+                                            _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _p(d_Y), _p(d_tau_ext)))
+
+    def id_regressor_normal(self, model, d_q, d_qd, d_qdd, d_rhs, rows, d_work, d_A, d_b, d_rr, g=None, Ftip=None):
+        """Normal equations of the regressor on device buffers: A = sum Y^T Y (10n, 10n; d_A may be None), b = sum Y^T (rhs - tau_ext),
+        rr = sum |rhs - tau_ext|^2; d_work holds id_regressor_normal_workspace_bytes(model, rows).  Asynchronous (capturable)."""
+        _check(self.lib.mp_id_regressor_normal_f64(self.handle, model.handle, _p(d_q), _p(d_qd), _p(d_qdd), _p(d_rhs), int(rows),
+                                                   _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _p(d_work),
+                                                   _p(d_A), _p(d_b), _p(d_rr)))
+
+    def id_regressor_host(self, model: HipModel, q, qd, qdd, g=None, Ftip=None):
+        """(Y (rows, n, 10n), tau_ext (rows, n)) of (rows, n) host rows."""
+        q, qd, qdd = _regressor_rows(model, q, qd, qdd)
+        Y, te = np.empty((q.shape[0], model.n, 10 * model.n)), np.empty(q.shape)
+        _check(self.lib.mp_id_regressor_host_f64(self.handle, model.handle, _dptr(q), _dptr(qd), _dptr(qdd), q.shape[0],
+                                                 _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _dptr(Y), _dptr(te)))
+        return Y, te
+
+    def id_regressor_normal_host(self, model: HipModel, q, qd, qdd, rhs, g=None, Ftip=None, want_A: bool = True):
+        """(A (10n, 10n) or None, b (10n), rr) of (rows, n) host rows."""
+        q, qd, qdd, rhs = _regressor_rows(model, q, qd, qdd, rhs)
+        w = 10 * model.n
+        A, b, rr = (np.empty((w, w)) if want_A else None), np.empty(w), np.empty(1)
+        _check(self.lib.mp_id_regressor_normal_host_f64(self.handle, model.handle, _dptr(q), _dptr(qd), _dptr(qdd), _dptr(rhs), q.shape[0],
+                                                        _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _dptr(A),
+                                                        _dptr(b), _dptr(rr)))
+        return A, b, float(rr[0])
+
     def fd_trajectory_vjp(self, model, d_theta0, d_dtheta0, d_taumat, d_Ftipmat, B, N, g, dt, intRes, d_gpos, d_gvel, d_gacc, d_work,
                           d_gtheta0, d_gdtheta0, d_gtaumat):
         """Gradients of the roll-out on device buffers (float64, csrc/mp_rollout_vjp.h), time-major taumat / Ftipmat / cotangents /
@@ -1085,6 +1123,41 @@ def fd_trajectory_vjp_workspace_bytes(model: "HipModel", B: int, N: int, intRes:
     if v < 0:
         _check(-v)
     return v
+
+
+def _regressor_rows(model, q, *others):
+    q = _as_c(q, np.float64, name="q")
+    if q.ndim != 2 or q.shape[1] != model.n:
+        raise ValueError(f"q must be (rows, {model.n}); got {q.shape}")
+    return (q,) + tuple(_as_c(a, np.float64, q.shape, name) for a, name in zip(others, ("qd", "qdd", "rhs")))
+
+
+def id_regressor_normal_workspace_bytes(model: "HipModel", rows: int) -> int:
+    """Device workspace of mp_id_regressor_normal_f64 (per-workgroup partial sums)."""
+    v = int(load_library().mp_id_regressor_normal_workspace_bytes(model.handle, int(rows)))
+    if v < 0:
+        _check(-v)
+    return v
+
+
+def cpu_id_regressor(model: "HipModel", q, qd, qdd, g=None, Ftip=None, nthreads: int = 0):
+    """CPU twin of HipContext.id_regressor_host: (Y (rows, n, 10n), tau_ext (rows, n))."""
+    q, qd, qdd = _regressor_rows(model, q, qd, qdd)
+    Y, te = np.empty((q.shape[0], model.n, 10 * model.n)), np.empty(q.shape)
+    _check(load_library().mp_id_regressor_cpu_f64(model.handle, _dptr(q), _dptr(qd), _dptr(qdd), q.shape[0], _dptr(_vec_or_none(g, 3, "g")),
+                                                  _dptr(_vec_or_none(Ftip, 6, "Ftip")), _dptr(Y), _dptr(te), int(nthreads)))
+    return Y, te
+
+
+def cpu_id_regressor_normal(model: "HipModel", q, qd, qdd, rhs, g=None, Ftip=None, want_A: bool = True, nthreads: int = 0):
+    """CPU twin of HipContext.id_regressor_normal_host: (A or None, b, rr)."""
+    q, qd, qdd, rhs = _regressor_rows(model, q, qd, qdd, rhs)
+    w = 10 * model.n
+    A, b, rr = (np.empty((w, w)) if want_A else None), np.empty(w), np.empty(1)
+    _check(load_library().mp_id_regressor_normal_cpu_f64(model.handle, _dptr(q), _dptr(qd), _dptr(qdd), _dptr(rhs), q.shape[0],
+                                                         _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _dptr(A),
+                                                         _dptr(b), _dptr(rr), int(nthreads)))
+    return A, b, float(rr[0])
 
 
 def cpu_fd_trajectory_vjp(model: "HipModel", theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos=None, gvel=None, gacc=None,

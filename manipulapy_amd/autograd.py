@@ -4,12 +4,15 @@
     tau = mpa.inverse_dynamics(dyn, q, qd, qdd, g, Ftip)          # q, qd, qdd: CPU float64 tensors, (n,) or (rows, n)
     J = torch.autograd.functional.jacobian(lambda q: mpa.inverse_dynamics(dyn, q, qd, qdd, g, Ftip), q)
     pos, vel, acc = mpa.forward_dynamics_trajectory(planner, theta0, dtheta0, taumat, g, Ftipmat, dt=0.01, intRes=1)
+    tau = mpa.inverse_dynamics_parameters(dyn, params, q, qd, qdd, g, Ftip)   # differentiable in params (n, 10)
 
 The forward value is the registered inverse / forward dynamics operation, the backward pass the vector-Jacobian product with the
 registered derivative operation ("dynamics.inverse_derivatives" / "dynamics.fwd_derivatives"): the GPU under the "hip" backend,
 the CPU twin otherwise.  forward_dynamics_trajectory is a planner's roll-out ("dynamics.forward_trajectory") whose backward pass is
 the reverse pass through its sub-steps ("dynamics.forward_trajectory_vjp", csrc/mp_rollout_vjp.h).  Once differentiable (no second derivatives).  g and Ftip are constants: a tensor among them that
-requires grad is refused.  Imported on demand only - never from the package's __init__ (torch stays optional).
+requires grad is refused.  inverse_dynamics_parameters is tau = Y(q, qd, qdd) pi + tau_ext ("dynamics.inverse_regressor"), whose
+backward pass is sum Y^T g_tau from the normal-equations operation ("dynamics.inverse_regressor_normal", no A, rhs = g_tau): Y is
+never formed.  Imported on demand only - never from the package's __init__ (torch stays optional).
 """
 from __future__ import annotations
 
@@ -18,7 +21,7 @@ import torch
 
 from .registry import execute_registered_kernel
 
-__all__ = ["inverse_dynamics", "forward_dynamics", "forward_dynamics_trajectory"]
+__all__ = ["inverse_dynamics", "forward_dynamics", "forward_dynamics_trajectory", "inverse_dynamics_parameters"]
 
 
 def _const(v, name):
@@ -130,3 +133,36 @@ def forward_dynamics_trajectory(planner, theta0, dtheta0, taumat, g=None, Ftipma
     Ftipmat (N, 6) / (B, N, 6) or None.  The float32 cast of the rows counts as the identity; g and Ftipmat are constants."""
     return _ForwardDynamicsTrajectory.apply(planner, _as_tensor(theta0), _as_tensor(dtheta0), _as_tensor(taumat), _const(g, "g"),
                                             _const(Ftipmat, "Ftipmat"), float(dt), int(intRes))
+
+
+class _InverseDynamicsParameters(torch.autograd.Function):
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gtau):
+        dyn, q, qd, qdd, g = ctx.args
+        gt = np.ascontiguousarray(np.atleast_2d(gtau.detach().cpu().numpy()).astype(np.float64))
+        model = dyn._derivative_model("inverse_dynamics_parameters")
+        _, b, _ = execute_registered_kernel("dynamics.inverse_regressor_normal", model, q, qd, qdd, gt, g, None, want_A=False)
+        return None, torch.from_numpy(b.reshape(ctx.shape)), None, None, None, None, None
+
+    @staticmethod
+    def forward(ctx, dyn, params, q, qd, qdd, g, Ftip):
+        one = q.dim() == 1
+        a, b, c = _rows(q, "q"), _rows(qd, "qd"), _rows(qdd, "qdd")
+        pi = _rows(params, "params").reshape(-1)
+        Y, te = dyn.inverse_dynamics_regressor(a, b, c, g, Ftip)
+        ctx.args, ctx.shape = (dyn, a, b, c, g), tuple(params.shape)
+        out = torch.from_numpy(np.einsum("rjp,p->rj", Y, pi) + te)
+        return out[0] if one else out
+
+
+def inverse_dynamics_parameters(dyn, params, q, qd, qdd, g=None, Ftip=None) -> torch.Tensor:
+    """tau = Y(q, qd, qdd, g) pi + tau_ext(q, Ftip) of a ManipulatorDynamics (with Mlist_per_link, n <= 8) at the inertial parameters
+    `params` ((n, 10) or (10n,), ManipulatorDynamics.inertial_parameters()'s convention), differentiable in params only.  (n,) inputs
+    give (n,), (rows, n) inputs (rows, n).  Gradients with respect to q, qd, qdd are not provided here (inverse_dynamics has them)."""
+    for x, name in ((q, "q"), (qd, "qd"), (qdd, "qdd")):
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise ValueError(f"inverse_dynamics_parameters: {name} requires grad - this function is differentiable in params only "
+                             "(use inverse_dynamics for gradients with respect to the state)")
+    return _InverseDynamicsParameters.apply(dyn, _as_tensor(params), _as_tensor(q), _as_tensor(qd), _as_tensor(qdd), _const(g, "g"),
+                                            _const(Ftip, "Ftip"))

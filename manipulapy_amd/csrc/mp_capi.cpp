@@ -337,6 +337,9 @@ bool pool_owned(mp_ctx* ctx, const void* p, size_t bytes) {
 // float32 model resident in device memory (read by the *_dm kernels with scalar loads), followed in the same buffer by the
 // float64 model (read by the float64 re-evaluation of ill-conditioned float32 rows in the generic kernels, MpCall::cold_model)
 constexpr size_t kDevModelD = (sizeof(MpModel<float>) + 255) & ~(size_t)255;  // offset of the float64 copy
+// ... and then the inertial-parameter map of the regressor (mp_model::pmap, csrc/mp_regressor.h)
+constexpr size_t kDevModelMap = (kDevModelD + sizeof(MpModel<double>) + 255) & ~(size_t)255;
+constexpr size_t kDevModelBytes = kDevModelMap + sizeof(mp_model::pmap);
 int device_model(mp_ctx* ctx, const mp_model* model, const MpModel<float>** out) {
   auto it = ctx->dev_models.find(model->uid);
   if (it == ctx->dev_models.end()) {
@@ -346,19 +349,21 @@ int device_model(mp_ctx* ctx, const mp_model* model, const MpModel<float>** out)
       // a blocking hipMemcpy would tie the legacy stream to the capturing one and is refused) and waited for, so the replays'
       // kernels - and the eager launches after the capture - find it
       RelaxedCapture relaxed(true);
-      const size_t bytes = (kDevModelD + sizeof(MpModel<double>) + 255) & ~size_t(255);
+      const size_t bytes = (kDevModelBytes + 255) & ~size_t(255);
       HIP_TRY(hipMalloc(&d, bytes));
       ctx->live[d] = bytes;
       hipError_t he = hipMemcpyAsync(d, &model->f, sizeof(MpModel<float>), hipMemcpyHostToDevice, ctx->copy);
       if (he == hipSuccess) he = hipMemcpyAsync((char*)d + kDevModelD, &model->d, sizeof(MpModel<double>), hipMemcpyHostToDevice, ctx->copy);
+      if (he == hipSuccess) he = hipMemcpyAsync((char*)d + kDevModelMap, model->pmap, sizeof model->pmap, hipMemcpyHostToDevice, ctx->copy);
       if (he == hipSuccess) he = hipStreamSynchronize(ctx->copy);
       if (he != hipSuccess) { ctx->free_by_size[bytes].push_back(d); return hip_err(he, "device copy of the model (first use inside a capture)"); }
     } else {
-      if (int rc = mp_malloc(ctx, kDevModelD + sizeof(MpModel<double>), &d)) return rc;
+      if (int rc = mp_malloc(ctx, kDevModelBytes, &d)) return rc;
       // (on the compute stream and waited for: the first kernel that reads the copy follows on that stream, and the streams are
       // non-blocking - nothing orders them with a copy on the null stream)
       HIP_TRY(hipMemcpyAsync(d, &model->f, sizeof(MpModel<float>), hipMemcpyHostToDevice, ctx->compute));
       HIP_TRY(hipMemcpyAsync((char*)d + kDevModelD, &model->d, sizeof(MpModel<double>), hipMemcpyHostToDevice, ctx->compute));
+      HIP_TRY(hipMemcpyAsync((char*)d + kDevModelMap, model->pmap, sizeof model->pmap, hipMemcpyHostToDevice, ctx->compute));
       HIP_TRY(hipStreamSynchronize(ctx->compute));
     }
     it = ctx->dev_models.emplace(model->uid, d).first;
@@ -905,6 +910,61 @@ static int deriv_impl(const char* fn, bool fd, mp_ctx* ctx, const mp_model* mode
   if (fd) HIP_TRY(mpk_fd_deriv(ctx->compute, model->d, c, ftip, d_q, d_qd, d_x, d_y, d_dq, d_dqd, d_mat, (long)rows));
   else HIP_TRY(mpk_id_deriv(ctx->compute, model->d, c, ftip, d_q, d_qd, d_x, d_y, d_dq, d_dqd, d_mat, (long)rows));
   return MP_OK;
+}
+
+// dynamics regressor (mp_regressor.h): float64, unrolled models only; the kernels read the inertial-parameter map from the
+// model's device copy.  Y's row holds n x 10n values, A 10n x 10n.
+constexpr int MP_REG_P = 10;
+static int regressor_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd,
+                          int64_t rows, const double* g, const double* Ftip, double* d_Y, double* d_tau_ext) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (rows == 0) return MP_OK;
+  REQUIRE(d_q && d_qd && d_qdd && d_Y, "%s: null device pointer", fn);
+  REQUIRE(aligned16(d_q) && aligned16(d_qd) && aligned16(d_qdd) && aligned16(d_Y) && aligned16(d_tau_ext),
+          "%s: device pointers must be 16-byte aligned", fn);
+  const MpModel<float>* dm = nullptr;
+  if (int rc = device_model(ctx, model, &dm)) return rc;
+  const double* dmap = (const double*)((const char*)dm + kDevModelMap);
+  MpCall<double> c;
+  make_call<double>(model, g, Ftip, &c);
+  PROFILE_SCOPE(ctx, fn);
+  HIP_TRY(mpk_id_regressor(ctx->compute, model->d, dmap, c, any_nonzero(Ftip), d_q, d_qd, d_qdd, d_Y, d_tau_ext, (long)rows));
+  return MP_OK;
+}
+static int regressor_normal_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd,
+                                 const double* d_qdd, const double* d_rhs, int64_t rows, const double* g, const double* Ftip,
+                                 void* d_work, double* d_A, double* d_b, double* d_rr) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  REQUIRE(d_b && d_rr, "%s: null device pointer", fn);
+  REQUIRE(aligned16(d_A) && aligned16(d_b) && aligned16(d_rr), "%s: device pointers must be 16-byte aligned", fn);
+  const size_t w = (size_t)MP_REG_P * (size_t)model->d.n;
+  PROFILE_SCOPE(ctx, fn);
+  if (rows == 0) {
+    if (d_A) HIP_TRY(hipMemsetAsync(d_A, 0, w * w * sizeof(double), ctx->compute));
+    HIP_TRY(hipMemsetAsync(d_b, 0, w * sizeof(double), ctx->compute));
+    HIP_TRY(hipMemsetAsync(d_rr, 0, sizeof(double), ctx->compute));
+    return MP_OK;
+  }
+  REQUIRE(d_q && d_qd && d_qdd && d_rhs && d_work, "%s: null device pointer", fn);
+  REQUIRE(aligned16(d_q) && aligned16(d_qd) && aligned16(d_qdd) && aligned16(d_rhs) && aligned16(d_work),
+          "%s: device pointers must be 16-byte aligned", fn);
+  const MpModel<float>* dm = nullptr;
+  if (int rc = device_model(ctx, model, &dm)) return rc;
+  const double* dmap = (const double*)((const char*)dm + kDevModelMap);
+  MpCall<double> c;
+  make_call<double>(model, g, Ftip, &c);
+  HIP_TRY(mpk_id_regressor_normal(ctx->compute, model->d, dmap, c, any_nonzero(Ftip), d_q, d_qd, d_qdd, d_rhs, (long)rows,
+                                  (double*)d_work, d_A, d_b, d_rr));
+  return MP_OK;
+}
+int64_t regressor_normal_work_bytes(int n, int64_t rows) {
+  return rows <= 0 ? 0 : (int64_t)mp_reg_normal_groups((long)rows) * (int64_t)mp_reg_normal_stride(n) * (int64_t)sizeof(double);
 }
 
 // reverse mode through the roll-out (mp_rollout_vjp.h): float64, unrolled models only
@@ -1602,7 +1662,8 @@ int mp_model_create(int n, const double* S, const double* Mcom, const double* G,
   // checked against the unrolled ones and the goldens on the 6..8-joint robots too
   const char* looped = getenv("MANIPULAPY_HIP_LOOPED");
   if (n <= MP_MAX_DOF && !(looped && looped[0] == '1')) {
-    rc = mp_compile_model(n, S, Mcom, G, M_ee, joint_limits, torque_limits, &m->d, msg, sizeof msg);
+    std::memset(m->pmap, 0, sizeof m->pmap);
+    rc = mp_compile_model(n, S, Mcom, G, M_ee, joint_limits, torque_limits, &m->d, msg, sizeof msg, m->pmap);
     if (!rc) mp_model_cast(m->d, &m->f);
   } else {  // 9..32 joints: the looped kernels' model; d / f only carry the joint count
     m->big = true;
@@ -2133,6 +2194,23 @@ int mp_fd_derivatives_f64(mp_ctx* ctx, const mp_model* model, const double* d_q,
                           double* d_Minv) {
   return deriv_impl("mp_fd_derivatives_f64", true, ctx, model, d_q, d_qd, d_tau, rows, g, Ftip, d_qdd, d_dqdd_dq, d_dqdd_dqd, d_Minv);
 }
+int mp_id_regressor_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd, int64_t rows,
+                        const double* g, const double* Ftip, double* d_Y, double* d_tau_ext) {
+  return regressor_impl("mp_id_regressor_f64", ctx, model, d_q, d_qd, d_qdd, rows, g, Ftip, d_Y, d_tau_ext);
+}
+int64_t mp_id_regressor_normal_workspace_bytes(const mp_model* model, int64_t rows) {
+  if (!model) return -set_err(MP_ERR_INVALID, "mp_id_regressor_normal_workspace_bytes: null model");
+  if (rows < 0) return -set_err(MP_ERR_INVALID, "mp_id_regressor_normal_workspace_bytes: negative row count");
+  if (model->big)
+    return -set_err(MP_ERR_UNSUPPORTED, "mp_id_regressor_normal_workspace_bytes: not available for models with more than %d joints "
+                    "(this one has %d)", MP_MAX_DOF, model->d.n);
+  return regressor_normal_work_bytes(model->d.n, rows);
+}
+int mp_id_regressor_normal_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd,
+                               const double* d_rhs, int64_t rows, const double* g, const double* Ftip, void* d_work, double* d_A,
+                               double* d_b, double* d_rr) {
+  return regressor_normal_impl("mp_id_regressor_normal_f64", ctx, model, d_q, d_qd, d_qdd, d_rhs, rows, g, Ftip, d_work, d_A, d_b, d_rr);
+}
 int64_t mp_fd_trajectory_vjp_workspace_bytes(const mp_model* model, int64_t B, int64_t N, int intRes) {
   if (!model) return -set_err(MP_ERR_INVALID, "mp_fd_trajectory_vjp_workspace_bytes: null model");
   if (B < 0 || N < 0 || intRes < 1)
@@ -2281,6 +2359,70 @@ int mp_fd_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double*
                                int64_t rows, const double* g, const double* Ftip, double* qdd, double* dqdd_dq, double* dqdd_dqd,
                                double* Minv) {
   return deriv_host_impl("mp_fd_derivatives_host_f64", true, ctx, model, q, qd, tau, rows, g, Ftip, qdd, dqdd_dq, dqdd_dqd, Minv);
+}
+
+int mp_id_regressor_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd, int64_t rows,
+                             const double* g, const double* Ftip, double* Y, double* tau_ext) {
+  const char* fn = "mp_id_regressor_host_f64";
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (rows == 0) return MP_OK;
+  REQUIRE(q && qd && qdd && Y, "%s: null host pointer", fn);
+  const size_t n = (size_t)model->d.n, vb = (size_t)rows * n * sizeof(double), yb = vb * n * MP_REG_P;
+  Scratch sc(ctx);
+  void *dq, *dqd, *dqdd, *dY, *dte = nullptr;
+  if (int rc = sc.get(vb, &dq)) return rc;
+  if (int rc = sc.get(vb, &dqd)) return rc;
+  if (int rc = sc.get(vb, &dqdd)) return rc;
+  if (int rc = sc.get(yb, &dY)) return rc;
+  if (tau_ext) if (int rc = sc.get(vb, &dte)) return rc;
+  H2D(dq, q, vb);
+  H2D(dqd, qd, vb);
+  H2D(dqdd, qdd, vb);
+  if (int rc = regressor_impl(fn, ctx, model, (double*)dq, (double*)dqd, (double*)dqdd, rows, g, Ftip, (double*)dY, (double*)dte)) return rc;
+  D2H(Y, dY, yb);
+  if (tau_ext) D2H(tau_ext, dte, vb);
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+int mp_id_regressor_normal_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd,
+                                    const double* rhs, int64_t rows, const double* g, const double* Ftip, double* A, double* b,
+                                    double* rr) {
+  const char* fn = "mp_id_regressor_normal_host_f64";
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  REQUIRE(b && rr && (rows == 0 || (q && qd && qdd && rhs)), "%s: null host pointer", fn);
+  const size_t n = (size_t)model->d.n, vb = (size_t)rows * n * sizeof(double), w = n * MP_REG_P;
+  Scratch sc(ctx);
+  void *dq = nullptr, *dqd = nullptr, *dqdd = nullptr, *drhs = nullptr, *dwork = nullptr, *dA = nullptr, *db, *drr;
+  if (rows > 0) {
+    if (int rc = sc.get(vb, &dq)) return rc;
+    if (int rc = sc.get(vb, &dqd)) return rc;
+    if (int rc = sc.get(vb, &dqdd)) return rc;
+    if (int rc = sc.get(vb, &drhs)) return rc;
+    if (int rc = sc.get((size_t)regressor_normal_work_bytes((int)n, rows), &dwork)) return rc;
+  }
+  if (A) if (int rc = sc.get(w * w * sizeof(double), &dA)) return rc;
+  if (int rc = sc.get(w * sizeof(double), &db)) return rc;
+  if (int rc = sc.get(sizeof(double), &drr)) return rc;
+  if (rows > 0) {
+    H2D(dq, q, vb);
+    H2D(dqd, qd, vb);
+    H2D(dqdd, qdd, vb);
+    H2D(drhs, rhs, vb);
+  }
+  if (int rc = regressor_normal_impl(fn, ctx, model, (double*)dq, (double*)dqd, (double*)dqdd, (double*)drhs, rows, g, Ftip, dwork,
+                                     (double*)dA, (double*)db, (double*)drr))
+    return rc;
+  if (A) D2H(A, dA, w * w * sizeof(double));
+  D2H(b, db, w * sizeof(double));
+  D2H(rr, drr, sizeof(double));
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
 }
 
 int mp_pd_regulation_host_f64(mp_ctx* ctx, const mp_model* model, const double* theta0, const double* theta_des, const double* Kp,

@@ -23,6 +23,7 @@
 #include "mp_ik.h"
 #include "mp_handles.h"
 #include "mp_model_compile.h"
+#include "mp_regressor.h"
 #include "mp_rollout_vjp.h"
 
 namespace {
@@ -448,6 +449,90 @@ int mp_fd_derivatives_cpu_f64(const mp_model* model, const double* q, const doub
                               const double* g, const double* Ftip, double* qdd, double* dqdd_dq, double* dqdd_dqd, double* Minv,
                               int nthreads) {
   return deriv_cpu("mp_fd_derivatives_cpu_f64", true, model, q, qd, tau, rows, g, Ftip, qdd, dqdd_dq, dqdd_dqd, Minv, nthreads);
+}
+// dynamics regressor (mp_regressor.h): the kernels' per-row code over host rows
+static int regressor_cpu_check(const char* fn, const mp_model* model, int64_t rows) {
+  char msg[192];
+  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
+  if (model->big) {
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (rows < 0) { std::snprintf(msg, sizeof msg, "%s: negative row count", fn); return fail(msg); }
+  return MP_OK;
+}
+int mp_id_regressor_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, int64_t rows, const double* g,
+                            const double* Ftip, double* Y, double* tau_ext, int nthreads) {
+  const char* fn = "mp_id_regressor_cpu_f64";
+  if (int rc = regressor_cpu_check(fn, model, rows)) return rc;
+  if (rows == 0) return MP_OK;
+  if (!q || !qd || !qdd || !Y) { char msg[96]; std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
+  const MpModel<double>& M = model->d;
+  const MpCall<double> C = make_call<double>(model, g, Ftip);
+  const bool ftip = any_nonzero(Ftip);
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(rows, 64, nthreads, [&](int64_t lo, int64_t hi) {
+      for (int64_t r = lo; r < hi; ++r) {
+        if (ftip) mp_id_regressor_row<N, true>(M, model->pmap, C, q, qd, qdd, Y, tau_ext, (long)r);
+        else mp_id_regressor_row<N, false>(M, model->pmap, C, q, qd, qdd, Y, tau_ext, (long)r);
+      }
+    });
+  })
+  return MP_OK;
+}
+// Normal equations: the rows are cut into a number of chunks fixed by the row count alone (never by the thread count); each chunk
+// sums its rows in order, then the chunks are added in order - repeat calls are bit-identical.  Only A's upper triangle is summed
+// and then mirrored.
+int mp_id_regressor_normal_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, const double* rhs,
+                                   int64_t rows, const double* g, const double* Ftip, double* A, double* b, double* rr, int nthreads) {
+  const char* fn = "mp_id_regressor_normal_cpu_f64";
+  if (int rc = regressor_cpu_check(fn, model, rows)) return rc;
+  if (!b || !rr || (rows > 0 && (!q || !qd || !qdd || !rhs))) {
+    char msg[96];
+    std::snprintf(msg, sizeof msg, "%s: null pointer", fn);
+    return fail(msg);
+  }
+  const MpModel<double>& M = model->d;
+  const int W = MP_REG_P * M.n;
+  const int64_t chunks = std::min<int64_t>(256, (rows + 63) / 64), per = chunks ? (rows + chunks - 1) / chunks : 0;
+  const size_t stride = (size_t)W * W + W + 1;
+  std::vector<double> part((size_t)chunks * stride, 0.0);
+  const MpCall<double> C = make_call<double>(model, g, Ftip);
+  const bool ftip = any_nonzero(Ftip);
+  const bool with_a = A != nullptr;
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(chunks, 1, nthreads, [&](int64_t lo, int64_t hi) {
+      constexpr int WN = MP_REG_P * N;
+      double y[N][WN], res[N];
+      auto put = [&](int j, int col, double v) { y[j][col] = v; };
+      auto rs = [&](int j, double v) { res[j] = v; };
+      for (int64_t ch = lo; ch < hi; ++ch) {
+        double* P = part.data() + (size_t)ch * stride;
+        for (int64_t r = ch * per; r < std::min(rows, (ch + 1) * per); ++r) {
+          if (ftip) mp_id_regressor_normal_part<N, true, 1>(M, model->pmap, C, q, qd, qdd, rhs, (long)r, 0, put, rs);
+          else mp_id_regressor_normal_part<N, false, 1>(M, model->pmap, C, q, qd, qdd, rhs, (long)r, 0, put, rs);
+          for (int j = 0; j < N; ++j) {
+            if (with_a)
+              for (int a = 0; a < WN; ++a)
+                for (int c = a; c < WN; ++c) P[a * WN + c] += y[j][a] * y[j][c];
+            for (int a = 0; a < WN; ++a) P[WN * WN + a] += y[j][a] * res[j];
+            P[WN * WN + WN] += res[j] * res[j];
+          }
+        }
+      }
+    });
+  })
+  for (size_t e = 0; e < stride; ++e) {
+    double v = 0.0;
+    for (int64_t ch = 0; ch < chunks; ++ch) v += part[(size_t)ch * stride + e];
+    const size_t ww = (size_t)W * W;
+    if (e < ww) {
+      const size_t i = e / W, j = e % W;
+      if (with_a && i <= j) { A[e] = v; A[j * W + i] = v; }
+    } else if (e < ww + W) b[e - ww] = v;
+    else rr[0] = v;
+  }
+  return MP_OK;
 }
 // reverse mode through the roll-out (mp_rollout_vjp.h): the kernel's per-trajectory code over batch-major host arrays, each thread
 // with its own workspace of (N + intRes) 2n doubles

@@ -53,10 +53,17 @@ MP_HD void mp_deriv_dstep_up(S rev, T nx, T ny, T fx, T fy, T& dnx, T& dny, T& d
   dfy = rev * fx;
 }
 
+// No per-link observer (what every derivative pass uses)
+struct MpDerivNoHook {
+  template <typename T> MP_HD void operator()(int, T, T, T, T, T, T, T, T, T, T, T, T) const {}
+};
+
 // The primal recursion (mp_rnea_impl's arithmetic, in the same order) keeping what the sweeps need; tau is not clipped.
-template <typename T, int N, bool HAS_FTIP, typename MT>
+// `hook(i, twist w, v, acceleration dw, dv)` sees each link's final twist and acceleration in link frame i (the dynamics
+// regressor, mp_regressor.h, reads them there).
+template <typename T, int N, bool HAS_FTIP, typename MT, typename H = MpDerivNoHook>
 MP_HD void mp_deriv_primal(const MT& M, const MpCall<T>& C, const T (&q)[N], const T (&qd)[N], const T (&qdd)[N],
-                           MpDerivPrimal<T, N>& P, T (&tau)[N]) {
+                           MpDerivPrimal<T, N>& P, T (&tau)[N], const H& hook = H()) {
   mp_joint_state<T, N>(M, q, P.js);
   T fnx[N], fny[N], fnz[N], ffx[N], ffy[N], ffz[N];
   T wx = 0, wy = 0, wz = 0, vx = 0, vy = 0, vz = 0;
@@ -90,6 +97,7 @@ MP_HD void mp_deriv_primal(const MT& M, const MpCall<T>& C, const T (&q)[N], con
     dvy -= qdr * vx + qdp * wx;
     dvz += ap;
     P.wx[i] = wx; P.wy[i] = wy; P.wz[i] = wz; P.vx[i] = vx; P.vy[i] = vy; P.vz[i] = vz;
+    hook(i, wx, wy, wz, vx, vy, vz, dwx, dwy, dwz, dvx, dvy, dvz);
     const T pnx = J.Ixx * wx + J.Ixy * wy + J.Ixz * wz + (J.hy * vz - J.hz * vy);
     const T pny = J.Ixy * wx + J.Iyy * wy + J.Iyz * wz + (J.hz * vx - J.hx * vz);
     const T pnz = J.Ixz * wx + J.Iyz * wy + J.Izz * wz + (J.hx * vy - J.hy * vx);

@@ -10,6 +10,7 @@ struct mp_model {
   bool big = false;    // MP_MAX_DOF < n <= MP_BIG_DOF: only bd / bf hold the joints; the looped kernels (csrc/mp_dyn.h) read them
   MpBigModel<double> bd;
   MpBigModel<float> bf;
+  double pmap[MP_MAX_DOF * 100];  // n <= MP_MAX_DOF: per link the 10 x 10 inertial-parameter map D (mp_inertial_map, mp_regressor.h)
   uint64_t uid;  // never reused, so a context's device copies cannot alias a destroyed model
 };
 

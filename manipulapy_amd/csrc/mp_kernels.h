@@ -42,6 +42,24 @@ hipError_t mpk_fd_deriv(hipStream_t s, const MpModel<double>& M, const MpCall<do
                         const double* tau, double* qdd, double* dq, double* dqd, double* Minv, long rows);
 // reverse mode through the roll-out (csrc/mp_rollout_vjp.h) on the time-major layout: taumat / Ftipmat / gp / gv / ga / gtau (Nt, B, *),
 // theta0 / dtheta0 / gth0 / gdth0 (B, n); Ftipmat and the cotangents may be null; `work` holds (B Nt + B intRes) 2n doubles
+// dynamics regressor (csrc/mp_regressor.h), float64, 1..MP_MAX_DOF joints; Dmap = the model's n x 100 inertial-parameter map in
+// device memory.  Y (rows, n, 10n); tau_ext may be null.
+hipError_t mpk_id_regressor(hipStream_t s, const MpModel<double>& M, const double* Dmap, const MpCall<double>& C, bool ftip,
+                            const double* q, const double* qd, const double* qdd, double* Y, double* tau_ext, long rows);
+// Normal equations of the regressor without Y in memory: a fixed grid of mp_reg_normal_groups(rows) workgroups, each over tiles of
+// mp_reg_normal_tile() rows, leaves its partial sums (mp_reg_normal_stride(n) doubles) in `work`; a second kernel adds them in
+// workgroup order.  A (10n, 10n, may be null), b (10n), rr (1).  rows >= 1.
+constexpr int kRegNormalLanes = 5;       // lanes that build one row (a divisor of 10: each builds 10 / lanes columns of every block)
+constexpr int kRegNormalMaxGroups = 1024;
+constexpr int mp_reg_normal_tile() { return 64 / kRegNormalLanes; }
+inline long mp_reg_normal_groups(long rows) {
+  const long tiles = (rows + mp_reg_normal_tile() - 1) / mp_reg_normal_tile();
+  return tiles < kRegNormalMaxGroups ? (tiles > 0 ? tiles : 1) : kRegNormalMaxGroups;
+}
+constexpr long mp_reg_normal_stride(int n) { return ((100L * n * n + 10L * n + 1) + 1) & ~1L; }
+hipError_t mpk_id_regressor_normal(hipStream_t s, const MpModel<double>& M, const double* Dmap, const MpCall<double>& C, bool ftip,
+                                   const double* q, const double* qd, const double* qdd, const double* rhs, long rows, double* work,
+                                   double* A, double* b, double* rr);
 hipError_t mpk_fd_traj_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, const double* theta0, const double* dtheta0,
                            const double* taumat, const double* Ftipmat, long B, long Nt, double h, int intRes, const double* gp,
                            const double* gv, const double* ga, double* work, double* gth0, double* gdth0, double* gtau);

@@ -15,6 +15,7 @@
 #include "mp_dyn.h"
 #include "mp_ik.h"
 #include "mp_kernels.h"
+#include "mp_regressor.h"
 #include "mp_rollout_vjp.h"
 
 namespace {
@@ -279,6 +280,119 @@ __global__ __launch_bounds__(kDerivBlock) void k_fd_traj_vjp(const MpModel<doubl
   double* sub = work + B * Nt * (2 * N) + b * (2 * N);
   mp_fd_traj_vjp<N, HAS_FTIP>(M, C, th0 + o, dth0 + o, taumat + o, HAS_FTIP ? Fm + b * 6 : nullptr, B, Nt, h, intRes, gp ? gp + o : nullptr,
                               gv ? gv + o : nullptr, ga ? ga + o : nullptr, ck, B, sub, B, gth0 + o, gdth0 + o, gtau + o);
+}
+
+// ------------------------------------------------------- dynamics regressor (float64, mp_regressor.h)
+// One lane per row, like k_id_deriv: write-bound (10 n^2 doubles a row)
+template <int N, bool HAS_FTIP>
+__global__ __launch_bounds__(kDerivBlock) void k_id_regressor(const MpModel<double> M, const double* __restrict__ Dmap,
+                                                              const MpCall<double> C, const double* __restrict__ q,
+                                                              const double* __restrict__ qd, const double* __restrict__ qdd,
+                                                              double* __restrict__ Y, double* __restrict__ tau_ext, long rows) {
+  const long r = (long)blockIdx.x * kDerivBlock + threadIdx.x;
+  if (r >= rows) return;
+  mp_id_regressor_row<N, HAS_FTIP>(M, Dmap, C, q, qd, qdd, Y, tau_ext, r);
+}
+
+// Normal equations, fused: one wave a workgroup, a fixed grid striding over tiles of T = 64 / LANES rows.  Per tile, LANES lanes
+// build each row's Y (its n rows of 10n) and its residual rhs - tau_ext into LDS; then lane L < 55 adds the tile's n T rows of Y
+// into its n x n register block (bi, bj), bi <= bj, of the upper triangle of A (10 blocks a side, whatever n), every lane one or
+// two entries of b, lane 63 the squared residuals.  The wave's partials go to `work` once at the end; nothing reaches memory per row.
+template <int N, bool HAS_FTIP, bool WITH_A>
+__global__ __launch_bounds__(64) void k_id_regressor_normal(const MpModel<double> M, const double* __restrict__ Dmap,
+                                                            const MpCall<double> C, const double* __restrict__ q,
+                                                            const double* __restrict__ qd, const double* __restrict__ qdd,
+                                                            const double* __restrict__ rhs, long rows, double* __restrict__ work) {
+  constexpr int LANES = kRegNormalLanes, T = 64 / LANES, W = MP_REG_P * N, R = T * N;
+  static_assert(MP_REG_P % LANES == 0, "lanes per row must divide the 10 parameters");
+  __shared__ double Ys[R * W];
+  __shared__ double Rs[R];
+  const int L = threadIdx.x;
+  const int t = L / LANES, sub = L % LANES;
+  int bi = 0, rem = L < 55 ? L : 0;  // (bi, bj) = the L-th upper block in row order
+  while (rem >= 10 - bi) { rem -= 10 - bi; ++bi; }
+  const int bj = bi + rem;
+  double acc[N][N];
+#pragma unroll
+  for (int x = 0; x < N; ++x)
+#pragma unroll
+    for (int y = 0; y < N; ++y) acc[x][y] = 0.0;
+  double ab0 = 0.0, ab1 = 0.0, arr = 0.0;
+  const long tiles = (rows + T - 1) / T;
+  for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long r = tile * T + t;
+    if (t < T) {
+      double* yrow = Ys + t * N * W;
+      if (r < rows) {
+        mp_id_regressor_normal_part<N, HAS_FTIP, LANES>(
+            M, Dmap, C, q, qd, qdd, rhs, r, sub, [&](int j, int col, double v) { yrow[j * W + col] = v; },
+            [&](int j, double v) { Rs[t * N + j] = v; });
+      } else {  // past the last row: zeros
+        for (int e = sub; e < N * W; e += LANES) yrow[e] = 0.0;
+        if (sub == 0)
+          for (int j = 0; j < N; ++j) Rs[t * N + j] = 0.0;
+      }
+    }
+    __syncthreads();
+    for (int row = 0; row < R; ++row) {
+      const double* y = Ys + row * W;
+      const double res = Rs[row];
+      if (WITH_A) {
+        double u[N], v[N];
+#pragma unroll
+        for (int x = 0; x < N; ++x) { u[x] = y[bi * N + x]; v[x] = y[bj * N + x]; }
+#pragma unroll
+        for (int x = 0; x < N; ++x)
+#pragma unroll
+          for (int z = 0; z < N; ++z) acc[x][z] += u[x] * v[z];
+      }
+      if (L < W) ab0 += y[L] * res;
+      if (L + 64 < W) ab1 += y[L + 64] * res;
+      if (L == 63) arr += res * res;
+    }
+    __syncthreads();
+  }
+  double* out = work + (long)blockIdx.x * mp_reg_normal_stride(N);
+  if (WITH_A && L < 55) {
+#pragma unroll
+    for (int x = 0; x < N; ++x)
+#pragma unroll
+      for (int z = 0; z < N; ++z) out[(bi * N + x) * W + bj * N + z] = acc[x][z];
+  }
+  if (L < W) out[W * W + L] = ab0;
+  if (L + 64 < W) out[W * W + L + 64] = ab1;
+  if (L == 63) out[W * W + W] = arr;
+}
+// The partials added in workgroup order (four interleaved sums, then combined: a fixed order, so repeat calls are bit-identical).
+// A entry (i, j) is read from the upper block that holds (i, j) or (j, i): A comes out exactly symmetric.
+template <int N>
+__global__ __launch_bounds__(256) void k_id_regressor_normal_reduce(const double* __restrict__ work, int groups, bool with_a,
+                                                                    double* __restrict__ A, double* __restrict__ b,
+                                                                    double* __restrict__ rr) {
+  constexpr int W = MP_REG_P * N;
+  const int e = (int)(blockIdx.x * 256 + threadIdx.x);
+  const int first = with_a ? 0 : W * W;
+  if (first + e >= W * W + W + 1) return;
+  const int o = first + e;
+  int src = o;
+  if (o < W * W) {
+    const int i = o / W, j = o % W;
+    src = (i / N <= j / N) ? o : j * W + i;
+  }
+  const long stride = mp_reg_normal_stride(N);
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+  int g = 0;
+  for (; g + 3 < groups; g += 4) {
+    s0 += work[(long)g * stride + src];
+    s1 += work[(long)(g + 1) * stride + src];
+    s2 += work[(long)(g + 2) * stride + src];
+    s3 += work[(long)(g + 3) * stride + src];
+  }
+  for (; g < groups; ++g) s0 += work[(long)g * stride + src];
+  const double v = (s0 + s1) + (s2 + s3);
+  if (o < W * W) A[o] = v;
+  else if (o < W * W + W) b[o - W * W] = v;
+  else rr[0] = v;
 }
 
 // one wave per block: the roll-out's LDS tile is per wave and nothing is shared between waves
@@ -724,6 +838,33 @@ hipError_t mpk_fd_traj_vjp(hipStream_t s, const MpModel<double>& M, const MpCall
                                     h, intRes, gp, gv, ga, work, gth0, gdth0, gtau);
     else hipLaunchKernelGGL((k_fd_traj_vjp<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt,
                             h, intRes, gp, gv, ga, work, gth0, gdth0, gtau);
+  })
+  return hipGetLastError();
+}
+
+hipError_t mpk_id_regressor(hipStream_t s, const MpModel<double>& M, const double* Dmap, const MpCall<double>& C, bool ftip,
+                            const double* q, const double* qd, const double* qdd, double* Y, double* tau_ext, long rows) {
+  if (rows <= 0) return hipSuccess;
+  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(M.n, {
+    if (ftip) hipLaunchKernelGGL((k_id_regressor<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, Dmap, C, q, qd, qdd, Y, tau_ext, rows);
+    else hipLaunchKernelGGL((k_id_regressor<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, Dmap, C, q, qd, qdd, Y, tau_ext, rows);
+  })
+  return hipGetLastError();
+}
+hipError_t mpk_id_regressor_normal(hipStream_t s, const MpModel<double>& M, const double* Dmap, const MpCall<double>& C, bool ftip,
+                                   const double* q, const double* qd, const double* qdd, const double* rhs, long rows, double* work,
+                                   double* A, double* b, double* rr) {
+  if (rows <= 0) return hipSuccess;
+  const unsigned G = (unsigned)mp_reg_normal_groups(rows);
+  const bool with_a = A != nullptr;
+  MP_DISPATCH_N(M.n, {
+    if (ftip && with_a) hipLaunchKernelGGL((k_id_regressor_normal<N, true, true>), dim3(G), dim3(64), 0, s, M, Dmap, C, q, qd, qdd, rhs, rows, work);
+    else if (ftip) hipLaunchKernelGGL((k_id_regressor_normal<N, true, false>), dim3(G), dim3(64), 0, s, M, Dmap, C, q, qd, qdd, rhs, rows, work);
+    else if (with_a) hipLaunchKernelGGL((k_id_regressor_normal<N, false, true>), dim3(G), dim3(64), 0, s, M, Dmap, C, q, qd, qdd, rhs, rows, work);
+    else hipLaunchKernelGGL((k_id_regressor_normal<N, false, false>), dim3(G), dim3(64), 0, s, M, Dmap, C, q, qd, qdd, rhs, rows, work);
+    const int W = MP_REG_P * N, outs = (with_a ? W * W : 0) + W + 1;
+    hipLaunchKernelGGL((k_id_regressor_normal_reduce<N>), dim3((outs + 255) / 256), dim3(256), 0, s, work, (int)G, with_a, A, b, rr);
   })
   return hipGetLastError();
 }

@@ -110,11 +110,37 @@ void compiled_fk(const MpModelT<double, CAP>& m, const double* q, double* T /*16
 void mp_compiled_fk(const MpModel<double>& m, const double* q, double* T) { compiled_fk<MP_MAX_DOF>(m, q, T); }
 void mp_compiled_fk(const MpBigModel<double>& m, const double* q, double* T) { compiled_fk<MP_BIG_DOF>(m, q, T); }
 
+// Inertial parameters of one link, CoM-frame convention -> link frame (the regressor's public convention, mp_regressor.h):
+// pi = [m, h, I] with h = m c, I about the CoM frame's origin, both in that frame; R, p = the CoM frame's pose in link frame i.
+//   m' = m,   h' = m p + R h,   I' = R I R^T + m (|p|^2 1 - p p^T) + 2 (p . R h) 1 - p (R h)^T - (R h) p^T
+// At h = 0 this is step 4 of compile_model below.  Linear in pi: D's column c is the map of the unit vector e_c.
+void mp_inertial_map(const double R[9], const double p[3], double D[100]) {
+  for (int c = 0; c < 10; ++c) {
+    double e[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    e[c] = 1.0;
+    const double m = e[0];
+    const double I[9] = {e[4], e[5], e[6], e[5], e[7], e[8], e[6], e[8], e[9]};
+    double u[3], RI[9], Io[9];
+    for (int r = 0; r < 3; ++r) u[r] = R[3 * r] * e[1] + R[3 * r + 1] * e[2] + R[3 * r + 2] * e[3];
+    for (int r = 0; r < 3; ++r)
+      for (int k = 0; k < 3; ++k) RI[3 * r + k] = R[3 * r] * I[k] + R[3 * r + 1] * I[3 + k] + R[3 * r + 2] * I[6 + k];
+    const double p2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2], pu = p[0] * u[0] + p[1] * u[1] + p[2] * u[2];
+    for (int r = 0; r < 3; ++r)
+      for (int k = 0; k < 3; ++k) {
+        const double rir = RI[3 * r] * R[3 * k] + RI[3 * r + 1] * R[3 * k + 1] + RI[3 * r + 2] * R[3 * k + 2];
+        const double one = r == k ? 1.0 : 0.0;
+        Io[3 * r + k] = rir + m * (p2 * one - p[r] * p[k]) + 2.0 * pu * one - p[r] * u[k] - u[r] * p[k];
+      }
+    const double o[10] = {m, m * p[0] + u[0], m * p[1] + u[1], m * p[2] + u[2], Io[0], Io[1], Io[2], Io[4], Io[5], Io[8]};
+    for (int a = 0; a < 10; ++a) D[10 * a + c] = o[a];
+  }
+}
+
 namespace {
 template <int CAP>
 int compile_model(int n, const double* S, const double* Mcom, const double* G, const double* M_ee,
                   const double* joint_limits, const double* torque_limits, MpModelT<double, CAP>* out, char* err,
-                  size_t errlen) {
+                  size_t errlen, double* pmap) {
   if (n < 1 || n > CAP) { fail(err, errlen, "dof %d outside 1..%g", n, (double)CAP); return 1; }
   std::memset(out, 0, sizeof(*out));
   out->n = n;
@@ -238,6 +264,7 @@ int compile_model(int n, const double* S, const double* Mcom, const double* G, c
     C.x = {Mc[0], Mc[4], Mc[8]}; C.y = {Mc[1], Mc[5], Mc[9]}; C.z = {Mc[2], Mc[6], Mc[10]}; C.o = {Mc[3], Mc[7], Mc[11]};
     double Rc[9], cp[3];
     rel(H[i], C, Rc, cp);
+    if (pmap) mp_inertial_map(Rc, cp, pmap + 100 * i);
     double Ic[9], Io[9];
     for (int r = 0; r < 3; ++r)
       for (int cc = 0; cc < 3; ++cc) Ic[3 * r + cc] = 0.5 * (Gi[r * 6 + cc] + Gi[cc * 6 + r]);
@@ -313,13 +340,13 @@ int compile_model(int n, const double* S, const double* Mcom, const double* G, c
 
 int mp_compile_model(int n, const double* S, const double* Mcom, const double* G, const double* M_ee,
                      const double* joint_limits, const double* torque_limits, MpModel<double>* out, char* err,
-                     size_t errlen) {
-  return compile_model<MP_MAX_DOF>(n, S, Mcom, G, M_ee, joint_limits, torque_limits, out, err, errlen);
+                     size_t errlen, double* inertial_map) {
+  return compile_model<MP_MAX_DOF>(n, S, Mcom, G, M_ee, joint_limits, torque_limits, out, err, errlen, inertial_map);
 }
 int mp_compile_model_big(int n, const double* S, const double* Mcom, const double* G, const double* M_ee,
                          const double* joint_limits, const double* torque_limits, MpBigModel<double>* out, char* err,
                          size_t errlen) {
-  return compile_model<MP_BIG_DOF>(n, S, Mcom, G, M_ee, joint_limits, torque_limits, out, err, errlen);
+  return compile_model<MP_BIG_DOF>(n, S, Mcom, G, M_ee, joint_limits, torque_limits, out, err, errlen, nullptr);
 }
 
 // per-call constants (gravity, tip wrench) seen from the frame link 1 is attached to

@@ -6,9 +6,14 @@
 #include "mp_model.h"
 
 // Returns 0 on success; otherwise a non-zero code and a message in `err`.  n <= MP_MAX_DOF / n <= MP_BIG_DOF.
+// inertial_map (may be null): n x 100 doubles, link i's map D_i of mp_inertial_map below.
 int mp_compile_model(int n, const double* S, const double* Mcom, const double* G, const double* M_ee,
                      const double* joint_limits, const double* torque_limits, MpModel<double>* out, char* err,
-                     size_t errlen);
+                     size_t errlen, double* inertial_map = nullptr);
+// D (10 x 10, row-major, [a][c] = d pi_link[a] / d pi[c]) of the link whose CoM frame has rotation R (row-major) and origin p in
+// its link frame: inertial parameters [m, hx, hy, hz, Ixx, Ixy, Ixz, Iyy, Iyz, Izz] in the CoM frame (h = m c, I about that
+// frame's origin) -> the same in the link frame (mp_regressor.h)
+void mp_inertial_map(const double R[9], const double p[3], double D[100]);
 int mp_compile_model_big(int n, const double* S, const double* Mcom, const double* G, const double* M_ee,
                          const double* joint_limits, const double* torque_limits, MpBigModel<double>* out, char* err,
                          size_t errlen);

@@ -219,6 +219,71 @@ class ManipulatorDynamics(SerialManipulator):
         inputs, (rows, n, n) for 2-D ones (one g / Ftip for all rows)."""
         return self._derivatives("dynamics.fwd_derivatives", "forward_dynamics_derivatives", thetalist, dthetalist, taulist, g, Ftip)
 
+    # ---- dynamics regressor and inertial-parameter identification (float64, n <= 8; csrc/mp_regressor.h)
+    # pi_i = [m, hx, hy, hz, Ixx, Ixy, Ixz, Iyy, Iyz, Izz] in link i's CoM frame at the home pose (Mlist_per_link[i]): h = m c with c
+    # the centre of mass from that frame's origin, I the inertia about that origin.  tau = Y pi + tau_ext (tau_ext: the tip wrench's
+    # share).
+    def inertial_parameters(self) -> np.ndarray:
+        """(n, 10) inertial parameters of the model as loaded: [m, 0, 0, 0, Ic entries] (Glist[i] = blockdiag(Ic, m 1))."""
+        model = self._derivative_model("inertial_parameters")
+        out = np.zeros((model.n, 10))
+        for i, G in enumerate(np.asarray(self.Glist, dtype=np.float64)):
+            Ic = 0.5 * (G[:3, :3] + G[:3, :3].T)
+            out[i] = [G[3, 3], 0.0, 0.0, 0.0, Ic[0, 0], Ic[0, 1], Ic[0, 2], Ic[1, 1], Ic[1, 2], Ic[2, 2]]
+        return out
+
+    def inverse_dynamics_regressor(self, thetalist, dthetalist, ddthetalist, g, Ftip=None):
+        """(Y, tau_ext) with tau = Y @ inertial_parameters().ravel() + tau_ext: (n, 10n) and (n,) for 1-D inputs, (rows, n, 10n) and
+        (rows, n) for 2-D ones (one g / Ftip for all rows).  Y[.., j, 10 k + c] = d tau_j / d pi_k[c]."""
+        model = self._derivative_model("inverse_dynamics_regressor")
+        one = np.ndim(thetalist) == 1
+        q, qd, qdd = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (thetalist, dthetalist, ddthetalist))
+        Y, te = execute_registered_kernel("dynamics.inverse_regressor", model, q, qd, qdd, g, Ftip)
+        return (Y[0], te[0]) if one else (Y, te)
+
+    def identify_inertial_parameters(self, thetalist, dthetalist, ddthetalist, taulist, g, Ftip=None, prior=None,
+                                     ridge: float = 1e-8) -> dict:
+        """Least-squares inertial parameters from (rows, n) samples of (q, qd, qdd, tau): the normal equations A = sum Y^T Y,
+        b = sum Y^T (tau - tau_ext) are reduced on the device without forming Y, then (A + ridge s 1) pi = b + ridge s prior is solved
+        on the host (float64, eigh), s = mean(diag(A)).  The ridge pulls the parameters that the data cannot identify (Y is
+        rank-deficient for every real arm: only base parameters are identifiable) towards `prior` (default inertial_parameters()).
+        Returns {"params" (n, 10), "A", "b", "rows", "rank" (eigenvalues of A above 1e-10 max), "residual_rms"}."""
+        model = self._derivative_model("identify_inertial_parameters")
+        q, qd, qdd, tau = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (thetalist, dthetalist, ddthetalist, taulist))
+        A, b, rr = execute_registered_kernel("dynamics.inverse_regressor_normal", model, q, qd, qdd, tau, g, Ftip)
+        w = 10 * model.n
+        p0 = (self.inertial_parameters() if prior is None else np.asarray(prior, dtype=np.float64)).reshape(w)
+        s = float(np.mean(np.diag(A))) or 1.0
+        lam, V = np.linalg.eigh(0.5 * (A + A.T) + ridge * s * np.eye(w))
+        pi = V @ ((V.T @ (b + ridge * s * p0)) / lam)
+        ev = np.linalg.eigvalsh(0.5 * (A + A.T))
+        rank = int(np.sum(ev > 1e-10 * max(float(ev.max()), 0.0))) if ev.size and ev.max() > 0 else 0
+        rows = q.shape[0]
+        res2 = max(rr - 2.0 * float(pi @ b) + float(pi @ A @ pi), 0.0)
+        return {"params": pi.reshape(model.n, 10), "A": A, "b": b, "rows": rows, "rank": rank,
+                "residual_rms": float(np.sqrt(res2 / max(rows * model.n, 1)))}
+
+    def with_inertial_parameters(self, params) -> "ManipulatorDynamics":
+        """A new ManipulatorDynamics with the inertial parameters `params` ((n, 10) or (10n,), this model's convention): per link
+        c = h / m, Ic = I - m (|c|^2 1 - c c^T), the CoM frame moved by c along its own axes, Glist = blockdiag(Ic, m 1)."""
+        model = self._derivative_model("with_inertial_parameters")
+        P = np.asarray(params, dtype=np.float64).reshape(model.n, 10)
+        Ml = np.array(self.Mlist_per_link, dtype=np.float64)
+        Gl = []
+        for i, (m, hx, hy, hz, Ixx, Ixy, Ixz, Iyy, Iyz, Izz) in enumerate(P):
+            if not m > 0.0:
+                raise ValueError(f"with_inertial_parameters: link {i} has mass {m}; masses must be positive")
+            c = np.array([hx, hy, hz]) / m
+            I = np.array([[Ixx, Ixy, Ixz], [Ixy, Iyy, Iyz], [Ixz, Iyz, Izz]])
+            G = np.zeros((6, 6))
+            G[:3, :3] = I - m * (np.dot(c, c) * np.eye(3) - np.outer(c, c))
+            G[3:, 3:] = m * np.eye(3)
+            Gl.append(G)
+            Ml[i, :3, 3] = Ml[i, :3, 3] + Ml[i, :3, :3] @ c
+        out = type(self)(self.M_list, self.omega_list, self.r_list, self.b_list, self.S_list, self.B_list, Gl, list(Ml))
+        out.joint_limits = self.joint_limits
+        return out
+
     def partial_derivative(self, i: int, j: int, k: int, thetalist, epsilon: float = 1e-6) -> float:
         """dM[i, j] / dtheta_k by the reference's central difference (dynamics/cache.py:39-52)."""
         q = np.asarray(thetalist, dtype=np.float64)

@@ -299,6 +299,14 @@ def _launch_fd_derivatives_cpu(model, q, qd, tau, g=None, Ftip=None):
     return _hip.cpu_fd_derivatives(model, q, qd, tau, g, Ftip)
 
 
+def _launch_id_regressor_cpu(model, q, qd, qdd, g=None, Ftip=None):
+    return _hip.cpu_id_regressor(model, q, qd, qdd, g, Ftip)
+
+
+def _launch_id_regressor_normal_cpu(model, q, qd, qdd, rhs, g=None, Ftip=None, want_A=True):
+    return _hip.cpu_id_regressor_normal(model, q, qd, qdd, rhs, g, Ftip, want_A)
+
+
 def _launch_fd_trajectory_vjp_cpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos=None, gvel=None, gacc=None,
                                   layout="batch_major"):
     if layout == "time_major":   # the CPU twin walks batch-major rows: (N, B, *) <-> (B, N, *) on the host
@@ -419,6 +427,14 @@ def _launch_fd_derivatives_gpu(model, q, qd, tau, g=None, Ftip=None):
     return get_context().fd_derivatives_host(model, q, qd, tau, g, Ftip)
 
 
+def _launch_id_regressor_gpu(model, q, qd, qdd, g=None, Ftip=None):
+    return get_context().id_regressor_host(model, q, qd, qdd, g, Ftip)
+
+
+def _launch_id_regressor_normal_gpu(model, q, qd, qdd, rhs, g=None, Ftip=None, want_A=True):
+    return get_context().id_regressor_normal_host(model, q, qd, qdd, rhs, g, Ftip, want_A)
+
+
 def _launch_fd_trajectory_vjp_gpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos=None, gvel=None, gacc=None,
                                   layout="batch_major"):
     return get_context().fd_trajectory_vjp_host(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos, gvel, gacc, layout=layout)
@@ -496,6 +512,11 @@ def _build_kernel_registry() -> KernelRegistry:
         # analytical derivatives (csrc/mp_deriv.h).  The forward one is "dynamics.fwd_derivatives": the registry's sorted name list is
         # pinned right after "dynamics.forward" by the unknown-name message test, and "dynamics.forward_*" would land there
         ("dynamics.inverse_derivatives", "mp_id_derivatives_host_f64", _launch_id_derivatives_gpu, _launch_id_derivatives_cpu),
+        # dynamics regressor and the normal equations of inertial-parameter identification (csrc/mp_regressor.h); both names sort
+        # after "dynamics.forward_trajectory"
+        ("dynamics.inverse_regressor", "mp_id_regressor_host_f64", _launch_id_regressor_gpu, _launch_id_regressor_cpu),
+        ("dynamics.inverse_regressor_normal", "mp_id_regressor_normal_host_f64", _launch_id_regressor_normal_gpu,
+         _launch_id_regressor_normal_cpu),
         ("dynamics.fwd_derivatives", "mp_fd_derivatives_host_f64", _launch_fd_derivatives_gpu, _launch_fd_derivatives_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
