@@ -372,10 +372,12 @@ int device_model(mp_ctx* ctx, const mp_model* model, const MpModel<float>** out)
   return MP_OK;
 }
 // a float32 call's constants + where its kernels find the float64 model.  Generic kernels only (the specialised programs carry
-// the literal).
-void make_call_f32(mp_ctx* ctx, const mp_model* model, const double* g, const double* Ftip, MpCall<float>* c) {
+// the literal); `generic_kernel`: the launch goes to a generic kernel even if the model is specialised (an entry that has no
+// specialised float32 program, mp_fk_jac_id_f32) - without the float64 model its ill-conditioned rows would be re-evaluated
+// with the float32 model's constants and differ from the same rows of the unspecialised model.
+void make_call_f32(mp_ctx* ctx, const mp_model* model, const double* g, const double* Ftip, MpCall<float>* c, bool generic_kernel = false) {
   make_call<float>(model, g, Ftip, c);
-  if (model->big || find_spec(ctx, model)) return;
+  if (model->big || (!generic_kernel && find_spec(ctx, model))) return;
   auto it = ctx->dev_models.find(model->uid);
   if (it == ctx->dev_models.end()) {
     const MpModel<float>* dm = nullptr;
@@ -546,11 +548,13 @@ mp_ctx::HardSlot* pick_rider(mp_ctx* ctx, hipFunction_t fn, const mp_ctx::HardSl
     if (hs.busy && &hs != self && hs.fn == fn && fn && (hs.nt != 0) == generated && (!best || hs.seq < best->seq)) best = &hs;
   return best;
 }
-template <typename T> void make_call_ctx(mp_ctx* ctx, const mp_model* model, const double* g, const double* Ftip, MpCall<T>* c);
-template <> void make_call_ctx<float>(mp_ctx* ctx, const mp_model* model, const double* g, const double* Ftip, MpCall<float>* c) {
-  make_call_f32(ctx, model, g, Ftip, c);
+template <typename T>
+void make_call_ctx(mp_ctx* ctx, const mp_model* model, const double* g, const double* Ftip, MpCall<T>* c, bool generic_kernel = false);
+template <>
+void make_call_ctx<float>(mp_ctx* ctx, const mp_model* model, const double* g, const double* Ftip, MpCall<float>* c, bool generic_kernel) {
+  make_call_f32(ctx, model, g, Ftip, c, generic_kernel);
 }
-template <> void make_call_ctx<double>(mp_ctx*, const mp_model* model, const double* g, const double* Ftip, MpCall<double>* c) {
+template <> void make_call_ctx<double>(mp_ctx*, const mp_model* model, const double* g, const double* Ftip, MpCall<double>* c, bool) {
   make_call<double>(model, g, Ftip, c);
 }
 
@@ -733,7 +737,7 @@ static int fkjid_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const 
   REQUIRE(aligned16(d_q) && aligned16(d_qd) && aligned16(d_qdd) && aligned16(d_T) && aligned16(d_J) && aligned16(d_tau),
           "%s: device pointers must be 16-byte aligned", fn);
   MpCall<T> c;
-  make_call_ctx<T>(ctx, model, g, Ftip, &c);
+  make_call_ctx<T>(ctx, model, g, Ftip, &c, /*generic_kernel=*/sizeof(T) == 4);   // (float32: no specialised program, see below)
   PROFILE_SCOPE(ctx, fn);
   if (model->big) return launch_big_fk_jac_id<T>(ctx, model, c, any_nonzero(Ftip), d_q, d_qd, d_qdd, d_T, d_J, d_tau, (long)rows);
   const int src = launch_fkjid_spec(ctx, model, c, any_nonzero(Ftip), d_q, d_qd, d_qdd, d_T, d_J, d_tau, (long)rows);
