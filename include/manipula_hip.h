@@ -65,6 +65,13 @@ int mp_ctx_synchronize(mp_ctx* ctx);  /* waits for every stream of the context *
  * that holds the stream can read pool memory with its own copies and kernels.)  The reference has no streams of its
  * own to expose (its launchers return finished host arrays, cuda_kernels/trajectory_kernels.py:1043-1081). */
 int mp_ctx_get_stream(mp_ctx* ctx, void** hip_stream);
+/* Stream order with a caller's stream (a hipStream_t through a void*; NULL = the device's null stream) WITHOUT handing the compute
+ * stream out, so parking is left as it is (unlike mp_ctx_get_stream): each records a HIP event on one stream and makes the other
+ * wait for it.  _wait_for_stream: the compute stream waits for what is enqueued on hip_stream so far; _stream_wait_for_ctx:
+ * hip_stream waits for what is enqueued on the compute stream so far (parked passes are run first).  A framework that hands device
+ * tensors to the device-pointer entry points joins both ways around them (manipulapy_amd/autograd.py). */
+int mp_ctx_wait_for_stream(mp_ctx* ctx, void* hip_stream);
+int mp_ctx_stream_wait_for_ctx(mp_ctx* ctx, void* hip_stream);
 /* name, CU count, total HBM bytes — replaces get_gpu_properties(), cuda_kernels/registry.py:335-356 */
 int mp_ctx_properties(mp_ctx* ctx, char* name, size_t name_len, int* compute_units, uint64_t* hbm_bytes);
 /* Launch a 1-block probe kernel that writes its lane ids and check the result on the host.
@@ -255,6 +262,18 @@ int mp_id_derivatives_f64(mp_ctx* ctx, const mp_model* model, const double* d_q,
 int mp_fd_derivatives_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_tau,
                           int64_t rows, const double* g, const double* Ftip, double* d_qdd, double* d_dqdd_dq, double* d_dqdd_dqd,
                           double* d_Minv);
+/* Vector-Jacobian products of the same two functions (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED above that), by reverse
+ * mode through the Newton-Euler recursion (csrc/mp_adjoint.h): O(n) per row, no Jacobian formed.  All arrays (rows,n).
+ *   inverse dynamics at (q, qd, qdd), cotangent gtau:  gq = dtau_dq^T gtau, gqd = dtau_dqd^T gtau, gqdd = M gtau (may be NULL)
+ *   forward dynamics at (q, qd, tau), cotangent gqdd:  qdd (may be NULL), gtau = M^-1 gqdd (may be NULL), gq = dqdd_dq^T gqdd,
+ *                                                      gqd = dqdd_dqd^T gqdd
+ * Derivatives of the unclipped torque; a row with a non-finite input or cotangent comes back NaN in every output of that row only.
+ * The device forms are asynchronous (no synchronisation, no allocation: they may be captured into a launch graph); the _host forms
+ * take their device memory from the context's pool; the _cpu twins are listed with the others below. */
+int mp_id_vjp_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd, const double* d_gtau,
+                  int64_t rows, const double* g, const double* Ftip, double* d_gq, double* d_gqd, double* d_gqdd);
+int mp_fd_vjp_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_tau, const double* d_gqdd,
+                  int64_t rows, const double* g, const double* Ftip, double* d_qdd, double* d_gq, double* d_gqd, double* d_gtau);
 
 /* forward_dynamics_trajectory for B independent trajectories (planning/trajectory_dynamics.py:382-423,
  * :580-708; replaces forward_dynamics_kernel, cuda_kernels/trajectory_kernels.py:604-705): semi-implicit
@@ -378,6 +397,10 @@ int mp_id_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double*
 int mp_fd_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* tau,
                                int64_t rows, const double* g, const double* Ftip, double* qdd, double* dqdd_dq, double* dqdd_dqd,
                                double* Minv);
+int mp_id_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd, const double* gtau,
+                       int64_t rows, const double* g, const double* Ftip, double* gq, double* gqd, double* gqdd);
+int mp_fd_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* tau, const double* gqdd,
+                       int64_t rows, const double* g, const double* Ftip, double* qdd, double* gq, double* gqd, double* gtau);
 int mp_fd_trajectory_host_f32(mp_ctx* ctx, const mp_model* model, const float* theta0, const float* dtheta0,
                               const float* taumat, const float* Ftipmat, int64_t B, int64_t N, const double* g,
                               double dt, int intRes, float* pos, float* vel, float* acc);
@@ -436,6 +459,10 @@ int mp_id_derivatives_cpu_f64(const mp_model* model, const double* q, const doub
 int mp_fd_derivatives_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* tau, int64_t rows,
                               const double* g, const double* Ftip, double* qdd, double* dqdd_dq, double* dqdd_dqd, double* Minv,
                               int nthreads);
+int mp_id_vjp_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, const double* gtau, int64_t rows,
+                      const double* g, const double* Ftip, double* gq, double* gqd, double* gqdd, int nthreads);
+int mp_fd_vjp_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* tau, const double* gqdd, int64_t rows,
+                      const double* g, const double* Ftip, double* qdd, double* gq, double* gqd, double* gtau, int nthreads);
 int mp_fd_trajectory_cpu_f32(const mp_model* model, const float* theta0, const float* dtheta0, const float* taumat,
                              const float* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, float* pos,
                              float* vel, float* acc, int nthreads);

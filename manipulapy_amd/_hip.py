@@ -49,6 +49,8 @@ SIGNATURES = {
     "mp_ctx_destroy": (ctypes.c_int, [_vp]),
     "mp_ctx_synchronize": (ctypes.c_int, [_vp]),
     "mp_ctx_get_stream": (ctypes.c_int, [_vp, ctypes.POINTER(_vp)]),
+    "mp_ctx_wait_for_stream": (ctypes.c_int, [_vp, _vp]),
+    "mp_ctx_stream_wait_for_ctx": (ctypes.c_int, [_vp, _vp]),
     "mp_ctx_properties": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint64)]),
     "mp_selftest": (ctypes.c_int, [_vp]),
     "mp_stream_bandwidth": (ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
@@ -106,6 +108,12 @@ SIGNATURES = {
     "mp_fd_derivatives_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
     "mp_id_derivatives_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "mp_fd_derivatives_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_id_vjp_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp, _vp]),
+    "mp_fd_vjp_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
+    "mp_id_vjp_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_fd_vjp_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_id_vjp_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_fd_vjp_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_id_regressor_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp]),
     "mp_id_regressor_normal_workspace_bytes": (ctypes.c_int64, [_vp, _i64]),
     "mp_id_regressor_normal_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
@@ -534,6 +542,14 @@ class HipContext:
         _check(self.lib.mp_ctx_get_stream(self.handle, ctypes.byref(p)))
         return p.value or 0
 
+    def wait_for_stream(self, hip_stream: int) -> None:
+        """The compute stream waits for what is enqueued on `hip_stream` (an integer hipStream_t; 0 = the null stream) so far."""
+        _check(self.lib.mp_ctx_wait_for_stream(self.handle, _vp(int(hip_stream)) if hip_stream else None))
+
+    def stream_wait_for_ctx(self, hip_stream: int) -> None:
+        """`hip_stream` waits for what is enqueued on the compute stream so far (unlike `stream`, parking is left as it is)."""
+        _check(self.lib.mp_ctx_stream_wait_for_ctx(self.handle, _vp(int(hip_stream)) if hip_stream else None))
+
     def capture(self) -> _Capture:
         """``with ctx.capture() as cap: <device-pointer launches>`` -> ``cap.graph`` (HipGraph)."""
         return _Capture(self)
@@ -590,6 +606,18 @@ class HipContext:
         _check(self.lib.mp_fd_derivatives_f64(self.handle, model.handle, _p(d_q), _p(d_qd), _p(d_tau), int(rows),
                                               _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _p(d_qdd),
                                               _p(d_dqdd_dq), _p(d_dqdd_dqd), _p(d_Minv)))
+
+    def id_vjp(self, model, d_q, d_qd, d_qdd, d_gtau, rows, d_gq, d_gqd, d_gqdd=None, g=None, Ftip=None):
+        """Inverse-dynamics vector-Jacobian product on device buffers (float64; csrc/mp_adjoint.h); asynchronous (capturable)."""
+        _check(self.lib.mp_id_vjp_f64(self.handle, model.handle, _p(d_q), _p(d_qd), _p(d_qdd), _p(d_gtau), int(rows),
+                                      _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _p(d_gq), _p(d_gqd),
+                                      _p(d_gqdd)))
+
+    def fd_vjp(self, model, d_q, d_qd, d_tau, d_gqdd, rows, d_gq, d_gqd, d_qdd=None, d_gtau=None, g=None, Ftip=None):
+        """Forward-dynamics vector-Jacobian product on device buffers (float64; csrc/mp_adjoint.h); asynchronous (capturable)."""
+        _check(self.lib.mp_fd_vjp_f64(self.handle, model.handle, _p(d_q), _p(d_qd), _p(d_tau), _p(d_gqdd), int(rows),
+                                      _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _p(d_qdd), _p(d_gq),
+                                      _p(d_gqd), _p(d_gtau)))
 
     def cartesian_trajectory(self, d_Xstart, d_Xend, B, N, Tf, method, d_pos, d_vel, d_acc, d_orient):
         _check(self.lib.mp_cartesian_trajectory_f32(self.handle, _p(d_Xstart), _p(d_Xend), int(B), int(N), float(Tf), int(method),
@@ -763,6 +791,14 @@ class HipContext:
     def fd_derivatives_host(self, model: HipModel, q, qd, tau, g=None, Ftip=None):
         """(qdd, dqdd_dq, dqdd_dqd, Minv) of (rows, n) host rows: [row, i, j] = d qdd_i / d x_j; Minv = dqdd_dtau."""
         return _derivatives(self.lib.mp_fd_derivatives_host_f64, (self.handle,), model, q, qd, tau, g, Ftip, "tau")
+
+    def id_vjp_host(self, model: HipModel, q, qd, qdd, gtau, g=None, Ftip=None):
+        """(gq, gqd, gqdd = M gtau) of (rows, n) host rows and cotangents gtau."""
+        return _vjp(self.lib.mp_id_vjp_host_f64, (self.handle,), model, q, qd, qdd, gtau, g, Ftip, False)
+
+    def fd_vjp_host(self, model: HipModel, q, qd, tau, gqdd, g=None, Ftip=None):
+        """(qdd, gq, gqd, gtau = M^-1 gqdd) of (rows, n) host rows and cotangents gqdd."""
+        return _vjp(self.lib.mp_fd_vjp_host_f64, (self.handle,), model, q, qd, tau, gqdd, g, Ftip, True)
 
     def fd_trajectory_host(self, model: HipModel, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64,
                            layout: str = "batch_major", device_layout: str | None = None, out=None):
@@ -1041,6 +1077,33 @@ def cpu_id_derivatives(model: "HipModel", q, qd, qdd, g=None, Ftip=None, nthread
 def cpu_fd_derivatives(model: "HipModel", q, qd, tau, g=None, Ftip=None, nthreads: int = 0):
     """CPU twin of HipContext.fd_derivatives_host: (qdd, dqdd_dq, dqdd_dqd, Minv)."""
     return _derivatives(load_library().mp_fd_derivatives_cpu_f64, (), model, q, qd, tau, g, Ftip, "tau", nthreads)
+
+
+def _vjp(fn, lead, model, q, qd, x, cot, g, Ftip, fd, nthreads=None):
+    q = _as_c(q, np.float64, name="q")
+    if q.ndim != 2 or q.shape[1] != model.n:
+        raise ValueError(f"q must be (rows, {model.n}); got {q.shape}")
+    qd = _as_c(qd, np.float64, q.shape, "qd")
+    x = _as_c(x, np.float64, q.shape, "tau" if fd else "qdd")
+    cot = _as_c(cot, np.float64, q.shape, "gqdd" if fd else "gtau")
+    rows = q.shape[0]
+    out = [np.empty_like(q) for _ in range(4 if fd else 3)]
+    args = list(lead) + [model.handle, _dptr(q), _dptr(qd), _dptr(x), _dptr(cot), rows, _dptr(_vec_or_none(g, 3, "g")),
+                         _dptr(_vec_or_none(Ftip, 6, "Ftip"))] + [_dptr(o) for o in out]
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return tuple(out)
+
+
+def cpu_id_vjp(model: "HipModel", q, qd, qdd, gtau, g=None, Ftip=None, nthreads: int = 0):
+    """CPU twin of HipContext.id_vjp_host: (gq, gqd, gqdd)."""
+    return _vjp(load_library().mp_id_vjp_cpu_f64, (), model, q, qd, qdd, gtau, g, Ftip, False, nthreads)
+
+
+def cpu_fd_vjp(model: "HipModel", q, qd, tau, gqdd, g=None, Ftip=None, nthreads: int = 0):
+    """CPU twin of HipContext.fd_vjp_host: (qdd, gq, gqd, gtau)."""
+    return _vjp(load_library().mp_fd_vjp_cpu_f64, (), model, q, qd, tau, gqdd, g, Ftip, True, nthreads)
 
 
 def _pd_regulation_args(model, theta0, theta_des, Kp, Kd, g, steps):

@@ -13,6 +13,16 @@ the reverse pass through its sub-steps ("dynamics.forward_trajectory_vjp", csrc/
 requires grad is refused.  inverse_dynamics_parameters is tau = Y(q, qd, qdd) pi + tau_ext ("dynamics.inverse_regressor"), whose
 backward pass is sum Y^T g_tau from the normal-equations operation ("dynamics.inverse_regressor_normal", no A, rhs = g_tau): Y is
 never formed.  Imported on demand only - never from the package's __init__ (torch stays optional).
+
+Device tensors.  inverse_dynamics / forward_dynamics also take ROCm float64 tensors (q, qd and qdd / tau all on the device of the
+library's context, MANIPULAPY_HIP_DEVICE, default 0).  Placing the tensors there is the opt-in: they run on the GPU whatever
+set_backend says.  The forward value comes from the float64 inverse / forward dynamics kernels (unclipped tau; qdd), the backward
+pass from the reverse-mode vector-Jacobian kernels ("dynamics.inverse_vjp" / "dynamics.fwd_vjp", csrc/mp_adjoint.h): only the
+inputs are saved, no Jacobian is formed, and no row or gradient leaves the device.  Every launch is ordered on
+torch.cuda.current_stream() (the library's compute stream waits for it before the launch, and it waits for the compute stream after).
+float32 device tensors, a mix of host and device tensors and a device other than the context's are refused (TypeError / ValueError).
+g and Ftip are per-call constants: a device tensor among them is copied to the host (3 / 6 numbers, a synchronising copy).
+inverse_dynamics_parameters and forward_dynamics_trajectory take CPU tensors only.
 """
 from __future__ import annotations
 
@@ -53,15 +63,103 @@ def _vjp(gy: torch.Tensor, J: np.ndarray, one: bool) -> torch.Tensor:
     return out[0] if one else out
 
 
+def _on_device(*ts) -> bool:
+    return any(isinstance(t, torch.Tensor) and t.device.type == "cuda" for t in ts)
+
+
+def _device_rows(ts, names):
+    """(context, contiguous 16-byte-aligned detached tensors) of ROCm float64 state tensors on the library context's device."""
+    from .registry import get_context
+
+    hctx = get_context()
+    shape = ts[0].shape
+    out = []
+    for t, name in zip(ts, names):
+        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+            dev = t.device if isinstance(t, torch.Tensor) else "host"
+            raise ValueError(f"{name}: mixed devices - every state tensor must be on the GPU when one is (got {dev})")
+        if t.dtype != torch.float64:
+            raise TypeError(f"{name}: device tensors must be float64, got {t.dtype}")
+        if t.device.index != hctx.device_id:
+            raise ValueError(f"{name}: on {t.device}, but the library's context is on cuda:{hctx.device_id} "
+                             f"(set {_device_env()} to choose it)")
+        if t.shape != shape:
+            raise ValueError(f"{name}: shape {tuple(t.shape)} differs from {tuple(shape)}")
+        t = t.detach().contiguous()
+        if t.data_ptr() % 16:
+            t = t.clone()
+        out.append(t)
+    return hctx, out
+
+
+def _device_env():
+    from .registry import HIP_DEVICE_ENV
+
+    return HIP_DEVICE_ENV
+
+
+def _device_launch(hctx, launch):
+    """`launch()` ordered on torch's current stream: the compute stream waits for it before, and it waits for the compute stream
+    after - so the inputs are ready when the kernel starts and torch's caching allocator cannot hand an input or output to a later
+    op before the kernel is done with it."""
+    s = torch.cuda.current_stream().cuda_stream
+    hctx.wait_for_stream(s)
+    launch()
+    hctx.stream_wait_for_ctx(s)
+
+
+def _device_forward(fn_ctx, kind, dyn, q, qd, x, g, Ftip):
+    model = dyn._derivative_model(f"autograd.{kind}_dynamics")
+    hctx, (a, b, c) = _device_rows((q, qd, x), ("q", "qd", "qdd" if kind == "inverse" else "tau"))
+    n = model.n
+    if a.shape[-1] != n or a.dim() not in (1, 2):
+        raise ValueError(f"q must be ({n},) or (rows, {n}), got {tuple(a.shape)}")
+    rows = a.numel() // n
+    out = torch.empty_like(a)
+    if kind == "inverse":
+        _device_launch(hctx, lambda: hctx.id_trajectory(model, a.data_ptr(), b.data_ptr(), c.data_ptr(), rows, out.data_ptr(), g, Ftip,
+                                                        dtype=np.float64))
+    else:
+        _device_launch(hctx, lambda: hctx.forward_dynamics(model, a.data_ptr(), b.data_ptr(), c.data_ptr(), rows, out.data_ptr(), g,
+                                                           Ftip, dtype=np.float64))
+    fn_ctx.save_for_backward(q, qd, x)
+    fn_ctx.device, fn_ctx.model, fn_ctx.consts = True, model, (g, Ftip)
+    return out
+
+
+def _device_backward(fn_ctx, kind, gy):
+    q, qd, x = fn_ctx.saved_tensors
+    g, Ftip = fn_ctx.consts
+    model = fn_ctx.model
+    hctx, (a, b, c, cot) = _device_rows((q, qd, x, gy.to(torch.float64)), ("q", "qd", "x", "cotangent"))
+    rows = a.numel() // model.n
+    gq, gqd = torch.empty_like(a), torch.empty_like(a)
+    gx = torch.empty_like(a) if fn_ctx.needs_input_grad[3] else None
+    p = (lambda t: None if t is None else t.data_ptr())  # noqa: E731
+    if kind == "inverse":
+        launch = lambda: hctx.id_vjp(model, a.data_ptr(), b.data_ptr(), c.data_ptr(), cot.data_ptr(), rows, gq.data_ptr(),  # noqa: E731
+                                     gqd.data_ptr(), p(gx), g, Ftip)
+    else:
+        launch = lambda: hctx.fd_vjp(model, a.data_ptr(), b.data_ptr(), c.data_ptr(), cot.data_ptr(), rows, gq.data_ptr(),  # noqa: E731
+                                     gqd.data_ptr(), None, p(gx), g, Ftip)
+    _device_launch(hctx, launch)
+    return None, gq, gqd, gx, None, None
+
+
 class _InverseDynamics(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gtau):
+        if ctx.device:
+            return _device_backward(ctx, "inverse", gtau)
         dq, dqd, M = ctx.jac
         return None, _vjp(gtau, dq, ctx.one), _vjp(gtau, dqd, ctx.one), _vjp(gtau, M, ctx.one), None, None
 
     @staticmethod
     def forward(ctx, dyn, q, qd, qdd, g, Ftip):
+        if _on_device(q, qd, qdd):
+            return _device_forward(ctx, "inverse", dyn, q, qd, qdd, g, Ftip)
+        ctx.device = False
         one = q.dim() == 1
         a, b, c = _rows(q, "q"), _rows(qd, "qd"), _rows(qdd, "qdd")
         tau, dq, dqd, M = _derivatives("dynamics.inverse_derivatives", dyn, a, b, c, g, Ftip)
@@ -74,11 +172,16 @@ class _ForwardDynamics(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gqdd):
+        if ctx.device:
+            return _device_backward(ctx, "forward", gqdd)
         dq, dqd, Minv = ctx.jac
         return None, _vjp(gqdd, dq, ctx.one), _vjp(gqdd, dqd, ctx.one), _vjp(gqdd, Minv, ctx.one), None, None
 
     @staticmethod
     def forward(ctx, dyn, q, qd, tau, g, Ftip):
+        if _on_device(q, qd, tau):
+            return _device_forward(ctx, "forward", dyn, q, qd, tau, g, Ftip)
+        ctx.device = False
         one = q.dim() == 1
         a, b, c = _rows(q, "q"), _rows(qd, "qd"), _rows(tau, "tau")
         qdd, dq, dqd, Minv = _derivatives("dynamics.fwd_derivatives", dyn, a, b, c, g, Ftip)
@@ -93,7 +196,8 @@ def _as_tensor(x):
 
 def inverse_dynamics(dyn, q, qd, qdd, g=None, Ftip=None) -> torch.Tensor:
     """tau = ID(q, qd, qdd, g, Ftip) of a ManipulatorDynamics (with Mlist_per_link, n <= 8), differentiable in q, qd, qdd.
-    (n,) inputs give (n,), (rows, n) inputs (rows, n); one g / Ftip for every row."""
+    (n,) inputs give (n,), (rows, n) inputs (rows, n); one g / Ftip for every row.  CPU float64 tensors, or ROCm float64 tensors on
+    the library context's device (computed there, module docstring); a device g / Ftip is copied to the host."""
     return _InverseDynamics.apply(dyn, _as_tensor(q), _as_tensor(qd), _as_tensor(qdd), _const(g, "g"), _const(Ftip, "Ftip"))
 
 

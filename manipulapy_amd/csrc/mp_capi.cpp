@@ -916,6 +916,29 @@ static int deriv_impl(const char* fn, bool fd, mp_ctx* ctx, const mp_model* mode
   return MP_OK;
 }
 
+// vector-Jacobian products (mp_adjoint.h): float64, unrolled models only.  x = qdd (ID) / tau (FD), cot = the cotangent;
+// ID: o1 = gq, o2 = gqd, o3 = gqdd (may be null), y unused;  FD: y = qdd (may be null), o1 = gq, o2 = gqd, o3 = gtau (may be null)
+static int vjp_impl(const char* fn, bool fd, mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_x,
+                    const double* d_cot, int64_t rows, const double* g, const double* Ftip, double* d_y, double* d_o1, double* d_o2,
+                    double* d_o3) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (rows == 0) return MP_OK;
+  REQUIRE(d_q && d_qd && d_x && d_cot && d_o1 && d_o2, "%s: null device pointer", fn);
+  REQUIRE(aligned16(d_q) && aligned16(d_qd) && aligned16(d_x) && aligned16(d_cot) && aligned16(d_o1) && aligned16(d_o2) &&
+              (!d_y || aligned16(d_y)) && (!d_o3 || aligned16(d_o3)),
+          "%s: device pointers must be 16-byte aligned", fn);
+  MpCall<double> c;
+  make_call<double>(model, g, Ftip, &c);
+  const bool ftip = any_nonzero(Ftip);
+  PROFILE_SCOPE(ctx, fn);
+  if (fd) HIP_TRY(mpk_fd_vjp(ctx->compute, model->d, c, ftip, d_q, d_qd, d_x, d_cot, d_y, d_o1, d_o2, d_o3, (long)rows));
+  else HIP_TRY(mpk_id_vjp(ctx->compute, model->d, c, ftip, d_q, d_qd, d_x, d_cot, d_o1, d_o2, d_o3, (long)rows));
+  return MP_OK;
+}
+
 // dynamics regressor (mp_regressor.h): float64, unrolled models only; the kernels read the inertial-parameter map from the
 // model's device copy.  Y's row holds n x 10n values, A 10n x 10n.
 constexpr int MP_REG_P = 10;
@@ -1286,6 +1309,29 @@ int mp_ctx_get_stream(mp_ctx* ctx, void** hip_stream) {
   ctx->stream_exported = true;  // sticky: every later float32 launch enqueues its float64 pass at once, whoever owns its arrays
   *hip_stream = (void*)ctx->compute;
   return MP_OK;
+}
+
+// Stream order between the compute stream and a caller's stream through a fresh HIP event (recorded on `from`, waited on by `to`,
+// released at once: the wait keeps what it needs).  Neither hands the compute stream out, so parking stays as it was.
+static int join_streams(const char* fn, mp_ctx* ctx, hipStream_t from, hipStream_t to) {
+  hipEvent_t ev = nullptr;
+  HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  hipError_t e = hipEventRecord(ev, from);
+  if (e == hipSuccess) e = hipStreamWaitEvent(to, ev, 0);
+  (void)hipEventDestroy(ev);
+  if (e != hipSuccess) return hip_err(e, fn);
+  (void)ctx;
+  return MP_OK;
+}
+int mp_ctx_wait_for_stream(mp_ctx* ctx, void* hip_stream) {
+  REQUIRE(ctx, "mp_ctx_wait_for_stream: null context");
+  CTX_ENTER(ctx);
+  return join_streams("mp_ctx_wait_for_stream", ctx, (hipStream_t)hip_stream, ctx->compute);
+}
+int mp_ctx_stream_wait_for_ctx(mp_ctx* ctx, void* hip_stream) {
+  REQUIRE(ctx, "mp_ctx_stream_wait_for_ctx: null context");
+  CTX_ENTER(ctx);  // (parked float64 passes run first: hip_stream then waits for their torques too)
+  return join_streams("mp_ctx_stream_wait_for_ctx", ctx, ctx->compute, (hipStream_t)hip_stream);
 }
 
 int mp_ctx_synchronize(mp_ctx* ctx) {
@@ -2198,6 +2244,14 @@ int mp_fd_derivatives_f64(mp_ctx* ctx, const mp_model* model, const double* d_q,
                           double* d_Minv) {
   return deriv_impl("mp_fd_derivatives_f64", true, ctx, model, d_q, d_qd, d_tau, rows, g, Ftip, d_qdd, d_dqdd_dq, d_dqdd_dqd, d_Minv);
 }
+int mp_id_vjp_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd, const double* d_gtau,
+                  int64_t rows, const double* g, const double* Ftip, double* d_gq, double* d_gqd, double* d_gqdd) {
+  return vjp_impl("mp_id_vjp_f64", false, ctx, model, d_q, d_qd, d_qdd, d_gtau, rows, g, Ftip, nullptr, d_gq, d_gqd, d_gqdd);
+}
+int mp_fd_vjp_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_tau, const double* d_gqdd,
+                  int64_t rows, const double* g, const double* Ftip, double* d_qdd, double* d_gq, double* d_gqd, double* d_gtau) {
+  return vjp_impl("mp_fd_vjp_f64", true, ctx, model, d_q, d_qd, d_tau, d_gqdd, rows, g, Ftip, d_qdd, d_gq, d_gqd, d_gtau);
+}
 int mp_id_regressor_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd, int64_t rows,
                         const double* g, const double* Ftip, double* d_Y, double* d_tau_ext) {
   return regressor_impl("mp_id_regressor_f64", ctx, model, d_q, d_qd, d_qdd, rows, g, Ftip, d_Y, d_tau_ext);
@@ -2363,6 +2417,49 @@ int mp_fd_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double*
                                int64_t rows, const double* g, const double* Ftip, double* qdd, double* dqdd_dq, double* dqdd_dqd,
                                double* Minv) {
   return deriv_host_impl("mp_fd_derivatives_host_f64", true, ctx, model, q, qd, tau, rows, g, Ftip, qdd, dqdd_dq, dqdd_dqd, Minv);
+}
+
+static int vjp_host_impl(const char* fn, bool fd, mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* x,
+                         const double* cot, int64_t rows, const double* g, const double* Ftip, double* y, double* o1, double* o2,
+                         double* o3) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (rows == 0) return MP_OK;
+  REQUIRE(q && qd && x && cot && o1 && o2, "%s: null host pointer", fn);
+  const size_t vb = (size_t)rows * (size_t)model->d.n * sizeof(double);
+  Scratch sc(ctx);
+  void *dq, *dqd, *dx, *dc, *dy = nullptr, *d1, *d2, *d3 = nullptr;
+  if (int rc = sc.get(vb, &dq)) return rc;
+  if (int rc = sc.get(vb, &dqd)) return rc;
+  if (int rc = sc.get(vb, &dx)) return rc;
+  if (int rc = sc.get(vb, &dc)) return rc;
+  if (y) if (int rc = sc.get(vb, &dy)) return rc;
+  if (int rc = sc.get(vb, &d1)) return rc;
+  if (int rc = sc.get(vb, &d2)) return rc;
+  if (o3) if (int rc = sc.get(vb, &d3)) return rc;
+  H2D(dq, q, vb);
+  H2D(dqd, qd, vb);
+  H2D(dx, x, vb);
+  H2D(dc, cot, vb);
+  if (int rc = vjp_impl(fn, fd, ctx, model, (double*)dq, (double*)dqd, (double*)dx, (double*)dc, rows, g, Ftip, (double*)dy, (double*)d1,
+                        (double*)d2, (double*)d3))
+    return rc;
+  if (y) D2H(y, dy, vb);
+  D2H(o1, d1, vb);
+  D2H(o2, d2, vb);
+  if (o3) D2H(o3, d3, vb);
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+int mp_id_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd, const double* gtau,
+                       int64_t rows, const double* g, const double* Ftip, double* gq, double* gqd, double* gqdd) {
+  return vjp_host_impl("mp_id_vjp_host_f64", false, ctx, model, q, qd, qdd, gtau, rows, g, Ftip, nullptr, gq, gqd, gqdd);
+}
+int mp_fd_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* tau, const double* gqdd,
+                       int64_t rows, const double* g, const double* Ftip, double* qdd, double* gq, double* gqd, double* gtau) {
+  return vjp_host_impl("mp_fd_vjp_host_f64", true, ctx, model, q, qd, tau, gqdd, rows, g, Ftip, qdd, gq, gqd, gtau);
 }
 
 int mp_id_regressor_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd, int64_t rows,

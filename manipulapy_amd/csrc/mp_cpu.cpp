@@ -19,6 +19,7 @@
 #include "../../include/manipula_hip.h"
 #include "mp_core.h"
 #include "mp_deriv.h"
+#include "mp_adjoint.h"
 #include "mp_dyn.h"
 #include "mp_ik.h"
 #include "mp_handles.h"
@@ -449,6 +450,45 @@ int mp_fd_derivatives_cpu_f64(const mp_model* model, const double* q, const doub
                               const double* g, const double* Ftip, double* qdd, double* dqdd_dq, double* dqdd_dqd, double* Minv,
                               int nthreads) {
   return deriv_cpu("mp_fd_derivatives_cpu_f64", true, model, q, qd, tau, rows, g, Ftip, qdd, dqdd_dq, dqdd_dqd, Minv, nthreads);
+}
+// vector-Jacobian products (mp_adjoint.h): the kernels' per-row code over host rows.  x = qdd (ID) / tau (FD), cot = the cotangent;
+// ID: o1 = gq, o2 = gqd, o3 = gqdd (may be null), y unused;  FD: y = qdd (may be null), o1 = gq, o2 = gqd, o3 = gtau (may be null)
+static int vjp_cpu(const char* fn, bool fd, const mp_model* model, const double* q, const double* qd, const double* x, const double* cot,
+                   int64_t rows, const double* g, const double* Ftip, double* y, double* o1, double* o2, double* o3, int nthreads) {
+  char msg[192];
+  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
+  if (model->big) {
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (rows < 0) { std::snprintf(msg, sizeof msg, "%s: negative row count", fn); return fail(msg); }
+  if (rows == 0) return MP_OK;
+  if (!q || !qd || !x || !cot || !o1 || !o2) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
+  const MpModel<double>& M = model->d;
+  const MpCall<double> C = make_call<double>(model, g, Ftip);
+  const bool ftip = any_nonzero(Ftip);
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(rows, 128, nthreads, [&](int64_t lo, int64_t hi) {
+      for (int64_t r = lo; r < hi; ++r) {
+        if (fd) {
+          if (ftip) mp_fd_vjp_row<N, true>(M, C, q, qd, x, cot, y, o1, o2, o3, (long)r);
+          else mp_fd_vjp_row<N, false>(M, C, q, qd, x, cot, y, o1, o2, o3, (long)r);
+        } else {
+          if (ftip) mp_id_vjp_row<N, true>(M, C, q, qd, x, cot, o1, o2, o3, (long)r);
+          else mp_id_vjp_row<N, false>(M, C, q, qd, x, cot, o1, o2, o3, (long)r);
+        }
+      }
+    });
+  })
+  return MP_OK;
+}
+int mp_id_vjp_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, const double* gtau, int64_t rows,
+                      const double* g, const double* Ftip, double* gq, double* gqd, double* gqdd, int nthreads) {
+  return vjp_cpu("mp_id_vjp_cpu_f64", false, model, q, qd, qdd, gtau, rows, g, Ftip, nullptr, gq, gqd, gqdd, nthreads);
+}
+int mp_fd_vjp_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* tau, const double* gqdd, int64_t rows,
+                      const double* g, const double* Ftip, double* qdd, double* gq, double* gqd, double* gtau, int nthreads) {
+  return vjp_cpu("mp_fd_vjp_cpu_f64", true, model, q, qd, tau, gqdd, rows, g, Ftip, qdd, gq, gqd, gtau, nthreads);
 }
 // dynamics regressor (mp_regressor.h): the kernels' per-row code over host rows
 static int regressor_cpu_check(const char* fn, const mp_model* model, int64_t rows) {

@@ -12,6 +12,7 @@
 
 #include "mp_bodies.h"
 #include "mp_deriv.h"
+#include "mp_adjoint.h"
 #include "mp_dyn.h"
 #include "mp_ik.h"
 #include "mp_kernels.h"
@@ -262,6 +263,26 @@ __global__ __launch_bounds__(kDerivBlock) void k_fd_deriv(const MpModel<double> 
   const long r = (long)blockIdx.x * kDerivBlock + threadIdx.x;
   if (r >= rows) return;
   mp_fd_deriv_row<N, HAS_FTIP>(M, C, q, qd, tau, qdd, dq, dqd, Minv, r);
+}
+
+// vector-Jacobian products by reverse mode (mp_adjoint.h): one lane per row, the block size of the derivative kernels
+template <int N, bool HAS_FTIP>
+__global__ __launch_bounds__(kDerivBlock) void k_id_vjp(const MpModel<double> M, const MpCall<double> C, const double* __restrict__ q,
+                                                        const double* __restrict__ qd, const double* __restrict__ qdd,
+                                                        const double* __restrict__ gtau, double* __restrict__ gq, double* __restrict__ gqd,
+                                                        double* __restrict__ gqdd, long rows) {
+  const long r = (long)blockIdx.x * kDerivBlock + threadIdx.x;
+  if (r >= rows) return;
+  mp_id_vjp_row<N, HAS_FTIP>(M, C, q, qd, qdd, gtau, gq, gqd, gqdd, r);
+}
+template <int N, bool HAS_FTIP>
+__global__ __launch_bounds__(kDerivBlock) void k_fd_vjp(const MpModel<double> M, const MpCall<double> C, const double* __restrict__ q,
+                                                        const double* __restrict__ qd, const double* __restrict__ tau,
+                                                        const double* __restrict__ gqdd, double* __restrict__ qdd, double* __restrict__ gq,
+                                                        double* __restrict__ gqd, double* __restrict__ gtau, long rows) {
+  const long r = (long)blockIdx.x * kDerivBlock + threadIdx.x;
+  if (r >= rows) return;
+  mp_fd_vjp_row<N, HAS_FTIP>(M, C, q, qd, tau, gqdd, qdd, gq, gqd, gtau, r);
 }
 
 // reverse mode through the roll-out (mp_rollout_vjp.h): one lane = one trajectory on the time-major layout, so that the 64 lanes of a
@@ -824,6 +845,27 @@ hipError_t mpk_fd_deriv(hipStream_t s, const MpModel<double>& M, const MpCall<do
   MP_DISPATCH_N(M.n, {
     if (ftip) hipLaunchKernelGGL((k_fd_deriv<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, qdd, dq, dqd, Minv, rows);
     else hipLaunchKernelGGL((k_fd_deriv<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, qdd, dq, dqd, Minv, rows);
+  })
+  return hipGetLastError();
+}
+
+hipError_t mpk_id_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
+                      const double* qdd, const double* gtau, double* gq, double* gqd, double* gqdd, long rows) {
+  if (rows <= 0) return hipSuccess;
+  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(M.n, {
+    if (ftip) hipLaunchKernelGGL((k_id_vjp<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, qdd, gtau, gq, gqd, gqdd, rows);
+    else hipLaunchKernelGGL((k_id_vjp<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, qdd, gtau, gq, gqd, gqdd, rows);
+  })
+  return hipGetLastError();
+}
+hipError_t mpk_fd_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
+                      const double* tau, const double* gqdd, double* qdd, double* gq, double* gqd, double* gtau, long rows) {
+  if (rows <= 0) return hipSuccess;
+  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(M.n, {
+    if (ftip) hipLaunchKernelGGL((k_fd_vjp<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, gqdd, qdd, gq, gqd, gtau, rows);
+    else hipLaunchKernelGGL((k_fd_vjp<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, gqdd, qdd, gq, gqd, gtau, rows);
   })
   return hipGetLastError();
 }

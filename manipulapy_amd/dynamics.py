@@ -219,6 +219,25 @@ class ManipulatorDynamics(SerialManipulator):
         inputs, (rows, n, n) for 2-D ones (one g / Ftip for all rows)."""
         return self._derivatives("dynamics.fwd_derivatives", "forward_dynamics_derivatives", thetalist, dthetalist, taulist, g, Ftip)
 
+    # ---- vector-Jacobian products (float64, n <= 8; csrc/mp_adjoint.h): reverse mode, no Jacobian formed
+    def _vjp(self, op, what, q, qd, x, cot, g, Ftip):
+        model = self._derivative_model(what)
+        one = np.ndim(q) == 1
+        q2, qd2, x2, c2 = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (q, qd, x, cot))
+        out = execute_registered_kernel(op, model, q2, qd2, x2, c2, g, Ftip)
+        return tuple(o[0] for o in out) if one else tuple(out)
+
+    def inverse_dynamics_vjp(self, thetalist, dthetalist, ddthetalist, gtau, g, Ftip):
+        """(gq, gqd, gqdd) = (dtau_dq^T gtau, dtau_dqd^T gtau, M gtau) of tau = inverse_dynamics(...) for the cotangent gtau: (n,)
+        each for 1-D inputs, (rows, n) for 2-D ones (one g / Ftip for all rows).  Derivatives of the unclipped torque."""
+        return self._vjp("dynamics.inverse_vjp", "inverse_dynamics_vjp", thetalist, dthetalist, ddthetalist, gtau, g, Ftip)
+
+    def forward_dynamics_vjp(self, thetalist, dthetalist, taulist, gqdd, g, Ftip):
+        """(gq, gqd, gtau) = (dqdd_dq^T gqdd, dqdd_dqd^T gqdd, M^-1 gqdd) of qdd = forward_dynamics(...) for the cotangent gqdd;
+        shapes as inverse_dynamics_vjp."""
+        _, gq, gqd, gtau = self._vjp("dynamics.fwd_vjp", "forward_dynamics_vjp", thetalist, dthetalist, taulist, gqdd, g, Ftip)
+        return gq, gqd, gtau
+
     # ---- dynamics regressor and inertial-parameter identification (float64, n <= 8; csrc/mp_regressor.h)
     # pi_i = [m, hx, hy, hz, Ixx, Ixy, Ixz, Iyy, Iyz, Izz] in link i's CoM frame at the home pose (Mlist_per_link[i]): h = m c with c
     # the centre of mass from that frame's origin, I the inertia about that origin.  tau = Y pi + tau_ext (tau_ext: the tip wrench's

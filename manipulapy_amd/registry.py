@@ -299,6 +299,14 @@ def _launch_fd_derivatives_cpu(model, q, qd, tau, g=None, Ftip=None):
     return _hip.cpu_fd_derivatives(model, q, qd, tau, g, Ftip)
 
 
+def _launch_id_vjp_cpu(model, q, qd, qdd, gtau, g=None, Ftip=None):
+    return _hip.cpu_id_vjp(model, q, qd, qdd, gtau, g, Ftip)
+
+
+def _launch_fd_vjp_cpu(model, q, qd, tau, gqdd, g=None, Ftip=None):
+    return _hip.cpu_fd_vjp(model, q, qd, tau, gqdd, g, Ftip)
+
+
 def _launch_id_regressor_cpu(model, q, qd, qdd, g=None, Ftip=None):
     return _hip.cpu_id_regressor(model, q, qd, qdd, g, Ftip)
 
@@ -427,6 +435,14 @@ def _launch_fd_derivatives_gpu(model, q, qd, tau, g=None, Ftip=None):
     return get_context().fd_derivatives_host(model, q, qd, tau, g, Ftip)
 
 
+def _launch_id_vjp_gpu(model, q, qd, qdd, gtau, g=None, Ftip=None):
+    return get_context().id_vjp_host(model, q, qd, qdd, gtau, g, Ftip)
+
+
+def _launch_fd_vjp_gpu(model, q, qd, tau, gqdd, g=None, Ftip=None):
+    return get_context().fd_vjp_host(model, q, qd, tau, gqdd, g, Ftip)
+
+
 def _launch_id_regressor_gpu(model, q, qd, qdd, g=None, Ftip=None):
     return get_context().id_regressor_host(model, q, qd, qdd, g, Ftip)
 
@@ -518,6 +534,9 @@ def _build_kernel_registry() -> KernelRegistry:
         ("dynamics.inverse_regressor_normal", "mp_id_regressor_normal_host_f64", _launch_id_regressor_normal_gpu,
          _launch_id_regressor_normal_cpu),
         ("dynamics.fwd_derivatives", "mp_fd_derivatives_host_f64", _launch_fd_derivatives_gpu, _launch_fd_derivatives_cpu),
+        # vector-Jacobian products by reverse mode (csrc/mp_adjoint.h); both names sort after "dynamics.forward_trajectory"
+        ("dynamics.inverse_vjp", "mp_id_vjp_host_f64", _launch_id_vjp_gpu, _launch_id_vjp_cpu),
+        ("dynamics.fwd_vjp", "mp_fd_vjp_host_f64", _launch_fd_vjp_gpu, _launch_fd_vjp_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):
