@@ -275,6 +275,18 @@ int mp_id_vjp_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const d
 int mp_fd_vjp_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_tau, const double* d_gqdd,
                   int64_t rows, const double* g, const double* Ftip, double* d_qdd, double* d_gq, double* d_gqd, double* d_gtau);
 
+/* Vector-Jacobian products of forward kinematics and the Jacobian (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED above that), by
+ * reverse mode through the compiled chain (csrc/mp_kin_vjp.h): O(n) per row, no 4x4xn or 6xnxn tensor formed.
+ *   frame 0 = space, 1 = body (anything else is refused).  q (rows,n); cotangents gT (rows,4,4) and gJ (rows,6,n), either may be NULL
+ *   (= 0); outputs T (rows,4,4), J (rows,6,n, in `frame`) and gq = d<gT, T> / dq + d<gJ, J> / dq (rows,n), each may be NULL, at least
+ *   one required.  The cotangents are read only for gq; the bottom row of gT does not contribute.  With no cotangents this is FK plus
+ *   the Jacobian in either frame.
+ * A row with a non-finite q or cotangent comes back NaN in every output of that row only.  The device form is asynchronous (no
+ * synchronisation, no allocation: it may be captured into a launch graph); the _host form takes its device memory from the context's
+ * pool; the _cpu twin is listed with the others below. */
+int mp_fk_jac_vjp_f64(mp_ctx* ctx, const mp_model* model, int frame, const double* d_q, const double* d_gT, const double* d_gJ,
+                      int64_t rows, double* d_T, double* d_J, double* d_gq);
+
 /* forward_dynamics_trajectory for B independent trajectories (planning/trajectory_dynamics.py:382-423,
  * :580-708; replaces forward_dynamics_kernel, cuda_kernels/trajectory_kernels.py:604-705): semi-implicit
  * Euler, intRes sub-steps of dt/intRes, positions clipped to the joint limits after every sub-step, row 0 =
@@ -401,6 +413,8 @@ int mp_id_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, cons
                        int64_t rows, const double* g, const double* Ftip, double* gq, double* gqd, double* gqdd);
 int mp_fd_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* tau, const double* gqdd,
                        int64_t rows, const double* g, const double* Ftip, double* qdd, double* gq, double* gqd, double* gtau);
+int mp_fk_jac_vjp_host_f64(mp_ctx* ctx, const mp_model* model, int frame, const double* q, const double* gT, const double* gJ,
+                           int64_t rows, double* T, double* J, double* gq);
 int mp_fd_trajectory_host_f32(mp_ctx* ctx, const mp_model* model, const float* theta0, const float* dtheta0,
                               const float* taumat, const float* Ftipmat, int64_t B, int64_t N, const double* g,
                               double dt, int intRes, float* pos, float* vel, float* acc);
@@ -463,6 +477,8 @@ int mp_id_vjp_cpu_f64(const mp_model* model, const double* q, const double* qd, 
                       const double* g, const double* Ftip, double* gq, double* gqd, double* gqdd, int nthreads);
 int mp_fd_vjp_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* tau, const double* gqdd, int64_t rows,
                       const double* g, const double* Ftip, double* qdd, double* gq, double* gqd, double* gtau, int nthreads);
+int mp_fk_jac_vjp_cpu_f64(const mp_model* model, int frame, const double* q, const double* gT, const double* gJ, int64_t rows,
+                          double* T, double* J, double* gq, int nthreads);
 int mp_fd_trajectory_cpu_f32(const mp_model* model, const float* theta0, const float* dtheta0, const float* taumat,
                              const float* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, float* pos,
                              float* vel, float* acc, int nthreads);

@@ -114,6 +114,9 @@ SIGNATURES = {
     "mp_fd_vjp_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "mp_id_vjp_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_fd_vjp_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_fk_jac_vjp_f64": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "mp_fk_jac_vjp_host_f64": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp]),
+    "mp_fk_jac_vjp_cpu_f64": (ctypes.c_int, [_vp, ctypes.c_int, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_id_regressor_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp]),
     "mp_id_regressor_normal_workspace_bytes": (ctypes.c_int64, [_vp, _i64]),
     "mp_id_regressor_normal_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
@@ -619,6 +622,12 @@ class HipContext:
                                       _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _p(d_qdd), _p(d_gq),
                                       _p(d_gqd), _p(d_gtau)))
 
+    def fk_jac_vjp(self, model, frame, d_q, d_gT, d_gJ, rows, d_T=None, d_J=None, d_gq=None):
+        """Reverse mode through FK + Jacobian on device buffers (float64; csrc/mp_kin_vjp.h): frame "space" / "body"; the cotangents
+        d_gT (rows,4,4) / d_gJ (rows,6,n) may be None (= 0), every output may be None (at least one given); asynchronous (capturable)."""
+        _check(self.lib.mp_fk_jac_vjp_f64(self.handle, model.handle, _frame_code(frame), _p(d_q), _p(d_gT), _p(d_gJ), int(rows), _p(d_T),
+                                          _p(d_J), _p(d_gq)))
+
     def cartesian_trajectory(self, d_Xstart, d_Xend, B, N, Tf, method, d_pos, d_vel, d_acc, d_orient):
         _check(self.lib.mp_cartesian_trajectory_f32(self.handle, _p(d_Xstart), _p(d_Xend), int(B), int(N), float(Tf), int(method),
                                                     _p(d_pos), _p(d_vel), _p(d_acc), _p(d_orient)))
@@ -799,6 +808,11 @@ class HipContext:
     def fd_vjp_host(self, model: HipModel, q, qd, tau, gqdd, g=None, Ftip=None):
         """(qdd, gq, gqd, gtau = M^-1 gqdd) of (rows, n) host rows and cotangents gqdd."""
         return _vjp(self.lib.mp_fd_vjp_host_f64, (self.handle,), model, q, qd, tau, gqdd, g, Ftip, True)
+
+    def fk_jac_vjp_host(self, model: HipModel, q, gT=None, gJ=None, frame="space", want_T=False, want_J=False, want_gq=True):
+        """(T (rows,4,4), J (rows,6,n) in `frame`, gq (rows,n)) of (rows, n) host rows and cotangents gT (rows,4,4) / gJ (rows,6,n)
+        (None = 0); an output not asked for is None."""
+        return _kin_vjp(self.lib.mp_fk_jac_vjp_host_f64, (self.handle,), model, frame, q, gT, gJ, want_T, want_J, want_gq)
 
     def fd_trajectory_host(self, model: HipModel, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64,
                            layout: str = "batch_major", device_layout: str | None = None, out=None):
@@ -1104,6 +1118,37 @@ def cpu_id_vjp(model: "HipModel", q, qd, qdd, gtau, g=None, Ftip=None, nthreads:
 def cpu_fd_vjp(model: "HipModel", q, qd, tau, gqdd, g=None, Ftip=None, nthreads: int = 0):
     """CPU twin of HipContext.fd_vjp_host: (qdd, gq, gqd, gtau)."""
     return _vjp(load_library().mp_fd_vjp_cpu_f64, (), model, q, qd, tau, gqdd, g, Ftip, True, nthreads)
+
+
+def _frame_code(frame) -> int:
+    if frame in ("space", 0):
+        return 0
+    if frame in ("body", 1):
+        return 1
+    raise ValueError(f"frame must be 'space' or 'body', got {frame!r}")
+
+
+def _kin_vjp(fn, lead, model, frame, q, gT, gJ, want_T, want_J, want_gq, nthreads=None):
+    code = _frame_code(frame)
+    q = _as_c(q, np.float64, name="q")
+    if q.ndim != 2 or q.shape[1] != model.n:
+        raise ValueError(f"q must be (rows, {model.n}); got {q.shape}")
+    rows, n = q.shape
+    gT = None if gT is None else _as_c(gT, np.float64, (rows, 4, 4), "gT")
+    gJ = None if gJ is None else _as_c(gJ, np.float64, (rows, 6, n), "gJ")
+    T = np.empty((rows, 4, 4)) if want_T else None
+    J = np.empty((rows, 6, n)) if want_J else None
+    gq = np.empty((rows, n)) if want_gq else None
+    args = list(lead) + [model.handle, code, _dptr(q), _dptr(gT), _dptr(gJ), rows, _dptr(T), _dptr(J), _dptr(gq)]
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return T, J, gq
+
+
+def cpu_fk_jac_vjp(model: "HipModel", q, gT=None, gJ=None, frame="space", want_T=False, want_J=False, want_gq=True, nthreads: int = 0):
+    """CPU twin of HipContext.fk_jac_vjp_host: (T, J, gq), None where not asked for."""
+    return _kin_vjp(load_library().mp_fk_jac_vjp_cpu_f64, (), model, frame, q, gT, gJ, want_T, want_J, want_gq, nthreads)
 
 
 def _pd_regulation_args(model, theta0, theta_des, Kp, Kd, g, steps):

@@ -23,6 +23,16 @@ torch.cuda.current_stream() (the library's compute stream waits for it before th
 float32 device tensors, a mix of host and device tensors and a device other than the context's are refused (TypeError / ValueError).
 g and Ftip are per-call constants: a device tensor among them is copied to the host (3 / 6 numbers, a synchronising copy).
 inverse_dynamics_parameters and forward_dynamics_trajectory take CPU tensors only.
+
+Kinematics.  fk_jacobian(sm, q, frame) returns (T, J) = (SerialManipulator.forward_kinematics(q), .jacobian(q, frame)) of a chain of
+at most 8 joints, differentiable in q; forward_kinematics / jacobian are its two halves.  The forward value and the backward pass are
+one registered operation ("kinematics.fk_jacobian_vjp", csrc/mp_kin_vjp.h): the backward pass takes both cotangents in one launch
+(a cotangent torch does not provide is not read), O(n) per row, no Jacobian of T or J formed.  CPU float64 tensors and ROCm float64
+tensors, with the same rules and the same stream order as the dynamics above; only q is saved.  A truncated q and frame="body" on a
+model whose B_list is not Ad(M^-1) S_list are refused (no gradient there).
+
+    T, J = mpa.fk_jacobian(sm, q, "body")          # q: (n,) or (rows, n)
+    w = torch.sqrt(torch.det(J @ J.transpose(-1, -2)))
 """
 from __future__ import annotations
 
@@ -31,7 +41,8 @@ import torch
 
 from .registry import execute_registered_kernel
 
-__all__ = ["inverse_dynamics", "forward_dynamics", "forward_dynamics_trajectory", "inverse_dynamics_parameters"]
+__all__ = ["inverse_dynamics", "forward_dynamics", "forward_dynamics_trajectory", "inverse_dynamics_parameters", "fk_jacobian",
+           "forward_kinematics", "jacobian"]
 
 
 def _const(v, name):
@@ -270,3 +281,67 @@ def inverse_dynamics_parameters(dyn, params, q, qd, qdd, g=None, Ftip=None) -> t
                              "(use inverse_dynamics for gradients with respect to the state)")
     return _InverseDynamicsParameters.apply(dyn, _as_tensor(params), _as_tensor(q), _as_tensor(qd), _as_tensor(qdd), _const(g, "g"),
                                             _const(Ftip, "Ftip"))
+
+
+class _FkJacobian(torch.autograd.Function):
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gT, gJ):
+        if not ctx.needs_input_grad[1] or (gT is None and gJ is None):
+            return None, None, None
+        (q,) = ctx.saved_tensors
+        model, frame = ctx.model, ctx.frame
+        if ctx.device:
+            hctx, (a,) = _device_rows((q,), ("q",))
+            cot = [None if c is None else _device_rows((c.to(torch.float64),), (name,))[1][0] for c, name in ((gT, "gT"), (gJ, "gJ"))]
+            gq = torch.empty_like(a)
+            p = (lambda t: None if t is None else t.data_ptr())  # noqa: E731
+            _device_launch(hctx, lambda: hctx.fk_jac_vjp(model, frame, a.data_ptr(), p(cot[0]), p(cot[1]), a.numel() // model.n,
+                                                         None, None, gq.data_ptr()))
+            return None, gq, None
+        rows = q.numel() // model.n
+        cT, cJ = (None if c is None else np.ascontiguousarray(c.detach().cpu().numpy(), dtype=np.float64).reshape(rows, *tail)
+                  for c, tail in ((gT, (4, 4)), (gJ, (6, model.n))))
+        _, _, gq = execute_registered_kernel("kinematics.fk_jacobian_vjp", model, _rows(q, "q"), cT, cJ, frame)
+        return None, torch.from_numpy(gq.reshape(q.shape)), None
+
+    @staticmethod
+    def forward(ctx, sm, q, frame):
+        model = sm._gradient_model(q.shape[-1] if q.dim() else 0, frame, "autograd.fk_jacobian")
+        n = model.n
+        if q.dim() not in (1, 2):
+            raise ValueError(f"q must be ({n},) or (rows, {n}), got {tuple(q.shape)}")
+        ctx.set_materialize_grads(False)
+        ctx.model, ctx.frame = model, frame
+        lead = tuple(q.shape[:-1])
+        if _on_device(q):
+            hctx, (a,) = _device_rows((q,), ("q",))
+            T = a.new_empty(lead + (4, 4))
+            J = a.new_empty(lead + (6, n))
+            _device_launch(hctx, lambda: hctx.fk_jac_vjp(model, frame, a.data_ptr(), None, None, a.numel() // n, T.data_ptr(),
+                                                         J.data_ptr(), None))
+            ctx.device = True
+        else:
+            T, J, _ = execute_registered_kernel("kinematics.fk_jacobian_vjp", model, _rows(q, "q"), None, None, frame, want_T=True,
+                                                want_J=True, want_gq=False)
+            T, J = torch.from_numpy(T.reshape(lead + (4, 4))), torch.from_numpy(J.reshape(lead + (6, n)))
+            ctx.device = False
+        ctx.save_for_backward(q)
+        return T, J
+
+
+def fk_jacobian(sm, q, frame: str = "space"):
+    """(T, J): the end-effector pose (4, 4) and the Jacobian (6, n) in `frame` of a SerialManipulator (or ManipulatorDynamics) with at
+    most 8 joints, differentiable in q; (rows, 4, 4) / (rows, 6, n) for (rows, n) joint values.  CPU float64 tensors, or ROCm float64
+    tensors on the library context's device (computed there, module docstring)."""
+    return _FkJacobian.apply(sm, _as_tensor(q), frame)
+
+
+def forward_kinematics(sm, q, frame: str = "space") -> torch.Tensor:
+    """T of fk_jacobian: SerialManipulator.forward_kinematics(q, frame), differentiable in q."""
+    return fk_jacobian(sm, q, frame)[0]
+
+
+def jacobian(sm, q, frame: str = "space") -> torch.Tensor:
+    """J of fk_jacobian: SerialManipulator.jacobian(q, frame), differentiable in q."""
+    return fk_jacobian(sm, q, frame)[1]

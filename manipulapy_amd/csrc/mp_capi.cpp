@@ -939,6 +939,24 @@ static int vjp_impl(const char* fn, bool fd, mp_ctx* ctx, const mp_model* model,
   return MP_OK;
 }
 
+// reverse mode through FK + Jacobian (mp_kin_vjp.h): float64, unrolled models only; frame 0 = space, 1 = body
+static int kin_vjp_impl(const char* fn, mp_ctx* ctx, const mp_model* model, int frame, const double* d_q, const double* d_gT,
+                        const double* d_gJ, int64_t rows, double* d_T, double* d_J, double* d_gq) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(frame == 0 || frame == 1, "%s: frame must be 0 (space) or 1 (body), got %d", fn, frame);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (rows == 0) return MP_OK;
+  REQUIRE(d_q, "%s: null device pointer", fn);
+  REQUIRE(d_T || d_J || d_gq, "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_q) && aligned16(d_gT) && aligned16(d_gJ) && aligned16(d_T) && aligned16(d_J) && aligned16(d_gq),
+          "%s: device pointers must be 16-byte aligned", fn);
+  PROFILE_SCOPE(ctx, fn);
+  HIP_TRY(mpk_fk_jac_vjp(ctx->compute, model->d, frame, d_q, d_gT, d_gJ, d_T, d_J, d_gq, (long)rows));
+  return MP_OK;
+}
+
 // dynamics regressor (mp_regressor.h): float64, unrolled models only; the kernels read the inertial-parameter map from the
 // model's device copy.  Y's row holds n x 10n values, A 10n x 10n.
 constexpr int MP_REG_P = 10;
@@ -2252,6 +2270,10 @@ int mp_fd_vjp_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const d
                   int64_t rows, const double* g, const double* Ftip, double* d_qdd, double* d_gq, double* d_gqd, double* d_gtau) {
   return vjp_impl("mp_fd_vjp_f64", true, ctx, model, d_q, d_qd, d_tau, d_gqdd, rows, g, Ftip, d_qdd, d_gq, d_gqd, d_gtau);
 }
+int mp_fk_jac_vjp_f64(mp_ctx* ctx, const mp_model* model, int frame, const double* d_q, const double* d_gT, const double* d_gJ,
+                      int64_t rows, double* d_T, double* d_J, double* d_gq) {
+  return kin_vjp_impl("mp_fk_jac_vjp_f64", ctx, model, frame, d_q, d_gT, d_gJ, rows, d_T, d_J, d_gq);
+}
 int mp_id_regressor_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd, int64_t rows,
                         const double* g, const double* Ftip, double* d_Y, double* d_tau_ext) {
   return regressor_impl("mp_id_regressor_f64", ctx, model, d_q, d_qd, d_qdd, rows, g, Ftip, d_Y, d_tau_ext);
@@ -2460,6 +2482,38 @@ int mp_id_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, cons
 int mp_fd_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* tau, const double* gqdd,
                        int64_t rows, const double* g, const double* Ftip, double* qdd, double* gq, double* gqd, double* gtau) {
   return vjp_host_impl("mp_fd_vjp_host_f64", true, ctx, model, q, qd, tau, gqdd, rows, g, Ftip, qdd, gq, gqd, gtau);
+}
+
+int mp_fk_jac_vjp_host_f64(mp_ctx* ctx, const mp_model* model, int frame, const double* q, const double* gT, const double* gJ,
+                           int64_t rows, double* T, double* J, double* gq) {
+  const char* fn = "mp_fk_jac_vjp_host_f64";
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(frame == 0 || frame == 1, "%s: frame must be 0 (space) or 1 (body), got %d", fn, frame);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (rows == 0) return MP_OK;
+  REQUIRE(q, "%s: null host pointer", fn);
+  REQUIRE(T || J || gq, "%s: at least one output is required", fn);
+  const size_t vb = (size_t)rows * (size_t)model->d.n * sizeof(double), tb = (size_t)rows * 16 * sizeof(double);
+  Scratch sc(ctx);
+  void *dq, *dgT = nullptr, *dgJ = nullptr, *dT = nullptr, *dJ = nullptr, *dgq = nullptr;
+  if (int rc = sc.get(vb, &dq)) return rc;
+  if (gq && gT) if (int rc = sc.get(tb, &dgT)) return rc;
+  if (gq && gJ) if (int rc = sc.get(6 * vb, &dgJ)) return rc;
+  if (T) if (int rc = sc.get(tb, &dT)) return rc;
+  if (J) if (int rc = sc.get(6 * vb, &dJ)) return rc;
+  if (gq) if (int rc = sc.get(vb, &dgq)) return rc;
+  H2D(dq, q, vb);
+  if (dgT) H2D(dgT, gT, tb);
+  if (dgJ) H2D(dgJ, gJ, 6 * vb);
+  if (int rc = kin_vjp_impl(fn, ctx, model, frame, (double*)dq, (double*)dgT, (double*)dgJ, rows, (double*)dT, (double*)dJ, (double*)dgq))
+    return rc;
+  if (T) D2H(T, dT, tb);
+  if (J) D2H(J, dJ, 6 * vb);
+  if (gq) D2H(gq, dgq, vb);
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
 }
 
 int mp_id_regressor_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd, int64_t rows,

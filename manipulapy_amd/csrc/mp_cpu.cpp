@@ -20,6 +20,7 @@
 #include "mp_core.h"
 #include "mp_deriv.h"
 #include "mp_adjoint.h"
+#include "mp_kin_vjp.h"
 #include "mp_dyn.h"
 #include "mp_ik.h"
 #include "mp_handles.h"
@@ -489,6 +490,35 @@ int mp_id_vjp_cpu_f64(const mp_model* model, const double* q, const double* qd, 
 int mp_fd_vjp_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* tau, const double* gqdd, int64_t rows,
                       const double* g, const double* Ftip, double* qdd, double* gq, double* gqd, double* gtau, int nthreads) {
   return vjp_cpu("mp_fd_vjp_cpu_f64", true, model, q, qd, tau, gqdd, rows, g, Ftip, qdd, gq, gqd, gtau, nthreads);
+}
+// reverse mode through FK + Jacobian (mp_kin_vjp.h): the kernel's per-row code over host rows; frame 0 = space, 1 = body
+int mp_fk_jac_vjp_cpu_f64(const mp_model* model, int frame, const double* q, const double* gT, const double* gJ, int64_t rows,
+                          double* T, double* J, double* gq, int nthreads) {
+  const char* fn = "mp_fk_jac_vjp_cpu_f64";
+  char msg[192];
+  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
+  if (model->big) {
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (frame != 0 && frame != 1) {
+    std::snprintf(msg, sizeof msg, "%s: frame must be 0 (space) or 1 (body), got %d", fn, frame);
+    return fail(msg);
+  }
+  if (rows < 0) { std::snprintf(msg, sizeof msg, "%s: negative row count", fn); return fail(msg); }
+  if (rows == 0) return MP_OK;
+  if (!q) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
+  if (!T && !J && !gq) { std::snprintf(msg, sizeof msg, "%s: at least one output is required", fn); return fail(msg); }
+  const MpModel<double>& M = model->d;
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(rows, 256, nthreads, [&](int64_t lo, int64_t hi) {
+      for (int64_t r = lo; r < hi; ++r) {
+        if (frame == 0) mp_fk_jac_vjp_row<double, N, 0>(M, q, gT, gJ, T, J, gq, (long)r);
+        else mp_fk_jac_vjp_row<double, N, 1>(M, q, gT, gJ, T, J, gq, (long)r);
+      }
+    });
+  })
+  return MP_OK;
 }
 // dynamics regressor (mp_regressor.h): the kernels' per-row code over host rows
 static int regressor_cpu_check(const char* fn, const mp_model* model, int64_t rows) {

@@ -45,6 +45,10 @@ hipError_t mpk_id_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<doub
                       const double* qdd, const double* gtau, double* gq, double* gqd, double* gqdd, long rows);
 hipError_t mpk_fd_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
                       const double* tau, const double* gqdd, double* qdd, double* gq, double* gqd, double* gtau, long rows);
+// reverse mode through FK + Jacobian (csrc/mp_kin_vjp.h), float64, 1..MP_MAX_DOF joints; frame 0 = space, 1 = body; gT / gJ (inputs)
+// and Tout / Jout / gq (outputs) may be null
+hipError_t mpk_fk_jac_vjp(hipStream_t s, const MpModel<double>& M, int frame, const double* q, const double* gT, const double* gJ,
+                         double* Tout, double* Jout, double* gq, long rows);
 // reverse mode through the roll-out (csrc/mp_rollout_vjp.h) on the time-major layout: taumat / Ftipmat / gp / gv / ga / gtau (Nt, B, *),
 // theta0 / dtheta0 / gth0 / gdth0 (B, n); Ftipmat and the cotangents may be null; `work` holds (B Nt + B intRes) 2n doubles
 // dynamics regressor (csrc/mp_regressor.h), float64, 1..MP_MAX_DOF joints; Dmap = the model's n x 100 inertial-parameter map in

@@ -13,6 +13,7 @@
 #include "mp_bodies.h"
 #include "mp_deriv.h"
 #include "mp_adjoint.h"
+#include "mp_kin_vjp.h"
 #include "mp_dyn.h"
 #include "mp_ik.h"
 #include "mp_kernels.h"
@@ -283,6 +284,130 @@ __global__ __launch_bounds__(kDerivBlock) void k_fd_vjp(const MpModel<double> M,
   const long r = (long)blockIdx.x * kDerivBlock + threadIdx.x;
   if (r >= rows) return;
   mp_fd_vjp_row<N, HAS_FTIP>(M, C, q, qd, tau, gqdd, qdd, gq, gqd, gtau, r);
+}
+
+// ------------------------------------------------------- reverse mode through FK + Jacobian (float64, mp_kin_vjp.h)
+// The mirror of mp_wave_store_flat for loads.  A lane that reads its own long cotangent row (gJ: 288 B at n = 6, 384 B at n = 8)
+// issues loads whose lanes are a row apart: every instruction touches 64 lines (mp_bodies.h measured that pattern at 4.0 against
+// 5.4 TB/s on stores).  Here a FULL wave reads its 64 consecutive rows as flat 16-byte chunks, non-temporal, so that one load
+// instruction covers a contiguous kilobyte, and stages them 16 rows at a time in its LDS slice (mp_wave_store_flat's pitch: an odd
+// number of chunks, conflict-free for the row reads), where the 16 lanes that own the rows pick them up.  The next pass's chunks are
+// requested before the current pass is staged.
+template <typename T, int COUNT>
+__device__ __forceinline__ void mp_wave_load_flat(const T* __restrict__ gbase, long row0, int lane, T (&v)[COUNT],
+                                                  char* __restrict__ lds) {
+  constexpr int ROWB = COUNT * (int)sizeof(T), CH = ROWB / 16, ROWS = 16, TOTAL = ROWS * CH, NJ = (TOTAL + 63) / 64;
+  static_assert(ROWB % 16 == 0, "rows of whole 16-byte chunks");
+  constexpr int PITCH = (CH % 2 == 1) ? ROWB : ((ROWB + 127) / 128) * 128 + 16;
+  static_assert(ROWS * PITCH <= MP_WAVE_LDS_BYTES, "wave staging slice too small");
+  const mp_u4* g = reinterpret_cast<const mp_u4*>(gbase + row0 * COUNT);
+  mp_u4 buf[2][NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+    if (j * 64 + lane < TOTAL) buf[0][j] = mp_stream_load(g + j * 64 + lane);
+#pragma unroll
+  for (int pass = 0; pass < 64 / ROWS; ++pass) {
+    if (pass + 1 < 64 / ROWS) {
+#pragma unroll
+      for (int j = 0; j < NJ; ++j)
+        if (j * 64 + lane < TOTAL) buf[(pass + 1) & 1][j] = mp_stream_load(g + (pass + 1) * TOTAL + j * 64 + lane);
+    }
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int f = j * 64 + lane;  // flat chunk index inside this pass's 16 rows
+      if (f < TOTAL) {
+        const int row = f / CH, col = f - row * CH;
+        *reinterpret_cast<mp_u4*>(lds + row * PITCH + col * 16) = buf[pass & 1][j];
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if ((lane >> 4) == pass) {
+      const T* src = reinterpret_cast<const T*>(lds + (lane & (ROWS - 1)) * PITCH);
+#pragma unroll
+      for (int e = 0; e < COUNT; ++e) v[e] = src[e];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+}
+
+// One lane per row, one wave per block (kFkBlock: the wave's LDS slice).  q moves as whole lines (MpRowStage), the cotangents through
+// mp_wave_load_flat, T / J / g leave through the wave-cooperative stores; the last, partial wave reads per lane.  The cotangents are
+// read only when gq is requested; a null cotangent is zero.  The pose cotangent is reduced to its 6-vector before gJ is read, so the
+// 6N Jacobian columns and the 6N cotangents are the registers the sweep holds.
+template <int N, int FRAME>
+__global__ __launch_bounds__(kFkBlock) void k_fk_jac_vjp(const MpModel<double> M, const double* __restrict__ q,
+                                                         const double* __restrict__ gT, const double* __restrict__ gJ,
+                                                         double* __restrict__ Tout, double* __restrict__ Jout, double* __restrict__ gq,
+                                                         long rows) {
+  using ST = MpRowStage<double, N>;
+  static_assert(ST::SPAN <= MP_WAVE_LDS_BYTES, "one array's 64 rows fit the wave's staging slice");
+  __shared__ __attribute__((aligned(16))) char lds[MP_WAVE_LDS_BYTES];
+  const int lane = (int)threadIdx.x;
+  const long row0 = (long)blockIdx.x * kFkBlock;
+  if (row0 >= rows) return;
+  const long left = rows - row0;
+  const int nvalid = left < 64 ? (int)left : 64;
+  const bool full = nvalid == 64;
+  const long rr = lane < nvalid ? row0 + lane : rows - 1;  // out-of-range lanes recompute the last row, store nothing
+  double a[N];
+  if (full) {
+    mp_u4 bq[ST::NJ];
+    ST::fetch(q, row0, lane, bq);
+    ST::stage(bq, lane, lds);
+    ST::sync();
+    ST::row_in(lds, lane, a);
+    ST::sync();
+  } else {
+    RunIO<double, N>::load(q, rr, a);
+  }
+  MpBad<double> bad;
+  bad.add(a);
+  double TT[16], JJ[6 * N], g[N];
+  mp_kin_primal<double, N, FRAME>(M, a, TT, JJ);
+  if (gq != nullptr) {
+    double w[6];
+    {
+      double ct[16];
+      if (gT == nullptr) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k) ct[k] = 0.0;
+      } else if (full) {
+        mp_wave_load_flat<double, 16>(gT, row0, lane, ct, lds);
+      } else {
+        RunIO<double, 16>::load(gT, rr, ct);
+      }
+      bad.add(ct);
+      mp_kin_pose_cotangent<double, FRAME>(TT, ct, w);
+    }
+    double cj[6 * N];
+    if (gJ == nullptr) {
+#pragma unroll
+      for (int k = 0; k < 6 * N; ++k) cj[k] = 0.0;
+    } else if (full) {
+      mp_wave_load_flat<double, 6 * N>(gJ, row0, lane, cj, lds);
+    } else {
+      RunIO<double, 6 * N>::load(gJ, rr, cj);
+    }
+    bad.add(cj);
+    mp_kin_sweep<double, N, FRAME>(JJ, w, cj, g);
+  }
+  const bool poison = bad.any();
+  if (Tout != nullptr) {
+    mp_poison_if(poison, TT);
+    mp_wave_store_auto<double, 16>(Tout, row0, lane, nvalid, TT, lds);
+  }
+  if (Jout != nullptr) {
+    mp_poison_if(poison, JJ);
+    mp_wave_store_auto<double, 6 * N>(Jout, row0, lane, nvalid, JJ, lds);
+  }
+  if (gq != nullptr) {
+    mp_poison_if(poison, g);
+    mp_wave_store_auto<double, N>(gq, row0, lane, nvalid, g, lds);
+  }
 }
 
 // reverse mode through the roll-out (mp_rollout_vjp.h): one lane = one trajectory on the time-major layout, so that the 64 lanes of a
@@ -671,6 +796,7 @@ hipError_t mpk_stream_mix(hipStream_t s, int reads, int writes, bool nontemporal
     return hipGetLastError();                                                                                                     \
   }
   MP_MIX(0, 1) MP_MIX(1, 1) MP_MIX(3, 1) MP_MIX(1, 3) MP_MIX(2, 3) MP_MIX(1, 2) MP_MIX(2, 1)
+  MP_MIX(9, 1) MP_MIX(10, 1)   // the read-heavy mixes of k_fk_jac_vjp (q + gT + gJ in, gq out: 9.7 : 1 at n = 6, 9 : 1 at n = 8)
 #undef MP_MIX
   return hipErrorInvalidValue;
 }
@@ -866,6 +992,17 @@ hipError_t mpk_fd_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<doub
   MP_DISPATCH_N(M.n, {
     if (ftip) hipLaunchKernelGGL((k_fd_vjp<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, gqdd, qdd, gq, gqd, gtau, rows);
     else hipLaunchKernelGGL((k_fd_vjp<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, gqdd, qdd, gq, gqd, gtau, rows);
+  })
+  return hipGetLastError();
+}
+
+hipError_t mpk_fk_jac_vjp(hipStream_t s, const MpModel<double>& M, int frame, const double* q, const double* gT, const double* gJ,
+                         double* Tout, double* Jout, double* gq, long rows) {
+  if (rows <= 0) return hipSuccess;
+  const unsigned gb = (unsigned)((rows + kFkBlock - 1) / kFkBlock);
+  MP_DISPATCH_N(M.n, {
+    if (frame == 0) hipLaunchKernelGGL((k_fk_jac_vjp<N, 0>), dim3(gb), dim3(kFkBlock), 0, s, M, q, gT, gJ, Tout, Jout, gq, rows);
+    else hipLaunchKernelGGL((k_fk_jac_vjp<N, 1>), dim3(gb), dim3(kFkBlock), 0, s, M, q, gT, gJ, Tout, Jout, gq, rows);
   })
   return hipGetLastError();
 }

@@ -152,6 +152,32 @@ class SerialManipulator:
             J = np.concatenate([Rt @ Jw, Rt @ (Jv - pxJw)], axis=1)
         return J if np.ndim(thetalist) == 2 else J[0]
 
+    # ---- reverse mode through FK + Jacobian (float64, n <= 8; csrc/mp_kin_vjp.h)
+    def kinematics_vjp(self, thetalist, gT=None, gJ=None, frame: str = "space") -> np.ndarray:
+        """g_q = d/dq (<gT, T> + <gJ, J>) with T = forward_kinematics(q) and J = jacobian(q, frame), for the cotangents gT (4, 4) and
+        gJ (6, n) - or (rows, 4, 4) / (rows, 6, n) with (rows, n) joint values - either may be None (= 0): (n,) or (rows, n).  One
+        launch, no Jacobian of T or J formed; the bottom row of gT does not contribute.  Only the compiled chain has a gradient: a
+        truncated joint vector and frame="body" on a model whose B_list is not Ad(M^-1) S_list are refused."""
+        model = self._gradient_model(np.shape(thetalist)[-1], frame, "kinematics_vjp")
+        one = np.ndim(thetalist) == 1
+        q = np.atleast_2d(np.asarray(thetalist, dtype=np.float64))
+        rows = q.shape[0]
+        cT = None if gT is None else np.asarray(gT, dtype=np.float64).reshape(rows, 4, 4)
+        cJ = None if gJ is None else np.asarray(gJ, dtype=np.float64).reshape(rows, 6, model.n)
+        _, _, gq = execute_registered_kernel("kinematics.fk_jacobian_vjp", model, q, cT, cJ, frame)
+        return gq[0] if one else gq
+
+    def _gradient_model(self, nvalues: int, frame: str, what: str) -> _hip.HipModel:
+        """The compiled model, for gradients of FK / J at `nvalues` joint values in `frame` - or the refusal of what it does not cover."""
+        if frame not in ("space", "body"):
+            raise ValueError("Invalid frame specified. Choose 'space' or 'body'.")
+        n = self.S_list.shape[1]
+        if nvalues != n:
+            raise ValueError(f"{what}: {nvalues} joint values for a {n}-joint chain - gradients of a truncated chain are not provided")
+        if frame == "body" and not self._B_consistent:
+            raise ValueError(f"{what}: this model's B_list is not Ad(M^-1) S_list - body-frame gradients are not provided")
+        return self._kin_model()
+
     # ---- inverse kinematics (reference kinematics/ik.py:39-311)
     def batch_inverse_kinematics(self, T_desired_batch, thetalist0_batch, eomg: float = 1e-6, ev: float = 1e-6,
                                  max_iterations: int = 10000, damping: float = 2e-2, step_cap: float = 0.3,

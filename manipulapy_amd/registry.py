@@ -307,6 +307,10 @@ def _launch_fd_vjp_cpu(model, q, qd, tau, gqdd, g=None, Ftip=None):
     return _hip.cpu_fd_vjp(model, q, qd, tau, gqdd, g, Ftip)
 
 
+def _launch_fk_jac_vjp_cpu(model, q, gT=None, gJ=None, frame="space", want_T=False, want_J=False, want_gq=True):
+    return _hip.cpu_fk_jac_vjp(model, q, gT, gJ, frame, want_T, want_J, want_gq)
+
+
 def _launch_id_regressor_cpu(model, q, qd, qdd, g=None, Ftip=None):
     return _hip.cpu_id_regressor(model, q, qd, qdd, g, Ftip)
 
@@ -443,6 +447,10 @@ def _launch_fd_vjp_gpu(model, q, qd, tau, gqdd, g=None, Ftip=None):
     return get_context().fd_vjp_host(model, q, qd, tau, gqdd, g, Ftip)
 
 
+def _launch_fk_jac_vjp_gpu(model, q, gT=None, gJ=None, frame="space", want_T=False, want_J=False, want_gq=True):
+    return get_context().fk_jac_vjp_host(model, q, gT, gJ, frame, want_T, want_J, want_gq)
+
+
 def _launch_id_regressor_gpu(model, q, qd, qdd, g=None, Ftip=None):
     return get_context().id_regressor_host(model, q, qd, qdd, g, Ftip)
 
@@ -518,6 +526,8 @@ def _build_kernel_registry() -> KernelRegistry:
         ("dynamics.fused_trajectory_inverse", "mp_traj_id_fused_host_f32", _launch_fused_gpu, _launch_fused_cpu),
         ("kinematics.fk_jacobian", "mp_fk_jac_id_host_f64", _launch_fk_jac_gpu, _launch_fk_jac_cpu),
         ("kinematics.inverse", "mp_inverse_kinematics_host_f64", _launch_ik_gpu, _launch_ik_cpu),
+        # reverse mode through FK + Jacobian (csrc/mp_kin_vjp.h); sorts after the pinned start of the name list
+        ("kinematics.fk_jacobian_vjp", "mp_fk_jac_vjp_host_f64", _launch_fk_jac_vjp_gpu, _launch_fk_jac_vjp_cpu),
         ("dynamics.mass_matrix", "mp_mass_matrix_host_f64", _launch_mass_matrix_gpu, _launch_mass_matrix_cpu),
         ("dynamics.forward", "mp_forward_dynamics_host_f64", _launch_forward_dynamics_gpu, _launch_forward_dynamics_cpu),
         ("dynamics.forward_trajectory", "mp_fd_trajectory_host_f32 / _f64", _launch_fd_trajectory_gpu, _launch_fd_trajectory_cpu),

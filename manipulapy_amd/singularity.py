@@ -14,6 +14,8 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
+from .registry import execute_registered_kernel
+
 __all__ = ["Singularity"]
 
 
@@ -51,6 +53,32 @@ class Singularity:
         s = self._singular_values(thetalist)
         m = np.prod(s, axis=-1)
         return m[()] if m.ndim == 0 else m
+
+    def manipulability_gradient(self, thetalist):
+        """(w, dw_dq): the manipulability w = prod sigma_k of J_s (as `manipulability`) and its gradient in q, (), (n,) for one
+        configuration or (rows,), (rows, n) for a batch (float64, n <= 8).  One FK + J launch gives J, a batched host SVD the
+        cotangent gJ = sum_k (prod_{l != k} sigma_l) u_k v_k^T = dw/dJ, and one "kinematics.fk_jacobian_vjp" launch dw/dq = gJ . dJ/dq.
+
+        Away from singularities this is the gradient of w.  At a configuration where exactly one singular value is 0, w has a kink
+        (sigma_min behaves like |x| across the singular set): the result is +-(prod_{l != min} sigma_l) grad x with the sign of
+        whatever (u, v) pair the SVD picked.  A small step along it increases w in either sign, so gradient ascent leaves the
+        singularity (central differences give about 0 there).  Where two or more singular values vanish the gradient is 0."""
+        sm = self.serial_manipulator
+        model = sm._gradient_model(np.shape(thetalist)[-1], "space", "manipulability_gradient")
+        one = np.ndim(thetalist) == 1
+        q = np.atleast_2d(np.asarray(thetalist, dtype=np.float64))
+        J = np.asarray(sm.jacobian(q, frame="space"), dtype=np.float64)
+        with np.errstate(all="ignore"):
+            U, s, Vt = np.linalg.svd(J, full_matrices=False)   # (rows, 6, k), (rows, k), (rows, k, n), k = min(6, n)
+        k = s.shape[-1]
+        ones = np.ones_like(s[:, :1])
+        before = np.cumprod(np.concatenate([ones, s[:, :-1]], axis=1), axis=1)               # prod_{l < k} sigma_l
+        after = np.cumprod(np.concatenate([ones, s[:, :0:-1]], axis=1), axis=1)[:, ::-1]     # prod_{l > k} sigma_l
+        coef = before * after
+        gJ = np.einsum("rk,rik,rkj->rij", coef, U[:, :, :k], Vt[:, :k, :])
+        _, _, g = execute_registered_kernel("kinematics.fk_jacobian_vjp", model, q, None, gJ, "space")
+        w = np.prod(s, axis=-1)
+        return (w[0], g[0]) if one else (w, g)
 
     def workspace_monte_carlo(self, joint_limits: Sequence[Tuple[float, float]], num_samples: int = 10000,
                               seed: Optional[int] = 1234, hull: bool = True) -> Dict[str, np.ndarray]:
