@@ -232,3 +232,13 @@ extern "C" int hostsim_ik(int n, const double* S, const double* Mcom, const doub
   }
   return 1;
 }
+
+// the restart noise of the inverse kinematics over arrays: mp_ik_key of `rows` problems (Td rows x 16, th0 rows x n), and
+// mp_ik_normal of `count` (seed, key, restart, joint) tuples
+extern "C" void hostsim_ik_key(int n, long rows, const double* Td, const double* th0, unsigned long long* out) {
+  for (long r = 0; r < rows; ++r) out[r] = mp_ik_key(n, Td + r * 16, th0 + r * n);
+}
+extern "C" void hostsim_ik_normal(long count, const unsigned* seed, const unsigned long long* key, const int* restart, const int* joint,
+                                  double* out) {
+  for (long i = 0; i < count; ++i) out[i] = mp_ik_normal(seed[i], key[i], restart[i], joint[i]);
+}

@@ -28,6 +28,22 @@ def timed(ctx, fn, steps=10, warmup=2):
     return ms
 
 
+def ik_outcome(ctx, model, d_theta, d_T, d_ok, B):
+    """What a timed IK launch returned: share of successes, and the worst pose residual (rotation angle in rad, translation
+    in m) of the successful rows, from forward kinematics of the returned joint values against the targets."""
+    ok = d_ok.download((B,), np.int32) == 1
+    d_Ts = ctx.alloc(B * 128)
+    ctx.fk_jac_id(model, d_theta, None, None, B, d_Ts, None, None)
+    ctx.synchronize()
+    Ts, Tt = d_Ts.download((B, 4, 4), np.float64)[ok], d_T.download((B, 4, 4), np.float64)[ok]
+    d_Ts.free()
+    if not ok.any():
+        return 0.0, None, None
+    trace = np.einsum("bij,bij->b", Ts[:, :3, :3], Tt[:, :3, :3])   # tr(Rs^T Rt)
+    angle = np.arccos(np.clip(0.5 * (trace - 1.0), -1.0, 1.0))
+    return float(ok.mean()), float(angle.max()), float(np.linalg.norm(Tt[:, :3, 3] - Ts[:, :3, 3], axis=1).max())
+
+
 def main():
     rows = int(os.environ.get("ROWS", 1 << 22))
     ctx = _hip.HipContext(0)
@@ -104,16 +120,20 @@ def main():
         dok, dit, drs = ctx.alloc(B * 4), ctx.alloc(B * 4), ctx.alloc(B * 4)
         ms = timed(ctx, lambda: ctx.inverse_kinematics(model, dT, d0, B, dth, dok, dit, drs, joint_limits=lim, max_iterations=200),
                    steps=3, warmup=1)
-        ok = dok.download((B,), np.int32); it = dit.download((B,), np.int32)
+        it = dit.download((B,), np.int32)
+        share, worst_rot, worst_trans = ik_outcome(ctx, model, dth, dT, dok, B)
         out.append(dict(op="inverse_kinematics", robot=robot, dtype="float64", problems=B, ms=ms, problems_per_s=B / ms * 1e3,
-                        success_rate=float(ok.mean()), mean_iterations=float(it.mean()), max_iterations=int(it.max()),
+                        success_rate=share, worst_success_rot_err=worst_rot, worst_success_trans_err=worst_trans,
+                        mean_iterations=float(it.mean()), max_iterations=int(it.max()),
                         iterations_per_s=float(it.sum()) / ms * 1e3))
         ctx.specialize(model)
         ms = timed(ctx, lambda: ctx.inverse_kinematics(model, dT, d0, B, dth, dok, dit, drs, joint_limits=lim, max_iterations=200),
                    steps=3, warmup=1)
-        ok = dok.download((B,), np.int32); it = dit.download((B,), np.int32)
+        it = dit.download((B,), np.int32)
+        share, worst_rot, worst_trans = ik_outcome(ctx, model, dth, dT, dok, B)
         out.append(dict(op="inverse_kinematics (specialised)", robot=robot, dtype="float64", problems=B, ms=ms,
-                        problems_per_s=B / ms * 1e3, success_rate=float(ok.mean()), mean_iterations=float(it.mean()),
+                        problems_per_s=B / ms * 1e3, success_rate=share, worst_success_rot_err=worst_rot,
+                        worst_success_trans_err=worst_trans, mean_iterations=float(it.mean()),
                         iterations_per_s=float(it.sum()) / ms * 1e3))
         for b in (dq, dT, d0, dth, dok, dit, drs):
             b.free()
