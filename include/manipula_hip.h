@@ -287,6 +287,34 @@ int mp_fd_vjp_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const d
 int mp_fk_jac_vjp_f64(mp_ctx* ctx, const mp_model* model, int frame, const double* d_q, const double* d_gT, const double* d_gJ,
                       int64_t rows, double* d_T, double* d_J, double* d_gq);
 
+/* Operational-space (task-space) dynamics and task-space computed torque (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED above
+ * that; csrc/mp_opspace.h).  Twists are [w; v].  frame 0 = space, 1 = body, 2 = hybrid (J_h = blkdiag(R, R) J_b, R the rotation of
+ * T = FK(q): angular velocity and tool-origin velocity, both in space axes); task 0 = full (m = 6 rows), 1 = linear (rows 3..5, m = 3),
+ * 2 = angular (rows 0..2, m = 3); anything else is refused, as is a negative or non-finite damping.  With J the selected m x n block,
+ * c(q, qd) the velocity-product torques, g(q) the gravity torques (g = NULL: (0, 0, -9.81)) and lambda = damping:
+ *   A = J M^-1 J^T + lambda^2 1 (m x m)    Lambda = A^-1    Jbar = M^-1 J^T Lambda (n x m, the dynamically consistent inverse)
+ *   mu = Lambda (J M^-1 c - Jdot qd)       p = Lambda J M^-1 g
+ *   tau(a*, tau0) = J^T (Lambda a* + mu + p) + (1 - J^T Jbar^T) tau0
+ * so that, with lambda = 0, forward dynamics of tau gives J qdd + Jdot qd = a* whatever the null-space torque tau0 is.  No tip wrench
+ * enters: a wrench F at the tool is the caller's J^T F added to tau.  A is formed through the Cholesky factor of M (W = L^-1 J^T,
+ * A = W^T W + lambda^2 1) and factored by Cholesky itself; M^-1 is never formed.
+ *   mp_opspace_f64: q, qd (rows,n) -> T (rows,4,4), J (rows,m,n), Jdqd = Jdot qd (rows,m), Lambda (rows,m,m), Jbar (rows,n,m),
+ *     mu (rows,m), p (rows,m); every output may be NULL, at least one is required.
+ *   mp_opspace_torque_f64: q, qd (rows,n), acc = a* (rows,m), tau0 (rows,n) or NULL (= 0) -> tau (rows,n); nothing wider than a row of
+ *     n values is read or written.
+ * A pivot d_j of the Cholesky factorisation of A that is not positive makes the Lambda-dependent outputs of that row NaN (Lambda, Jbar,
+ * mu, p, tau); T, J and Jdqd of the row stay valid.  "Positive" is judged against rounding: d_j > 2^-46 A_jj (64 eps, what the
+ * subtracted products and W leave in d_j; a matrix that fails has cond(A) above 1e13).  So a singular pose with damping = 0 gives NaN,
+ * and so does one whose damping is too small to lift the pivot over that threshold (lambda^2 <= 2^-46 A_jj, lambda below about 1e-7
+ * for A_jj of order 1): choose a damping that matters at the scale of A.  A row with a non-finite input comes back NaN in every output of that row only.
+ * rows = 0 is a no-op.  The device forms are asynchronous (no synchronisation, no allocation: they may be captured into a launch graph);
+ * the _host forms take their device memory from the context's pool; the _cpu twins are listed with the others below. */
+int mp_opspace_f64(mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* d_q, const double* d_qd,
+                   int64_t rows, const double* g, double* d_T, double* d_J, double* d_Jdqd, double* d_Lambda, double* d_Jbar, double* d_mu,
+                   double* d_p);
+int mp_opspace_torque_f64(mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* d_q, const double* d_qd,
+                          const double* d_acc, const double* d_tau0, int64_t rows, const double* g, double* d_tau);
+
 /* forward_dynamics_trajectory for B independent trajectories (planning/trajectory_dynamics.py:382-423,
  * :580-708; replaces forward_dynamics_kernel, cuda_kernels/trajectory_kernels.py:604-705): semi-implicit
  * Euler, intRes sub-steps of dt/intRes, positions clipped to the joint limits after every sub-step, row 0 =
@@ -415,6 +443,11 @@ int mp_fd_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, cons
                        int64_t rows, const double* g, const double* Ftip, double* qdd, double* gq, double* gqd, double* gtau);
 int mp_fk_jac_vjp_host_f64(mp_ctx* ctx, const mp_model* model, int frame, const double* q, const double* gT, const double* gJ,
                            int64_t rows, double* T, double* J, double* gq);
+int mp_opspace_host_f64(mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* q, const double* qd,
+                        int64_t rows, const double* g, double* T, double* J, double* Jdqd, double* Lambda, double* Jbar, double* mu,
+                        double* p);
+int mp_opspace_torque_host_f64(mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* q, const double* qd,
+                               const double* acc, const double* tau0, int64_t rows, const double* g, double* tau);
 int mp_fd_trajectory_host_f32(mp_ctx* ctx, const mp_model* model, const float* theta0, const float* dtheta0,
                               const float* taumat, const float* Ftipmat, int64_t B, int64_t N, const double* g,
                               double dt, int intRes, float* pos, float* vel, float* acc);
@@ -479,6 +512,11 @@ int mp_fd_vjp_cpu_f64(const mp_model* model, const double* q, const double* qd, 
                       const double* g, const double* Ftip, double* qdd, double* gq, double* gqd, double* gtau, int nthreads);
 int mp_fk_jac_vjp_cpu_f64(const mp_model* model, int frame, const double* q, const double* gT, const double* gJ, int64_t rows,
                           double* T, double* J, double* gq, int nthreads);
+int mp_opspace_cpu_f64(const mp_model* model, int frame, int task, double damping, const double* q, const double* qd, int64_t rows,
+                       const double* g, double* T, double* J, double* Jdqd, double* Lambda, double* Jbar, double* mu, double* p,
+                       int nthreads);
+int mp_opspace_torque_cpu_f64(const mp_model* model, int frame, int task, double damping, const double* q, const double* qd,
+                              const double* acc, const double* tau0, int64_t rows, const double* g, double* tau, int nthreads);
 int mp_fd_trajectory_cpu_f32(const mp_model* model, const float* theta0, const float* dtheta0, const float* taumat,
                              const float* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, float* pos,
                              float* vel, float* acc, int nthreads);

@@ -117,6 +117,12 @@ SIGNATURES = {
     "mp_fk_jac_vjp_f64": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "mp_fk_jac_vjp_host_f64": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp]),
     "mp_fk_jac_vjp_cpu_f64": (ctypes.c_int, [_vp, ctypes.c_int, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_opspace_f64": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, _vp, _i64, _c_dp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_opspace_host_f64": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_opspace_cpu_f64": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_opspace_torque_f64": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _vp, _vp, _vp, _vp, _i64, _c_dp, _vp]),
+    "mp_opspace_torque_host_f64": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp]),
+    "mp_opspace_torque_cpu_f64": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_double, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_int]),
     "mp_id_regressor_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp]),
     "mp_id_regressor_normal_workspace_bytes": (ctypes.c_int64, [_vp, _i64]),
     "mp_id_regressor_normal_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
@@ -239,6 +245,12 @@ def _vec_or_none(v, k, name):
     if v is None:
         return None
     return _as_c(v, np.float64, (k,), name)
+
+
+# operational-space dynamics (csrc/mp_opspace.h): the output names of mp_opspace_*_f64 in the order of its arguments
+OPSPACE_OUTPUTS = ("T", "J", "Jdot_qd", "Lambda", "Jbar", "mu", "p")
+_OPSPACE_FRAMES = {"space": 0, "body": 1, "hybrid": 2}
+_OPSPACE_TASKS = {"full": 0, "linear": 1, "angular": 2}
 
 
 class DeviceBuffer:
@@ -628,6 +640,22 @@ class HipContext:
         _check(self.lib.mp_fk_jac_vjp_f64(self.handle, model.handle, _frame_code(frame), _p(d_q), _p(d_gT), _p(d_gJ), int(rows), _p(d_T),
                                           _p(d_J), _p(d_gq)))
 
+    def opspace(self, model, frame, task, damping, d_q, d_qd, rows, g=None, d_T=None, d_J=None, d_Jdqd=None, d_Lambda=None, d_Jbar=None,
+                d_mu=None, d_p=None):
+        """Operational-space dynamics on device buffers (float64; csrc/mp_opspace.h): frame "space" / "body" / "hybrid", task "full" /
+        "linear" / "angular" (m = 6 / 3 / 3 rows); outputs T (rows,4,4), J (rows,m,n), Jdqd (rows,m), Lambda (rows,m,m), Jbar (rows,n,m),
+        mu / p (rows,m), each may be None (at least one given); asynchronous (capturable)."""
+        _check(self.lib.mp_opspace_f64(self.handle, model.handle, _opspace_frame(frame), _opspace_task(task), float(damping), _p(d_q),
+                                       _p(d_qd), int(rows), _dptr(_vec_or_none(g, 3, "g")), _p(d_T), _p(d_J), _p(d_Jdqd), _p(d_Lambda),
+                                       _p(d_Jbar), _p(d_mu), _p(d_p)))
+
+    def opspace_torque(self, model, frame, task, damping, d_q, d_qd, d_acc, d_tau0, rows, d_tau, g=None):
+        """Task-space computed torque on device buffers: d_acc (rows,m), d_tau0 (rows,n) or None -> d_tau (rows,n); asynchronous
+        (capturable)."""
+        _check(self.lib.mp_opspace_torque_f64(self.handle, model.handle, _opspace_frame(frame), _opspace_task(task), float(damping),
+                                              _p(d_q), _p(d_qd), _p(d_acc), _p(d_tau0), int(rows), _dptr(_vec_or_none(g, 3, "g")),
+                                              _p(d_tau)))
+
     def cartesian_trajectory(self, d_Xstart, d_Xend, B, N, Tf, method, d_pos, d_vel, d_acc, d_orient):
         _check(self.lib.mp_cartesian_trajectory_f32(self.handle, _p(d_Xstart), _p(d_Xend), int(B), int(N), float(Tf), int(method),
                                                     _p(d_pos), _p(d_vel), _p(d_acc), _p(d_orient)))
@@ -813,6 +841,14 @@ class HipContext:
         """(T (rows,4,4), J (rows,6,n) in `frame`, gq (rows,n)) of (rows, n) host rows and cotangents gT (rows,4,4) / gJ (rows,6,n)
         (None = 0); an output not asked for is None."""
         return _kin_vjp(self.lib.mp_fk_jac_vjp_host_f64, (self.handle,), model, frame, q, gT, gJ, want_T, want_J, want_gq)
+
+    def opspace_host(self, model: HipModel, q, qd, g=None, frame="hybrid", task="full", damping=0.0, want=OPSPACE_OUTPUTS):
+        """Operational-space dynamics of (rows, n) host rows: a dict of the outputs named in `want` (OPSPACE_OUTPUTS)."""
+        return _opspace(self.lib.mp_opspace_host_f64, (self.handle,), model, frame, task, damping, q, qd, g, want)
+
+    def opspace_torque_host(self, model: HipModel, q, qd, acc, g=None, tau0=None, frame="hybrid", task="full", damping=0.0):
+        """tau (rows, n) for the task accelerations acc (rows, m) and the null-space torques tau0 (rows, n) or None."""
+        return _opspace_torque(self.lib.mp_opspace_torque_host_f64, (self.handle,), model, frame, task, damping, q, qd, acc, tau0, g)
 
     def fd_trajectory_host(self, model: HipModel, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64,
                            layout: str = "batch_major", device_layout: str | None = None, out=None):
@@ -1149,6 +1185,73 @@ def _kin_vjp(fn, lead, model, frame, q, gT, gJ, want_T, want_J, want_gq, nthread
 def cpu_fk_jac_vjp(model: "HipModel", q, gT=None, gJ=None, frame="space", want_T=False, want_J=False, want_gq=True, nthreads: int = 0):
     """CPU twin of HipContext.fk_jac_vjp_host: (T, J, gq), None where not asked for."""
     return _kin_vjp(load_library().mp_fk_jac_vjp_cpu_f64, (), model, frame, q, gT, gJ, want_T, want_J, want_gq, nthreads)
+
+
+def _opspace_frame(frame) -> int:
+    if frame in _OPSPACE_FRAMES:
+        return _OPSPACE_FRAMES[frame]
+    if frame in (0, 1, 2) and not isinstance(frame, bool):
+        return int(frame)
+    raise ValueError(f"frame must be 'space', 'body' or 'hybrid', got {frame!r}")
+
+
+def _opspace_task(task) -> int:
+    if task in _OPSPACE_TASKS:
+        return _OPSPACE_TASKS[task]
+    if task in (0, 1, 2) and not isinstance(task, bool):
+        return int(task)
+    raise ValueError(f"task must be 'full', 'linear' or 'angular', got {task!r}")
+
+
+def _opspace_rows(model, q, qd):
+    q = _as_c(q, np.float64, name="q")
+    if q.ndim != 2 or q.shape[1] != model.n:
+        raise ValueError(f"q must be (rows, {model.n}); got {q.shape}")
+    return q, _as_c(qd, np.float64, q.shape, "qd")
+
+
+def _opspace(fn, lead, model, frame, task, damping, q, qd, g, want, nthreads=None):
+    fc, tc = _opspace_frame(frame), _opspace_task(task)
+    q, qd = _opspace_rows(model, q, qd)
+    unknown = [w for w in want if w not in OPSPACE_OUTPUTS]
+    if unknown or not want:
+        raise ValueError(f"want must name at least one of {OPSPACE_OUTPUTS}; got {tuple(want)!r}")
+    rows, n = q.shape
+    m = 6 if tc == 0 else 3
+    shapes = {"T": (rows, 4, 4), "J": (rows, m, n), "Jdot_qd": (rows, m), "Lambda": (rows, m, m), "Jbar": (rows, n, m), "mu": (rows, m),
+              "p": (rows, m)}
+    out = {k: (np.empty(shapes[k]) if k in want else None) for k in OPSPACE_OUTPUTS}
+    args = list(lead) + [model.handle, fc, tc, float(damping), _dptr(q), _dptr(qd), rows, _dptr(_vec_or_none(g, 3, "g"))]
+    args += [_dptr(out[k]) for k in OPSPACE_OUTPUTS]
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def _opspace_torque(fn, lead, model, frame, task, damping, q, qd, acc, tau0, g, nthreads=None):
+    fc, tc = _opspace_frame(frame), _opspace_task(task)
+    q, qd = _opspace_rows(model, q, qd)
+    rows = q.shape[0]
+    acc = _as_c(acc, np.float64, (rows, 6 if tc == 0 else 3), "acc")
+    tau0 = None if tau0 is None else _as_c(tau0, np.float64, q.shape, "tau0")
+    tau = np.empty(q.shape)
+    args = list(lead) + [model.handle, fc, tc, float(damping), _dptr(q), _dptr(qd), _dptr(acc), _dptr(tau0), rows,
+                         _dptr(_vec_or_none(g, 3, "g")), _dptr(tau)]
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return tau
+
+
+def cpu_opspace(model: "HipModel", q, qd, g=None, frame="hybrid", task="full", damping=0.0, want=OPSPACE_OUTPUTS, nthreads: int = 0):
+    """CPU twin of HipContext.opspace_host."""
+    return _opspace(load_library().mp_opspace_cpu_f64, (), model, frame, task, damping, q, qd, g, want, nthreads)
+
+
+def cpu_opspace_torque(model: "HipModel", q, qd, acc, g=None, tau0=None, frame="hybrid", task="full", damping=0.0, nthreads: int = 0):
+    """CPU twin of HipContext.opspace_torque_host."""
+    return _opspace_torque(load_library().mp_opspace_torque_cpu_f64, (), model, frame, task, damping, q, qd, acc, tau0, g, nthreads)
 
 
 def _pd_regulation_args(model, theta0, theta_des, Kp, Kd, g, steps):

@@ -113,6 +113,60 @@ class ManipulatorController:
         tau = np.einsum("rij,ri->rj", Jv, kp - kd)
         return tau[0] if single else tau
 
+    def operational_space_control(self, T_desired, V_desired, A_desired, thetalist, dthetalist, g, Kp, Kd, tau_null=None,
+                                  frame: str = "hybrid", task: str = "full", damping: float = 0.0) -> np.ndarray:
+        """Task-space computed torque (operational-space control): tau = J^T (Lambda a* + mu + p) + (1 - J^T Jbar^T) tau_null with
+        a* = A_d + Kd (V_d - J qd) + Kp e, so that the pose error obeys e'' + Kd e' + Kp e = 0 away from singularities.
+        frame "hybrid": e = [log(R_d R^T)v; p_d - p], twists = (angular velocity, tool-origin velocity) in space axes; frame "body":
+        e = [log(R^T R_d)v; R^T (p_d - p)], body twists.  task "full" / "linear" / "angular" keeps the matching rows of e, V_d, A_d
+        (m = 6 / 3 / 3 values).  T_desired (4, 4) or (rows, 4, 4); V_desired / A_desired (m,) or (rows, m); gains: a scalar, (m,) or
+        (m, m).  (n,) for 1-D joint states, (rows, n) for 2-D ones.  T, J and Jdot qd come from one operational-space launch, the
+        torque from one more; no mass matrix or Lambda reaches the host."""
+        if frame == "space":
+            raise ValueError("operational_space_control: the pose error has no space-frame form here - use frame='hybrid' or 'body', "
+                             "or form the task acceleration yourself and call ManipulatorDynamics.operational_space_torque")
+        if frame not in ("hybrid", "body"):
+            raise ValueError(f"frame must be 'hybrid' or 'body', got {frame!r}")
+        if task not in ("full", "linear", "angular"):
+            raise ValueError(f"task must be 'full', 'linear' or 'angular', got {task!r}")
+        from .registry import execute_registered_kernel
+        from .utils import rotation_log_rows
+
+        q = np.asarray(thetalist, dtype=np.float64)
+        single = q.ndim == 1
+        q2, qd2 = np.atleast_2d(q), np.atleast_2d(np.asarray(dthetalist, dtype=np.float64))
+        rows = q2.shape[0]
+        m = 6 if task == "full" else 3
+        model = self.dynamics._derivative_model("operational_space_control")
+        kin = execute_registered_kernel("dynamics.operational_space", model, q2, qd2, g, frame, task, damping, ("T", "J", "Jdot_qd"))
+        T, J = kin["T"], kin["J"]
+        Td = np.broadcast_to(np.asarray(T_desired, dtype=np.float64), (rows, 4, 4))
+        R, Rd = T[:, :3, :3], Td[:, :3, :3]
+        dp = Td[:, :3, 3] - T[:, :3, 3]
+        if frame == "hybrid":
+            ew, ev = rotation_log_rows(Rd @ R.transpose(0, 2, 1)), dp
+        else:
+            ew, ev = rotation_log_rows(R.transpose(0, 2, 1) @ Rd), np.einsum("rji,rj->ri", R, dp)
+        e = {"full": np.concatenate([ew, ev], axis=1), "linear": ev, "angular": ew}[task]
+        Vd = np.broadcast_to(np.asarray(V_desired, dtype=np.float64), (rows, m))
+        Ad = np.broadcast_to(np.asarray(A_desired, dtype=np.float64), (rows, m))
+        de = Vd - np.einsum("rij,rj->ri", J, qd2)
+
+        def gain(K, x, name):
+            K = np.asarray(K, dtype=np.float64)
+            if K.ndim == 2:
+                if K.shape != (m, m):
+                    raise ValueError(f"{name} must be a scalar, ({m},) or ({m}, {m}); got {K.shape}")
+                return x @ K.T
+            if K.ndim == 1 and K.shape != (m,):
+                raise ValueError(f"{name} must be a scalar, ({m},) or ({m}, {m}); got {K.shape}")
+            return K * x
+
+        acc = Ad + gain(Kd, de, "Kd") + gain(Kp, e, "Kp")
+        t0 = None if tau_null is None else np.atleast_2d(np.asarray(tau_null, dtype=np.float64))
+        tau = execute_registered_kernel("dynamics.operational_space_torque", model, q2, qd2, acc, g, t0, frame, task, damping)
+        return tau[0] if single else tau
+
     def robust_control(self, thetalist, dthetalist, ddthetalist, g, Ftip, disturbance_estimate, adaptation_gain) -> np.ndarray:
         """M qdd + c + g + J^T Ftip + gain * disturbance estimate (reference control/robust_adaptive.py:17-66): the first four
         terms ARE inverse dynamics, so this is one launch plus an addition."""

@@ -7,6 +7,7 @@
 
 #include <atomic>
 #include <set>
+#include <cmath>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -954,6 +955,53 @@ static int kin_vjp_impl(const char* fn, mp_ctx* ctx, const mp_model* model, int 
           "%s: device pointers must be 16-byte aligned", fn);
   PROFILE_SCOPE(ctx, fn);
   HIP_TRY(mpk_fk_jac_vjp(ctx->compute, model->d, frame, d_q, d_gT, d_gJ, d_T, d_J, d_gq, (long)rows));
+  return MP_OK;
+}
+
+// operational-space dynamics and task-space torque (mp_opspace.h): float64, unrolled models only; frame 0 = space, 1 = body,
+// 2 = hybrid; task 0 = full, 1 = linear, 2 = angular
+static int opspace_args(const char* fn, int frame, int task, double damping, int64_t rows) {
+  REQUIRE(frame >= 0 && frame <= 2, "%s: frame must be 0 (space), 1 (body) or 2 (hybrid), got %d", fn, frame);
+  REQUIRE(task >= 0 && task <= 2, "%s: task must be 0 (full), 1 (linear) or 2 (angular), got %d", fn, task);
+  REQUIRE(std::isfinite(damping) && damping >= 0.0, "%s: damping must be finite and >= 0", fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  return MP_OK;
+}
+static int opspace_impl(const char* fn, mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* d_q,
+                        const double* d_qd, int64_t rows, const double* g, double* d_T, double* d_J, double* d_Jdqd, double* d_Lambda,
+                        double* d_Jbar, double* d_mu, double* d_p) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  if (int rc = opspace_args(fn, frame, task, damping, rows)) return rc;
+  if (rows == 0) return MP_OK;
+  REQUIRE(d_q && d_qd, "%s: null device pointer", fn);
+  REQUIRE(d_T || d_J || d_Jdqd || d_Lambda || d_Jbar || d_mu || d_p, "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_q) && aligned16(d_qd) && aligned16(d_T) && aligned16(d_J) && aligned16(d_Jdqd) && aligned16(d_Lambda) &&
+              aligned16(d_Jbar) && aligned16(d_mu) && aligned16(d_p),
+          "%s: device pointers must be 16-byte aligned", fn);
+  MpCall<double> c;
+  make_call<double>(model, g, nullptr, &c);
+  PROFILE_SCOPE(ctx, fn);
+  HIP_TRY(mpk_opspace(ctx->compute, model->d, c, frame, task, damping * damping, d_q, d_qd, d_T, d_J, d_Jdqd, d_Lambda, d_Jbar, d_mu, d_p,
+                      (long)rows));
+  return MP_OK;
+}
+static int opspace_torque_impl(const char* fn, mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* d_q,
+                               const double* d_qd, const double* d_acc, const double* d_tau0, int64_t rows, const double* g,
+                               double* d_tau) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  if (int rc = opspace_args(fn, frame, task, damping, rows)) return rc;
+  if (rows == 0) return MP_OK;
+  REQUIRE(d_q && d_qd && d_acc && d_tau, "%s: null device pointer", fn);
+  REQUIRE(aligned16(d_q) && aligned16(d_qd) && aligned16(d_acc) && aligned16(d_tau0) && aligned16(d_tau),
+          "%s: device pointers must be 16-byte aligned", fn);
+  MpCall<double> c;
+  make_call<double>(model, g, nullptr, &c);
+  PROFILE_SCOPE(ctx, fn);
+  HIP_TRY(mpk_opspace_torque(ctx->compute, model->d, c, frame, task, damping * damping, d_q, d_qd, d_acc, d_tau0, d_tau, (long)rows));
   return MP_OK;
 }
 
@@ -2274,6 +2322,15 @@ int mp_fk_jac_vjp_f64(mp_ctx* ctx, const mp_model* model, int frame, const doubl
                       int64_t rows, double* d_T, double* d_J, double* d_gq) {
   return kin_vjp_impl("mp_fk_jac_vjp_f64", ctx, model, frame, d_q, d_gT, d_gJ, rows, d_T, d_J, d_gq);
 }
+int mp_opspace_f64(mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* d_q, const double* d_qd,
+                   int64_t rows, const double* g, double* d_T, double* d_J, double* d_Jdqd, double* d_Lambda, double* d_Jbar, double* d_mu,
+                   double* d_p) {
+  return opspace_impl("mp_opspace_f64", ctx, model, frame, task, damping, d_q, d_qd, rows, g, d_T, d_J, d_Jdqd, d_Lambda, d_Jbar, d_mu, d_p);
+}
+int mp_opspace_torque_f64(mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* d_q, const double* d_qd,
+                          const double* d_acc, const double* d_tau0, int64_t rows, const double* g, double* d_tau) {
+  return opspace_torque_impl("mp_opspace_torque_f64", ctx, model, frame, task, damping, d_q, d_qd, d_acc, d_tau0, rows, g, d_tau);
+}
 int mp_id_regressor_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd, int64_t rows,
                         const double* g, const double* Ftip, double* d_Y, double* d_tau_ext) {
   return regressor_impl("mp_id_regressor_f64", ctx, model, d_q, d_qd, d_qdd, rows, g, Ftip, d_Y, d_tau_ext);
@@ -2512,6 +2569,66 @@ int mp_fk_jac_vjp_host_f64(mp_ctx* ctx, const mp_model* model, int frame, const 
   if (T) D2H(T, dT, tb);
   if (J) D2H(J, dJ, 6 * vb);
   if (gq) D2H(gq, dgq, vb);
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+
+int mp_opspace_host_f64(mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* q, const double* qd,
+                        int64_t rows, const double* g, double* T, double* J, double* Jdqd, double* Lambda, double* Jbar, double* mu,
+                        double* p) {
+  const char* fn = "mp_opspace_host_f64";
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  if (int rc = opspace_args(fn, frame, task, damping, rows)) return rc;
+  if (rows == 0) return MP_OK;
+  REQUIRE(q && qd, "%s: null host pointer", fn);
+  REQUIRE(T || J || Jdqd || Lambda || Jbar || mu || p, "%s: at least one output is required", fn);
+  const size_t n = (size_t)model->d.n, m = task == 0 ? 6 : 3, rb = (size_t)rows * sizeof(double);
+  double* const host[7] = {T, J, Jdqd, Lambda, Jbar, mu, p};
+  const size_t bytes[7] = {16 * rb, m * n * rb, m * rb, m * m * rb, n * m * rb, m * rb, m * rb};
+  Scratch sc(ctx);
+  void *dq, *dqd, *dev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (int rc = sc.get(n * rb, &dq)) return rc;
+  if (int rc = sc.get(n * rb, &dqd)) return rc;
+  for (int k = 0; k < 7; ++k)
+    if (host[k]) if (int rc = sc.get(bytes[k], &dev[k])) return rc;
+  H2D(dq, q, n * rb);
+  H2D(dqd, qd, n * rb);
+  if (int rc = opspace_impl(fn, ctx, model, frame, task, damping, (double*)dq, (double*)dqd, rows, g, (double*)dev[0], (double*)dev[1],
+                            (double*)dev[2], (double*)dev[3], (double*)dev[4], (double*)dev[5], (double*)dev[6]))
+    return rc;
+  for (int k = 0; k < 7; ++k)
+    if (host[k]) D2H(host[k], dev[k], bytes[k]);
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+
+int mp_opspace_torque_host_f64(mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* q, const double* qd,
+                               const double* acc, const double* tau0, int64_t rows, const double* g, double* tau) {
+  const char* fn = "mp_opspace_torque_host_f64";
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  if (int rc = opspace_args(fn, frame, task, damping, rows)) return rc;
+  if (rows == 0) return MP_OK;
+  REQUIRE(q && qd && acc && tau, "%s: null host pointer", fn);
+  const size_t vb = (size_t)rows * (size_t)model->d.n * sizeof(double), ab = (size_t)rows * (task == 0 ? 6 : 3) * sizeof(double);
+  Scratch sc(ctx);
+  void *dq, *dqd, *dacc, *dt0 = nullptr, *dtau;
+  if (int rc = sc.get(vb, &dq)) return rc;
+  if (int rc = sc.get(vb, &dqd)) return rc;
+  if (int rc = sc.get(ab, &dacc)) return rc;
+  if (tau0) if (int rc = sc.get(vb, &dt0)) return rc;
+  if (int rc = sc.get(vb, &dtau)) return rc;
+  H2D(dq, q, vb);
+  H2D(dqd, qd, vb);
+  H2D(dacc, acc, ab);
+  if (dt0) H2D(dt0, tau0, vb);
+  if (int rc = opspace_torque_impl(fn, ctx, model, frame, task, damping, (double*)dq, (double*)dqd, (double*)dacc, (double*)dt0, rows, g,
+                                   (double*)dtau))
+    return rc;
+  D2H(tau, dtau, vb);
   HIP_TRY(hipStreamSynchronize(ctx->compute));
   return MP_OK;
 }

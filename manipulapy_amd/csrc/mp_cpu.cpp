@@ -21,6 +21,7 @@
 #include "mp_deriv.h"
 #include "mp_adjoint.h"
 #include "mp_kin_vjp.h"
+#include "mp_opspace.h"
 #include "mp_dyn.h"
 #include "mp_ik.h"
 #include "mp_handles.h"
@@ -516,6 +517,62 @@ int mp_fk_jac_vjp_cpu_f64(const mp_model* model, int frame, const double* q, con
         if (frame == 0) mp_fk_jac_vjp_row<double, N, 0>(M, q, gT, gJ, T, J, gq, (long)r);
         else mp_fk_jac_vjp_row<double, N, 1>(M, q, gT, gJ, T, J, gq, (long)r);
       }
+    });
+  })
+  return MP_OK;
+}
+// operational-space dynamics and task-space torque (mp_opspace.h): the kernels' per-row code over host rows
+static int opspace_cpu_check(const char* fn, const mp_model* model, int frame, int task, double damping, int64_t rows) {
+  char msg[192];
+  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
+  if (model->big) {
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (frame < 0 || frame > 2) {
+    std::snprintf(msg, sizeof msg, "%s: frame must be 0 (space), 1 (body) or 2 (hybrid), got %d", fn, frame);
+    return fail(msg);
+  }
+  if (task < 0 || task > 2) {
+    std::snprintf(msg, sizeof msg, "%s: task must be 0 (full), 1 (linear) or 2 (angular), got %d", fn, task);
+    return fail(msg);
+  }
+  if (!(std::isfinite(damping) && damping >= 0.0)) { std::snprintf(msg, sizeof msg, "%s: damping must be finite and >= 0", fn); return fail(msg); }
+  if (rows < 0) { std::snprintf(msg, sizeof msg, "%s: negative row count", fn); return fail(msg); }
+  return MP_OK;
+}
+int mp_opspace_cpu_f64(const mp_model* model, int frame, int task, double damping, const double* q, const double* qd, int64_t rows,
+                       const double* g, double* T, double* J, double* Jdqd, double* Lambda, double* Jbar, double* mu, double* p,
+                       int nthreads) {
+  const char* fn = "mp_opspace_cpu_f64";
+  char msg[192];
+  if (int rc = opspace_cpu_check(fn, model, frame, task, damping, rows)) return rc;
+  if (rows == 0) return MP_OK;
+  if (!q || !qd) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
+  if (!T && !J && !Jdqd && !Lambda && !Jbar && !mu && !p) { std::snprintf(msg, sizeof msg, "%s: at least one output is required", fn); return fail(msg); }
+  const MpModel<double>& M = model->d;
+  const MpCall<double> C = make_call<double>(model, g, nullptr);
+  const double lam2 = damping * damping;
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(rows, 64, nthreads, [&](int64_t lo, int64_t hi) {
+      for (int64_t r = lo; r < hi; ++r) mp_opspace_cpu_row<N>(M, C, frame, task, lam2, q, qd, T, J, Jdqd, Lambda, Jbar, mu, p, (long)r);
+    });
+  })
+  return MP_OK;
+}
+int mp_opspace_torque_cpu_f64(const mp_model* model, int frame, int task, double damping, const double* q, const double* qd,
+                              const double* acc, const double* tau0, int64_t rows, const double* g, double* tau, int nthreads) {
+  const char* fn = "mp_opspace_torque_cpu_f64";
+  char msg[192];
+  if (int rc = opspace_cpu_check(fn, model, frame, task, damping, rows)) return rc;
+  if (rows == 0) return MP_OK;
+  if (!q || !qd || !acc || !tau) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
+  const MpModel<double>& M = model->d;
+  const MpCall<double> C = make_call<double>(model, g, nullptr);
+  const double lam2 = damping * damping;
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(rows, 64, nthreads, [&](int64_t lo, int64_t hi) {
+      for (int64_t r = lo; r < hi; ++r) mp_opspace_torque_cpu_row<N>(M, C, frame, task, lam2, q, qd, acc, tau0, tau, (long)r);
     });
   })
   return MP_OK;

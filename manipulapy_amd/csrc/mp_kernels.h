@@ -49,6 +49,13 @@ hipError_t mpk_fd_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<doub
 // and Tout / Jout / gq (outputs) may be null
 hipError_t mpk_fk_jac_vjp(hipStream_t s, const MpModel<double>& M, int frame, const double* q, const double* gT, const double* gJ,
                          double* Tout, double* Jout, double* gq, long rows);
+// operational-space dynamics and task-space torque (csrc/mp_opspace.h), float64, 1..MP_MAX_DOF joints; frame 0 = space, 1 = body,
+// 2 = hybrid; task 0 = full, 1 = linear, 2 = angular; lam2 = damping^2; every output of mpk_opspace and tau0 may be null
+hipError_t mpk_opspace(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, int frame, int task, double lam2, const double* q,
+                       const double* qd, double* Tout, double* Jout, double* Jdqd, double* Lam, double* Jbar, double* mu, double* p,
+                       long rows);
+hipError_t mpk_opspace_torque(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, int frame, int task, double lam2,
+                              const double* q, const double* qd, const double* acc, const double* tau0, double* tau, long rows);
 // reverse mode through the roll-out (csrc/mp_rollout_vjp.h) on the time-major layout: taumat / Ftipmat / gp / gv / ga / gtau (Nt, B, *),
 // theta0 / dtheta0 / gth0 / gdth0 (B, n); Ftipmat and the cotangents may be null; `work` holds (B Nt + B intRes) 2n doubles
 // dynamics regressor (csrc/mp_regressor.h), float64, 1..MP_MAX_DOF joints; Dmap = the model's n x 100 inertial-parameter map in

@@ -14,6 +14,7 @@
 #include "mp_deriv.h"
 #include "mp_adjoint.h"
 #include "mp_kin_vjp.h"
+#include "mp_opspace.h"
 #include "mp_dyn.h"
 #include "mp_ik.h"
 #include "mp_kernels.h"
@@ -407,6 +408,122 @@ __global__ __launch_bounds__(kFkBlock) void k_fk_jac_vjp(const MpModel<double> M
   if (gq != nullptr) {
     mp_poison_if(poison, g);
     mp_wave_store_auto<double, N>(gq, row0, lane, nvalid, g, lds);
+  }
+}
+
+// ------------------------------------------------------- operational-space dynamics and torque (float64, mp_opspace.h)
+// One lane per row, one wave per block.  A full wave moves its 64 rows of q / qd as whole lines (MpRowStage, two regions of the
+// wave's slice); the last, partial wave reads per lane and its out-of-range lanes recompute the last row and store nothing.
+template <int N>
+__device__ __forceinline__ void mp_os_rows_in(const double* __restrict__ q, const double* __restrict__ qd, long row0, long rr, int lane,
+                                              bool full, double (&a)[N], double (&b)[N], char* __restrict__ lds) {
+  using ST = MpRowStage<double, N>;
+  static_assert(2 * ST::SPAN <= MP_WAVE_LDS_BYTES, "two arrays' 64 rows fit the wave's staging slice");
+  if (full) {
+    mp_u4 bq[ST::NJ], bd[ST::NJ];
+    ST::fetch(q, row0, lane, bq);
+    ST::fetch(qd, row0, lane, bd);
+    ST::stage(bq, lane, lds);
+    ST::stage(bd, lane, lds + ST::SPAN);
+    ST::sync();
+    ST::row_in(lds, lane, a);
+    ST::row_in(lds + ST::SPAN, lane, b);
+    ST::sync();
+  } else {
+    RunIO<double, N>::load(q, rr, a);
+    RunIO<double, N>::load(qd, rr, b);
+  }
+}
+// one more (rows, COUNT) input array, the same way
+template <int COUNT>
+__device__ __forceinline__ void mp_os_row_in(const double* __restrict__ x, long row0, long rr, int lane, bool full, double (&v)[COUNT],
+                                             char* __restrict__ lds) {
+  using ST = MpRowStage<double, COUNT>;
+  if (full) {
+    mp_u4 bx[ST::NJ];
+    ST::fetch(x, row0, lane, bx);
+    ST::stage(bx, lane, lds);
+    ST::sync();
+    ST::row_in(lds, lane, v);
+    ST::sync();
+  } else {
+    RunIO<double, COUNT>::load(x, rr, v);
+  }
+}
+
+// the wave-cooperative stores of k_fk_jac_vjp as mp_opspace_row's output functor: every lane of the wave calls it
+struct MpOsWaveOut {
+  long row0;
+  int lane, nvalid;
+  char* lds;
+  template <int COUNT>
+  __device__ __forceinline__ void operator()(double* __restrict__ base, const double (&v)[COUNT]) const {
+    mp_wave_store_auto<double, COUNT>(base, row0, lane, nvalid, v, lds);
+  }
+};
+
+// T, J, Jdot qd, Lambda, Jbar, mu, p of every row: frame / task / the null outputs are wave-uniform branches of one instance per N
+template <int N>
+__global__ __launch_bounds__(kDerivBlock) void k_opspace(const MpModel<double> M, const MpCall<double> C, int frame, int task, double lam2,
+                                                         const double* __restrict__ q, const double* __restrict__ qd,
+                                                         double* __restrict__ Tout, double* __restrict__ Jout, double* __restrict__ Jdqd,
+                                                         double* __restrict__ Lam, double* __restrict__ Jbar, double* __restrict__ mu,
+                                                         double* __restrict__ p, long rows) {
+  __shared__ __attribute__((aligned(16))) char lds[MP_WAVE_LDS_BYTES];
+  const int lane = (int)threadIdx.x;
+  const long row0 = (long)blockIdx.x * kDerivBlock;
+  if (row0 >= rows) return;
+  const long left = rows - row0;
+  const int nvalid = left < 64 ? (int)left : 64;
+  const long rr = lane < nvalid ? row0 + lane : rows - 1;
+  double a[N], b[N];
+  mp_os_rows_in<N>(q, qd, row0, rr, lane, nvalid == 64, a, b, lds);
+  MpBad<double> bad;
+  bad.add(a); bad.add(b);
+  const MpOsWaveOut out{row0, lane, nvalid, lds};
+  mp_opspace_row<N>(M, C, frame, task, lam2, a, b, bad.any(), out, Tout, Jout, Jdqd, Lam, Jbar, mu, p);
+}
+
+// The hot path: q, qd, the task acceleration (rows, m) and tau0 (rows, n; may be null) in, tau (rows, n) out - nothing wider than a
+// row of n values touches memory.
+template <int N>
+__global__ __launch_bounds__(kDerivBlock) void k_opspace_torque(const MpModel<double> M, const MpCall<double> C, int frame, int task,
+                                                                double lam2, const double* __restrict__ q, const double* __restrict__ qd,
+                                                                const double* __restrict__ acc, const double* __restrict__ tau0,
+                                                                double* __restrict__ tau, long rows) {
+  using ST = MpRowStage<double, N>;
+  __shared__ __attribute__((aligned(16))) char lds[MP_WAVE_LDS_BYTES];
+  const int lane = (int)threadIdx.x;
+  const long row0 = (long)blockIdx.x * kDerivBlock;
+  if (row0 >= rows) return;
+  const long left = rows - row0;
+  const int nvalid = left < 64 ? (int)left : 64;
+  const bool full = nvalid == 64;
+  const long rr = lane < nvalid ? row0 + lane : rows - 1;
+  double a[N], b[N], x[6], t0[N], t[N];
+  mp_os_rows_in<N>(q, qd, row0, rr, lane, full, a, b, lds);
+  if (task == 0) {
+    mp_os_row_in<6>(acc, row0, rr, lane, full, x, lds);
+  } else {
+    double x3[3];
+    mp_os_row_in<3>(acc, row0, rr, lane, full, x3, lds);
+    x[0] = x3[0]; x[1] = x3[1]; x[2] = x3[2]; x[3] = 0.0; x[4] = 0.0; x[5] = 0.0;
+  }
+  if (tau0 != nullptr) {
+    mp_os_row_in<N>(tau0, row0, rr, lane, full, t0, lds);
+  } else {
+#pragma unroll
+    for (int k = 0; k < N; ++k) t0[k] = 0.0;
+  }
+  MpBad<double> bad;
+  bad.add(a); bad.add(b); bad.add(x); bad.add(t0);
+  mp_opspace_torque_row<N>(M, C, frame, task, lam2, a, b, x, t0, bad.any(), t);
+  if (full) {
+    ST::row_out(lds, lane, t);
+    ST::sync();
+    ST::flush(tau, row0, lane, lds);
+  } else if (lane < nvalid) {
+    RunIO<double, N>::store(tau, rr, t);
   }
 }
 
@@ -1003,6 +1120,28 @@ hipError_t mpk_fk_jac_vjp(hipStream_t s, const MpModel<double>& M, int frame, co
   MP_DISPATCH_N(M.n, {
     if (frame == 0) hipLaunchKernelGGL((k_fk_jac_vjp<N, 0>), dim3(gb), dim3(kFkBlock), 0, s, M, q, gT, gJ, Tout, Jout, gq, rows);
     else hipLaunchKernelGGL((k_fk_jac_vjp<N, 1>), dim3(gb), dim3(kFkBlock), 0, s, M, q, gT, gJ, Tout, Jout, gq, rows);
+  })
+  return hipGetLastError();
+}
+
+hipError_t mpk_opspace(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, int frame, int task, double lam2, const double* q,
+                       const double* qd, double* Tout, double* Jout, double* Jdqd, double* Lam, double* Jbar, double* mu, double* p,
+                       long rows) {
+  if (rows <= 0) return hipSuccess;
+  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(M.n, {
+    hipLaunchKernelGGL((k_opspace<N>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, frame, task, lam2, q, qd, Tout, Jout, Jdqd, Lam, Jbar, mu, p,
+                       rows);
+  })
+  return hipGetLastError();
+}
+
+hipError_t mpk_opspace_torque(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, int frame, int task, double lam2,
+                              const double* q, const double* qd, const double* acc, const double* tau0, double* tau, long rows) {
+  if (rows <= 0) return hipSuccess;
+  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(M.n, {
+    hipLaunchKernelGGL((k_opspace_torque<N>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, frame, task, lam2, q, qd, acc, tau0, tau, rows);
   })
   return hipGetLastError();
 }

@@ -238,6 +238,31 @@ class ManipulatorDynamics(SerialManipulator):
         _, gq, gqd, gtau = self._vjp("dynamics.fwd_vjp", "forward_dynamics_vjp", thetalist, dthetalist, taulist, gqdd, g, Ftip)
         return gq, gqd, gtau
 
+    # ---- operational-space dynamics and task-space torque (float64, n <= 8; csrc/mp_opspace.h)
+    def operational_space_dynamics(self, thetalist, dthetalist, g, frame: str = "hybrid", task: str = "full", damping: float = 0.0) -> dict:
+        """{"T", "J", "Jdot_qd", "Lambda", "Jbar", "mu", "p"} of the tool in `frame` ("space", "body", or "hybrid": angular and
+        tool-origin velocity in space axes) for the rows of `task` ("full": [w; v], m = 6; "linear": v; "angular": w; m = 3):
+        Lambda = (J M^-1 J^T + damping^2 1)^-1, Jbar = M^-1 J^T Lambda, mu = Lambda (J M^-1 c - Jdot qd), p = Lambda J M^-1 g.
+        Shapes (4, 4), (m, n), (m,), (m, m), (n, m), (m,), (m,) for 1-D inputs, with a leading rows axis for 2-D ones (one g for all
+        rows).  A singular pose with damping = 0 gives NaN in Lambda, Jbar, mu and p of that row only."""
+        model = self._derivative_model("operational_space_dynamics")
+        one = np.ndim(thetalist) == 1
+        q, qd = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (thetalist, dthetalist))
+        out = execute_registered_kernel("dynamics.operational_space", model, q, qd, g, frame, task, damping)
+        return {k: v[0] for k, v in out.items()} if one else out
+
+    def operational_space_torque(self, thetalist, dthetalist, task_acceleration, g, tau_null=None, frame: str = "hybrid",
+                                 task: str = "full", damping: float = 0.0) -> np.ndarray:
+        """tau = J^T (Lambda a* + mu + p) + (1 - J^T Jbar^T) tau_null for the task acceleration a* ((m,) or (rows, m)): with
+        damping = 0, forward_dynamics of it gives J qdd + Jdot qd = a* whatever tau_null is.  One launch; no Jacobian, mass matrix or
+        Lambda leaves the device.  A tip wrench F is the caller's J^T F."""
+        model = self._derivative_model("operational_space_torque")
+        one = np.ndim(thetalist) == 1
+        q, qd, acc = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (thetalist, dthetalist, task_acceleration))
+        t0 = None if tau_null is None else np.atleast_2d(np.asarray(tau_null, dtype=np.float64))
+        tau = execute_registered_kernel("dynamics.operational_space_torque", model, q, qd, acc, g, t0, frame, task, damping)
+        return tau[0] if one else tau
+
     # ---- dynamics regressor and inertial-parameter identification (float64, n <= 8; csrc/mp_regressor.h)
     # pi_i = [m, hx, hy, hz, Ixx, Ixy, Ixz, Iyy, Iyz, Izz] in link i's CoM frame at the home pose (Mlist_per_link[i]): h = m c with c
     # the centre of mass from that frame's origin, I the inertia about that origin.  tau = Y pi + tau_ext (tau_ext: the tip wrench's

@@ -311,6 +311,14 @@ def _launch_fk_jac_vjp_cpu(model, q, gT=None, gJ=None, frame="space", want_T=Fal
     return _hip.cpu_fk_jac_vjp(model, q, gT, gJ, frame, want_T, want_J, want_gq)
 
 
+def _launch_opspace_cpu(model, q, qd, g=None, frame="hybrid", task="full", damping=0.0, want=_hip.OPSPACE_OUTPUTS):
+    return _hip.cpu_opspace(model, q, qd, g, frame, task, damping, want)
+
+
+def _launch_opspace_torque_cpu(model, q, qd, acc, g=None, tau0=None, frame="hybrid", task="full", damping=0.0):
+    return _hip.cpu_opspace_torque(model, q, qd, acc, g, tau0, frame, task, damping)
+
+
 def _launch_id_regressor_cpu(model, q, qd, qdd, g=None, Ftip=None):
     return _hip.cpu_id_regressor(model, q, qd, qdd, g, Ftip)
 
@@ -451,6 +459,14 @@ def _launch_fk_jac_vjp_gpu(model, q, gT=None, gJ=None, frame="space", want_T=Fal
     return get_context().fk_jac_vjp_host(model, q, gT, gJ, frame, want_T, want_J, want_gq)
 
 
+def _launch_opspace_gpu(model, q, qd, g=None, frame="hybrid", task="full", damping=0.0, want=_hip.OPSPACE_OUTPUTS):
+    return get_context().opspace_host(model, q, qd, g, frame, task, damping, want)
+
+
+def _launch_opspace_torque_gpu(model, q, qd, acc, g=None, tau0=None, frame="hybrid", task="full", damping=0.0):
+    return get_context().opspace_torque_host(model, q, qd, acc, g, tau0, frame, task, damping)
+
+
 def _launch_id_regressor_gpu(model, q, qd, qdd, g=None, Ftip=None):
     return get_context().id_regressor_host(model, q, qd, qdd, g, Ftip)
 
@@ -547,6 +563,9 @@ def _build_kernel_registry() -> KernelRegistry:
         # vector-Jacobian products by reverse mode (csrc/mp_adjoint.h); both names sort after "dynamics.forward_trajectory"
         ("dynamics.inverse_vjp", "mp_id_vjp_host_f64", _launch_id_vjp_gpu, _launch_id_vjp_cpu),
         ("dynamics.fwd_vjp", "mp_fd_vjp_host_f64", _launch_fd_vjp_gpu, _launch_fd_vjp_cpu),
+        # operational-space dynamics and task-space torque (csrc/mp_opspace.h); both names sort after "dynamics.forward_trajectory"
+        ("dynamics.operational_space", "mp_opspace_host_f64", _launch_opspace_gpu, _launch_opspace_cpu),
+        ("dynamics.operational_space_torque", "mp_opspace_torque_host_f64", _launch_opspace_torque_gpu, _launch_opspace_torque_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):

@@ -78,15 +78,34 @@ def MatrixLog3(R) -> np.ndarray:
     """so(3) logarithm as a skew matrix (utils/so3.py:172-191)."""
     R = np.asarray(R, dtype=np.float64)
     cs, theta = _cos_and_angle(R)
-    if theta > np.pi - 1e-2:
+    if theta > np.pi - _HALF_TURN_BAND:
         return skew_symmetric(theta * _half_turn_axis(R, cs))
+    return 0.5 * float(_log3_coefficient(cs)) * (R - R.T)
+
+
+_HALF_TURN_BAND = 1e-2  # rad from pi within which the logarithm's axis comes from the symmetric part
+
+
+def _log3_coefficient(cs):
+    """theta / sin(theta) from cos(theta), a scalar or an array: the Taylor band above cos = 1 - 5e-5, acos of the clipped cosine
+    elsewhere (utils/so3.py:172-191).  Not for the half-turn band, where sin(theta) vanishes."""
+    cs = np.asarray(cs, dtype=np.float64)
     u = 1.0 - cs
-    if cs > 1.0 - 5e-5:
-        coef = 1.0 + u / 3.0 + u * u * (4.0 / 45.0)
-    else:
-        c = float(np.clip(cs, -1.0 + 1e-7, 1.0 - 1e-7))
-        coef = np.arccos(c) / np.sqrt(max(1.0 - c * c, 1e-30))
-    return 0.5 * coef * (R - R.T)
+    c = np.clip(cs, -1.0 + 1e-7, 1.0 - 1e-7)
+    return np.where(cs > 1.0 - 5e-5, 1.0 + u / 3.0 + u * u * (4.0 / 45.0), np.arccos(c) / np.sqrt(np.maximum(1.0 - c * c, 1e-30)))
+
+
+def rotation_log_rows(R) -> np.ndarray:
+    """The rotation vectors log(R)v of (rows, 3, 3) rotations, (rows, 3): MatrixLog3 on whole arrays, with its angle, bands and
+    coefficient.  The rows in the half-turn band, where the axis comes from the symmetric part, go through MatrixLog3 one by one."""
+    R = np.asarray(R, dtype=np.float64)
+    vee = np.stack([R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]], axis=1)
+    cs = np.clip((np.trace(R, axis1=1, axis2=2) - 1.0) / 2.0, -1.0, 1.0)
+    theta = np.arctan2(np.sqrt(np.maximum(np.sum(vee * vee, axis=1), 1e-300)) / 2.0, cs)  # _cos_and_angle, row by row
+    out = 0.5 * _log3_coefficient(cs)[:, None] * vee
+    for r in np.nonzero(theta > np.pi - _HALF_TURN_BAND)[0]:
+        out[r] = skew_symmetric_to_vector(MatrixLog3(R[r]))
+    return out
 
 
 def _exp3_coefficients(t2: float) -> Tuple[float, float]:
