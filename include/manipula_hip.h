@@ -378,6 +378,50 @@ int mp_fd_trajectory_vjp_tm_f64(mp_ctx* ctx, const mp_model* model, const double
                                 const double* d_taumat, const double* d_Ftipmat, int64_t B, int64_t N, const double* g, double dt,
                                 int intRes, const double* d_gpos, const double* d_gvel, const double* d_gacc, void* d_work,
                                 double* d_gtheta0, double* d_gdtheta0, double* d_gtaumat);
+/* Batched iLQR about a roll-out (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED above that; intRes = 1, gravity per call, no tip
+ * wrench; N >= 2, else MP_ERR_INVALID): the Riccati backward pass and the closed-loop roll-out (csrc/mp_ilqr.h).  No counterpart in this
+ * ABI's reference interface.  Indexing is the roll-out's: rows i = 0..N-1, row 0 the given state, torque row i >= 1 drives step i
+ * (torque row 0 is unused), h = dt:
+ *     a = FD(q_{i-1}, qd_{i-1}, u_i; g),  qd_i = qd_{i-1} + h a,  w = q_{i-1} + h qd_i,  q_i = clip(w, qmin, qmax),
+ *     m = [qmin <= w <= qmax]  (inclusive, as the roll-out's gradient)
+ * State x = (q, qd).  With Aq = da/dq, Av = da/dqd, Mi = M^-1 - the three blocks of mp_fd_derivatives_f64 at (q_{i-1}, qd_{i-1}, u_i) -
+ *     A_i = [[m (1 + h^2 Aq), m h (1 + h Av)], [h Aq, 1 + h Av]],    B_i = [[m h^2 Mi], [h Mi]]      (m scales rows)
+ * Cost per trajectory, diagonal weights shared by the batch (host vectors wq, wf of 2n and wr of n entries), e = x - xref, xref per
+ * trajectory (N rows of 2n):
+ *     J = 1/2 sum_{i=1}^{N-1} u_i^T wr u_i + 1/2 sum_{i=1}^{N-2} e_i^T wq e_i + 1/2 e_{N-1}^T wf e_{N-1}
+ * Backward pass, i = N-1 .. 1, from S = diag(wf), s = wf e_{N-1}:
+ *     Qx = A^T s,  Qu = wr u_i + B^T s,  Qxx = A^T S A,  Quu = diag(wr) + B^T S B,  Qux = B^T S A
+ *     K_i = -(Quu + reg 1)^-1 Qux,  k_i = -(Quu + reg 1)^-1 Qu  (Cholesky),  dV1 += k_i^T Qu,  dV2 += 1/2 k_i^T Quu k_i
+ *     s <- Qx + K^T Quu k + K^T Qu + Qux^T k,  S <- Qxx + K^T Quu K + K^T Qux + Qux^T K  (the unregularised Quu; S kept symmetric)
+ *     if i - 1 >= 1:  s += wq e_{i-1},  S += diag(wq)
+ * reg (B) is per trajectory.  Outputs: K (N rows of n x 2n, row 0 zero), k (N rows of n, row 0 zero), dV (B,2) = (dV1, dV2), status (B)
+ * int32: 0 fine; i > 0 the factor of Quu + reg 1 met a pivot at or below 2^-46 of its diagonal term first at step i - that trajectory
+ * gets K = 0, k = 0, dV = 0; -1 a non-finite input - that trajectory's K, k (rows 1..N-1) and dV are NaN.
+ * Roll-out: A B lanes, lane (a, b) runs trajectory b with u_i = tau_i + alpha[a,b] k_i + K_i (x_{i-1} - xbar_{i-1}) about the nominal
+ * (pos, vel) with the roll-out's own step arithmetic; cost (A,B) = J; opos / ovel / otau (all three or none) receive the float64 states
+ * and the applied torques (row 0 = theta0, dtheta0, torque row 0).  K and k may both be NULL (open loop: pos / vel are not read).  A
+ * trajectory with a non-finite input or state gets a NaN cost and NaN rows.
+ *   _tm_f64:   device pointers on the time-major layout: pos / vel / taumat (N,B,n), xref (N,B,2n), K (N,B,n,2n), k (N,B,n), opos /
+ *              ovel / otau (N,A B,n); the blocks are those of the (N-1) B rows (pos[0:N-1], vel[0:N-1], taumat[1:N]) - contiguous
+ *              slices, so mp_fd_derivatives_f64 produces them as they are (with B n odd the torque slice starts 8 bytes off the
+ *              16-byte boundary that entry asks for: copy it first - mp_transpose_rows with outer = 1 is a device copy).  The kernel
+ *              runs 16 lanes a trajectory with the value matrix in LDS and needs no workspace:
+ *              mp_ilqr_backward_workspace_bytes(model, B, N) is 0 and d_work may be NULL.  (MANIPULAPY_HIP_ILQR_BACKWARD=lane, read at
+ *              every call, selects the one-lane-per-trajectory kernel kept for A/B measurements; the byte count is then 12 n^2 B
+ *              doubles and d_work is required.)  Asynchronous (no synchronisation, no allocation: may be captured into a launch graph).
+ *   _host_f64: batch-major host arrays (B,N,*), K (B,N,n,2n), opos / ovel / otau (A,B,N,n); converted on the device, memory from the
+ *              context's pool.  The backward form runs the derivative launch itself.
+ *   _cpu_f64:  the CPU twins of the host forms.
+ * mp_ilqr_backward_workspace_bytes returns the byte count, or minus an MP_ERR_* code. */
+int64_t mp_ilqr_backward_workspace_bytes(const mp_model* model, int64_t B, int64_t N);
+int mp_ilqr_backward_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_pos, const double* d_vel, const double* d_taumat,
+                            const double* d_dqdd_dq, const double* d_dqdd_dqd, const double* d_Minv, const double* d_xref,
+                            const double* wq, const double* wr, const double* wf, const double* d_reg, int64_t B, int64_t N, double dt,
+                            void* d_work, double* d_K, double* d_k, double* d_dV, int32_t* d_status);
+int mp_ilqr_rollout_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_theta0, const double* d_dtheta0, const double* d_taumat,
+                           const double* d_pos, const double* d_vel, const double* d_K, const double* d_k, const double* d_alpha,
+                           const double* d_xref, const double* wq, const double* wr, const double* wf, int64_t A, int64_t B, int64_t N,
+                           const double* g, double dt, double* d_cost, double* d_opos, double* d_ovel, double* d_otau);
 /* d_dst (inner, outer, row_bytes) <- d_src (outer, inner, row_bytes): converts between the batch-major API arrays
  * (B,N,n) and the time-major layout (N,B,n), either way.  row_bytes: a multiple of 4, at most 256 (32 float64 joints). */
 int mp_transpose_rows(mp_ctx* ctx, const void* d_src, int64_t outer, int64_t inner, int64_t row_bytes, void* d_dst);
@@ -429,6 +473,13 @@ int mp_fd_trajectory_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const doub
                                   const double* taumat, const double* Ftipmat, int64_t B, int64_t N, const double* g, double dt,
                                   int intRes, const double* gpos, const double* gvel, const double* gacc, double* gtheta0,
                                   double* gdtheta0, double* gtaumat);
+int mp_ilqr_backward_host_f64(mp_ctx* ctx, const mp_model* model, const double* pos, const double* vel, const double* taumat,
+                              const double* xref, const double* wq, const double* wr, const double* wf, const double* reg, int64_t B,
+                              int64_t N, const double* g, double dt, double* K, double* k, double* dV, int32_t* status);
+int mp_ilqr_rollout_host_f64(mp_ctx* ctx, const mp_model* model, const double* theta0, const double* dtheta0, const double* taumat,
+                             const double* pos, const double* vel, const double* K, const double* k, const double* alpha,
+                             const double* xref, const double* wq, const double* wr, const double* wf, int64_t A, int64_t B, int64_t N,
+                             const double* g, double dt, double* cost, double* opos, double* ovel, double* otau);
 int mp_forward_dynamics_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd,
                                  const double* tau, int64_t rows, const double* g, const double* Ftip, double* qdd);
 int mp_id_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd,
@@ -524,6 +575,13 @@ int mp_id_regressor_cpu_f64(const mp_model* model, const double* q, const double
                             const double* Ftip, double* Y, double* tau_ext, int nthreads);
 int mp_id_regressor_normal_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, const double* rhs,
                                    int64_t rows, const double* g, const double* Ftip, double* A, double* b, double* rr, int nthreads);
+int mp_ilqr_backward_cpu_f64(const mp_model* model, const double* pos, const double* vel, const double* taumat, const double* xref,
+                             const double* wq, const double* wr, const double* wf, const double* reg, int64_t B, int64_t N,
+                             const double* g, double dt, double* K, double* k, double* dV, int32_t* status, int nthreads);
+int mp_ilqr_rollout_cpu_f64(const mp_model* model, const double* theta0, const double* dtheta0, const double* taumat, const double* pos,
+                            const double* vel, const double* K, const double* k, const double* alpha, const double* xref,
+                            const double* wq, const double* wr, const double* wf, int64_t A, int64_t B, int64_t N, const double* g,
+                            double dt, double* cost, double* opos, double* ovel, double* otau, int nthreads);
 int mp_fd_trajectory_vjp_cpu_f64(const mp_model* model, const double* theta0, const double* dtheta0, const double* taumat,
                                  const double* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, const double* gpos,
                                  const double* gvel, const double* gacc, double* gtheta0, double* gdtheta0, double* gtaumat,

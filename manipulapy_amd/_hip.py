@@ -131,6 +131,13 @@ SIGNATURES = {
     "mp_fd_trajectory_vjp_workspace_bytes": (ctypes.c_int64, [_vp, _i64, _i64, ctypes.c_int]),
     "mp_fd_trajectory_vjp_tm_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_fd_trajectory_vjp_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_ilqr_backward_workspace_bytes": (ctypes.c_int64, [_vp, _i64, _i64]),
+    "mp_ilqr_backward_tm_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_dp, _c_dp, _c_dp, _vp, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "mp_ilqr_rollout_tm_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "mp_ilqr_backward_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, _c_dp, _c_dp, _c_dp, _vp]),
+    "mp_ilqr_rollout_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, ctypes.c_double, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_ilqr_backward_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, _c_dp, _c_dp, _c_dp, _vp, ctypes.c_int]),
+    "mp_ilqr_rollout_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, ctypes.c_double, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_fd_trajectory_host_f32": (ctypes.c_int, [_vp, _vp, _c_fp, _c_fp, _c_fp, _c_fp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp]),
     "mp_fd_trajectory_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp]),
     "mp_cartesian_trajectory_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp]),
@@ -1000,6 +1007,36 @@ class HipContext:
                     b.free()
         return gth, gdth, gtau
 
+    def ilqr_backward(self, model, d_pos, d_vel, d_taumat, d_dq, d_dqd, d_Minv, d_xref, wq, wr, wf, d_reg, B, N, dt, d_work, d_K, d_k,
+                      d_dV, d_status):
+        """The Riccati backward pass on device buffers (float64, csrc/mp_ilqr.h), time-major pos / vel / taumat (N, B, n), xref
+        (N, B, 2n), the blocks of mp_fd_derivatives_f64 over the (N - 1) B rows (pos[0:N-1], vel[0:N-1], taumat[1:N]), reg (B); writes
+        K (N, B, n, 2n), k (N, B, n), dV (B, 2), status (B) int32; d_work holds ilqr_backward_workspace_bytes(model, B, N) (0: may be None).
+        Asynchronous (capturable)."""
+        wq, wr, wf = _ilqr_weights(model, wq, wr, wf)
+        _check(self.lib.mp_ilqr_backward_tm_f64(self.handle, model.handle, _p(d_pos), _p(d_vel), _p(d_taumat), _p(d_dq), _p(d_dqd),
+                                                _p(d_Minv), _p(d_xref), _dptr(wq), _dptr(wr), _dptr(wf), _p(d_reg), int(B), int(N),
+                                                float(dt), _p(d_work), _p(d_K), _p(d_k), _p(d_dV), _p(d_status)))
+
+    def ilqr_rollout(self, model, d_theta0, d_dtheta0, d_taumat, d_pos, d_vel, d_K, d_k, d_alpha, d_xref, wq, wr, wf, A, B, N, g, dt,
+                     d_cost, d_opos=None, d_ovel=None, d_otau=None):
+        """The closed-loop roll-out on device buffers: A B lanes, alpha / cost (A, B), the float64 rows (N, A B, n) when the three
+        outputs are given; d_K / d_k (and then d_pos / d_vel) may be None for the open loop.  Asynchronous (capturable)."""
+        wq, wr, wf = _ilqr_weights(model, wq, wr, wf)
+        _check(self.lib.mp_ilqr_rollout_tm_f64(self.handle, model.handle, _p(d_theta0), _p(d_dtheta0), _p(d_taumat), _p(d_pos), _p(d_vel),
+                                               _p(d_K), _p(d_k), _p(d_alpha), _p(d_xref), _dptr(wq), _dptr(wr), _dptr(wf), int(A), int(B),
+                                               int(N), _dptr(_vec_or_none(g, 3, "g")), float(dt), _p(d_cost), _p(d_opos), _p(d_ovel),
+                                               _p(d_otau)))
+
+    def ilqr_backward_host(self, model: HipModel, pos, vel, taumat, xref, wq, wr, wf, reg, g, dt):
+        """(K (B, N, n, 2n), k (B, N, n), dV (B, 2), status (B) int32) of batch-major host arrays; the derivative launch is part of it."""
+        return _ilqr_backward(self.lib.mp_ilqr_backward_host_f64, (self.handle,), model, pos, vel, taumat, xref, wq, wr, wf, reg, g, dt)
+
+    def ilqr_rollout_host(self, model: HipModel, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr, wf, g, dt, want_rows=True):
+        """(cost (A, B), pos, vel, tau (A, B, N, n) or None) of batch-major host arrays; alpha (A, B); K / k may be None."""
+        return _ilqr_rollout(self.lib.mp_ilqr_rollout_host_f64, (self.handle,), model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref,
+                             wq, wr, wf, g, dt, want_rows)
+
     def fd_trajectory(self, model, d_theta0, d_dtheta0, d_taumat, d_Ftipmat, B, N, g, dt, intRes, d_pos, d_vel, d_acc,
                       dtype=np.float32, time_major: bool = False):
         """Device pointers.  time_major=False: taumat (B,N,n), Ftipmat (B,N,6), outputs (B,N,n); True: (N,B,*) throughout."""
@@ -1381,6 +1418,78 @@ def cpu_fd_trajectory_vjp(model: "HipModel", theta0, dtheta0, taumat, g, Ftipmat
                                                        _dptr(_vec_or_none(g, 3, "g")), float(dt), int(intRes), *[_dptr(x) for x in G],
                                                        _dptr(gth), _dptr(gdth), _dptr(gtau), int(nthreads)))
     return gth, gdth, gtau
+
+
+def _ilqr_weights(model, wq, wr, wf):
+    n = model.n
+    return _as_c(wq, np.float64, (2 * n,), "wq"), _as_c(wr, np.float64, (n,), "wr"), _as_c(wf, np.float64, (2 * n,), "wf")
+
+
+def _ilqr_rows(model, taumat, others):
+    tm = _as_c(taumat, np.float64, name="taumat")
+    if tm.ndim != 3 or tm.shape[2] != model.n:
+        raise ValueError(f"taumat must be (B, N, {model.n}); got {tm.shape}")
+    return tm, [None if a is None else _as_c(a, np.float64, tm.shape[:2] + (w,), name) for a, w, name in others]
+
+
+def ilqr_backward_workspace_bytes(model: "HipModel", B: int, N: int) -> int:
+    """Device workspace of mp_ilqr_backward_tm_f64: 0 for the cooperative kernel that ships (pass any buffer, or None); 12 n^2 B doubles
+    under MANIPULAPY_HIP_ILQR_BACKWARD=lane."""
+    v = int(load_library().mp_ilqr_backward_workspace_bytes(model.handle, int(B), int(N)))
+    if v < 0:
+        _check(-v)
+    return v
+
+
+def _ilqr_backward(fn, lead, model, pos, vel, taumat, xref, wq, wr, wf, reg, g, dt, nthreads=None):
+    n = model.n
+    tm, (p, v, x) = _ilqr_rows(model, taumat, ((pos, n, "pos"), (vel, n, "vel"), (xref, 2 * n, "xref")))
+    B, N = tm.shape[:2]
+    wq, wr, wf = _ilqr_weights(model, wq, wr, wf)
+    rg = _as_c(np.broadcast_to(np.asarray(reg, dtype=np.float64), (B,)), np.float64, (B,), "reg")
+    K, k, dV, st = np.zeros((B, N, n, 2 * n)), np.zeros((B, N, n)), np.zeros((B, 2)), np.zeros(B, dtype=np.int32)
+    args = list(lead) + [model.handle, _dptr(p), _dptr(v), _dptr(tm), _dptr(x), _dptr(wq), _dptr(wr), _dptr(wf), _dptr(rg), B, N,
+                         _dptr(_vec_or_none(g, 3, "g")), float(dt), _dptr(K), _dptr(k), _dptr(dV), st.ctypes.data_as(_vp)]
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return K, k, dV, st
+
+
+def _ilqr_rollout(fn, lead, model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr, wf, g, dt, want_rows, nthreads=None):
+    n = model.n
+    tm, (p, v, x, kk) = _ilqr_rows(model, taumat, ((pos, n, "pos"), (vel, n, "vel"), (xref, 2 * n, "xref"), (k, n, "k")))
+    B, N = tm.shape[:2]
+    th, dth = _as_c(theta0, np.float64, (B, n), "theta0"), _as_c(dtheta0, np.float64, (B, n), "dtheta0")
+    KK = None if K is None else _as_c(K, np.float64, (B, N, n, 2 * n), "K")
+    if (KK is None) != (kk is None) or (KK is not None and (p is None or v is None)):
+        raise ValueError("K and k must both be given, with the nominal pos and vel, or both be None")
+    al = _as_c(alpha, np.float64, name="alpha")
+    if al.ndim != 2 or al.shape[1] != B:
+        raise ValueError(f"alpha must be (A, {B}); got {al.shape}")
+    A = al.shape[0]
+    wq, wr, wf = _ilqr_weights(model, wq, wr, wf)
+    cost = np.zeros((A, B))
+    rows = [np.zeros((A, B, N, n)) for _ in range(3)] if want_rows else [None, None, None]
+    args = list(lead) + [model.handle, _dptr(th), _dptr(dth), _dptr(tm), _dptr(p), _dptr(v), _dptr(KK), _dptr(kk), _dptr(al), _dptr(x),
+                         _dptr(wq), _dptr(wr), _dptr(wf), A, B, N, _dptr(_vec_or_none(g, 3, "g")), float(dt), _dptr(cost)] \
+        + [_dptr(r) for r in rows]
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return cost, rows[0], rows[1], rows[2]
+
+
+def cpu_ilqr_backward(model: "HipModel", pos, vel, taumat, xref, wq, wr, wf, reg, g, dt, nthreads: int = 0):
+    """CPU twin of HipContext.ilqr_backward_host: (K (B, N, n, 2n), k (B, N, n), dV (B, 2), status (B))."""
+    return _ilqr_backward(load_library().mp_ilqr_backward_cpu_f64, (), model, pos, vel, taumat, xref, wq, wr, wf, reg, g, dt, nthreads)
+
+
+def cpu_ilqr_rollout(model: "HipModel", theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr, wf, g, dt, want_rows=True,
+                     nthreads: int = 0):
+    """CPU twin of HipContext.ilqr_rollout_host: (cost (A, B), pos, vel, tau (A, B, N, n) or None)."""
+    return _ilqr_rollout(load_library().mp_ilqr_rollout_cpu_f64, (), model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr,
+                         wf, g, dt, want_rows, nthreads)
 
 
 def cpu_cartesian_trajectory(Xstart, Xend, Tf, N, method, nthreads: int = 0):

@@ -22,6 +22,7 @@
 #include "../../include/manipula_hip.h"
 #include "mp_jit.h"
 #include "mp_ik.h"
+#include "mp_ilqr.h"
 #include "mp_kernels.h"
 #include "mp_model_compile.h"
 #include "mp_handles.h"
@@ -1143,6 +1144,213 @@ static int fdtraj_vjp_host_impl(const char* fn, mp_ctx* ctx, const mp_model* mod
     D2H((char*)gtheta0 + b0 * sr, dg0, nb * sr);
     D2H((char*)gdtheta0 + b0 * sr, dg1, nb * sr);
     D2H((char*)gtaumat + b0 * tr, stage, nb * tr);
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+
+// batched iLQR (mp_ilqr.h): float64, unrolled models only, intRes = 1.  The weights are host vectors (2n, n, 2n) and travel as kernel
+// arguments.  k_batch_major: K / k are (B, N, ...) instead of (N, B, ...) - what the host forms hand back.
+static int ilqr_weights(const char* fn, int n, const double* wq, const double* wr, const double* wf, MpIlqrWeights* W) {
+  REQUIRE(wq && wr && wf, "%s: null weight vector", fn);
+  std::memset(W, 0, sizeof *W);
+  for (int j = 0; j < 2 * n; ++j) {
+    REQUIRE(std::isfinite(wq[j]) && std::isfinite(wf[j]), "%s: non-finite weight", fn);
+    W->wq[j] = wq[j];
+    W->wf[j] = wf[j];
+  }
+  for (int j = 0; j < n; ++j) {
+    REQUIRE(std::isfinite(wr[j]), "%s: non-finite weight", fn);
+    W->wr[j] = wr[j];
+  }
+  return MP_OK;
+}
+// MANIPULAPY_HIP_ILQR_BACKWARD=lane (read at every call): the one-lane-per-trajectory kernel and its global workspace instead of the
+// cooperative LDS kernel - kept for A/B measurements (tools/ilqr_bench.py)
+static bool ilqr_lane_variant() {
+  const char* e = getenv("MANIPULAPY_HIP_ILQR_BACKWARD");
+  return e && std::strcmp(e, "lane") == 0;
+}
+static int ilqr_backward_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* d_pos, const double* d_vel,
+                              const double* d_taumat, const double* d_dq, const double* d_dqd, const double* d_Minv, const double* d_xref,
+                              const double* wq, const double* wr, const double* wf, const double* d_reg, int64_t B, int64_t N, double dt,
+                              bool k_batch_major, void* d_work, double* d_K, double* d_k, double* d_dV, int32_t* d_status) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(B >= 0, "%s: negative B (%lld)", fn, (long long)B);
+  REQUIRE(N >= 2, "%s: N must be >= 2 (got %lld)", fn, (long long)N);
+  MpIlqrWeights W;
+  if (int rc = ilqr_weights(fn, model->d.n, wq, wr, wf, &W)) return rc;
+  if (B == 0) return MP_OK;
+  const bool lane = ilqr_lane_variant();
+  REQUIRE(d_pos && d_vel && d_taumat && d_dq && d_dqd && d_Minv && d_xref && d_reg && (d_work || !lane) && d_K && d_k && d_dV && d_status,
+          "%s: null device pointer", fn);
+  REQUIRE(aligned16(d_pos) && aligned16(d_vel) && aligned16(d_taumat) && aligned16(d_dq) && aligned16(d_dqd) && aligned16(d_Minv) &&
+              aligned16(d_xref) && aligned16(d_reg) && aligned16(d_work) && aligned16(d_K) && aligned16(d_k) && aligned16(d_dV) &&
+              aligned16(d_status),
+          "%s: device pointers must be 16-byte aligned", fn);
+  PROFILE_SCOPE(ctx, fn);
+  HIP_TRY(mpk_ilqr_backward(ctx->compute, model->d, W, d_pos, d_vel, d_taumat, d_dq, d_dqd, d_Minv, d_xref, d_reg, (long)B, (long)N, dt,
+                            k_batch_major, lane ? (double*)d_work : nullptr, d_K, d_k, d_dV, (int*)d_status));
+  return MP_OK;
+}
+static int ilqr_rollout_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* d_theta0, const double* d_dtheta0,
+                             const double* d_taumat, const double* d_pos, const double* d_vel, const double* d_K, const double* d_k,
+                             const double* d_alpha, const double* d_xref, const double* wq, const double* wr, const double* wf, int64_t A,
+                             int64_t B, int64_t N, const double* g, double dt, bool k_batch_major, double* d_cost, double* d_opos,
+                             double* d_ovel, double* d_otau) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(A >= 0 && B >= 0, "%s: negative A (%lld) or B (%lld)", fn, (long long)A, (long long)B);
+  REQUIRE(N >= 2, "%s: N must be >= 2 (got %lld)", fn, (long long)N);
+  MpIlqrWeights W;
+  if (int rc = ilqr_weights(fn, model->d.n, wq, wr, wf, &W)) return rc;
+  if (A == 0 || B == 0) return MP_OK;
+  REQUIRE(d_theta0 && d_dtheta0 && d_taumat && d_alpha && d_xref && d_cost, "%s: null device pointer", fn);
+  REQUIRE((d_K != nullptr) == (d_k != nullptr), "%s: K and k must both be given or both be null", fn);
+  REQUIRE(!d_K || (d_pos && d_vel), "%s: the gains need the nominal pos and vel", fn);
+  REQUIRE((d_opos != nullptr) == (d_ovel != nullptr) && (d_opos != nullptr) == (d_otau != nullptr),
+          "%s: the three row outputs must all be given or all be null", fn);
+  REQUIRE(aligned16(d_theta0) && aligned16(d_dtheta0) && aligned16(d_taumat) && aligned16(d_pos) && aligned16(d_vel) && aligned16(d_K) &&
+              aligned16(d_k) && aligned16(d_alpha) && aligned16(d_xref) && aligned16(d_cost) && aligned16(d_opos) && aligned16(d_ovel) &&
+              aligned16(d_otau),
+          "%s: device pointers must be 16-byte aligned", fn);
+  MpCall<double> c;
+  make_call<double>(model, g, nullptr, &c);
+  PROFILE_SCOPE(ctx, fn);
+  HIP_TRY(mpk_ilqr_rollout(ctx->compute, model->d, c, W, d_theta0, d_dtheta0, d_taumat, d_pos, d_vel, d_K, d_k, d_alpha, d_xref, (long)A,
+                           (long)B, (long)N, dt, k_batch_major, d_cost, d_opos, d_ovel, d_otau));
+  return MP_OK;
+}
+// batch-major host arrays: upload -> (B, N, *) to (N, B, *) on the device -> the derivative launch and the backward pass -> download;
+// the kernel writes K / k batch-major itself (a row of K is wider than mp_transpose_rows moves)
+static int ilqr_backward_host_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* pos, const double* vel,
+                                   const double* taumat, const double* xref, const double* wq, const double* wr, const double* wf,
+                                   const double* reg, int64_t B, int64_t N, const double* g, double dt, double* K, double* k, double* dV,
+                                   int32_t* status) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(B >= 0, "%s: negative B (%lld)", fn, (long long)B);
+  REQUIRE(N >= 2, "%s: N must be >= 2 (got %lld)", fn, (long long)N);
+  if (B == 0) return MP_OK;
+  REQUIRE(pos && vel && taumat && xref && reg && K && k && dV && status, "%s: null host pointer", fn);
+  const int n = model->d.n;
+  const size_t sr = (size_t)n * sizeof(double), tr = (size_t)N * sr, blk = (size_t)(N - 1) * B * n * sr;
+  Scratch sc(ctx);
+  void *dp, *dv, *dt_, *dx, *dr, *dq, *dqd, *dmi, *dwork, *dK, *dk, *ddV, *dst, *stage;
+  if (int rc = sc.get(B * tr, &dp)) return rc;
+  if (int rc = sc.get(B * tr, &dv)) return rc;
+  if (int rc = sc.get(B * tr, &dt_)) return rc;
+  if (int rc = sc.get(2 * B * tr, &dx)) return rc;
+  if (int rc = sc.get(B * sizeof(double), &dr)) return rc;
+  if (int rc = sc.get(blk, &dq)) return rc;
+  if (int rc = sc.get(blk, &dqd)) return rc;
+  if (int rc = sc.get(blk, &dmi)) return rc;
+  if (int rc = sc.get(ilqr_lane_variant() ? (size_t)B * mp_ilqr_work_doubles(n) * sizeof(double) : 0, &dwork)) return rc;
+  if (int rc = sc.get(2 * B * tr * n, &dK)) return rc;
+  if (int rc = sc.get(B * tr, &dk)) return rc;
+  if (int rc = sc.get(B * 2 * sizeof(double), &ddV)) return rc;
+  if (int rc = sc.get(B * sizeof(int32_t), &dst)) return rc;
+  if (int rc = sc.get(2 * B * tr, &stage)) return rc;
+  auto up_tm = [&](const double* src, size_t row, void* dst_) -> int {  // (B, N, row) host -> (N, B, row) device
+    H2D(stage, src, B * row * N);
+    return mp_transpose_rows(ctx, stage, B, N, (int64_t)row, dst_);
+  };
+  if (int rc = up_tm(pos, sr, dp)) return rc;
+  if (int rc = up_tm(vel, sr, dv)) return rc;
+  if (int rc = up_tm(taumat, sr, dt_)) return rc;
+  if (int rc = up_tm(xref, 2 * sr, dx)) return rc;
+  H2D(dr, reg, B * sizeof(double));
+  const double* dtau1 = (const double*)dt_ + B * n;  // torque rows 1..N-1; with B n odd they start 8 bytes off the alignment asked for
+  if ((B * n) & 1) {
+    void* cp;
+    if (int rc = sc.get((size_t)(N - 1) * B * sr, &cp)) return rc;
+    if (int rc = mp_transpose_rows(ctx, dtau1, 1, (N - 1) * B, (int64_t)sr, cp)) return rc;  // outer = 1: a device copy
+    dtau1 = (const double*)cp;
+  }
+  if (int rc = deriv_impl(fn, true, ctx, model, (double*)dp, (double*)dv, dtau1, (N - 1) * B, g, nullptr, nullptr, (double*)dq,
+                          (double*)dqd, (double*)dmi))
+    return rc;
+  if (int rc = ilqr_backward_impl(fn, ctx, model, (double*)dp, (double*)dv, (double*)dt_, (double*)dq, (double*)dqd, (double*)dmi,
+                                  (double*)dx, wq, wr, wf, (double*)dr, B, N, dt, true, dwork, (double*)dK, (double*)dk, (double*)ddV,
+                                  (int32_t*)dst))
+    return rc;
+  D2H(K, dK, 2 * B * tr * n);
+  D2H(k, dk, B * tr);
+  D2H(dV, ddV, B * 2 * sizeof(double));
+  D2H(status, dst, B * sizeof(int32_t));
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+static int ilqr_rollout_host_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* theta0, const double* dtheta0,
+                                  const double* taumat, const double* pos, const double* vel, const double* K, const double* k,
+                                  const double* alpha, const double* xref, const double* wq, const double* wr, const double* wf, int64_t A,
+                                  int64_t B, int64_t N, const double* g, double dt, double* cost, double* opos, double* ovel,
+                                  double* otau) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(A >= 0 && B >= 0, "%s: negative A (%lld) or B (%lld)", fn, (long long)A, (long long)B);
+  REQUIRE(N >= 2, "%s: N must be >= 2 (got %lld)", fn, (long long)N);
+  if (A == 0 || B == 0) return MP_OK;
+  REQUIRE(theta0 && dtheta0 && taumat && alpha && xref && cost, "%s: null host pointer", fn);
+  REQUIRE((K != nullptr) == (k != nullptr), "%s: K and k must both be given or both be null", fn);
+  REQUIRE(!K || (pos && vel), "%s: the gains need the nominal pos and vel", fn);
+  REQUIRE((opos != nullptr) == (ovel != nullptr) && (opos != nullptr) == (otau != nullptr),
+          "%s: the three row outputs must all be given or all be null", fn);
+  const int n = model->d.n;
+  const size_t sr = (size_t)n * sizeof(double), tr = (size_t)N * sr, L = (size_t)A * B;
+  Scratch sc(ctx);
+  void *d0, *d1, *dt_, *dp = nullptr, *dv = nullptr, *dK = nullptr, *dk = nullptr, *da, *dx, *dc, *dop = nullptr, *dov = nullptr,
+       *dot = nullptr, *stage;
+  if (int rc = sc.get(B * sr, &d0)) return rc;
+  if (int rc = sc.get(B * sr, &d1)) return rc;
+  if (int rc = sc.get(B * tr, &dt_)) return rc;
+  if (K) {
+    if (int rc = sc.get(B * tr, &dp)) return rc;
+    if (int rc = sc.get(B * tr, &dv)) return rc;
+    if (int rc = sc.get(2 * B * tr * n, &dK)) return rc;
+    if (int rc = sc.get(B * tr, &dk)) return rc;
+  }
+  if (int rc = sc.get(L * sizeof(double), &da)) return rc;
+  if (int rc = sc.get(2 * B * tr, &dx)) return rc;
+  if (int rc = sc.get(L * sizeof(double), &dc)) return rc;
+  if (opos) {
+    if (int rc = sc.get(L * tr, &dop)) return rc;
+    if (int rc = sc.get(L * tr, &dov)) return rc;
+    if (int rc = sc.get(L * tr, &dot)) return rc;
+  }
+  if (int rc = sc.get(std::max(2 * B * tr, opos ? L * tr : (size_t)0), &stage)) return rc;
+  auto up_tm = [&](const double* src, size_t row, void* dst_) -> int {
+    H2D(stage, src, B * row * N);
+    return mp_transpose_rows(ctx, stage, B, N, (int64_t)row, dst_);
+  };
+  H2D(d0, theta0, B * sr);
+  H2D(d1, dtheta0, B * sr);
+  if (int rc = up_tm(taumat, sr, dt_)) return rc;
+  if (K) {
+    if (int rc = up_tm(pos, sr, dp)) return rc;
+    if (int rc = up_tm(vel, sr, dv)) return rc;
+    H2D(dK, K, 2 * B * tr * n);
+    H2D(dk, k, B * tr);
+  }
+  if (int rc = up_tm(xref, 2 * sr, dx)) return rc;
+  H2D(da, alpha, L * sizeof(double));
+  if (int rc = ilqr_rollout_impl(fn, ctx, model, (double*)d0, (double*)d1, (double*)dt_, (double*)dp, (double*)dv, (double*)dK, (double*)dk,
+                                 (double*)da, (double*)dx, wq, wr, wf, A, B, N, g, dt, true, (double*)dc, (double*)dop, (double*)dov,
+                                 (double*)dot))
+    return rc;
+  D2H(cost, dc, L * sizeof(double));
+  if (opos) {
+    void* outs[3] = {dop, dov, dot};
+    double* hosts[3] = {opos, ovel, otau};
+    for (int i = 0; i < 3; ++i) {  // (N, A B, n) -> (A B, N, n), staged in stream order
+      if (int rc = mp_transpose_rows(ctx, outs[i], N, (int64_t)L, (int64_t)sr, stage)) return rc;
+      D2H(hosts[i], stage, L * tr);
+    }
   }
   HIP_TRY(hipStreamSynchronize(ctx->compute));
   return MP_OK;
@@ -2367,6 +2575,41 @@ int mp_fd_trajectory_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const doub
                                   double* gdtheta0, double* gtaumat) {
   return fdtraj_vjp_host_impl("mp_fd_trajectory_vjp_host_f64", ctx, model, theta0, dtheta0, taumat, Ftipmat, B, N, g, dt, intRes, gpos,
                               gvel, gacc, gtheta0, gdtheta0, gtaumat);
+}
+int64_t mp_ilqr_backward_workspace_bytes(const mp_model* model, int64_t B, int64_t N) {
+  if (!model) return -set_err(MP_ERR_INVALID, "mp_ilqr_backward_workspace_bytes: null model");
+  if (B < 0 || N < 2) return -set_err(MP_ERR_INVALID, "mp_ilqr_backward_workspace_bytes: negative B, or N < 2");
+  if (model->big)
+    return -set_err(MP_ERR_UNSUPPORTED, "mp_ilqr_backward_workspace_bytes: not available for models with more than %d joints "
+                    "(this one has %d)", MP_MAX_DOF, model->d.n);
+  return ilqr_lane_variant() ? B * (int64_t)mp_ilqr_work_doubles(model->d.n) * (int64_t)sizeof(double) : 0;
+}
+int mp_ilqr_backward_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_pos, const double* d_vel, const double* d_taumat,
+                            const double* d_dqdd_dq, const double* d_dqdd_dqd, const double* d_Minv, const double* d_xref,
+                            const double* wq, const double* wr, const double* wf, const double* d_reg, int64_t B, int64_t N, double dt,
+                            void* d_work, double* d_K, double* d_k, double* d_dV, int32_t* d_status) {
+  return ilqr_backward_impl("mp_ilqr_backward_tm_f64", ctx, model, d_pos, d_vel, d_taumat, d_dqdd_dq, d_dqdd_dqd, d_Minv, d_xref, wq, wr, wf,
+                            d_reg, B, N, dt, false, d_work, d_K, d_k, d_dV, d_status);
+}
+int mp_ilqr_rollout_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_theta0, const double* d_dtheta0, const double* d_taumat,
+                           const double* d_pos, const double* d_vel, const double* d_K, const double* d_k, const double* d_alpha,
+                           const double* d_xref, const double* wq, const double* wr, const double* wf, int64_t A, int64_t B, int64_t N,
+                           const double* g, double dt, double* d_cost, double* d_opos, double* d_ovel, double* d_otau) {
+  return ilqr_rollout_impl("mp_ilqr_rollout_tm_f64", ctx, model, d_theta0, d_dtheta0, d_taumat, d_pos, d_vel, d_K, d_k, d_alpha, d_xref, wq,
+                           wr, wf, A, B, N, g, dt, false, d_cost, d_opos, d_ovel, d_otau);
+}
+int mp_ilqr_backward_host_f64(mp_ctx* ctx, const mp_model* model, const double* pos, const double* vel, const double* taumat,
+                              const double* xref, const double* wq, const double* wr, const double* wf, const double* reg, int64_t B,
+                              int64_t N, const double* g, double dt, double* K, double* k, double* dV, int32_t* status) {
+  return ilqr_backward_host_impl("mp_ilqr_backward_host_f64", ctx, model, pos, vel, taumat, xref, wq, wr, wf, reg, B, N, g, dt, K, k, dV,
+                                 status);
+}
+int mp_ilqr_rollout_host_f64(mp_ctx* ctx, const mp_model* model, const double* theta0, const double* dtheta0, const double* taumat,
+                             const double* pos, const double* vel, const double* K, const double* k, const double* alpha,
+                             const double* xref, const double* wq, const double* wr, const double* wf, int64_t A, int64_t B, int64_t N,
+                             const double* g, double dt, double* cost, double* opos, double* ovel, double* otau) {
+  return ilqr_rollout_host_impl("mp_ilqr_rollout_host_f64", ctx, model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr, wf, A,
+                                B, N, g, dt, cost, opos, ovel, otau);
 }
 int mp_fd_trajectory_f32(mp_ctx* ctx, const mp_model* model, const float* d_theta0, const float* d_dtheta0,
                          const float* d_taumat, const float* d_Ftipmat, int64_t B, int64_t N, const double* g, double dt,

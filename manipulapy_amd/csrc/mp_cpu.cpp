@@ -28,6 +28,7 @@
 #include "mp_model_compile.h"
 #include "mp_regressor.h"
 #include "mp_rollout_vjp.h"
+#include "mp_ilqr.h"
 
 namespace {
 const double kG[3] = {0.0, 0.0, -9.81};
@@ -696,6 +697,99 @@ int mp_fd_trajectory_vjp_cpu_f64(const mp_model* model, const double* theta0, co
                                        gtheta0 + s, gdtheta0 + s, gtaumat + o);
         else mp_fd_traj_vjp<N, false>(M, C, theta0 + s, dtheta0 + s, taumat + o, nullptr, 1, (long)Nt, h, intRes, gp, gv, ga, ck, 1, sub, 1,
                                       gtheta0 + s, gdtheta0 + s, gtaumat + o);
+      }
+    });
+  })
+  return MP_OK;
+}
+// batched iLQR (mp_ilqr.h): the kernels' per-trajectory code over batch-major host arrays.  The backward twin forms the derivative
+// blocks of its trajectory itself (mp_fd_deriv_row over rows (pos[0:N-1], vel[0:N-1], tau[1:N])), each thread with its own workspace.
+static int ilqr_cpu_check(const char* fn, const mp_model* model, int64_t B, int64_t Nt, const double* wq, const double* wr,
+                          const double* wf) {
+  char msg[192];
+  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
+  if (model->big) {
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (B < 0) { std::snprintf(msg, sizeof msg, "%s: negative B", fn); return fail(msg); }
+  if (Nt < 2) { std::snprintf(msg, sizeof msg, "%s: N must be >= 2 (got %lld)", fn, (long long)Nt); return fail(msg); }
+  if (!wq || !wr || !wf) { std::snprintf(msg, sizeof msg, "%s: null weight vector", fn); return fail(msg); }
+  for (int j = 0; j < 2 * model->d.n; ++j)
+    if (!std::isfinite(wq[j]) || !std::isfinite(wf[j]) || !std::isfinite(wr[j / 2])) {
+      std::snprintf(msg, sizeof msg, "%s: non-finite weight", fn);
+      return fail(msg);
+    }
+  return MP_OK;
+}
+int mp_ilqr_backward_cpu_f64(const mp_model* model, const double* pos, const double* vel, const double* taumat, const double* xref,
+                             const double* wq, const double* wr, const double* wf, const double* reg, int64_t B, int64_t Nt,
+                             const double* g, double dt, double* K, double* k, double* dV, int32_t* status, int nthreads) {
+  const char* fn = "mp_ilqr_backward_cpu_f64";
+  if (int rc = ilqr_cpu_check(fn, model, B, Nt, wq, wr, wf)) return rc;
+  if (B == 0) return MP_OK;
+  if (!pos || !vel || !taumat || !xref || !reg || !K || !k || !dV || !status) {
+    char msg[96];
+    std::snprintf(msg, sizeof msg, "%s: null pointer", fn);
+    return fail(msg);
+  }
+  const MpModel<double>& M = model->d;
+  const MpCall<double> C = make_call<double>(model, g, nullptr);
+  // MANIPULAPY_ILQR_CPU_FORM=coop (read at every call): the cooperative form of the device kernel, lane by lane, instead of the
+  // one-lane-per-trajectory form - for tests of that form without a GPU
+  const char* form = getenv("MANIPULAPY_ILQR_CPU_FORM");
+  const bool coop = form && std::strcmp(form, "coop") == 0;
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(B, 1, nthreads, [&](int64_t lo, int64_t hi) {
+      const size_t blk = (size_t)(Nt - 1) * N * N;
+      std::vector<double> buf(3 * blk + (size_t)mp_ilqr_work_doubles(N));
+      double *dq = buf.data(), *dqd = dq + blk, *mi = dqd + blk, *work = mi + blk;
+      for (int64_t b = lo; b < hi; ++b) {
+        const int64_t o = b * Nt * N;
+        for (int64_t r = 0; r + 1 < Nt; ++r)
+          mp_fd_deriv_row<N, false>(M, C, pos + o, vel + o, taumat + o + N, nullptr, dq, dqd, mi, (long)r);
+        int st = 0;
+        if (coop) {   // the device's cooperative form, its 16 lanes run in turn phase by phase
+          const MpIlqrArgs A{pos + o, vel + o, taumat + o, 1, (long)Nt, dt, dq, dqd, mi, 1, xref + 2 * o, 1, wq, wr, wf, reg[b],
+                             K + 2 * o * N, k + o, 1, dV + 2 * b, &st, true};
+          mp_ilqr_backward_coop_host<N>(M, A);
+        } else {
+          mp_ilqr_backward<N>(M, pos + o, vel + o, taumat + o, 1, (long)Nt, dt, dq, dqd, mi, 1, xref + 2 * o, 1, wq, wr, wf, reg[b], work, 1,
+                              K + 2 * o * N, k + o, 1, dV + 2 * b, &st);
+        }
+        status[b] = st;
+      }
+    });
+  })
+  return MP_OK;
+}
+int mp_ilqr_rollout_cpu_f64(const mp_model* model, const double* theta0, const double* dtheta0, const double* taumat, const double* pos,
+                            const double* vel, const double* K, const double* k, const double* alpha, const double* xref,
+                            const double* wq, const double* wr, const double* wf, int64_t A, int64_t B, int64_t Nt, const double* g,
+                            double dt, double* cost, double* opos, double* ovel, double* otau, int nthreads) {
+  const char* fn = "mp_ilqr_rollout_cpu_f64";
+  if (int rc = ilqr_cpu_check(fn, model, B, Nt, wq, wr, wf)) return rc;
+  char msg[160];
+  if (A < 0) { std::snprintf(msg, sizeof msg, "%s: negative A", fn); return fail(msg); }
+  if (A == 0 || B == 0) return MP_OK;
+  if (!theta0 || !dtheta0 || !taumat || !alpha || !xref || !cost) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
+  if ((K != nullptr) != (k != nullptr) || (K && (!pos || !vel))) {
+    std::snprintf(msg, sizeof msg, "%s: K and k must both be given, with the nominal pos and vel, or both be null", fn);
+    return fail(msg);
+  }
+  if ((opos != nullptr) != (ovel != nullptr) || (opos != nullptr) != (otau != nullptr)) {
+    std::snprintf(msg, sizeof msg, "%s: the three row outputs must all be given or all be null", fn);
+    return fail(msg);
+  }
+  const MpModel<double>& M = model->d;
+  const MpCall<double> C = make_call<double>(model, g, nullptr);
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(A * B, 1, nthreads, [&](int64_t lo, int64_t hi) {
+      for (int64_t l = lo; l < hi; ++l) {
+        const int64_t b = l % B, o = b * Nt * N, lo_ = l * Nt * N;
+        mp_ilqr_rollout<N>(M, C, theta0 + b * N, dtheta0 + b * N, taumat + o, K ? pos + o : nullptr, K ? vel + o : nullptr, 1,
+                           K ? K + 2 * o * N : nullptr, K ? k + o : nullptr, 1, alpha[l], xref + 2 * o, 1, wq, wr, wf, (long)Nt, dt,
+                           cost + l, opos ? opos + lo_ : nullptr, opos ? ovel + lo_ : nullptr, opos ? otau + lo_ : nullptr, 1);
       }
     });
   })

@@ -79,6 +79,21 @@ hipError_t mpk_id_regressor_normal(hipStream_t s, const MpModel<double>& M, cons
 hipError_t mpk_fd_traj_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, const double* theta0, const double* dtheta0,
                            const double* taumat, const double* Ftipmat, long B, long Nt, double h, int intRes, const double* gp,
                            const double* gv, const double* ga, double* work, double* gth0, double* gdth0, double* gtau);
+// batched iLQR (csrc/mp_ilqr.h) on the time-major layout, float64, 1..MP_MAX_DOF joints: pos / vel / tau (Nt, B, n), the derivative
+// blocks of the (Nt - 1) B rows (pos[0:Nt-1], vel[0:Nt-1], tau[1:Nt]), xref (Nt, B, 2n), reg (B).  work == nullptr: the cooperative
+// kernel (16 lanes a trajectory, LDS); otherwise the one-lane-per-trajectory kernel, `work` holding B mp_ilqr_work_doubles(n) doubles.  K (Nt, B, n, 2n) / k (Nt, B, n), or (B, Nt, ...) with k_batch_major.  The roll-out runs A B lanes: alpha / cost (A, B),
+// opos / ovel / otau (Nt, A B, n) or all null; K and k may both be null (open loop).
+struct MpIlqrWeights {
+  double wq[2 * MP_MAX_DOF], wr[MP_MAX_DOF], wf[2 * MP_MAX_DOF];
+};
+hipError_t mpk_ilqr_backward(hipStream_t s, const MpModel<double>& M, const MpIlqrWeights& Wt, const double* pos, const double* vel,
+                             const double* tau, const double* dq, const double* dqd, const double* Minv, const double* xref,
+                             const double* reg, long B, long Nt, double h, bool k_batch_major, double* work, double* K, double* k,
+                             double* dV, int* status);
+hipError_t mpk_ilqr_rollout(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, const MpIlqrWeights& Wt, const double* th0,
+                            const double* dth0, const double* tau, const double* pos, const double* vel, const double* K, const double* k,
+                            const double* alpha, const double* xref, long A, long B, long Nt, double h, bool k_batch_major, double* cost,
+                            double* opos, double* ovel, double* otau);
 // Ftipmat == nullptr: no tip wrench.  h = dt / intRes.  Outputs are float32 (B, Nt, n).
 template <typename T>
 hipError_t mpk_fd_traj(hipStream_t s, const MpModel<T>& M, const MpCall<T>& C, const T* theta0, const T* dtheta0,

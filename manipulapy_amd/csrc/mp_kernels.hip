@@ -20,6 +20,7 @@
 #include "mp_kernels.h"
 #include "mp_regressor.h"
 #include "mp_rollout_vjp.h"
+#include "mp_ilqr.h"
 
 namespace {
 
@@ -543,6 +544,78 @@ __global__ __launch_bounds__(kDerivBlock) void k_fd_traj_vjp(const MpModel<doubl
   double* sub = work + B * Nt * (2 * N) + b * (2 * N);
   mp_fd_traj_vjp<N, HAS_FTIP>(M, C, th0 + o, dth0 + o, taumat + o, HAS_FTIP ? Fm + b * 6 : nullptr, B, Nt, h, intRes, gp ? gp + o : nullptr,
                               gv ? gv + o : nullptr, ga ? ga + o : nullptr, ck, B, sub, B, gth0 + o, gdth0 + o, gtau + o);
+}
+
+// batched iLQR (mp_ilqr.h), one lane = one trajectory on the time-major layout like k_fd_traj_vjp.  The 2n x 2n value matrix and its
+// products live in `work` (element e of trajectory b at e B + b: a wave's lanes touch one run of doubles).  K / k rows: time-major
+// (N, B, *) or, kbm = 1, batch-major (B, N, *), which is what the host form hands back.
+template <int N>
+__global__ __launch_bounds__(kDerivBlock) void k_ilqr_backward(const MpModel<double> M, const MpIlqrWeights Wt, const double* __restrict__ pos,
+                                                               const double* __restrict__ vel, const double* __restrict__ tau,
+                                                               const double* __restrict__ dq, const double* __restrict__ dqd,
+                                                               const double* __restrict__ Minv, const double* __restrict__ xref,
+                                                               const double* __restrict__ reg, long B, long Nt, double h, int kbm,
+                                                               double* __restrict__ work, double* __restrict__ K, double* __restrict__ k,
+                                                               double* __restrict__ dV, int* __restrict__ status) {
+  const long b = (long)blockIdx.x * kDerivBlock + threadIdx.x;
+  if (b >= B) return;
+  const long o = b * N, kb = kbm ? b * Nt : b, ks = kbm ? 1 : B;
+  mp_ilqr_backward<N>(M, pos + o, vel + o, tau + o, B, Nt, h, dq + b * (N * N), dqd + b * (N * N), Minv + b * (N * N), B, xref + b * (2 * N),
+                      B, Wt.wq, Wt.wr, Wt.wf, reg[b], work + b, B, K + kb * (2 * N * N), k + kb * N, ks, dV + b * 2, status + b);
+}
+
+// The cooperative form (mp_ilqr.h): 16 lanes a trajectory, four trajectories a wave, one wave a workgroup.  S, R / G, Qux, K, Quu and the
+// step's blocks sit in LDS (7.3 KB a trajectory at n = 8); nothing but the inputs, K and k touches global memory.  A group past the end
+// of the batch runs trajectory B - 1 along (the barriers need every lane) and stores nothing.
+template <int N>
+__global__ __launch_bounds__(64) void k_ilqr_backward_coop(const MpModel<double> M, const MpIlqrWeights Wt, const double* __restrict__ pos,
+                                                           const double* __restrict__ vel, const double* __restrict__ tau,
+                                                           const double* __restrict__ dq, const double* __restrict__ dqd,
+                                                           const double* __restrict__ Minv, const double* __restrict__ xref,
+                                                           const double* __restrict__ reg, long B, long Nt, double h, int kbm,
+                                                           double* __restrict__ K, double* __restrict__ k, double* __restrict__ dV,
+                                                           int* __restrict__ status) {
+  __shared__ MpIlqrShared<N> shared[4];
+  const int grp = (int)threadIdx.x >> 4, lane = (int)threadIdx.x & 15;
+  long b = (long)blockIdx.x * 4 + grp;
+  const bool act = b < B;
+  if (!act) b = B - 1;
+  const long o = b * N, kb = kbm ? b * Nt : b, ks = kbm ? 1 : B;
+  const MpIlqrArgs A{pos + o, vel + o, tau + o, B, Nt, h, dq + b * (N * N), dqd + b * (N * N), Minv + b * (N * N), B, xref + b * (2 * N), B,
+                     Wt.wq, Wt.wr, Wt.wf, reg[b], K + kb * (2 * N * N), k + kb * N, ks, dV + b * 2, status + b, act};
+  MpIlqrShared<N>& sh = shared[grp];
+  MpIlqrLane<N> L;
+  mp_ilqr_coop_phase<N>(MP_ILQR_PH_INIT, 0, M, A, sh, L, lane);
+  __syncthreads();
+  for (long i = Nt - 1; i >= 1; --i) {
+    mp_ilqr_coop_phase<N>(0, i, M, A, sh, L, lane); __syncthreads();
+    mp_ilqr_coop_phase<N>(1, i, M, A, sh, L, lane); __syncthreads();
+    mp_ilqr_coop_phase<N>(2, i, M, A, sh, L, lane); __syncthreads();
+    mp_ilqr_coop_phase<N>(3, i, M, A, sh, L, lane); __syncthreads();
+    mp_ilqr_coop_phase<N>(4, i, M, A, sh, L, lane); __syncthreads();
+    mp_ilqr_coop_phase<N>(5, i, M, A, sh, L, lane); __syncthreads();
+  }
+  mp_ilqr_coop_phase<N>(MP_ILQR_PH_FLAG, 0, M, A, sh, L, lane);
+  __syncthreads();
+  mp_ilqr_coop_phase<N>(MP_ILQR_PH_FINAL, 0, M, A, sh, L, lane);
+}
+
+// one lane per (candidate a, trajectory b): lane l = a B + b reads trajectory b's nominal and gains and writes column l of the outputs
+template <int N>
+__global__ __launch_bounds__(kDerivBlock) void k_ilqr_rollout(const MpModel<double> M, const MpCall<double> C, const MpIlqrWeights Wt,
+                                                              const double* __restrict__ th0, const double* __restrict__ dth0,
+                                                              const double* __restrict__ tau, const double* __restrict__ pos,
+                                                              const double* __restrict__ vel, const double* __restrict__ K,
+                                                              const double* __restrict__ k, const double* __restrict__ alpha,
+                                                              const double* __restrict__ xref, long A, long B, long Nt, double h, int kbm,
+                                                              double* __restrict__ cost, double* __restrict__ opos,
+                                                              double* __restrict__ ovel, double* __restrict__ otau) {
+  const long l = (long)blockIdx.x * kDerivBlock + threadIdx.x;
+  if (l >= A * B) return;
+  const long b = l % B, o = b * N, kb = kbm ? b * Nt : b, ks = kbm ? 1 : B;
+  mp_ilqr_rollout<N>(M, C, th0 + o, dth0 + o, tau + o, K ? pos + o : nullptr, K ? vel + o : nullptr, B, K ? K + kb * (2 * N * N) : nullptr,
+                     K ? k + kb * N : nullptr, ks, alpha[l], xref + b * (2 * N), B, Wt.wq, Wt.wr, Wt.wf, Nt, h, cost + l,
+                     opos ? opos + l * N : nullptr, opos ? ovel + l * N : nullptr, opos ? otau + l * N : nullptr, A * B);
 }
 
 // ------------------------------------------------------- dynamics regressor (float64, mp_regressor.h)
@@ -1156,6 +1229,39 @@ hipError_t mpk_fd_traj_vjp(hipStream_t s, const MpModel<double>& M, const MpCall
                                     h, intRes, gp, gv, ga, work, gth0, gdth0, gtau);
     else hipLaunchKernelGGL((k_fd_traj_vjp<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt,
                             h, intRes, gp, gv, ga, work, gth0, gdth0, gtau);
+  })
+  return hipGetLastError();
+}
+
+hipError_t mpk_ilqr_backward(hipStream_t s, const MpModel<double>& M, const MpIlqrWeights& Wt, const double* pos, const double* vel,
+                             const double* tau, const double* dq, const double* dqd, const double* Minv, const double* xref,
+                             const double* reg, long B, long Nt, double h, bool k_batch_major, double* work, double* K, double* k,
+                             double* dV, int* status) {
+  if (B <= 0 || Nt <= 0) return hipSuccess;
+  if (!work) {   // no workspace: the cooperative form
+    if ((B + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
+    MP_DISPATCH_N(M.n, {
+      hipLaunchKernelGGL((k_ilqr_backward_coop<N>), dim3((unsigned)((B + 3) / 4)), dim3(64), 0, s, M, Wt, pos, vel, tau, dq, dqd, Minv, xref,
+                         reg, B, Nt, h, (int)k_batch_major, K, k, dV, status);
+    })
+    return hipGetLastError();
+  }
+  const unsigned gb = (unsigned)((B + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(M.n, {
+    hipLaunchKernelGGL((k_ilqr_backward<N>), dim3(gb), dim3(kDerivBlock), 0, s, M, Wt, pos, vel, tau, dq, dqd, Minv, xref, reg, B, Nt, h,
+                       (int)k_batch_major, work, K, k, dV, status);
+  })
+  return hipGetLastError();
+}
+hipError_t mpk_ilqr_rollout(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, const MpIlqrWeights& Wt, const double* th0,
+                            const double* dth0, const double* tau, const double* pos, const double* vel, const double* K, const double* k,
+                            const double* alpha, const double* xref, long A, long B, long Nt, double h, bool k_batch_major, double* cost,
+                            double* opos, double* ovel, double* otau) {
+  if (A <= 0 || B <= 0 || Nt <= 0) return hipSuccess;
+  const unsigned gb = (unsigned)((A * B + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(M.n, {
+    hipLaunchKernelGGL((k_ilqr_rollout<N>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, Wt, th0, dth0, tau, pos, vel, K, k, alpha, xref, A, B,
+                       Nt, h, (int)k_batch_major, cost, opos, ovel, otau);
   })
   return hipGetLastError();
 }

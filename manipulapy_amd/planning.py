@@ -365,6 +365,90 @@ class OptimizedTrajectoryPlanning:
                                                        one(grad_positions), one(grad_velocities), one(grad_accelerations))
         return {k: v[0] for k, v in r.items()}
 
+    # ------------------------------------------------------------------ batched LQR / iLQR about a roll-out (csrc/mp_ilqr.h)
+    def _ilqr_problem(self, what, theta0, dtheta0, taumat, x_ref, wq, wr, wf, dt, g, layout):
+        """Checks the arguments of batch_lqr_gains / batch_ilqr and returns (the four primitives behind one interface, "gpu" | "cpu"):
+        device-resident (_IlqrDevice) when the call is routed to the GPU, host arrays through the registered CPU launchers (_IlqrHost)
+        otherwise.  The callers count the whole operation - set-up, launches, driver - as one call of that kind once it is done."""
+        if layout not in ("batch_major", "time_major"):
+            raise ValueError("layout must be 'batch_major' or 'time_major'")
+        for name, a in (("theta0", theta0), ("dtheta0", dtheta0), ("taumat", taumat), ("x_ref", x_ref)):
+            if np.asarray(a).dtype == np.float32:
+                raise TypeError(f"{what}: {name} is float32 - the roll-out gradients are computed on float64 state only")
+        model = self._vjp_model(what)
+        n = model.n
+        th = np.ascontiguousarray(theta0, dtype=np.float64)
+        if th.ndim != 2 or th.shape[1] != n:
+            raise ValueError(f"initial states must be (B, {n}); got {th.shape}")
+        B = th.shape[0]
+        dth = _hip._as_c(dtheta0, np.float64, (B, n), "dtheta0")
+        tm, xr = np.asarray(taumat, dtype=np.float64), np.asarray(x_ref, dtype=np.float64)
+        if layout == "time_major":
+            tm, xr = np.swapaxes(tm, 0, 1), np.swapaxes(xr, 0, 1)
+        if tm.ndim != 3 or tm.shape[0] != B or tm.shape[2] != n:
+            raise ValueError(f"taumat must be (B, N, {n}) (or (N, B, {n}) time-major); got {np.asarray(taumat).shape}")
+        N = tm.shape[1]
+        if N < 2:
+            raise ValueError(f"{what}: N must be >= 2 (got {N})")
+        if xr.shape != (B, N, 2 * n):
+            raise ValueError(f"x_ref must be (B, N, {2 * n}) (or (N, B, {2 * n}) time-major); got {np.asarray(x_ref).shape}")
+        bc = lambda w, m, name: _hip._as_c(np.broadcast_to(np.asarray(w, dtype=np.float64), (m,)), np.float64, (m,), name)  # noqa: E731
+        wq, wr, wf = bc(wq, 2 * n, "wq"), bc(wr, n, "wr"), bc(wf, 2 * n, "wf")
+        if g is None:
+            g = np.array([0.0, 0.0, -9.81])
+        args = (model, th, dth, np.ascontiguousarray(tm), np.ascontiguousarray(xr), wq, wr, wf, np.asarray(g, dtype=np.float64), float(dt))
+        if self._gpu_routed():
+            return _IlqrDevice(_reg.get_context(), *args), "gpu"
+        if not self._forced_cpu:
+            _reg._refuse_silent_cpu("dynamics.ilqr_backward")
+        return _IlqrHost(*args), "cpu"
+
+    @staticmethod
+    def _ilqr_layout(a, layout):
+        return a if layout == "batch_major" else np.ascontiguousarray(np.swapaxes(a, 0, 1))
+
+    def batch_lqr_gains(self, theta0, dtheta0, taumat, x_ref, wq, wr, wf, dt, g=None, reg=0.0, layout: str = "batch_major"):
+        """Time-varying LQR about the roll-out of `taumat` from (theta0, dtheta0) for B trajectories at once: one float64 roll-out, one
+        launch of the forward-dynamics derivatives and one Riccati backward pass (csrc/mp_ilqr.h; conventions in
+        include/manipula_hip.h).  theta0 / dtheta0 (B, n), taumat (B, N, n), x_ref (B, N, 2n); wq / wf (2n), wr (n) diagonal weights
+        (scalars broadcast); reg a scalar or (B,).  Returns {"K": (B, N, n, 2n), "k": (B, N, n), "expected_reduction": (B, 2) = (dV1,
+        dV2), "status": (B,) int32, "positions", "velocities": (B, N, n) float64, "cost": (B,)}; rows 0 of K and k are zero.
+        layout="time_major": taumat, x_ref and the row outputs are (N, B, ...)."""
+        t0 = time.time()
+        prob, route = self._ilqr_problem("batch_lqr_gains", theta0, dtheta0, taumat, x_ref, wq, wr, wf, dt, g, layout)
+        try:
+            J = prob.nominal()
+            dV, status = prob.backward(np.broadcast_to(np.asarray(reg, dtype=np.float64), (prob.B,)))
+            r = prob.result()
+        finally:
+            prob.close()
+            self._count(route, t0)
+        out = {"K": r["K"], "k": r["k"], "positions": r["positions"], "velocities": r["velocities"]}
+        out = {key: self._ilqr_layout(v, layout) for key, v in out.items()}
+        out.update({"expected_reduction": dV, "status": status, "cost": J})
+        return out
+
+    def batch_ilqr(self, theta0, dtheta0, taumat, x_ref, wq, wr, wf, dt, g=None, max_iter: int = 50, tol: float = 1e-9,
+                   reg0: float = 1e-6, layout: str = "batch_major"):
+        """iLQR for B problems at once from the nominal torques `taumat` (arguments as batch_lqr_gains).  The driver below is shared by
+        both backends - only the four primitives (nominal roll-out, backward pass, candidate costs, accepted roll-out) dispatch - and on
+        the GPU the states, derivative blocks and gains stay on the device: an iteration brings back the costs, dV and status.
+        Rules: candidates alpha = 2^0 .. 2^-7, the largest with J - J_alpha >= 1e-4 (-(alpha dV1 + alpha^2 dV2)) is taken and reg <-
+        max(reg / 10, 1e-9); none, or status > 0: reg <- 10 reg and alpha = 0.  A trajectory is converged, and frozen at alpha = 0 from
+        then on, once an accepted step lowers J by at most tol (1 + |J|) or -dV1 <= tol (1 + |J|).  Stops when all are converged or at
+        max_iter.  Returns {"taumat", "positions", "velocities": (B, N, n), "K": (B, N, n, 2n), "k": (B, N, n), "cost": (B,),
+        "iterations": (B,), "converged": (B,), "cost_history": (iterations + 1, B), "alpha_history": (iterations, B)}."""
+        t0 = time.time()
+        prob, route = self._ilqr_problem("batch_ilqr", theta0, dtheta0, taumat, x_ref, wq, wr, wf, dt, g, layout)
+        try:
+            out = _ilqr_drive(prob, max_iter, tol, reg0)
+            r = prob.result()
+        finally:
+            prob.close()
+            self._count(route, t0)
+        out.update({key: self._ilqr_layout(r[key], layout) for key in ("taumat", "positions", "velocities", "K", "k")})
+        return out
+
     # ------------------------------------------------------------------ legacy dynamics objects (Mlist_per_link=None)
     # The reference's approximation for such objects is not rigid-body dynamics (dynamics/mass_matrix.py:101-132), so there
     # is no compiled model and no kernel for it: the planner walks the rows on the host exactly as the reference's CPU
@@ -560,3 +644,162 @@ class OptimizedTrajectoryPlanning:
 
 
 TrajectoryPlanning = OptimizedTrajectoryPlanning  # alias kept by the reference (planning/__init__.py)
+
+
+def _ilqr_drive(prob, max_iter, tol, reg0):
+    """The iLQR iteration of batch_ilqr over a set of primitives (nominal / backward / costs / accept): every decision is taken here, on
+    the host, from costs, dV and status alone."""
+    B = prob.B
+    alphas = 2.0 ** -np.arange(8.0)
+    J = prob.nominal()
+    reg = np.full(B, float(reg0))
+    conv, dead = np.zeros(B, dtype=bool), ~np.isfinite(J)
+    iters = np.zeros(B, dtype=np.int64)
+    hist, ahist = [J.copy()], []
+    for _ in range(int(max_iter)):
+        if (conv | dead).all():
+            break
+        dV, status = prob.backward(reg)
+        Jc = prob.costs(np.repeat(alphas[:, None], B, axis=1))
+        active = ~(conv | dead)
+        with np.errstate(invalid="ignore"):
+            pred = -(alphas[:, None] * dV[None, :, 0] + alphas[:, None] ** 2 * dV[None, :, 1])
+            ok = np.isfinite(Jc) & (J[None] - Jc >= 1e-4 * pred) & (status == 0)[None] & active[None]
+        took = ok.any(axis=0)
+        alpha = np.where(took, alphas[np.argmax(ok, axis=0)], 0.0)
+        Jn = prob.accept(alpha)
+        scale = tol * (1.0 + np.abs(J))
+        with np.errstate(invalid="ignore"):
+            flat = (status == 0) & (-dV[:, 0] <= scale)
+            newly = active & ((took & (J - Jn <= scale)) | flat)
+        reg = np.where(active, np.where(took, np.maximum(reg / 10.0, 1e-9), reg * 10.0), reg)
+        iters[active] += 1
+        dead |= status < 0
+        conv |= newly
+        J = np.where(took, Jn, J)
+        hist.append(J.copy())
+        ahist.append(alpha)
+    return {"cost": J, "iterations": iters, "converged": conv, "cost_history": np.array(hist),
+            "alpha_history": np.array(ahist).reshape(len(ahist), B)}
+
+
+class _IlqrHost:
+    """The iLQR primitives on host arrays through the registered launchers' CPU side (the C ABI's *_cpu twins)."""
+
+    def __init__(self, model, th, dth, tm, xr, wq, wr, wf, g, dt):
+        self.model, self.th, self.dth, self.tau, self.xr = model, th, dth, tm, xr
+        self.w, self.g, self.dt = (wq, wr, wf), g, dt
+        self.B, self.N, self.n = tm.shape
+        self.pos = self.vel = None
+        self.K, self.k = np.zeros((self.B, self.N, self.n, 2 * self.n)), np.zeros(tm.shape)
+        self._roll = _reg.get_registered_kernel("dynamics.ilqr_rollout").cpu_launcher
+        self._back = _reg.get_registered_kernel("dynamics.ilqr_backward").cpu_launcher
+
+    def nominal(self):
+        cost, pos, vel, _ = self._roll(self.model, self.th, self.dth, self.tau, None, None, None, None, np.zeros((1, self.B)), self.xr,
+                                       *self.w, self.g, self.dt, True)
+        self.pos, self.vel = pos[0], vel[0]
+        return cost[0]
+
+    def backward(self, reg):
+        self.K, self.k, dV, status = self._back(self.model, self.pos, self.vel, self.tau, self.xr, *self.w, reg, self.g, self.dt)
+        return dV, status
+
+    def costs(self, alpha):
+        return self._roll(self.model, self.th, self.dth, self.tau, self.pos, self.vel, self.K, self.k, alpha, self.xr, *self.w, self.g,
+                          self.dt, False)[0]
+
+    def accept(self, alpha):
+        cost, pos, vel, tau = self._roll(self.model, self.th, self.dth, self.tau, self.pos, self.vel, self.K, self.k, alpha[None], self.xr,
+                                         *self.w, self.g, self.dt, True)
+        self.pos, self.vel, self.tau = pos[0], vel[0], tau[0]
+        return cost[0]
+
+    def result(self):
+        return {"taumat": self.tau, "positions": self.pos, "velocities": self.vel, "K": self.K, "k": self.k}
+
+    def close(self):
+        pass
+
+
+class _IlqrDevice:
+    """The same primitives on device buffers (time-major): states, derivative blocks and gains never leave the device; a call brings
+    back costs, dV and status only, and result() the final arrays."""
+
+    def __init__(self, ctx, model, th, dth, tm, xr, wq, wr, wf, g, dt):
+        self.ctx, self.model, self.w, self.g, self.dt = ctx, model, (wq, wr, wf), g, dt
+        self.B, self.N, self.n = B, N, n = tm.shape
+        self.bufs = []
+        f8 = 8
+        rows = N * B * n * f8
+        try:
+            self.th, self.dth = self._up(th), self._up(dth)
+            self.tau = [self._up(np.swapaxes(tm, 0, 1)), self._new(rows)]
+            self.pos, self.vel = [self._new(rows), self._new(rows)], [self._new(rows), self._new(rows)]
+            self.xr = self._up(np.swapaxes(xr, 0, 1))
+            blk = (N - 1) * B * n * n * f8
+            self.dq, self.dqd, self.mi = self._new(blk), self._new(blk), self._new(blk)
+            self.K, self.k = self._new(2 * rows * n), self._new(rows)
+            self.work = self._new(_hip.ilqr_backward_workspace_bytes(model, B, N))
+            self.reg, self.dV, self.status = self._new(B * f8), self._new(2 * B * f8), self._new(B * 4)
+            self.alpha, self.cost = self._new(8 * B * f8), self._new(8 * B * f8)
+            self.tau1 = self._new((N - 1) * B * n * f8) if (B * n) % 2 else None
+            ctx.memset(self.K, 0, 2 * rows * n)
+            ctx.memset(self.k, 0, rows)
+        except Exception:
+            self.close()
+            raise
+        self.cur = 0
+
+    def _new(self, nbytes):
+        self.bufs.append(self.ctx.alloc(nbytes))
+        return self.bufs[-1]
+
+    def _up(self, a):
+        self.bufs.append(self.ctx.to_device(np.ascontiguousarray(a)))
+        return self.bufs[-1]
+
+    def _rollout(self, alpha, closed, rows):
+        A, c, o = alpha.shape[0], self.cur, 1 - self.cur
+        if A > 8:
+            raise ValueError("at most 8 step sizes a launch")
+        self.alpha.upload(alpha)
+        loop = (self.pos[c], self.vel[c], self.K, self.k) if closed else (None, None, None, None)
+        outs = (self.pos[o], self.vel[o], self.tau[o]) if rows else (None, None, None)
+        self.ctx.ilqr_rollout(self.model, self.th, self.dth, self.tau[c], *loop, self.alpha, self.xr, *self.w, A, self.B, self.N, self.g,
+                              self.dt, self.cost, *outs)
+        if rows:
+            self.cur = o
+        return self.cost.download((A, self.B), np.float64)
+
+    def nominal(self):
+        return self._rollout(np.zeros((1, self.B)), False, True)[0]
+
+    def backward(self, reg):
+        B, N, n, c = self.B, self.N, self.n, self.cur
+        self.reg.upload(np.ascontiguousarray(reg, dtype=np.float64))
+        tau1 = self.tau[c].offset(B * n * 8)    # torque rows 1..N-1
+        if (B * n) % 2:                         # 8 bytes off the 16-byte boundary the derivative entry asks for: a device copy
+            self.ctx.transpose_rows(tau1, 1, (N - 1) * B, n * 8, self.tau1)
+            tau1 = self.tau1
+        self.ctx.fd_derivatives(self.model, self.pos[c], self.vel[c], tau1, (N - 1) * B, self.dq, self.dqd, d_Minv=self.mi, g=self.g)
+        self.ctx.ilqr_backward(self.model, self.pos[c], self.vel[c], self.tau[c], self.dq, self.dqd, self.mi, self.xr, *self.w, self.reg, B,
+                               N, self.dt, self.work, self.K, self.k, self.dV, self.status)
+        return self.dV.download((B, 2), np.float64), self.status.download((B,), np.int32)
+
+    def costs(self, alpha):
+        return self._rollout(np.ascontiguousarray(alpha, dtype=np.float64), True, False)
+
+    def accept(self, alpha):
+        return self._rollout(np.ascontiguousarray(alpha, dtype=np.float64)[None], True, True)[0]
+
+    def result(self):
+        B, N, n, c = self.B, self.N, self.n, self.cur
+        bm = lambda buf, tail: np.ascontiguousarray(np.swapaxes(buf.download((N, B) + tail, np.float64), 0, 1))  # noqa: E731
+        return {"taumat": bm(self.tau[c], (n,)), "positions": bm(self.pos[c], (n,)), "velocities": bm(self.vel[c], (n,)),
+                "K": bm(self.K, (n, 2 * n)), "k": bm(self.k, (n,))}
+
+    def close(self):
+        for b in self.bufs:
+            b.free()
+        self.bufs = []

@@ -337,6 +337,14 @@ def _launch_fd_trajectory_vjp_cpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt
     return _hip.cpu_fd_trajectory_vjp(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos, gvel, gacc)
 
 
+def _launch_ilqr_backward_cpu(model, pos, vel, taumat, xref, wq, wr, wf, reg, g, dt):
+    return _hip.cpu_ilqr_backward(model, pos, vel, taumat, xref, wq, wr, wf, reg, g, dt)
+
+
+def _launch_ilqr_rollout_cpu(model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr, wf, g, dt, want_rows=True):
+    return _hip.cpu_ilqr_rollout(model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr, wf, g, dt, want_rows)
+
+
 def _launch_fd_trajectory_cpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64, layout="batch_major",
                               device_layout=None):
     del device_layout   # (a device-side choice; the host rows are walked in whatever order they come)
@@ -480,6 +488,14 @@ def _launch_fd_trajectory_vjp_gpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt
     return get_context().fd_trajectory_vjp_host(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, gpos, gvel, gacc, layout=layout)
 
 
+def _launch_ilqr_backward_gpu(model, pos, vel, taumat, xref, wq, wr, wf, reg, g, dt):
+    return get_context().ilqr_backward_host(model, pos, vel, taumat, xref, wq, wr, wf, reg, g, dt)
+
+
+def _launch_ilqr_rollout_gpu(model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr, wf, g, dt, want_rows=True):
+    return get_context().ilqr_rollout_host(model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr, wf, g, dt, want_rows)
+
+
 def _launch_fd_trajectory_gpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64, layout="batch_major",
                               device_layout=None):
     return get_context().fd_trajectory_host(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=dtype, layout=layout,
@@ -566,6 +582,10 @@ def _build_kernel_registry() -> KernelRegistry:
         # operational-space dynamics and task-space torque (csrc/mp_opspace.h); both names sort after "dynamics.forward_trajectory"
         ("dynamics.operational_space", "mp_opspace_host_f64", _launch_opspace_gpu, _launch_opspace_cpu),
         ("dynamics.operational_space_torque", "mp_opspace_torque_host_f64", _launch_opspace_torque_gpu, _launch_opspace_torque_cpu),
+        # batched iLQR: the Riccati backward pass and the closed-loop roll-out (csrc/mp_ilqr.h); both names sort after
+        # "dynamics.forward_trajectory"
+        ("dynamics.ilqr_backward", "mp_ilqr_backward_host_f64 / _tm_f64", _launch_ilqr_backward_gpu, _launch_ilqr_backward_cpu),
+        ("dynamics.ilqr_rollout", "mp_ilqr_rollout_host_f64 / _tm_f64", _launch_ilqr_rollout_gpu, _launch_ilqr_rollout_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):
