@@ -422,6 +422,53 @@ int mp_ilqr_rollout_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_t
                            const double* d_pos, const double* d_vel, const double* d_K, const double* d_k, const double* d_alpha,
                            const double* d_xref, const double* wq, const double* wr, const double* wf, int64_t A, int64_t B, int64_t N,
                            const double* g, double dt, double* d_cost, double* d_opos, double* d_ovel, double* d_otau);
+/* Batched time-optimal path parameterisation under torque, acceleration and velocity limits (float64, models of 1..8 joints -
+ * MP_ERR_UNSUPPORTED above that; csrc/mp_toppra.h).  The method is TOPP by reachability analysis (TOPP-RA).  No counterpart in this
+ * ABI's reference interface.
+ * Path grid: s_i = i / (N - 1), i = 0..N-1, D = 1 / (N - 1), N >= 3 (else MP_ERR_INVALID).  The caller gives q, q' = dq/ds, q'' = d2q/ds2
+ * at the grid points.  With qd = q' sd and qdd = q' sdd + q'' sd^2 the torque is tau = a sdd + b sd^2 + c,
+ *     a = M(q) q',    b = M(q) q'' + C(q, q') q'  (the velocity-quadratic forces at "velocity" q'),    c = g(q) + Js^T Ftip.
+ * mp_path_dynamics_f64 takes the three vectors from recursions over the row's link frames that share its joint state - (velocity 0,
+ * acceleration q', no gravity), (velocity q', acceleration q'', no gravity), (everything 0, base acceleration -g, the wrench) - never
+ * from a difference of inverse-dynamics results, and writes xbar_i = min_j (vmax_j / |q'_ij|)^2 over the joints with q'_ij != 0
+ * (+inf when there is none).  A row with a non-finite input gets NaN in a, b, c and xbar.
+ * Constraints at grid point i on (u, x) = (sdd_i, sd_i^2), each a row p u + q x + r <= 0:
+ *     torque        tau_lo <= a u + b x + c <= tau_hi         (2n rows; an infinite bound is an absent row, it enters no arithmetic)
+ *     acceleration  -a_max <= q' u + q'' x <= a_max           (2n rows, optional)
+ *     speed         0 <= x <= xbar_i
+ *     transition    K_{i+1,lo} <= x + 2 D u <= K_{i+1,hi}     (x_{i+1} = x_i + 2 D u_i)
+ * Backward pass, i = N-2 .. 0 from K_{N-1} = [sd_end^2, sd_end^2]:  K_i = [min x, max x] over that polygon - two linear programmes in
+ * two variables.  For fixed x the feasible u is [alpha(x), beta(x)] (alpha the largest of the lines with p < 0, beta the smallest of
+ * those with p > 0, rows with p = 0 bound x directly); beta - alpha is concave and piecewise linear; from x = xbar_i (max) or 0 (min)
+ * the two active lines are evaluated and x jumps to their intersection until beta >= alpha - a Newton step on a concave function,
+ * monotone from outside the feasible interval, finitely many pieces.  A tangent that does not lead back: the set is empty.
+ * Forward pass, i = 0 .. N-2 from x_0 = sd_start^2:  u_i = beta(x_i) (the greatest admissible acceleration),
+ *     x_{i+1} = clip(x_i + 2 D u_i, K_{i+1}),    u_{N-1} := u_{N-2}  (the constraints of the last point are not imposed).
+ * Time: t_0 = 0, t_{i+1} = t_i + 2 D / (sqrt x_i + sqrt x_{i+1}) (+inf through an interior stop, which is not an error), duration = t_{N-1}.
+ * Rows: qd_i = q'_i sqrt x_i,  qdd_i = q'_i u_i + q''_i x_i,  tau_i = a_i u_i + b_i x_i + c_i.
+ * status (B) int32: 0 fine; i + 1 (1..N-1) the controllable set is first empty, going backward, at grid point i; -2 sd_end^2 > xbar_{N-1},
+ * or sd_start^2 outside K_0; -1 a non-finite input or a grid row whose q' is all zero (non-finite a, b, c or xbar in the _tm form).
+ * Order of the tests: -1, the end speed, i + 1, the start speed.  With status != 0 that path's x, u, t, duration and rows are NaN and
+ * its K is NaN from the failing point down (all of K for -1 and for the end speed, none of it for the start speed); other paths are
+ * untouched.
+ * Limits are host vectors: velocity_limits (n) finite and positive; torque_limits (n, 2) = (lo, hi) pairs, either may be infinite,
+ * NULL = none; acceleration_limits (n) positive, NULL = none.  sd_start / sd_end (B) are per path.  g[3] and Ftip[6] per call, both
+ * nullable, as for the inverse-dynamics entries.
+ *   mp_path_dynamics_f64: device rows of q, q', q'' in any layout -> a, b, c (rows, n), xbar (rows).  Asynchronous.
+ *   mp_toppra_tm_f64:     device pointers on the time-major layout: a / b / c / dq / ddq (N,B,n), xbar (N,B) -> K (N,B,2), x / u / t
+ *                         (N,B), duration (B), status (B), qd / qdd / tau (N,B,n) (all three or none).  dq / ddq may be NULL without
+ *                         acceleration limits and row outputs.  Asynchronous, allocates nothing, may be captured into a launch graph.
+ *   mp_toppra_host_f64:   batch-major host arrays q / dq / ddq (B,N,n) -> K (B,N,2), x / u / t (B,N), duration, status (B), qd / qdd /
+ *                         tau (B,N,n) (all three or none); converted on the device with mp_transpose_rows, memory from the context's pool.
+ *   mp_path_dynamics_cpu_f64 / mp_toppra_cpu_f64: the CPU twins of mp_path_dynamics_f64 (host rows) and mp_toppra_host_f64;
+ *   mp_toppra_sweep_cpu_f64: the sweep alone on given batch-major coefficients. */
+int mp_path_dynamics_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_dq, const double* d_ddq, int64_t rows,
+                         const double* velocity_limits, const double* g, const double* Ftip, double* d_a, double* d_b, double* d_c,
+                         double* d_xbar);
+int mp_toppra_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_a, const double* d_b, const double* d_c, const double* d_xbar,
+                     const double* d_dq, const double* d_ddq, const double* torque_limits, const double* acceleration_limits,
+                     const double* d_sd_start, const double* d_sd_end, int64_t B, int64_t N, double* d_K, double* d_x, double* d_u,
+                     double* d_t, double* d_duration, int32_t* d_status, double* d_qd, double* d_qdd, double* d_tau);
 /* d_dst (inner, outer, row_bytes) <- d_src (outer, inner, row_bytes): converts between the batch-major API arrays
  * (B,N,n) and the time-major layout (N,B,n), either way.  row_bytes: a multiple of 4, at most 256 (32 float64 joints). */
 int mp_transpose_rows(mp_ctx* ctx, const void* d_src, int64_t outer, int64_t inner, int64_t row_bytes, void* d_dst);
@@ -480,6 +527,10 @@ int mp_ilqr_rollout_host_f64(mp_ctx* ctx, const mp_model* model, const double* t
                              const double* pos, const double* vel, const double* K, const double* k, const double* alpha,
                              const double* xref, const double* wq, const double* wr, const double* wf, int64_t A, int64_t B, int64_t N,
                              const double* g, double dt, double* cost, double* opos, double* ovel, double* otau);
+int mp_toppra_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* dq, const double* ddq,
+                       const double* velocity_limits, const double* torque_limits, const double* acceleration_limits,
+                       const double* sd_start, const double* sd_end, int64_t B, int64_t N, const double* g, const double* Ftip, double* K,
+                       double* x, double* u, double* t, double* duration, int32_t* status, double* qd, double* qdd, double* tau);
 int mp_forward_dynamics_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd,
                                  const double* tau, int64_t rows, const double* g, const double* Ftip, double* qdd);
 int mp_id_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd,
@@ -582,6 +633,17 @@ int mp_ilqr_rollout_cpu_f64(const mp_model* model, const double* theta0, const d
                             const double* vel, const double* K, const double* k, const double* alpha, const double* xref,
                             const double* wq, const double* wr, const double* wf, int64_t A, int64_t B, int64_t N, const double* g,
                             double dt, double* cost, double* opos, double* ovel, double* otau, int nthreads);
+int mp_path_dynamics_cpu_f64(const mp_model* model, const double* q, const double* dq, const double* ddq, int64_t rows,
+                             const double* velocity_limits, const double* g, const double* Ftip, double* a, double* b, double* c,
+                             double* xbar, int nthreads);
+int mp_toppra_sweep_cpu_f64(int n, const double* a, const double* b, const double* c, const double* xbar, const double* dq,
+                            const double* ddq, const double* torque_limits, const double* acceleration_limits, const double* sd_start,
+                            const double* sd_end, int64_t B, int64_t N, double* K, double* x, double* u, double* t, double* duration,
+                            int32_t* status, double* qd, double* qdd, double* tau, int nthreads);
+int mp_toppra_cpu_f64(const mp_model* model, const double* q, const double* dq, const double* ddq, const double* velocity_limits,
+                      const double* torque_limits, const double* acceleration_limits, const double* sd_start, const double* sd_end,
+                      int64_t B, int64_t N, const double* g, const double* Ftip, double* K, double* x, double* u, double* t,
+                      double* duration, int32_t* status, double* qd, double* qdd, double* tau, int nthreads);
 int mp_fd_trajectory_vjp_cpu_f64(const mp_model* model, const double* theta0, const double* dtheta0, const double* taumat,
                                  const double* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, const double* gpos,
                                  const double* gvel, const double* gacc, double* gtheta0, double* gdtheta0, double* gtaumat,

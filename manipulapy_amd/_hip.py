@@ -138,6 +138,12 @@ SIGNATURES = {
     "mp_ilqr_rollout_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, ctypes.c_double, _c_dp, _c_dp, _c_dp, _c_dp]),
     "mp_ilqr_backward_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, _c_dp, _c_dp, _c_dp, _vp, ctypes.c_int]),
     "mp_ilqr_rollout_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _i64, _c_dp, ctypes.c_double, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_path_dynamics_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
+    "mp_toppra_tm_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c_dp, _c_dp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_toppra_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _vp, _c_dp, _c_dp, _c_dp]),
+    "mp_path_dynamics_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_toppra_sweep_cpu_f64": (ctypes.c_int, [ctypes.c_int, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _vp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_toppra_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _vp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_fd_trajectory_host_f32": (ctypes.c_int, [_vp, _vp, _c_fp, _c_fp, _c_fp, _c_fp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp]),
     "mp_fd_trajectory_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp]),
     "mp_cartesian_trajectory_f32": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp]),
@@ -1037,6 +1043,30 @@ class HipContext:
         return _ilqr_rollout(self.lib.mp_ilqr_rollout_host_f64, (self.handle,), model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref,
                              wq, wr, wf, g, dt, want_rows)
 
+    def path_dynamics(self, model, d_q, d_dq, d_ddq, rows, velocity_limits, d_a, d_b, d_c, d_xbar, g=None, Ftip=None):
+        """The path-dynamics coefficients on device rows in any layout (float64, csrc/mp_toppra.h): tau = a sdd + b sd^2 + c per row and
+        xbar = min_j (vmax_j / |q'_j|)^2.  Asynchronous (capturable)."""
+        _check(self.lib.mp_path_dynamics_f64(self.handle, model.handle, _p(d_q), _p(d_dq), _p(d_ddq), int(rows),
+                                             _dptr(_as_c(velocity_limits, np.float64, (model.n,), "velocity_limits")),
+                                             _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _p(d_a), _p(d_b), _p(d_c),
+                                             _p(d_xbar)))
+
+    def toppra(self, model, d_a, d_b, d_c, d_xbar, d_dq, d_ddq, torque_limits, acceleration_limits, d_sd_start, d_sd_end, B, N, d_K, d_x,
+               d_u, d_t, d_duration, d_status, d_qd=None, d_qdd=None, d_tau=None):
+        """The backward and forward sweep on time-major device buffers: a / b / c / dq / ddq (N, B, n), xbar (N, B), sd_start / sd_end (B)
+        -> K (N, B, 2), x / u / t (N, B), duration (B), status (B) int32 and, when given, the rows qd / qdd / tau (N, B, n).
+        Asynchronous, allocates nothing (capturable)."""
+        tl, al = _toppra_limits(model.n, torque_limits, acceleration_limits)
+        _check(self.lib.mp_toppra_tm_f64(self.handle, model.handle, _p(d_a), _p(d_b), _p(d_c), _p(d_xbar), _p(d_dq), _p(d_ddq), _dptr(tl),
+                                         _dptr(al), _p(d_sd_start), _p(d_sd_end), int(B), int(N), _p(d_K), _p(d_x), _p(d_u), _p(d_t),
+                                         _p(d_duration), _p(d_status), _p(d_qd), _p(d_qdd), _p(d_tau)))
+
+    def toppra_host(self, model: HipModel, q, dq, ddq, velocity_limits, torque_limits=None, acceleration_limits=None, sd_start=0.0,
+                    sd_end=0.0, g=None, Ftip=None, want_rows=True):
+        """Time-optimal parameterisation of batch-major host paths q / dq / ddq (B, N, n): the dict of _toppra_call."""
+        return _toppra_call(self.lib.mp_toppra_host_f64, (self.handle,), model, q, dq, ddq, velocity_limits, torque_limits,
+                            acceleration_limits, sd_start, sd_end, g, Ftip, want_rows)
+
     def fd_trajectory(self, model, d_theta0, d_dtheta0, d_taumat, d_Ftipmat, B, N, g, dt, intRes, d_pos, d_vel, d_acc,
                       dtype=np.float32, time_major: bool = False):
         """Device pointers.  time_major=False: taumat (B,N,n), Ftipmat (B,N,6), outputs (B,N,n); True: (N,B,*) throughout."""
@@ -1490,6 +1520,89 @@ def cpu_ilqr_rollout(model: "HipModel", theta0, dtheta0, taumat, pos, vel, K, k,
     """CPU twin of HipContext.ilqr_rollout_host: (cost (A, B), pos, vel, tau (A, B, N, n) or None)."""
     return _ilqr_rollout(load_library().mp_ilqr_rollout_cpu_f64, (), model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr,
                          wf, g, dt, want_rows, nthreads)
+
+
+def _toppra_limits(n, torque_limits, acceleration_limits):
+    tl = None if torque_limits is None else _as_c(torque_limits, np.float64, (n, 2), "torque_limits")
+    al = None if acceleration_limits is None else _as_c(acceleration_limits, np.float64, (n,), "acceleration_limits")
+    return tl, al
+
+
+def _toppra_paths(n, q, dq, ddq, sd_start, sd_end):
+    q = _as_c(q, np.float64, name="path_q")
+    if q.ndim != 3 or q.shape[2] != n:
+        raise ValueError(f"path_q must be (B, N, {n}); got {q.shape}")
+    B = q.shape[0]
+    dq, ddq = _as_c(dq, np.float64, q.shape, "path_dq"), _as_c(ddq, np.float64, q.shape, "path_ddq")
+    s0 = _as_c(np.broadcast_to(np.asarray(sd_start, dtype=np.float64), (B,)), np.float64, (B,), "sd_start")
+    s1 = _as_c(np.broadcast_to(np.asarray(sd_end, dtype=np.float64), (B,)), np.float64, (B,), "sd_end")
+    return q, dq, ddq, s0, s1
+
+
+def _toppra_outputs(B, N, n, want_rows):
+    out = {"controllable": np.zeros((B, N, 2)), "sd2": np.zeros((B, N)), "sdd": np.zeros((B, N)), "time": np.zeros((B, N)),
+           "duration": np.zeros(B), "status": np.zeros(B, dtype=np.int32)}
+    rows = [np.zeros((B, N, n)) for _ in range(3)] if want_rows else [None, None, None]
+    out["velocities"], out["accelerations"], out["torques"] = rows
+    ptrs = [_dptr(out["controllable"]), _dptr(out["sd2"]), _dptr(out["sdd"]), _dptr(out["time"]), _dptr(out["duration"]),
+            out["status"].ctypes.data_as(_vp)] + [_dptr(r) for r in rows]
+    return out, ptrs
+
+
+def _toppra_call(fn, lead, model, q, dq, ddq, velocity_limits, torque_limits, acceleration_limits, sd_start, sd_end, g, Ftip, want_rows,
+                 nthreads=None):
+    """{"sd2", "sdd", "time" (B, N), "duration" (B), "velocities", "accelerations", "torques" (B, N, n) or None, "controllable"
+    (B, N, 2), "status" (B) int32} of mp_toppra_host_f64 / mp_toppra_cpu_f64."""
+    n = model.n
+    q, dq, ddq, s0, s1 = _toppra_paths(n, q, dq, ddq, sd_start, sd_end)
+    B, N = q.shape[:2]
+    vl = _as_c(velocity_limits, np.float64, (n,), "velocity_limits")
+    tl, al = _toppra_limits(n, torque_limits, acceleration_limits)
+    out, ptrs = _toppra_outputs(B, N, n, want_rows)
+    args = list(lead) + [model.handle, _dptr(q), _dptr(dq), _dptr(ddq), _dptr(vl), _dptr(tl), _dptr(al), _dptr(s0), _dptr(s1), B, N,
+                         _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip"))] + ptrs
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return out
+
+
+def cpu_path_dynamics(model: "HipModel", q, dq, ddq, velocity_limits, g=None, Ftip=None, nthreads: int = 0):
+    """CPU twin of HipContext.path_dynamics on host rows (rows, n): (a, b, c (rows, n), xbar (rows,))."""
+    q = _as_c(q, np.float64, name="q")
+    if q.ndim != 2 or q.shape[1] != model.n:
+        raise ValueError(f"q must be (rows, {model.n}); got {q.shape}")
+    dq, ddq = _as_c(dq, np.float64, q.shape, "dq"), _as_c(ddq, np.float64, q.shape, "ddq")
+    a, b, c, xbar = np.zeros_like(q), np.zeros_like(q), np.zeros_like(q), np.zeros(q.shape[0])
+    _check(load_library().mp_path_dynamics_cpu_f64(model.handle, _dptr(q), _dptr(dq), _dptr(ddq), q.shape[0],
+                                                   _dptr(_as_c(velocity_limits, np.float64, (model.n,), "velocity_limits")),
+                                                   _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip")), _dptr(a), _dptr(b),
+                                                   _dptr(c), _dptr(xbar), int(nthreads)))
+    return a, b, c, xbar
+
+
+def cpu_toppra_sweep(a, b, c, xbar, dq, ddq, torque_limits=None, acceleration_limits=None, sd_start=0.0, sd_end=0.0, want_rows=True,
+                     nthreads: int = 0):
+    """The sweep alone (mp_toppra_sweep_cpu_f64) on given batch-major coefficients a / b / c / dq / ddq (B, N, n), xbar (B, N): the dict
+    of _toppra_call."""
+    a = _as_c(a, np.float64, name="a")
+    if a.ndim != 3:
+        raise ValueError(f"a must be (B, N, n); got {a.shape}")
+    B, N, n = a.shape
+    a, dq, ddq, s0, s1 = _toppra_paths(n, a, dq, ddq, sd_start, sd_end)
+    b, c, xbar = _as_c(b, np.float64, a.shape, "b"), _as_c(c, np.float64, a.shape, "c"), _as_c(xbar, np.float64, (B, N), "xbar")
+    tl, al = _toppra_limits(n, torque_limits, acceleration_limits)
+    out, ptrs = _toppra_outputs(B, N, n, want_rows)
+    _check(load_library().mp_toppra_sweep_cpu_f64(n, _dptr(a), _dptr(b), _dptr(c), _dptr(xbar), _dptr(dq), _dptr(ddq), _dptr(tl), _dptr(al),
+                                                  _dptr(s0), _dptr(s1), B, N, *ptrs, int(nthreads)))
+    return out
+
+
+def cpu_toppra(model: "HipModel", q, dq, ddq, velocity_limits, torque_limits=None, acceleration_limits=None, sd_start=0.0, sd_end=0.0,
+               g=None, Ftip=None, want_rows=True, nthreads: int = 0):
+    """CPU twin of HipContext.toppra_host."""
+    return _toppra_call(load_library().mp_toppra_cpu_f64, (), model, q, dq, ddq, velocity_limits, torque_limits, acceleration_limits,
+                        sd_start, sd_end, g, Ftip, want_rows, nthreads)
 
 
 def cpu_cartesian_trajectory(Xstart, Xend, Tf, N, method, nthreads: int = 0):

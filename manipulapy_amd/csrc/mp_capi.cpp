@@ -23,6 +23,7 @@
 #include "mp_jit.h"
 #include "mp_ik.h"
 #include "mp_ilqr.h"
+#include "mp_toppra.h"
 #include "mp_kernels.h"
 #include "mp_model_compile.h"
 #include "mp_handles.h"
@@ -1356,6 +1357,162 @@ static int ilqr_rollout_host_impl(const char* fn, mp_ctx* ctx, const mp_model* m
   return MP_OK;
 }
 
+// time-optimal path parameterisation (mp_toppra.h): float64, unrolled models only.  The limits are host vectors and travel as kernel
+// arguments: velocity (n, finite and positive), torque (n, 2) or null (none), acceleration (n) or null (none).
+static int toppra_vmax(const char* fn, int n, const double* vlim, MpToppraVmax* V) {
+  REQUIRE(vlim, "%s: null velocity limits", fn);
+  std::memset(V, 0, sizeof *V);
+  for (int j = 0; j < n; ++j) {
+    REQUIRE(std::isfinite(vlim[j]) && vlim[j] > 0.0, "%s: velocity limits must be finite and positive", fn);
+    V->v[j] = vlim[j];
+  }
+  return MP_OK;
+}
+static int toppra_limits(const char* fn, int n, const double* tlim, const double* alim, MpToppraLimits* L) {
+  std::memset(L, 0, sizeof *L);
+  for (int j = 0; j < n; ++j) {
+    L->tau_lo[j] = tlim ? tlim[2 * j] : -INFINITY;
+    L->tau_hi[j] = tlim ? tlim[2 * j + 1] : INFINITY;
+    L->amax[j] = alim ? alim[j] : INFINITY;
+    REQUIRE(!std::isnan(L->tau_lo[j]) && !std::isnan(L->tau_hi[j]) && L->tau_lo[j] <= L->tau_hi[j],
+            "%s: torque limits must be ordered pairs (lo <= hi, either may be infinite)", fn);
+    REQUIRE(L->amax[j] > 0.0, "%s: acceleration limits must be positive", fn);
+  }
+  return MP_OK;
+}
+// The row outputs are written by the sweep's forward pass: measured 0.85 (xArm6) and 0.90 (Panda) of the time of the sweep followed
+// by the row-parallel launch k_path_rows.  MANIPULAPY_HIP_TOPPRA_EPILOGUE=separate (read at every call, so a captured
+// graph keeps the variant it was captured with) selects that launch instead; it exists for tools/toppra_bench.py to time the loser.
+static bool toppra_separate_epilogue() {
+  const char* e = getenv("MANIPULAPY_HIP_TOPPRA_EPILOGUE");
+  return e && std::strcmp(e, "separate") == 0;
+}
+static int path_dynamics_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_dq,
+                              const double* d_ddq, int64_t rows, const double* vlim, const double* g, const double* Ftip, double* d_a,
+                              double* d_b, double* d_c, double* d_xbar) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  MpToppraVmax V;
+  if (int rc = toppra_vmax(fn, model->d.n, vlim, &V)) return rc;
+  if (rows == 0) return MP_OK;
+  REQUIRE(d_q && d_dq && d_ddq && d_a && d_b && d_c && d_xbar, "%s: null device pointer", fn);
+  REQUIRE(aligned16(d_q) && aligned16(d_dq) && aligned16(d_ddq) && aligned16(d_a) && aligned16(d_b) && aligned16(d_c) && aligned16(d_xbar),
+          "%s: device pointers must be 16-byte aligned", fn);
+  MpCall<double> c;
+  make_call<double>(model, g, Ftip, &c);
+  PROFILE_SCOPE(ctx, fn);
+  HIP_TRY(mpk_path_coeffs(ctx->compute, model->d, c, any_nonzero(Ftip), V, d_q, d_dq, d_ddq, d_a, d_b, d_c, d_xbar, (long)rows));
+  return MP_OK;
+}
+static int toppra_tm_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* d_a, const double* d_b, const double* d_c,
+                          const double* d_xbar, const double* d_dq, const double* d_ddq, const double* tlim, const double* alim,
+                          const double* d_sd_start, const double* d_sd_end, int64_t B, int64_t N, double* d_K, double* d_x, double* d_u,
+                          double* d_t, double* d_dur, int32_t* d_status, double* d_qd, double* d_qdd, double* d_tau) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(B >= 0, "%s: negative B (%lld)", fn, (long long)B);
+  REQUIRE(N >= 3, "%s: N must be >= 3 (got %lld)", fn, (long long)N);
+  MpToppraLimits L;
+  if (int rc = toppra_limits(fn, model->d.n, tlim, alim, &L)) return rc;
+  if (B == 0) return MP_OK;
+  REQUIRE(d_a && d_b && d_c && d_xbar && d_sd_start && d_sd_end && d_K && d_x && d_u && d_t && d_dur && d_status,
+          "%s: null device pointer", fn);
+  REQUIRE((d_qd != nullptr) == (d_qdd != nullptr) && (d_qd != nullptr) == (d_tau != nullptr),
+          "%s: the three row outputs must all be given or all be null", fn);
+  REQUIRE(!(alim || d_tau) || (d_dq && d_ddq), "%s: acceleration limits and the row outputs need the path derivatives dq and ddq", fn);
+  REQUIRE(aligned16(d_a) && aligned16(d_b) && aligned16(d_c) && aligned16(d_xbar) && aligned16(d_dq) && aligned16(d_ddq) &&
+              aligned16(d_sd_start) && aligned16(d_sd_end) && aligned16(d_K) && aligned16(d_x) && aligned16(d_u) && aligned16(d_t) &&
+              aligned16(d_dur) && aligned16(d_status) && aligned16(d_qd) && aligned16(d_qdd) && aligned16(d_tau),
+          "%s: device pointers must be 16-byte aligned", fn);
+  const bool fused = d_tau && !toppra_separate_epilogue();
+  PROFILE_SCOPE(ctx, fn);
+  HIP_TRY(mpk_toppra_sweep(ctx->compute, model->d.n, L, alim != nullptr, d_a, d_b, d_c, d_xbar, d_dq, d_ddq, d_sd_start, d_sd_end, (long)B,
+                           (long)N, d_K, d_x, d_u, d_t, d_dur, (int*)d_status, fused ? d_qd : nullptr, fused ? d_qdd : nullptr,
+                           fused ? d_tau : nullptr));
+  if (d_tau && !fused)
+    HIP_TRY(mpk_path_rows(ctx->compute, model->d.n, d_a, d_b, d_c, d_dq, d_ddq, d_x, d_u, d_qd, d_qdd, d_tau, (long)(B * N)));
+  return MP_OK;
+}
+// batch-major host arrays: upload -> (B, N, n) to (N, B, n) on the device -> coefficients, sweep, rows -> back to batch-major -> download
+static int toppra_host_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* q, const double* dq, const double* ddq,
+                            const double* vlim, const double* tlim, const double* alim, const double* sd_start, const double* sd_end,
+                            int64_t B, int64_t N, const double* g, const double* Ftip, double* K, double* x, double* u, double* t,
+                            double* dur, int32_t* status, double* qd, double* qdd, double* tau) {
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(B >= 0, "%s: negative B (%lld)", fn, (long long)B);
+  REQUIRE(N >= 3, "%s: N must be >= 3 (got %lld)", fn, (long long)N);
+  MpToppraVmax V;
+  MpToppraLimits L;
+  if (int rc = toppra_vmax(fn, model->d.n, vlim, &V)) return rc;
+  if (int rc = toppra_limits(fn, model->d.n, tlim, alim, &L)) return rc;
+  if (B == 0) return MP_OK;
+  REQUIRE(q && dq && ddq && sd_start && sd_end && K && x && u && t && dur && status, "%s: null host pointer", fn);
+  REQUIRE((qd != nullptr) == (qdd != nullptr) && (qd != nullptr) == (tau != nullptr),
+          "%s: the three row outputs must all be given or all be null", fn);
+  const int n = model->d.n;
+  const size_t sr = (size_t)n * sizeof(double), rows = (size_t)B * N, col = rows * sizeof(double);
+  Scratch sc(ctx);
+  void *dq0, *dq1, *dq2, *da, *db, *dc, *dxb, *ds0, *ds1, *dK, *dx, *du, *dt_, *ddur, *dst, *stage, *o[3] = {nullptr, nullptr, nullptr};
+  if (int rc = sc.get(rows * sr, &dq0)) return rc;
+  if (int rc = sc.get(rows * sr, &dq1)) return rc;
+  if (int rc = sc.get(rows * sr, &dq2)) return rc;
+  if (int rc = sc.get(rows * sr, &da)) return rc;
+  if (int rc = sc.get(rows * sr, &db)) return rc;
+  if (int rc = sc.get(rows * sr, &dc)) return rc;
+  if (int rc = sc.get(col, &dxb)) return rc;
+  if (int rc = sc.get(B * sizeof(double), &ds0)) return rc;
+  if (int rc = sc.get(B * sizeof(double), &ds1)) return rc;
+  if (int rc = sc.get(2 * col, &dK)) return rc;
+  if (int rc = sc.get(col, &dx)) return rc;
+  if (int rc = sc.get(col, &du)) return rc;
+  if (int rc = sc.get(col, &dt_)) return rc;
+  if (int rc = sc.get(B * sizeof(double), &ddur)) return rc;
+  if (int rc = sc.get(B * sizeof(int32_t), &dst)) return rc;
+  if (int rc = sc.get(std::max(rows * sr, 2 * col), &stage)) return rc;
+  if (tau)
+    for (int i = 0; i < 3; ++i)
+      if (int rc = sc.get(rows * sr, &o[i])) return rc;
+  auto up_tm = [&](const double* src, void* dst_) -> int {   // (B, N, n) host -> (N, B, n) device
+    H2D(stage, src, rows * sr);
+    return mp_transpose_rows(ctx, stage, B, N, (int64_t)sr, dst_);
+  };
+  if (int rc = up_tm(q, dq0)) return rc;
+  if (int rc = up_tm(dq, dq1)) return rc;
+  if (int rc = up_tm(ddq, dq2)) return rc;
+  H2D(ds0, sd_start, B * sizeof(double));
+  H2D(ds1, sd_end, B * sizeof(double));
+  if (int rc = path_dynamics_impl(fn, ctx, model, (double*)dq0, (double*)dq1, (double*)dq2, (int64_t)rows, vlim, g, Ftip, (double*)da,
+                                  (double*)db, (double*)dc, (double*)dxb))
+    return rc;
+  if (int rc = toppra_tm_impl(fn, ctx, model, (double*)da, (double*)db, (double*)dc, (double*)dxb, (double*)dq1, (double*)dq2, tlim, alim,
+                              (double*)ds0, (double*)ds1, B, N, (double*)dK, (double*)dx, (double*)du, (double*)dt_, (double*)ddur,
+                              (int32_t*)dst, (double*)o[0], (double*)o[1], (double*)o[2]))
+    return rc;
+  auto down_bm = [&](void* src, size_t row, double* dst_) -> int {   // (N, B, row) device -> (B, N, row) host, staged in stream order
+    if (int rc = mp_transpose_rows(ctx, src, N, B, (int64_t)row, stage)) return rc;
+    D2H(dst_, stage, rows * row);
+    return MP_OK;
+  };
+  if (int rc = down_bm(dK, 2 * sizeof(double), K)) return rc;
+  if (int rc = down_bm(dx, sizeof(double), x)) return rc;
+  if (int rc = down_bm(du, sizeof(double), u)) return rc;
+  if (int rc = down_bm(dt_, sizeof(double), t)) return rc;
+  if (tau) {
+    double* hosts[3] = {qd, qdd, tau};
+    for (int i = 0; i < 3; ++i)
+      if (int rc = down_bm(o[i], sr, hosts[i])) return rc;
+  }
+  D2H(dur, ddur, B * sizeof(double));
+  D2H(status, dst, B * sizeof(int32_t));
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+
 // specialised forward-dynamics roll-out (float32 only): -1 = none available, otherwise the launch's return code
 int launch_fd_spec(mp_ctx* ctx, const mp_model* model, const MpCall<float>& c, const float* th0, const float* dth0,
                     const float* taumat, const float* Fm, long B, long Nt, float h, int intRes, float* pos, float* vel, float* acc,
@@ -2610,6 +2767,25 @@ int mp_ilqr_rollout_host_f64(mp_ctx* ctx, const mp_model* model, const double* t
                              const double* g, double dt, double* cost, double* opos, double* ovel, double* otau) {
   return ilqr_rollout_host_impl("mp_ilqr_rollout_host_f64", ctx, model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr, wf, A,
                                 B, N, g, dt, cost, opos, ovel, otau);
+}
+int mp_path_dynamics_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_dq, const double* d_ddq, int64_t rows,
+                         const double* velocity_limits, const double* g, const double* Ftip, double* d_a, double* d_b, double* d_c,
+                         double* d_xbar) {
+  return path_dynamics_impl("mp_path_dynamics_f64", ctx, model, d_q, d_dq, d_ddq, rows, velocity_limits, g, Ftip, d_a, d_b, d_c, d_xbar);
+}
+int mp_toppra_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_a, const double* d_b, const double* d_c, const double* d_xbar,
+                     const double* d_dq, const double* d_ddq, const double* torque_limits, const double* acceleration_limits,
+                     const double* d_sd_start, const double* d_sd_end, int64_t B, int64_t N, double* d_K, double* d_x, double* d_u,
+                     double* d_t, double* d_duration, int32_t* d_status, double* d_qd, double* d_qdd, double* d_tau) {
+  return toppra_tm_impl("mp_toppra_tm_f64", ctx, model, d_a, d_b, d_c, d_xbar, d_dq, d_ddq, torque_limits, acceleration_limits, d_sd_start,
+                        d_sd_end, B, N, d_K, d_x, d_u, d_t, d_duration, d_status, d_qd, d_qdd, d_tau);
+}
+int mp_toppra_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* dq, const double* ddq,
+                       const double* velocity_limits, const double* torque_limits, const double* acceleration_limits,
+                       const double* sd_start, const double* sd_end, int64_t B, int64_t N, const double* g, const double* Ftip, double* K,
+                       double* x, double* u, double* t, double* duration, int32_t* status, double* qd, double* qdd, double* tau) {
+  return toppra_host_impl("mp_toppra_host_f64", ctx, model, q, dq, ddq, velocity_limits, torque_limits, acceleration_limits, sd_start,
+                          sd_end, B, N, g, Ftip, K, x, u, t, duration, status, qd, qdd, tau);
 }
 int mp_fd_trajectory_f32(mp_ctx* ctx, const mp_model* model, const float* d_theta0, const float* d_dtheta0,
                          const float* d_taumat, const float* d_Ftipmat, int64_t B, int64_t N, const double* g, double dt,

@@ -29,6 +29,7 @@
 #include "mp_regressor.h"
 #include "mp_rollout_vjp.h"
 #include "mp_ilqr.h"
+#include "mp_toppra.h"
 
 namespace {
 const double kG[3] = {0.0, 0.0, -9.81};
@@ -794,6 +795,130 @@ int mp_ilqr_rollout_cpu_f64(const mp_model* model, const double* theta0, const d
     });
   })
   return MP_OK;
+}
+// time-optimal path parameterisation (mp_toppra.h): the kernels' per-row and per-path code over batch-major host arrays
+static int toppra_cpu_limits(const char* fn, int n, const double* vlim, const double* tlim, const double* alim, MpToppraVmax* V,
+                             MpToppraLimits* L) {
+  char msg[192];
+  if (V) std::memset(V, 0, sizeof *V);
+  std::memset(L, 0, sizeof *L);
+  for (int j = 0; j < n; ++j) {
+    if (V) {
+      if (!vlim) { std::snprintf(msg, sizeof msg, "%s: null velocity limits", fn); return fail(msg); }
+      if (!(std::isfinite(vlim[j]) && vlim[j] > 0.0)) {
+        std::snprintf(msg, sizeof msg, "%s: velocity limits must be finite and positive", fn);
+        return fail(msg);
+      }
+      V->v[j] = vlim[j];
+    }
+    L->tau_lo[j] = tlim ? tlim[2 * j] : -INFINITY;
+    L->tau_hi[j] = tlim ? tlim[2 * j + 1] : INFINITY;
+    L->amax[j] = alim ? alim[j] : INFINITY;
+    if (std::isnan(L->tau_lo[j]) || std::isnan(L->tau_hi[j]) || !(L->tau_lo[j] <= L->tau_hi[j])) {
+      std::snprintf(msg, sizeof msg, "%s: torque limits must be ordered pairs (lo <= hi, either may be infinite)", fn);
+      return fail(msg);
+    }
+    if (!(L->amax[j] > 0.0)) { std::snprintf(msg, sizeof msg, "%s: acceleration limits must be positive", fn); return fail(msg); }
+  }
+  return MP_OK;
+}
+static int toppra_cpu_model(const char* fn, const mp_model* model) {
+  char msg[192];
+  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
+  if (model->big) {
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  return MP_OK;
+}
+int mp_path_dynamics_cpu_f64(const mp_model* model, const double* q, const double* dq, const double* ddq, int64_t rows,
+                             const double* velocity_limits, const double* g, const double* Ftip, double* a, double* b, double* c,
+                             double* xbar, int nthreads) {
+  const char* fn = "mp_path_dynamics_cpu_f64";
+  if (int rc = toppra_cpu_model(fn, model)) return rc;
+  if (rows < 0) return fail("mp_path_dynamics_cpu_f64: negative row count");
+  MpToppraVmax V;
+  MpToppraLimits L;
+  if (int rc = toppra_cpu_limits(fn, model->d.n, velocity_limits, nullptr, nullptr, &V, &L)) return rc;
+  if (rows == 0) return MP_OK;
+  if (!q || !dq || !ddq || !a || !b || !c || !xbar) return fail("mp_path_dynamics_cpu_f64: null pointer");
+  const MpModel<double>& M = model->d;
+  const MpCall<double> C = make_call<double>(model, g, Ftip);
+  const bool ftip = any_nonzero(Ftip);
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(rows, 256, nthreads, [&](int64_t lo, int64_t hi) {
+      for (int64_t r = lo; r < hi; ++r) {
+        if (ftip) mp_path_coeffs_row<N, true>(M, C, V, q, dq, ddq, a, b, c, xbar, (long)r);
+        else mp_path_coeffs_row<N, false>(M, C, V, q, dq, ddq, a, b, c, xbar, (long)r);
+      }
+    });
+  })
+  return MP_OK;
+}
+// the sweep alone on given coefficients (batch-major (B, N, n) / (B, N)); qd / qdd / tau all or none
+int mp_toppra_sweep_cpu_f64(int n, const double* a, const double* b, const double* c, const double* xbar, const double* dq,
+                            const double* ddq, const double* torque_limits, const double* acceleration_limits, const double* sd_start,
+                            const double* sd_end, int64_t B, int64_t Nt, double* K, double* x, double* u, double* t, double* duration,
+                            int32_t* status, double* qd, double* qdd, double* tau, int nthreads) {
+  const char* fn = "mp_toppra_sweep_cpu_f64";
+  char msg[160];
+  if (n < 1 || n > MP_MAX_DOF) { std::snprintf(msg, sizeof msg, "%s: n must be 1..%d", fn, MP_MAX_DOF); return mp_set_error(MP_ERR_UNSUPPORTED, msg); }
+  if (B < 0) { std::snprintf(msg, sizeof msg, "%s: negative B", fn); return fail(msg); }
+  if (Nt < 3) { std::snprintf(msg, sizeof msg, "%s: N must be >= 3 (got %lld)", fn, (long long)Nt); return fail(msg); }
+  MpToppraLimits L;
+  if (int rc = toppra_cpu_limits(fn, n, nullptr, torque_limits, acceleration_limits, nullptr, &L)) return rc;
+  if (B == 0) return MP_OK;
+  if (!a || !b || !c || !xbar || !sd_start || !sd_end || !K || !x || !u || !t || !duration || !status) {
+    std::snprintf(msg, sizeof msg, "%s: null pointer", fn);
+    return fail(msg);
+  }
+  if ((qd != nullptr) != (qdd != nullptr) || (qd != nullptr) != (tau != nullptr)) {
+    std::snprintf(msg, sizeof msg, "%s: the three row outputs must all be given or all be null", fn);
+    return fail(msg);
+  }
+  if ((acceleration_limits || tau) && (!dq || !ddq)) {
+    std::snprintf(msg, sizeof msg, "%s: acceleration limits and the row outputs need the path derivatives dq and ddq", fn);
+    return fail(msg);
+  }
+  const bool acc = acceleration_limits != nullptr;
+  MP_CPU_DISPATCH(n, {
+    parallel_for(B, 1, nthreads, [&](int64_t lo, int64_t hi) {
+      for (int64_t p = lo; p < hi; ++p) {
+        const int64_t o = p * Nt * N, s = p * Nt;
+        int st = 0;
+        if (acc)
+          mp_toppra_sweep<N, true>(L, a + o, b + o, c + o, xbar + s, dq + o, ddq + o, 1, (long)Nt, sd_start[p], sd_end[p], K + 2 * s, x + s,
+                                   u + s, t + s, duration + p, &st, tau ? qd + o : nullptr, tau ? qdd + o : nullptr, tau ? tau + o : nullptr);
+        else
+          mp_toppra_sweep<N, false>(L, a + o, b + o, c + o, xbar + s, dq ? dq + o : nullptr, ddq ? ddq + o : nullptr, 1, (long)Nt,
+                                    sd_start[p], sd_end[p], K + 2 * s, x + s, u + s, t + s, duration + p, &st, tau ? qd + o : nullptr,
+                                    tau ? qdd + o : nullptr, tau ? tau + o : nullptr);
+        status[p] = st;
+      }
+    });
+  })
+  return MP_OK;
+}
+int mp_toppra_cpu_f64(const mp_model* model, const double* q, const double* dq, const double* ddq, const double* velocity_limits,
+                      const double* torque_limits, const double* acceleration_limits, const double* sd_start, const double* sd_end,
+                      int64_t B, int64_t Nt, const double* g, const double* Ftip, double* K, double* x, double* u, double* t,
+                      double* duration, int32_t* status, double* qd, double* qdd, double* tau, int nthreads) {
+  const char* fn = "mp_toppra_cpu_f64";
+  if (int rc = toppra_cpu_model(fn, model)) return rc;
+  if (B < 0) return fail("mp_toppra_cpu_f64: negative B");
+  if (Nt < 3) { char msg[96]; std::snprintf(msg, sizeof msg, "%s: N must be >= 3 (got %lld)", fn, (long long)Nt); return fail(msg); }
+  const int n = model->d.n;
+  std::vector<double> co;
+  try {
+    co.resize((size_t)B * Nt * (3 * n + 1));
+  } catch (...) {
+    return mp_set_error(MP_ERR_INVALID, "mp_toppra_cpu_f64: out of memory for the coefficients");
+  }
+  const size_t blk = (size_t)B * Nt * n;
+  double *a = co.data(), *b = a + blk, *c = b + blk, *xb = c + blk;
+  if (int rc = mp_path_dynamics_cpu_f64(model, q, dq, ddq, B * Nt, velocity_limits, g, Ftip, a, b, c, xb, nthreads)) return rc;
+  return mp_toppra_sweep_cpu_f64(n, a, b, c, xb, dq, ddq, torque_limits, acceleration_limits, sd_start, sd_end, B, Nt, K, x, u, t, duration,
+                                 status, qd, qdd, tau, nthreads);
 }
 int mp_fd_trajectory_cpu_f32(const mp_model* model, const float* theta0, const float* dtheta0, const float* taumat,
                              const float* Ftipmat, int64_t B, int64_t N, const double* g, double dt, int intRes, float* pos,

@@ -94,6 +94,21 @@ hipError_t mpk_ilqr_rollout(hipStream_t s, const MpModel<double>& M, const MpCal
                             const double* dth0, const double* tau, const double* pos, const double* vel, const double* K, const double* k,
                             const double* alpha, const double* xref, long A, long B, long Nt, double h, bool k_batch_major, double* cost,
                             double* opos, double* ovel, double* otau);
+// time-optimal path parameterisation (csrc/mp_toppra.h), float64, 1..MP_MAX_DOF joints.  mpk_path_coeffs: one lane per row of q / q' / q''
+// in any layout -> a, b, c (rows, n), xbar (rows).  mpk_toppra_sweep: one lane per path on the time-major layout, coefficients (Nt, B, n),
+// xbar (Nt, B), sd_start / sd_end (B) -> K (Nt, B, 2), x / u / t (Nt, B), dur (B), status (B); dq / ddq are read when `acc` or when the
+// three row outputs oqd / oqdd / otau (Nt, B, n) are given (the epilogue fused into the forward pass).  mpk_path_rows: the epilogue as a
+// launch of its own, one lane per row.
+struct MpToppraLimits;
+struct MpToppraVmax;
+hipError_t mpk_path_coeffs(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const MpToppraVmax& V,
+                           const double* q, const double* dq, const double* ddq, double* a, double* b, double* c, double* xbar, long rows);
+hipError_t mpk_toppra_sweep(hipStream_t s, int n, const MpToppraLimits& lim, bool acc, const double* a, const double* b, const double* c,
+                            const double* xbar, const double* dq, const double* ddq, const double* sd_start, const double* sd_end, long B,
+                            long Nt, double* K, double* x, double* u, double* t, double* dur, int* status, double* oqd, double* oqdd,
+                            double* otau);
+hipError_t mpk_path_rows(hipStream_t s, int n, const double* a, const double* b, const double* c, const double* dq, const double* ddq,
+                         const double* x, const double* u, double* oqd, double* oqdd, double* otau, long rows);
 // Ftipmat == nullptr: no tip wrench.  h = dt / intRes.  Outputs are float32 (B, Nt, n).
 template <typename T>
 hipError_t mpk_fd_traj(hipStream_t s, const MpModel<T>& M, const MpCall<T>& C, const T* theta0, const T* dtheta0,

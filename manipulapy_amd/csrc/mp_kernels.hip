@@ -21,6 +21,7 @@
 #include "mp_regressor.h"
 #include "mp_rollout_vjp.h"
 #include "mp_ilqr.h"
+#include "mp_toppra.h"
 
 namespace {
 
@@ -616,6 +617,50 @@ __global__ __launch_bounds__(kDerivBlock) void k_ilqr_rollout(const MpModel<doub
   mp_ilqr_rollout<N>(M, C, th0 + o, dth0 + o, tau + o, K ? pos + o : nullptr, K ? vel + o : nullptr, B, K ? K + kb * (2 * N * N) : nullptr,
                      K ? k + kb * N : nullptr, ks, alpha[l], xref + b * (2 * N), B, Wt.wq, Wt.wr, Wt.wf, Nt, h, cost + l,
                      opos ? opos + l * N : nullptr, opos ? ovel + l * N : nullptr, opos ? otau + l * N : nullptr, A * B);
+}
+
+// ------------------------------------------------------- time-optimal path parameterisation (float64, mp_toppra.h)
+// The path-dynamics coefficients: one lane per grid row, like k_id_deriv; reads 3 n doubles a row, writes 3 n + 1
+template <int N, bool HAS_FTIP>
+__global__ __launch_bounds__(kDerivBlock) void k_path_coeffs(const MpModel<double> M, const MpCall<double> C, const MpToppraVmax V,
+                                                             const double* __restrict__ q, const double* __restrict__ dq,
+                                                             const double* __restrict__ ddq, double* __restrict__ a, double* __restrict__ b,
+                                                             double* __restrict__ c, double* __restrict__ xbar, long rows) {
+  const long r = (long)blockIdx.x * kDerivBlock + threadIdx.x;
+  if (r >= rows) return;
+  mp_path_coeffs_row<N, HAS_FTIP>(M, C, V, q, dq, ddq, a, b, c, xbar, r);
+}
+
+// The sweep: one lane per path on the time-major layout like k_fd_traj_vjp, so a wave's lanes read one run of doubles a row.  A
+// sequential chain of Nt - 1 small LPs and Nt - 1 forward steps per lane: latency-bound, not bandwidth-bound.  K is written by the
+// backward pass and read back by the same lane in the forward pass (no __restrict__ on it).
+template <int N, bool ACC>
+__global__ __launch_bounds__(kDerivBlock) void k_toppra_sweep(const MpToppraLimits lim, const double* __restrict__ a,
+                                                              const double* __restrict__ b, const double* __restrict__ c,
+                                                              const double* __restrict__ xbar, const double* __restrict__ dq,
+                                                              const double* __restrict__ ddq, const double* __restrict__ sd_start,
+                                                              const double* __restrict__ sd_end, long B, long Nt, double* K,
+                                                              double* __restrict__ x, double* __restrict__ u, double* __restrict__ t,
+                                                              double* __restrict__ dur, int* __restrict__ status, double* __restrict__ oqd,
+                                                              double* __restrict__ oqdd, double* __restrict__ otau) {
+  const long p = (long)blockIdx.x * kDerivBlock + threadIdx.x;
+  if (p >= B) return;
+  const long o = p * N;
+  mp_toppra_sweep<N, ACC>(lim, a + o, b + o, c + o, xbar + p, dq ? dq + o : nullptr, ddq ? ddq + o : nullptr, B, Nt, sd_start[p], sd_end[p],
+                          K + 2 * p, x + p, u + p, t + p, dur + p, status + p, otau ? oqd + o : nullptr, otau ? oqdd + o : nullptr,
+                          otau ? otau + o : nullptr);
+}
+
+// The epilogue as a launch of its own: one lane per row, reads 5 n + 2 doubles, writes 3 n
+template <int N>
+__global__ __launch_bounds__(kDerivBlock) void k_path_rows(const double* __restrict__ a, const double* __restrict__ b,
+                                                           const double* __restrict__ c, const double* __restrict__ dq,
+                                                           const double* __restrict__ ddq, const double* __restrict__ x,
+                                                           const double* __restrict__ u, double* __restrict__ oqd, double* __restrict__ oqdd,
+                                                           double* __restrict__ otau, long rows) {
+  const long r = (long)blockIdx.x * kDerivBlock + threadIdx.x;
+  if (r >= rows) return;
+  mp_path_rows_row<N>(a, b, c, dq, ddq, x[r], u[r], oqd, oqdd, otau, r);
 }
 
 // ------------------------------------------------------- dynamics regressor (float64, mp_regressor.h)
@@ -1263,6 +1308,41 @@ hipError_t mpk_ilqr_rollout(hipStream_t s, const MpModel<double>& M, const MpCal
     hipLaunchKernelGGL((k_ilqr_rollout<N>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, Wt, th0, dth0, tau, pos, vel, K, k, alpha, xref, A, B,
                        Nt, h, (int)k_batch_major, cost, opos, ovel, otau);
   })
+  return hipGetLastError();
+}
+
+hipError_t mpk_path_coeffs(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const MpToppraVmax& V,
+                           const double* q, const double* dq, const double* ddq, double* a, double* b, double* c, double* xbar, long rows) {
+  if (rows <= 0) return hipSuccess;
+  if ((rows + kDerivBlock - 1) / kDerivBlock > 0x7fffffffL) return hipErrorInvalidValue;
+  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(M.n, {
+    if (ftip) hipLaunchKernelGGL((k_path_coeffs<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, V, q, dq, ddq, a, b, c, xbar, rows);
+    else hipLaunchKernelGGL((k_path_coeffs<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, V, q, dq, ddq, a, b, c, xbar, rows);
+  })
+  return hipGetLastError();
+}
+hipError_t mpk_toppra_sweep(hipStream_t s, int n, const MpToppraLimits& lim, bool acc, const double* a, const double* b, const double* c,
+                            const double* xbar, const double* dq, const double* ddq, const double* sd_start, const double* sd_end, long B,
+                            long Nt, double* K, double* x, double* u, double* t, double* dur, int* status, double* oqd, double* oqdd,
+                            double* otau) {
+  if (B <= 0) return hipSuccess;
+  if (Nt < 3 || (B + kDerivBlock - 1) / kDerivBlock > 0x7fffffffL) return hipErrorInvalidValue;
+  const unsigned gb = (unsigned)((B + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(n, {
+    if (acc) hipLaunchKernelGGL((k_toppra_sweep<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, lim, a, b, c, xbar, dq, ddq, sd_start, sd_end,
+                                B, Nt, K, x, u, t, dur, status, oqd, oqdd, otau);
+    else hipLaunchKernelGGL((k_toppra_sweep<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, lim, a, b, c, xbar, dq, ddq, sd_start, sd_end, B,
+                            Nt, K, x, u, t, dur, status, oqd, oqdd, otau);
+  })
+  return hipGetLastError();
+}
+hipError_t mpk_path_rows(hipStream_t s, int n, const double* a, const double* b, const double* c, const double* dq, const double* ddq,
+                         const double* x, const double* u, double* oqd, double* oqdd, double* otau, long rows) {
+  if (rows <= 0) return hipSuccess;
+  if ((rows + kDerivBlock - 1) / kDerivBlock > 0x7fffffffL) return hipErrorInvalidValue;
+  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
+  MP_DISPATCH_N(n, { hipLaunchKernelGGL((k_path_rows<N>), dim3(gb), dim3(kDerivBlock), 0, s, a, b, c, dq, ddq, x, u, oqd, oqdd, otau, rows); })
   return hipGetLastError();
 }
 

@@ -55,6 +55,9 @@ class OptimizedTrajectoryPlanning:
         self.joint_limits = np.asarray(joint_limits, dtype=np.float32)
         self.torque_limits = (np.asarray(torque_limits, dtype=np.float32) if torque_limits is not None
                               else np.array([[-np.inf, np.inf]] * len(joint_limits), dtype=np.float32))
+        # the limits as given, unrounded: what the float64 time-optimal parameterisation takes for torque_limits=None
+        self._torque_limits_f64 = (np.array(torque_limits, dtype=np.float64) if torque_limits is not None
+                                   else self.torque_limits.astype(np.float64))
         self.kernel_type = kernel_type if kernel_type is not None else "auto"
         self.target_speedup = target_speedup if target_speedup is not None else 40.0
         self.enable_profiling = bool(enable_profiling)
@@ -448,6 +451,80 @@ class OptimizedTrajectoryPlanning:
             self._count(route, t0)
         out.update({key: self._ilqr_layout(r[key], layout) for key in ("taumat", "positions", "velocities", "K", "k")})
         return out
+
+    # ------------------------------------------------------------------ time-optimal path parameterisation (csrc/mp_toppra.h)
+    def batch_time_optimal_parameterization(self, path_q, path_dq, path_ddq, velocity_limits, torque_limits=None,
+                                            acceleration_limits=None, sd_start=0.0, sd_end=0.0, g=None, Ftip=None,
+                                            layout: str = "batch_major") -> Dict[str, np.ndarray]:
+        """The fastest timing s(t) of B geometric paths q(s) within the torque, velocity and (optional) acceleration limits, by
+        reachability analysis on the grid s_i = i / (N - 1) (conventions in include/manipula_hip.h).  path_q / path_dq / path_ddq
+        (B, N, n) float64: q, dq/ds, d2q/ds2 at the grid points, N >= 3; velocity_limits (n) finite and positive; torque_limits (n, 2),
+        entries may be infinite, None = this planner's own (as given to the constructor, in float64); acceleration_limits (n) or None; sd_start / sd_end the path speeds at both
+        ends, scalars or (B,).  Returns {"sd2", "sdd", "time": (B, N), "duration": (B,), "velocities", "accelerations", "torques":
+        (B, N, n), "controllable": (B, N, 2), "status": (B,) int32}; status 0 fine, i + 1 the controllable set is empty at grid point
+        i, -2 a boundary speed is not admissible, -1 a non-finite input or a grid row whose dq/ds is all zero - the results of such a
+        path are NaN, other paths are untouched.  layout="time_major": the paths and every (B, N, ...) output are (N, B, ...).  One
+        row-parallel dynamics launch and one sequential sweep a path; on the "hip" backend the coefficients never leave the device."""
+        if layout not in ("batch_major", "time_major"):
+            raise ValueError("layout must be 'batch_major' or 'time_major'")
+        for name, a in (("path_q", path_q), ("path_dq", path_dq), ("path_ddq", path_ddq)):
+            if np.asarray(a).dtype == np.float32:
+                raise TypeError(f"batch_time_optimal_parameterization: {name} is float32 - the parameterisation is float64 only")
+        model = self._vjp_model("batch_time_optimal_parameterization")
+        n = model.n
+        q, dq, ddq = (np.asarray(a, dtype=np.float64) for a in (path_q, path_dq, path_ddq))
+        if layout == "time_major":
+            q, dq, ddq = (np.swapaxes(a, 0, 1) if a.ndim == 3 else a for a in (q, dq, ddq))
+        if q.ndim != 3 or q.shape[2] != n or dq.shape != q.shape or ddq.shape != q.shape:
+            raise ValueError(f"path_q, path_dq and path_ddq must all be (B, N, {n}) (or (N, B, {n}) time-major); got "
+                             f"{np.asarray(path_q).shape}, {np.asarray(path_dq).shape}, {np.asarray(path_ddq).shape}")
+        if q.shape[1] < 3:
+            raise ValueError(f"batch_time_optimal_parameterization: N must be >= 3 (got {q.shape[1]})")
+        vl = np.asarray(velocity_limits, dtype=np.float64)
+        if vl.shape != (n,) or not (np.isfinite(vl) & (vl > 0)).all():
+            raise ValueError(f"velocity_limits must be ({n},), finite and positive")
+        tl = np.asarray(self._torque_limits_f64 if torque_limits is None else torque_limits, dtype=np.float64)
+        if tl.shape != (n, 2) or np.isnan(tl).any() or (tl[:, 0] > tl[:, 1]).any():
+            raise ValueError(f"torque_limits must be ({n}, 2) pairs (lo <= hi, either may be infinite)")
+        al = None
+        if acceleration_limits is not None:
+            al = np.asarray(acceleration_limits, dtype=np.float64)
+            if al.shape != (n,) or not (al > 0).all():
+                raise ValueError(f"acceleration_limits must be ({n},) and positive")
+        out = self._dispatch("planning.time_optimal", model, np.ascontiguousarray(q), np.ascontiguousarray(dq), np.ascontiguousarray(ddq),
+                             vl, tl, al, sd_start, sd_end, g, Ftip)
+        if layout == "time_major":
+            out = {k: (np.ascontiguousarray(np.swapaxes(v, 0, 1)) if v.ndim >= 2 else v) for k, v in out.items()}
+        return out
+
+    def batch_time_optimal_joint_trajectory(self, thetastart_batch, thetaend_batch, N, velocity_limits, torque_limits=None,
+                                            acceleration_limits=None, sd_start=0.0, sd_end=0.0, g=None, Ftip=None) -> Dict[str, np.ndarray]:
+        """batch_time_optimal_parameterization of the straight joint-space lines q(s) = start + s (end - start) of B (start, end)
+        pairs (B, n), on N grid points: dq/ds = end - start, d2q/ds2 = 0.  Adds "positions" (B, N, n) to the result."""
+        sb, eb = np.asarray(thetastart_batch, dtype=np.float64), np.asarray(thetaend_batch, dtype=np.float64)
+        if sb.ndim != 2 or sb.shape != eb.shape:
+            raise ValueError(f"start/end batches must both be (B, n); got {sb.shape} and {eb.shape}")
+        N = int(N)
+        if N < 3:
+            raise ValueError(f"batch_time_optimal_joint_trajectory: N must be >= 3 (got {N})")
+        s = np.arange(N, dtype=np.float64) / (N - 1)
+        d = eb - sb
+        q = sb[:, None, :] + s[None, :, None] * d[:, None, :]
+        dq = np.broadcast_to(d[:, None, :], q.shape)
+        out = self.batch_time_optimal_parameterization(q, dq, np.zeros_like(q), velocity_limits, torque_limits, acceleration_limits,
+                                                       sd_start, sd_end, g, Ftip)
+        out["positions"] = q
+        return out
+
+    def time_optimal_joint_trajectory(self, thetastart, thetaend, N, velocity_limits, torque_limits=None, acceleration_limits=None,
+                                      sd_start=0.0, sd_end=0.0, g=None, Ftip=None) -> Dict[str, np.ndarray]:
+        """batch_time_optimal_joint_trajectory for one (start, end) pair: every result without its leading batch axis."""
+        s, e = np.asarray(thetastart, dtype=np.float64), np.asarray(thetaend, dtype=np.float64)
+        if s.ndim != 1 or s.shape != e.shape:
+            raise ValueError(f"thetastart and thetaend must both be (n,); got {s.shape} and {e.shape}")
+        r = self.batch_time_optimal_joint_trajectory(s[None], e[None], N, velocity_limits, torque_limits, acceleration_limits,
+                                                     float(sd_start), float(sd_end), g, Ftip)
+        return {k: v[0] for k, v in r.items()}
 
     # ------------------------------------------------------------------ legacy dynamics objects (Mlist_per_link=None)
     # The reference's approximation for such objects is not rigid-body dynamics (dynamics/mass_matrix.py:101-132), so there

@@ -345,6 +345,11 @@ def _launch_ilqr_rollout_cpu(model, theta0, dtheta0, taumat, pos, vel, K, k, alp
     return _hip.cpu_ilqr_rollout(model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr, wf, g, dt, want_rows)
 
 
+def _launch_time_optimal_cpu(model, q, dq, ddq, velocity_limits, torque_limits, acceleration_limits, sd_start, sd_end, g, Ftip,
+                             want_rows=True):
+    return _hip.cpu_toppra(model, q, dq, ddq, velocity_limits, torque_limits, acceleration_limits, sd_start, sd_end, g, Ftip, want_rows)
+
+
 def _launch_fd_trajectory_cpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64, layout="batch_major",
                               device_layout=None):
     del device_layout   # (a device-side choice; the host rows are walked in whatever order they come)
@@ -496,6 +501,12 @@ def _launch_ilqr_rollout_gpu(model, theta0, dtheta0, taumat, pos, vel, K, k, alp
     return get_context().ilqr_rollout_host(model, theta0, dtheta0, taumat, pos, vel, K, k, alpha, xref, wq, wr, wf, g, dt, want_rows)
 
 
+def _launch_time_optimal_gpu(model, q, dq, ddq, velocity_limits, torque_limits, acceleration_limits, sd_start, sd_end, g, Ftip,
+                             want_rows=True):
+    return get_context().toppra_host(model, q, dq, ddq, velocity_limits, torque_limits, acceleration_limits, sd_start, sd_end, g, Ftip,
+                                     want_rows)
+
+
 def _launch_fd_trajectory_gpu(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=np.float64, layout="batch_major",
                               device_layout=None):
     return get_context().fd_trajectory_host(model, theta0, dtheta0, taumat, g, Ftipmat, dt, intRes, dtype=dtype, layout=layout,
@@ -586,6 +597,9 @@ def _build_kernel_registry() -> KernelRegistry:
         # "dynamics.forward_trajectory"
         ("dynamics.ilqr_backward", "mp_ilqr_backward_host_f64 / _tm_f64", _launch_ilqr_backward_gpu, _launch_ilqr_backward_cpu),
         ("dynamics.ilqr_rollout", "mp_ilqr_rollout_host_f64 / _tm_f64", _launch_ilqr_rollout_gpu, _launch_ilqr_rollout_cpu),
+        # time-optimal path parameterisation: path-dynamics coefficients and the reachability sweep (csrc/mp_toppra.h)
+        ("planning.time_optimal", "mp_toppra_host_f64 / mp_path_dynamics_f64 + mp_toppra_tm_f64", _launch_time_optimal_gpu,
+         _launch_time_optimal_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):

@@ -80,6 +80,8 @@ class _Joint:
     axis: np.ndarray
     limit: Optional[Tuple[float, float]]
     mimic: Optional[Tuple[str, float, float]]  # (joint, multiplier, offset)
+    velocity: float = float("inf")  # <limit velocity= effort=>, inf where absent
+    effort: float = float("inf")
 
     def child_pose(self, q: float) -> np.ndarray:
         """Pose of the child link in the parent link for joint value q."""
@@ -147,7 +149,10 @@ def _parse(path: str) -> Tuple[Dict[str, _Link], List[_Joint]]:
         limit = (float(lim.get("lower", 0)), float(lim.get("upper", 0))) if lim is not None else None
         mm = je.find("mimic")
         mimic = (mm.get("joint"), float(mm.get("multiplier", 1)), float(mm.get("offset", 0))) if mm is not None else None
-        joints.append(_Joint(name, kind, pe.get("link"), ce.get("link"), _origin_matrix(je.find("origin")), axis, limit, mimic))
+        velocity = float(lim.get("velocity", "inf")) if lim is not None else float("inf")
+        effort = float(lim.get("effort", "inf")) if lim is not None else float("inf")
+        joints.append(_Joint(name, kind, pe.get("link"), ce.get("link"), _origin_matrix(je.find("origin")), axis, limit, mimic, velocity,
+                             effort))
     return links, joints
 
 
@@ -233,6 +238,8 @@ def extract_tables(path: str, tip_link: Optional[str] = None) -> Dict[str, objec
     B = _adjoint(np.linalg.inv(M)) @ S
     return {"M": M, "S_list": S, "B_list": B, "G_list": G, "Mlist_per_link": Mcom, "joint_limits": limits, "omega_list": om,
             "r_list": rl, "joint_names": [j.name for j in actuated], "ee_name": ee,
+            "velocity_limits": np.array([j.velocity for j in actuated], dtype=np.float64),
+            "effort_limits": np.array([j.effort for j in actuated], dtype=np.float64),
             "_tree": {"links": links, "joints": joints, "chain": chain, "roots": roots, "actuated": actuated}}
 
 
@@ -251,6 +258,9 @@ class URDFToSerialManipulator:
         self.urdf_name = str(urdf_name)
         t = extract_tables(self.urdf_name, tip_link)
         self.tables = t
+        # (n,) each, from <limit velocity= effort=>, inf where the attribute is absent; `robot_data` keeps the reference's keys
+        self.velocity_limits = t["velocity_limits"].copy()
+        self.effort_limits = t["effort_limits"].copy()
         self.robot_data = {"M": t["M"], "omega_list": t["S_list"][:3, :], "Slist": t["S_list"], "Blist": t["B_list"],
                            "Glist": t["G_list"], "actuated_joints_num": t["S_list"].shape[1],
                            "joint_limits": [tuple(r) for r in t["joint_limits"]], "Mlist_per_link": t["Mlist_per_link"]}
