@@ -663,6 +663,66 @@ int mp_cartesian_trajectory_cpu_f32(const double* Xstart, const double* Xend, in
 int mp_pd_regulation_cpu_f64(const mp_model* model, const double* theta0, const double* theta_des, const double* Kp, const double* Kd,
                              int64_t K, const double* g, double dt, int steps, double* errors, int32_t* count, int nthreads);
 
+/* ---- sphere-model collision distances, cost and gradients (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED above that;
+ * csrc/mp_collision.h).  No counterpart in this ABI's reference interface, whose collision checker has no geometry.
+ * Robot spheres: S of them (1..64), each with a link index k in 0..n (0 = the fixed base; link k moves with joints 1..k), a radius > 0
+ *   and a centre c given in the SPACE frame at the home configuration q = 0: its world centre at q is prod_{j<=k} exp([S_j] q_j) c.
+ *   mp_collision_create turns the centres into link-local coordinates of the compiled frames and sorts the spheres by link; every
+ *   index it reports is the caller's.  Self pairs: P >= 0 pairs (a, b) of caller indices, a != b.
+ * World obstacles: O >= 0 rows of a kind and 16 doubles (unused ones are ignored), kept in device memory with their count:
+ *     MP_OBSTACLE_SPHERE   c[3], r                      sd(p) = |p - c| - r
+ *     MP_OBSTACLE_CAPSULE  p0[3], p1[3], r              sd(p) = |p - closest point of the segment| - r;  p0 = p1 is a sphere
+ *     MP_OBSTACLE_BOX      c[3], R[9] row-major, h[3]   columns of R = the box axes in the world, l = R^T (p - c), q_i = |l_i| - h_i:
+ *                          outside (some q_i > 0) sd = |max(q, 0)|, direction R (sign(l_i) max(q_i, 0)) / sd; otherwise sd = max_i q_i <= 0
+ *                          with the direction R (sign(l_i) e_i) of the nearest face i, ties to the lowest axis; sign(0) = +
+ *   sd is negative inside; the direction n is the outward unit vector d sd / d p; it is 0 where its length would be below 1e-300
+ *   (coincident centres, a point on a capsule's axis or segment).  r and h may be 0, not negative.
+ * Per row (every output may be NULL; the host forms need at least one):
+ *     dist_world (rows)        min over (sphere s on a link >= 1, obstacle o) of d_so = sd_o(p_s) - r_s; +inf if there is none
+ *     arg_world (rows,2) int32 that (sphere, obstacle), or (-1, -1); of equal minima the first in (link, caller index), then obstacle order
+ *     dist_self (rows)         min over the pairs of d_ab = |p_a - p_b| - r_a - r_b; +inf without pairs;  arg_self (rows,2) = (a, b) of
+ *                              the first such pair, or (-1, -1)
+ *     grad_dist_world, grad_dist_self (rows,n)   d dist / d q = n^T J_p(q) at the witness (for a pair, of p_a minus of p_b, n the
+ *                              direction from b to a), zero columns beyond the witness's link; zeros without a witness
+ *     cost (rows)              sum_{s on a link >= 1, o} phi(d_so; eps_world) + sum_pairs phi(d_ab; eps_self), the CHOMP hinge
+ *                              phi = -d + eps/2 (d < 0), (d - eps)^2 / (2 eps) (0 <= d < eps), 0 beyond: C1; eps_* > 0 and finite
+ *     grad (rows,n)            d cost / d q.  With F = phi'(d) n (+F on a, -F on b for a pair) and the space-frame wrench of link k
+ *                              W_k = [sum p x F; sum F]:  grad_j = J_s,j . sum_{k >= j} W_k, one sweep from the tip
+ *   The base's spheres (link 0) meet the world in no output: they are constants of q; they take part in the pairs.
+ *   A row with a non-finite q has NaN in every float output and -1 in the indices; other rows are untouched.
+ * mp_collision_create validates and copies the tables: S outside 1..64, a link outside 0..n, a radius that is not positive and finite,
+ *   a non-finite centre, a pair index outside 0..S-1 or a == b are MP_ERR_INVALID with a message.  The handle belongs to the model's
+ *   joint count, not to a context; mp_collision_destroy releases it and its device tables (no launch that uses it may be in flight).
+ * mp_collision_set_world(ctx, h, O, kind, params): kind (O) int32, params (O,16) host arrays.  An unknown kind, a non-finite or negative
+ *   parameter that the kind uses, or a box R with |R^T R - 1| > 1e-9 is MP_ERR_INVALID and leaves the previous world in place.  The
+ *   table is copied to the context's device behind the launches already on its compute stream and the call returns when the copy is
+ *   done; launches made afterwards - replays of a graph captured earlier included, as long as O does not outgrow the table's capacity
+ *   (it grows in steps of 64 obstacles; a replaced table stays allocated until the handle is destroyed) - see the new world.  The robot's
+ *   tables are not rebuilt.  ctx = NULL sets the world of the _cpu twin only; a handle that no call has given a world has O = 0.  Not
+ *   allowed during a capture.
+ * mp_collision_f64: d_q (rows,n) device rows, 16-byte aligned like every output.  Asynchronous, no synchronisation; it allocates nothing
+ *   once the handle is resident on the context (its first mp_collision_set_world, mp_collision_f64 or _host_f64 there makes it so),
+ *   and may then be captured into a launch graph.  mp_collision_host_f64: host arrays, device memory from the context's pool.
+ *   mp_collision_cpu_f64: the kernel's per-row code on the host, no context. */
+#define MP_OBSTACLE_SPHERE 0
+#define MP_OBSTACLE_CAPSULE 1
+#define MP_OBSTACLE_BOX 2
+#define MP_COLLISION_MAX_SPHERES 64
+typedef struct mp_collision mp_collision;
+int mp_collision_create(const mp_model* model, int S, const int32_t* link, const double* centre, const double* radius, int P,
+                        const int32_t* pairs, mp_collision** out);
+int mp_collision_destroy(mp_collision* h);
+int mp_collision_set_world(mp_ctx* ctx, mp_collision* h, int O, const int32_t* kind, const double* params);
+int mp_collision_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q, int64_t rows, double eps_world,
+                     double eps_self, double* d_dist_world, int32_t* d_arg_world, double* d_dist_self, int32_t* d_arg_self,
+                     double* d_grad_dist_world, double* d_grad_dist_self, double* d_cost, double* d_grad);
+int mp_collision_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q, int64_t rows, double eps_world,
+                          double eps_self, double* dist_world, int32_t* arg_world, double* dist_self, int32_t* arg_self,
+                          double* grad_dist_world, double* grad_dist_self, double* cost, double* grad);
+int mp_collision_cpu_f64(const mp_model* model, const mp_collision* h, const double* q, int64_t rows, double eps_world, double eps_self,
+                         double* dist_world, int32_t* arg_world, double* dist_self, int32_t* arg_self, double* grad_dist_world,
+                         double* grad_dist_self, double* cost, double* grad, int nthreads);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new; the reference is single-device) ------
  * Trajectory batches are sharded over ranks with no exchange during compute; the only collective is
  * the all-gather that reassembles the torque history.  Rank 0 creates the id, the launcher

@@ -21,9 +21,20 @@ from .urdf import URDFToSerialManipulator
 from . import trac_ik
 from .trac_ik import TracIKSolver, trac_ik_solve
 
+
+
+def __getattr__(name):  # the collision module is imported on first use
+    if name in ("collision", "SphereCollisionModel"):
+        import importlib
+
+        mod = importlib.import_module(".collision", __name__)
+        return mod if name == "collision" else mod.SphereCollisionModel
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 __version__ = "0.1.0"
 __all__ = ["ArrayBackend", "HipBackend", "NumpyBackend", "get_backend", "get_registered", "register", "set_backend",
            "use_backend", "BackendNotSupportedError", "KernelRegistration", "KernelRegistry", "check_hip_availability",
            "execute_registered_kernel", "get_context", "get_gpu_properties", "get_registered_kernel",
            "SerialManipulator", "ManipulatorDynamics", "OptimizedTrajectoryPlanning", "TrajectoryPlanning", "ManipulatorController", "Singularity", "ik_helpers", "utils", "PotentialField",
-           "load_robot", "robot_tables", "robot_urdf", "URDFToSerialManipulator", "trac_ik", "TracIKSolver", "trac_ik_solve"]
+           "load_robot", "robot_tables", "robot_urdf", "URDFToSerialManipulator", "trac_ik", "TracIKSolver", "trac_ik_solve", "SphereCollisionModel"]

@@ -173,6 +173,12 @@ SIGNATURES = {
     "mp_fd_trajectory_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, _i64, _c_dp, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp, ctypes.c_int]),
     "mp_inverse_kinematics_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, ctypes.c_int64, _c_dp, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_uint32, _c_dp, _vp, _vp, _vp, ctypes.c_int]),
     "mp_cartesian_trajectory_cpu_f32": (ctypes.c_int, [_c_dp, _c_dp, _i64, _i64, ctypes.c_double, ctypes.c_int, _c_fp, _c_fp, _c_fp, _c_fp, ctypes.c_int]),
+    "mp_collision_create": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _c_dp, _c_dp, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
+    "mp_collision_destroy": (ctypes.c_int, [_vp]),
+    "mp_collision_set_world": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _c_dp]),
+    "mp_collision_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_collision_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _i64, ctypes.c_double, ctypes.c_double, _c_dp, _vp, _c_dp, _vp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_collision_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _i64, ctypes.c_double, ctypes.c_double, _c_dp, _vp, _c_dp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_comm_unique_id": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8)]),
     "mp_comm_create": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     "mp_comm_destroy": (ctypes.c_int, [_vp]),
@@ -668,6 +674,23 @@ class HipContext:
         _check(self.lib.mp_opspace_torque_f64(self.handle, model.handle, _opspace_frame(frame), _opspace_task(task), float(damping),
                                               _p(d_q), _p(d_qd), _p(d_acc), _p(d_tau0), int(rows), _dptr(_vec_or_none(g, 3, "g")),
                                               _p(d_tau)))
+
+    def collision(self, model, collision, d_q, rows, eps_world, eps_self, d_dist_world=None, d_arg_world=None, d_dist_self=None,
+                  d_arg_self=None, d_grad_dist_world=None, d_grad_dist_self=None, d_cost=None, d_grad=None):
+        """Sphere-model collision distances, cost and gradients on device buffers (float64; csrc/mp_collision.h): `collision` is a
+        HipCollision; d_q (rows,n); outputs dist_* / cost (rows), arg_* (rows,2) int32, grad_* (rows,n), each may be None (at least one
+        given); asynchronous (capturable once the handle has been used or given a world on this context)."""
+        _check(self.lib.mp_collision_f64(self.handle, model.handle, collision.handle, _p(d_q), int(rows), float(eps_world),
+                                         float(eps_self), _p(d_dist_world), _p(d_arg_world), _p(d_dist_self), _p(d_arg_self),
+                                         _p(d_grad_dist_world), _p(d_grad_dist_self), _p(d_cost), _p(d_grad)))
+
+    def collision_host(self, model, collision, q, eps_world, eps_self, want=None):
+        """The same on host rows through the context's pool: a dict of the outputs named in `want` (default: all of COLLISION_OUTPUTS)."""
+        return _collision((self.handle,), self.lib.mp_collision_host_f64, model, collision, q, eps_world, eps_self, want)
+
+    def collision_set_world(self, collision, kinds, params):
+        """Replaces the obstacle table of `collision` on this context's device, behind the launches already on its stream."""
+        collision.set_world(kinds, params, ctx=self)
 
     def cartesian_trajectory(self, d_Xstart, d_Xend, B, N, Tf, method, d_pos, d_vel, d_acc, d_orient):
         _check(self.lib.mp_cartesian_trajectory_f32(self.handle, _p(d_Xstart), _p(d_Xend), int(B), int(N), float(Tf), int(method),
@@ -1319,6 +1342,78 @@ def cpu_opspace(model: "HipModel", q, qd, g=None, frame="hybrid", task="full", d
 def cpu_opspace_torque(model: "HipModel", q, qd, acc, g=None, tau0=None, frame="hybrid", task="full", damping=0.0, nthreads: int = 0):
     """CPU twin of HipContext.opspace_torque_host."""
     return _opspace_torque(load_library().mp_opspace_torque_cpu_f64, (), model, frame, task, damping, q, qd, acc, tau0, g, nthreads)
+
+
+COLLISION_OUTPUTS = ("dist_world", "arg_world", "dist_self", "arg_self", "grad_dist_world", "grad_dist_self", "cost", "grad")
+OBSTACLE_SPHERE, OBSTACLE_CAPSULE, OBSTACLE_BOX = 0, 1, 2
+MP_COLLISION_MAX_SPHERES = 64
+
+
+class HipCollision:
+    """Sphere collision model of one robot (mp_collision_create).  Host-only object: no GPU needed to build one.  links (S) in 0..n,
+    centres (S,3) in the space frame at q = 0, radii (S), pairs (P,2) of sphere indices."""
+
+    def __init__(self, model: "HipModel", links, centres, radii, pairs=None):
+        self.lib = load_library()
+        self.handle = None
+        lk = np.ascontiguousarray(np.asarray(links, dtype=np.int32).reshape(-1))
+        S = lk.shape[0]
+        c = _as_c(centres, np.float64, (S, 3), "centres")
+        r = _as_c(radii, np.float64, (S,), "radii")
+        pr = np.zeros((0, 2), dtype=np.int32) if pairs is None else np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
+        p = _vp()
+        _check(self.lib.mp_collision_create(model.handle, S, lk.ctypes.data_as(_vp), _dptr(c), _dptr(r), pr.shape[0],
+                                            pr.ctypes.data_as(_vp) if pr.shape[0] else None, ctypes.byref(p)))
+        self.handle = p
+        self.n, self.S, self.P = model.n, S, pr.shape[0]
+
+    def set_world(self, kinds, params, ctx: Optional["HipContext"] = None) -> None:
+        """kinds (O) of OBSTACLE_*, params (O,16).  ctx=None sets the world the CPU twin reads; with a context the table is also copied
+        to its device."""
+        kd = np.ascontiguousarray(np.asarray(kinds, dtype=np.int32).reshape(-1))
+        O = kd.shape[0]
+        pm = _as_c(np.zeros((0, 16)) if O == 0 else params, np.float64, (O, 16), "params")
+        _check(self.lib.mp_collision_set_world(None if ctx is None else ctx.handle, self.handle, O, kd.ctypes.data_as(_vp) if O else None,
+                                               _dptr(pm) if O else None))
+
+    def destroy(self) -> None:
+        if getattr(self, "handle", None) is not None:
+            self.lib.mp_collision_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def _collision(lead, fn, model, collision, q, eps_world, eps_self, want, nthreads=None):
+    want = COLLISION_OUTPUTS if want is None else tuple(want)
+    for w in want:
+        if w not in COLLISION_OUTPUTS:
+            raise ValueError(f"unknown collision output {w!r}; choose from {COLLISION_OUTPUTS}")
+    q = _as_c(q, np.float64, name="q")
+    if q.ndim != 2 or q.shape[1] != model.n:
+        raise ValueError(f"q must be (rows, {model.n}); got {q.shape}")
+    rows, n = q.shape
+    shapes = {"dist_world": (rows,), "arg_world": (rows, 2), "dist_self": (rows,), "arg_self": (rows, 2), "grad_dist_world": (rows, n),
+              "grad_dist_self": (rows, n), "cost": (rows,), "grad": (rows, n)}
+    out = {w: np.empty(shapes[w], dtype=np.int32 if w.startswith("arg") else np.float64) for w in want}
+    ptrs = []
+    for w in COLLISION_OUTPUTS:
+        a = out.get(w)
+        ptrs.append(None if a is None else (a.ctypes.data_as(_vp) if w.startswith("arg") else _dptr(a)))
+    args = list(lead) + [model.handle, collision.handle, _dptr(q), rows, float(eps_world), float(eps_self)] + ptrs
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return out
+
+
+def cpu_collision(model: "HipModel", collision: "HipCollision", q, eps_world, eps_self, want=None, nthreads: int = 0) -> dict:
+    """CPU twin of HipContext.collision_host."""
+    return _collision((), load_library().mp_collision_cpu_f64, model, collision, q, eps_world, eps_self, want, nthreads)
 
 
 def _pd_regulation_args(model, theta0, theta_des, Kp, Kd, g, steps):

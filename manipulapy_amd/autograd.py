@@ -42,7 +42,7 @@ import torch
 from .registry import execute_registered_kernel
 
 __all__ = ["inverse_dynamics", "forward_dynamics", "forward_dynamics_trajectory", "inverse_dynamics_parameters", "fk_jacobian",
-           "forward_kinematics", "jacobian"]
+           "forward_kinematics", "jacobian", "collision_cost"]
 
 
 def _const(v, name):
@@ -345,3 +345,40 @@ def forward_kinematics(sm, q, frame: str = "space") -> torch.Tensor:
 def jacobian(sm, q, frame: str = "space") -> torch.Tensor:
     """J of fk_jacobian: SerialManipulator.jacobian(q, frame), differentiable in q."""
     return fk_jacobian(sm, q, frame)[1]
+
+
+class _CollisionCost(torch.autograd.Function):
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gcost):
+        if gcost is None or not ctx.needs_input_grad[1]:
+            return None, None, None, None
+        (grad,) = ctx.saved_tensors
+        return None, grad * gcost.to(grad.dtype).unsqueeze(-1), None, None
+
+    @staticmethod
+    def forward(ctx, cm, q, eps_world, eps_self):
+        n = cm.n
+        if q.dim() not in (1, 2, 3) or q.shape[-1] != n:
+            raise ValueError(f"q must be ({n},), (rows, {n}) or (B, N, {n}), got {tuple(q.shape)}")
+        lead = tuple(q.shape[:-1])
+        if _on_device(q):
+            hctx, (a,) = _device_rows((q,), ("q",))
+            cm.sync_world(hctx)
+            cost, grad = a.new_empty(lead), torch.empty_like(a)
+            _device_launch(hctx, lambda: hctx.collision(cm.model, cm.handle, a.data_ptr(), a.numel() // n, eps_world, eps_self,
+                                                        d_cost=cost.data_ptr(), d_grad=grad.data_ptr()))
+        else:
+            r = execute_registered_kernel("planning.collision_spheres", cm, _rows(q, "q").reshape(-1, n), eps_world, eps_self,
+                                          ("cost", "grad"))
+            cost, grad = torch.from_numpy(r["cost"].reshape(lead)), torch.from_numpy(r["grad"].reshape(lead + (n,)))
+        ctx.save_for_backward(grad)
+        return cost
+
+
+def collision_cost(model, q, eps_world: float, eps_self: float) -> torch.Tensor:
+    """The hinge collision cost of a collision.SphereCollisionModel at q ((n,), (rows, n) or (B, N, n)), one value a row,
+    differentiable in q: the backward pass is the kernel's own gradient times the incoming cotangent.  CPU float64 tensors, or ROCm
+    float64 tensors on the library context's device (computed there on torch's current stream, module docstring).  Once
+    differentiable: a second derivative is not provided and asking for one raises."""
+    return _CollisionCost.apply(model, _as_tensor(q), float(eps_world), float(eps_self))

@@ -1,0 +1,167 @@
+"""Sphere-model collision checking for batches of configurations: signed distances to primitive obstacles and between the robot's
+own spheres, the CHOMP hinge cost and its gradient (csrc/mp_collision.h; the conventions are those of include/manipula_hip.h).
+
+The robot is S spheres, each fixed to a link (0 = the base .. n) and given by its centre in the space frame at q = 0; the world is a
+table of spheres, capsules and oriented boxes that can be replaced at any time.  No meshes: `potential_field.CollisionChecker` keeps
+mirroring the reference's mesh-less checker and is not touched by this module.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+
+from . import _hip
+from .registry import execute_registered_kernel
+
+__all__ = ["SphereCollisionModel", "COLLISION_OP"]
+
+# The registry's sorted name list starts with "control.pd_regulation" (the unknown-name message is pinned by a test), so the operation
+# lives in the "planning" family rather than in one of its own that would sort ahead of it.
+COLLISION_OP = "planning.collision_spheres"
+
+
+def _hip_model_of(obj) -> _hip.HipModel:
+    if isinstance(obj, _hip.HipModel):
+        return obj
+    if hasattr(obj, "_kin_model"):            # SerialManipulator
+        return obj._kin_model()
+    if hasattr(obj, "_derivative_model"):     # ManipulatorDynamics
+        return obj._derivative_model("SphereCollisionModel")
+    raise TypeError(f"expected a SerialManipulator, a ManipulatorDynamics or a compiled model, got {type(obj).__name__}")
+
+
+class SphereCollisionModel:
+    """links (S,) in 0..n, centres (S, 3) in the space frame at the home configuration, radii (S,), pairs (P, 2) of sphere indices
+    checked against each other (None: no self-collision pairs)."""
+
+    def __init__(self, serial_manipulator_or_dynamics, links, centres, radii, pairs=None):
+        self.model = _hip_model_of(serial_manipulator_or_dynamics)
+        self.n = self.model.n
+        self.links = np.asarray(links, dtype=np.int32).reshape(-1).copy()
+        self.centres = np.asarray(centres, dtype=np.float64).reshape(-1, 3).copy()
+        self.radii = np.asarray(radii, dtype=np.float64).reshape(-1).copy()
+        self.pairs = np.zeros((0, 2), dtype=np.int32) if pairs is None else np.asarray(pairs, dtype=np.int32).reshape(-1, 2).copy()
+        self.handle = _hip.HipCollision(self.model, self.links, self.centres, self.radii, self.pairs)
+        self.kinds = np.zeros(0, dtype=np.int32)
+        self.params = np.zeros((0, 16))
+        self._version = 0
+        self._uploaded = {}  # id(context) -> world version on its device
+
+    # ------------------------------------------------------------------ construction from a kinematic chain
+    @classmethod
+    def from_points(cls, serial_manipulator_or_dynamics, points, radius, spacing=None, base_radius=None, base_centre=None):
+        """Spheres of `radius` strung along the segments points[i] -> points[i + 1], i = 0..n-1 (home positions in the space frame);
+        segment i moves with link i + 1.  A segment of length L gets max(1, ceil(L / spacing)) spheres, evenly spread (spacing
+        defaults to the radius); a zero-length segment gets one.  `base_radius` adds one sphere on link 0 at `base_centre` (default:
+        the origin).  Default pairs: all pairs on links at least two apart that do not overlap at home."""
+        pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+        n = pts.shape[0] - 1
+        radius = float(radius)
+        step = radius if spacing is None else float(spacing)
+        if not (radius > 0 and step > 0):
+            raise ValueError("radius and spacing must be positive")
+        links, centres, radii = [], [], []
+        if base_radius is not None:
+            links.append(0)
+            centres.append(np.zeros(3) if base_centre is None else np.asarray(base_centre, dtype=np.float64).reshape(3))
+            radii.append(float(base_radius))
+        for i in range(n):
+            a, b = pts[i], pts[i + 1]
+            m = max(1, int(np.ceil(np.linalg.norm(b - a) / step - 1e-9)))
+            for k in range(m):
+                links.append(i + 1)
+                centres.append(a + (k + 0.5) / m * (b - a))
+                radii.append(radius)
+        links, centres, radii = np.array(links, dtype=np.int32), np.array(centres), np.array(radii)
+        if len(links) > _hip.MP_COLLISION_MAX_SPHERES:
+            raise ValueError(f"{len(links)} spheres, more than {_hip.MP_COLLISION_MAX_SPHERES}: raise the spacing")
+        return cls(serial_manipulator_or_dynamics, links, centres, radii, cls.default_pairs(links, centres, radii))
+
+    @staticmethod
+    def default_pairs(links, centres, radii) -> np.ndarray:
+        """All pairs (a < b) on links at least two apart whose spheres do not overlap at the home configuration."""
+        out = []
+        for a in range(len(links)):
+            for b in range(a + 1, len(links)):
+                if abs(int(links[a]) - int(links[b])) >= 2 and np.linalg.norm(centres[a] - centres[b]) > radii[a] + radii[b]:
+                    out.append((a, b))
+        return np.array(out, dtype=np.int32).reshape(-1, 2)
+
+    @classmethod
+    def from_urdf(cls, processor, radius, spacing=None, base_radius=None):
+        """From a URDFToSerialManipulator: the points are the home origins of the child links of consecutive actuated joints, then
+        the end effector (processor.link_fk(zeros)); the base sphere, if asked for, sits at the root link's origin.  Link k is the
+        child link of actuated joint k (a gripper's mimic finger is not modelled: the screw model holds it still)."""
+        by_child = {j.child: j for j in processor._tree["chain"]}
+        prev = None
+        for j in processor._tree["actuated"]:  # each actuated joint must hang off the previous one's child through fixed joints
+            cur = j.parent
+            while prev is not None and cur != prev.child:
+                up = by_child.get(cur)
+                if up is None or up in processor._tree["actuated"] or up.mimic is not None:
+                    raise ValueError(f"from_urdf: joint {j.name} is not downstream of {prev.name}: the actuated joints are not one chain")
+                cur = up.parent
+            prev = j
+        home = processor.link_fk(np.zeros(processor.num_dofs))
+        names = [j.child for j in processor._tree["actuated"]] + [processor.end_effector_name]
+        pts = np.array([home[name][:3, 3] for name in names])
+        root = processor._tree["roots"][0]
+        return cls.from_points(processor.serial_manipulator, pts, radius, spacing, base_radius, home[root][:3, 3])
+
+    # ------------------------------------------------------------------ the world
+    def set_world(self, spheres=None, capsules=None, boxes=None) -> None:
+        """spheres (k, 4) rows [centre, r]; capsules (k, 7) rows [p0, p1, r]; boxes (k, 15) rows [centre, R row-major, half-extents]
+        or a list of (centre, R (3, 3), half_extents) triples.  The table holds the spheres, then the capsules, then the boxes:
+        obstacle indices in `arg_world` count in that order.  Replaces the previous world; the sphere model is not rebuilt."""
+        kinds, rows = [], []
+        for kind, data, width in ((_hip.OBSTACLE_SPHERE, spheres, 4), (_hip.OBSTACLE_CAPSULE, capsules, 7), (_hip.OBSTACLE_BOX, boxes, 15)):
+            if data is None or len(data) == 0:
+                continue
+            if kind == _hip.OBSTACLE_BOX and not isinstance(data, np.ndarray):
+                data = [np.concatenate([np.asarray(c, dtype=np.float64).reshape(3), np.asarray(R, dtype=np.float64).reshape(9),
+                                        np.asarray(h, dtype=np.float64).reshape(3)]) for c, R, h in data]
+            arr = np.asarray(data, dtype=np.float64).reshape(-1, width)
+            for r in arr:
+                kinds.append(kind)
+                rows.append(np.concatenate([r, np.zeros(16 - width)]))
+        self.set_world_table(kinds, np.array(rows).reshape(-1, 16))
+
+    def set_world_table(self, kinds, params) -> None:
+        """The obstacle table as the C interface takes it: kinds (O,), params (O, 16)."""
+        kinds = np.asarray(kinds, dtype=np.int32).reshape(-1)
+        params = np.asarray(params, dtype=np.float64).reshape(-1, 16)
+        self.handle.set_world(kinds, params)   # validates; the CPU twin reads this copy
+        self.kinds, self.params = kinds.copy(), params.copy()
+        self._version += 1
+
+    def sync_world(self, ctx) -> None:
+        """Makes the world on `ctx`'s device the current one (a copy behind the launches already on its stream; no-op when it is)."""
+        if self._uploaded.get(id(ctx)) != self._version:
+            self.handle.set_world(self.kinds, self.params, ctx=ctx)
+            self._uploaded[id(ctx)] = self._version
+
+    # ------------------------------------------------------------------ queries
+    def _run(self, q, eps_world, eps_self, want):
+        q = np.asarray(q, dtype=np.float64)
+        if q.ndim not in (1, 2, 3) or q.shape[-1] != self.n:
+            raise ValueError(f"q must be ({self.n},), (rows, {self.n}) or (B, N, {self.n}); got {q.shape}")
+        lead = q.shape[:-1]
+        out = execute_registered_kernel(COLLISION_OP, self, np.ascontiguousarray(q.reshape(-1, self.n)), eps_world, eps_self, want)
+        return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}
+
+    def distances(self, q, want_grad: bool = False) -> dict:
+        """dist_world, arg_world, dist_self, arg_self of every row of q ((rows, n) or (B, N, n)); with `want_grad` also
+        grad_dist_world and grad_dist_self."""
+        want = ("dist_world", "arg_world", "dist_self", "arg_self") + (("grad_dist_world", "grad_dist_self") if want_grad else ())
+        return self._run(q, 1.0, 1.0, want)
+
+    def cost(self, q, eps_world, eps_self, want_grad: bool = True):
+        """The hinge cost of every row, and its gradient with `want_grad`: cost, or (cost, grad)."""
+        r = self._run(q, eps_world, eps_self, ("cost", "grad") if want_grad else ("cost",))
+        return (r["cost"], r["grad"]) if want_grad else r["cost"]
+
+    def in_collision(self, q, margin: float = 0.0) -> np.ndarray:
+        """True where the world or the self clearance of a row is below `margin`."""
+        r = self._run(q, 1.0, 1.0, ("dist_world", "dist_self"))
+        return (r["dist_world"] < margin) | (r["dist_self"] < margin)

@@ -3342,4 +3342,141 @@ int mp_ctx_flush_parked(mp_ctx* ctx) {
   return MP_OK;
 }
 int mp_ctx_device(mp_ctx* ctx) { return ctx->device; }
+// ---- sphere-model collision (mp_collision.h).  The handle's tables live in device memory of their own (not the pool: a handle
+// outlives contexts), one copy per context that has used it; mp_collision_destroy (mp_cpu.cpp) releases them through `release`.
+static void collision_release(mp_collision* h) {
+  if (h->resident.empty()) return;
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  for (auto& kv : h->resident) {
+    mp_collision::Resident& R = kv.second;
+    (void)hipSetDevice(R.device);
+    if (R.sph) (void)hipFree(R.sph);
+    if (R.world) (void)hipFree(R.world);
+    for (void* p : R.retired) (void)hipFree(p);
+  }
+  h->resident.clear();
+  if (prev >= 0) (void)hipSetDevice(prev);
+}
+// header + obstacles to the context's table, growing it in steps of 64 obstacles; returns when the copy is done
+static int collision_upload_world(mp_ctx* ctx, mp_collision::Resident& R, const std::vector<MpColObstacle>& w) {
+  const int O = (int)w.size();
+  if (!R.world || O > R.cap) {
+    const int cap = O <= 64 ? 64 : ((O + 63) / 64) * 64;
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, sizeof(MpColWorld) + (size_t)cap * sizeof(MpColObstacle)));
+    if (R.world) R.retired.push_back(R.world);
+    R.world = p;
+    R.cap = cap;
+  }
+  std::vector<char> img(sizeof(MpColWorld) + (size_t)O * sizeof(MpColObstacle));
+  const MpColWorld hdr = {O, {0, 0, 0}};
+  std::memcpy(img.data(), &hdr, sizeof hdr);
+  if (O) std::memcpy(img.data() + sizeof hdr, w.data(), (size_t)O * sizeof(MpColObstacle));
+  H2D(R.world, img.data(), img.size());
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+static int collision_resident(const char* fn, mp_ctx* ctx, mp_collision* h, mp_collision::Resident** out) {
+  auto it = h->resident.find(ctx->uid);
+  if (it != h->resident.end()) { *out = &it->second; return MP_OK; }
+  REQUIRE(!ctx->capturing, "%s: the collision handle is not on this context's device yet: call mp_collision_set_world or launch once before the capture", fn);
+  mp_collision::Resident R;
+  R.device = ctx->device;
+  const size_t pb = h->pairs.size() * sizeof(MpColPair);
+  HIP_TRY(hipMalloc(&R.sph, sizeof(MpColSpheres) + (pb ? pb : sizeof(MpColPair))));
+  h->release = collision_release;
+  mp_collision::Resident& K = h->resident[ctx->uid] = R;
+  H2D(K.sph, &h->sph, sizeof(MpColSpheres));
+  if (pb) H2D(static_cast<char*>(K.sph) + sizeof(MpColSpheres), h->pairs.data(), pb);
+  if (int rc = collision_upload_world(ctx, K, h->world)) return rc;
+  *out = &K;
+  return MP_OK;
+}
+static int collision_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q, int64_t rows,
+                          double eps_world, double eps_self, double* d_dw, int32_t* d_aw, double* d_ds, int32_t* d_as, double* d_gdw,
+                          double* d_gds, double* d_cost, double* d_grad) {
+  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  REQUIRE(eps_world > 0.0 && eps_self > 0.0 && std::isfinite(eps_world) && std::isfinite(eps_self),
+          "%s: eps_world and eps_self must be positive and finite", fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (rows == 0) return MP_OK;
+  REQUIRE(d_q, "%s: null device pointer", fn);
+  REQUIRE(d_dw || d_aw || d_ds || d_as || d_gdw || d_gds || d_cost || d_grad, "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_q) && aligned16(d_dw) && aligned16(d_aw) && aligned16(d_ds) && aligned16(d_as) && aligned16(d_gdw) &&
+              aligned16(d_gds) && aligned16(d_cost) && aligned16(d_grad),
+          "%s: device pointers must be 16-byte aligned", fn);
+  std::lock_guard<std::mutex> hl(h->mu);
+  mp_collision::Resident* R = nullptr;
+  if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
+  PROFILE_SCOPE(ctx, fn);
+  HIP_TRY(mpk_collision(ctx->compute, model->d, h->sph.S, static_cast<const MpColSpheres*>(R->sph),
+                        reinterpret_cast<const MpColPair*>(static_cast<const char*>(R->sph) + sizeof(MpColSpheres)),
+                        static_cast<const MpColWorld*>(R->world), d_q, (long)rows, eps_world, eps_self, d_dw, d_aw, d_ds, d_as, d_gdw,
+                        d_gds, d_cost, d_grad));
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_collision_set_world(mp_ctx* ctx, mp_collision* h, int O, const int32_t* kind, const double* params) {
+  const char* fn = "mp_collision_set_world";
+  REQUIRE(h, "%s: null collision handle", fn);
+  std::vector<MpColObstacle> w;
+  if (int rc = mp_collision_pack_world(fn, O, kind, params, &w)) return rc;
+  if (!ctx) {
+    std::lock_guard<std::mutex> hl(h->mu);
+    h->world.swap(w);
+    return MP_OK;
+  }
+  CTX_ENTER(ctx);
+  REQUIRE(!ctx->capturing, "%s: not allowed while a launch graph is being captured (mp_graph_begin)", fn);
+  std::lock_guard<std::mutex> hl(h->mu);
+  h->world.swap(w);
+  auto it = h->resident.find(ctx->uid);
+  if (it != h->resident.end()) return collision_upload_world(ctx, it->second, h->world);
+  mp_collision::Resident* R = nullptr;
+  return collision_resident(fn, ctx, h, &R);  // (uploads the world with the rest)
+}
+
+int mp_collision_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q, int64_t rows, double eps_world,
+                     double eps_self, double* d_dist_world, int32_t* d_arg_world, double* d_dist_self, int32_t* d_arg_self,
+                     double* d_grad_dist_world, double* d_grad_dist_self, double* d_cost, double* d_grad) {
+  return collision_impl("mp_collision_f64", ctx, model, h, d_q, rows, eps_world, eps_self, d_dist_world, d_arg_world, d_dist_self,
+                        d_arg_self, d_grad_dist_world, d_grad_dist_self, d_cost, d_grad);
+}
+
+int mp_collision_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q, int64_t rows, double eps_world,
+                          double eps_self, double* dist_world, int32_t* arg_world, double* dist_self, int32_t* arg_self,
+                          double* grad_dist_world, double* grad_dist_self, double* cost, double* grad) {
+  const char* fn = "mp_collision_host_f64";
+  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (rows == 0) return MP_OK;
+  REQUIRE(q, "%s: null host pointer", fn);
+  const size_t n = (size_t)model->d.n, rb = (size_t)rows * sizeof(double), ib = (size_t)rows * 2 * sizeof(int32_t);
+  void* const host[8] = {dist_world, arg_world, dist_self, arg_self, grad_dist_world, grad_dist_self, cost, grad};
+  const size_t bytes[8] = {rb, ib, rb, ib, n * rb, n * rb, rb, n * rb};
+  Scratch sc(ctx);
+  void *dq, *dev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (int rc = sc.get(n * rb, &dq)) return rc;
+  for (int k = 0; k < 8; ++k)
+    if (host[k]) if (int rc = sc.get(bytes[k], &dev[k])) return rc;
+  H2D(dq, q, n * rb);
+  if (int rc = collision_impl(fn, ctx, model, h, (double*)dq, rows, eps_world, eps_self, (double*)dev[0], (int32_t*)dev[1], (double*)dev[2],
+                              (int32_t*)dev[3], (double*)dev[4], (double*)dev[5], (double*)dev[6], (double*)dev[7]))
+    return rc;
+  for (int k = 0; k < 8; ++k)
+    if (host[k]) D2H(host[k], dev[k], bytes[k]);
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+
+}  // extern "C"
+
 int mp_set_error(int code, const char* msg) { return set_err(code, "%s", msg); }

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 #include <thread>
 #include <type_traits>
 #include <vector>
@@ -30,6 +31,7 @@
 #include "mp_rollout_vjp.h"
 #include "mp_ilqr.h"
 #include "mp_toppra.h"
+#include "mp_collision.h"
 
 namespace {
 const double kG[3] = {0.0, 0.0, -9.81};
@@ -1048,6 +1050,164 @@ int mp_cartesian_trajectory_cpu_f32(const double* Xstart, const double* Xend, in
       std::memcpy(orient + r * 9, o, sizeof o);
     }
   });
+  return MP_OK;
+}
+
+// ---- sphere-model collision (mp_collision.h): the tables' checks, the handle, and the kernel's per-row code over host rows
+static int col_fail(const char* fmt, const char* fn, long a = 0, double b = 0.0) {
+  char msg[256];
+  std::snprintf(msg, sizeof msg, fmt, fn, a, b);
+  return fail(msg);
+}
+
+int mp_collision_create(const mp_model* model, int S, const int32_t* link, const double* centre, const double* radius, int P,
+                        const int32_t* pairs, mp_collision** out) {
+  const char* fn = "mp_collision_create";
+  if (!out) return col_fail("%s: null output", fn);
+  *out = nullptr;
+  if (!model) return col_fail("%s: null model", fn);
+  if (model->big) {
+    char msg[192];
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (S < 1 || S > MP_COL_MAX_SPHERES) return col_fail("%s: %ld spheres, outside 1..64", fn, S);
+  if (P < 0) return col_fail("%s: negative pair count", fn);
+  if (!link || !centre || !radius || (P > 0 && !pairs)) return col_fail("%s: null table", fn);
+  const MpModel<double>& M = model->d;
+  const int n = M.n;
+  for (int s = 0; s < S; ++s) {
+    if (link[s] < 0 || link[s] > n) return col_fail("%s: sphere %ld: link outside 0..n", fn, s);
+    if (!(radius[s] > 0.0) || !std::isfinite(radius[s])) return col_fail("%s: sphere %ld: radius %g is not positive and finite", fn, s, radius[s]);
+    for (int k = 0; k < 3; ++k)
+      if (!std::isfinite(centre[3 * s + k])) return col_fail("%s: sphere %ld: non-finite centre", fn, s);
+  }
+  for (int k = 0; k < P; ++k) {
+    const int a = pairs[2 * k], b = pairs[2 * k + 1];
+    if (a < 0 || a >= S || b < 0 || b >= S) return col_fail("%s: pair %ld: sphere index outside 0..S-1", fn, k);
+    if (a == b) return col_fail("%s: pair %ld: a sphere paired with itself", fn, k);
+  }
+  mp_collision* h = new (std::nothrow) mp_collision;
+  if (!h) return col_fail("%s: out of host memory", fn);
+  h->n = n;
+  // the link frames at the home configuration
+  double R[MP_MAX_DOF][9], p[MP_MAX_DOF][3];
+  switch (n) {
+#define MP_COL_HOME(NN)                                                              \
+    case NN: {                                                                       \
+      double z[NN] = {}, Rn[NN][9], pn[NN][3];                                       \
+      mp_col_link_frames<NN>(M, z, Rn, pn);                                          \
+      std::memcpy(R, Rn, sizeof Rn); std::memcpy(p, pn, sizeof pn);                  \
+    } break;
+    MP_COL_HOME(1) MP_COL_HOME(2) MP_COL_HOME(3) MP_COL_HOME(4) MP_COL_HOME(5) MP_COL_HOME(6) MP_COL_HOME(7) MP_COL_HOME(8)
+#undef MP_COL_HOME
+    default: delete h; return col_fail("%s: dof outside 1..8", fn);
+  }
+  MpColSpheres& T = h->sph;
+  std::memset(&T, 0, sizeof T);
+  T.S = S; T.P = P;
+  int at = 0, where[MP_COL_MAX_SPHERES];  // caller index -> sorted index
+  for (int k = 0; k <= MP_MAX_DOF; ++k) {   // a stable sort by link
+    T.first[k] = at;
+    for (int s = 0; s < S; ++s) {
+      if (link[s] != k) continue;
+      T.caller[at] = s; T.link[at] = k; T.radius[at] = radius[s];
+      const double* c = centre + 3 * s;
+      if (k == 0) {
+        T.local[at][0] = c[0]; T.local[at][1] = c[1]; T.local[at][2] = c[2];
+      } else {  // R_k(0)^T (c - p_k(0))
+        const double* Rk = R[k - 1];
+        const double dx = c[0] - p[k - 1][0], dy = c[1] - p[k - 1][1], dz = c[2] - p[k - 1][2];
+        for (int a = 0; a < 3; ++a) T.local[at][a] = Rk[a] * dx + Rk[3 + a] * dy + Rk[6 + a] * dz;
+      }
+      where[s] = at++;
+    }
+  }
+  T.first[MP_MAX_DOF + 1] = at;
+  h->pairs.resize((size_t)P);
+  for (int k = 0; k < P; ++k) { h->pairs[(size_t)k].a = where[pairs[2 * k]]; h->pairs[(size_t)k].b = where[pairs[2 * k + 1]]; }
+  *out = h;
+  return MP_OK;
+}
+
+int mp_collision_destroy(mp_collision* h) {
+  if (!h) return MP_OK;
+  if (h->release) h->release(h);
+  delete h;
+  return MP_OK;
+}
+
+}  // extern "C"
+
+int mp_collision_pack_world(const char* fn, int O, const int32_t* kind, const double* params, std::vector<MpColObstacle>* out) {
+  if (O < 0) return col_fail("%s: negative obstacle count", fn);
+  if (O > 0 && (!kind || !params)) return col_fail("%s: null obstacle table", fn);
+  std::vector<MpColObstacle> w((size_t)O);
+  for (int o = 0; o < O; ++o) {
+    const double* p = params + 16 * (size_t)o;
+    int used = 0;
+    if (kind[o] == MP_OBSTACLE_SPHERE) used = 4;
+    else if (kind[o] == MP_OBSTACLE_CAPSULE) used = 7;
+    else if (kind[o] == MP_OBSTACLE_BOX) used = 15;
+    else return col_fail("%s: obstacle %ld: unknown kind", fn, o);
+    for (int k = 0; k < used; ++k)
+      if (!std::isfinite(p[k])) return col_fail("%s: obstacle %ld: non-finite parameter", fn, o);
+    if (kind[o] == MP_OBSTACLE_SPHERE && p[3] < 0.0) return col_fail("%s: obstacle %ld: negative radius", fn, o);
+    if (kind[o] == MP_OBSTACLE_CAPSULE && p[6] < 0.0) return col_fail("%s: obstacle %ld: negative radius", fn, o);
+    if (kind[o] == MP_OBSTACLE_BOX) {
+      for (int k = 12; k < 15; ++k)
+        if (p[k] < 0.0) return col_fail("%s: obstacle %ld: negative half-extent", fn, o);
+      for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+          double dot = 0.0;
+          for (int k = 0; k < 3; ++k) dot += p[3 + 3 * k + a] * p[3 + 3 * k + b];
+          if (std::fabs(dot - (a == b ? 1.0 : 0.0)) > 1e-9) return col_fail("%s: obstacle %ld: box rotation is not orthonormal to 1e-9", fn, o);
+        }
+    }
+    MpColObstacle& ob = w[(size_t)o];
+    std::memset(&ob, 0, sizeof ob);
+    std::memcpy(ob.p, p, (size_t)used * sizeof(double));
+    ob.kind = kind[o];
+  }
+  out->swap(w);
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_collision_cpu_f64(const mp_model* model, const mp_collision* h, const double* q, int64_t rows, double eps_world, double eps_self,
+                         double* dist_world, int32_t* arg_world, double* dist_self, int32_t* arg_self, double* grad_dist_world,
+                         double* grad_dist_self, double* cost, double* grad, int nthreads) {
+  const char* fn = "mp_collision_cpu_f64";
+  if (!model || !h) return col_fail("%s: null model or collision handle", fn);
+  if (model->big) {
+    char msg[192];
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (h->n != model->d.n) return col_fail("%s: the collision handle was made for a model of %ld joints", fn, h->n);
+  if (!(eps_world > 0.0) || !(eps_self > 0.0) || !std::isfinite(eps_world) || !std::isfinite(eps_self))
+    return col_fail("%s: eps_world and eps_self must be positive and finite", fn);
+  if (rows < 0) return col_fail("%s: negative row count", fn);
+  if (rows == 0) return MP_OK;
+  if (!q) return col_fail("%s: null pointer", fn);
+  if (!dist_world && !arg_world && !dist_self && !arg_self && !grad_dist_world && !grad_dist_self && !cost && !grad)
+    return col_fail("%s: at least one output is required", fn);
+  const MpModel<double>& M = model->d;
+  const MpColWorld hdr = {(int)h->world.size(), {0, 0, 0}};
+  const MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*> tb = {&h->sph, h->pairs.data(), &hdr,
+                                                                                                          h->world.data()};
+  const bool want_grad = grad_dist_world || grad_dist_self || grad;
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(rows, 64, nthreads, [&](int64_t lo, int64_t hi) {
+      for (int64_t r = lo; r < hi; ++r) {
+        if (want_grad) mp_collision_cpu_row<N, true>(M, tb, q, eps_world, eps_self, (long)r, dist_world, arg_world, dist_self, arg_self,
+                                                     grad_dist_world, grad_dist_self, cost, grad);
+        else mp_collision_cpu_row<N, false>(M, tb, q, eps_world, eps_self, (long)r, dist_world, arg_world, dist_self, arg_self, nullptr,
+                                            nullptr, cost, nullptr);
+      }
+    });
+  })
   return MP_OK;
 }
 

@@ -1,7 +1,11 @@
 // Handle layouts shared by the translation units that implement the C ABI (mp_capi.cpp, mp_cpu.cpp).
 #pragma once
 #include <cstdint>
+#include <map>
+#include <mutex>
+#include <vector>
 
+#include "mp_collision.h"
 #include "mp_model.h"
 
 struct mp_model {
@@ -13,5 +17,26 @@ struct mp_model {
   double pmap[MP_MAX_DOF * 100];  // n <= MP_MAX_DOF: per link the 10 x 10 inertial-parameter map D (mp_inertial_map, mp_regressor.h)
   uint64_t uid;  // never reused, so a context's device copies cannot alias a destroyed model
 };
+
+// Sphere collision model (mp_collision.h): the host tables, and per context that has used it the device copies.  The device side is
+// mp_capi.cpp's: it registers `release` when it makes the first copy, mp_collision_destroy (mp_cpu.cpp) calls it.
+struct mp_collision {
+  int n = 0;                          // joint count of the model it was made for
+  MpColSpheres sph;
+  std::vector<MpColPair> pairs;
+  std::vector<MpColObstacle> world;   // the _cpu twin's world (and the last one set on any context)
+  struct Resident {
+    int device = -1;
+    void* sph = nullptr;              // MpColSpheres, then the pairs
+    void* world = nullptr;            // MpColWorld, then `cap` obstacles
+    int cap = 0;
+    std::vector<void*> retired;       // outgrown world tables that captured graphs may still read
+  };
+  std::map<uint64_t, Resident> resident;  // by context uid
+  std::mutex mu;
+  void (*release)(mp_collision*) = nullptr;
+};
+// checks an obstacle table and packs it; 0 or an MP_ERR_* code with the message set (mp_cpu.cpp)
+int mp_collision_pack_world(const char* fn, int O, const int32_t* kind, const double* params, std::vector<MpColObstacle>* out);
 
 int mp_set_error(int code, const char* msg);  // thread-local message of mp_last_error (mp_capi.cpp; C++ linkage)

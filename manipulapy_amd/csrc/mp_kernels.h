@@ -174,3 +174,12 @@ hipError_t mpk_traj_id_hard(hipStream_t s, const MpModel<float>* d_model, int n,
 hipError_t mpk_traj_id_tab(hipStream_t s, const MpModel<float>& M, const MpCall<float>& C, bool ftip, const float* start,
                            const float* end, long B, long Nt, const double* tab, float* tau);
 
+// sphere-model collision distances, cost and gradients (csrc/mp_collision.h), float64, 1..MP_MAX_DOF joints; S sizes the dynamic LDS;
+// the tables are device-resident; every output may be null
+struct MpColSpheres;
+struct MpColPair;
+struct MpColWorld;
+hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
+                         const MpColWorld* d_world, const double* q, long rows, double eps_world, double eps_self, double* dist_world,
+                         int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world, double* grad_dist_self, double* cost,
+                         double* grad);

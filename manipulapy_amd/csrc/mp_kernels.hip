@@ -22,6 +22,7 @@
 #include "mp_rollout_vjp.h"
 #include "mp_ilqr.h"
 #include "mp_toppra.h"
+#include "mp_collision.h"
 
 namespace {
 
@@ -410,6 +411,68 @@ __global__ __launch_bounds__(kFkBlock) void k_fk_jac_vjp(const MpModel<double> M
   if (gq != nullptr) {
     mp_poison_if(poison, g);
     mp_wave_store_auto<double, N>(gq, row0, lane, nvalid, g, lds);
+  }
+}
+
+// ------------------------------------------------------- sphere-model collision distances, cost and gradients (float64, mp_collision.h)
+// One lane per row, one wave per block.  q moves as whole lines (MpRowStage) and is the only per-row read; the sphere, pair and obstacle
+// tables are read through constant-address-space pointers, so every lane of the wave visits the same sphere, obstacle and pair in step
+// and the tables cost scalar loads only.  The world centres are parked in dynamic LDS as [sphere][xyz][lane] (24 S bytes a lane, sized
+// by the launcher from the model's S) for the pair loop; the wave's static slice stages q and the row outputs.  The n-wide outputs
+// leave through the wave-cooperative stores, the one- and two-value ones as one coalesced store a lane.
+typedef const __attribute__((address_space(4))) MpColSpheres MpColSpheresConst;
+typedef const __attribute__((address_space(4))) MpColPair MpColPairConst;
+typedef const __attribute__((address_space(4))) MpColWorld MpColWorldConst;
+typedef const __attribute__((address_space(4))) MpColObstacle MpColObstacleConst;
+
+template <int N, bool WANT_GRAD>
+__global__ __launch_bounds__(64) void k_collision(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
+                                                  const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
+                                                  const double* __restrict__ q, long rows, double eps_world, double eps_self,
+                                                  double* __restrict__ dist_world, int* __restrict__ arg_world,
+                                                  double* __restrict__ dist_self, int* __restrict__ arg_self,
+                                                  double* __restrict__ grad_dist_world, double* __restrict__ grad_dist_self,
+                                                  double* __restrict__ cost, double* __restrict__ grad) {
+  using ST = MpRowStage<double, N>;
+  static_assert(ST::SPAN <= MP_WAVE_LDS_BYTES, "one array's 64 rows fit the wave's staging slice");
+  __shared__ __attribute__((aligned(16))) char lds[MP_WAVE_LDS_BYTES];
+  extern __shared__ __attribute__((aligned(16))) double mp_col_park[];
+  const int lane = (int)threadIdx.x;
+  const long row0 = (long)blockIdx.x * 64;
+  if (row0 >= rows) return;
+  const long left = rows - row0;
+  const int nvalid = left < 64 ? (int)left : 64;
+  const long rr = lane < nvalid ? row0 + lane : rows - 1;  // out-of-range lanes recompute the last row, store nothing
+  double a[N];
+  if (nvalid == 64) {
+    mp_u4 bq[ST::NJ];
+    ST::fetch(q, row0, lane, bq);
+    ST::stage(bq, lane, lds);
+    ST::sync();
+    ST::row_in(lds, lane, a);
+    ST::sync();
+  } else {
+    RunIO<double, N>::load(q, rr, a);
+  }
+  MpBad<double> bad;
+  bad.add(a);
+  const MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*> tb = {
+      (MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
+  MpColParkLanes park{mp_col_park + lane};
+  MpColRow<N> o;
+  mp_collision_row<N, WANT_GRAD>(M, tb, a, eps_world, eps_self, park, o);
+  mp_collision_poison<N, WANT_GRAD>(bad.any(), o);
+  if (lane < nvalid) {
+    if (dist_world != nullptr) dist_world[rr] = o.dist_world;
+    if (dist_self != nullptr) dist_self[rr] = o.dist_self;
+    if (cost != nullptr) cost[rr] = o.cost;
+    if (arg_world != nullptr) *reinterpret_cast<int2*>(arg_world + 2 * rr) = make_int2(o.arg_world[0], o.arg_world[1]);
+    if (arg_self != nullptr) *reinterpret_cast<int2*>(arg_self + 2 * rr) = make_int2(o.arg_self[0], o.arg_self[1]);
+  }
+  if constexpr (WANT_GRAD) {
+    if (grad_dist_world != nullptr) mp_wave_store_auto<double, N>(grad_dist_world, row0, lane, nvalid, o.grad_dist_world, lds);
+    if (grad_dist_self != nullptr) mp_wave_store_auto<double, N>(grad_dist_self, row0, lane, nvalid, o.grad_dist_self, lds);
+    if (grad != nullptr) mp_wave_store_auto<double, N>(grad, row0, lane, nvalid, o.grad, lds);
   }
 }
 
@@ -1239,6 +1302,34 @@ hipError_t mpk_fk_jac_vjp(hipStream_t s, const MpModel<double>& M, int frame, co
     if (frame == 0) hipLaunchKernelGGL((k_fk_jac_vjp<N, 0>), dim3(gb), dim3(kFkBlock), 0, s, M, q, gT, gJ, Tout, Jout, gq, rows);
     else hipLaunchKernelGGL((k_fk_jac_vjp<N, 1>), dim3(gb), dim3(kFkBlock), 0, s, M, q, gT, gJ, Tout, Jout, gq, rows);
   })
+  return hipGetLastError();
+}
+
+// dynamic LDS: the park of S world centres for 64 lanes; beyond the default limit the function's own limit is raised first
+hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
+                         const MpColWorld* d_world, const double* q, long rows, double eps_world, double eps_self, double* dist_world,
+                         int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world, double* grad_dist_self, double* cost,
+                         double* grad) {
+  if (rows <= 0) return hipSuccess;
+  if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
+  const unsigned gb = (unsigned)((rows + 63) / 64);
+  const unsigned park = (unsigned)S * 3u * 64u * (unsigned)sizeof(double);
+  const bool want_grad = grad_dist_world != nullptr || grad_dist_self != nullptr || grad != nullptr;
+#define MP_COL_LAUNCH(WG)                                                                                                              \
+  do {                                                                                                                                 \
+    if (park + MP_WAVE_LDS_BYTES > 64u * 1024u) {                                                                                      \
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_collision<N, WG>),                                     \
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)park);                                 \
+      if (e != hipSuccess) return e;                                                                                                   \
+    }                                                                                                                                  \
+    hipLaunchKernelGGL((k_collision<N, WG>), dim3(gb), dim3(64), park, s, M, d_sph, d_pairs, d_world, q, rows, eps_world, eps_self,    \
+                       dist_world, arg_world, dist_self, arg_self, grad_dist_world, grad_dist_self, cost, grad);                       \
+  } while (0)
+  MP_DISPATCH_N(M.n, {
+    if (want_grad) MP_COL_LAUNCH(true);
+    else MP_COL_LAUNCH(false);
+  })
+#undef MP_COL_LAUNCH
   return hipGetLastError();
 }
 

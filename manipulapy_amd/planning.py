@@ -526,6 +526,30 @@ class OptimizedTrajectoryPlanning:
                                                      float(sd_start), float(sd_end), g, Ftip)
         return {k: v[0] for k, v in r.items()}
 
+    def batch_trajectory_clearance(self, positions, collision_model, margin: float = 0.0) -> Dict[str, np.ndarray]:
+        """Clearance of B trajectories (B, N, n) under a collision.SphereCollisionModel (whose world is the one last given to its
+        set_world): {"world_clearance", "self_clearance": (B,) the smallest signed distance along each trajectory (+inf where the
+        model has no obstacle / no pair), "world_step", "self_step": (B,) the first step at which it occurs, "first_violation": (B,)
+        the first step whose world or self clearance is below `margin`, -1 if there is none}.  A trajectory with a non-finite row
+        reports NaN clearances.  One row-parallel launch; the reduction over the steps is done on the host."""
+        pos = np.asarray(positions, dtype=np.float64)
+        n = collision_model.n
+        if pos.ndim != 3 or pos.shape[2] != n:
+            raise ValueError(f"positions must be (B, N, {n}); got {pos.shape}")
+        B, N = pos.shape[:2]
+        want = ("dist_world", "dist_self")
+        r = self._dispatch("planning.collision_spheres", collision_model, np.ascontiguousarray(pos.reshape(B * N, n)), 1.0, 1.0, want)
+        dw, ds = r["dist_world"].reshape(B, N), r["dist_self"].reshape(B, N)
+        out = {}
+        for key, d in (("world", dw), ("self", ds)):
+            bad = np.isnan(d).any(axis=1)
+            step = np.argmin(np.where(np.isnan(d), np.inf, d), axis=1)
+            out[f"{key}_clearance"] = np.where(bad, np.nan, d[np.arange(B), step])
+            out[f"{key}_step"] = step.astype(np.int64)
+        below = (dw < margin) | (ds < margin)
+        out["first_violation"] = np.where(below.any(axis=1), np.argmax(below, axis=1), -1).astype(np.int64)
+        return out
+
     # ------------------------------------------------------------------ legacy dynamics objects (Mlist_per_link=None)
     # The reference's approximation for such objects is not rigid-body dynamics (dynamics/mass_matrix.py:101-132), so there
     # is no compiled model and no kernel for it: the planner walks the rows on the host exactly as the reference's CPU

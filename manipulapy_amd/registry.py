@@ -311,6 +311,10 @@ def _launch_fk_jac_vjp_cpu(model, q, gT=None, gJ=None, frame="space", want_T=Fal
     return _hip.cpu_fk_jac_vjp(model, q, gT, gJ, frame, want_T, want_J, want_gq)
 
 
+def _launch_collision_cpu(cm, q, eps_world, eps_self, want=None):
+    return _hip.cpu_collision(cm.model, cm.handle, q, eps_world, eps_self, want)
+
+
 def _launch_opspace_cpu(model, q, qd, g=None, frame="hybrid", task="full", damping=0.0, want=_hip.OPSPACE_OUTPUTS):
     return _hip.cpu_opspace(model, q, qd, g, frame, task, damping, want)
 
@@ -468,6 +472,12 @@ def _launch_fd_vjp_gpu(model, q, qd, tau, gqdd, g=None, Ftip=None):
     return get_context().fd_vjp_host(model, q, qd, tau, gqdd, g, Ftip)
 
 
+def _launch_collision_gpu(cm, q, eps_world, eps_self, want=None):
+    ctx = get_context()
+    cm.sync_world(ctx)
+    return ctx.collision_host(cm.model, cm.handle, q, eps_world, eps_self, want)
+
+
 def _launch_fk_jac_vjp_gpu(model, q, gT=None, gJ=None, frame="space", want_T=False, want_J=False, want_gq=True):
     return get_context().fk_jac_vjp_host(model, q, gT, gJ, frame, want_T, want_J, want_gq)
 
@@ -600,6 +610,8 @@ def _build_kernel_registry() -> KernelRegistry:
         # time-optimal path parameterisation: path-dynamics coefficients and the reachability sweep (csrc/mp_toppra.h)
         ("planning.time_optimal", "mp_toppra_host_f64 / mp_path_dynamics_f64 + mp_toppra_tm_f64", _launch_time_optimal_gpu,
          _launch_time_optimal_cpu),
+        # sphere-model collision distances, cost and gradients (csrc/mp_collision.h; first argument: a collision.SphereCollisionModel)
+        ("planning.collision_spheres", "mp_collision_host_f64", _launch_collision_gpu, _launch_collision_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):
