@@ -723,6 +723,62 @@ int mp_collision_cpu_f64(const mp_model* model, const mp_collision* h, const dou
                          double* dist_world, int32_t* arg_world, double* dist_self, int32_t* arg_self, double* grad_dist_world,
                          double* grad_dist_self, double* cost, double* grad, int nthreads);
 
+/* ---- continuous collision checking of joint-space edges by conservative advancement (float64, models of 1..8 joints -
+ * MP_ERR_UNSUPPORTED above that; csrc/mp_collision.h).  Is the straight motion from q_a to q_b free under the sphere model above, and
+ * if not, where does it stop?  The answer is a proof over the whole interval, not a sample.
+ * Edge e: q(t) = q_a + t D, D = q_b - q_a, t in [0, 1].  Candidates are those of mp_collision_f64: (sphere on a link >= 1, obstacle)
+ *   with d_so, and the self pairs with d_ab.  The clearance of a candidate is c = d - margin.
+ * Motion bounds, fixed at mp_collision_create (joints are 1-based; link k moves with joints 1..k):
+ *   anchor A_j of a revolute joint = the point of its axis nearest the origin at home, w_j x v_j of its unit screw (w_j, v_j);
+ *   r_j(c), for a sphere centre c on link k and a revolute joint j <= k = the length of the polyline c -> A_i1 -> A_i2 -> ... -> A_j
+ *     through the anchors of the revolute joints i with j < i <= k in descending order (a rotation about axis i keeps the distance
+ *     to a point of that axis, so this bounds the distance from c to axis j in every configuration);
+ *   rho[j][k] = max of r_j(c) over the spheres of link k; 0 if the link has none, if k < j, or if joint j is prismatic.
+ *   mp_collision_motion_bounds(h, rho) copies the table: rho (n, n + 1) row-major, row j - 1, column k = 0..n.
+ * Per edge: a prismatic joint i between them (j < i <= k) lengthens the polyline by at most |q_i|:
+ *     e[j][k] = sum over the prismatic i, j < i <= k, of max(|q_a,i|, |q_b,i|)
+ *   The speed of link kb relative to link ka (0 <= ka < kb <= n) per unit t is at most
+ *     L[ka][kb] = sum_{j = ka+1..kb} |D_j| w_j,   w_j = rho[j][kb] + e[j][kb] (revolute j),  1 (prismatic j)
+ *   A world candidate on link k uses L[0][k]; a pair on links ka < kb uses L[ka][kb] (their distance is frame-invariant: only the
+ *   joints between them count); a pair on one link uses 0.  All three obstacle kinds' sd are 1-Lipschitz, so every candidate
+ *   satisfies d(t') >= d(t) - L (t' - t).
+ * Iteration: t_0 = 0.  At t_i every candidate is evaluated: c_i = min c, tau_i = min c / L over the candidates (L = 0 contributes
+ *   +inf); `steps` counts the evaluations.  c_i <= tol: BLOCKED, t = t_i.  Otherwise t_i + tau_i >= 1: FREE, t = 1 (the last
+ *   interval, end point included, is proven without evaluating it).  Otherwise t_{i+1} = t_i + tau_i.  After max_steps evaluations
+ *   without a decision: UNDECIDED, t = the last t_i - proven: clearance > margin on [0, t).
+ * Per edge (every output may be NULL; the host forms need at least one):
+ *     status (edges) int32     MP_EDGE_FREE 0, MP_EDGE_BLOCKED 1, MP_EDGE_UNDECIDED 2, MP_EDGE_INVALID -1
+ *     t (edges), steps (edges) int32
+ *     clearance (edges)        the smallest min(dist_world, dist_self) over the evaluated configurations; +inf without candidates
+ *     witness (edges,3) int32  (0 world | 1 self, i, j) of that value, in the caller's indices: (0, sphere, obstacle) or (1, a, b).
+ *                              Ties within world or within self resolve as arg_world / arg_self above; a world and a self candidate
+ *                              of equal clearance: world; equal minima across evaluated configurations: the first evaluated.
+ *                              (-1, -1, -1) without candidates
+ *   A non-finite q_a or q_b gives MP_EDGE_INVALID with NaN in t and clearance, 0 steps and a -1 witness; other edges are untouched.
+ *   D = 0 gives one step: FREE or BLOCKED at 0.  No obstacles and no pairs: FREE in one step.
+ *   margin must be finite, tol positive and finite, max_steps in 1..65536: anything else is MP_ERR_INVALID with a message.
+ * mp_collision_edges_f64: d_q_from, d_q_to (edges,n) device rows, 16-byte aligned like every output.  One launch: the edges are
+ *   handed to the resident lanes through a queue (iteration counts differ widely between neighbouring edges), so the order in which
+ *   they are processed is not the order of the arrays; every edge's outputs depend on that edge alone.  max_blocks > 0 caps the grid
+ *   (0: as many one-wave blocks as the device keeps resident, at most ceil(edges / 64)).  Asynchronous, no synchronisation; it
+ *   allocates nothing once the handle is resident on the context and may then be captured into a launch graph (the queue head's reset
+ *   is part of it).  mp_collision_edges_host_f64: host arrays, device memory from the context's pool.
+ *   mp_collision_edges_cpu_f64: the kernel's per-edge code on the host, no context. */
+#define MP_EDGE_FREE 0
+#define MP_EDGE_BLOCKED 1
+#define MP_EDGE_UNDECIDED 2
+#define MP_EDGE_INVALID (-1)
+int mp_collision_motion_bounds(const mp_collision* h, double* rho);
+int mp_collision_edges_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q_from, const double* d_q_to, int64_t edges,
+                           double margin, double tol, int max_steps, int max_blocks, int32_t* d_status, double* d_t, int32_t* d_steps,
+                           double* d_clearance, int32_t* d_witness);
+int mp_collision_edges_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q_from, const double* q_to, int64_t edges,
+                                double margin, double tol, int max_steps, int32_t* status, double* t, int32_t* steps, double* clearance,
+                                int32_t* witness);
+int mp_collision_edges_cpu_f64(const mp_model* model, const mp_collision* h, const double* q_from, const double* q_to, int64_t edges,
+                               double margin, double tol, int max_steps, int32_t* status, double* t, int32_t* steps, double* clearance,
+                               int32_t* witness, int nthreads);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new; the reference is single-device) ------
  * Trajectory batches are sharded over ranks with no exchange during compute; the only collective is
  * the all-gather that reassembles the torque history.  Rank 0 creates the id, the launcher

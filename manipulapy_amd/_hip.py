@@ -179,6 +179,10 @@ SIGNATURES = {
     "mp_collision_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_collision_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _i64, ctypes.c_double, ctypes.c_double, _c_dp, _vp, _c_dp, _vp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "mp_collision_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _i64, ctypes.c_double, ctypes.c_double, _c_dp, _vp, _c_dp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_collision_motion_bounds": (ctypes.c_int, [_vp, _c_dp]),
+    "mp_collision_edges_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
+    "mp_collision_edges_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _c_dp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _c_dp, _vp, _c_dp, _vp]),
+    "mp_collision_edges_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _c_dp, _vp, _c_dp, _vp, ctypes.c_int]),
     "mp_comm_unique_id": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8)]),
     "mp_comm_create": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     "mp_comm_destroy": (ctypes.c_int, [_vp]),
@@ -687,6 +691,21 @@ class HipContext:
     def collision_host(self, model, collision, q, eps_world, eps_self, want=None):
         """The same on host rows through the context's pool: a dict of the outputs named in `want` (default: all of COLLISION_OUTPUTS)."""
         return _collision((self.handle,), self.lib.mp_collision_host_f64, model, collision, q, eps_world, eps_self, want)
+
+    def collision_edges(self, model, collision, d_q_from, d_q_to, edges, margin, tol, max_steps, d_status=None, d_t=None, d_steps=None,
+                        d_clearance=None, d_witness=None, max_blocks: int = 0):
+        """Continuous collision check of joint-space edges on device buffers (float64; csrc/mp_collision.h): d_q_from, d_q_to
+        (edges,n); outputs status / steps (edges) int32, t / clearance (edges), witness (edges,3) int32, each may be None (at least
+        one given).  `max_blocks` > 0 caps the grid of the work queue.  Asynchronous (capturable once the handle has been used or
+        given a world on this context)."""
+        _check(self.lib.mp_collision_edges_f64(self.handle, model.handle, collision.handle, _p(d_q_from), _p(d_q_to), int(edges),
+                                               float(margin), float(tol), int(max_steps), int(max_blocks), _p(d_status), _p(d_t),
+                                               _p(d_steps), _p(d_clearance), _p(d_witness)))
+
+    def collision_edges_host(self, model, collision, q_from, q_to, margin, tol, max_steps, want=None):
+        """The same on host rows through the context's pool: a dict of the outputs named in `want` (default: all of EDGE_OUTPUTS)."""
+        return _collision_edges((self.handle,), self.lib.mp_collision_edges_host_f64, model, collision, q_from, q_to, margin, tol,
+                                max_steps, want)
 
     def collision_set_world(self, collision, kinds, params):
         """Replaces the obstacle table of `collision` on this context's device, behind the launches already on its stream."""
@@ -1376,6 +1395,12 @@ class HipCollision:
         _check(self.lib.mp_collision_set_world(None if ctx is None else ctx.handle, self.handle, O, kd.ctypes.data_as(_vp) if O else None,
                                                _dptr(pm) if O else None))
 
+    def motion_bounds(self) -> np.ndarray:
+        """rho (n, n + 1): row j - 1, column k = the largest distance of a sphere centre of link k from the axis of revolute joint j."""
+        rho = np.zeros((self.n, self.n + 1))
+        _check(self.lib.mp_collision_motion_bounds(self.handle, _dptr(rho)))
+        return rho
+
     def destroy(self) -> None:
         if getattr(self, "handle", None) is not None:
             self.lib.mp_collision_destroy(self.handle)
@@ -1414,6 +1439,40 @@ def _collision(lead, fn, model, collision, q, eps_world, eps_self, want, nthread
 def cpu_collision(model: "HipModel", collision: "HipCollision", q, eps_world, eps_self, want=None, nthreads: int = 0) -> dict:
     """CPU twin of HipContext.collision_host."""
     return _collision((), load_library().mp_collision_cpu_f64, model, collision, q, eps_world, eps_self, want, nthreads)
+
+
+EDGE_OUTPUTS = ("status", "t", "steps", "clearance", "witness")
+EDGE_FREE, EDGE_BLOCKED, EDGE_UNDECIDED, EDGE_INVALID = 0, 1, 2, -1
+
+
+def _collision_edges(lead, fn, model, collision, q_from, q_to, margin, tol, max_steps, want, nthreads=None):
+    want = EDGE_OUTPUTS if want is None else tuple(want)
+    for w in want:
+        if w not in EDGE_OUTPUTS:
+            raise ValueError(f"unknown edge output {w!r}; choose from {EDGE_OUTPUTS}")
+    qa = _as_c(q_from, np.float64, name="q_from")
+    if qa.ndim != 2 or qa.shape[1] != model.n:
+        raise ValueError(f"q_from must be (edges, {model.n}); got {qa.shape}")
+    E = qa.shape[0]
+    qb = _as_c(q_to, np.float64, (E, model.n), "q_to")
+    shapes = {"status": (E,), "t": (E,), "steps": (E,), "clearance": (E,), "witness": (E, 3)}
+    out = {w: np.empty(shapes[w], dtype=np.float64 if w in ("t", "clearance") else np.int32) for w in want}
+    ptrs = []
+    for w in EDGE_OUTPUTS:
+        a = out.get(w)
+        ptrs.append(None if a is None else (_dptr(a) if w in ("t", "clearance") else a.ctypes.data_as(_vp)))
+    args = list(lead) + [model.handle, collision.handle, _dptr(qa), _dptr(qb), E, float(margin), float(tol), int(max_steps)] + ptrs
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return out
+
+
+def cpu_collision_edges(model: "HipModel", collision: "HipCollision", q_from, q_to, margin, tol, max_steps, want=None,
+                        nthreads: int = 0) -> dict:
+    """CPU twin of HipContext.collision_edges_host."""
+    return _collision_edges((), load_library().mp_collision_edges_cpu_f64, model, collision, q_from, q_to, margin, tol, max_steps, want,
+                            nthreads)
 
 
 def _pd_regulation_args(model, theta0, theta_des, Kp, Kd, g, steps):

@@ -14,11 +14,12 @@ import numpy as np
 from . import _hip
 from .registry import execute_registered_kernel
 
-__all__ = ["SphereCollisionModel", "COLLISION_OP"]
+__all__ = ["SphereCollisionModel", "COLLISION_OP", "EDGES_OP"]
 
 # The registry's sorted name list starts with "control.pd_regulation" (the unknown-name message is pinned by a test), so the operation
 # lives in the "planning" family rather than in one of its own that would sort ahead of it.
 COLLISION_OP = "planning.collision_spheres"
+EDGES_OP = "planning.collision_edges"
 
 
 def _hip_model_of(obj) -> _hip.HipModel:
@@ -50,11 +51,12 @@ class SphereCollisionModel:
 
     # ------------------------------------------------------------------ construction from a kinematic chain
     @classmethod
-    def from_points(cls, serial_manipulator_or_dynamics, points, radius, spacing=None, base_radius=None, base_centre=None):
+    def from_points(cls, serial_manipulator_or_dynamics, points, radius, spacing=None, base_radius=None, base_centre=None,
+                    pair_clearance: float = 0.0):
         """Spheres of `radius` strung along the segments points[i] -> points[i + 1], i = 0..n-1 (home positions in the space frame);
         segment i moves with link i + 1.  A segment of length L gets max(1, ceil(L / spacing)) spheres, evenly spread (spacing
         defaults to the radius); a zero-length segment gets one.  `base_radius` adds one sphere on link 0 at `base_centre` (default:
-        the origin).  Default pairs: all pairs on links at least two apart that do not overlap at home."""
+        the origin).  Default pairs: all pairs on links at least two apart whose home clearance exceeds `pair_clearance`."""
         pts = np.asarray(points, dtype=np.float64).reshape(-1, 3)
         n = pts.shape[0] - 1
         radius = float(radius)
@@ -76,20 +78,22 @@ class SphereCollisionModel:
         links, centres, radii = np.array(links, dtype=np.int32), np.array(centres), np.array(radii)
         if len(links) > _hip.MP_COLLISION_MAX_SPHERES:
             raise ValueError(f"{len(links)} spheres, more than {_hip.MP_COLLISION_MAX_SPHERES}: raise the spacing")
-        return cls(serial_manipulator_or_dynamics, links, centres, radii, cls.default_pairs(links, centres, radii))
+        return cls(serial_manipulator_or_dynamics, links, centres, radii, cls.default_pairs(links, centres, radii, pair_clearance))
 
     @staticmethod
-    def default_pairs(links, centres, radii) -> np.ndarray:
-        """All pairs (a < b) on links at least two apart whose spheres do not overlap at the home configuration."""
+    def default_pairs(links, centres, radii, pair_clearance: float = 0.0) -> np.ndarray:
+        """All pairs (a < b) on links at least two apart whose clearance |c_a - c_b| - r_a - r_b at the home configuration exceeds
+        `pair_clearance` (0: the spheres do not overlap).  A pair that sits permanently below margin + tol blocks every edge of
+        `check_edges` at t = 0: give a `pair_clearance` above that sum to leave such pairs out."""
         out = []
         for a in range(len(links)):
             for b in range(a + 1, len(links)):
-                if abs(int(links[a]) - int(links[b])) >= 2 and np.linalg.norm(centres[a] - centres[b]) > radii[a] + radii[b]:
+                if abs(int(links[a]) - int(links[b])) >= 2 and np.linalg.norm(centres[a] - centres[b]) > radii[a] + radii[b] + pair_clearance:
                     out.append((a, b))
         return np.array(out, dtype=np.int32).reshape(-1, 2)
 
     @classmethod
-    def from_urdf(cls, processor, radius, spacing=None, base_radius=None):
+    def from_urdf(cls, processor, radius, spacing=None, base_radius=None, pair_clearance: float = 0.0):
         """From a URDFToSerialManipulator: the points are the home origins of the child links of consecutive actuated joints, then
         the end effector (processor.link_fk(zeros)); the base sphere, if asked for, sits at the root link's origin.  Link k is the
         child link of actuated joint k (a gripper's mimic finger is not modelled: the screw model holds it still)."""
@@ -107,7 +111,7 @@ class SphereCollisionModel:
         names = [j.child for j in processor._tree["actuated"]] + [processor.end_effector_name]
         pts = np.array([home[name][:3, 3] for name in names])
         root = processor._tree["roots"][0]
-        return cls.from_points(processor.serial_manipulator, pts, radius, spacing, base_radius, home[root][:3, 3])
+        return cls.from_points(processor.serial_manipulator, pts, radius, spacing, base_radius, home[root][:3, 3], pair_clearance)
 
     # ------------------------------------------------------------------ the world
     def set_world(self, spheres=None, capsules=None, boxes=None) -> None:
@@ -165,3 +169,22 @@ class SphereCollisionModel:
         """True where the world or the self clearance of a row is below `margin`."""
         r = self._run(q, 1.0, 1.0, ("dist_world", "dist_self"))
         return (r["dist_world"] < margin) | (r["dist_self"] < margin)
+
+    # ------------------------------------------------------------------ edges
+    def motion_bounds(self) -> np.ndarray:
+        """rho (n, n + 1): rho[j - 1, k] = the largest distance a sphere centre of link k can have from the axis of the revolute
+        joint j <= k (prismatic joints between them not counted); 0 for a prismatic j, for k < j and for a link without spheres."""
+        return self.handle.motion_bounds()
+
+    def check_edges(self, q_from, q_to, margin: float = 0.0, tol: float = 1e-3, max_steps: int = 512, want=None) -> dict:
+        """Continuous check of the straight joint-space motions q_from -> q_to ((E, n) or any common leading shape) by conservative
+        advancement: {"status" (0 free, 1 blocked, 2 undecided, -1 invalid), "t", "steps", "clearance", "witness" (.., 3)} or the
+        subset named in `want`.  FREE proves clearance > margin on the whole edge; BLOCKED stops at the first evaluated t whose
+        clearance is <= margin + tol, with [0, t) proven; UNDECIDED (max_steps evaluations) proves [0, t)."""
+        qa, qb = np.asarray(q_from, dtype=np.float64), np.asarray(q_to, dtype=np.float64)
+        if qa.shape != qb.shape or qa.ndim < 1 or qa.shape[-1] != self.n:
+            raise ValueError(f"q_from and q_to must have one shape (..., {self.n}); got {qa.shape} and {qb.shape}")
+        lead = qa.shape[:-1]
+        out = execute_registered_kernel(EDGES_OP, self, np.ascontiguousarray(qa.reshape(-1, self.n)),
+                                        np.ascontiguousarray(qb.reshape(-1, self.n)), margin, tol, max_steps, want)
+        return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}

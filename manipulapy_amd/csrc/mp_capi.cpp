@@ -3353,6 +3353,7 @@ static void collision_release(mp_collision* h) {
     (void)hipSetDevice(R.device);
     if (R.sph) (void)hipFree(R.sph);
     if (R.world) (void)hipFree(R.world);
+    if (R.counter) (void)hipFree(R.counter);
     for (void* p : R.retired) (void)hipFree(p);
   }
   h->resident.clear();
@@ -3385,6 +3386,10 @@ static int collision_resident(const char* fn, mp_ctx* ctx, mp_collision* h, mp_c
   R.device = ctx->device;
   const size_t pb = h->pairs.size() * sizeof(MpColPair);
   HIP_TRY(hipMalloc(&R.sph, sizeof(MpColSpheres) + (pb ? pb : sizeof(MpColPair))));
+  if (hipMalloc(&R.counter, 256) != hipSuccess) {
+    (void)hipFree(R.sph);
+    return set_err(MP_ERR_HIP, "%s: out of device memory", fn);
+  }
   h->release = collision_release;
   mp_collision::Resident& K = h->resident[ctx->uid] = R;
   H2D(K.sph, &h->sph, sizeof(MpColSpheres));
@@ -3420,7 +3425,72 @@ static int collision_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp
   return MP_OK;
 }
 
+static int collision_edges_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_qa,
+                                const double* d_qb, int64_t edges, double margin, double tol, int max_steps, int max_blocks,
+                                int32_t* d_status, double* d_t, int32_t* d_steps, double* d_clear, int32_t* d_witness) {
+  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
+  REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
+  REQUIRE(edges >= 0, "%s: negative edge count", fn);
+  if (edges == 0) return MP_OK;
+  REQUIRE(d_qa && d_qb, "%s: null device pointer", fn);
+  REQUIRE(d_status || d_t || d_steps || d_clear || d_witness, "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_qa) && aligned16(d_qb) && aligned16(d_status) && aligned16(d_t) && aligned16(d_steps) && aligned16(d_clear) &&
+              aligned16(d_witness),
+          "%s: device pointers must be 16-byte aligned", fn);
+  std::lock_guard<std::mutex> hl(h->mu);
+  mp_collision::Resident* R = nullptr;
+  if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
+  PROFILE_SCOPE(ctx, fn);
+  const MpColEdgeParams P = {margin, tol, max_steps, 0};
+  HIP_TRY(mpk_collision_edges(ctx->compute, model->d, h->sph.S, static_cast<const MpColSpheres*>(R->sph),
+                              reinterpret_cast<const MpColPair*>(static_cast<const char*>(R->sph) + sizeof(MpColSpheres)),
+                              static_cast<const MpColWorld*>(R->world), d_qa, d_qb, (long)edges, P, d_status, d_t, d_steps, d_clear,
+                              d_witness, static_cast<unsigned long long*>(R->counter), ctx->compute_units, max_blocks));
+  return MP_OK;
+}
+
 extern "C" {
+
+int mp_collision_edges_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q_from, const double* d_q_to, int64_t edges,
+                           double margin, double tol, int max_steps, int max_blocks, int32_t* d_status, double* d_t, int32_t* d_steps,
+                           double* d_clearance, int32_t* d_witness) {
+  return collision_edges_impl("mp_collision_edges_f64", ctx, model, h, d_q_from, d_q_to, edges, margin, tol, max_steps, max_blocks,
+                              d_status, d_t, d_steps, d_clearance, d_witness);
+}
+
+int mp_collision_edges_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q_from, const double* q_to, int64_t edges,
+                                double margin, double tol, int max_steps, int32_t* status, double* t, int32_t* steps, double* clearance,
+                                int32_t* witness) {
+  const char* fn = "mp_collision_edges_host_f64";
+  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(edges >= 0, "%s: negative edge count", fn);
+  if (edges == 0) return mp_collision_edges_check(fn, margin, tol, max_steps);
+  REQUIRE(q_from && q_to, "%s: null host pointer", fn);
+  const size_t n = (size_t)model->d.n, rb = (size_t)edges * sizeof(double), ib = (size_t)edges * sizeof(int32_t);
+  void* const host[5] = {status, t, steps, clearance, witness};
+  const size_t bytes[5] = {ib, rb, ib, rb, 3 * ib};
+  Scratch sc(ctx);
+  void *da, *db, *dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  if (int rc = sc.get(n * rb, &da)) return rc;
+  if (int rc = sc.get(n * rb, &db)) return rc;
+  for (int k = 0; k < 5; ++k)
+    if (host[k]) if (int rc = sc.get(bytes[k], &dev[k])) return rc;
+  H2D(da, q_from, n * rb);
+  H2D(db, q_to, n * rb);
+  if (int rc = collision_edges_impl(fn, ctx, model, h, (double*)da, (double*)db, edges, margin, tol, max_steps, 0, (int32_t*)dev[0],
+                                    (double*)dev[1], (int32_t*)dev[2], (double*)dev[3], (int32_t*)dev[4]))
+    return rc;
+  for (int k = 0; k < 5; ++k)
+    if (host[k]) D2H(host[k], dev[k], bytes[k]);
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
 
 int mp_collision_set_world(mp_ctx* ctx, mp_collision* h, int O, const int32_t* kind, const double* params) {
   const char* fn = "mp_collision_set_world";

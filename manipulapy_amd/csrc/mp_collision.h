@@ -30,6 +30,10 @@ struct MpColSpheres {
   int link[MP_COL_MAX_SPHERES];
   double radius[MP_COL_MAX_SPHERES];
   double local[MP_COL_MAX_SPHERES][3];
+  // motion bounds of the edge check: rho[j - 1][k] = the largest distance a sphere centre of link k can have from the axis of the
+  // revolute joint j <= k, whatever the configuration (prismatic joints between them not counted: mp_col_edge_begin adds them per
+  // edge); 0 for a prismatic j, for k < j and for a link without spheres
+  double rho[MP_MAX_DOF][MP_MAX_DOF + 1];
 };
 struct MpColPair { int a, b; };
 struct MpColObstacle {
@@ -332,4 +336,204 @@ void mp_collision_cpu_row(const MT& M, const TB& tb, const double* q, double eps
       if (grad) grad[r * N + j] = o.grad[j];
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Continuous collision checking of joint-space edges by conservative advancement (the contract: include/manipula_hip.h,
+// mp_collision_edges_*).  The kernel k_collision_edges (mp_kernels.hip) and the CPU twin instantiate the same templates.
+//
+// Per edge, once (mp_col_edge_begin): the n (n + 1) / 2 speed bounds L[ka][kb], 0 <= ka < kb <= n, from the handle's rho table and the
+// edge's own prismatic travel.  They are per lane but read at wave-uniform link numbers, so they live in a table of their own beside
+// the park (BOUNDS: LDS [entry][lane] in the kernel, a local array in the twin) and never in indexed registers.
+// Per configuration (mp_collision_edge_eval): the FK sweep, the park and the candidate loops of mp_collision_row without cost or
+// gradients.  Every world candidate of one link shares L[0][link], and c -> c / L is monotone, so the link's smallest distance gives its
+// step with one division; a pair's step is compared as c < tau L and divided only where it lowers tau.
+constexpr int MP_COL_EDGE_FREE = 0, MP_COL_EDGE_BLOCKED = 1, MP_COL_EDGE_UNDECIDED = 2, MP_COL_EDGE_INVALID = -1;  // = MP_EDGE_*
+constexpr int MP_COL_EDGE_MAX_STEPS = 65536;
+
+MP_HD constexpr int mp_col_bound_index(int ka, int kb) { return kb * (kb - 1) / 2 + ka; }  // ka < kb
+template <int N>
+struct MpColBoundsLocal {
+  double v[N * (N + 1) / 2];
+  MP_HD void put(int i, double x) { v[i] = x; }
+  MP_HD double get(int i) const { return v[i]; }
+};
+struct MpColBoundsLanes {  // [entry][lane]
+  double* base;            // already offset by the lane
+  MP_HD void put(int i, double x) { base[i * 64] = x; }
+  MP_HD double get(int i) const { return base[i * 64]; }
+};
+
+struct MpColEdgeParams {
+  double margin, tol;
+  int max_steps, pad;
+};
+
+struct MpColEdgeEval {
+  double dist_world, dist_self, tau;  // tau = min (d - margin) / L over the candidates with L > 0, +inf if there is none
+  int arg_world[2], arg_self[2];
+};
+
+template <int N, typename MT, typename TB, typename PARK, typename BOUNDS>
+MP_HD void mp_collision_edge_eval(const MT& M, const TB& tb, const double (&q)[N], double margin, PARK& park, const BOUNDS& L,
+                                  MpColEdgeEval& out) {
+  const double inf = __builtin_huge_val();
+  MpJointState<double, N> js;
+  mp_joint_state<double, N>(M, q, js);
+  const int O = tb.world->O, P = tb.sph->P;
+  double dw = inf, tau = inf;
+  int aws = -1, awo = -1;
+  {
+    const int s1 = tb.sph->first[1];
+    for (int s = 0; s < s1; ++s) park.put(s, tb.sph->local[s][0], tb.sph->local[s][1], tb.sph->local[s][2]);
+  }
+  MpColFrame f;
+  f.base(M);
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    if (i > 0) f.fixed(mp_joint_of(M, i));
+    f.moved(js.c[i], js.s[i], js.d[i]);
+    const int s0 = tb.sph->first[i + 1], s1 = tb.sph->first[i + 2];
+    double dl = inf;  // the link's smallest distance
+    for (int s = s0; s < s1; ++s) {
+      const double lx = tb.sph->local[s][0], ly = tb.sph->local[s][1], lz = tb.sph->local[s][2];
+      const double cx = f.p0 + f.x0 * lx + f.y0 * ly + f.z0 * lz;
+      const double cy = f.p1 + f.x1 * lx + f.y1 * ly + f.z1 * lz;
+      const double cz = f.p2 + f.x2 * lx + f.y2 * ly + f.z2 * lz;
+      park.put(s, cx, cy, cz);
+      const double rs = tb.sph->radius[s];
+      const int who = tb.sph->caller[s];
+      for (int o = 0; o < O; ++o) {
+        double sd, nx, ny, nz;
+        mp_col_signed_distance(tb.obs[o], cx, cy, cz, sd, nx, ny, nz);
+        const double d = sd - rs;
+        if (d < dw) { dw = d; aws = who; awo = o; }
+        dl = d < dl ? d : dl;
+      }
+    }
+    if (s1 > s0 && O > 0) {
+      const double Lw = L.get(mp_col_bound_index(0, i + 1));
+      const double c = dl - margin;
+      if (Lw > 0.0 && c < tau * Lw) tau = c / Lw;
+    }
+  }
+  double ds = inf;
+  int as0 = -1, as1 = -1;
+  for (int k = 0; k < P; ++k) {
+    const int a = tb.pairs[k].a, b = tb.pairs[k].b;
+    double ax, ay, az, bx, by, bz;
+    park.get(a, ax, ay, az);
+    park.get(b, bx, by, bz);
+    const double dx = ax - bx, dy = ay - by, dz = az - bz;
+    const double d = mp_sqrt(dx * dx + dy * dy + dz * dz) - tb.sph->radius[a] - tb.sph->radius[b];
+    if (d < ds) { ds = d; as0 = tb.sph->caller[a]; as1 = tb.sph->caller[b]; }
+    const int la = tb.sph->link[a], lb = tb.sph->link[b];
+    if (la != lb) {  // wave-uniform; a pair on one link keeps its distance
+      const double Lp = L.get(la < lb ? mp_col_bound_index(la, lb) : mp_col_bound_index(lb, la));
+      const double c = d - margin;
+      if (Lp > 0.0 && c < tau * Lp) tau = c / Lp;
+    }
+  }
+  out.dist_world = dw; out.dist_self = ds; out.tau = tau;
+  out.arg_world[0] = aws; out.arg_world[1] = awo; out.arg_self[0] = as0; out.arg_self[1] = as1;
+}
+
+template <int N>
+struct MpColEdgeState {
+  double qa[N], dq[N];
+  double t, clearance;
+  int steps, witness[3];
+  bool bad;  // a non-finite end point: the edge runs as q = 0 (one step) and is reported INVALID
+};
+
+// qa, qb -> the state at t = 0 and the edge's speed bounds.  For link kb the joints are walked from kb down: w_j = rho[j][kb] + the
+// prismatic travel passed so far (revolute), 1 (prismatic); L[j - 1][kb] is the running sum of |dq_j| w_j.
+template <int N, typename MT, typename SP, typename BOUNDS>
+MP_HD void mp_col_edge_begin(const MT& M, const SP& sph, const double (&qa)[N], const double (&qb)[N], MpColEdgeState<N>& S, BOUNDS& L) {
+  MpBad<double> bad;
+  bad.add(qa);
+  bad.add(qb);
+  S.bad = bad.any();
+  double reach[N];  // max(|qa_j|, |qb_j|)
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    S.qa[j] = S.bad ? 0.0 : qa[j];
+    S.dq[j] = S.bad ? 0.0 : qb[j] - qa[j];
+    reach[j] = S.bad ? 0.0 : mp_max(mp_abs(qa[j]), mp_abs(qb[j]));
+  }
+#pragma unroll
+  for (int kb = 1; kb <= N; ++kb) {
+    double e = 0.0, acc = 0.0;
+#pragma unroll
+    for (int j = kb; j >= 1; --j) {
+      const bool rev = mp_joint_of(M, j - 1).rev != 0.0;
+      const double w = rev ? sph->rho[j - 1][kb] + e : 1.0;
+      acc += mp_abs(S.dq[j - 1]) * w;
+      L.put(mp_col_bound_index(j - 1, kb), acc);
+      if (!rev) e += reach[j - 1];
+    }
+  }
+  S.t = 0.0;
+  S.clearance = __builtin_huge_val();
+  S.steps = 0;
+  S.witness[0] = -1; S.witness[1] = -1; S.witness[2] = -1;
+}
+
+// One evaluation at S.t.  Returns 0 while the edge is running, otherwise 1 + its status (FREE / BLOCKED / UNDECIDED; S.t is then the
+// reported t).  An INVALID edge is the caller's to report (S.bad).
+template <int N, typename MT, typename TB, typename PARK, typename BOUNDS>
+MP_HD int mp_col_edge_iterate(const MT& M, const TB& tb, const MpColEdgeParams& P, MpColEdgeState<N>& S, PARK& park, const BOUNDS& L) {
+  double q[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) q[j] = S.qa[j] + S.t * S.dq[j];
+  MpColEdgeEval ev;
+  mp_collision_edge_eval<N>(M, tb, q, P.margin, park, L, ev);
+  S.steps += 1;
+  const bool world = ev.dist_world <= ev.dist_self;  // equal: world first
+  const double d = world ? ev.dist_world : ev.dist_self;
+  if (d < S.clearance) {  // of equal minima the first evaluated stays
+    S.clearance = d;
+    S.witness[0] = world ? 0 : 1;
+    S.witness[1] = world ? ev.arg_world[0] : ev.arg_self[0];
+    S.witness[2] = world ? ev.arg_world[1] : ev.arg_self[1];
+  }
+  if (d - P.margin <= P.tol) return 1 + MP_COL_EDGE_BLOCKED;
+  if (S.t + ev.tau >= 1.0) { S.t = 1.0; return 1 + MP_COL_EDGE_FREE; }
+  if (S.steps >= P.max_steps) return 1 + MP_COL_EDGE_UNDECIDED;
+  S.t += ev.tau;
+  return 0;
+}
+
+// the row an edge reports: INVALID overrides whatever the zero edge gave
+template <int N>
+MP_HD void mp_col_edge_result(const MpColEdgeState<N>& S, int done, int& status, double& t, int& steps, double& clearance, int (&witness)[3]) {
+  status = S.bad ? MP_COL_EDGE_INVALID : done - 1;
+  t = S.t; clearance = S.clearance;
+  mp_poison_if(S.bad, t);
+  mp_poison_if(S.bad, clearance);
+  steps = S.bad ? 0 : S.steps;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) witness[k] = S.bad ? -1 : S.witness[k];
+}
+
+// One edge of the C entry over plain host rows, for the CPU twin.  Any output may be null.
+template <int N, typename MT, typename TB>
+void mp_collision_edge_cpu(const MT& M, const TB& tb, const double* q_from, const double* q_to, const MpColEdgeParams& P, long e,
+                           int* status, double* t, int* steps, double* clearance, int* witness) {
+  double a[N], b[N];
+  for (int j = 0; j < N; ++j) { a[j] = q_from[e * N + j]; b[j] = q_to[e * N + j]; }
+  MpColParkLocal park;
+  MpColBoundsLocal<N> L;
+  MpColEdgeState<N> S;
+  mp_col_edge_begin<N>(M, tb.sph, a, b, S, L);
+  int done;
+  while (!(done = mp_col_edge_iterate<N>(M, tb, P, S, park, L))) {}
+  int st, sp, w[3];
+  double tt, cl;
+  mp_col_edge_result<N>(S, done, st, tt, sp, cl, w);
+  if (status) status[e] = st;
+  if (t) t[e] = tt;
+  if (steps) steps[e] = sp;
+  if (clearance) clearance[e] = cl;
+  if (witness) { witness[3 * e] = w[0]; witness[3 * e + 1] = w[1]; witness[3 * e + 2] = w[2]; }
 }

@@ -1124,6 +1124,29 @@ int mp_collision_create(const mp_model* model, int S, const int32_t* link, const
     }
   }
   T.first[MP_MAX_DOF + 1] = at;
+  // The motion bounds of the edge check.  Anchor A_j of a revolute joint: the point of its axis nearest the origin at home (the axis
+  // is the z line of link frame j).  r_j(c) for a centre c on link k: the polyline c -> A_i1 -> ... -> A_j through the anchors of the
+  // revolute joints j < i <= k in descending order - a rotation about axis i keeps the distance to a point of that axis, so the
+  // polyline's length bounds |c(q) - A_j(q)| at every q that moves no prismatic joint between them.
+  double A[MP_MAX_DOF][3];
+  bool rev[MP_MAX_DOF];
+  for (int j = 0; j < n; ++j) {
+    const double w[3] = {R[j][2], R[j][5], R[j][8]};
+    const double along = w[0] * p[j][0] + w[1] * p[j][1] + w[2] * p[j][2];
+    for (int a = 0; a < 3; ++a) A[j][a] = p[j][a] - along * w[a];
+    rev[j] = M.j[j].rev != 0.0;
+  }
+  for (int s = 0; s < S; ++s) {
+    const int k = link[s];
+    double at3[3] = {centre[3 * s], centre[3 * s + 1], centre[3 * s + 2]}, len = 0.0;
+    for (int j = k; j >= 1; --j) {  // joint j (1-based) walks down from the sphere's link
+      if (!rev[j - 1]) continue;
+      const double dx = at3[0] - A[j - 1][0], dy = at3[1] - A[j - 1][1], dz = at3[2] - A[j - 1][2];
+      len += std::sqrt(dx * dx + dy * dy + dz * dz);
+      for (int a = 0; a < 3; ++a) at3[a] = A[j - 1][a];
+      if (len > T.rho[j - 1][k]) T.rho[j - 1][k] = len;
+    }
+  }
   h->pairs.resize((size_t)P);
   for (int k = 0; k < P; ++k) { h->pairs[(size_t)k].a = where[pairs[2 * k]]; h->pairs[(size_t)k].b = where[pairs[2 * k + 1]]; }
   *out = h;
@@ -1206,6 +1229,55 @@ int mp_collision_cpu_f64(const mp_model* model, const mp_collision* h, const dou
         else mp_collision_cpu_row<N, false>(M, tb, q, eps_world, eps_self, (long)r, dist_world, arg_world, dist_self, arg_self, nullptr,
                                             nullptr, cost, nullptr);
       }
+    });
+  })
+  return MP_OK;
+}
+
+}  // extern "C"
+
+// ---- continuous collision checking of joint-space edges (mp_collision.h, mp_collision_edge_*)
+int mp_collision_edges_check(const char* fn, double margin, double tol, int max_steps) {
+  if (!std::isfinite(margin)) return col_fail("%s: margin must be finite", fn);
+  if (!(tol > 0.0) || !std::isfinite(tol)) return col_fail("%s: tol must be positive and finite", fn);
+  if (max_steps < 1 || max_steps > MP_COL_EDGE_MAX_STEPS) return col_fail("%s: max_steps %ld outside 1..65536", fn, max_steps);
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_collision_motion_bounds(const mp_collision* h, double* rho) {
+  const char* fn = "mp_collision_motion_bounds";
+  if (!h || !rho) return col_fail("%s: null pointer", fn);
+  for (int j = 0; j < h->n; ++j)
+    for (int k = 0; k <= h->n; ++k) rho[j * (h->n + 1) + k] = h->sph.rho[j][k];
+  return MP_OK;
+}
+
+int mp_collision_edges_cpu_f64(const mp_model* model, const mp_collision* h, const double* q_from, const double* q_to, int64_t edges,
+                               double margin, double tol, int max_steps, int32_t* status, double* t, int32_t* steps, double* clearance,
+                               int32_t* witness, int nthreads) {
+  const char* fn = "mp_collision_edges_cpu_f64";
+  if (!model || !h) return col_fail("%s: null model or collision handle", fn);
+  if (model->big) {
+    char msg[192];
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (h->n != model->d.n) return col_fail("%s: the collision handle was made for a model of %ld joints", fn, h->n);
+  if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
+  if (edges < 0) return col_fail("%s: negative edge count", fn);
+  if (edges == 0) return MP_OK;
+  if (!q_from || !q_to) return col_fail("%s: null pointer", fn);
+  if (!status && !t && !steps && !clearance && !witness) return col_fail("%s: at least one output is required", fn);
+  const MpModel<double>& M = model->d;
+  const MpColWorld hdr = {(int)h->world.size(), {0, 0, 0}};
+  const MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*> tb = {&h->sph, h->pairs.data(), &hdr,
+                                                                                                          h->world.data()};
+  const MpColEdgeParams P = {margin, tol, max_steps, 0};
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(edges, 16, nthreads, [&](int64_t lo, int64_t hi) {
+      for (int64_t e = lo; e < hi; ++e) mp_collision_edge_cpu<N>(M, tb, q_from, q_to, P, (long)e, status, t, steps, clearance, witness);
     });
   })
   return MP_OK;

@@ -30,6 +30,7 @@ struct mp_collision {
     void* sph = nullptr;              // MpColSpheres, then the pairs
     void* world = nullptr;            // MpColWorld, then `cap` obstacles
     int cap = 0;
+    void* counter = nullptr;          // the 8-byte work-queue head of k_collision_edges
     std::vector<void*> retired;       // outgrown world tables that captured graphs may still read
   };
   std::map<uint64_t, Resident> resident;  // by context uid
@@ -38,5 +39,7 @@ struct mp_collision {
 };
 // checks an obstacle table and packs it; 0 or an MP_ERR_* code with the message set (mp_cpu.cpp)
 int mp_collision_pack_world(const char* fn, int O, const int32_t* kind, const double* params, std::vector<MpColObstacle>* out);
+// the edge check's parameters: margin finite, tol positive and finite, max_steps in 1..65536; 0 or MP_ERR_INVALID (mp_cpu.cpp)
+int mp_collision_edges_check(const char* fn, double margin, double tol, int max_steps);
 
 int mp_set_error(int code, const char* msg);  // thread-local message of mp_last_error (mp_capi.cpp; C++ linkage)

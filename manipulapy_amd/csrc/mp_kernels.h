@@ -183,3 +183,11 @@ hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, int S, const M
                          const MpColWorld* d_world, const double* q, long rows, double eps_world, double eps_self, double* dist_world,
                          int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world, double* grad_dist_self, double* cost,
                          double* grad);
+// continuous collision checking of joint-space edges (csrc/mp_collision.h): a work queue over `edges`, one evaluated configuration a
+// trip; queue_counter (8 bytes of device memory) is zeroed on the stream first.  The grid is the resident blocks of the device
+// (occupancy x compute_units), at most ceil(edges / 64) and at most max_blocks if that is positive.
+struct MpColEdgeParams;
+hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
+                               const MpColWorld* d_world, const double* q_from, const double* q_to, long edges, const MpColEdgeParams& P,
+                               int* status, double* t, int* steps, double* clearance, int* witness, unsigned long long* queue_counter,
+                               int compute_units, int max_blocks);

@@ -476,6 +476,53 @@ __global__ __launch_bounds__(64) void k_collision(const MpModel<double> M, const
   }
 }
 
+// ------------------------------------------------------- continuous collision checking of joint-space edges (float64, mp_collision.h)
+// One wave per block (the park is [sphere][xyz][lane]), tables through constant-address-space pointers as in k_collision.  Work queue
+// as in k_ik: a lane without an edge takes the next index from the device counter, every trip of the loop evaluates ONE configuration
+// of the lane's own edge, and a finished lane writes its row and fetches another - iteration counts run from 1 to a few hundred between
+// neighbouring edges.  The loop ends because the counter only grows and every edge ends within max_steps.  Dynamic LDS: the park of
+// S centres, then the edge's n (n + 1) / 2 speed bounds [entry][lane] - per lane, but read at wave-uniform link numbers.  Each lane
+// reads and writes only its own column of both, so no barrier is needed.  The 2 n inputs of an edge are plain per-lane loads.
+template <int N>
+__global__ __launch_bounds__(64) void k_collision_edges(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
+                                                        const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
+                                                        const double* __restrict__ q_from, const double* __restrict__ q_to, long edges,
+                                                        const MpColEdgeParams P, int* __restrict__ status, double* __restrict__ t,
+                                                        int* __restrict__ steps, double* __restrict__ clearance,
+                                                        int* __restrict__ witness, unsigned long long* __restrict__ next) {
+  extern __shared__ __attribute__((aligned(16))) double mp_col_edge_lds[];
+  const int lane = (int)threadIdx.x;
+  const MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*> tb = {
+      (MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
+  MpColParkLanes park{mp_col_edge_lds + lane};
+  MpColBoundsLanes L{mp_col_edge_lds + 3 * 64 * tb.sph->S + lane};
+  MpColEdgeState<N> S;
+  bool have = false;
+  long row = 0;
+  for (;;) {
+    if (!have) {
+      row = (long)atomicAdd(next, 1ull);
+      if (row >= edges) break;
+      double a[N], b[N];
+      RunIO<double, N>::load(q_from, row, a);
+      RunIO<double, N>::load(q_to, row, b);
+      mp_col_edge_begin<N>(M, tb.sph, a, b, S, L);
+      have = true;
+    }
+    if (const int done = mp_col_edge_iterate<N>(M, tb, P, S, park, L)) {
+      int st, sp, w[3];
+      double tt, cl;
+      mp_col_edge_result<N>(S, done, st, tt, sp, cl, w);
+      if (status != nullptr) status[row] = st;
+      if (t != nullptr) t[row] = tt;
+      if (steps != nullptr) steps[row] = sp;
+      if (clearance != nullptr) clearance[row] = cl;
+      if (witness != nullptr) { witness[3 * row] = w[0]; witness[3 * row + 1] = w[1]; witness[3 * row + 2] = w[2]; }
+      have = false;
+    }
+  }
+}
+
 // ------------------------------------------------------- operational-space dynamics and torque (float64, mp_opspace.h)
 // One lane per row, one wave per block.  A full wave moves its 64 rows of q / qd as whole lines (MpRowStage, two regions of the
 // wave's slice); the last, partial wave reads per lane and its out-of-range lanes recompute the last row and store nothing.
@@ -1330,6 +1377,35 @@ hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, int S, const M
     else MP_COL_LAUNCH(false);
   })
 #undef MP_COL_LAUNCH
+  return hipGetLastError();
+}
+
+// dynamic LDS: the park and the speed bounds of 64 lanes.  The grid holds the blocks the device keeps resident; the queue feeds them.
+hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
+                               const MpColWorld* d_world, const double* q_from, const double* q_to, long edges, const MpColEdgeParams& P,
+                               int* status, double* t, int* steps, double* clearance, int* witness, unsigned long long* queue_counter,
+                               int compute_units, int max_blocks) {
+  if (edges <= 0) return hipSuccess;
+  if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(queue_counter, 0, sizeof(unsigned long long), s);
+  if (e != hipSuccess) return e;
+  const long want = (edges + 63) / 64;
+  MP_DISPATCH_N(M.n, {
+    const unsigned lds = (unsigned)(3 * S + N * (N + 1) / 2) * 64u * (unsigned)sizeof(double);
+    const void* fn = reinterpret_cast<const void*>(&k_collision_edges<N>);
+    if (lds > 64u * 1024u) {
+      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return e;
+    }
+    int per_cu = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds);
+    if (e != hipSuccess) return e;
+    long grid = (long)(per_cu > 0 ? per_cu : 1) * (compute_units > 0 ? compute_units : 256);
+    grid = grid < want ? grid : want;
+    if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
+    hipLaunchKernelGGL((k_collision_edges<N>), dim3((unsigned)grid), dim3(64), lds, s, M, d_sph, d_pairs, d_world, q_from, q_to, edges, P,
+                       status, t, steps, clearance, witness, queue_counter);
+  })
   return hipGetLastError();
 }
 

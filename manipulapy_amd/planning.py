@@ -550,6 +550,32 @@ class OptimizedTrajectoryPlanning:
         out["first_violation"] = np.where(below.any(axis=1), np.argmax(below, axis=1), -1).astype(np.int64)
         return out
 
+    def batch_validate_path(self, waypoints, collision_model, margin: float = 0.0, tol: float = 1e-3,
+                            max_steps: int = 512) -> Dict[str, np.ndarray]:
+        """Continuous validation of B piecewise-linear joint-space paths (B, W, n) under a collision.SphereCollisionModel: every
+        segment waypoint[i] -> waypoint[i + 1] is checked over its whole length by conservative advancement (SphereCollisionModel.
+        check_edges), all B (W - 1) segments in one launch.  {"free": (B,) every segment proven free (an UNDECIDED or INVALID segment
+        counts as not free), "first_blocked_segment": (B,) the first segment that is not free, -1 if none, "blocked_at": (B,) that
+        segment's index + its t (NaN for a free path or an invalid segment), "segment_status": (B, W - 1), "clearance": (B,) the
+        smallest clearance over the configurations evaluated on the path (NaN with an invalid segment)}."""
+        wp = np.asarray(waypoints, dtype=np.float64)
+        n = collision_model.n
+        if wp.ndim != 3 or wp.shape[2] != n or wp.shape[1] < 2:
+            raise ValueError(f"waypoints must be (B, W >= 2, {n}); got {wp.shape}")
+        B, W = wp.shape[:2]
+        qa = np.ascontiguousarray(wp[:, :-1].reshape(B * (W - 1), n))
+        qb = np.ascontiguousarray(wp[:, 1:].reshape(B * (W - 1), n))
+        r = self._dispatch("planning.collision_edges", collision_model, qa, qb, margin, tol, max_steps, ("status", "t", "clearance"))
+        status, t, clear = (r[k].reshape(B, W - 1) for k in ("status", "t", "clearance"))
+        stopped = status != 0
+        free = ~stopped.any(axis=1)
+        first = np.where(free, -1, np.argmax(stopped, axis=1)).astype(np.int64)
+        at = t[np.arange(B), np.maximum(first, 0)]
+        bad = np.isnan(clear)
+        return {"free": free, "first_blocked_segment": first, "blocked_at": np.where(free, np.nan, first + at),
+                "segment_status": status,
+                "clearance": np.where(bad.any(axis=1), np.nan, np.where(bad, np.inf, clear).min(axis=1))}
+
     # ------------------------------------------------------------------ legacy dynamics objects (Mlist_per_link=None)
     # The reference's approximation for such objects is not rigid-body dynamics (dynamics/mass_matrix.py:101-132), so there
     # is no compiled model and no kernel for it: the planner walks the rows on the host exactly as the reference's CPU

@@ -315,6 +315,10 @@ def _launch_collision_cpu(cm, q, eps_world, eps_self, want=None):
     return _hip.cpu_collision(cm.model, cm.handle, q, eps_world, eps_self, want)
 
 
+def _launch_collision_edges_cpu(cm, q_from, q_to, margin, tol, max_steps, want=None):
+    return _hip.cpu_collision_edges(cm.model, cm.handle, q_from, q_to, margin, tol, max_steps, want)
+
+
 def _launch_opspace_cpu(model, q, qd, g=None, frame="hybrid", task="full", damping=0.0, want=_hip.OPSPACE_OUTPUTS):
     return _hip.cpu_opspace(model, q, qd, g, frame, task, damping, want)
 
@@ -478,6 +482,12 @@ def _launch_collision_gpu(cm, q, eps_world, eps_self, want=None):
     return ctx.collision_host(cm.model, cm.handle, q, eps_world, eps_self, want)
 
 
+def _launch_collision_edges_gpu(cm, q_from, q_to, margin, tol, max_steps, want=None):
+    ctx = get_context()
+    cm.sync_world(ctx)
+    return ctx.collision_edges_host(cm.model, cm.handle, q_from, q_to, margin, tol, max_steps, want)
+
+
 def _launch_fk_jac_vjp_gpu(model, q, gT=None, gJ=None, frame="space", want_T=False, want_J=False, want_gq=True):
     return get_context().fk_jac_vjp_host(model, q, gT, gJ, frame, want_T, want_J, want_gq)
 
@@ -612,6 +622,8 @@ def _build_kernel_registry() -> KernelRegistry:
          _launch_time_optimal_cpu),
         # sphere-model collision distances, cost and gradients (csrc/mp_collision.h; first argument: a collision.SphereCollisionModel)
         ("planning.collision_spheres", "mp_collision_host_f64", _launch_collision_gpu, _launch_collision_cpu),
+        # continuous collision check of joint-space edges by conservative advancement (csrc/mp_collision.h, mp_collision_edge_*)
+        ("planning.collision_edges", "mp_collision_edges_host_f64", _launch_collision_edges_gpu, _launch_collision_edges_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):

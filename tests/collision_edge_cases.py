@@ -1,0 +1,295 @@
+"""Shared by test_collision_edges_host.py and test_gpu_collision_edges.py: the seeded edge cases, a NumPy oracle of the contract of
+include/manipula_hip.h ("continuous collision checking of joint-space edges") and the comparison rule.
+
+The oracle is the iteration of the header on collision_cases.oracle_poses / signed_distance, vectorised over the edges that are still
+running.  It restates the motion bounds from S_list (anchors w x v, the polylines, rho) and uses nothing of the library's edge code.
+It takes a dtype: its float64 run against its np.longdouble run is the yardstick of the rule below.
+
+Cases: the robots of collision_cases.ROBOTS with their spheres and world (world seed 103), margin 0.02, tol 1e-3.  The models are
+built with pair_clearance = PAIR_CLEARANCE so that no pair sits permanently below margin + tol; "chain3" carries
+64 spheres (the kernel's largest park) and a prismatic joint.  Recipe of the edges (make_edge_case): 90 % of q_a come from rows whose oracle clearance
+exceeds margin + 0.03 and 10 % from rows at or below margin (the class of each edge is drawn at random, so it is independent of s);
+q_b = q_a + s u with u a random unit direction, the prismatic components of s u multiplied by 0.2; s cycles through
+(0, 0.1, 0.5, 1.5, 3.0) over consecutive edges, so every wave mixes one-step and hundred-step edges.
+
+Conditions a case must meet (asserted by test_collision_edges_host.py::test_case_conditions; they are conditions, not measurements):
+    at least 25 % of the edges FREE, at least 15 % BLOCKED with t > 0, at least 5 % BLOCKED at 0, both world and self witnesses among
+    the blocked, UNDECIDED at most 1 % at max_steps = 512, the float64 and longdouble oracles agree on status and steps of EVERY
+    edge, no edge has a decision gap below GAP.
+The decision gap of an edge is the minimum over its steps of |c_i - tol| and, at the steps where c_i > tol (the only ones where the
+comparison is made), |t_i + tau_i - 1|.
+
+The rule (twin against oracle, kernel against twin and oracle):
+    status, steps and witness equal the oracle's on every edge whose gap is >= GAP; at most 0.5 % of the edges may be excused and the
+    oracle's own count is 0;
+    max |t - t_oracle| <= T_BOUND and max |clearance - clearance_oracle| <= CLEARANCE_BOUND over the edges that are not excused
+    (+inf compares by equality), each 100 x the oracle's measured float64-against-longdouble difference of that quantity, the worst
+    robot's.  test_measured_figures asserts that the constants are not below what it measures.
+Measured on these cases (4099 edges a robot, seed 7 each - the first seed tried; float64 oracle, identical status and steps in longdouble):
+    robot    free    blocked t>0   at 0    undecided   steps mean / p95 / max   smallest gap   max |dt|   max |dclearance|
+    ur5      70.4 %  19.8 %        9.8 %   0           10.6 / 40 / 213          4.0e-7         2.6e-15    8.3e-16
+    panda    72.6 %  17.2 %        9.8 %   0.37 %      48.5 / 191 / 512         1.1e-8         2.7e-15    7.4e-16
+    xarm6    70.9 %  19.3 %        9.8 %   0           12.3 / 46 / 223          8.8e-8         2.3e-15    4.3e-16
+    chain3   73.4 %  16.7 %        9.8 %   0            6.3 / 23 / 129          5.6e-7         1.1e-15    1.0e-15
+The CPU twin sits at most 1.7e-14 (t, panda) and 2.7e-15 (clearance, chain3) from the float64 oracle, 6 % and 2.4 % of the bounds.
+"""
+import functools
+
+import numpy as np
+
+import collision_cases as cc
+from manipulapy_amd import _hip, robots
+from manipulapy_amd.collision import SphereCollisionModel
+from manipulapy_amd.urdf import URDFToSerialManipulator
+
+MARGIN, TOL, MAX_STEPS = 0.02, 1e-3, 512
+PAIR_CLEARANCE = 0.06
+GAP = 1e-9
+EDGES = 4099
+S_CYCLE = (0.0, 0.1, 0.5, 1.5, 3.0)
+FREE, BLOCKED, UNDECIDED, INVALID = 0, 1, 2, -1
+EDGE_KEYS = ("status", "t", "steps", "clearance", "witness")
+
+# the oracle's float64-against-longdouble differences, the worst robot's (absolute: t lies in [0, 1], clearances are metres)
+MEASURED_T = 2.7e-15
+MEASURED_CLEARANCE = 1.1e-15
+T_BOUND = 100 * MEASURED_T
+CLEARANCE_BOUND = 100 * MEASURED_CLEARANCE
+
+
+# ------------------------------------------------------------------------------------------------ cases
+def _chain3():
+    """collision_cases' chain3 (64 spheres, the base sphere included), its pairs chosen with PAIR_CLEARANCE"""
+    from test_random_robots import random_robot
+
+    tb = random_robot(np.random.default_rng(11), 3, ("general", "prismatic", "general"))
+    lim = np.asarray(tb.joint_limits, dtype=np.float64).copy()
+    lim[1] = [-0.4, 0.4]
+    model = _hip.HipModel(tb.S, tb.Mcom, tb.G, tb.M_ee, lim)
+    pts = np.array([tb.Mcom[i][:3, 3] for i in range(3)] + [tb.M_ee[:3, 3]])
+    cm = SphereCollisionModel.from_points(model, pts, cc.RADIUS, base_radius=cc.BASE_RADIUS, pair_clearance=PAIR_CLEARANCE)
+    assert len(cm.links) == 64
+    return cm, np.asarray(tb.S, dtype=np.float64), lim
+
+
+@functools.lru_cache(maxsize=None)
+def make_model(name):
+    """(SphereCollisionModel with the world of collision_cases.make_case set, S_list, joint limits)"""
+    if name == "chain3":
+        cm, S_list, lim = _chain3()
+    else:
+        proc = URDFToSerialManipulator(robots.robot_urdf(name))
+        cm = SphereCollisionModel.from_urdf(proc, cc.RADIUS, base_radius=cc.BASE_RADIUS, pair_clearance=PAIR_CLEARANCE)
+        S_list = np.asarray(proc.tables["S_list"], dtype=np.float64)
+        lim = np.asarray(proc.tables["joint_limits"], dtype=np.float64)
+    sp, ca, bx = cc.make_world(103)
+    cm.set_world(spheres=sp, capsules=ca, boxes=bx)
+    return cm, S_list, lim
+
+
+SEEDS = {"ur5": 7, "panda": 7, "xarm6": 7, "chain3": 7}
+
+
+@functools.lru_cache(maxsize=None)
+def make_edge_case(name, edges=EDGES):
+    """{"cm", "S_list", "qa", "qb" (edges, n)} by the recipe of the module's docstring."""
+    cm, S_list, lim = make_model(name)
+    n = lim.shape[0]
+    rng = np.random.default_rng(SEEDS[name])
+    lo, hi = np.clip(lim[:, 0], -3, 3), np.clip(lim[:, 1], -3, 3)
+    low = rng.random(edges) < 0.1  # q_a at or below the margin
+    model = Model(S_list, cm)
+    free_rows, low_rows = [], []
+    need_free, need_low = int((~low).sum()), int(low.sum())
+    while sum(map(len, free_rows)) < need_free or sum(map(len, low_rows)) < need_low:
+        pool = rng.uniform(lo, hi, (4096, n))
+        ev = model.evaluate(pool, None, MARGIN, np.float64)
+        c = np.minimum(ev["dist_world"], ev["dist_self"])
+        free_rows.append(pool[c > MARGIN + 0.03])
+        low_rows.append(pool[c <= MARGIN])
+    qa = np.empty((edges, n))
+    qa[~low] = np.concatenate(free_rows)[:need_free]
+    qa[low] = np.concatenate(low_rows)[:need_low]
+    u = rng.normal(size=(edges, n))
+    u /= np.linalg.norm(u, axis=1, keepdims=True)
+    step = np.asarray(S_CYCLE)[np.arange(edges) % len(S_CYCLE)][:, None] * u
+    step[:, ~model.revolute] *= 0.2
+    return {"cm": cm, "S_list": S_list, "qa": np.ascontiguousarray(qa), "qb": np.ascontiguousarray(qa + step), "name": name}
+
+
+# ------------------------------------------------------------------------------------------------ oracle
+def oracle_rho(S_list, links, centres):
+    """rho (n, n + 1) of the header, restated from the screws: anchors w x v, polylines through the revolute anchors."""
+    S_list = np.asarray(S_list, dtype=np.float64)
+    n = S_list.shape[1]
+    w, v = S_list[:3].T, S_list[3:].T
+    revolute = np.linalg.norm(w, axis=1) > 0
+    rho = np.zeros((n, n + 1))
+    for s in range(len(links)):
+        k = int(links[s])
+        at, length = np.asarray(centres[s], dtype=np.float64), 0.0
+        for j in range(k, 0, -1):
+            if not revolute[j - 1]:
+                continue
+            unit = w[j - 1] / np.linalg.norm(w[j - 1])
+            anchor = np.cross(unit, v[j - 1] / np.linalg.norm(w[j - 1]))
+            length += np.linalg.norm(at - anchor)
+            at = anchor
+            rho[j - 1, k] = max(rho[j - 1, k], length)
+    return rho
+
+
+class Model:
+    """The tables of one sphere model in the order the header documents for ties, and the oracle built on them."""
+
+    def __init__(self, S_list, cm):
+        self.S_list = np.asarray(S_list, dtype=np.float64)
+        self.n = self.S_list.shape[1]
+        self.revolute = np.linalg.norm(self.S_list[:3], axis=0) > 0
+        self.links = np.asarray(cm.links, dtype=np.int64)
+        self.centres, self.radii = np.asarray(cm.centres), np.asarray(cm.radii)
+        self.pairs = np.asarray(cm.pairs, dtype=np.int64).reshape(-1, 2)
+        self.kinds, self.params = np.asarray(cm.kinds), np.asarray(cm.params)
+        self.rho = oracle_rho(self.S_list, self.links, self.centres)
+        # world candidates: (link, caller index), then obstacle order
+        self.moving = np.array(sorted((s for s in range(len(self.links)) if self.links[s] > 0), key=lambda s: (self.links[s], s)),
+                               dtype=np.int64)
+
+    def bounds(self, qa, qb, dt):
+        """L (edges, n + 1, n + 1): L[:, ka, kb] for ka < kb, 0 elsewhere."""
+        qa, qb = qa.astype(dt), qb.astype(dt)
+        E, n = qa.shape
+        D = np.abs(qb - qa)
+        reach = np.maximum(np.abs(qa), np.abs(qb))
+        rho = self.rho.astype(dt)
+        L = np.zeros((E, n + 1, n + 1), dtype=dt)
+        for kb in range(1, n + 1):
+            for ka in range(kb):
+                for j in range(ka + 1, kb + 1):
+                    if self.revolute[j - 1]:
+                        e = sum((reach[:, i - 1] for i in range(j + 1, kb + 1) if not self.revolute[i - 1]), np.zeros(E, dtype=dt))
+                        L[:, ka, kb] += D[:, j - 1] * (rho[j - 1, kb] + e)
+                    else:
+                        L[:, ka, kb] += D[:, j - 1]
+        return L
+
+    def evaluate(self, q, L, margin, dt):
+        """dist_world, arg_world, dist_self, arg_self of every row and, with L, tau = min c / L over the candidates with L > 0."""
+        q = np.asarray(q).astype(dt)
+        rows = q.shape[0]
+        R, p = cc.oracle_poses(self.S_list, q, dt)
+        ctr = np.einsum("srab,sb->sra", R[self.links], self.centres.astype(dt)) + p[self.links]  # (S, rows, 3)
+        inf = dt(np.inf)
+        out = {}
+        tau = np.full(rows, inf, dtype=dt)
+        m, O = self.moving, len(self.kinds)
+        if len(m) and O:
+            pts = ctr[m].reshape(-1, 3)
+            d = np.stack([cc.signed_distance(int(self.kinds[o]), self.params[o], pts, dt)[0].reshape(len(m), rows) for o in range(O)], axis=2)
+            d = (d - self.radii[m].astype(dt)[:, None, None]).transpose(1, 0, 2).reshape(rows, len(m) * O)  # sphere-major, obstacle-minor
+            k = np.argmin(d, axis=1)  # the first of equal minima
+            out["dist_world"] = d[np.arange(rows), k]
+            out["arg_world"] = np.column_stack([m[k // O], k % O]).astype(np.int32)
+            if L is not None:
+                Lc = np.repeat(L[:, 0, self.links[m]], O, axis=1)
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    tau = np.minimum(tau, np.where(Lc > 0, (d - dt(margin)) / np.where(Lc > 0, Lc, 1), inf).min(axis=1))
+        else:
+            out["dist_world"], out["arg_world"] = np.full(rows, inf, dtype=dt), np.full((rows, 2), -1, dtype=np.int32)
+        if len(self.pairs):
+            a, b = self.pairs[:, 0], self.pairs[:, 1]
+            diff = ctr[a] - ctr[b]
+            d = (np.sqrt((diff * diff).sum(axis=2)) - self.radii[a].astype(dt)[:, None] - self.radii[b].astype(dt)[:, None]).T
+            k = np.argmin(d, axis=1)
+            out["dist_self"] = d[np.arange(rows), k]
+            out["arg_self"] = self.pairs[k].astype(np.int32)
+            if L is not None:
+                la, lb = self.links[a], self.links[b]
+                Lc = L[:, np.minimum(la, lb), np.maximum(la, lb)]  # 0 on the diagonal: a pair on one link
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    tau = np.minimum(tau, np.where(Lc > 0, (d - dt(margin)) / np.where(Lc > 0, Lc, 1), inf).min(axis=1))
+        else:
+            out["dist_self"], out["arg_self"] = np.full(rows, inf, dtype=dt), np.full((rows, 2), -1, dtype=np.int32)
+        out["tau"] = tau
+        return out
+
+    def edges(self, qa, qb, margin=MARGIN, tol=TOL, max_steps=MAX_STEPS, dt=np.float64):
+        """status, t, steps, clearance, witness and gap of every (finite) edge: the iteration of the header."""
+        qa, qb = np.asarray(qa).astype(dt), np.asarray(qb).astype(dt)
+        E = qa.shape[0]
+        L = self.bounds(qa, qb, dt)
+        inf = dt(np.inf)
+        status = np.full(E, -2, dtype=np.int32)
+        t = np.zeros(E, dtype=dt)
+        steps = np.zeros(E, dtype=np.int32)
+        clearance = np.full(E, inf, dtype=dt)
+        witness = np.full((E, 3), -1, dtype=np.int32)
+        gap = np.full(E, inf, dtype=dt)
+        run = np.arange(E)
+        while len(run):
+            ev = self.evaluate(qa[run] + t[run][:, None] * (qb[run] - qa[run]), L[run], margin, dt)
+            steps[run] += 1
+            world = ev["dist_world"] <= ev["dist_self"]
+            d = np.where(world, ev["dist_world"], ev["dist_self"])
+            better = d < clearance[run]
+            idx = run[better]
+            clearance[idx] = d[better]
+            witness[idx, 0] = np.where(world, 0, 1)[better]
+            witness[idx, 1:] = np.where(world[:, None], ev["arg_world"], ev["arg_self"])[better]
+            c = d - dt(margin)
+            blocked = c <= dt(tol)
+            reach = t[run] + ev["tau"]
+            free = ~blocked & (reach >= 1)
+            out = ~blocked & ~free & (steps[run] >= max_steps)
+            with np.errstate(invalid="ignore"):
+                g = np.minimum(np.abs(c - dt(tol)), np.where(blocked, inf, np.abs(reach - 1)))
+            gap[run] = np.minimum(gap[run], g)
+            status[run[blocked]] = BLOCKED
+            status[run[free]] = FREE
+            t[run[free]] = 1
+            status[run[out]] = UNDECIDED
+            go = ~blocked & ~free & ~out
+            t[run[go]] = reach[go]
+            run = run[go]
+        return {"status": status, "t": t, "steps": steps, "clearance": clearance, "witness": witness, "gap": gap}
+
+
+@functools.lru_cache(maxsize=None)
+def model_of(name):
+    cm, S_list, _ = make_model(name)
+    return Model(S_list, cm)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_of(name, max_steps=MAX_STEPS, long=False):
+    """The oracle on the whole case (computed once and shared: treat as read-only)."""
+    case = make_edge_case(name)
+    return model_of(name).edges(case["qa"], case["qb"], MARGIN, TOL, max_steps, np.longdouble if long else np.float64)
+
+
+# ------------------------------------------------------------------------------------------------ the rule
+def check_against_oracle(got, ref, label, show=True):
+    """The rule of this module on every output present in `got` (ref: the oracle over the same edges).  Returns the figures."""
+    firm = ref["gap"] >= GAP
+    excused = int((~firm).sum())
+    E = len(firm)
+    if show:
+        print(f"{label}: {excused} of {E} edges excused (gap below {GAP:g})")
+    assert excused <= 0.005 * E, f"{label}: {excused} edges too close to call"
+    for k in ("status", "steps", "witness"):
+        if k in got:
+            same = got[k][firm] == ref[k][firm]
+            assert np.all(same), f"{label}: {k} differs from the oracle on {int((~same).sum())} entries"
+    figures = {}
+    for k, bound in (("t", T_BOUND), ("clearance", CLEARANCE_BOUND)):
+        if k not in got:
+            continue
+        x, r = got[k][firm], ref[k][firm].astype(np.float64)
+        fin = np.isfinite(r)
+        assert np.array_equal(x[~fin], r[~fin]), f"{label}: infinite {k} entries differ"
+        err = float(np.abs(x[fin] - r[fin]).max()) if fin.any() else 0.0
+        figures[k] = err
+        if show:
+            print(f"{label}: {k}: max difference {err:.3g} (bound {bound:.3g})")
+        assert err <= bound, f"{label}: {k} misses the bound {bound:.3g}: {err:.3g}"
+    return figures
