@@ -118,7 +118,9 @@ int mp_memcpy_d2h(mp_ctx* ctx, void* h_dst, const void* d_src, size_t bytes); /*
 int mp_memset(mp_ctx* ctx, void* d_dst, int value, size_t bytes);
 /* page-locked host buffers (the reference's pinned staging, cuda_kernels/memory.py:12-50, handed to the caller): the
  * *_host_* entry points below accept any host pointer; on buffers from mp_host_alloc the upload, the kernels and
- * the download of a large call overlap chunk by chunk (pageable memory is staged by the runtime and serialises). */
+ * the download of a large call overlap chunk by chunk (pageable memory is staged by the runtime and serialises).
+ * When a *_host_* entry point returns an error, no transfer to or from the caller's arrays is pending any more, and
+ * the contents of its output arrays are unspecified. */
 int mp_host_alloc(mp_ctx* ctx, size_t bytes, void** h_ptr);
 int mp_host_free(mp_ctx* ctx, void* h_ptr); /* ctx may be NULL: the buffer outlives the context that allocated it */
 

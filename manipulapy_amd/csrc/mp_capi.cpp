@@ -253,7 +253,7 @@ void make_call(const mp_model* m, const double* g, const double* Ftip, MpCall<T>
   mp_call_cast(cd, c);
 }
 
-// RAII device scratch from the pool for the *_host wrappers
+// RAII device scratch from the pool: the *_host entry points take theirs through HostCall, the self-checks directly
 struct Scratch {
   mp_ctx* ctx;
   std::vector<void*> bufs;
@@ -791,6 +791,148 @@ static int host_pipeline(mp_ctx* ctx, int64_t rows, int64_t chunk, Up up, Run ru
 #define UP(dst, src, bytes) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->copy))
 #define DOWN(dst, src, bytes) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->copy_out))
 
+// Device staging of one *_host call.  The entry point declares every host array once and gets its device pointer back; an absent
+// (null) host array maps to a null device pointer and moves nothing.  A failed allocation or copy is kept in `rc`: what follows it
+// becomes a no-op, so call sites check nothing, and run() / run_rows() / finish() - an entry's only exit - return the first error.
+// On every path, failure included, they drain the compute stream (the pipeline: its three streams), so no transfer to or from the
+// caller's arrays is pending when the entry returns.
+//   in / out / inout     whole arrays: uploaded at once / downloaded by finish(), in the order they were declared
+//   in_tm / out_tm       the same for batch-major host arrays whose device copy is time-major: through the stage block (stage(),
+//                        asked for once at the largest size that passes through it) and mp_transpose_rows, in stream order
+//   in_rows / out_rows   arrays of `rows` rows, moved by run_rows()
+//   work                 scratch only (0 bytes still yields a valid 16-byte block)
+// The blocks come from the pool and go back to it with the object; the pool's reuse is ordered on the compute stream (Scratch).
+struct HostCall {
+  mp_ctx* ctx;
+  int rc = MP_OK;
+  explicit HostCall(mp_ctx* c, int64_t rows = 0) : ctx(c), sc(c), nrows(rows) {}
+
+  template <class T = void> T* work(size_t bytes) {
+    void* p = nullptr;
+    if (rc == MP_OK) rc = sc.get(bytes, &p);
+    return static_cast<T*>(p);
+  }
+  template <class T> const T* in(const T* host, size_t bytes) {
+    T* d = host ? work<T>(bytes) : nullptr;
+    if (d) upload(d, host, bytes);
+    return d;
+  }
+  template <class T> T* out(T* host, size_t bytes) {
+    T* d = host ? work<T>(bytes) : nullptr;
+    if (d) outs.push_back({host, d, bytes, 0, 0});
+    return d;
+  }
+  template <class T> T* inout(T* host, size_t bytes) {
+    T* d = out(host, bytes);
+    if (d) upload(d, host, bytes);
+    return d;
+  }
+  void stage(size_t bytes) { staged = work(bytes); }
+  // host (outer, inner, row) -> device (inner, outer, row)
+  template <class T> const T* in_tm(const T* host, int64_t outer, int64_t inner, size_t row) {
+    T* d = host ? work<T>((size_t)(outer * inner) * row) : nullptr;
+    if (d) upload_tm(d, host, outer, inner, row);
+    return d;
+  }
+  // device (outer, inner, row) -> host (inner, outer, row)
+  template <class T> T* out_tm(T* host, int64_t outer, int64_t inner, size_t row) {
+    T* d = host ? work<T>((size_t)(outer * inner) * row) : nullptr;
+    if (d) outs.push_back({host, d, row, outer, inner});
+    return d;
+  }
+  template <class T> const T* in_rows(const T* host, size_t row_bytes) {
+    T* d = host ? work<T>((size_t)nrows * row_bytes) : nullptr;
+    if (d) by_row.push_back({(char*)const_cast<T*>(host), (char*)d, row_bytes, false});
+    return d;
+  }
+  template <class T> T* out_rows(T* host, size_t row_bytes) {
+    T* d = host ? work<T>((size_t)nrows * row_bytes) : nullptr;
+    if (d) by_row.push_back({(char*)host, (char*)d, row_bytes, true});
+    return d;
+  }
+
+  // the transfers themselves, on the compute stream (an entry that moves its arrays piecewise calls them directly)
+  void upload(void* dst, const void* src, size_t bytes) {
+    step([&]() -> int { H2D(dst, src, bytes); return MP_OK; });
+  }
+  void download(void* dst, const void* src, size_t bytes) {
+    step([&]() -> int { D2H(dst, src, bytes); return MP_OK; });
+  }
+  void upload_tm(void* dst, const void* src, int64_t outer, int64_t inner, size_t row) {
+    upload(staged, src, (size_t)(outer * inner) * row);
+    step([&] { return mp_transpose_rows(ctx, staged, outer, inner, (int64_t)row, dst); });
+  }
+  void download_tm(void* dst, const void* src, int64_t outer, int64_t inner, size_t row) {
+    step([&] { return mp_transpose_rows(ctx, src, outer, inner, (int64_t)row, staged); });
+    download(dst, staged, (size_t)(outer * inner) * row);
+  }
+
+  template <class F> void step(F f) {
+    if (rc == MP_OK) rc = f();
+  }
+  // The parked float64 passes run before the downloads read their torques.  Only the float32 inverse-dynamics and fused entries
+  // park one; for every other entry CTX_ENTER flushed on the way in and its launches park nothing, so the call finds no busy slot
+  // and returns.
+  int finish() {
+    step([&] { return hard_flush(ctx); });
+    for (const Out& o : outs) {
+      if (o.outer) download_tm(o.host, o.dev, o.outer, o.inner, o.bytes);
+      else download(o.host, o.dev, o.bytes);
+    }
+    const hipError_t he = hipStreamSynchronize(ctx->compute);
+    if (rc == MP_OK && he != hipSuccess) rc = hip_err(he, "hipStreamSynchronize(ctx->compute)");
+    return rc;
+  }
+  template <class F> int run(F launch) {
+    step(launch);
+    return finish();
+  }
+  // launch(r0, nr) works on rows [r0, r0 + nr) of the row-declared arrays (device pointers of row r0: at()).
+  // Page-locked arrays throughout and at least `min_rows` rows: the rows are cut into chunks of `chunk` and the three stages
+  // overlap - upload of chunk k+1 (copy stream), kernels of chunk k (compute stream), download of chunk k-1 (copy-out stream);
+  // events order the stages of one chunk (host_pipeline).  PCIe is full duplex, so the call costs about its larger direction.
+  // Pageable buffers are staged by the runtime on the calling thread, which serialises the stages anyway (measured: chunking then
+  // costs 8 %), so only page-locked calls are chunked; every other call is one upload, one launch, one download.
+  template <class F> int run_rows(int64_t chunk, int64_t min_rows, F launch) {
+    bool pipelined = rc == MP_OK && nrows >= min_rows;
+    for (const Rows& a : by_row) pipelined = pipelined && is_pinned_host(a.host);
+    if (!pipelined) {
+      for (const Rows& a : by_row) {
+        if (a.down) outs.push_back({a.host, a.dev, (size_t)nrows * a.row, 0, 0});
+        else upload(a.dev, a.host, (size_t)nrows * a.row);
+      }
+      return run([&] { return launch((int64_t)0, nrows); });
+    }
+    return rc = host_pipeline(
+               ctx, nrows, chunk,
+               [&](int64_t r0, int64_t nr) -> int {
+                 for (const Rows& a : by_row)
+                   if (!a.down) UP(a.dev + r0 * a.row, a.host + r0 * a.row, nr * a.row);
+                 return MP_OK;
+               },
+               [&](int64_t r0, int64_t nr) -> int {
+                 if (int e = launch(r0, nr)) return e;
+                 return hard_flush(ctx);  // (as in finish(): the chunk's download follows)
+               },
+               [&](int64_t r0, int64_t nr) -> int {
+                 for (const Rows& a : by_row)
+                   if (a.down) DOWN(a.host + r0 * a.row, a.dev + r0 * a.row, nr * a.row);
+                 return MP_OK;
+               });
+  }
+
+ private:
+  struct Out { void *host, *dev; size_t bytes; int64_t outer, inner; };  // outer != 0: out_tm, `bytes` is its row
+  struct Rows { char *host, *dev; size_t row; bool down; };
+  Scratch sc;
+  int64_t nrows;
+  void* staged = nullptr;
+  std::vector<Out> outs;
+  std::vector<Rows> by_row;
+};
+// `p` advanced by `elems` elements; null stays null (an array that was not asked for)
+template <class T> T* at(T* p, int64_t elems) { return p ? p + elems : nullptr; }
+
 template <typename T>
 static int id_host_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const T* q, const T* qd, const T* qdd,
                         int64_t rows, const double* g, const double* Ftip, T* tau) {
@@ -799,55 +941,14 @@ static int id_host_impl(const char* fn, mp_ctx* ctx, const mp_model* model, cons
   REQUIRE(rows >= 0, "%s: negative row count", fn);
   if (rows == 0) return MP_OK;
   REQUIRE(q && qd && qdd && tau, "%s: null host pointer", fn);
-  const size_t row_b = (size_t)model->d.n * sizeof(T), bytes = (size_t)rows * row_b;
-  Scratch sc(ctx);
-  void *dq, *dqd, *dqdd, *dt;
-  if (int rc = sc.get(bytes, &dq)) return rc;
-  if (int rc = sc.get(bytes, &dqd)) return rc;
-  if (int rc = sc.get(bytes, &dqdd)) return rc;
-  if (int rc = sc.get(bytes, &dt)) return rc;
-  // Chunked three-stage pipeline: upload of chunk k+1 (copy stream), kernel of chunk k (compute stream) and download
-  // of chunk k-1 (copy-out stream) overlap; events order the stages of one chunk.  PCIe is full duplex, so with
-  // page-locked buffers the call costs about the upload alone.
-  // Pageable buffers are staged by the runtime on the calling thread, which serialises the stages anyway (measured:
-  // chunking then costs 8 %), so only page-locked calls are chunked.
-  const int64_t chunk = host_chunk_rows();
-  const bool pinned = is_pinned_host(q) && is_pinned_host(qd) && is_pinned_host(qdd) && is_pinned_host(tau);
-  const int64_t nchunks = pinned ? (rows + chunk - 1) / chunk : 1;
-  if (nchunks < 2) {
-    H2D(dq, q, bytes);
-    H2D(dqd, qd, bytes);
-    H2D(dqdd, qdd, bytes);
-    int rc = id_impl<T>(fn, ctx, model, (T*)dq, (T*)dqd, (T*)dqdd, rows, g, Ftip, (T*)dt);
-    if (!rc) rc = hard_flush(ctx);  // the download below reads the torques: a parked float64 pass runs now
-    if (rc) {
-      (void)hipStreamSynchronize(ctx->compute);
-      return rc;
-    }
-    D2H(tau, dt, bytes);
-    HIP_TRY(hipStreamSynchronize(ctx->compute));
-    return MP_OK;
-  }
-  char *cq = (char*)dq, *cqd = (char*)dqd, *cqdd = (char*)dqdd, *ct = (char*)dt;
-  return host_pipeline(
-      ctx, rows, chunk,
-      [&](int64_t r0, int64_t nr) -> int {
-        const size_t off = (size_t)r0 * row_b, nb = (size_t)nr * row_b;
-        UP(cq + off, (const char*)q + off, nb);
-        UP(cqd + off, (const char*)qd + off, nb);
-        UP(cqdd + off, (const char*)qdd + off, nb);
-        return MP_OK;
-      },
-      [&](int64_t r0, int64_t nr) -> int {
-        const size_t off = (size_t)r0 * row_b;
-        if (int rc = id_impl<T>(fn, ctx, model, (T*)(cq + off), (T*)(cqd + off), (T*)(cqdd + off), nr, g, Ftip, (T*)(ct + off))) return rc;
-        return hard_flush(ctx);  // the chunk's download follows
-      },
-      [&](int64_t r0, int64_t nr) -> int {
-        const size_t off = (size_t)r0 * row_b;
-        DOWN((char*)tau + off, ct + off, (size_t)nr * row_b);
-        return MP_OK;
-      });
+  const int64_t n = model->d.n;
+  HostCall h(ctx, rows);
+  const T *dq = h.in_rows(q, n * sizeof(T)), *dqd = h.in_rows(qd, n * sizeof(T)), *dqdd = h.in_rows(qdd, n * sizeof(T));
+  T* dt = h.out_rows(tau, n * sizeof(T));
+  const int64_t chunk = host_chunk_rows();  // pipelined from two chunks on
+  return h.run_rows(chunk, chunk + 1, [&](int64_t r0, int64_t nr) {
+    return id_impl<T>(fn, ctx, model, dq + r0 * n, dqd + r0 * n, dqdd + r0 * n, nr, g, Ftip, dt + r0 * n);
+  });
 }
 
 template <typename T>
@@ -1111,43 +1212,31 @@ static int fdtraj_vjp_host_impl(const char* fn, mp_ctx* ctx, const mp_model* mod
   if (cb >= 64) cb &= ~(int64_t)63;
   cb = std::min(cb, B);
   const size_t sr = (size_t)n * sizeof(double), tr = (size_t)N * sr, fr = (size_t)N * 6 * sizeof(double);
-  Scratch sc(ctx);
-  void *d0, *d1, *dtau, *dF = nullptr, *dgp = nullptr, *dgv = nullptr, *dga = nullptr, *dwork, *dg0, *dg1, *dgt, *stage;
-  if (int rc = sc.get(cb * sr, &d0)) return rc;
-  if (int rc = sc.get(cb * sr, &d1)) return rc;
-  if (int rc = sc.get(cb * tr, &dtau)) return rc;
-  if (Ftipmat) if (int rc = sc.get(cb * fr, &dF)) return rc;
-  if (gpos) if (int rc = sc.get(cb * tr, &dgp)) return rc;
-  if (gvel) if (int rc = sc.get(cb * tr, &dgv)) return rc;
-  if (gacc) if (int rc = sc.get(cb * tr, &dga)) return rc;
-  if (int rc = sc.get((size_t)vjp_work_doubles(n, cb, N, intRes) * sizeof(double), &dwork)) return rc;
-  if (int rc = sc.get(cb * sr, &dg0)) return rc;
-  if (int rc = sc.get(cb * sr, &dg1)) return rc;
-  if (int rc = sc.get(cb * tr, &dgt)) return rc;
-  if (int rc = sc.get(cb * std::max(tr, fr), &stage)) return rc;  // batch-major staging, reused in stream order
+  // the blocks hold one chunk and serve every chunk, so the arrays are moved chunk by chunk rather than declared
+  HostCall h(ctx);
+  h.stage(cb * std::max(tr, fr));  // batch-major staging, reused in stream order
+  double *d0 = h.work<double>(cb * sr), *d1 = h.work<double>(cb * sr), *dtau = h.work<double>(cb * tr);
+  double *dF = Ftipmat ? h.work<double>(cb * fr) : nullptr, *dgp = gpos ? h.work<double>(cb * tr) : nullptr;
+  double *dgv = gvel ? h.work<double>(cb * tr) : nullptr, *dga = gacc ? h.work<double>(cb * tr) : nullptr;
+  void* dwork = h.work((size_t)vjp_work_doubles(n, cb, N, intRes) * sizeof(double));
+  double *dg0 = h.work<double>(cb * sr), *dg1 = h.work<double>(cb * sr), *dgt = h.work<double>(cb * tr);
   for (int64_t b0 = 0; b0 < B; b0 += cb) {
     const int64_t nb = std::min(cb, B - b0);
-    auto up_tm = [&](const double* src, size_t row, void* dst) -> int {  // (nb, N, row) host -> (N, nb, row) device
-      H2D(stage, (const char*)src + b0 * row * N, nb * row * N);
-      return mp_transpose_rows(ctx, stage, nb, N, (int64_t)row, dst);
-    };
-    H2D(d0, (const char*)theta0 + b0 * sr, nb * sr);
-    H2D(d1, (const char*)dtheta0 + b0 * sr, nb * sr);
-    if (int rc = up_tm(taumat, sr, dtau)) return rc;
-    if (Ftipmat) if (int rc = up_tm(Ftipmat, 6 * sizeof(double), dF)) return rc;
-    if (gpos) if (int rc = up_tm(gpos, sr, dgp)) return rc;
-    if (gvel) if (int rc = up_tm(gvel, sr, dgv)) return rc;
-    if (gacc) if (int rc = up_tm(gacc, sr, dga)) return rc;
-    if (int rc = fdtraj_vjp_impl(fn, ctx, model, (double*)d0, (double*)d1, (double*)dtau, (double*)dF, nb, N, g, dt, intRes, (double*)dgp,
-                                 (double*)dgv, (double*)dga, dwork, (double*)dg0, (double*)dg1, (double*)dgt))
-      return rc;
-    if (int rc = mp_transpose_rows(ctx, dgt, N, nb, (int64_t)sr, stage)) return rc;
-    D2H((char*)gtheta0 + b0 * sr, dg0, nb * sr);
-    D2H((char*)gdtheta0 + b0 * sr, dg1, nb * sr);
-    D2H((char*)gtaumat + b0 * tr, stage, nb * tr);
+    h.upload(d0, theta0 + b0 * n, nb * sr);
+    h.upload(d1, dtheta0 + b0 * n, nb * sr);
+    h.upload_tm(dtau, taumat + b0 * N * n, nb, N, sr);
+    if (dF) h.upload_tm(dF, Ftipmat + b0 * N * 6, nb, N, 6 * sizeof(double));
+    if (dgp) h.upload_tm(dgp, gpos + b0 * N * n, nb, N, sr);
+    if (dgv) h.upload_tm(dgv, gvel + b0 * N * n, nb, N, sr);
+    if (dga) h.upload_tm(dga, gacc + b0 * N * n, nb, N, sr);
+    h.step([&] {
+      return fdtraj_vjp_impl(fn, ctx, model, d0, d1, dtau, dF, nb, N, g, dt, intRes, dgp, dgv, dga, dwork, dg0, dg1, dgt);
+    });
+    h.download(gtheta0 + b0 * n, dg0, nb * sr);
+    h.download(gdtheta0 + b0 * n, dg1, nb * sr);
+    h.download_tm(gtaumat + b0 * N * n, dgt, N, nb, sr);
   }
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  return h.finish();
 }
 
 // batched iLQR (mp_ilqr.h): float64, unrolled models only, intRes = 1.  The weights are host vectors (2n, n, 2n) and travel as kernel
@@ -1240,51 +1329,25 @@ static int ilqr_backward_host_impl(const char* fn, mp_ctx* ctx, const mp_model* 
   REQUIRE(pos && vel && taumat && xref && reg && K && k && dV && status, "%s: null host pointer", fn);
   const int n = model->d.n;
   const size_t sr = (size_t)n * sizeof(double), tr = (size_t)N * sr, blk = (size_t)(N - 1) * B * n * sr;
-  Scratch sc(ctx);
-  void *dp, *dv, *dt_, *dx, *dr, *dq, *dqd, *dmi, *dwork, *dK, *dk, *ddV, *dst, *stage;
-  if (int rc = sc.get(B * tr, &dp)) return rc;
-  if (int rc = sc.get(B * tr, &dv)) return rc;
-  if (int rc = sc.get(B * tr, &dt_)) return rc;
-  if (int rc = sc.get(2 * B * tr, &dx)) return rc;
-  if (int rc = sc.get(B * sizeof(double), &dr)) return rc;
-  if (int rc = sc.get(blk, &dq)) return rc;
-  if (int rc = sc.get(blk, &dqd)) return rc;
-  if (int rc = sc.get(blk, &dmi)) return rc;
-  if (int rc = sc.get(ilqr_lane_variant() ? (size_t)B * mp_ilqr_work_doubles(n) * sizeof(double) : 0, &dwork)) return rc;
-  if (int rc = sc.get(2 * B * tr * n, &dK)) return rc;
-  if (int rc = sc.get(B * tr, &dk)) return rc;
-  if (int rc = sc.get(B * 2 * sizeof(double), &ddV)) return rc;
-  if (int rc = sc.get(B * sizeof(int32_t), &dst)) return rc;
-  if (int rc = sc.get(2 * B * tr, &stage)) return rc;
-  auto up_tm = [&](const double* src, size_t row, void* dst_) -> int {  // (B, N, row) host -> (N, B, row) device
-    H2D(stage, src, B * row * N);
-    return mp_transpose_rows(ctx, stage, B, N, (int64_t)row, dst_);
-  };
-  if (int rc = up_tm(pos, sr, dp)) return rc;
-  if (int rc = up_tm(vel, sr, dv)) return rc;
-  if (int rc = up_tm(taumat, sr, dt_)) return rc;
-  if (int rc = up_tm(xref, 2 * sr, dx)) return rc;
-  H2D(dr, reg, B * sizeof(double));
-  const double* dtau1 = (const double*)dt_ + B * n;  // torque rows 1..N-1; with B n odd they start 8 bytes off the alignment asked for
-  if ((B * n) & 1) {
-    void* cp;
-    if (int rc = sc.get((size_t)(N - 1) * B * sr, &cp)) return rc;
-    if (int rc = mp_transpose_rows(ctx, dtau1, 1, (N - 1) * B, (int64_t)sr, cp)) return rc;  // outer = 1: a device copy
-    dtau1 = (const double*)cp;
-  }
-  if (int rc = deriv_impl(fn, true, ctx, model, (double*)dp, (double*)dv, dtau1, (N - 1) * B, g, nullptr, nullptr, (double*)dq,
-                          (double*)dqd, (double*)dmi))
-    return rc;
-  if (int rc = ilqr_backward_impl(fn, ctx, model, (double*)dp, (double*)dv, (double*)dt_, (double*)dq, (double*)dqd, (double*)dmi,
-                                  (double*)dx, wq, wr, wf, (double*)dr, B, N, dt, true, dwork, (double*)dK, (double*)dk, (double*)ddV,
-                                  (int32_t*)dst))
-    return rc;
-  D2H(K, dK, 2 * B * tr * n);
-  D2H(k, dk, B * tr);
-  D2H(dV, ddV, B * 2 * sizeof(double));
-  D2H(status, dst, B * sizeof(int32_t));
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  h.stage(2 * B * tr);
+  const double *dp = h.in_tm(pos, B, N, sr), *dv = h.in_tm(vel, B, N, sr), *dt_ = h.in_tm(taumat, B, N, sr);
+  const double *dx = h.in_tm(xref, B, N, 2 * sr), *dr = h.in(reg, B * sizeof(double));
+  double *dq = h.work<double>(blk), *dqd = h.work<double>(blk), *dmi = h.work<double>(blk);
+  void* dwork = h.work(ilqr_lane_variant() ? (size_t)B * mp_ilqr_work_doubles(n) * sizeof(double) : 0);
+  double *dK = h.out(K, 2 * B * tr * n), *dk = h.out(k, B * tr), *ddV = h.out(dV, B * 2 * sizeof(double));
+  int32_t* dst = h.out(status, B * sizeof(int32_t));
+  // torque rows 1..N-1; with B n odd they start 8 bytes off the alignment asked for and are copied to a block of their own
+  double* realigned = ((B * n) & 1) ? h.work<double>((size_t)(N - 1) * B * sr) : nullptr;
+  return h.run([&]() -> int {
+    const double* dtau1 = dt_ + B * n;
+    if (realigned) {
+      if (int rc = mp_transpose_rows(ctx, dtau1, 1, (N - 1) * B, (int64_t)sr, realigned)) return rc;  // outer = 1: a device copy
+      dtau1 = realigned;
+    }
+    if (int rc = deriv_impl(fn, true, ctx, model, dp, dv, dtau1, (N - 1) * B, g, nullptr, nullptr, dq, dqd, dmi)) return rc;
+    return ilqr_backward_impl(fn, ctx, model, dp, dv, dt_, dq, dqd, dmi, dx, wq, wr, wf, dr, B, N, dt, true, dwork, dK, dk, ddV, dst);
+  });
 }
 static int ilqr_rollout_host_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const double* theta0, const double* dtheta0,
                                   const double* taumat, const double* pos, const double* vel, const double* K, const double* k,
@@ -1304,57 +1367,17 @@ static int ilqr_rollout_host_impl(const char* fn, mp_ctx* ctx, const mp_model* m
           "%s: the three row outputs must all be given or all be null", fn);
   const int n = model->d.n;
   const size_t sr = (size_t)n * sizeof(double), tr = (size_t)N * sr, L = (size_t)A * B;
-  Scratch sc(ctx);
-  void *d0, *d1, *dt_, *dp = nullptr, *dv = nullptr, *dK = nullptr, *dk = nullptr, *da, *dx, *dc, *dop = nullptr, *dov = nullptr,
-       *dot = nullptr, *stage;
-  if (int rc = sc.get(B * sr, &d0)) return rc;
-  if (int rc = sc.get(B * sr, &d1)) return rc;
-  if (int rc = sc.get(B * tr, &dt_)) return rc;
-  if (K) {
-    if (int rc = sc.get(B * tr, &dp)) return rc;
-    if (int rc = sc.get(B * tr, &dv)) return rc;
-    if (int rc = sc.get(2 * B * tr * n, &dK)) return rc;
-    if (int rc = sc.get(B * tr, &dk)) return rc;
-  }
-  if (int rc = sc.get(L * sizeof(double), &da)) return rc;
-  if (int rc = sc.get(2 * B * tr, &dx)) return rc;
-  if (int rc = sc.get(L * sizeof(double), &dc)) return rc;
-  if (opos) {
-    if (int rc = sc.get(L * tr, &dop)) return rc;
-    if (int rc = sc.get(L * tr, &dov)) return rc;
-    if (int rc = sc.get(L * tr, &dot)) return rc;
-  }
-  if (int rc = sc.get(std::max(2 * B * tr, opos ? L * tr : (size_t)0), &stage)) return rc;
-  auto up_tm = [&](const double* src, size_t row, void* dst_) -> int {
-    H2D(stage, src, B * row * N);
-    return mp_transpose_rows(ctx, stage, B, N, (int64_t)row, dst_);
-  };
-  H2D(d0, theta0, B * sr);
-  H2D(d1, dtheta0, B * sr);
-  if (int rc = up_tm(taumat, sr, dt_)) return rc;
-  if (K) {
-    if (int rc = up_tm(pos, sr, dp)) return rc;
-    if (int rc = up_tm(vel, sr, dv)) return rc;
-    H2D(dK, K, 2 * B * tr * n);
-    H2D(dk, k, B * tr);
-  }
-  if (int rc = up_tm(xref, 2 * sr, dx)) return rc;
-  H2D(da, alpha, L * sizeof(double));
-  if (int rc = ilqr_rollout_impl(fn, ctx, model, (double*)d0, (double*)d1, (double*)dt_, (double*)dp, (double*)dv, (double*)dK, (double*)dk,
-                                 (double*)da, (double*)dx, wq, wr, wf, A, B, N, g, dt, true, (double*)dc, (double*)dop, (double*)dov,
-                                 (double*)dot))
-    return rc;
-  D2H(cost, dc, L * sizeof(double));
-  if (opos) {
-    void* outs[3] = {dop, dov, dot};
-    double* hosts[3] = {opos, ovel, otau};
-    for (int i = 0; i < 3; ++i) {  // (N, A B, n) -> (A B, N, n), staged in stream order
-      if (int rc = mp_transpose_rows(ctx, outs[i], N, (int64_t)L, (int64_t)sr, stage)) return rc;
-      D2H(hosts[i], stage, L * tr);
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  h.stage(std::max(2 * B * tr, opos ? L * tr : (size_t)0));
+  const double *d0 = h.in(theta0, B * sr), *d1 = h.in(dtheta0, B * sr), *dt_ = h.in_tm(taumat, B, N, sr);
+  const double *dp = h.in_tm(K ? pos : nullptr, B, N, sr), *dv = h.in_tm(K ? vel : nullptr, B, N, sr);  // the nominal: with gains only
+  const double *dK = h.in(K, 2 * B * tr * n), *dk = h.in(k, B * tr);
+  const double *dx = h.in_tm(xref, B, N, 2 * sr), *da = h.in(alpha, L * sizeof(double));
+  double* dc = h.out(cost, L * sizeof(double));
+  double *dop = h.out_tm(opos, N, (int64_t)L, sr), *dov = h.out_tm(ovel, N, (int64_t)L, sr), *dot = h.out_tm(otau, N, (int64_t)L, sr);
+  return h.run([&] {
+    return ilqr_rollout_impl(fn, ctx, model, d0, d1, dt_, dp, dv, dK, dk, da, dx, wq, wr, wf, A, B, N, g, dt, true, dc, dop, dov, dot);
+  });
 }
 
 // time-optimal path parameterisation (mp_toppra.h): float64, unrolled models only.  The limits are host vectors and travel as kernel
@@ -1456,61 +1479,20 @@ static int toppra_host_impl(const char* fn, mp_ctx* ctx, const mp_model* model, 
           "%s: the three row outputs must all be given or all be null", fn);
   const int n = model->d.n;
   const size_t sr = (size_t)n * sizeof(double), rows = (size_t)B * N, col = rows * sizeof(double);
-  Scratch sc(ctx);
-  void *dq0, *dq1, *dq2, *da, *db, *dc, *dxb, *ds0, *ds1, *dK, *dx, *du, *dt_, *ddur, *dst, *stage, *o[3] = {nullptr, nullptr, nullptr};
-  if (int rc = sc.get(rows * sr, &dq0)) return rc;
-  if (int rc = sc.get(rows * sr, &dq1)) return rc;
-  if (int rc = sc.get(rows * sr, &dq2)) return rc;
-  if (int rc = sc.get(rows * sr, &da)) return rc;
-  if (int rc = sc.get(rows * sr, &db)) return rc;
-  if (int rc = sc.get(rows * sr, &dc)) return rc;
-  if (int rc = sc.get(col, &dxb)) return rc;
-  if (int rc = sc.get(B * sizeof(double), &ds0)) return rc;
-  if (int rc = sc.get(B * sizeof(double), &ds1)) return rc;
-  if (int rc = sc.get(2 * col, &dK)) return rc;
-  if (int rc = sc.get(col, &dx)) return rc;
-  if (int rc = sc.get(col, &du)) return rc;
-  if (int rc = sc.get(col, &dt_)) return rc;
-  if (int rc = sc.get(B * sizeof(double), &ddur)) return rc;
-  if (int rc = sc.get(B * sizeof(int32_t), &dst)) return rc;
-  if (int rc = sc.get(std::max(rows * sr, 2 * col), &stage)) return rc;
-  if (tau)
-    for (int i = 0; i < 3; ++i)
-      if (int rc = sc.get(rows * sr, &o[i])) return rc;
-  auto up_tm = [&](const double* src, void* dst_) -> int {   // (B, N, n) host -> (N, B, n) device
-    H2D(stage, src, rows * sr);
-    return mp_transpose_rows(ctx, stage, B, N, (int64_t)sr, dst_);
-  };
-  if (int rc = up_tm(q, dq0)) return rc;
-  if (int rc = up_tm(dq, dq1)) return rc;
-  if (int rc = up_tm(ddq, dq2)) return rc;
-  H2D(ds0, sd_start, B * sizeof(double));
-  H2D(ds1, sd_end, B * sizeof(double));
-  if (int rc = path_dynamics_impl(fn, ctx, model, (double*)dq0, (double*)dq1, (double*)dq2, (int64_t)rows, vlim, g, Ftip, (double*)da,
-                                  (double*)db, (double*)dc, (double*)dxb))
-    return rc;
-  if (int rc = toppra_tm_impl(fn, ctx, model, (double*)da, (double*)db, (double*)dc, (double*)dxb, (double*)dq1, (double*)dq2, tlim, alim,
-                              (double*)ds0, (double*)ds1, B, N, (double*)dK, (double*)dx, (double*)du, (double*)dt_, (double*)ddur,
-                              (int32_t*)dst, (double*)o[0], (double*)o[1], (double*)o[2]))
-    return rc;
-  auto down_bm = [&](void* src, size_t row, double* dst_) -> int {   // (N, B, row) device -> (B, N, row) host, staged in stream order
-    if (int rc = mp_transpose_rows(ctx, src, N, B, (int64_t)row, stage)) return rc;
-    D2H(dst_, stage, rows * row);
-    return MP_OK;
-  };
-  if (int rc = down_bm(dK, 2 * sizeof(double), K)) return rc;
-  if (int rc = down_bm(dx, sizeof(double), x)) return rc;
-  if (int rc = down_bm(du, sizeof(double), u)) return rc;
-  if (int rc = down_bm(dt_, sizeof(double), t)) return rc;
-  if (tau) {
-    double* hosts[3] = {qd, qdd, tau};
-    for (int i = 0; i < 3; ++i)
-      if (int rc = down_bm(o[i], sr, hosts[i])) return rc;
-  }
-  D2H(dur, ddur, B * sizeof(double));
-  D2H(status, dst, B * sizeof(int32_t));
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  h.stage(std::max(rows * sr, 2 * col));
+  const double *dq0 = h.in_tm(q, B, N, sr), *dq1 = h.in_tm(dq, B, N, sr), *dq2 = h.in_tm(ddq, B, N, sr);
+  const double *ds0 = h.in(sd_start, B * sizeof(double)), *ds1 = h.in(sd_end, B * sizeof(double));
+  double *da = h.work<double>(rows * sr), *db = h.work<double>(rows * sr), *dc = h.work<double>(rows * sr), *dxb = h.work<double>(col);
+  double *dK = h.out_tm(K, N, B, 2 * sizeof(double)), *dx = h.out_tm(x, N, B, sizeof(double)), *du = h.out_tm(u, N, B, sizeof(double));
+  double* dt_ = h.out_tm(t, N, B, sizeof(double));
+  double *dqd = h.out_tm(qd, N, B, sr), *dqdd = h.out_tm(qdd, N, B, sr), *dtau = h.out_tm(tau, N, B, sr);
+  double* ddur = h.out(dur, B * sizeof(double));
+  int32_t* dst = h.out(status, B * sizeof(int32_t));
+  return h.run([&]() -> int {
+    if (int rc = path_dynamics_impl(fn, ctx, model, dq0, dq1, dq2, (int64_t)rows, vlim, g, Ftip, da, db, dc, dxb)) return rc;
+    return toppra_tm_impl(fn, ctx, model, da, db, dc, dxb, dq1, dq2, tlim, alim, ds0, ds1, B, N, dK, dx, du, dt_, ddur, dst, dqd, dqdd, dtau);
+  });
 }
 
 // specialised forward-dynamics roll-out (float32 only): -1 = none available, otherwise the launch's return code
@@ -1574,59 +1556,17 @@ static int fdtraj_host_impl(const char* fn, mp_ctx* ctx, const mp_model* model, 
   REQUIRE(B >= 0 && N >= 0, "%s: negative B or N", fn);
   if (B == 0 || N == 0) return MP_OK;
   REQUIRE(theta0 && dtheta0 && taumat && pos && vel && acc, "%s: null host pointer", fn);
-  const size_t n = (size_t)model->d.n, sb = (size_t)B * n * sizeof(T), tb = (size_t)B * (size_t)N * n * sizeof(T);
-  const size_t fb = (size_t)B * (size_t)N * 6 * sizeof(T), ob = (size_t)B * (size_t)N * n * sizeof(float);
-  Scratch sc(ctx);
-  void *d0, *d1, *dt_, *df = nullptr, *dp, *dv, *da;
-  if (int rc = sc.get(sb, &d0)) return rc;
-  if (int rc = sc.get(sb, &d1)) return rc;
-  if (int rc = sc.get(tb, &dt_)) return rc;
-  if (Ftipmat) if (int rc = sc.get(fb, &df)) return rc;
-  if (int rc = sc.get(ob, &dp)) return rc;
-  if (int rc = sc.get(ob, &dv)) return rc;
-  if (int rc = sc.get(ob, &da)) return rc;
-  // Page-locked arrays: the batch is cut into chunks of whole trajectories and the three stages overlap - upload of chunk k + 1,
-  // roll-out of chunk k, download of chunk k - 1 (host_pipeline, as for the inverse-dynamics and FK entry points).  A roll-out
-  // moves (n + 6) sizeof(T) bytes up and 12 n down per step, so with full-duplex PCIe the call costs about its larger direction.
-  {
-    const bool pinned = is_pinned_host(theta0) && is_pinned_host(dtheta0) && is_pinned_host(taumat) && (!Ftipmat || is_pinned_host(Ftipmat)) &&
-                        is_pinned_host(pos) && is_pinned_host(vel) && is_pinned_host(acc);
-    const int64_t cb = std::max<int64_t>(64, (host_chunk_rows() / std::max<int64_t>(N, 1)) & ~(int64_t)63);  // trajectories per chunk
-    if (pinned && B >= 2 * cb) {
-      const size_t srow = n * sizeof(T), trow = (size_t)N * n * sizeof(T), frow = (size_t)N * 6 * sizeof(T), orow = (size_t)N * n * sizeof(float);
-      char *c0 = (char*)d0, *c1 = (char*)d1, *ct = (char*)dt_, *cf = (char*)df, *cp = (char*)dp, *cv = (char*)dv, *ca = (char*)da;
-      return host_pipeline(
-          ctx, B, cb,
-          [&](int64_t b0, int64_t nb) -> int {
-            UP(c0 + b0 * srow, (const char*)theta0 + b0 * srow, nb * srow);
-            UP(c1 + b0 * srow, (const char*)dtheta0 + b0 * srow, nb * srow);
-            UP(ct + b0 * trow, (const char*)taumat + b0 * trow, nb * trow);
-            if (Ftipmat) UP(cf + b0 * frow, (const char*)Ftipmat + b0 * frow, nb * frow);
-            return MP_OK;
-          },
-          [&](int64_t b0, int64_t nb) -> int {
-            return fdtraj_impl<T>(fn, ctx, model, (T*)(c0 + b0 * srow), (T*)(c1 + b0 * srow), (T*)(ct + b0 * trow),
-                                  Ftipmat ? (T*)(cf + b0 * frow) : nullptr, nb, N, g, dt, intRes, (float*)(cp + b0 * orow),
-                                  (float*)(cv + b0 * orow), (float*)(ca + b0 * orow));
-          },
-          [&](int64_t b0, int64_t nb) -> int {
-            DOWN((char*)pos + b0 * orow, cp + b0 * orow, nb * orow);
-            DOWN((char*)vel + b0 * orow, cv + b0 * orow, nb * orow);
-            DOWN((char*)acc + b0 * orow, ca + b0 * orow, nb * orow);
-            return MP_OK;
-          });
-    }
-  }
-  H2D(d0, theta0, sb);
-  H2D(d1, dtheta0, sb);
-  H2D(dt_, taumat, tb);
-  if (Ftipmat) H2D(df, Ftipmat, fb);
-  if (int rc = fdtraj_impl<T>(fn, ctx, model, (T*)d0, (T*)d1, (T*)dt_, (T*)df, B, N, g, dt, intRes, (float*)dp, (float*)dv, (float*)da)) return rc;
-  D2H(pos, dp, ob);
-  D2H(vel, dv, ob);
-  D2H(acc, da, ob);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  // Rows are whole trajectories: one moves (n + 6) sizeof(T) bytes up and 12 n down per step.
+  const int64_t n = model->d.n, tn = N * n;
+  HostCall h(ctx, B);
+  const T *d0 = h.in_rows(theta0, n * sizeof(T)), *d1 = h.in_rows(dtheta0, n * sizeof(T)), *dt_ = h.in_rows(taumat, tn * sizeof(T));
+  const T* df = h.in_rows(Ftipmat, N * 6 * sizeof(T));
+  float *dp = h.out_rows(pos, tn * sizeof(float)), *dv = h.out_rows(vel, tn * sizeof(float)), *da = h.out_rows(acc, tn * sizeof(float));
+  const int64_t cb = std::max<int64_t>(64, (host_chunk_rows() / std::max<int64_t>(N, 1)) & ~(int64_t)63);  // trajectories per chunk
+  return h.run_rows(cb, 2 * cb, [&](int64_t b0, int64_t nb) {
+    return fdtraj_impl<T>(fn, ctx, model, d0 + b0 * n, d1 + b0 * n, dt_ + b0 * tn, at(df, b0 * N * 6), nb, N, g, dt, intRes, dp + b0 * tn,
+                          dv + b0 * tn, da + b0 * tn);
+  });
 }
 }  // namespace
 
@@ -2540,21 +2480,10 @@ int mp_batch_trajectory_host_f32(mp_ctx* ctx, const mp_model* model, const float
   if (B == 0 || N == 0) return MP_OK;
   REQUIRE(start && end && pos && vel && acc, "mp_batch_trajectory_host_f32: null host pointer");
   const size_t n = (size_t)model->d.n, in_b = (size_t)B * n * sizeof(float), out_b = (size_t)B * (size_t)N * n * sizeof(float);
-  Scratch sc(ctx);
-  void *ds, *de, *dp, *dv, *da;
-  if (int rc = sc.get(in_b, &ds)) return rc;
-  if (int rc = sc.get(in_b, &de)) return rc;
-  if (int rc = sc.get(out_b, &dp)) return rc;
-  if (int rc = sc.get(out_b, &dv)) return rc;
-  if (int rc = sc.get(out_b, &da)) return rc;
-  H2D(ds, start, in_b);
-  H2D(de, end, in_b);
-  if (int rc = mp_batch_trajectory_f32(ctx, model, (float*)ds, (float*)de, B, N, Tf, method, (float*)dp, (float*)dv, (float*)da)) return rc;
-  D2H(pos, dp, out_b);
-  D2H(vel, dv, out_b);
-  D2H(acc, da, out_b);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const float *ds = h.in(start, in_b), *de = h.in(end, in_b);
+  float *dp = h.out(pos, out_b), *dv = h.out(vel, out_b), *da = h.out(acc, out_b);
+  return h.run([&] { return mp_batch_trajectory_f32(ctx, model, ds, de, B, N, Tf, method, dp, dv, da); });
 }
 
 int mp_id_trajectory_host_f32(mp_ctx* ctx, const mp_model* model, const float* q, const float* qd, const float* qdd,
@@ -2573,18 +2502,10 @@ int mp_traj_id_fused_host_f32(mp_ctx* ctx, const mp_model* model, const float* s
   if (B == 0 || N == 0) return MP_OK;
   REQUIRE(start && end && tau, "mp_traj_id_fused_host_f32: null host pointer");
   const size_t n = (size_t)model->d.n, in_b = (size_t)B * n * sizeof(float), out_b = (size_t)B * (size_t)N * n * sizeof(float);
-  Scratch sc(ctx);
-  void *ds, *de, *dt;
-  if (int rc = sc.get(in_b, &ds)) return rc;
-  if (int rc = sc.get(in_b, &de)) return rc;
-  if (int rc = sc.get(out_b, &dt)) return rc;
-  H2D(ds, start, in_b);
-  H2D(de, end, in_b);
-  if (int rc = mp_traj_id_fused_f32(ctx, model, (float*)ds, (float*)de, B, N, Tf, method, g, Ftip, (float*)dt)) return rc;
-  if (int rc = hard_flush(ctx)) return rc;  // the launch's float64 pass, parked: the download reads its rows
-  D2H(tau, dt, out_b);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const float *ds = h.in(start, in_b), *de = h.in(end, in_b);
+  float* dt = h.out(tau, out_b);
+  return h.run([&] { return mp_traj_id_fused_f32(ctx, model, ds, de, B, N, Tf, method, g, Ftip, dt); });
 }
 
 int mp_fk_jac_id_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd,
@@ -2594,61 +2515,16 @@ int mp_fk_jac_id_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, c
   if (rows == 0) return MP_OK;
   REQUIRE(q && (T || J || tau), "mp_fk_jac_id_host_f64: q and at least one output are required");
   REQUIRE(!tau || (qd && qdd), "mp_fk_jac_id_host_f64: tau requested without qd / qdd");
-  const size_t n = (size_t)model->d.n, row_b = n * sizeof(double), rb = (size_t)rows * row_b;
-  Scratch sc(ctx);
-  void *dq = nullptr, *dqd = nullptr, *dqdd = nullptr, *dT = nullptr, *dJ = nullptr, *dt = nullptr;
-  if (int rc = sc.get(rb, &dq)) return rc;
-  if (tau) {
-    if (int rc = sc.get(rb, &dqd)) return rc;
-    if (int rc = sc.get(rb, &dqdd)) return rc;
-    if (int rc = sc.get(rb, &dt)) return rc;
-  }
-  if (T) if (int rc = sc.get((size_t)rows * 16 * sizeof(double), &dT)) return rc;
-  if (J) if (int rc = sc.get(rb * 6, &dJ)) return rc;
-  // page-locked arrays throughout and more than one chunk: upload, kernels and the (much larger) download overlap
-  const int64_t chunk = host_chunk_rows();
-  const bool pinned = is_pinned_host(q) && (!tau || (is_pinned_host(qd) && is_pinned_host(qdd) && is_pinned_host(tau))) &&
-                      (!T || is_pinned_host(T)) && (!J || is_pinned_host(J));
-  if (pinned && rows > chunk) {
-    char *cq = (char*)dq, *cqd = (char*)dqd, *cqdd = (char*)dqdd, *ct = (char*)dt, *cT = (char*)dT, *cJ = (char*)dJ;
-    return host_pipeline(
-        ctx, rows, chunk,
-        [&](int64_t r0, int64_t nr) -> int {
-          const size_t off = (size_t)r0 * row_b, nb = (size_t)nr * row_b;
-          UP(cq + off, (const char*)q + off, nb);
-          if (tau) {
-            UP(cqd + off, (const char*)qd + off, nb);
-            UP(cqdd + off, (const char*)qdd + off, nb);
-          }
-          return MP_OK;
-        },
-        [&](int64_t r0, int64_t nr) -> int {
-          const size_t off = (size_t)r0 * row_b;
-          return mp_fk_jac_id_f64(ctx, model, (double*)(cq + off), tau ? (double*)(cqd + off) : nullptr,
-                                  tau ? (double*)(cqdd + off) : nullptr, nr, g, Ftip, T ? (double*)(cT + (size_t)r0 * 128) : nullptr,
-                                  J ? (double*)(cJ + off * 6) : nullptr, tau ? (double*)(ct + off) : nullptr);
-        },
-        [&](int64_t r0, int64_t nr) -> int {
-          const size_t off = (size_t)r0 * row_b, nb = (size_t)nr * row_b;
-          if (T) DOWN((char*)T + (size_t)r0 * 128, cT + (size_t)r0 * 128, (size_t)nr * 128);
-          if (J) DOWN((char*)J + off * 6, cJ + off * 6, nb * 6);
-          if (tau) DOWN((char*)tau + off, ct + off, nb);
-          return MP_OK;
-        });
-  }
-  H2D(dq, q, rb);
-  if (tau) {
-    H2D(dqd, qd, rb);
-    H2D(dqdd, qdd, rb);
-  }
-  if (int rc = mp_fk_jac_id_f64(ctx, model, (double*)dq, (double*)dqd, (double*)dqdd, rows, g, Ftip, (double*)dT,
-                                (double*)dJ, (double*)dt))
-    return rc;
-  if (T) D2H(T, dT, (size_t)rows * 16 * sizeof(double));
-  if (J) D2H(J, dJ, rb * 6);
-  if (tau) D2H(tau, dt, rb);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  const int64_t n = model->d.n;
+  const size_t row_b = (size_t)n * sizeof(double);
+  HostCall h(ctx, rows);
+  const double *dq = h.in_rows(q, row_b), *dqd = h.in_rows(tau ? qd : nullptr, row_b), *dqdd = h.in_rows(tau ? qdd : nullptr, row_b);
+  double *dT = h.out_rows(T, 16 * sizeof(double)), *dJ = h.out_rows(J, 6 * row_b), *dt = h.out_rows(tau, row_b);
+  const int64_t chunk = host_chunk_rows();  // pipelined from two chunks on: the download is much the larger direction
+  return h.run_rows(chunk, chunk + 1, [&](int64_t r0, int64_t nr) {
+    return mp_fk_jac_id_f64(ctx, model, dq + r0 * n, at(dqd, r0 * n), at(dqdd, r0 * n), nr, g, Ftip, at(dT, r0 * 16), at(dJ, r0 * 6 * n),
+                            at(dt, r0 * n));
+  });
 }
 
 int mp_mass_matrix_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, int64_t rows, double* d_M) {
@@ -2842,15 +2718,10 @@ int mp_mass_matrix_host_f64(mp_ctx* ctx, const mp_model* model, const double* q,
   if (rows == 0) return MP_OK;
   REQUIRE(q && M, "mp_mass_matrix_host_f64: null host pointer");
   const size_t n = (size_t)model->d.n, qb = (size_t)rows * n * sizeof(double), mb = qb * n;
-  Scratch sc(ctx);
-  void *dq, *dM;
-  if (int rc = sc.get(qb, &dq)) return rc;
-  if (int rc = sc.get(mb, &dM)) return rc;
-  H2D(dq, q, qb);
-  if (int rc = mp_mass_matrix_f64(ctx, model, (double*)dq, rows, (double*)dM)) return rc;
-  D2H(M, dM, mb);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const double* dq = h.in(q, qb);
+  double* dM = h.out(M, mb);
+  return h.run([&] { return mp_mass_matrix_f64(ctx, model, dq, rows, dM); });
 }
 int mp_forward_dynamics_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* tau,
                                  int64_t rows, const double* g, const double* Ftip, double* qdd) {
@@ -2859,19 +2730,10 @@ int mp_forward_dynamics_host_f64(mp_ctx* ctx, const mp_model* model, const doubl
   if (rows == 0) return MP_OK;
   REQUIRE(q && qd && tau && qdd, "mp_forward_dynamics_host_f64: null host pointer");
   const size_t bytes = (size_t)rows * (size_t)model->d.n * sizeof(double);
-  Scratch sc(ctx);
-  void *dq, *dqd, *dt, *dout;
-  if (int rc = sc.get(bytes, &dq)) return rc;
-  if (int rc = sc.get(bytes, &dqd)) return rc;
-  if (int rc = sc.get(bytes, &dt)) return rc;
-  if (int rc = sc.get(bytes, &dout)) return rc;
-  H2D(dq, q, bytes);
-  H2D(dqd, qd, bytes);
-  H2D(dt, tau, bytes);
-  if (int rc = mp_forward_dynamics_f64(ctx, model, (double*)dq, (double*)dqd, (double*)dt, rows, g, Ftip, (double*)dout)) return rc;
-  D2H(qdd, dout, bytes);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const double *dq = h.in(q, bytes), *dqd = h.in(qd, bytes), *dt = h.in(tau, bytes);
+  double* dout = h.out(qdd, bytes);
+  return h.run([&] { return mp_forward_dynamics_f64(ctx, model, dq, dqd, dt, rows, g, Ftip, dout); });
 }
 
 static int deriv_host_impl(const char* fn, bool fd, mp_ctx* ctx, const mp_model* model, const double* q, const double* qd,
@@ -2884,27 +2746,10 @@ static int deriv_host_impl(const char* fn, bool fd, mp_ctx* ctx, const mp_model*
   if (rows == 0) return MP_OK;
   REQUIRE(q && qd && x && dq && dqd, "%s: null host pointer", fn);
   const size_t vb = (size_t)rows * (size_t)model->d.n * sizeof(double), mb = vb * (size_t)model->d.n;
-  Scratch sc(ctx);
-  void *dq_in, *dqd_in, *dx, *dy = nullptr, *ddq, *ddqd, *dmat = nullptr;
-  if (int rc = sc.get(vb, &dq_in)) return rc;
-  if (int rc = sc.get(vb, &dqd_in)) return rc;
-  if (int rc = sc.get(vb, &dx)) return rc;
-  if (y) if (int rc = sc.get(vb, &dy)) return rc;
-  if (int rc = sc.get(mb, &ddq)) return rc;
-  if (int rc = sc.get(mb, &ddqd)) return rc;
-  if (mat) if (int rc = sc.get(mb, &dmat)) return rc;
-  H2D(dq_in, q, vb);
-  H2D(dqd_in, qd, vb);
-  H2D(dx, x, vb);
-  if (int rc = deriv_impl(fn, fd, ctx, model, (double*)dq_in, (double*)dqd_in, (double*)dx, rows, g, Ftip, (double*)dy, (double*)ddq,
-                          (double*)ddqd, (double*)dmat))
-    return rc;
-  if (y) D2H(y, dy, vb);
-  D2H(dq, ddq, mb);
-  D2H(dqd, ddqd, mb);
-  if (mat) D2H(mat, dmat, mb);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const double *dq_in = h.in(q, vb), *dqd_in = h.in(qd, vb), *dx = h.in(x, vb);
+  double *dy = h.out(y, vb), *ddq = h.out(dq, mb), *ddqd = h.out(dqd, mb), *dmat = h.out(mat, mb);
+  return h.run([&] { return deriv_impl(fn, fd, ctx, model, dq_in, dqd_in, dx, rows, g, Ftip, dy, ddq, ddqd, dmat); });
 }
 int mp_id_derivatives_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd,
                                int64_t rows, const double* g, const double* Ftip, double* tau, double* dtau_dq, double* dtau_dqd,
@@ -2927,29 +2772,10 @@ static int vjp_host_impl(const char* fn, bool fd, mp_ctx* ctx, const mp_model* m
   if (rows == 0) return MP_OK;
   REQUIRE(q && qd && x && cot && o1 && o2, "%s: null host pointer", fn);
   const size_t vb = (size_t)rows * (size_t)model->d.n * sizeof(double);
-  Scratch sc(ctx);
-  void *dq, *dqd, *dx, *dc, *dy = nullptr, *d1, *d2, *d3 = nullptr;
-  if (int rc = sc.get(vb, &dq)) return rc;
-  if (int rc = sc.get(vb, &dqd)) return rc;
-  if (int rc = sc.get(vb, &dx)) return rc;
-  if (int rc = sc.get(vb, &dc)) return rc;
-  if (y) if (int rc = sc.get(vb, &dy)) return rc;
-  if (int rc = sc.get(vb, &d1)) return rc;
-  if (int rc = sc.get(vb, &d2)) return rc;
-  if (o3) if (int rc = sc.get(vb, &d3)) return rc;
-  H2D(dq, q, vb);
-  H2D(dqd, qd, vb);
-  H2D(dx, x, vb);
-  H2D(dc, cot, vb);
-  if (int rc = vjp_impl(fn, fd, ctx, model, (double*)dq, (double*)dqd, (double*)dx, (double*)dc, rows, g, Ftip, (double*)dy, (double*)d1,
-                        (double*)d2, (double*)d3))
-    return rc;
-  if (y) D2H(y, dy, vb);
-  D2H(o1, d1, vb);
-  D2H(o2, d2, vb);
-  if (o3) D2H(o3, d3, vb);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const double *dq = h.in(q, vb), *dqd = h.in(qd, vb), *dx = h.in(x, vb), *dc = h.in(cot, vb);
+  double *dy = h.out(y, vb), *d1 = h.out(o1, vb), *d2 = h.out(o2, vb), *d3 = h.out(o3, vb);
+  return h.run([&] { return vjp_impl(fn, fd, ctx, model, dq, dqd, dx, dc, rows, g, Ftip, dy, d1, d2, d3); });
 }
 int mp_id_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd, const double* gtau,
                        int64_t rows, const double* g, const double* Ftip, double* gq, double* gqd, double* gqdd) {
@@ -2972,24 +2798,10 @@ int mp_fk_jac_vjp_host_f64(mp_ctx* ctx, const mp_model* model, int frame, const 
   REQUIRE(q, "%s: null host pointer", fn);
   REQUIRE(T || J || gq, "%s: at least one output is required", fn);
   const size_t vb = (size_t)rows * (size_t)model->d.n * sizeof(double), tb = (size_t)rows * 16 * sizeof(double);
-  Scratch sc(ctx);
-  void *dq, *dgT = nullptr, *dgJ = nullptr, *dT = nullptr, *dJ = nullptr, *dgq = nullptr;
-  if (int rc = sc.get(vb, &dq)) return rc;
-  if (gq && gT) if (int rc = sc.get(tb, &dgT)) return rc;
-  if (gq && gJ) if (int rc = sc.get(6 * vb, &dgJ)) return rc;
-  if (T) if (int rc = sc.get(tb, &dT)) return rc;
-  if (J) if (int rc = sc.get(6 * vb, &dJ)) return rc;
-  if (gq) if (int rc = sc.get(vb, &dgq)) return rc;
-  H2D(dq, q, vb);
-  if (dgT) H2D(dgT, gT, tb);
-  if (dgJ) H2D(dgJ, gJ, 6 * vb);
-  if (int rc = kin_vjp_impl(fn, ctx, model, frame, (double*)dq, (double*)dgT, (double*)dgJ, rows, (double*)dT, (double*)dJ, (double*)dgq))
-    return rc;
-  if (T) D2H(T, dT, tb);
-  if (J) D2H(J, dJ, 6 * vb);
-  if (gq) D2H(gq, dgq, vb);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const double *dq = h.in(q, vb), *dgT = h.in(gq ? gT : nullptr, tb), *dgJ = h.in(gq ? gJ : nullptr, 6 * vb);  // cotangents: for gq only
+  double *dT = h.out(T, tb), *dJ = h.out(J, 6 * vb), *dgq = h.out(gq, vb);
+  return h.run([&] { return kin_vjp_impl(fn, ctx, model, frame, dq, dgT, dgJ, rows, dT, dJ, dgq); });
 }
 
 int mp_opspace_host_f64(mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* q, const double* qd,
@@ -3004,23 +2816,11 @@ int mp_opspace_host_f64(mp_ctx* ctx, const mp_model* model, int frame, int task,
   REQUIRE(q && qd, "%s: null host pointer", fn);
   REQUIRE(T || J || Jdqd || Lambda || Jbar || mu || p, "%s: at least one output is required", fn);
   const size_t n = (size_t)model->d.n, m = task == 0 ? 6 : 3, rb = (size_t)rows * sizeof(double);
-  double* const host[7] = {T, J, Jdqd, Lambda, Jbar, mu, p};
-  const size_t bytes[7] = {16 * rb, m * n * rb, m * rb, m * m * rb, n * m * rb, m * rb, m * rb};
-  Scratch sc(ctx);
-  void *dq, *dqd, *dev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (int rc = sc.get(n * rb, &dq)) return rc;
-  if (int rc = sc.get(n * rb, &dqd)) return rc;
-  for (int k = 0; k < 7; ++k)
-    if (host[k]) if (int rc = sc.get(bytes[k], &dev[k])) return rc;
-  H2D(dq, q, n * rb);
-  H2D(dqd, qd, n * rb);
-  if (int rc = opspace_impl(fn, ctx, model, frame, task, damping, (double*)dq, (double*)dqd, rows, g, (double*)dev[0], (double*)dev[1],
-                            (double*)dev[2], (double*)dev[3], (double*)dev[4], (double*)dev[5], (double*)dev[6]))
-    return rc;
-  for (int k = 0; k < 7; ++k)
-    if (host[k]) D2H(host[k], dev[k], bytes[k]);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const double *dq = h.in(q, n * rb), *dqd = h.in(qd, n * rb);
+  double *dT = h.out(T, 16 * rb), *dJ = h.out(J, m * n * rb), *dJdqd = h.out(Jdqd, m * rb), *dLambda = h.out(Lambda, m * m * rb);
+  double *dJbar = h.out(Jbar, n * m * rb), *dmu = h.out(mu, m * rb), *dp = h.out(p, m * rb);
+  return h.run([&] { return opspace_impl(fn, ctx, model, frame, task, damping, dq, dqd, rows, g, dT, dJ, dJdqd, dLambda, dJbar, dmu, dp); });
 }
 
 int mp_opspace_torque_host_f64(mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* q, const double* qd,
@@ -3033,23 +2833,10 @@ int mp_opspace_torque_host_f64(mp_ctx* ctx, const mp_model* model, int frame, in
   if (rows == 0) return MP_OK;
   REQUIRE(q && qd && acc && tau, "%s: null host pointer", fn);
   const size_t vb = (size_t)rows * (size_t)model->d.n * sizeof(double), ab = (size_t)rows * (task == 0 ? 6 : 3) * sizeof(double);
-  Scratch sc(ctx);
-  void *dq, *dqd, *dacc, *dt0 = nullptr, *dtau;
-  if (int rc = sc.get(vb, &dq)) return rc;
-  if (int rc = sc.get(vb, &dqd)) return rc;
-  if (int rc = sc.get(ab, &dacc)) return rc;
-  if (tau0) if (int rc = sc.get(vb, &dt0)) return rc;
-  if (int rc = sc.get(vb, &dtau)) return rc;
-  H2D(dq, q, vb);
-  H2D(dqd, qd, vb);
-  H2D(dacc, acc, ab);
-  if (dt0) H2D(dt0, tau0, vb);
-  if (int rc = opspace_torque_impl(fn, ctx, model, frame, task, damping, (double*)dq, (double*)dqd, (double*)dacc, (double*)dt0, rows, g,
-                                   (double*)dtau))
-    return rc;
-  D2H(tau, dtau, vb);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const double *dq = h.in(q, vb), *dqd = h.in(qd, vb), *dacc = h.in(acc, ab), *dt0 = h.in(tau0, vb);
+  double* dtau = h.out(tau, vb);
+  return h.run([&] { return opspace_torque_impl(fn, ctx, model, frame, task, damping, dq, dqd, dacc, dt0, rows, g, dtau); });
 }
 
 int mp_id_regressor_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd, int64_t rows,
@@ -3062,21 +2849,10 @@ int mp_id_regressor_host_f64(mp_ctx* ctx, const mp_model* model, const double* q
   if (rows == 0) return MP_OK;
   REQUIRE(q && qd && qdd && Y, "%s: null host pointer", fn);
   const size_t n = (size_t)model->d.n, vb = (size_t)rows * n * sizeof(double), yb = vb * n * MP_REG_P;
-  Scratch sc(ctx);
-  void *dq, *dqd, *dqdd, *dY, *dte = nullptr;
-  if (int rc = sc.get(vb, &dq)) return rc;
-  if (int rc = sc.get(vb, &dqd)) return rc;
-  if (int rc = sc.get(vb, &dqdd)) return rc;
-  if (int rc = sc.get(yb, &dY)) return rc;
-  if (tau_ext) if (int rc = sc.get(vb, &dte)) return rc;
-  H2D(dq, q, vb);
-  H2D(dqd, qd, vb);
-  H2D(dqdd, qdd, vb);
-  if (int rc = regressor_impl(fn, ctx, model, (double*)dq, (double*)dqd, (double*)dqdd, rows, g, Ftip, (double*)dY, (double*)dte)) return rc;
-  D2H(Y, dY, yb);
-  if (tau_ext) D2H(tau_ext, dte, vb);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const double *dq = h.in(q, vb), *dqd = h.in(qd, vb), *dqdd = h.in(qdd, vb);
+  double *dY = h.out(Y, yb), *dte = h.out(tau_ext, vb);
+  return h.run([&] { return regressor_impl(fn, ctx, model, dq, dqd, dqdd, rows, g, Ftip, dY, dte); });
 }
 int mp_id_regressor_normal_host_f64(mp_ctx* ctx, const mp_model* model, const double* q, const double* qd, const double* qdd,
                                     const double* rhs, int64_t rows, const double* g, const double* Ftip, double* A, double* b,
@@ -3088,32 +2864,15 @@ int mp_id_regressor_normal_host_f64(mp_ctx* ctx, const mp_model* model, const do
   REQUIRE(rows >= 0, "%s: negative row count", fn);
   REQUIRE(b && rr && (rows == 0 || (q && qd && qdd && rhs)), "%s: null host pointer", fn);
   const size_t n = (size_t)model->d.n, vb = (size_t)rows * n * sizeof(double), w = n * MP_REG_P;
-  Scratch sc(ctx);
-  void *dq = nullptr, *dqd = nullptr, *dqdd = nullptr, *drhs = nullptr, *dwork = nullptr, *dA = nullptr, *db, *drr;
-  if (rows > 0) {
-    if (int rc = sc.get(vb, &dq)) return rc;
-    if (int rc = sc.get(vb, &dqd)) return rc;
-    if (int rc = sc.get(vb, &dqdd)) return rc;
-    if (int rc = sc.get(vb, &drhs)) return rc;
-    if (int rc = sc.get((size_t)regressor_normal_work_bytes((int)n, rows), &dwork)) return rc;
+  HostCall h(ctx);
+  const double *dq = nullptr, *dqd = nullptr, *dqdd = nullptr, *drhs = nullptr;
+  void* dwork = nullptr;
+  if (rows > 0) {  // (no rows: the launch only zeroes A, b and rr, which are downloaded all the same)
+    dq = h.in(q, vb), dqd = h.in(qd, vb), dqdd = h.in(qdd, vb), drhs = h.in(rhs, vb);
+    dwork = h.work((size_t)regressor_normal_work_bytes((int)n, rows));
   }
-  if (A) if (int rc = sc.get(w * w * sizeof(double), &dA)) return rc;
-  if (int rc = sc.get(w * sizeof(double), &db)) return rc;
-  if (int rc = sc.get(sizeof(double), &drr)) return rc;
-  if (rows > 0) {
-    H2D(dq, q, vb);
-    H2D(dqd, qd, vb);
-    H2D(dqdd, qdd, vb);
-    H2D(drhs, rhs, vb);
-  }
-  if (int rc = regressor_normal_impl(fn, ctx, model, (double*)dq, (double*)dqd, (double*)dqdd, (double*)drhs, rows, g, Ftip, dwork,
-                                     (double*)dA, (double*)db, (double*)drr))
-    return rc;
-  if (A) D2H(A, dA, w * w * sizeof(double));
-  D2H(b, db, w * sizeof(double));
-  D2H(rr, drr, sizeof(double));
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  double *dA = h.out(A, w * w * sizeof(double)), *db = h.out(b, w * sizeof(double)), *drr = h.out(rr, sizeof(double));
+  return h.run([&] { return regressor_normal_impl(fn, ctx, model, dq, dqd, dqdd, drhs, rows, g, Ftip, dwork, dA, db, drr); });
 }
 
 int mp_pd_regulation_host_f64(mp_ctx* ctx, const mp_model* model, const double* theta0, const double* theta_des, const double* Kp,
@@ -3125,37 +2884,23 @@ int mp_pd_regulation_host_f64(mp_ctx* ctx, const mp_model* model, const double* 
   REQUIRE(std::isfinite(dt), "mp_pd_regulation_host_f64: dt must be finite");
   const size_t qb = (size_t)K * (size_t)model->d.n * sizeof(double), kb = (size_t)K * sizeof(double),
                eb = (size_t)K * (size_t)steps * sizeof(double), cb = (size_t)K * sizeof(int32_t);
-  Scratch sc(ctx);
-  void *d0, *dd, *dkp, *dkd, *de, *dc;
-  if (int rc = sc.get(qb, &d0)) return rc;
-  if (int rc = sc.get(qb, &dd)) return rc;
-  if (int rc = sc.get(kb, &dkp)) return rc;
-  if (int rc = sc.get(kb, &dkd)) return rc;
-  if (int rc = sc.get(eb, &de)) return rc;
-  if (int rc = sc.get(cb, &dc)) return rc;
-  H2D(d0, theta0, qb);
-  H2D(dd, theta_des, qb);
-  H2D(dkp, Kp, kb);
-  H2D(dkd, Kd, kb);
-  if (eb) H2D(de, errors, eb);  // entries past a run's count keep the caller's values
+  HostCall h(ctx);
+  const double *d0 = h.in(theta0, qb), *dd = h.in(theta_des, qb), *dkp = h.in(Kp, kb), *dkd = h.in(Kd, kb);
+  double* de = eb ? h.inout(errors, eb) : h.work<double>(0);  // in-out: entries past a run's count keep the caller's values
+  int32_t* dc = h.out(count, cb);
   MpCall<double> c;
   make_call<double>(model, g, nullptr, &c);
-  {
+  return h.run([&]() -> int {
     PROFILE_SCOPE(ctx, "mp_pd_regulation_host_f64");
     if (model->big) {
       const MpBigModel<double>* dm = nullptr;
       if (int rc = device_big_model<double>(ctx, model, &dm)) return rc;
-      HIP_TRY(mpk_dyn_pd_regulation(ctx->compute, model->d.n, dm, c, (double*)d0, (double*)dd, (double*)dkp, (double*)dkd, (long)K, dt, steps,
-                                    (double*)de, (int*)dc));
+      HIP_TRY(mpk_dyn_pd_regulation(ctx->compute, model->d.n, dm, c, d0, dd, dkp, dkd, (long)K, dt, steps, de, (int*)dc));
     } else {
-      HIP_TRY(mpk_pd_regulation(ctx->compute, model->d, c, (double*)d0, (double*)dd, (double*)dkp, (double*)dkd, (long)K, dt, steps,
-                                (double*)de, (int*)dc));
+      HIP_TRY(mpk_pd_regulation(ctx->compute, model->d, c, d0, dd, dkp, dkd, (long)K, dt, steps, de, (int*)dc));
     }
-  }
-  if (eb) D2H(errors, de, eb);
-  D2H(count, dc, cb);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+    return MP_OK;
+  });
 }
 
 int mp_cartesian_trajectory_f32(mp_ctx* ctx, const double* d_Xstart, const double* d_Xend, int64_t B, int64_t N, double Tf,
@@ -3178,23 +2923,10 @@ int mp_cartesian_trajectory_host_f32(mp_ctx* ctx, const double* Xstart, const do
   if (B == 0 || N == 0) return MP_OK;
   REQUIRE(Xstart && Xend && pos && vel && acc && orient, "mp_cartesian_trajectory_host_f32: null host pointer");
   const size_t xb = (size_t)B * 16 * sizeof(double), pb = (size_t)B * (size_t)N * 3 * sizeof(float);
-  Scratch sc(ctx);
-  void *ds, *de, *dp, *dv, *da, *dor;
-  if (int rc = sc.get(xb, &ds)) return rc;
-  if (int rc = sc.get(xb, &de)) return rc;
-  if (int rc = sc.get(pb, &dp)) return rc;
-  if (int rc = sc.get(pb, &dv)) return rc;
-  if (int rc = sc.get(pb, &da)) return rc;
-  if (int rc = sc.get(pb * 3, &dor)) return rc;
-  H2D(ds, Xstart, xb);
-  H2D(de, Xend, xb);
-  if (int rc = mp_cartesian_trajectory_f32(ctx, (double*)ds, (double*)de, B, N, Tf, method, (float*)dp, (float*)dv, (float*)da, (float*)dor)) return rc;
-  D2H(pos, dp, pb);
-  D2H(vel, dv, pb);
-  D2H(acc, da, pb);
-  D2H(orient, dor, pb * 3);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const double *ds = h.in(Xstart, xb), *de = h.in(Xend, xb);
+  float *dp = h.out(pos, pb), *dv = h.out(vel, pb), *da = h.out(acc, pb), *dor = h.out(orient, pb * 3);
+  return h.run([&] { return mp_cartesian_trajectory_f32(ctx, ds, de, B, N, Tf, method, dp, dv, da, dor); });
 }
 
 int mp_potential_field_f32(mp_ctx* ctx, const float* d_positions, const float* goal, const float* d_obstacles, int64_t P,
@@ -3215,19 +2947,10 @@ int mp_potential_field_host_f32(mp_ctx* ctx, const float* positions, const float
   if (P == 0) return MP_OK;
   REQUIRE(positions && goal && potential && gradient && (O == 0 || obstacles), "mp_potential_field_host_f32: null pointer");
   const size_t pb = (size_t)P * 3 * sizeof(float), ob = (size_t)O * 3 * sizeof(float);
-  Scratch sc(ctx);
-  void *dp, *dob = nullptr, *du, *dg;
-  if (int rc = sc.get(pb, &dp)) return rc;
-  if (O) if (int rc = sc.get(ob, &dob)) return rc;
-  if (int rc = sc.get((size_t)P * sizeof(float), &du)) return rc;
-  if (int rc = sc.get(pb, &dg)) return rc;
-  H2D(dp, positions, pb);
-  if (O) H2D(dob, obstacles, ob);
-  if (int rc = mp_potential_field_f32(ctx, (float*)dp, goal, (float*)dob, P, O, influence_distance, (float*)du, (float*)dg)) return rc;
-  D2H(potential, du, (size_t)P * sizeof(float));
-  D2H(gradient, dg, pb);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const float *dp = h.in(positions, pb), *dob = h.in(O ? obstacles : nullptr, ob);
+  float *du = h.out(potential, (size_t)P * sizeof(float)), *dg = h.out(gradient, pb);
+  return h.run([&] { return mp_potential_field_f32(ctx, dp, goal, dob, P, O, influence_distance, du, dg); });
 }
 
 }  // extern "C"
@@ -3306,27 +3029,14 @@ int mp_inverse_kinematics_host_f64(mp_ctx* ctx, const mp_model* model, const dou
   if (B == 0) return MP_OK;
   REQUIRE(T_desired && theta0 && theta && success && iterations && restarts, "mp_inverse_kinematics_host_f64: null host pointer");
   const size_t tb = (size_t)B * 16 * sizeof(double), qb = (size_t)B * (size_t)model->d.n * sizeof(double), ib = (size_t)B * sizeof(int32_t);
-  Scratch sc(ctx);
-  void *dT, *d0, *dq, *dok, *dit, *drs;
-  if (int rc = sc.get(tb, &dT)) return rc;
-  if (int rc = sc.get(qb, &d0)) return rc;
-  if (int rc = sc.get(qb, &dq)) return rc;
-  if (int rc = sc.get(ib, &dok)) return rc;
-  if (int rc = sc.get(ib, &dit)) return rc;
-  if (int rc = sc.get(ib, &drs)) return rc;
-  H2D(dT, T_desired, tb);
-  H2D(d0, theta0, qb);
-  if (int rc = mp_inverse_kinematics_f64(ctx, model, (double*)dT, (double*)d0, B, joint_limits, eomg, ev, max_iterations, damping,
-                                         step_cap, weight_orientation, weight_position, adaptive_tuning, backtracking, seed, (double*)dq,
-                                         (int32_t*)dok,
-                                         (int32_t*)dit, (int32_t*)drs))
-    return rc;
-  D2H(theta, dq, qb);
-  D2H(success, dok, ib);
-  D2H(iterations, dit, ib);
-  D2H(restarts, drs, ib);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall h(ctx);
+  const double *dT = h.in(T_desired, tb), *d0 = h.in(theta0, qb);
+  double* dq = h.out(theta, qb);
+  int32_t *dok = h.out(success, ib), *dit = h.out(iterations, ib), *drs = h.out(restarts, ib);
+  return h.run([&] {
+    return mp_inverse_kinematics_f64(ctx, model, dT, d0, B, joint_limits, eomg, ev, max_iterations, damping, step_cap, weight_orientation,
+                                     weight_position, adaptive_tuning, backtracking, seed, dq, dok, dit, drs);
+  });
 }
 
 }  // extern "C"
@@ -3473,23 +3183,16 @@ int mp_collision_edges_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision
   if (edges == 0) return mp_collision_edges_check(fn, margin, tol, max_steps);
   REQUIRE(q_from && q_to, "%s: null host pointer", fn);
   const size_t n = (size_t)model->d.n, rb = (size_t)edges * sizeof(double), ib = (size_t)edges * sizeof(int32_t);
-  void* const host[5] = {status, t, steps, clearance, witness};
-  const size_t bytes[5] = {ib, rb, ib, rb, 3 * ib};
-  Scratch sc(ctx);
-  void *da, *db, *dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (int rc = sc.get(n * rb, &da)) return rc;
-  if (int rc = sc.get(n * rb, &db)) return rc;
-  for (int k = 0; k < 5; ++k)
-    if (host[k]) if (int rc = sc.get(bytes[k], &dev[k])) return rc;
-  H2D(da, q_from, n * rb);
-  H2D(db, q_to, n * rb);
-  if (int rc = collision_edges_impl(fn, ctx, model, h, (double*)da, (double*)db, edges, margin, tol, max_steps, 0, (int32_t*)dev[0],
-                                    (double*)dev[1], (int32_t*)dev[2], (double*)dev[3], (int32_t*)dev[4]))
-    return rc;
-  for (int k = 0; k < 5; ++k)
-    if (host[k]) D2H(host[k], dev[k], bytes[k]);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall hc(ctx);  // (h is the collision handle)
+  const double *da = hc.in(q_from, n * rb), *db = hc.in(q_to, n * rb);
+  int32_t* dstatus = hc.out(status, ib);
+  double* dt = hc.out(t, rb);
+  int32_t* dsteps = hc.out(steps, ib);
+  double* dclear = hc.out(clearance, rb);
+  int32_t* dwit = hc.out(witness, 3 * ib);
+  return hc.run([&] {
+    return collision_edges_impl(fn, ctx, model, h, da, db, edges, margin, tol, max_steps, 0, dstatus, dt, dsteps, dclear, dwit);
+  });
 }
 
 int mp_collision_set_world(mp_ctx* ctx, mp_collision* h, int O, const int32_t* kind, const double* params) {
@@ -3530,21 +3233,14 @@ int mp_collision_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, c
   if (rows == 0) return MP_OK;
   REQUIRE(q, "%s: null host pointer", fn);
   const size_t n = (size_t)model->d.n, rb = (size_t)rows * sizeof(double), ib = (size_t)rows * 2 * sizeof(int32_t);
-  void* const host[8] = {dist_world, arg_world, dist_self, arg_self, grad_dist_world, grad_dist_self, cost, grad};
-  const size_t bytes[8] = {rb, ib, rb, ib, n * rb, n * rb, rb, n * rb};
-  Scratch sc(ctx);
-  void *dq, *dev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (int rc = sc.get(n * rb, &dq)) return rc;
-  for (int k = 0; k < 8; ++k)
-    if (host[k]) if (int rc = sc.get(bytes[k], &dev[k])) return rc;
-  H2D(dq, q, n * rb);
-  if (int rc = collision_impl(fn, ctx, model, h, (double*)dq, rows, eps_world, eps_self, (double*)dev[0], (int32_t*)dev[1], (double*)dev[2],
-                              (int32_t*)dev[3], (double*)dev[4], (double*)dev[5], (double*)dev[6], (double*)dev[7]))
-    return rc;
-  for (int k = 0; k < 8; ++k)
-    if (host[k]) D2H(host[k], dev[k], bytes[k]);
-  HIP_TRY(hipStreamSynchronize(ctx->compute));
-  return MP_OK;
+  HostCall hc(ctx);  // (h is the collision handle)
+  const double* dq = hc.in(q, n * rb);
+  double* ddw = hc.out(dist_world, rb);
+  int32_t* daw = hc.out(arg_world, ib);
+  double* dds = hc.out(dist_self, rb);
+  int32_t* das = hc.out(arg_self, ib);
+  double *dgw = hc.out(grad_dist_world, n * rb), *dgs = hc.out(grad_dist_self, n * rb), *dcost = hc.out(cost, rb), *dgrad = hc.out(grad, n * rb);
+  return hc.run([&] { return collision_impl(fn, ctx, model, h, dq, rows, eps_world, eps_self, ddw, daw, dds, das, dgw, dgs, dcost, dgrad); });
 }
 
 }  // extern "C"
