@@ -306,9 +306,13 @@ int mp_fk_jac_vjp_f64(mp_ctx* ctx, const mp_model* model, int frame, const doubl
  *     n values is read or written.
  * A pivot d_j of the Cholesky factorisation of A that is not positive makes the Lambda-dependent outputs of that row NaN (Lambda, Jbar,
  * mu, p, tau); T, J and Jdqd of the row stay valid.  "Positive" is judged against rounding: d_j > 2^-46 A_jj (64 eps, what the
- * subtracted products and W leave in d_j; a matrix that fails has cond(A) above 1e13).  So a singular pose with damping = 0 gives NaN,
- * and so does one whose damping is too small to lift the pivot over that threshold (lambda^2 <= 2^-46 A_jj, lambda below about 1e-7
- * for A_jj of order 1): choose a damping that matters at the scale of A.  A row with a non-finite input comes back NaN in every output of that row only.
+ * subtracted products and W leave in d_j; a matrix that fails has cond(A) above 1e13).  The converse is not promised: rounding can
+ * lift the pivot of a singular A over the threshold, so with damping = 0 a singular or nearly singular pose (cond(A) > 1e13) gives
+ * either NaN or finite values of the size of 1 / (eps |A|) - check cond(A) or use a damping where that matters.  A damping too small
+ * to lift a pivot over the threshold (lambda^2 <= 2^-46 A_jj, lambda below about 1e-7 for A_jj of order 1) changes nothing: choose
+ * one that matters at the scale of A.  One case is decided without factorising: a task with more rows than the chain has joints
+ * (m > n) has rank(A) <= n < m at every pose, and with damping = 0 every row is NaN in Lambda, Jbar, mu, p and tau (T, J and Jdqd
+ * stay valid).  A row with a non-finite input comes back NaN in every output of that row only.
  * rows = 0 is a no-op.  The device forms are asynchronous (no synchronisation, no allocation: they may be captured into a launch graph);
  * the _host forms take their device memory from the context's pool; the _cpu twins are listed with the others below. */
 int mp_opspace_f64(mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* d_q, const double* d_qd,

@@ -20,8 +20,10 @@
 // A = W^T W + lambda^2 1 is factored by Cholesky too; M^-1 is never formed:  J M^-1 x = W^T (L^-1 x),  M^-1 J^T y = L^-T (W y),
 // J^T y = L (W y).  Hence the torque without ever reading J again:
 //   tau = L W f + tau0,   A f = a* - Jdot qd + W^T L^-1 (h - tau0)
-// A pivot of A that is not positive (to within MP_OS_PIVOT_EPS of its diagonal term: a singular pose with lambda = 0) makes the
-// Lambda-dependent outputs of the row NaN - T, J and Jdot qd stay valid; a non-finite input makes every output of the row NaN.
+// A pivot of A that is not positive (to within MP_OS_PIVOT_EPS of its diagonal term) makes the Lambda-dependent outputs of the row
+// NaN - T, J and Jdot qd stay valid; a non-finite input makes every output of the row NaN.  A task with more rows than the chain has
+// joints (m > N) has rank(A) <= N < m at every pose: with lambda = 0 its rows are NaN by that count alone, without factorising -
+// rounding noise lifts the last pivots of such an A over the threshold on part of the rows (mp_opspace_rank_deficient).
 #pragma once
 
 #include "mp_core.h"
@@ -79,6 +81,21 @@ MP_HD void mp_os_back(const double (&L)[NN][NN], double (&b)[NN]) {
 }
 
 MP_HD int mp_opspace_dim(int task) { return task == 0 ? 6 : 3; }
+// m > N without damping: A = J M^-1 J^T (m x m) is singular whatever the pose.  Wave-uniform: task and lam2 are launch arguments.
+template <int N>
+MP_HD bool mp_opspace_rank_deficient(int task, double lam2) {
+  return lam2 == 0.0 && mp_opspace_dim(task) > N;
+}
+// a row of COUNT NaNs to `ptr` when it is given
+template <int COUNT, typename OUT>
+MP_HD void mp_os_nan_out(const OUT& out, double* ptr) {
+  if (!ptr) return;
+  double o[COUNT];
+#pragma unroll
+  for (int k = 0; k < COUNT; ++k) o[k] = 0.0;
+  mp_poison_if(true, o);
+  out(ptr, o);
+}
 
 // FK, the Jacobian in `frame` with the rows of `task` first and the others zero (6 x N row-major), and Jdot qd in the same order
 template <int N, typename MT>
@@ -234,6 +251,14 @@ MP_HD void mp_opspace_row(const MT& M, const MpCall<double>& C, int frame, int t
     }
   }
   if (!Lam && !Jbar && !mu && !p) return;
+  if (mp_opspace_rank_deficient<N>(task, lam2)) {
+    if (full) {
+      mp_os_nan_out<36>(out, Lam); mp_os_nan_out<6 * N>(out, Jbar); mp_os_nan_out<6>(out, mu); mp_os_nan_out<6>(out, p);
+    } else {
+      mp_os_nan_out<9>(out, Lam); mp_os_nan_out<3 * N>(out, Jbar); mp_os_nan_out<3>(out, mu); mp_os_nan_out<3>(out, p);
+    }
+    return;
+  }
   double L[N][N], dg[N], A[6][6];
   const bool bad = !mp_opspace_factor<N>(M, task, lam2, js, L, dg, J, A) || poison;  // J holds W from here on
   if (mu || p) {
@@ -355,6 +380,12 @@ MP_HD void mp_opspace_row(const MT& M, const MpCall<double>& C, int frame, int t
 template <int N, typename MT>
 MP_HD void mp_opspace_torque_row(const MT& M, const MpCall<double>& C, int frame, int task, double lam2, const double (&a)[N],
                                  const double (&b)[N], const double (&acc)[6], const double (&t0)[N], bool poison, double (&tau)[N]) {
+  if (mp_opspace_rank_deficient<N>(task, lam2)) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) tau[i] = 0.0;
+    mp_poison_if(true, tau);
+    return;
+  }
   MpJointState<double, N> js;
   mp_joint_state<double, N>(M, a, js);
   double TT[16], W[6 * N], jd[6];

@@ -244,7 +244,9 @@ class ManipulatorDynamics(SerialManipulator):
         tool-origin velocity in space axes) for the rows of `task` ("full": [w; v], m = 6; "linear": v; "angular": w; m = 3):
         Lambda = (J M^-1 J^T + damping^2 1)^-1, Jbar = M^-1 J^T Lambda, mu = Lambda (J M^-1 c - Jdot qd), p = Lambda J M^-1 g.
         Shapes (4, 4), (m, n), (m,), (m, m), (n, m), (m,), (m,) for 1-D inputs, with a leading rows axis for 2-D ones (one g for all
-        rows).  A singular pose with damping = 0 gives NaN in Lambda, Jbar, mu and p of that row only."""
+        rows).  With damping = 0, a row whose factorisation of J M^-1 J^T meets a non-positive pivot is NaN in Lambda, Jbar, mu and p (that
+        row only), and so is every row of a task with more rows than the chain has joints; a nearly singular pose may also come back
+        finite and huge (include/manipula_hip.h)."""
         model = self._derivative_model("operational_space_dynamics")
         one = np.ndim(thetalist) == 1
         q, qd = (np.atleast_2d(np.asarray(a, dtype=np.float64)) for a in (thetalist, dthetalist))

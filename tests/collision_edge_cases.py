@@ -94,8 +94,14 @@ SEEDS = {"ur5": 7, "panda": 7, "xarm6": 7, "chain3": 7}
 def make_edge_case(name, edges=EDGES):
     """{"cm", "S_list", "qa", "qb" (edges, n)} by the recipe of the module's docstring."""
     cm, S_list, lim = make_model(name)
+    qa, qb = draw_edges(cm, S_list, lim, SEEDS[name], edges)
+    return {"cm": cm, "S_list": S_list, "qa": qa, "qb": qb, "name": name}
+
+
+def draw_edges(cm, S_list, lim, seed, edges):
+    """qa, qb (edges, n) of the recipe for any sphere model (chain_cases.py draws its chains' edges here too)."""
     n = lim.shape[0]
-    rng = np.random.default_rng(SEEDS[name])
+    rng = np.random.default_rng(seed)
     lo, hi = np.clip(lim[:, 0], -3, 3), np.clip(lim[:, 1], -3, 3)
     low = rng.random(edges) < 0.1  # q_a at or below the margin
     model = Model(S_list, cm)
@@ -114,7 +120,7 @@ def make_edge_case(name, edges=EDGES):
     u /= np.linalg.norm(u, axis=1, keepdims=True)
     step = np.asarray(S_CYCLE)[np.arange(edges) % len(S_CYCLE)][:, None] * u
     step[:, ~model.revolute] *= 0.2
-    return {"cm": cm, "S_list": S_list, "qa": np.ascontiguousarray(qa), "qb": np.ascontiguousarray(qa + step), "name": name}
+    return np.ascontiguousarray(qa), np.ascontiguousarray(qa + step)
 
 
 # ------------------------------------------------------------------------------------------------ oracle

@@ -1,0 +1,248 @@
+"""The CPU twins against the independent oracles on chain_cases.chain(n), n = 1..8 - every joint count, prismatic joints included - for
+the families whose host tests only know the four arms and all-revolute chains.  No GPU.
+
+Each test first re-measures the oracle's own float64-against-longdouble difference on the new case and holds it to twice the constant
+the family's bound was sized from (as test_oracle_float64_error_is_what_the_bound_was_sized_from does), then applies the family's
+existing rule with its existing bound."""
+import numpy as np
+import pytest
+
+import chain_cases as ch
+import collision_cases as cc
+import opspace_cases as oc
+from manipulapy_amd import _hip
+
+
+def test_chains_are_the_documented_ones():
+    for n in ch.NS:
+        tb, prismatic, lim, model = ch.chain(n)
+        assert model.n == n and "".join("01"[int(p)] for p in prismatic) == ch.PRISMATIC[n]
+        assert (lim[prismatic] == [-0.4, 0.4]).all() and (lim[~prismatic] == [-2.5, 2.5]).all()
+    assert sum(ch.chain(n)[1].any() for n in ch.NS) == 3
+
+
+# ------------------------------------------------------------------------------------------------ operational space
+@pytest.mark.parametrize("n", ch.NS)
+def test_opspace_twin_matches_the_dense_oracle(n):
+    """T, J, Jdot qd under f64_rule, the Lambda-dependent outputs under kappa_rule(fixture=True), every frame x task at damping 0.1 (no
+    row may be left out) and at damping 0 where chain_cases.opspace_damping0_is_run says so; Jdot qd also against the central
+    difference of the twin's own Jacobian, as test_opspace_host.py holds it."""
+    model = ch.chain(n)[3]
+    q, qd = ch.opspace_inputs(n)
+    h = 1e-6
+    worst, kmed, ran0, out0 = 0.0, 0.0, [], 0.0
+    for frame in oc.FRAMES:
+        for task in oc.TASKS:
+            for damping in (ch.OPSPACE_DAMPING, 0.0):
+                want = ch.opspace_oracle(n, frame, task, damping)
+                kappa = want["kappa"]
+                what = f"n={n} {frame} {task} damping {damping}"
+                if damping == 0.0 and not ch.opspace_damping0_is_run(n, task, kappa):
+                    continue
+                if damping == 0.0:
+                    ran0.append((frame, task))
+                    out0 = max(out0, oc.left_out_share(kappa))
+                else:
+                    assert oc.left_out_share(kappa) == 0.0, f"{what}: rows with cond(A) > 1e10"
+                    kmed = max(kmed, float(np.median(kappa)))
+                o = _hip.cpu_opspace(model, q, qd, ch.G9, frame, task, damping)
+                oc.f64_rule(o["T"], want["T"], what + " T")
+                oc.f64_rule(o["J"], want["J"], what + " J")
+                oc.f64_rule(o["Jdot_qd"], want["Jdot_qd"], what + " Jdot_qd")
+                for name in oc.LAM:
+                    worst = max(worst, oc.kappa_rule(o[name], want[name], kappa, f"{what} {name}", fixture=True))
+            Jp = _hip.cpu_opspace(model, q + h * qd, qd, None, frame, task, 0.0, want=("J",))["J"]
+            Jm = _hip.cpu_opspace(model, q - h * qd, qd, None, frame, task, 0.0, want=("J",))["J"]
+            cd = np.einsum("rij,rj->ri", (Jp - Jm) / (2 * h), qd)
+            got = _hip.cpu_opspace(model, q, qd, None, frame, task, 0.0, want=("Jdot_qd",))["Jdot_qd"]
+            scale = np.maximum(1.0, np.abs(cd).max(axis=1, keepdims=True))
+            assert (np.abs(got - cd) <= 1e-7 * scale).all(), f"n={n} {frame} {task}: Jdot qd against the central difference"
+    print(f"\nopspace n={n}: damping {ch.OPSPACE_DAMPING}: rows left out 0, largest median cond(A) {kmed:.3g}; worst error / bound {worst:.3g}; "
+          f"damping 0 run on {ran0}, rows left out {out0:.2%} at most")
+    assert tuple(ran0) == ch.opspace_damping0_runs(n), "chain_cases.OPSPACE_DAMPING0 no longer describes the oracle"
+
+
+@pytest.mark.parametrize("n", ch.NS)
+def test_opspace_task_wider_than_the_chain_is_nan_without_damping(n):
+    """m > n: A = J M^-1 J^T has rank <= n < m at every pose.  With damping 0 the Lambda-dependent outputs and the torque of every row
+    are NaN - decided from (m, n), not by a pivot that rounding noise may lift over the threshold - and T, J, Jdot qd stay finite.
+    (Before the structural test this assertion failed on the twin: finite Lambda, Jbar, mu and p on 19.4 % of the 2000 rows for n = 2,
+    space / linear - entries of the size of 1 / (eps |A|).)"""
+    model = ch.chain(n)[3]
+    q, qd = ch.opspace_inputs(n)
+    rng = np.random.default_rng(9000 + n)
+    checked = 0
+    for task in oc.TASKS:
+        m = ch.opspace_dim(task)
+        if m <= n:
+            continue
+        for frame in oc.FRAMES:
+            o = _hip.cpu_opspace(model, q, qd, ch.G9, frame, task, 0.0)
+            tau = _hip.cpu_opspace_torque(model, q, qd, rng.normal(size=(len(q), m)), ch.G9, None, frame, task, 0.0)
+            finite = {k: float(np.isfinite(o[k]).reshape(len(q), -1).any(axis=1).mean()) for k in oc.LAM}
+            assert all(np.isnan(o[k]).all() for k in oc.LAM) and np.isnan(tau).all(), f"n={n} {frame} {task}: rows with finite values {finite}"
+            assert all(np.isfinite(o[k]).all() for k in oc.KIN), f"n={n} {frame} {task}"
+            o = _hip.cpu_opspace(model, q[:50], qd[:50], ch.G9, frame, task, ch.OPSPACE_DAMPING)     # damping makes A regular again
+            assert all(np.isfinite(v).all() for v in o.values())
+            checked += 1
+    assert checked == (9 if n < 3 else 3 if n < 6 else 0)
+
+
+@pytest.mark.parametrize("n", ch.NS)
+def test_opspace_closed_loop_identity(n):
+    """tau -> the existing forward dynamics -> J qdd + Jdot qd = a*, wherever the damping-0 comparison is run; with a null-space torque
+    of the size of a* where the task leaves a null space (n > m)."""
+    model = ch.chain(n)[3]
+    q, qd = ch.opspace_inputs(n)
+    rng = np.random.default_rng(9100 + n)
+    worst, ran = 0.0, 0
+    for frame in oc.FRAMES:
+        for task in oc.TASKS:
+            kappa = ch.opspace_oracle(n, frame, task, 0.0)["kappa"]
+            if not ch.opspace_damping0_is_run(n, task, kappa):
+                continue
+            m = ch.opspace_dim(task)
+            o = _hip.cpu_opspace(model, q, qd, ch.G9, frame, task, 0.0, want=("J", "Jdot_qd"))
+            acc = rng.normal(size=(len(q), m))
+            for t0 in (None,) + ((rng.normal(size=q.shape),) if n > m else ()):
+                tau = _hip.cpu_opspace_torque(model, q, qd, acc, ch.G9, t0, frame, task, 0.0)
+                qdd = _hip.cpu_forward_dynamics(model, q, qd, tau, ch.G9, None)
+                got = np.einsum("rij,rj->ri", o["J"], qdd) + o["Jdot_qd"]
+                worst = max(worst, oc.kappa_rule(got, acc, kappa, f"n={n} {frame} {task} tau0={t0 is not None}"))
+                ran += 1
+    assert ran > 0 or n < 3
+    print(f"\nopspace n={n}: closed loop on {ran} combinations, worst error / bound {worst:.3g}")
+
+
+# ------------------------------------------------------------------------------------------------ collision
+@pytest.mark.parametrize("n", ch.NS)
+def test_collision_twin_matches_the_oracle(n):
+    case = ch.collision_case(n)
+    cm = case["cm"]
+    r64, rld = cc.oracle_of(case), cc.oracle_of(case, dt=np.longdouble)
+    own = max(cc.relative_error(r64[k], rld[k]) for k in cc.FLOAT_OUTPUTS)
+    print(f"\ncollision n={n}: {len(cm.links)} spheres, {len(cm.pairs)} pairs, spacing {ch.collision_model(n)[2]}; oracle float64 against "
+          f"longdouble {own:.3g}")
+    assert own <= 2 * cc.MEASURED_ORACLE
+    assert len(cm.links) <= _hip.MP_COLLISION_MAX_SPHERES and (len(cm.pairs) == 0) == (n == 1)
+    scale = {key: cc._magnitude(r64[f"dist_{key}"]) or 1.0 for key in ("world", "self")}
+    assert all(int((r64[f"gap_{key}"] <= cc.BOUND * scale[key]).sum()) == 0 for key in ("world", "self")), "pick another row seed"
+    got = _hip.cpu_collision(cm.model, cm.handle, case["q"], cc.EPS_WORLD, cc.EPS_SELF)
+    worst = cc.check_against_oracle(got, r64, f"collision n={n} twin", show=False)
+    print(f"collision n={n}: twin against oracle, worst {max(worst.values()) * cc.BOUND:.3g} (bound {cc.BOUND:.3g})")
+    assert (r64["dist_world"] < 0).any() and (r64["dist_world"] > 0).any()   # both sides of the hinge
+
+
+# ------------------------------------------------------------------------------------------------ collision edges
+@pytest.mark.parametrize("n", ch.NS)
+def test_collision_edges_twin_matches_the_oracle(n):
+    """The case conditions of collision_edge_cases.py's docstring, per chain, then the module's rule.  n = 1 has no pairs and the pairs
+    of n = 2 never come near: their blocked edges can only have world witnesses (chain_cases.EDGE_WORLD_WITNESS_ONLY says why)."""
+    import collision_edge_cases as ec
+
+    case = ch.edge_case(n)
+    cm = case["cm"]
+    ref, ref_long = ch.edge_oracle(n), ch.edge_oracle(n, long=True)
+    st, t = ref["status"], ref["t"]
+    frac = {"free": (st == ec.FREE).mean(), "blocked_later": ((st == ec.BLOCKED) & (t > 0)).mean(),
+            "blocked_at_0": ((st == ec.BLOCKED) & (t == 0)).mean(), "undecided": (st == ec.UNDECIDED).mean()}
+    dt = float(np.abs(ref["t"] - ref_long["t"]).max())
+    fin = np.isfinite(ref_long["clearance"])
+    dc = float(np.abs(ref["clearance"][fin] - ref_long["clearance"][fin]).max())
+    print(f"\nedges n={n}: {len(cm.links)} spheres, {len(cm.pairs)} pairs; {frac}; steps max {ref['steps'].max()}; smallest gap "
+          f"{ref['gap'].min():.3g}; oracle float64 against longdouble: t {dt:.3g}, clearance {dc:.3g}")
+    assert frac["free"] >= 0.25 and frac["blocked_later"] >= 0.15 and frac["blocked_at_0"] >= 0.05 and frac["undecided"] <= 0.01
+    kinds = set(ref["witness"][st == ec.BLOCKED][:, 0].tolist())
+    if n in ch.EDGE_WORLD_WITNESS_ONLY:
+        assert (len(cm.pairs) == 0) == (n == 1) and kinds == {0}
+    else:
+        assert kinds == {0, 1}, f"witness kinds among the blocked: {kinds}"
+    assert np.array_equal(st, ref_long["status"]) and np.array_equal(ref["steps"], ref_long["steps"])
+    assert ref["gap"].min() >= ec.GAP and ref_long["gap"].min() >= ec.GAP
+    assert dt <= 2 * ec.MEASURED_T and dc <= 2 * ec.MEASURED_CLEARANCE
+    got = _hip.cpu_collision_edges(cm.model, cm.handle, case["qa"], case["qb"], ec.MARGIN, ec.TOL, ec.MAX_STEPS)
+    fig = ec.check_against_oracle(got, ref, f"edges n={n} twin", show=False)
+    print(f"edges n={n}: twin against oracle: t {fig['t']:.3g} (bound {ec.T_BOUND:.3g}), clearance {fig['clearance']:.3g} "
+          f"(bound {ec.CLEARANCE_BOUND:.3g})")
+
+
+# ------------------------------------------------------------------------------------------------ iLQR
+@pytest.mark.parametrize("n", ch.NS)
+def test_ilqr_twin_matches_the_oracle(n):
+    import ilqr_cases as ic
+
+    model, lim, case = ch.ilqr_case(n)
+    pos, vel, J0, blocks = ic.nominal_and_blocks(model, case)
+    w = (case["wq"], case["wr"], case["wf"])
+    B = len(J0)
+    for reg in (1e-6, 0.0):
+        o64 = ic.oracle_batch(lim, case, pos, vel, blocks, reg)
+        old = ic.oracle_batch(lim, case, pos, vel, blocks, reg, np.longdouble)
+        own = max(ic.rel_err(a, b).max() for a, b in zip(o64[:3], old[:3]))
+        assert own <= 2 * ic.MEASURED_F64
+        masked = o64[3]                     # the clip masks engage where make_case puts a joint at its limit: trajectories 0 and 1
+        assert np.array_equal(np.flatnonzero(masked), np.arange(min(n - 1, 2))), f"n={n}: masked trajectories {np.flatnonzero(masked)}"
+        K, k, dV, status = _hip.cpu_ilqr_backward(model, pos, vel, case["taumat"], case["xref"], *w, reg, ic.G9, ic.DT)
+        assert (status == 0).all() and not K[:, 0].any() and not k[:, 0].any()
+        worst = max(ic.within_bound(K, o64[0], "K"), ic.within_bound(k, o64[1], "k"), ic.within_bound(dV, o64[2], "dV"))
+        print(f"\nilqr n={n} reg {reg:g}: oracle float64 against longdouble {own:.3e}; twin against oracle {worst:.3e} (bound {ic.BOUND:.1e})")
+    # rule (c), at reg = 0: the first-order model against the true dynamics
+    a = ic.MODEL_ALPHA
+    roll = lambda K_, k_, alpha, rows=True: _hip.cpu_ilqr_rollout(model, case["theta0"], case["dtheta0"], case["taumat"], pos, vel, K_, k_,  # noqa: E731
+                                                                  alpha, case["xref"], *w, ic.G9, ic.DT, rows)
+    Ja = roll(K, k, np.full((1, B), a), rows=False)[0][0]
+    res = np.abs((Ja - J0) - (a * dV[:, 0] + a * a * dV[:, 1])) / np.abs(a * dV[:, 0])
+    print(f"ilqr n={n}: first-order model residual {res.max():.3e} of |alpha dV1| (bound {ic.MODEL_C:.1e})")
+    assert (dV[:, 0] < 0).all() and (dV[:, 1] > 0).all() and (res <= ic.MODEL_C).all()
+    # the open loop is the existing forward-dynamics roll-out
+    N = case["taumat"].shape[1]
+    cost, p, v, t = roll(np.zeros((B, N, n, 2 * n)), np.zeros((B, N, n)), np.zeros((1, B)))
+    assert np.array_equal(p[0], pos) and np.array_equal(v[0], vel) and np.array_equal(t[0], case["taumat"]) and np.array_equal(cost[0], J0)
+    rp, rv, _ = _hip.cpu_fd_trajectory(model, case["theta0"], case["dtheta0"], case["taumat"], ic.G9, None, ic.DT, 1, dtype=np.float64)
+    for got, want in ((p[0], rp), (v[0], rv)):
+        got = got.astype(np.float32)
+        assert (np.abs(got - want) <= np.spacing(np.maximum(np.abs(got), np.abs(want)))).all()
+
+
+# ------------------------------------------------------------------------------------------------ TOPP-RA
+@pytest.mark.parametrize("N", (33, 3))
+@pytest.mark.parametrize("n", ch.NS)
+def test_toppra_twin_matches_the_oracle(n, N):
+    import toppra_cases as tc
+
+    model, vlim, tlim, (q, dq, ddq) = ch.toppra_case(n, 6, N)
+    co = tc.oracle_coeffs(model, q, dq, ddq, vlim)
+    ora = tc.oracle_batch(*co, dq, ddq, tlim)
+    assert (ora["status"] == 0).all(), f"an infeasible draw: status {ora['status']}"
+    got = _hip.cpu_path_dynamics(model, q.reshape(-1, n), dq.reshape(-1, n), ddq.reshape(-1, n), vlim, tc.G9)
+    for g_, w_, what in zip(got, co, ("a", "b", "c", "xbar")):                # (b)
+        tc.f64_rule(g_, w_, f"n={n} {what}")
+    acc = np.maximum(np.abs(ora["accelerations"][:, :-1]).max(axis=(0, 1)) / 3.0, 1e-3)
+    for alim in (None, acc):
+        what = f"toppra n={n} N {N} acc {alim is not None}"
+        want = ora if alim is None else tc.oracle_batch(*co, dq, ddq, tlim, alim)
+        old = tc.oracle_batch(*co, dq, ddq, tlim, alim, dtype=np.longdouble)
+        assert (want["status"] == 0).all() and (old["status"] == 0).all()
+        assert ch.toppra_not_stalling(want).all(), f"{what}: a path stalls inside (sd2 {want['sd2'][:, 1:-1].min(axis=1)})"
+        xs = np.abs(old["sd2"]).max(axis=1)
+        figs = {"x": np.abs(want["sd2"] - old["sd2"]).max(axis=1) / xs,
+                "K": np.abs(want["controllable"] - old["controllable"]).reshape(len(xs), -1).max(axis=1) / xs,
+                "u": tc.rel_err(want["sdd"], old["sdd"]), "t": tc.rel_err(want["time"], old["time"])}
+        print(f"\n{what}: oracle float64 against longdouble " + ", ".join(f"{k} {float(np.max(v)):.3e}" for k, v in figs.items()))
+        for key, v in figs.items():
+            assert float(np.max(v)) <= 2 * {"x": tc.MEASURED_X, "K": tc.MEASURED_X, "u": tc.MEASURED_U, "t": tc.MEASURED_T}[key], key
+        sweep = _hip.cpu_toppra_sweep(*co, dq, ddq, tlim, alim)               # (a)
+        tc.rule_a(sweep, want, f"{what} sweep")
+        for key in ("velocities", "accelerations", "torques"):
+            tc.f64_rule(sweep[key], want[key], key)
+        full = _hip.cpu_toppra(model, q, dq, ddq, vlim, tlim, alim, g=tc.G9)  # (c)
+        assert (full["status"] == 0).all()
+        measured = ch.toppra_measured_excess(n)
+        own_excess, own_activity = tc.excess_and_activity(model, q, dq, ddq, want, vlim, tlim, alim, co[3])
+        excess, activity = tc.excess_and_activity(model, q, dq, ddq, full, vlim, tlim, alim, co[3])
+        print(f"{what}: limit excess: oracle {own_excess:.3e}, twin {excess:.3e} (slack {10 * measured:.1e}); smallest activity: oracle "
+              f"{own_activity:.17g}, twin {activity:.17g}")
+        assert own_excess <= 2 * measured and own_activity >= 1 - 2 * measured
+        assert excess <= 10 * measured and activity >= 1.0 - 10 * measured          # rule (c), toppra_cases.rule_c with this chain's constant
+        tc.f64_rule(full["sd2"], want["sd2"], "sd2 end to end")
+        tc.f64_rule(full["duration"], want["duration"], "duration end to end")

@@ -12,7 +12,7 @@ from conftest import golden_path
 from manipulapy_amd import _hip, registry
 from manipulapy_amd.control import ManipulatorController
 from opspace_cases import (FRAMES, KIN, LAM, ROBOTS, TASKS, f64_rule, kappa_of, kappa_rule, left_out_share, tight)
-from test_random_robots import random_robot
+from test_random_robots import FLAVOURS, random_robot
 
 MP_ERR_INVALID, MP_ERR_UNSUPPORTED = 1, 4  # include/manipula_hip.h
 ROWS = slice(4, 25)  # the seeded rows of dynamics_<robot>.npz; rows 0..3 are the zero and joint-limit poses (singular)
@@ -67,9 +67,10 @@ def test_jdot_qd_on_random_chains_with_prismatic_joints():
     for seed in range(8):
         rng = np.random.default_rng(3100 + seed)
         n = seed + 1
-        tb = random_robot(rng, n, ("general",))
+        tb = random_robot(rng, n, FLAVOURS[seed % len(FLAVOURS)])
         model = _hip.HipModel(tb.S, tb.Mcom, tb.G, tb.M_ee, tb.joint_limits)
         q, qd = rng.uniform(-2, 2, (5, n)), rng.normal(size=(5, n))
+        q[:, np.abs(tb.S[:3]).sum(axis=0) == 0] *= 0.1  # prismatic joints: decimetres, not radians
         h = 1e-6
         for frame in FRAMES:
             o = _hip.cpu_opspace(model, q, qd, None, frame, "full", 0.0, want=("J", "Jdot_qd"))
