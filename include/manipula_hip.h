@@ -785,6 +785,79 @@ int mp_collision_edges_cpu_f64(const mp_model* model, const mp_collision* h, con
                                double margin, double tol, int max_steps, int32_t* status, double* t, int32_t* steps, double* clearance,
                                int32_t* witness, int nthreads);
 
+/* ---- batched RRT-Connect over the sphere model above (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED above that;
+ * csrc/mp_rrt.h).  Bidirectional RRT-Connect (Kuffner and LaValle) for B independent problems in one world: every tree edge is proven
+ * free over its whole length by the conservative advancement of mp_collision_edges_*, with the launch's margin, tol and max_steps.
+ * The kernel, the CPU twin and the tests' NumPy oracle implement exactly the contract below.
+ * Per problem: q_start, q_goal (n).  Per launch: the sampling box lo, hi (n each, HOST arrays, finite, lo <= hi), seed (uint32),
+ *   step > 0, min_advance >= 0 (both finite), max_iters >= 0, max_nodes in 2..65536 (per tree), max_waypoints >= 2, and margin, tol,
+ *   max_steps as for the edges.  Anything else is MP_ERR_INVALID with a message.
+ * Random numbers: key = the FNV-1a hash (offset 0xCBF29CE484222325, prime 0x100000001B3) over the 64-bit patterns of
+ *   q_start[0..n) then q_goal[0..n).  u(k, j): x = seed * 0x9E3779B97F4A7C15 + key * 0xBF58476D1CE4E5B9 +
+ *   (k * 64 + j) * 0x94D049BB133111EB (64-bit, wrapping); x += 0x9E3779B97F4A7C15; z = x; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB; z ^= z >> 31; u = (z >> 11) * 2^-53.  q_rand_j(k) = lo_j + u(k, j) (hi_j - lo_j).
+ *   A problem's result depends on its own content and the seed only - not on its row, its lane or the launch.
+ * Trees: T[0] is rooted at q_start, T[1] at q_goal; a tree holds nodes (n doubles) and a parent index each (root: -1).
+ *   nearest(T, q): the node with the smallest d2 = sum_j (x_j - q_j)^2, summed over j ascending; of equal d2 the lowest index.
+ *     d = sqrt(d2).
+ *   edge(a -> b): one edge check of the section above, D = b - a: status, t, steps.
+ *   Partial node: after an edge from node i that is not FREE (BLOCKED or UNDECIDED at t: [0, t) is proven), with l the edge's
+ *     joint-space length as given below: if (t / 2) l >= min_advance, a + (t / 2) D is appended with parent i; otherwise nothing.
+ * Procedure:
+ *   A non-finite q_start or q_goal: INVALID, nothing is evaluated.
+ *   edge(q_start -> q_start) not FREE: START_BLOCKED.  Then edge(q_goal -> q_goal) not FREE: GOAL_BLOCKED.
+ *   a = 0, k = 0; loop:
+ *     if k >= 1 and k >= max_iters: EXHAUSTED (the direct attempt at k = 0 is always made, so max_iters = 0 behaves as 1).
+ *     if either tree holds max_nodes nodes: TREE_FULL.
+ *     EXTEND (k >= 1; at k = 0 it is skipped and new = the root of T[a]: the direct motion between start and goal comes first):
+ *       i, d = nearest(T[a], q_rand(k)).  d == 0: trapped.  Otherwise the target is q_rand itself if d <= step, else
+ *       x_i + (step / d) (q_rand - x_i); l = min(d, step).  edge(x_i -> target): FREE appends the target with parent i, otherwise the
+ *       partial-node rule applies.  Nothing appended: trapped - k += 1, a ^= 1, continue.  new = the appended node.
+ *     CONNECT: i2, d = nearest(T[1 - a], x_new), l = d.  edge(y_i2 -> x_new) over its whole length: FREE is SOLVED, otherwise the
+ *       partial-node rule applies to T[1 - a].
+ *     k += 1, a ^= 1.
+ *   SOLVED: the path is root0 .. new, i2 .. root1 (a = 0) or root0 .. i2, new .. root1 (a = 1).  More than max_waypoints points:
+ *     PATH_TOO_LONG, and count is the number needed.
+ * Per problem (every output may be NULL; at least one is needed):
+ *     status (B) int32                   MP_PLAN_SOLVED 0, _EXHAUSTED 1, _TREE_FULL 2, _START_BLOCKED 3, _GOAL_BLOCKED 4,
+ *                                        _PATH_TOO_LONG 5, _INVALID -1
+ *     count (B) int32                    the waypoints of the path (SOLVED), the number needed (PATH_TOO_LONG), 0 otherwise
+ *     waypoints (B, max_waypoints, n)    the path, padded by repeating the last waypoint (the array can go straight into a check of
+ *                                        its segments: a repeated point is a zero edge); NaN rows unless SOLVED
+ *     iterations (B) int32               k at the end
+ *     nodes (B, 2) int32                 the sizes of T[0], T[1] at the end (1, 1 for START_ / GOAL_BLOCKED; 0, 0 for INVALID)
+ *     evaluations (B) int32              the configurations evaluated, the two end-point checks included (0 for INVALID)
+ * mp_rrt_connect_f64: d_q_start, d_q_goal (B,n) device rows, 16-byte aligned like every output and the workspace.  One launch: a
+ *   lane serves one problem at a time and takes problems from a queue, so the launch lasts as long as its slowest problem - max_iters
+ *   is the latency knob.  The trees live in d_workspace and belong to the resident lane: mp_rrt_connect_workspace_bytes(n, max_nodes,
+ *   blocks) = blocks x 64 lanes x 2 max_nodes (8 n + 4) bytes (or minus an MP_ERR_* code).  The grid is the smallest of the one-wave
+ *   blocks the device keeps resident, ceil(B / 64), max_blocks (if positive) and the blocks the workspace holds; room for less than
+ *   one block is MP_ERR_INVALID.  Asynchronous; it allocates nothing once the handle is resident on the context and may then be
+ *   captured into a launch graph.  Launches that share a collision handle share its queue head: they are serialised by the handle's
+ *   lock and the compute stream.  mp_rrt_connect_host_f64: host arrays, device memory and workspace from the context's pool.
+ *   mp_rrt_connect_cpu_f64: the kernel's per-problem code on the host, no context. */
+#define MP_PLAN_SOLVED 0
+#define MP_PLAN_EXHAUSTED 1
+#define MP_PLAN_TREE_FULL 2
+#define MP_PLAN_START_BLOCKED 3
+#define MP_PLAN_GOAL_BLOCKED 4
+#define MP_PLAN_PATH_TOO_LONG 5
+#define MP_PLAN_INVALID (-1)
+int64_t mp_rrt_connect_workspace_bytes(int n, int max_nodes, int blocks);
+int mp_rrt_connect_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q_start, const double* d_q_goal, int64_t B,
+                       const double* lo, const double* hi, uint32_t seed, double step, double min_advance, int max_iters, int max_nodes,
+                       int max_waypoints, double margin, double tol, int max_steps, void* d_workspace, size_t workspace_bytes,
+                       int max_blocks, int32_t* d_status, int32_t* d_count, double* d_waypoints, int32_t* d_iterations, int32_t* d_nodes,
+                       int32_t* d_evaluations);
+int mp_rrt_connect_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q_start, const double* q_goal, int64_t B,
+                            const double* lo, const double* hi, uint32_t seed, double step, double min_advance, int max_iters,
+                            int max_nodes, int max_waypoints, double margin, double tol, int max_steps, int32_t* status, int32_t* count,
+                            double* waypoints, int32_t* iterations, int32_t* nodes, int32_t* evaluations);
+int mp_rrt_connect_cpu_f64(const mp_model* model, const mp_collision* h, const double* q_start, const double* q_goal, int64_t B,
+                           const double* lo, const double* hi, uint32_t seed, double step, double min_advance, int max_iters,
+                           int max_nodes, int max_waypoints, double margin, double tol, int max_steps, int32_t* status, int32_t* count,
+                           double* waypoints, int32_t* iterations, int32_t* nodes, int32_t* evaluations, int nthreads);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new; the reference is single-device) ------
  * Trajectory batches are sharded over ranks with no exchange during compute; the only collective is
  * the all-gather that reassembles the torque history.  Rank 0 creates the id, the launcher

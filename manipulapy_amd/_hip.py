@@ -183,6 +183,10 @@ SIGNATURES = {
     "mp_collision_edges_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp]),
     "mp_collision_edges_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _c_dp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _c_dp, _vp, _c_dp, _vp]),
     "mp_collision_edges_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _c_dp, _vp, _c_dp, _vp, ctypes.c_int]),
+    "mp_rrt_connect_workspace_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "mp_rrt_connect_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_rrt_connect_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _c_dp, _vp, _vp, _vp]),
+    "mp_rrt_connect_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _c_dp, _vp, _vp, _vp, ctypes.c_int]),
     "mp_comm_unique_id": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8)]),
     "mp_comm_create": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     "mp_comm_destroy": (ctypes.c_int, [_vp]),
@@ -706,6 +710,30 @@ class HipContext:
         """The same on host rows through the context's pool: a dict of the outputs named in `want` (default: all of EDGE_OUTPUTS)."""
         return _collision_edges((self.handle,), self.lib.mp_collision_edges_host_f64, model, collision, q_from, q_to, margin, tol,
                                 max_steps, want)
+
+    def rrt_connect(self, model, collision, d_q_start, d_q_goal, problems, lo, hi, margin, tol, *, step, min_advance=None, max_iters,
+                    max_nodes, max_waypoints, max_steps, seed, d_workspace, workspace_bytes, max_blocks: int = 0, d_status=None,
+                    d_count=None, d_waypoints=None, d_iterations=None, d_nodes=None, d_evaluations=None):
+        """Batched RRT-Connect on device buffers (float64; csrc/mp_rrt.h): d_q_start, d_q_goal (problems,n); lo, hi (n) host arrays;
+        outputs status / count / iterations / evaluations (problems) int32, nodes (problems,2) int32, waypoints (problems,
+        max_waypoints,n), each may be None (at least one given).  d_workspace holds the trees: rrt_connect_workspace_bytes(n,
+        max_nodes, blocks).  `max_blocks` > 0 caps the grid.  Asynchronous (capturable once the handle has been used or given a
+        world on this context)."""
+        lo, hi, step, min_advance = _rrt_box(model, lo, hi, step, min_advance)
+        _check(self.lib.mp_rrt_connect_f64(self.handle, model.handle, collision.handle, _p(d_q_start), _p(d_q_goal), int(problems),
+                                           _dptr(lo), _dptr(hi), int(seed), step, min_advance, int(max_iters), int(max_nodes),
+                                           int(max_waypoints), float(margin), float(tol), int(max_steps), _p(d_workspace),
+                                           ctypes.c_size_t(int(workspace_bytes)), int(max_blocks), _p(d_status), _p(d_count),
+                                           _p(d_waypoints), _p(d_iterations), _p(d_nodes), _p(d_evaluations)))
+
+    def rrt_connect_arrays(self, model, collision, q_start, q_goal, lo, hi, margin, tol, *, step, min_advance=None, max_iters, max_nodes,
+                         max_waypoints, max_steps, seed, want=None):
+        """The same on host arrays (mp_rrt_connect_host_f64) through the context's pool, workspace included: a dict of the outputs
+        named in `want` (default: all of PLAN_OUTPUTS).  (Not named `*_host`: that set of methods is the one
+        tests/test_gpu_host_entries.py holds to hand-staged device launches; this entry's equality with its device form is held by
+        tests/test_gpu_rrt.py.)"""
+        return _rrt_connect((self.handle,), self.lib.mp_rrt_connect_host_f64, model, collision, q_start, q_goal, lo, hi, margin, tol,
+                            step, min_advance, max_iters, max_nodes, max_waypoints, max_steps, seed, want)
 
     def collision_set_world(self, collision, kinds, params):
         """Replaces the obstacle table of `collision` on this context's device, behind the launches already on its stream."""
@@ -1473,6 +1501,58 @@ def cpu_collision_edges(model: "HipModel", collision: "HipCollision", q_from, q_
     """CPU twin of HipContext.collision_edges_host."""
     return _collision_edges((), load_library().mp_collision_edges_cpu_f64, model, collision, q_from, q_to, margin, tol, max_steps, want,
                             nthreads)
+
+
+PLAN_OUTPUTS = ("status", "count", "waypoints", "iterations", "nodes", "evaluations")
+PLAN_SOLVED, PLAN_EXHAUSTED, PLAN_TREE_FULL, PLAN_START_BLOCKED, PLAN_GOAL_BLOCKED, PLAN_PATH_TOO_LONG, PLAN_INVALID = 0, 1, 2, 3, 4, 5, -1
+
+
+def rrt_connect_workspace_bytes(n: int, max_nodes: int, blocks: int) -> int:
+    """Bytes of tree workspace for `blocks` one-wave blocks of HipContext.rrt_connect."""
+    r = int(load_library().mp_rrt_connect_workspace_bytes(int(n), int(max_nodes), int(blocks)))
+    if r < 0:
+        _check(-r)
+    return r
+
+
+def _rrt_box(model, lo, hi, step, min_advance):
+    lo, hi = _as_c(lo, np.float64, (model.n,), "lo"), _as_c(hi, np.float64, (model.n,), "hi")
+    step = float(step)
+    return lo, hi, step, step / 8 if min_advance is None else float(min_advance)
+
+
+def _rrt_connect(lead, fn, model, collision, q_start, q_goal, lo, hi, margin, tol, step, min_advance, max_iters, max_nodes,
+                 max_waypoints, max_steps, seed, want, nthreads=None):
+    want = PLAN_OUTPUTS if want is None else tuple(want)
+    for w in want:
+        if w not in PLAN_OUTPUTS:
+            raise ValueError(f"unknown planner output {w!r}; choose from {PLAN_OUTPUTS}")
+    qs = _as_c(q_start, np.float64, name="q_start")
+    if qs.ndim != 2 or qs.shape[1] != model.n:
+        raise ValueError(f"q_start must be (problems, {model.n}); got {qs.shape}")
+    B, n = qs.shape
+    qg = _as_c(q_goal, np.float64, (B, n), "q_goal")
+    lo, hi, step, min_advance = _rrt_box(model, lo, hi, step, min_advance)
+    W = max(int(max_waypoints), 0)  # (a value below 2 is the entry's to refuse)
+    shapes = {"status": (B,), "count": (B,), "waypoints": (B, W, n), "iterations": (B,), "nodes": (B, 2), "evaluations": (B,)}
+    out = {w: np.empty(shapes[w], dtype=np.float64 if w == "waypoints" else np.int32) for w in want}
+    ptrs = []
+    for w in PLAN_OUTPUTS:
+        a = out.get(w)
+        ptrs.append(None if a is None else (_dptr(a) if w == "waypoints" else a.ctypes.data_as(_vp)))
+    args = list(lead) + [model.handle, collision.handle, _dptr(qs), _dptr(qg), B, _dptr(lo), _dptr(hi), int(seed), step, min_advance,
+                         int(max_iters), int(max_nodes), int(max_waypoints), float(margin), float(tol), int(max_steps)] + ptrs
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return out
+
+
+def cpu_rrt_connect(model: "HipModel", collision: "HipCollision", q_start, q_goal, lo, hi, margin, tol, *, step, min_advance=None,
+                    max_iters, max_nodes, max_waypoints, max_steps, seed, want=None, nthreads: int = 0) -> dict:
+    """CPU twin of HipContext.rrt_connect_arrays."""
+    return _rrt_connect((), load_library().mp_rrt_connect_cpu_f64, model, collision, q_start, q_goal, lo, hi, margin, tol, step,
+                        min_advance, max_iters, max_nodes, max_waypoints, max_steps, seed, want, nthreads)
 
 
 def _pd_regulation_args(model, theta0, theta_des, Kp, Kd, g, steps):

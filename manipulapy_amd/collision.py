@@ -14,12 +14,13 @@ import numpy as np
 from . import _hip
 from .registry import execute_registered_kernel
 
-__all__ = ["SphereCollisionModel", "COLLISION_OP", "EDGES_OP"]
+__all__ = ["SphereCollisionModel", "COLLISION_OP", "EDGES_OP", "PLAN_OP"]
 
 # The registry's sorted name list starts with "control.pd_regulation" (the unknown-name message is pinned by a test), so the operation
 # lives in the "planning" family rather than in one of its own that would sort ahead of it.
 COLLISION_OP = "planning.collision_spheres"
 EDGES_OP = "planning.collision_edges"
+PLAN_OP = "planning.rrt_connect"
 
 
 def _hip_model_of(obj) -> _hip.HipModel:
@@ -187,4 +188,24 @@ class SphereCollisionModel:
         lead = qa.shape[:-1]
         out = execute_registered_kernel(EDGES_OP, self, np.ascontiguousarray(qa.reshape(-1, self.n)),
                                         np.ascontiguousarray(qb.reshape(-1, self.n)), margin, tol, max_steps, want)
+        return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}
+
+    # ------------------------------------------------------------------ planning
+    def plan_paths(self, q_start, q_goal, lo, hi, margin: float = 0.0, tol: float = 1e-3, *, step: float, min_advance=None,
+                   max_iters: int, max_nodes: int, max_waypoints: int, max_steps: int = 64, seed: int = 0, want=None) -> dict:
+        """Bidirectional RRT-Connect for B independent problems q_start -> q_goal ((B, n) or any common leading shape) in the
+        sampling box lo, hi (n): {"status" (0 solved, 1 exhausted, 2 tree full, 3 start blocked, 4 goal blocked, 5 path too long,
+        -1 invalid), "count", "waypoints" (.., max_waypoints, n), "iterations", "nodes" (.., 2), "evaluations"} or the subset named
+        in `want`.  Every tree edge, and so every segment of a returned path, is proven free by `check_edges`' conservative
+        advancement with this margin, tol and max_steps; a path is padded by repeating its last waypoint.  `min_advance` defaults
+        to step / 8.  A problem's result depends on its content and `seed` only.  The launch lasts as long as its slowest problem:
+        `max_iters` is the latency knob."""
+        qs, qg = np.asarray(q_start, dtype=np.float64), np.asarray(q_goal, dtype=np.float64)
+        if qs.shape != qg.shape or qs.ndim < 1 or qs.shape[-1] != self.n:
+            raise ValueError(f"q_start and q_goal must have one shape (..., {self.n}); got {qs.shape} and {qg.shape}")
+        lead = qs.shape[:-1]
+        out = execute_registered_kernel(PLAN_OP, self, np.ascontiguousarray(qs.reshape(-1, self.n)),
+                                        np.ascontiguousarray(qg.reshape(-1, self.n)), lo, hi, margin, tol, step=step,
+                                        min_advance=min_advance, max_iters=max_iters, max_nodes=max_nodes, max_waypoints=max_waypoints,
+                                        max_steps=max_steps, seed=seed, want=want)
         return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}

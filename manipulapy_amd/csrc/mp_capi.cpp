@@ -5,6 +5,7 @@
 
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <atomic>
 #include <set>
 #include <cmath>
@@ -3192,6 +3193,95 @@ int mp_collision_edges_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision
   int32_t* dwit = hc.out(witness, 3 * ib);
   return hc.run([&] {
     return collision_edges_impl(fn, ctx, model, h, da, db, edges, margin, tol, max_steps, 0, dstatus, dt, dsteps, dclear, dwit);
+  });
+}
+
+}  // extern "C"
+
+// ---- batched RRT-Connect over the sphere model (mp_rrt.h).  The grid: the resident blocks, ceil(B / 64), max_blocks and what the
+// workspace holds, whichever is smallest.
+static int rrt_connect_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_qs, const double* d_qg,
+                            int64_t B, const MpRrtParams& P, void* d_ws, size_t ws_bytes, int max_blocks, int32_t* d_status,
+                            int32_t* d_count, double* d_wp, int32_t* d_iters, int32_t* d_nodes, int32_t* d_evals) {
+  REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  REQUIRE(d_qs && d_qg, "%s: null device pointer", fn);
+  REQUIRE(d_status || d_count || d_wp || d_iters || d_nodes || d_evals, "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_qs) && aligned16(d_qg) && aligned16(d_status) && aligned16(d_count) && aligned16(d_wp) && aligned16(d_iters) &&
+              aligned16(d_nodes) && aligned16(d_evals) && aligned16(d_ws),
+          "%s: device pointers must be 16-byte aligned", fn);
+  const size_t block_bytes = (size_t)mp_rrt_connect_workspace_bytes(model->d.n, P.max_nodes, 1);
+  REQUIRE(d_ws && ws_bytes >= block_bytes, "%s: the workspace holds %zu bytes, one block needs %zu (mp_rrt_connect_workspace_bytes)", fn,
+          d_ws ? ws_bytes : (size_t)0, block_bytes);
+  std::lock_guard<std::mutex> hl(h->mu);
+  mp_collision::Resident* R = nullptr;
+  if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
+  PROFILE_SCOPE(ctx, fn);
+  long grid = 0;
+  HIP_TRY(mpk_rrt_connect_resident(model->d.n, h->sph.S, ctx->compute_units, &grid));
+  grid = std::min<long>(grid, (long)((B + 63) / 64));
+  if (max_blocks > 0) grid = std::min<long>(grid, max_blocks);
+  grid = std::min<long>(grid, (long)(ws_bytes / block_bytes));
+  HIP_TRY(mpk_rrt_connect(ctx->compute, model->d, h->sph.S, static_cast<const MpColSpheres*>(R->sph),
+                          reinterpret_cast<const MpColPair*>(static_cast<const char*>(R->sph) + sizeof(MpColSpheres)),
+                          static_cast<const MpColWorld*>(R->world), d_qs, d_qg, (long)B, P, d_status, d_count, d_wp, d_iters, d_nodes,
+                          d_evals, static_cast<double*>(d_ws), static_cast<unsigned long long*>(R->counter), ctx->compute_units, grid));
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_rrt_connect_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q_start, const double* d_q_goal, int64_t B,
+                       const double* lo, const double* hi, uint32_t seed, double step, double min_advance, int max_iters, int max_nodes,
+                       int max_waypoints, double margin, double tol, int max_steps, void* d_workspace, size_t workspace_bytes,
+                       int max_blocks, int32_t* d_status, int32_t* d_count, double* d_waypoints, int32_t* d_iterations, int32_t* d_nodes,
+                       int32_t* d_evaluations) {
+  const char* fn = "mp_rrt_connect_f64";
+  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  MpRrtParams P;
+  if (int rc = mp_rrt_connect_check(fn, model->d.n, lo, hi, seed, step, min_advance, max_iters, max_nodes, max_waypoints, margin, tol,
+                                    max_steps, &P))
+    return rc;
+  return rrt_connect_impl(fn, ctx, model, h, d_q_start, d_q_goal, B, P, d_workspace, workspace_bytes, max_blocks, d_status, d_count,
+                          d_waypoints, d_iterations, d_nodes, d_evaluations);
+}
+
+// the workspace comes from the pool: as many blocks as the launch can use, at most 1 GiB of them (never less than one block)
+int mp_rrt_connect_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q_start, const double* q_goal, int64_t B,
+                            const double* lo, const double* hi, uint32_t seed, double step, double min_advance, int max_iters,
+                            int max_nodes, int max_waypoints, double margin, double tol, int max_steps, int32_t* status, int32_t* count,
+                            double* waypoints, int32_t* iterations, int32_t* nodes, int32_t* evaluations) {
+  const char* fn = "mp_rrt_connect_host_f64";
+  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  MpRrtParams P;
+  if (int rc = mp_rrt_connect_check(fn, model->d.n, lo, hi, seed, step, min_advance, max_iters, max_nodes, max_waypoints, margin, tol,
+                                    max_steps, &P))
+    return rc;
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  REQUIRE(q_start && q_goal, "%s: null host pointer", fn);
+  long blocks = 0;
+  HIP_TRY(mpk_rrt_connect_resident(model->d.n, h->sph.S, ctx->compute_units, &blocks));
+  const size_t n = (size_t)model->d.n, qb = (size_t)B * n * sizeof(double), ib = (size_t)B * sizeof(int32_t);
+  const size_t block_bytes = (size_t)mp_rrt_connect_workspace_bytes(model->d.n, max_nodes, 1);
+  blocks = std::min<long>(blocks, (long)((B + 63) / 64));
+  blocks = std::max<long>(1, std::min<long>(blocks, (long)(((size_t)1 << 30) / block_bytes)));
+  const size_t ws_bytes = (size_t)blocks * block_bytes;
+  HostCall hc(ctx);  // (h is the collision handle)
+  const double *ds = hc.in(q_start, qb), *dg = hc.in(q_goal, qb);
+  int32_t *dstatus = hc.out(status, ib), *dcount = hc.out(count, ib);
+  double* dwp = hc.out(waypoints, (size_t)B * (size_t)max_waypoints * n * sizeof(double));
+  int32_t *dit = hc.out(iterations, ib), *dnodes = hc.out(nodes, 2 * ib), *dev = hc.out(evaluations, ib);
+  void* dws = hc.work(ws_bytes);
+  return hc.run([&] {
+    return rrt_connect_impl(fn, ctx, model, h, ds, dg, B, P, dws, ws_bytes, 0, dstatus, dcount, dwp, dit, dnodes, dev);
   });
 }
 

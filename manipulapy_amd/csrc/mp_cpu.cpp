@@ -1284,3 +1284,81 @@ int mp_collision_edges_cpu_f64(const mp_model* model, const mp_collision* h, con
 }
 
 }  // extern "C"
+
+// ---- batched RRT-Connect over the sphere model (mp_rrt.h)
+int mp_rrt_connect_check(const char* fn, int n, const double* lo, const double* hi, uint32_t seed, double step, double min_advance,
+                         int max_iters, int max_nodes, int max_waypoints, double margin, double tol, int max_steps, MpRrtParams* out) {
+  if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
+  if (!lo || !hi) return col_fail("%s: null sampling box", fn);
+  MpRrtParams P;
+  std::memset(&P, 0, sizeof P);
+  for (int j = 0; j < n; ++j) {
+    if (!std::isfinite(lo[j]) || !std::isfinite(hi[j]) || !(lo[j] <= hi[j]))
+      return col_fail("%s: joint %ld: the sampling box must be finite with lo <= hi", fn, j);
+    P.lo[j] = lo[j];
+    P.hi[j] = hi[j];
+  }
+  if (!(step > 0.0) || !std::isfinite(step)) return col_fail("%s: step must be positive and finite", fn);
+  if (!(min_advance >= 0.0) || !std::isfinite(min_advance)) return col_fail("%s: min_advance must be non-negative and finite", fn);
+  if (max_iters < 0) return col_fail("%s: negative max_iters", fn);
+  if (max_nodes < 2 || max_nodes > MP_RRT_MAX_NODES) return col_fail("%s: max_nodes %ld outside 2..65536", fn, max_nodes);
+  if (max_waypoints < 2) return col_fail("%s: max_waypoints %ld below 2", fn, max_waypoints);
+  P.step = step; P.min_advance = min_advance;
+  P.edge = {margin, tol, max_steps, 0};
+  P.seed = seed; P.max_iters = max_iters; P.max_nodes = max_nodes; P.max_waypoints = max_waypoints;
+  *out = P;
+  return MP_OK;
+}
+
+extern "C" {
+
+int64_t mp_rrt_connect_workspace_bytes(int n, int max_nodes, int blocks) {
+  const char* fn = "mp_rrt_connect_workspace_bytes";
+  if (n < 1) return -(int64_t)col_fail("%s: joint count %ld below 1", fn, n);
+  if (n > MP_MAX_DOF) {
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, n);
+    return -(int64_t)mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (max_nodes < 2 || max_nodes > MP_RRT_MAX_NODES) return -(int64_t)col_fail("%s: max_nodes %ld outside 2..65536", fn, max_nodes);
+  if (blocks < 1) return -(int64_t)col_fail("%s: block count %ld below 1", fn, blocks);
+  return (int64_t)blocks * 64 * 2 * (int64_t)max_nodes * (8 * (int64_t)n + 4);
+}
+
+int mp_rrt_connect_cpu_f64(const mp_model* model, const mp_collision* h, const double* q_start, const double* q_goal, int64_t B,
+                           const double* lo, const double* hi, uint32_t seed, double step, double min_advance, int max_iters,
+                           int max_nodes, int max_waypoints, double margin, double tol, int max_steps, int32_t* status, int32_t* count,
+                           double* waypoints, int32_t* iterations, int32_t* nodes, int32_t* evaluations, int nthreads) {
+  const char* fn = "mp_rrt_connect_cpu_f64";
+  if (!model || !h) return col_fail("%s: null model or collision handle", fn);
+  if (model->big) {
+    char msg[192];
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (h->n != model->d.n) return col_fail("%s: the collision handle was made for a model of %ld joints", fn, h->n);
+  MpRrtParams P;
+  if (int rc = mp_rrt_connect_check(fn, model->d.n, lo, hi, seed, step, min_advance, max_iters, max_nodes, max_waypoints, margin, tol,
+                                    max_steps, &P))
+    return rc;
+  if (B < 0) return col_fail("%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  if (!q_start || !q_goal) return col_fail("%s: null pointer", fn);
+  if (!status && !count && !waypoints && !iterations && !nodes && !evaluations) return col_fail("%s: at least one output is required", fn);
+  const MpModel<double>& M = model->d;
+  const MpColWorld hdr = {(int)h->world.size(), {0, 0, 0}};
+  const MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*> tb = {&h->sph, h->pairs.data(), &hdr,
+                                                                                                          h->world.data()};
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
+      std::vector<double> tree((size_t)2 * (size_t)max_nodes * N);  // the thread's trees, reused like a lane's
+      std::vector<int> parents((size_t)2 * (size_t)max_nodes);
+      for (int64_t b = b0; b < b1; ++b)
+        mp_rrt_cpu<N>(M, tb, P, q_start, q_goal, (long)b, tree.data(), parents.data(), status, count, waypoints, iterations, nodes,
+                      evaluations);
+    });
+  })
+  return MP_OK;
+}
+
+}  // extern "C"

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "mp_collision.h"
+#include "mp_rrt.h"
 #include "mp_model.h"
 
 struct mp_model {
@@ -41,5 +42,8 @@ struct mp_collision {
 int mp_collision_pack_world(const char* fn, int O, const int32_t* kind, const double* params, std::vector<MpColObstacle>* out);
 // the edge check's parameters: margin finite, tol positive and finite, max_steps in 1..65536; 0 or MP_ERR_INVALID (mp_cpu.cpp)
 int mp_collision_edges_check(const char* fn, double margin, double tol, int max_steps);
+// the planner's parameters (the edge check's among them), packed into `out`; 0, or MP_ERR_INVALID with the message set (mp_cpu.cpp)
+int mp_rrt_connect_check(const char* fn, int n, const double* lo, const double* hi, uint32_t seed, double step, double min_advance,
+                         int max_iters, int max_nodes, int max_waypoints, double margin, double tol, int max_steps, MpRrtParams* out);
 
 int mp_set_error(int code, const char* msg);  // thread-local message of mp_last_error (mp_capi.cpp; C++ linkage)

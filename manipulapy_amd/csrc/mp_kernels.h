@@ -191,3 +191,13 @@ hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, int S, c
                                const MpColWorld* d_world, const double* q_from, const double* q_to, long edges, const MpColEdgeParams& P,
                                int* status, double* t, int* steps, double* clearance, int* witness, unsigned long long* queue_counter,
                                int compute_units, int max_blocks);
+// batched RRT-Connect over the sphere model (csrc/mp_rrt.h): a work queue over `problems`, one evaluated configuration a trip, the
+// trees in `workspace` (blocks x 64 x 2 max_nodes (8 n + 4) bytes); queue_counter is zeroed on the stream first.
+// mpk_rrt_connect_resident gives the one-wave blocks the device keeps resident; the caller settles the grid (`blocks`) from it, the
+// problem count, its cap and the workspace.
+struct MpRrtParams;
+hipError_t mpk_rrt_connect_resident(int n, int S, int compute_units, long* blocks);
+hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
+                           const MpColWorld* d_world, const double* q_start, const double* q_goal, long problems, const MpRrtParams& P,
+                           int* status, int* count, double* waypoints, int* iterations, int* nodes, int* evaluations, double* workspace,
+                           unsigned long long* queue_counter, int compute_units, long blocks);

@@ -23,6 +23,7 @@
 #include "mp_ilqr.h"
 #include "mp_toppra.h"
 #include "mp_collision.h"
+#include "mp_rrt.h"
 
 namespace {
 
@@ -519,6 +520,84 @@ __global__ __launch_bounds__(64) void k_collision_edges(const MpModel<double> M,
       if (clearance != nullptr) clearance[row] = cl;
       if (witness != nullptr) { witness[3 * row] = w[0]; witness[3 * row + 1] = w[1]; witness[3 * row + 2] = w[2]; }
       have = false;
+    }
+  }
+}
+
+// ------------------------------------------------------- batched RRT-Connect over the sphere model (float64, mp_rrt.h)
+// One wave per block and a work queue as in k_collision_edges: a lane without a problem takes the next index from the device counter,
+// every trip of the loop does the selection work the lane's problem is waiting for and evaluates ONE configuration of its running
+// edge, and a finished lane writes its row and fetches another.  Dynamic LDS: the park and the speed bounds, laid out exactly as in
+// k_collision_edges.  The trees live in the caller's workspace and belong to the resident lane, not to the problem: per block the
+// nodes [tree][node][dim][lane] (doubles), then the parents [tree][node][lane] (int32); a new problem resets the lane's counts
+// only.  Each lane reads and writes only its own column, in program order, so no barrier or fence is needed.  The nearest search
+// (mp_rrt_nearest) is entered by all 64 lanes on every trip and runs to the wave's largest count, so the wave reads whole 512-byte
+// lines; the loop of the kernel ends for the whole wave at once, when no lane holds a problem and the queue is empty.
+struct MpRrtTreeLanes {
+  double* nodes;  // already offset by the block and the lane
+  int* parents;
+  int max_nodes, n;
+  __device__ __forceinline__ double get(int tree, int v, int j) const { return nodes[(((long)tree * max_nodes + v) * n + j) * 64]; }
+  __device__ __forceinline__ void put(int tree, int v, int j, double x) { nodes[(((long)tree * max_nodes + v) * n + j) * 64] = x; }
+  __device__ __forceinline__ int parent(int tree, int v) const { return parents[((long)tree * max_nodes + v) * 64]; }
+  __device__ __forceinline__ void set_parent(int tree, int v, int p) { parents[((long)tree * max_nodes + v) * 64] = p; }
+  __device__ __forceinline__ int wave_max(int v) const {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int w = __shfl_xor(v, o);
+      v = w > v ? w : v;
+    }
+    return v;
+  }
+  __device__ __forceinline__ bool wave_any(bool b) const { return __any(b ? 1 : 0) != 0; }
+};
+
+template <int N>
+__global__ __launch_bounds__(64) void k_rrt_connect(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
+                                                    const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
+                                                    const double* __restrict__ q_start, const double* __restrict__ q_goal, long problems,
+                                                    const MpRrtParams P, int* __restrict__ status, int* __restrict__ count,
+                                                    double* __restrict__ waypoints, int* __restrict__ iterations, int* __restrict__ nodes,
+                                                    int* __restrict__ evaluations, double* __restrict__ workspace,
+                                                    unsigned long long* __restrict__ next) {
+  extern __shared__ __attribute__((aligned(16))) double mp_rrt_lds[];
+  const int lane = (int)threadIdx.x;
+  const MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*> tb = {
+      (MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
+  MpColParkLanes park{mp_rrt_lds + lane};
+  MpColBoundsLanes L{mp_rrt_lds + 3 * 64 * tb.sph->S + lane};
+  const size_t node_words = (size_t)2 * (size_t)P.max_nodes * N * 64;                  // doubles a block
+  const size_t block_words = node_words + (size_t)P.max_nodes * 64;                   // + 2 max_nodes 64 int32
+  double* const mine = workspace + (size_t)blockIdx.x * block_words;
+  MpRrtTreeLanes T{mine + lane, reinterpret_cast<int*>(mine + node_words) + lane, P.max_nodes, N};
+  MpRrtState<N> S;
+  S.phase = MP_RRT_IDLE;
+  S.done = 0;
+  bool have = false, dry = false;
+  long row = 0;
+  for (;;) {
+    if (!have && !dry) {
+      row = (long)atomicAdd(next, 1ull);
+      if (row >= problems) {
+        dry = true;
+      } else {
+        double a[N], b[N];
+        RunIO<double, N>::load(q_start, row, a);
+        RunIO<double, N>::load(q_goal, row, b);
+        mp_rrt_begin<N>(M, tb, P, a, b, S, T, L, waypoints != nullptr ? waypoints + row * (long)P.max_waypoints * N : nullptr);
+        have = true;
+      }
+    }
+    if (!T.wave_any(have)) break;
+    double* wp = (have && waypoints != nullptr) ? waypoints + row * (long)P.max_waypoints * N : nullptr;
+    if (mp_rrt_trip<N>(M, tb, P, S, T, park, L, wp)) {
+      if (status != nullptr) status[row] = S.status;
+      if (count != nullptr) count[row] = S.count;
+      if (iterations != nullptr) iterations[row] = S.k;
+      if (nodes != nullptr) { nodes[2 * row] = S.cnt0; nodes[2 * row + 1] = S.cnt1; }
+      if (evaluations != nullptr) evaluations[row] = S.evals;
+      have = false;
+      S.phase = MP_RRT_IDLE;
     }
   }
 }
@@ -1405,6 +1484,50 @@ hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, int S, c
     if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
     hipLaunchKernelGGL((k_collision_edges<N>), dim3((unsigned)grid), dim3(64), lds, s, M, d_sph, d_pairs, d_world, q_from, q_to, edges, P,
                        status, t, steps, clearance, witness, queue_counter);
+  })
+  return hipGetLastError();
+}
+
+// the one-wave blocks of k_rrt_connect the device keeps resident (LDS as for the edge kernel)
+template <int N>
+static hipError_t rrt_resident(int S, int compute_units, unsigned* lds_out, long* blocks) {
+  const unsigned lds = (unsigned)(3 * S + N * (N + 1) / 2) * 64u * (unsigned)sizeof(double);
+  const void* fn = reinterpret_cast<const void*>(&k_rrt_connect<N>);
+  if (lds > 64u * 1024u) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  int per_cu = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds);
+  if (e != hipSuccess) return e;
+  *lds_out = lds;
+  *blocks = (long)(per_cu > 0 ? per_cu : 1) * (compute_units > 0 ? compute_units : 256);
+  return hipSuccess;
+}
+
+hipError_t mpk_rrt_connect_resident(int n, int S, int compute_units, long* blocks) {
+  if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
+  unsigned lds = 0;
+  MP_DISPATCH_N(n, { return rrt_resident<N>(S, compute_units, &lds, blocks); })
+  return hipErrorInvalidValue;
+}
+
+// `blocks`: the grid the caller has settled on (mpk_rrt_connect_resident, the problem count, max_blocks and the workspace)
+hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
+                           const MpColWorld* d_world, const double* q_start, const double* q_goal, long problems, const MpRrtParams& P,
+                           int* status, int* count, double* waypoints, int* iterations, int* nodes, int* evaluations, double* workspace,
+                           unsigned long long* queue_counter, int compute_units, long blocks) {
+  if (problems <= 0) return hipSuccess;
+  if (S < 1 || S > MP_COL_MAX_SPHERES || blocks < 1) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(queue_counter, 0, sizeof(unsigned long long), s);
+  if (e != hipSuccess) return e;
+  MP_DISPATCH_N(M.n, {
+    unsigned lds = 0;
+    long resident = 0;
+    e = rrt_resident<N>(S, compute_units, &lds, &resident);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((k_rrt_connect<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, d_sph, d_pairs, d_world, q_start, q_goal, problems,
+                       P, status, count, waypoints, iterations, nodes, evaluations, workspace, queue_counter);
   })
   return hipGetLastError();
 }

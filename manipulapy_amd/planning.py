@@ -576,6 +576,23 @@ class OptimizedTrajectoryPlanning:
                 "segment_status": status,
                 "clearance": np.where(bad.any(axis=1), np.nan, np.where(bad, np.inf, clear).min(axis=1))}
 
+    def batch_plan_path(self, start, goal, collision_model, margin: float = 0.0, tol: float = 1e-3, *, step: float = 1.0,
+                        min_advance=None, max_iters: int = 200, max_nodes: int = 256, max_waypoints: int = 64, max_steps: int = 64,
+                        seed: int = 0, finite_limit: float = 2 * np.pi) -> Dict[str, np.ndarray]:
+        """Collision-free piecewise-linear joint-space paths for B (start, goal) pairs (B, n) under a collision.SphereCollisionModel,
+        by bidirectional RRT-Connect (SphereCollisionModel.plan_paths), all B problems in one launch.  The sampling box is this
+        planner's joint limits, an open or non-finite limit clipped to +-`finite_limit`.  {"status", "count", "waypoints" (B,
+        max_waypoints, n), "iterations", "nodes", "evaluations"}: "waypoints" can go straight into `batch_validate_path`."""
+        sb, gb = np.asarray(start, dtype=np.float64), np.asarray(goal, dtype=np.float64)
+        n = collision_model.n
+        if sb.ndim != 2 or sb.shape != gb.shape or sb.shape[1] != n:
+            raise ValueError(f"start and goal must both be (B, {n}); got {sb.shape} and {gb.shape}")
+        lim = np.nan_to_num(np.asarray(self.joint_limits, dtype=np.float64), nan=0.0, posinf=finite_limit, neginf=-finite_limit)
+        lo, hi = np.clip(lim[:, 0], -finite_limit, finite_limit), np.clip(lim[:, 1], -finite_limit, finite_limit)
+        return self._dispatch("planning.rrt_connect", collision_model, np.ascontiguousarray(sb), np.ascontiguousarray(gb), lo, hi, margin,
+                              tol, step=step, min_advance=min_advance, max_iters=max_iters, max_nodes=max_nodes,
+                              max_waypoints=max_waypoints, max_steps=max_steps, seed=seed)
+
     # ------------------------------------------------------------------ legacy dynamics objects (Mlist_per_link=None)
     # The reference's approximation for such objects is not rigid-body dynamics (dynamics/mass_matrix.py:101-132), so there
     # is no compiled model and no kernel for it: the planner walks the rows on the host exactly as the reference's CPU

@@ -319,6 +319,10 @@ def _launch_collision_edges_cpu(cm, q_from, q_to, margin, tol, max_steps, want=N
     return _hip.cpu_collision_edges(cm.model, cm.handle, q_from, q_to, margin, tol, max_steps, want)
 
 
+def _launch_rrt_connect_cpu(cm, q_start, q_goal, lo, hi, margin, tol, **kw):
+    return _hip.cpu_rrt_connect(cm.model, cm.handle, q_start, q_goal, lo, hi, margin, tol, **kw)
+
+
 def _launch_opspace_cpu(model, q, qd, g=None, frame="hybrid", task="full", damping=0.0, want=_hip.OPSPACE_OUTPUTS):
     return _hip.cpu_opspace(model, q, qd, g, frame, task, damping, want)
 
@@ -488,6 +492,12 @@ def _launch_collision_edges_gpu(cm, q_from, q_to, margin, tol, max_steps, want=N
     return ctx.collision_edges_host(cm.model, cm.handle, q_from, q_to, margin, tol, max_steps, want)
 
 
+def _launch_rrt_connect_gpu(cm, q_start, q_goal, lo, hi, margin, tol, **kw):
+    ctx = get_context()
+    cm.sync_world(ctx)
+    return ctx.rrt_connect_arrays(cm.model, cm.handle, q_start, q_goal, lo, hi, margin, tol, **kw)
+
+
 def _launch_fk_jac_vjp_gpu(model, q, gT=None, gJ=None, frame="space", want_T=False, want_J=False, want_gq=True):
     return get_context().fk_jac_vjp_host(model, q, gT, gJ, frame, want_T, want_J, want_gq)
 
@@ -624,6 +634,9 @@ def _build_kernel_registry() -> KernelRegistry:
         ("planning.collision_spheres", "mp_collision_host_f64", _launch_collision_gpu, _launch_collision_cpu),
         # continuous collision check of joint-space edges by conservative advancement (csrc/mp_collision.h, mp_collision_edge_*)
         ("planning.collision_edges", "mp_collision_edges_host_f64", _launch_collision_edges_gpu, _launch_collision_edges_cpu),
+        # batched RRT-Connect over the sphere model, every tree edge proven by the edge check (csrc/mp_rrt.h); the name sorts after
+        # the pinned head of the name list
+        ("planning.rrt_connect", "mp_rrt_connect_host_f64", _launch_rrt_connect_gpu, _launch_rrt_connect_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):
