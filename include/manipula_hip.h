@@ -858,6 +858,76 @@ int mp_rrt_connect_cpu_f64(const mp_model* model, const mp_collision* h, const d
                            int max_nodes, int max_waypoints, double margin, double tol, int max_steps, int32_t* status, int32_t* count,
                            double* waypoints, int32_t* iterations, int32_t* nodes, int32_t* evaluations, int nthreads);
 
+/* ---- batched path shortcutting over the sphere model above (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED above that;
+ * csrc/mp_shortcut.h).  Randomised shortcutting (Geraerts and Overmars; Hauser and Ng-Thow-Hing) of B piecewise-linear joint-space
+ * paths in one world: two points are drawn on the path by arc length, the straight motion between them is proven free by the
+ * conservative advancement of mp_collision_edges_*, with the launch's margin, tol and max_steps, and if it is free it replaces the
+ * piece of path between them.  The kernel, the CPU twin and the tests' NumPy oracle implement exactly the contract below.
+ * Per problem: waypoints_in (W_in, n) and count_in.  The first count_in rows are the path p_0 .. p_{m-1}; the rest is ignored, so a
+ *   planner's padded `waypoints` and its `count` go straight in.  Per launch: W_in in 1..65536, seed (uint32), max_iters >= 0,
+ *   min_gain >= 0 and finite, max_waypoints in 2..65536 (the output rows W), and margin, tol, max_steps as for the edges.  Anything
+ *   else is MP_ERR_INVALID with a message.
+ * Start of a problem: count_in < 2: SKIPPED (a planner row that was not SOLVED has count 0).  count_in > W_in, count_in >
+ *   max_waypoints, or a non-finite value in the first count_in rows: INVALID.  Neither evaluates anything; both return NaN rows,
+ *   count 0, NaN lengths and 0 in the counters.
+ * Lengths: c_0 = 0, c_{i+1} = c_i + sqrt(sum_j (p_{i+1,j} - p_{i,j})^2), summed over j ascending; Lambda = c_{m-1}.  The table is
+ *   recomputed from scratch, by this same formula, after every accepted shortcut.
+ * Random numbers: key = the hash of mp_rrt_connect_* over p_0 then p_{m-1} of the INPUT path; u(k, j) as there, j = 0, 1.  A
+ *   problem's result depends on its own content and the seed only - not on its row, its lane or the launch.
+ * locate(s): i = the smallest index in 0..m-2 with s < c_{i+1}, m - 2 if there is none (a zero-length segment is never chosen);
+ *   lambda = (s - c_i) / (c_{i+1} - c_i); the point is p_i + lambda (p_{i+1} - p_i).
+ * Procedure, for k = 0, 1, ..:
+ *     m == 2 and (k < max_iters or k == 0): stop, STRAIGHT - a path of two waypoints is STRAIGHT before anything is drawn, whatever
+ *       max_iters is, and a path that becomes one ends at the head of the next iteration, if there is one.
+ *     k == max_iters: stop, DONE.
+ *     s_a = u(k, 0) Lambda, s_b = u(k, 1) Lambda, swapped so that s_a <= s_b; (i, a) = locate(s_a), (j, b) = locate(s_b).
+ *     i == j: nothing to gain, next k.
+ *     d = sqrt(sum_j (b_j - a_j)^2), gain = (s_b - s_a) - d.  gain <= min_gain: next k, with no edge check.
+ *     m' = m - (j - i) + 2.  m' > max_waypoints: skipped_full += 1, next k.
+ *     edge(a -> b), one edge check of the section above, D = b - a: FREE: the path becomes p_0 .. p_i, a, a + D, p_{j+1} .. p_{m-1}
+ *       (a + D, the end of the motion a + t D that the check has proven, is b to within an ulp), m = m', the lengths are recomputed,
+ *       accepted += 1.  BLOCKED or UNDECIDED: nothing changes.  Next k.
+ * What is proven: every segment the procedure creates is proven FREE; pieces of input segments are kept as they are, so the output is
+ *   as free as the input.  THE INPUT IS NOT CHECKED: validate it (mp_collision_edges_* over its segments, batch_validate_path in
+ *   Python) if it does not come from mp_rrt_connect_* under the same margin.  The output starts at p_0 and ends at p_{m-1} of the
+ *   input bit for bit.
+ * Per problem (every output may be NULL; at least one is needed):
+ *     status (B) int32                   MP_SHORTCUT_DONE 0, _STRAIGHT 1, _SKIPPED 2, _INVALID -1
+ *     count (B) int32                    the waypoints of the output path (0 for SKIPPED and INVALID)
+ *     waypoints (B, max_waypoints, n)    the path, padded by repeating the last waypoint as the planner pads; must not overlap
+ *                                        waypoints_in
+ *     length_in, length_out (B)          Lambda of the input path and of the output path
+ *     iterations (B) int32               k at the end
+ *     accepted, skipped_full (B) int32
+ *     evaluations (B) int32              the configurations evaluated
+ * mp_path_shortcut_f64: d_waypoints_in (B,W_in,n), d_count_in (B) int32 device arrays, 16-byte aligned like every output and the
+ *   workspace.  One launch: a lane serves one problem at a time and takes problems from a queue.  The working paths live in
+ *   d_workspace and belong to the resident lane: mp_path_shortcut_workspace_bytes(n, max_waypoints, blocks) = blocks x 64 lanes x
+ *   max_waypoints (8 n + 8) bytes (or minus an MP_ERR_* code).  The grid is the smallest of the one-wave blocks the device keeps
+ *   resident, ceil(B / 64), max_blocks (if positive) and the blocks the workspace holds; room for less than one block is
+ *   MP_ERR_INVALID.  Asynchronous; it allocates nothing once the handle is resident on the context and may then be captured into a
+ *   launch graph (the queue head's reset is part of it).  Launches that share a collision handle share its queue head: they are
+ *   serialised by the handle's lock and the compute stream.  mp_path_shortcut_host_f64: host arrays, device memory and workspace
+ *   from the context's pool.  mp_path_shortcut_cpu_f64: the kernel's per-problem code on the host, no context. */
+#define MP_SHORTCUT_DONE 0
+#define MP_SHORTCUT_STRAIGHT 1
+#define MP_SHORTCUT_SKIPPED 2
+#define MP_SHORTCUT_INVALID (-1)
+int64_t mp_path_shortcut_workspace_bytes(int n, int max_waypoints, int blocks);
+int mp_path_shortcut_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_waypoints_in, const int32_t* d_count_in,
+                         int64_t B, int64_t W_in, uint32_t seed, int max_iters, double min_gain, int max_waypoints, double margin,
+                         double tol, int max_steps, void* d_workspace, size_t workspace_bytes, int max_blocks, int32_t* d_status,
+                         int32_t* d_count, double* d_waypoints, double* d_length_in, double* d_length_out, int32_t* d_iterations,
+                         int32_t* d_accepted, int32_t* d_skipped_full, int32_t* d_evaluations);
+int mp_path_shortcut_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* waypoints_in, const int32_t* count_in,
+                              int64_t B, int64_t W_in, uint32_t seed, int max_iters, double min_gain, int max_waypoints, double margin,
+                              double tol, int max_steps, int32_t* status, int32_t* count, double* waypoints, double* length_in,
+                              double* length_out, int32_t* iterations, int32_t* accepted, int32_t* skipped_full, int32_t* evaluations);
+int mp_path_shortcut_cpu_f64(const mp_model* model, const mp_collision* h, const double* waypoints_in, const int32_t* count_in, int64_t B,
+                             int64_t W_in, uint32_t seed, int max_iters, double min_gain, int max_waypoints, double margin, double tol,
+                             int max_steps, int32_t* status, int32_t* count, double* waypoints, double* length_in, double* length_out,
+                             int32_t* iterations, int32_t* accepted, int32_t* skipped_full, int32_t* evaluations, int nthreads);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new; the reference is single-device) ------
  * Trajectory batches are sharded over ranks with no exchange during compute; the only collective is
  * the all-gather that reassembles the torque history.  Rank 0 creates the id, the launcher

@@ -187,6 +187,10 @@ SIGNATURES = {
     "mp_rrt_connect_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_rrt_connect_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _c_dp, _vp, _vp, _vp]),
     "mp_rrt_connect_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _c_dp, _vp, _vp, _vp, ctypes.c_int]),
+    "mp_path_shortcut_workspace_bytes": (ctypes.c_int64, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "mp_path_shortcut_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_path_shortcut_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _vp, _i64, _i64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _c_dp, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
+    "mp_path_shortcut_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _vp, _i64, _i64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _c_dp, _c_dp, _c_dp, _vp, _vp, _vp, _vp, ctypes.c_int]),
     "mp_comm_unique_id": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8)]),
     "mp_comm_create": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     "mp_comm_destroy": (ctypes.c_int, [_vp]),
@@ -734,6 +738,30 @@ class HipContext:
         tests/test_gpu_rrt.py.)"""
         return _rrt_connect((self.handle,), self.lib.mp_rrt_connect_host_f64, model, collision, q_start, q_goal, lo, hi, margin, tol,
                             step, min_advance, max_iters, max_nodes, max_waypoints, max_steps, seed, want)
+
+    def path_shortcut(self, model, collision, d_waypoints_in, d_count_in, problems, w_in, margin, tol, *, max_iters, min_gain=0.0,
+                      max_waypoints, max_steps, seed, d_workspace, workspace_bytes, max_blocks: int = 0, d_status=None, d_count=None,
+                      d_waypoints=None, d_length_in=None, d_length_out=None, d_iterations=None, d_accepted=None, d_skipped_full=None,
+                      d_evaluations=None):
+        """Batched path shortcutting on device buffers (float64; csrc/mp_shortcut.h): d_waypoints_in (problems,w_in,n), d_count_in
+        (problems) int32; outputs status / count / iterations / accepted / skipped_full / evaluations (problems) int32, length_in /
+        length_out (problems), waypoints (problems,max_waypoints,n), each may be None (at least one given).  d_workspace holds the
+        working paths: path_shortcut_workspace_bytes(n, max_waypoints, blocks).  `max_blocks` > 0 caps the grid.  Asynchronous
+        (capturable once the handle has been used or given a world on this context)."""
+        _check(self.lib.mp_path_shortcut_f64(self.handle, model.handle, collision.handle, _p(d_waypoints_in), _p(d_count_in),
+                                             int(problems), int(w_in), int(seed), int(max_iters), float(min_gain), int(max_waypoints),
+                                             float(margin), float(tol), int(max_steps), _p(d_workspace),
+                                             ctypes.c_size_t(int(workspace_bytes)), int(max_blocks), _p(d_status), _p(d_count),
+                                             _p(d_waypoints), _p(d_length_in), _p(d_length_out), _p(d_iterations), _p(d_accepted),
+                                             _p(d_skipped_full), _p(d_evaluations)))
+
+    def path_shortcut_arrays(self, model, collision, waypoints, count, margin, tol, *, max_iters, min_gain=0.0, max_waypoints=None,
+                             max_steps, seed, want=None):
+        """The same on host arrays (mp_path_shortcut_host_f64) through the context's pool, workspace included: a dict of the outputs
+        named in `want` (default: all of SHORTCUT_OUTPUTS).  (Not named `*_host`, as rrt_connect_arrays is not; this entry's equality
+        with its device form is held by tests/test_gpu_shortcut.py.)"""
+        return _path_shortcut((self.handle,), self.lib.mp_path_shortcut_host_f64, model, collision, waypoints, count, margin, tol,
+                              max_iters, min_gain, max_waypoints, max_steps, seed, want)
 
     def collision_set_world(self, collision, kinds, params):
         """Replaces the obstacle table of `collision` on this context's device, behind the launches already on its stream."""
@@ -1553,6 +1581,57 @@ def cpu_rrt_connect(model: "HipModel", collision: "HipCollision", q_start, q_goa
     """CPU twin of HipContext.rrt_connect_arrays."""
     return _rrt_connect((), load_library().mp_rrt_connect_cpu_f64, model, collision, q_start, q_goal, lo, hi, margin, tol, step,
                         min_advance, max_iters, max_nodes, max_waypoints, max_steps, seed, want, nthreads)
+
+
+SHORTCUT_OUTPUTS = ("status", "count", "waypoints", "length_in", "length_out", "iterations", "accepted", "skipped_full", "evaluations")
+SHORTCUT_DONE, SHORTCUT_STRAIGHT, SHORTCUT_SKIPPED, SHORTCUT_INVALID = 0, 1, 2, -1
+
+
+def path_shortcut_workspace_bytes(n: int, max_waypoints: int, blocks: int) -> int:
+    """Bytes of path workspace for `blocks` one-wave blocks of HipContext.path_shortcut."""
+    r = int(load_library().mp_path_shortcut_workspace_bytes(int(n), int(max_waypoints), int(blocks)))
+    if r < 0:
+        _check(-r)
+    return r
+
+
+def _path_shortcut(lead, fn, model, collision, waypoints, count, margin, tol, max_iters, min_gain, max_waypoints, max_steps, seed, want,
+                   nthreads=None):
+    want = SHORTCUT_OUTPUTS if want is None else tuple(want)
+    for w in want:
+        if w not in SHORTCUT_OUTPUTS:
+            raise ValueError(f"unknown shortcut output {w!r}; choose from {SHORTCUT_OUTPUTS}")
+    wp = _as_c(waypoints, np.float64, name="waypoints")
+    if wp.ndim != 3 or wp.shape[2] != model.n:
+        raise ValueError(f"waypoints must be (problems, W, {model.n}); got {wp.shape}")
+    B, w_in, n = wp.shape
+    cnt = np.asarray(count)
+    if cnt.dtype.kind not in "iu":  # (a silent cast would turn 2.9 into 2)
+        raise TypeError(f"count must be an integer array; got {cnt.dtype}")
+    if cnt.size and (cnt.min() < np.iinfo(np.int32).min or cnt.max() > np.iinfo(np.int32).max):
+        raise ValueError("count does not fit 32 bits")
+    cnt = _as_c(cnt.astype(np.int32), np.int32, (B,), "count")
+    W = w_in if max_waypoints is None else int(max_waypoints)
+    rows = max(W, 0)  # (a value below 2 is the entry's to refuse)
+    real = ("waypoints", "length_in", "length_out")
+    out = {w: np.empty((B, rows, n) if w == "waypoints" else (B,), dtype=np.float64 if w in real else np.int32) for w in want}
+    ptrs = []
+    for w in SHORTCUT_OUTPUTS:
+        a = out.get(w)
+        ptrs.append(None if a is None else (_dptr(a) if w in real else a.ctypes.data_as(_vp)))
+    args = list(lead) + [model.handle, collision.handle, _dptr(wp), cnt.ctypes.data_as(_vp), B, w_in, int(seed), int(max_iters),
+                         float(min_gain), W, float(margin), float(tol), int(max_steps)] + ptrs
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return out
+
+
+def cpu_path_shortcut(model: "HipModel", collision: "HipCollision", waypoints, count, margin, tol, *, max_iters, min_gain=0.0,
+                      max_waypoints=None, max_steps, seed, want=None, nthreads: int = 0) -> dict:
+    """CPU twin of HipContext.path_shortcut_arrays."""
+    return _path_shortcut((), load_library().mp_path_shortcut_cpu_f64, model, collision, waypoints, count, margin, tol, max_iters,
+                          min_gain, max_waypoints, max_steps, seed, want, nthreads)
 
 
 def _pd_regulation_args(model, theta0, theta_des, Kp, Kd, g, steps):

@@ -14,13 +14,14 @@ import numpy as np
 from . import _hip
 from .registry import execute_registered_kernel
 
-__all__ = ["SphereCollisionModel", "COLLISION_OP", "EDGES_OP", "PLAN_OP"]
+__all__ = ["SphereCollisionModel", "COLLISION_OP", "EDGES_OP", "PLAN_OP", "SHORTCUT_OP"]
 
 # The registry's sorted name list starts with "control.pd_regulation" (the unknown-name message is pinned by a test), so the operation
 # lives in the "planning" family rather than in one of its own that would sort ahead of it.
 COLLISION_OP = "planning.collision_spheres"
 EDGES_OP = "planning.collision_edges"
 PLAN_OP = "planning.rrt_connect"
+SHORTCUT_OP = "planning.shortcut_paths"
 
 
 def _hip_model_of(obj) -> _hip.HipModel:
@@ -208,4 +209,25 @@ class SphereCollisionModel:
                                         np.ascontiguousarray(qg.reshape(-1, self.n)), lo, hi, margin, tol, step=step,
                                         min_advance=min_advance, max_iters=max_iters, max_nodes=max_nodes, max_waypoints=max_waypoints,
                                         max_steps=max_steps, seed=seed, want=want)
+        return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}
+
+    def shortcut_paths(self, waypoints, count, margin: float = 0.0, tol: float = 1e-3, *, max_iters: int, min_gain: float = 0.0,
+                       max_waypoints=None, max_steps: int = 64, seed: int = 0, want=None) -> dict:
+        """Randomised shortcutting of B piecewise-linear paths, waypoints (B, W, n) with count (B,) real rows each (any common leading
+        shape; `plan_paths`' "waypoints" and "count" go straight in): {"status" (0 done, 1 straight, 2 skipped: fewer than two
+        waypoints, -1 invalid), "count", "waypoints" (.., max_waypoints, n), "length_in", "length_out", "iterations", "accepted",
+        "skipped_full", "evaluations"} or the subset named in `want`.  Per iteration two points are drawn on the path by arc length;
+        if the straight motion between them is shorter by more than `min_gain` and is proven free by `check_edges`' conservative
+        advancement with this margin, tol and max_steps, it replaces the piece between them.  `max_waypoints` (None: the input's W)
+        is the room of an output path: a shortcut inside one segment pair can add a waypoint, and one that would not fit is counted
+        in "skipped_full".  Every new segment is proven free and pieces of input segments are kept, so the output is as free as the
+        input; THE INPUT IS NOT CHECKED (OptimizedTrajectoryPlanning.batch_validate_path does that).  A path is padded by repeating
+        its last waypoint.  A problem's result depends on its content and `seed` only."""
+        wp, cnt = np.asarray(waypoints, dtype=np.float64), np.asarray(count)
+        if wp.ndim < 3 or wp.shape[-1] != self.n or cnt.shape != wp.shape[:-2]:
+            raise ValueError(f"waypoints must be (..., W, {self.n}) and count its leading shape; got {wp.shape} and {cnt.shape}")
+        lead = wp.shape[:-2]
+        out = execute_registered_kernel(SHORTCUT_OP, self, np.ascontiguousarray(wp.reshape((-1,) + wp.shape[-2:])),
+                                        cnt.reshape(-1), margin, tol, max_iters=max_iters,
+                                        min_gain=min_gain, max_waypoints=max_waypoints, max_steps=max_steps, seed=seed, want=want)
         return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}

@@ -3285,6 +3285,99 @@ int mp_rrt_connect_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h,
   });
 }
 
+}  // extern "C"
+
+// ---- batched path shortcutting over the sphere model (mp_shortcut.h).  The grid: the resident blocks, ceil(B / 64), max_blocks and
+// what the workspace holds, whichever is smallest.
+static int path_shortcut_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_in,
+                              const int32_t* d_count_in, int64_t B, const MpShortcutParams& P, void* d_ws, size_t ws_bytes,
+                              int max_blocks, int32_t* d_status, int32_t* d_count, double* d_wp, double* d_len_in, double* d_len_out,
+                              int32_t* d_iters, int32_t* d_accepted, int32_t* d_full, int32_t* d_evals) {
+  REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  REQUIRE(d_in && d_count_in, "%s: null device pointer", fn);
+  REQUIRE(d_status || d_count || d_wp || d_len_in || d_len_out || d_iters || d_accepted || d_full || d_evals,
+          "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_in) && aligned16(d_count_in) && aligned16(d_status) && aligned16(d_count) && aligned16(d_wp) &&
+              aligned16(d_len_in) && aligned16(d_len_out) && aligned16(d_iters) && aligned16(d_accepted) && aligned16(d_full) &&
+              aligned16(d_evals) && aligned16(d_ws),
+          "%s: device pointers must be 16-byte aligned", fn);
+  const size_t block_bytes = (size_t)mp_path_shortcut_workspace_bytes(model->d.n, P.max_waypoints, 1);
+  REQUIRE(d_ws && ws_bytes >= block_bytes, "%s: the workspace holds %zu bytes, one block needs %zu (mp_path_shortcut_workspace_bytes)", fn,
+          d_ws ? ws_bytes : (size_t)0, block_bytes);
+  std::lock_guard<std::mutex> hl(h->mu);
+  mp_collision::Resident* R = nullptr;
+  if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
+  PROFILE_SCOPE(ctx, fn);
+  long grid = 0;
+  unsigned lds = 0;
+  HIP_TRY(mpk_path_shortcut_resident(model->d.n, h->sph.S, ctx->compute_units, &grid, &lds));
+  grid = std::min<long>(grid, (long)((B + 63) / 64));
+  if (max_blocks > 0) grid = std::min<long>(grid, max_blocks);
+  grid = std::min<long>(grid, (long)(ws_bytes / block_bytes));
+  HIP_TRY(mpk_path_shortcut(ctx->compute, model->d, h->sph.S, static_cast<const MpColSpheres*>(R->sph),
+                            reinterpret_cast<const MpColPair*>(static_cast<const char*>(R->sph) + sizeof(MpColSpheres)),
+                            static_cast<const MpColWorld*>(R->world), d_in, d_count_in, (long)B, P, d_status, d_count, d_wp, d_len_in,
+                            d_len_out, d_iters, d_accepted, d_full, d_evals, static_cast<double*>(d_ws),
+                            static_cast<unsigned long long*>(R->counter), grid, lds));
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_path_shortcut_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_waypoints_in, const int32_t* d_count_in,
+                         int64_t B, int64_t W_in, uint32_t seed, int max_iters, double min_gain, int max_waypoints, double margin,
+                         double tol, int max_steps, void* d_workspace, size_t workspace_bytes, int max_blocks, int32_t* d_status,
+                         int32_t* d_count, double* d_waypoints, double* d_length_in, double* d_length_out, int32_t* d_iterations,
+                         int32_t* d_accepted, int32_t* d_skipped_full, int32_t* d_evaluations) {
+  const char* fn = "mp_path_shortcut_f64";
+  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  MpShortcutParams P;
+  if (int rc = mp_path_shortcut_check(fn, W_in, seed, max_iters, min_gain, max_waypoints, margin, tol, max_steps, &P)) return rc;
+  return path_shortcut_impl(fn, ctx, model, h, d_waypoints_in, d_count_in, B, P, d_workspace, workspace_bytes, max_blocks, d_status,
+                            d_count, d_waypoints, d_length_in, d_length_out, d_iterations, d_accepted, d_skipped_full, d_evaluations);
+}
+
+// the workspace comes from the pool: as many blocks as the launch can use, at most 1 GiB of them (never less than one block)
+int mp_path_shortcut_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* waypoints_in, const int32_t* count_in,
+                              int64_t B, int64_t W_in, uint32_t seed, int max_iters, double min_gain, int max_waypoints, double margin,
+                              double tol, int max_steps, int32_t* status, int32_t* count, double* waypoints, double* length_in,
+                              double* length_out, int32_t* iterations, int32_t* accepted, int32_t* skipped_full, int32_t* evaluations) {
+  const char* fn = "mp_path_shortcut_host_f64";
+  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  MpShortcutParams P;
+  if (int rc = mp_path_shortcut_check(fn, W_in, seed, max_iters, min_gain, max_waypoints, margin, tol, max_steps, &P)) return rc;
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  REQUIRE(waypoints_in && count_in, "%s: null host pointer", fn);
+  long blocks = 0;
+  unsigned lds = 0;  // (the launch asks again: path_shortcut_impl)
+  HIP_TRY(mpk_path_shortcut_resident(model->d.n, h->sph.S, ctx->compute_units, &blocks, &lds));
+  const size_t n = (size_t)model->d.n, ib = (size_t)B * sizeof(int32_t), db = (size_t)B * sizeof(double);
+  const size_t block_bytes = (size_t)mp_path_shortcut_workspace_bytes(model->d.n, max_waypoints, 1);
+  blocks = std::min<long>(blocks, (long)((B + 63) / 64));
+  blocks = std::max<long>(1, std::min<long>(blocks, (long)(((size_t)1 << 30) / block_bytes)));
+  const size_t ws_bytes = (size_t)blocks * block_bytes;
+  HostCall hc(ctx);  // (h is the collision handle)
+  const double* din = hc.in(waypoints_in, (size_t)B * (size_t)W_in * n * sizeof(double));
+  const int32_t* dcin = hc.in(count_in, ib);
+  int32_t *dstatus = hc.out(status, ib), *dcount = hc.out(count, ib);
+  double* dwp = hc.out(waypoints, (size_t)B * (size_t)max_waypoints * n * sizeof(double));
+  double *dli = hc.out(length_in, db), *dlo = hc.out(length_out, db);
+  int32_t *dit = hc.out(iterations, ib), *dacc = hc.out(accepted, ib), *dfull = hc.out(skipped_full, ib), *dev = hc.out(evaluations, ib);
+  void* dws = hc.work(ws_bytes);
+  return hc.run([&] {
+    return path_shortcut_impl(fn, ctx, model, h, din, dcin, B, P, dws, ws_bytes, 0, dstatus, dcount, dwp, dli, dlo, dit, dacc, dfull, dev);
+  });
+}
+
 int mp_collision_set_world(mp_ctx* ctx, mp_collision* h, int O, const int32_t* kind, const double* params) {
   const char* fn = "mp_collision_set_world";
   REQUIRE(h, "%s: null collision handle", fn);

@@ -1362,3 +1362,72 @@ int mp_rrt_connect_cpu_f64(const mp_model* model, const mp_collision* h, const d
 }
 
 }  // extern "C"
+
+// ---- batched path shortcutting over the sphere model (mp_shortcut.h)
+int mp_path_shortcut_check(const char* fn, int64_t w_in, uint32_t seed, int max_iters, double min_gain, int max_waypoints, double margin,
+                           double tol, int max_steps, MpShortcutParams* out) {
+  if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
+  if (w_in < 1 || w_in > MP_SC_MAX_WAYPOINTS) return col_fail("%s: %ld input rows a path, outside 1..65536", fn, (long)w_in);
+  if (max_iters < 0) return col_fail("%s: negative max_iters", fn);
+  if (!(min_gain >= 0.0) || !std::isfinite(min_gain)) return col_fail("%s: min_gain must be non-negative and finite", fn);
+  if (max_waypoints < 2 || max_waypoints > MP_SC_MAX_WAYPOINTS) return col_fail("%s: max_waypoints %ld outside 2..65536", fn, max_waypoints);
+  MpShortcutParams P;
+  std::memset(&P, 0, sizeof P);
+  P.edge = {margin, tol, max_steps, 0};
+  P.min_gain = min_gain;
+  P.seed = seed; P.max_iters = max_iters; P.max_waypoints = max_waypoints; P.w_in = (int)w_in;
+  *out = P;
+  return MP_OK;
+}
+
+extern "C" {
+
+int64_t mp_path_shortcut_workspace_bytes(int n, int max_waypoints, int blocks) {
+  const char* fn = "mp_path_shortcut_workspace_bytes";
+  if (n < 1) return -(int64_t)col_fail("%s: joint count %ld below 1", fn, n);
+  if (n > MP_MAX_DOF) {
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, n);
+    return -(int64_t)mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (max_waypoints < 2 || max_waypoints > MP_SC_MAX_WAYPOINTS)
+    return -(int64_t)col_fail("%s: max_waypoints %ld outside 2..65536", fn, max_waypoints);
+  if (blocks < 1) return -(int64_t)col_fail("%s: block count %ld below 1", fn, blocks);
+  return (int64_t)blocks * 64 * (int64_t)max_waypoints * (8 * (int64_t)n + 8);
+}
+
+int mp_path_shortcut_cpu_f64(const mp_model* model, const mp_collision* h, const double* waypoints_in, const int32_t* count_in, int64_t B,
+                             int64_t W_in, uint32_t seed, int max_iters, double min_gain, int max_waypoints, double margin, double tol,
+                             int max_steps, int32_t* status, int32_t* count, double* waypoints, double* length_in, double* length_out,
+                             int32_t* iterations, int32_t* accepted, int32_t* skipped_full, int32_t* evaluations, int nthreads) {
+  const char* fn = "mp_path_shortcut_cpu_f64";
+  if (!model || !h) return col_fail("%s: null model or collision handle", fn);
+  if (model->big) {
+    char msg[192];
+    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
+    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+  }
+  if (h->n != model->d.n) return col_fail("%s: the collision handle was made for a model of %ld joints", fn, h->n);
+  MpShortcutParams P;
+  if (int rc = mp_path_shortcut_check(fn, W_in, seed, max_iters, min_gain, max_waypoints, margin, tol, max_steps, &P)) return rc;
+  if (B < 0) return col_fail("%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  if (!waypoints_in || !count_in) return col_fail("%s: null pointer", fn);
+  if (!status && !count && !waypoints && !length_in && !length_out && !iterations && !accepted && !skipped_full && !evaluations)
+    return col_fail("%s: at least one output is required", fn);
+  const MpModel<double>& M = model->d;
+  const MpColWorld hdr = {(int)h->world.size(), {0, 0, 0}};
+  const MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*> tb = {&h->sph, h->pairs.data(), &hdr,
+                                                                                                          h->world.data()};
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
+      std::vector<double> pts((size_t)max_waypoints * N), cum((size_t)max_waypoints);  // the thread's path, reused like a lane's
+      for (int64_t b = b0; b < b1; ++b)
+        mp_shortcut_cpu<N>(M, tb, P, waypoints_in, count_in, (long)b, pts.data(), cum.data(), status, count, waypoints, length_in,
+                           length_out, iterations, accepted, skipped_full, evaluations);
+    });
+  })
+  return MP_OK;
+}
+
+}  // extern "C"

@@ -7,6 +7,7 @@
 
 #include "mp_collision.h"
 #include "mp_rrt.h"
+#include "mp_shortcut.h"
 #include "mp_model.h"
 
 struct mp_model {
@@ -45,5 +46,8 @@ int mp_collision_edges_check(const char* fn, double margin, double tol, int max_
 // the planner's parameters (the edge check's among them), packed into `out`; 0, or MP_ERR_INVALID with the message set (mp_cpu.cpp)
 int mp_rrt_connect_check(const char* fn, int n, const double* lo, const double* hi, uint32_t seed, double step, double min_advance,
                          int max_iters, int max_nodes, int max_waypoints, double margin, double tol, int max_steps, MpRrtParams* out);
+// the shortcutter's parameters (the edge check's among them), packed into `out`; 0, or MP_ERR_INVALID with the message set (mp_cpu.cpp)
+int mp_path_shortcut_check(const char* fn, int64_t w_in, uint32_t seed, int max_iters, double min_gain, int max_waypoints, double margin,
+                           double tol, int max_steps, MpShortcutParams* out);
 
 int mp_set_error(int code, const char* msg);  // thread-local message of mp_last_error (mp_capi.cpp; C++ linkage)

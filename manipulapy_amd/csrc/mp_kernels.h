@@ -201,3 +201,14 @@ hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, int S, const
                            const MpColWorld* d_world, const double* q_start, const double* q_goal, long problems, const MpRrtParams& P,
                            int* status, int* count, double* waypoints, int* iterations, int* nodes, int* evaluations, double* workspace,
                            unsigned long long* queue_counter, int compute_units, long blocks);
+// batched path shortcutting over the sphere model (csrc/mp_shortcut.h): the same queue, one evaluated configuration a trip, the
+// working paths in `workspace` (blocks x 64 x max_waypoints (8 n + 8) bytes); queue_counter is zeroed on the stream first.  The
+// caller settles the grid (`blocks`) from mpk_path_shortcut_resident, the problem count, its cap and the workspace, and hands the
+// dynamic LDS size it got there (`lds`) on to the launch.
+struct MpShortcutParams;
+hipError_t mpk_path_shortcut_resident(int n, int S, int compute_units, long* blocks, unsigned* lds);
+hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
+                             const MpColWorld* d_world, const double* waypoints_in, const int* count_in, long problems,
+                             const MpShortcutParams& P, int* status, int* count, double* waypoints, double* length_in,
+                             double* length_out, int* iterations, int* accepted, int* skipped_full, int* evaluations,
+                             double* workspace, unsigned long long* queue_counter, long blocks, unsigned lds);

@@ -24,6 +24,7 @@
 #include "mp_toppra.h"
 #include "mp_collision.h"
 #include "mp_rrt.h"
+#include "mp_shortcut.h"
 
 namespace {
 
@@ -598,6 +599,90 @@ __global__ __launch_bounds__(64) void k_rrt_connect(const MpModel<double> M, con
       if (evaluations != nullptr) evaluations[row] = S.evals;
       have = false;
       S.phase = MP_RRT_IDLE;
+    }
+  }
+}
+
+// ------------------------------------------------------- batched path shortcutting over the sphere model (float64, mp_shortcut.h)
+// One wave per block and the work queue of k_collision_edges / k_rrt_connect: a lane without a problem takes the next index from the
+// device counter, every trip of the loop does the selection work the lane's problem is waiting for and evaluates ONE configuration
+// of its running edge, and a finished lane writes its row and fetches another.  Dynamic LDS: the park and the speed bounds, laid out
+// exactly as in k_collision_edges.  The working path lives in the caller's workspace and belongs to the resident lane, not to the
+// problem: per block the waypoints [waypoint][dim][lane] (doubles), then the cumulative lengths [waypoint][lane]; a lane that takes
+// a new problem copies its count_in rows in.  Each lane reads and writes only its own column, in program order, so no barrier or
+// fence is needed.  The locate scan (mp_shortcut_locate) is entered by all 64 lanes on every pass and runs to the wave's largest m,
+// so the wave reads whole 512-byte lines; the splice and the recomputation of the lengths after an accepted shortcut are per lane.
+// The loop of the kernel ends for the whole wave at once, when no lane holds a problem and the queue is empty.
+struct MpShortcutPathLanes {
+  double* pts;  // already offset by the block and the lane
+  double* cum;
+  int n;
+  __device__ __forceinline__ double get(int w, int j) const { return pts[((long)w * n + j) * 64]; }
+  __device__ __forceinline__ void put(int w, int j, double x) { pts[((long)w * n + j) * 64] = x; }
+  __device__ __forceinline__ double len(int w) const { return cum[(long)w * 64]; }
+  __device__ __forceinline__ void set_len(int w, double x) { cum[(long)w * 64] = x; }
+  __device__ __forceinline__ int wave_max(int v) const {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int w = __shfl_xor(v, o);
+      v = w > v ? w : v;
+    }
+    return v;
+  }
+  __device__ __forceinline__ bool wave_any(bool b) const { return __any(b ? 1 : 0) != 0; }
+};
+
+template <int N>
+__global__ __launch_bounds__(64) void k_path_shortcut(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
+                                                      const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
+                                                      const double* __restrict__ waypoints_in, const int* __restrict__ count_in,
+                                                      long problems, const MpShortcutParams P, int* __restrict__ status,
+                                                      int* __restrict__ count, double* __restrict__ waypoints,
+                                                      double* __restrict__ length_in, double* __restrict__ length_out,
+                                                      int* __restrict__ iterations, int* __restrict__ accepted,
+                                                      int* __restrict__ skipped_full, int* __restrict__ evaluations,
+                                                      double* __restrict__ workspace, unsigned long long* __restrict__ next) {
+  extern __shared__ __attribute__((aligned(16))) double mp_shortcut_lds[];
+  const int lane = (int)threadIdx.x;
+  const MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*> tb = {
+      (MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
+  MpColParkLanes park{mp_shortcut_lds + lane};
+  MpColBoundsLanes L{mp_shortcut_lds + 3 * 64 * tb.sph->S + lane};
+  const size_t point_words = (size_t)P.max_waypoints * N * 64;           // doubles a block
+  const size_t block_words = point_words + (size_t)P.max_waypoints * 64;  // + the lengths
+  double* const mine = workspace + (size_t)blockIdx.x * block_words;
+  MpShortcutPathLanes T{mine + lane, mine + point_words + lane, N};
+  MpShortcutState<N> S;
+  S.phase = MP_SC_IDLE;
+  S.done = 0;
+  S.m = 0;
+  bool have = false, dry = false;
+  long row = 0;
+  for (;;) {
+    if (!have && !dry) {
+      row = (long)atomicAdd(next, 1ull);
+      if (row >= problems) {
+        dry = true;
+      } else {
+        mp_shortcut_begin<N>(P, waypoints_in + row * (long)P.w_in * N, count_in[row], S, T,
+                             waypoints != nullptr ? waypoints + row * (long)P.max_waypoints * N : nullptr);
+        have = true;
+      }
+    }
+    if (!T.wave_any(have)) break;
+    double* wp = (have && waypoints != nullptr) ? waypoints + row * (long)P.max_waypoints * N : nullptr;
+    if (mp_shortcut_trip<N>(M, tb, P, S, T, park, L, wp)) {
+      if (status != nullptr) status[row] = S.status;
+      if (count != nullptr) count[row] = S.m;
+      if (length_in != nullptr) length_in[row] = S.lam_in;
+      if (length_out != nullptr) length_out[row] = S.m > 0 ? T.len(S.m - 1) : __builtin_nan("");
+      if (iterations != nullptr) iterations[row] = S.k;
+      if (accepted != nullptr) accepted[row] = S.accepted;
+      if (skipped_full != nullptr) skipped_full[row] = S.skipped_full;
+      if (evaluations != nullptr) evaluations[row] = S.evals;
+      have = false;
+      S.phase = MP_SC_IDLE;
+      S.m = 0;
     }
   }
 }
@@ -1528,6 +1613,49 @@ hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, int S, const
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_rrt_connect<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, d_sph, d_pairs, d_world, q_start, q_goal, problems,
                        P, status, count, waypoints, iterations, nodes, evaluations, workspace, queue_counter);
+  })
+  return hipGetLastError();
+}
+
+// the one-wave blocks of k_path_shortcut the device keeps resident (LDS as for the edge kernel)
+template <int N>
+static hipError_t shortcut_resident(int S, int compute_units, unsigned* lds_out, long* blocks) {
+  const unsigned lds = (unsigned)(3 * S + N * (N + 1) / 2) * 64u * (unsigned)sizeof(double);
+  const void* fn = reinterpret_cast<const void*>(&k_path_shortcut<N>);
+  if (lds > 64u * 1024u) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  int per_cu = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds);
+  if (e != hipSuccess) return e;
+  *lds_out = lds;
+  *blocks = (long)(per_cu > 0 ? per_cu : 1) * (compute_units > 0 ? compute_units : 256);
+  return hipSuccess;
+}
+
+hipError_t mpk_path_shortcut_resident(int n, int S, int compute_units, long* blocks, unsigned* lds) {
+  if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
+  MP_DISPATCH_N(n, { return shortcut_resident<N>(S, compute_units, lds, blocks); })
+  return hipErrorInvalidValue;
+}
+
+// `blocks`: the grid the caller has settled on (mpk_path_shortcut_resident, the problem count, max_blocks and the workspace); `lds`:
+// the dynamic LDS mpk_path_shortcut_resident gave (it has raised the kernel's limit where that is needed), so the launch itself
+// makes no further runtime query
+hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
+                             const MpColWorld* d_world, const double* waypoints_in, const int* count_in, long problems,
+                             const MpShortcutParams& P, int* status, int* count, double* waypoints, double* length_in,
+                             double* length_out, int* iterations, int* accepted, int* skipped_full, int* evaluations,
+                             double* workspace, unsigned long long* queue_counter, long blocks, unsigned lds) {
+  if (problems <= 0) return hipSuccess;
+  if (S < 1 || S > MP_COL_MAX_SPHERES || blocks < 1) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(queue_counter, 0, sizeof(unsigned long long), s);
+  if (e != hipSuccess) return e;
+  MP_DISPATCH_N(M.n, {
+    hipLaunchKernelGGL((k_path_shortcut<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, d_sph, d_pairs, d_world, waypoints_in, count_in,
+                       problems, P, status, count, waypoints, length_in, length_out, iterations, accepted, skipped_full, evaluations,
+                       workspace, queue_counter);
   })
   return hipGetLastError();
 }

@@ -593,6 +593,22 @@ class OptimizedTrajectoryPlanning:
                               tol, step=step, min_advance=min_advance, max_iters=max_iters, max_nodes=max_nodes,
                               max_waypoints=max_waypoints, max_steps=max_steps, seed=seed)
 
+    def batch_shortcut_path(self, waypoints, count, collision_model, margin: float = 0.0, tol: float = 1e-3, *, max_iters: int = 100,
+                            min_gain: float = 0.0, max_waypoints=None, max_steps: int = 64, seed: int = 0) -> Dict[str, np.ndarray]:
+        """Shortens B piecewise-linear joint-space paths (B, W, n) with `count` (B,) real waypoints each - `batch_plan_path`'s
+        "waypoints" and "count" - by randomised shortcutting under a collision.SphereCollisionModel (SphereCollisionModel.
+        shortcut_paths), all B paths in one launch.  {"status", "count", "waypoints" (B, max_waypoints or W, n), "length_in",
+        "length_out", "iterations", "accepted", "skipped_full", "evaluations"}: rows that were not solved come back skipped, and
+        "waypoints" can go straight into `batch_validate_path`.  The input paths themselves are not checked."""
+        wp = np.asarray(waypoints, dtype=np.float64)
+        cnt = np.asarray(count)
+        n = collision_model.n
+        if wp.ndim != 3 or wp.shape[2] != n or cnt.shape != (wp.shape[0],):
+            raise ValueError(f"waypoints must be (B, W, {n}) and count (B,); got {wp.shape} and {cnt.shape}")
+        return self._dispatch("planning.shortcut_paths", collision_model, np.ascontiguousarray(wp),
+                              cnt, margin, tol, max_iters=max_iters, min_gain=min_gain,
+                              max_waypoints=max_waypoints, max_steps=max_steps, seed=seed)
+
     # ------------------------------------------------------------------ legacy dynamics objects (Mlist_per_link=None)
     # The reference's approximation for such objects is not rigid-body dynamics (dynamics/mass_matrix.py:101-132), so there
     # is no compiled model and no kernel for it: the planner walks the rows on the host exactly as the reference's CPU

@@ -323,6 +323,10 @@ def _launch_rrt_connect_cpu(cm, q_start, q_goal, lo, hi, margin, tol, **kw):
     return _hip.cpu_rrt_connect(cm.model, cm.handle, q_start, q_goal, lo, hi, margin, tol, **kw)
 
 
+def _launch_path_shortcut_cpu(cm, waypoints, count, margin, tol, **kw):
+    return _hip.cpu_path_shortcut(cm.model, cm.handle, waypoints, count, margin, tol, **kw)
+
+
 def _launch_opspace_cpu(model, q, qd, g=None, frame="hybrid", task="full", damping=0.0, want=_hip.OPSPACE_OUTPUTS):
     return _hip.cpu_opspace(model, q, qd, g, frame, task, damping, want)
 
@@ -498,6 +502,12 @@ def _launch_rrt_connect_gpu(cm, q_start, q_goal, lo, hi, margin, tol, **kw):
     return ctx.rrt_connect_arrays(cm.model, cm.handle, q_start, q_goal, lo, hi, margin, tol, **kw)
 
 
+def _launch_path_shortcut_gpu(cm, waypoints, count, margin, tol, **kw):
+    ctx = get_context()
+    cm.sync_world(ctx)
+    return ctx.path_shortcut_arrays(cm.model, cm.handle, waypoints, count, margin, tol, **kw)
+
+
 def _launch_fk_jac_vjp_gpu(model, q, gT=None, gJ=None, frame="space", want_T=False, want_J=False, want_gq=True):
     return get_context().fk_jac_vjp_host(model, q, gT, gJ, frame, want_T, want_J, want_gq)
 
@@ -637,6 +647,9 @@ def _build_kernel_registry() -> KernelRegistry:
         # batched RRT-Connect over the sphere model, every tree edge proven by the edge check (csrc/mp_rrt.h); the name sorts after
         # the pinned head of the name list
         ("planning.rrt_connect", "mp_rrt_connect_host_f64", _launch_rrt_connect_gpu, _launch_rrt_connect_cpu),
+        # batched shortcutting of the planner's paths, every new segment proven by the edge check (csrc/mp_shortcut.h); the name sorts
+        # after the pinned head of the name list
+        ("planning.shortcut_paths", "mp_path_shortcut_host_f64", _launch_path_shortcut_gpu, _launch_path_shortcut_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):
