@@ -335,3 +335,233 @@ def toppra_not_stalling(res):
     x = np.asarray(res["sd2"], dtype=np.float64)
     with np.errstate(invalid="ignore"):
         return (np.asarray(res["status"]) == 0) & (x[:, 1:-1].min(axis=1) > TOPPRA_STALL * x.max(axis=1))
+
+
+# ------------------------------------------------------------------------------------------------ RRT-Connect
+# rrt_cases' recipe (make_plan_case) on the model of edge_case(n) - the spheres of collision_model(n) with the pairs chosen at
+# collision_edge_cases.PAIR_CLEARANCE, the world of seed 103 - in the box of the chain's own joint limits (prismatic joints +-0.4):
+# PLAN_PROBLEMS = 67 problems a chain (one wave and three lanes), starts and goals clear by more than margin + 0.03, one start (problem
+# PLAN_PLANTED_START) and one goal (problem PLAN_PLANTED_GOAL, in the second wave) at or below the margin; margin, tol, step, min_advance,
+# max_steps and seed are rrt_cases' own.  The settings are reduced - max_iters 48, max_nodes 64, max_waypoints 64 - because the NumPy oracle
+# at rrt_cases' 131 problems and 200 iterations takes half a minute to a minute and a half a chain in float64 alone.
+# Measured (float64 oracle; identical discrete outputs in longdouble above the gap, no problem below rrt_cases.GAP; the two planted rows
+# are START_BLOCKED and GOAL_BLOCKED on every chain; TREE_FULL / PATH_TOO_LONG: problems of the twin at max_nodes 4 / max_waypoints 2):
+#     n  spheres  max_iters  seed  k = 0  later  exhausted  largest tree  most waypoints  evaluations mean / max  smallest gap
+#     1  18       48         31    47     0      18         19            2               230 / 914              7.5e-7
+#     2  31       48         31    34     5      26         24            9               524 / 1779             1.4e-7
+#     3  17       48         31    29     32     4          27            12              175 / 1271             2.0e-8
+#     4  51       16         31    13     11     41         12            10              488 / 1029             2.1e-8
+#     5  62       16         31    5      8      52         12            12              520 / 966              9.3e-8
+#     6  51       16         33    12     7      46         13            13              515 / 1139             8.9e-8
+#     7  43       16         32    9      13     43         14            14              570 / 1328             9.8e-8
+#     8  57       16         33    7      7      51         11            10              392 / 940              5.0e-8
+#     n  oracle float64 - longdouble waypoints  twin - oracle waypoints  TREE_FULL  PATH_TOO_LONG
+#     1  0                                      0                        18         0  (one joint: two waypoints or no path)
+#     2  3.9e-16                                1.6e-15                  31         5
+#     3  1.5e-14                                5.4e-14                  21         32
+#     4  2.7e-15                                3.1e-14                  46         11
+#     5  1.9e-15                                3.0e-14                  55         8
+#     6  9.9e-16                                7.0e-15                  50         7
+#     7  1.2e-14                                1.9e-14                  49         13
+#     8  9.5e-16                                1.2e-14                  51         7
+# Every chain stays within rrt_cases.MEASURED_WAYPOINT (2.3e-13), so the module's bound applies unchanged and no chain has a constant of
+# its own.
+PLAN_PROBLEMS = 67
+PLAN_PLANTED_START, PLAN_PLANTED_GOAL = 5, 65
+PLAN_MAX_NODES, PLAN_MAX_WAYPOINTS = 64, 64
+# max_iters per chain: 48, cut to 16 on the chains of 43 to 62 spheres and 463 to 979 pairs (n = 4..8), where an evaluation costs the
+# oracle and the kernel several times what it costs on the small chains (at 48 the longdouble oracle alone took 20 to 30 s a chain and
+# a GPU test 7 to 16 s)
+PLAN_MAX_ITERS = {1: 48, 2: 48, 3: 48, 4: 16, 5: 16, 6: 16, 7: 16, 8: 16}
+# the first case seed (31, 32, ...: rrt_cases.CASE_SEEDS starts at 31) whose case meets the conditions test_chain_cases_host.py asserts,
+# the tight shortcut run's skipped_full > 0 among them, at the chain's own PLAN_MAX_ITERS and SHORTCUT_MAX_ITERS (on n = 6 and 8 seed 31
+# solves only 4 problems after k >= 1 and seed 32 leaves the tight run without a shortcut skipped for room, as seed 31 does on n = 7)
+PLAN_SEED = {1: 31, 2: 31, 3: 31, 4: 31, 5: 31, 6: 33, 7: 32, 8: 33}
+# n = 1 only: in the world of seed 103 all 65 free pairs of the one-joint chain connect directly and no tree ever grows - a
+# one-dimensional planner connects at k = 0 or never.  This is the first world seed (103, 104, ...) in which the chain's free set has two
+# components, so that some pairs are solved directly (47) and some are EXHAUSTED (18).
+PLAN_WORLD_SEED_1 = 104
+
+
+@functools.lru_cache(maxsize=None)
+def plan_model(n, world_seed=None):
+    """(SphereCollisionModel, S_list, the oracle's Model) the planning cases of chain(n) run on."""
+    import collision_edge_cases as ec
+
+    cm, S_list, _ = collision_model(n, ec.PAIR_CLEARANCE)
+    seed = (PLAN_WORLD_SEED_1 if n == 1 else 103) if world_seed is None else world_seed
+    if seed != 103:                                       # (collision_model's own handle keeps the world of seed 103)
+        cm = SphereCollisionModel(cm.model, cm.links, cm.centres, cm.radii, cm.pairs)
+        sp, ca, bx = cc.make_world(seed)
+        cm.set_world(spheres=sp, capsules=ca, boxes=bx)
+    return cm, S_list, ec.Model(S_list, cm)
+
+
+def plan_params(n, **over):
+    import rrt_cases as rc
+
+    p = dict(step=rc.STEP, min_advance=rc.MIN_ADVANCE, max_waypoints=PLAN_MAX_WAYPOINTS, max_steps=rc.MAX_STEPS, seed=rc.SEED,
+             max_iters=PLAN_MAX_ITERS[n], max_nodes=PLAN_MAX_NODES)
+    p.update(over)
+    return p
+
+
+@functools.lru_cache(maxsize=None)
+def plan_case(n, seed=None, world_seed=None):
+    """{"cm", "S_list", "model", "lo", "hi", "qs", "qg" (PLAN_PROBLEMS, n), "n"} by the recipe above (shared: treat as read-only)."""
+    import rrt_cases as rc
+
+    cm, S_list, model = plan_model(n, world_seed)
+    lim = chain(n)[2]
+    lo, hi = np.ascontiguousarray(lim[:, 0]), np.ascontiguousarray(lim[:, 1])
+    rng = np.random.default_rng(PLAN_SEED[n] if seed is None else seed)
+    B = PLAN_PROBLEMS
+    free_rows, low_rows = [], []
+    while sum(map(len, free_rows)) < 2 * B or sum(map(len, low_rows)) < 2:
+        pool = rng.uniform(lo, hi, (4096, n))
+        ev = model.evaluate(pool, None, rc.MARGIN, np.float64)
+        c = np.minimum(ev["dist_world"], ev["dist_self"])
+        free_rows.append(pool[c > rc.MARGIN + 0.03])
+        low_rows.append(pool[c <= rc.MARGIN])
+    free, low = np.concatenate(free_rows), np.concatenate(low_rows)
+    qs, qg = free[:B].copy(), free[B:2 * B].copy()
+    qs[PLAN_PLANTED_START], qg[PLAN_PLANTED_GOAL] = low[0], low[1]
+    return {"cm": cm, "S_list": S_list, "model": model, "lo": lo, "hi": hi, "qs": np.ascontiguousarray(qs),
+            "qg": np.ascontiguousarray(qg), "n": n}
+
+
+def _frozen(over):
+    return tuple(sorted(over.items()))
+
+
+@functools.lru_cache(maxsize=None)
+def _plan_oracle(n, long, over, seed, world_seed):
+    import rrt_cases as rc
+
+    case = plan_case(n, seed, world_seed)
+    return rc.plan(case["model"], case["qs"], case["qg"], case["lo"], case["hi"], dt=np.longdouble if long else np.float64,
+                   **plan_params(n, **dict(over)))
+
+
+def plan_oracle(n, long=False, seed=None, world_seed=None, **over):
+    """rrt_cases.plan on the whole case (computed once and shared: treat as read-only); `over` replaces settings of plan_params."""
+    return _plan_oracle(n, long, _frozen(over), seed, world_seed)
+
+
+@functools.lru_cache(maxsize=None)
+def _plan_twin(n, over, seed, world_seed):
+    import rrt_cases as rc
+
+    case = plan_case(n, seed, world_seed)
+    cm = case["cm"]
+    return _hip.cpu_rrt_connect(cm.model, cm.handle, case["qs"], case["qg"], case["lo"], case["hi"], rc.MARGIN, rc.TOL,
+                                **plan_params(n, **dict(over)))
+
+
+def plan_twin(n, seed=None, world_seed=None, **over):
+    """The CPU twin on the whole case (computed once and shared: treat as read-only)."""
+    return _plan_twin(n, _frozen(over), seed, world_seed)
+
+
+# ------------------------------------------------------------------------------------------------ path shortcutting
+# The inputs: the planner twin's 67 rows of plan_case(n) widened by its own padding to shortcut_cases.W_IN = 66 rows, shortcut_cases' four
+# planted rows (the first two waypoints of the longest solved path; that path with a NaN; 65 points along a direct solution; the longest
+# path with its second waypoint repeated) and two more:
+#     SHORTCUT_PLANTED_ZERO   three identical waypoints (Lambda = 0: both draws are 0, no locate finds a segment, nothing is evaluated)
+#     SHORTCUT_PLANTED_FULL   the longest solved path with its padding counted in: count = max_waypoints = 64 exactly, the tail zero-length
+#                             segments (a shortcut between neighbouring segments would add a waypoint and has no room: skipped_full
+#                             in the NORMAL run, and a splice that fits moves a tail that ends in the row's last slot)
+# shortcut max_iters 50; the other settings are shortcut_cases' own.  The tight run has max_waypoints = the largest count among the
+# planner's rows.  On n = 1 every path is a straight segment of two waypoints (the planner's rows are STRAIGHT or SKIPPED only, the
+# "longest" path is a direct one) and the tight run is 2 waypoints wide.
+# Measured (float64 oracle, normal run / tight run; identical discrete outputs in longdouble, no problem below shortcut_cases.GAP; the
+# twin equals the float64 oracle in every bit of the waypoints and lengths on every chain):
+#     n  tight max_waypoints  done     straight  skipped  invalid  with an accepted shortcut  skipped for room  evaluations max  float64 - longdouble waypoints / lengths
+#     1  2                    3 / 0    48 / 48   20 / 20  2 / 5    0 / 0                      0 / 0             0                0 / 0
+#     2  9                    8 / 6    35 / 35   28 / 28  2 / 4    7 / 5                      15 / 15           949 / 863        7.3e-16 / 8.6e-16
+#     3  12                   35 / 33  30 / 30   6 / 6    2 / 4    34 / 32                    1 / 3             1230             7.0e-16 / 1.7e-15
+#     4  10                   14 / 12  14 / 14   43 / 43  2 / 4    13 / 11                    1 / 1             576              5.1e-16 / 7.6e-16
+#     5  12                   11 / 9   6 / 6     54 / 54  2 / 4    10 / 8                     0 / 2             757              5.3e-16 / 6.7e-16
+#     6  13                   10 / 8   13 / 13   48 / 48  2 / 4    9 / 7                      1 / 2             732 / 727        3.0e-16 / 4.7e-16
+#     7  14                   16 / 14  10 / 10   45 / 45  2 / 4    15 / 13                    0 / 2             715              6.3e-16 / 8.8e-16
+#     8  10                   10 / 8   8 / 8     53 / 53  2 / 4    9 / 7                      1 / 1             780              4.4e-16 / 9.8e-16
+# Every chain stays within shortcut_cases.MEASURED_WAYPOINT (3.6e-15) and MEASURED_LENGTH (5.6e-15), so the module's bounds apply
+# unchanged and no chain has a constant of its own.  skipped_full > 0 in the tight run holds on every chain 2..8.
+SHORTCUT_MAX_ITERS = {1: 50, 2: 50, 3: 50, 4: 20, 5: 20, 6: 20, 7: 20, 8: 20}       # cut on the large chains, as PLAN_MAX_ITERS is
+SHORTCUT_PLANTED_TWO, SHORTCUT_PLANTED_NAN, SHORTCUT_PLANTED_LONG, SHORTCUT_PLANTED_REPEAT, SHORTCUT_PLANTED_ZERO, SHORTCUT_PLANTED_FULL = (
+    PLAN_PROBLEMS + k for k in range(6))
+SHORTCUT_PROBLEMS = PLAN_PROBLEMS + 6
+# the chains on which the normal run skips a shortcut for room on SHORTCUT_PLANTED_FULL (elsewhere no iteration of that row draws a
+# gainful pair of neighbouring segments); test_chain_cases_host.py asserts that this is what the oracle says
+SHORTCUT_FULL_BITES = (2, 3, 4, 6, 8)
+
+
+def shortcut_params(n, **over):
+    import shortcut_cases as sc
+
+    return sc.params_of(**{"max_iters": SHORTCUT_MAX_ITERS[n], **over})
+
+
+@functools.lru_cache(maxsize=None)
+def shortcut_case(n, seed=None, world_seed=None):
+    """{"cm", "model", "n", "waypoints" (SHORTCUT_PROBLEMS, W_IN, n), "count" int32, "plan_status", "tight": the tight run's
+    max_waypoints} (computed once and shared: treat as read-only)."""
+    import rrt_cases as rc
+    import shortcut_cases as sc
+
+    case, plan = plan_case(n, seed, world_seed), plan_twin(n, seed, world_seed)
+    W = sc.MAX_WAYPOINTS
+    wp = np.concatenate([plan["waypoints"], np.repeat(plan["waypoints"][:, -1:], sc.W_IN - plan["waypoints"].shape[1], axis=1)], axis=1)
+    count = plan["count"].astype(np.int32)
+    solved = plan["status"] == rc.SOLVED
+    longest = int(np.argmax(np.where(solved, count, 0)))
+    direct = int(np.flatnonzero(solved & (count == 2))[0])
+    L = int(count[longest])
+    assert 2 <= L < W and (L >= 3 or n == 1)
+    planted = np.repeat(wp[longest][None], 6, axis=0)
+    pc = np.array([2, L, W + 1, L + 1, 3, W], dtype=np.int32)
+    planted[1, 1, n // 2] = np.nan
+    a, b = wp[direct, 0], wp[direct, 1]
+    planted[2] = b
+    planted[2, :W + 1] = a + np.linspace(0.0, 1.0, W + 1)[:, None] * (b - a)
+    planted[2, W] = b
+    planted[3, 2:] = wp[longest, 1:-1]
+    planted[4] = wp[longest, 0]
+    return {"cm": case["cm"], "model": case["model"], "n": n, "waypoints": np.ascontiguousarray(np.concatenate([wp, planted])),
+            "count": np.concatenate([count, pc]), "plan_status": plan["status"], "tight": int(count[solved].max())}
+
+
+def _shortcut_over(n, tight, over, seed=None, world_seed=None):
+    over = dict(over)
+    if tight:
+        over.setdefault("max_waypoints", shortcut_case(n, seed, world_seed)["tight"])
+    return over
+
+
+@functools.lru_cache(maxsize=None)
+def _shortcut_oracle(n, long, tight, over, seed, world_seed):
+    import shortcut_cases as sc
+
+    case = shortcut_case(n, seed, world_seed)
+    return sc.shortcut(case["model"], case["waypoints"], case["count"], dt=np.longdouble if long else np.float64,
+                       **shortcut_params(n, **_shortcut_over(n, tight, over, seed, world_seed)))
+
+
+def shortcut_oracle(n, long=False, tight=False, seed=None, world_seed=None, **over):
+    """shortcut_cases.shortcut on the whole case (computed once and shared: treat as read-only)."""
+    return _shortcut_oracle(n, long, tight, _frozen(over), seed, world_seed)
+
+
+@functools.lru_cache(maxsize=None)
+def _shortcut_twin(n, tight, over, seed, world_seed):
+    import shortcut_cases as sc
+
+    case = shortcut_case(n, seed, world_seed)
+    cm = case["cm"]
+    return _hip.cpu_path_shortcut(cm.model, cm.handle, case["waypoints"], case["count"], sc.MARGIN, sc.TOL,
+                                  **shortcut_params(n, **_shortcut_over(n, tight, over, seed, world_seed)))
+
+
+def shortcut_twin(n, tight=False, seed=None, world_seed=None, **over):
+    """The CPU twin on the whole case (computed once and shared: treat as read-only)."""
+    return _shortcut_twin(n, tight, _frozen(over), seed, world_seed)

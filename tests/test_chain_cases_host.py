@@ -3,7 +3,9 @@ the families whose host tests only know the four arms and all-revolute chains.  
 
 Each test first re-measures the oracle's own float64-against-longdouble difference on the new case and holds it to twice the constant
 the family's bound was sized from (as test_oracle_float64_error_is_what_the_bound_was_sized_from does), then applies the family's
-existing rule with its existing bound."""
+existing rule with its existing bound.  The planner and the shortcutter (chain_cases.plan_case / shortcut_case) are also held to the
+oracle at the limits - max_nodes 4 and 2, max_waypoints 3 and 2, max_iters 0, the tight shortcut run - and their paths to the edge
+checker; the slowest of these tests takes 18 s (the planner's float64 and longdouble oracles on n = 5)."""
 import numpy as np
 import pytest
 
@@ -246,3 +248,148 @@ def test_toppra_twin_matches_the_oracle(n, N):
         assert excess <= 10 * measured and activity >= 1.0 - 10 * measured          # rule (c), toppra_cases.rule_c with this chain's constant
         tc.f64_rule(full["sd2"], want["sd2"], "sd2 end to end")
         tc.f64_rule(full["duration"], want["duration"], "duration end to end")
+
+
+# ------------------------------------------------------------------------------------------------ RRT-Connect
+def _plan_mix(r):
+    import rrt_cases as rc
+
+    st, it = r["status"], r["iterations"]
+    return {"direct": int(((st == rc.SOLVED) & (it == 0)).sum()), "later": int(((st == rc.SOLVED) & (it >= 1)).sum()),
+            "exhausted": int((st == rc.EXHAUSTED).sum())}
+
+
+@pytest.mark.parametrize("n", ch.NS)
+def test_rrt_connect_twin_matches_the_oracle(n):
+    """The conditions a chain's planning case must meet (they are conditions, not measurements), the oracle's own float64-against-
+    longdouble waypoint difference against the constant rrt_cases' bound was sized from, then the module's rule."""
+    import rrt_cases as rc
+
+    ref, ref_long, twin = ch.plan_oracle(n), ch.plan_oracle(n, long=True), ch.plan_twin(n)
+    B, st, mix = ch.PLAN_PROBLEMS, ref["status"], _plan_mix(ref)
+    close = max(int((ref["gap"] < rc.GAP).sum()), int((ref_long["gap"] < rc.GAP).sum()))
+    firm = (ref["gap"] >= rc.GAP) & (ref_long["gap"] >= rc.GAP)
+    x, y = ref["waypoints"][firm], ref_long["waypoints"][firm]
+    assert np.array_equal(np.isnan(x), np.isnan(y))
+    fin = ~np.isnan(y)
+    own = float(np.abs(x[fin] - y[fin]).max())
+    print(f"\nrrt n={n}: {len(ch.plan_case(n)['cm'].links)} spheres; {mix}; largest tree {ref['nodes'].max()}, most waypoints "
+          f"{ref['count'].max()}; evaluations mean {ref['evaluations'].mean():.0f} max {ref['evaluations'].max()}; smallest gap "
+          f"{ref['gap'].min():.3g}, {close} below {rc.GAP:g}; oracle float64 against longdouble: waypoints {own:.3g}")
+    assert len(st) == B and st[ch.PLAN_PLANTED_START] == rc.START_BLOCKED and st[ch.PLAN_PLANTED_GOAL] == rc.GOAL_BLOCKED
+    if n == 1:      # one joint: connected at k = 0 or never; both outcomes occur in the world of chain_cases.PLAN_WORLD_SEED_1
+        assert mix["later"] == 0 and mix["direct"] >= 3 and mix["exhausted"] >= 4, mix
+    else:
+        assert mix["direct"] >= 3 and mix["later"] >= 5 and mix["exhausted"] >= 4, mix
+    assert close <= 0.02 * B
+    for k in rc.DISCRETE:
+        assert np.array_equal(ref[k][firm], ref_long[k][firm]), (n, k)
+    assert own <= rc.MEASURED_WAYPOINT                  # inside the module's constant: its bound applies unchanged
+    err = rc.check_against_oracle(twin, ref, f"rrt n={n} twin", show=False)
+    print(f"rrt n={n}: twin against oracle: waypoints {err:.3g} (bound {rc.WAYPOINT_BOUND:.3g})")
+
+
+PLAN_LIMITS = (("max_nodes", 4), ("max_nodes", 2), ("max_waypoints", 3), ("max_waypoints", 2), ("max_iters", 0))
+
+
+@pytest.mark.parametrize("key,value", PLAN_LIMITS)
+@pytest.mark.parametrize("n", ch.NS)
+def test_rrt_connect_limits(n, key, value):
+    """TREE_FULL (a node written at index max_nodes - 1), PATH_TOO_LONG, waypoint rows of 3 and 2 and max_iters = 0: the twin against
+    the oracle at the same settings; TREE_FULL occurs on every chain and PATH_TOO_LONG on every chain of two joints or more (one joint: two waypoints or no path)."""
+    import rrt_cases as rc
+
+    over = {key: value}
+    ref, twin = ch.plan_oracle(n, **over), ch.plan_twin(n, **over)
+    assert (ref["gap"] < rc.GAP).sum() <= 0.02 * ch.PLAN_PROBLEMS
+    rc.check_against_oracle(twin, ref, f"rrt n={n} {over} twin", show=False)
+    full, long = int((twin["status"] == rc.TREE_FULL).sum()), int((twin["status"] == rc.PATH_TOO_LONG).sum())
+    print(f"\nrrt n={n} {over}: tree full {full}, path too long {long}")
+    if key == "max_nodes":
+        stuck = twin["status"] == rc.TREE_FULL
+        assert twin["nodes"].max() == value and (twin["nodes"][stuck].max(axis=1) == value).all()
+        assert full > 0             # (on n = 1 too: in its world the trees of the pairs that never connect grow)
+    if key == "max_waypoints":
+        assert twin["waypoints"].shape[1] == value and (twin["count"][twin["status"] == rc.PATH_TOO_LONG] > value).all()
+        assert (long > 0) == (n >= 2)
+    if key == "max_iters":
+        assert twin["iterations"].max() <= 1 and (twin["nodes"] <= 2).all() and (twin["status"] == rc.EXHAUSTED).any()
+
+
+@pytest.fixture(scope="module")
+def chain_planner():
+    import manipulapy_amd as mp
+    from manipulapy_amd.planning import OptimizedTrajectoryPlanning
+
+    sm, dyn, lim = mp.load_robot("ur5")  # (batch_validate_path takes the joint count from the collision model)
+    return OptimizedTrajectoryPlanning(sm, None, dyn, lim, use_cuda=False)
+
+
+@pytest.mark.parametrize("n", ch.NS)
+def test_rrt_connect_paths_are_proven_free(chain_planner, n):
+    """Independent of the planner: every segment of every SOLVED path, padding included, is FREE for the edge checker at max_steps
+    512, and the path runs from q_start to q_goal bit for bit."""
+    import collision_edge_cases as ec
+    import rrt_cases as rc
+
+    case, got = ch.plan_case(n), ch.plan_twin(n)
+    solved = got["status"] == rc.SOLVED
+    wp = got["waypoints"][solved]
+    out = chain_planner.batch_validate_path(wp, case["cm"], rc.MARGIN, rc.TOL, max_steps=512)
+    assert out["free"].all(), f"n={n}: segments not free: {np.argwhere(out['segment_status'] != ec.FREE)[:5]}"
+    last = got["count"][solved] - 1
+    assert np.array_equal(wp[:, 0], case["qs"][solved]) and np.array_equal(wp[:, -1], case["qg"][solved])
+    assert np.array_equal(wp[np.arange(len(wp)), last], case["qg"][solved]) and got["count"][solved].min() >= 2
+    assert np.isnan(got["waypoints"][~solved]).all() and (got["count"][~solved] == 0).all()
+
+
+# ------------------------------------------------------------------------------------------------ path shortcutting
+@pytest.mark.parametrize("tight", (False, True))
+@pytest.mark.parametrize("n", ch.NS)
+def test_path_shortcut_twin_matches_the_oracle(chain_planner, n, tight):
+    """The conditions of a chain's shortcutting case, the oracle's own float64-against-longdouble differences against the constants
+    shortcut_cases' bounds were sized from, the module's rule on the normal and the tight run, then the checks that need no oracle."""
+    import rrt_cases as rc
+    import shortcut_cases as sc
+
+    case = ch.shortcut_case(n)
+    ref, ref_long, twin = ch.shortcut_oracle(n, tight=tight), ch.shortcut_oracle(n, long=True, tight=tight), ch.shortcut_twin(n, tight)
+    st, B = ref["status"], ch.SHORTCUT_PROBLEMS
+    W = case["tight"] if tight else sc.MAX_WAYPOINTS
+    close = max(int((ref["gap"] < sc.GAP).sum()), int((ref_long["gap"] < sc.GAP).sum()))
+    firm = (ref["gap"] >= sc.GAP) & (ref_long["gap"] >= sc.GAP)
+    dw = sc.difference(ref["waypoints"][firm], ref_long["waypoints"][firm])
+    dl = max(sc.difference(ref[k][firm], ref_long[k][firm]) for k in ("length_in", "length_out"))
+    print(f"\nshortcut n={n}{' tight, max_waypoints ' + str(W) if tight else ''}: {int((st == sc.DONE).sum())} done, "
+          f"{int((st == sc.STRAIGHT).sum())} straight, {int((st == sc.SKIPPED).sum())} skipped, {int((st == sc.INVALID).sum())} invalid; "
+          f"{int((ref['accepted'] > 0).sum())} with an accepted shortcut, {int(ref['checked'].sum())} edge checks, "
+          f"{int(ref['accepted'].sum())} accepted, {int(ref['skipped_full'].sum())} skipped for room; evaluations max "
+          f"{ref['evaluations'].max()}; smallest gap {ref['gap'].min():.3g}, {close} below {sc.GAP:g}; oracle float64 against "
+          f"longdouble: waypoints {dw:.3g}, lengths {dl:.3g}")
+    assert len(st) == B and ref["waypoints"].shape[1] == W
+    if not tight and n >= 2:
+        assert (ref["accepted"][:ch.PLAN_PROBLEMS] > 0).sum() >= 5
+    unsolved = np.flatnonzero(case["plan_status"] != rc.SOLVED)
+    assert len(unsolved) and (st[unsolved] == sc.SKIPPED).all()
+    two = ch.SHORTCUT_PLANTED_TWO
+    assert st[two] == sc.STRAIGHT and ref["evaluations"][two] == 0 and ref["iterations"][two] == 0
+    assert st[ch.SHORTCUT_PLANTED_NAN] == sc.INVALID and st[ch.SHORTCUT_PLANTED_LONG] == sc.INVALID
+    fits = lambda b: case["count"][b] <= W  # noqa: E731
+    assert st[ch.SHORTCUT_PLANTED_REPEAT] == (sc.DONE if fits(ch.SHORTCUT_PLANTED_REPEAT) else sc.INVALID)
+    zero = ch.SHORTCUT_PLANTED_ZERO
+    assert st[zero] == (sc.DONE if fits(zero) else sc.INVALID)
+    if fits(zero):          # Lambda = 0: every iteration passes without an edge
+        assert ref["iterations"][zero] == ch.SHORTCUT_MAX_ITERS[n] and ref["evaluations"][zero] == 0 and ref["length_out"][zero] == 0.0
+    full = ch.SHORTCUT_PLANTED_FULL
+    assert st[full] == (sc.INVALID if tight else sc.DONE)
+    if not tight:               # a path that fills its row: a shortcut between neighbouring segments has no room
+        assert (ref["skipped_full"][full] > 0) == (n in ch.SHORTCUT_FULL_BITES), int(ref["skipped_full"][full])
+    if tight:
+        assert (ref["skipped_full"].sum() > 0) == (n >= 2), int(ref["skipped_full"].sum())     # no room: the run bites on every chain
+    assert close <= 0.02 * B
+    for k in sc.DISCRETE:
+        assert np.array_equal(ref[k][firm], ref_long[k][firm]), (n, tight, k)
+    assert dw <= sc.MEASURED_WAYPOINT and dl <= sc.MEASURED_LENGTH      # inside the module's constants: its bounds apply unchanged
+    fig = sc.check_against_oracle(twin, ref, f"shortcut n={n} twin", show=False)
+    print(f"shortcut n={n}: twin against oracle: " + ", ".join(f"{k} {v:.3g}" for k, v in fig.items()))
+    sc.check_sound(chain_planner, case, twin, f"shortcut n={n} twin")

@@ -1,10 +1,19 @@
-"""GPU: every joint count 1..8 of the eight later kernel families on chain_cases.chain(n) - prismatic joints included - through the
+"""GPU: every joint count 1..8 of the ten later kernel families on chain_cases.chain(n) - prismatic joints included - through the
 DEVICE forms, each output buffer filled with 0xFF (a row the kernel skipped reads as NaN) and followed by a 4096-byte guard of 0xA5
 that must come back untouched (a store past the last valid row).  Kernels are held to their CPU twins under each family's existing
 kernel-against-twin rule and, where test_chain_cases_host.py has one, to the independent oracle.
 
 Row counts: 1 (a single lane), 63, 64 (a full wave: whole-line input staging), 65 and 197 (three waves and five lanes: the per-lane
-tail and the chunk of the row store that straddles the last row)."""
+tail and the chunk of the row store that straddles the last row).
+
+The two planning families (test_rrt_connect, test_path_shortcut) run chain_cases.plan_case / shortcut_case: 1, 64, 65 and all 67 / 73
+problems, the full count again on a grid of one block and on a workspace sized for one block, the limits (max_nodes 4 and 2,
+max_waypoints 3 and 2, max_iters 0, the tight run, w_in = max_waypoints) and non-finite problems; their workspaces are sized exactly
+and guarded like the outputs.  Measured on an MI355X, seconds a test (the oracle's NumPy run on the host included for n = 2, 5, 8):
+    n              1     2     3     4     5     6     7     8
+    rrt_connect    0.6   3.5   0.8   3.2   7.5   4.5   3.9   6.9
+    path_shortcut  0.1   2.1   1.0   <2.2  5.3   3.4   2.5   5.1
+(at max_iters 48 / 50 on every chain the same tests took 7 to 16 s on n = 4..8, which is why chain_cases cuts those chains' max_iters.)"""
 import numpy as np
 import pytest
 
@@ -528,3 +537,173 @@ def test_toppra(ctx, n, N, monkeypatch):
     for k in clean:
         assert np.array_equal(dirty[k][keep], clean[k][keep], equal_nan=True), k
         assert k == "status" or np.isnan(dirty[k][BAD]).all(), k
+
+
+# ------------------------------------------------------------------------------------------------ mp_rrt_connect_f64
+# Only the kernel runs MpRrtTreeLanes ([tree][node][dim][lane], the int32 parents behind the doubles, blockIdx.x * block_words), the
+# wave-wide loops with divergent lanes and the per-instance raise of the dynamic-LDS limit; the twin cannot stand in for them.  So
+# every output AND the workspace - sized exactly as mp_rrt_connect_workspace_bytes says - carry a guard band, and every discrete
+# output of every problem must equal the twin's (gap = inf: nobody is excused).
+PLAN_COUNTS = (1, 64, 65, ch.PLAN_PROBLEMS)
+ORACLE_NS = (2, 5, 8)             # the chains on which the kernel is held to the oracle too (the host test holds the twin to it everywhere)
+_PLAN_SHAPE = {"status": 1, "count": 1, "iterations": 1, "evaluations": 1, "nodes": 2}
+
+
+def _rrt(ctx, n, qs, qg, max_blocks=0, blocks=None, **over):
+    import rrt_cases as rc
+
+    case, p = ch.plan_case(n), ch.plan_params(n, **over)
+    cm = case["cm"]
+    B = len(qs)
+    ws_bytes = _hip.rrt_connect_workspace_bytes(n, p["max_nodes"], (B + 63) // 64 if blocks is None else blocks)
+    x = Inputs(ctx, qs, qg)
+    ws = Out(ctx, (ws_bytes,), np.uint8)                  # stale 0xFF nodes everywhere, and nothing behind the last block's parents
+    o = {k: Out(ctx, (B,) if w == 1 else (B, w), np.int32) for k, w in _PLAN_SHAPE.items()}
+    o["waypoints"] = Out(ctx, (B, p["max_waypoints"], n))
+    cm.sync_world(ctx)
+    ctx.rrt_connect(cm.model, cm.handle, x.bufs[0], x.bufs[1], B, case["lo"], case["hi"], rc.MARGIN, rc.TOL, d_workspace=ws.buf,
+                    workspace_bytes=ws_bytes, max_blocks=max_blocks, **p, **{"d_" + k: v.buf for k, v in o.items()})
+    ctx.synchronize()
+    x.free()
+    what = f"rrt n={n} problems={B} {over}"
+    ws.take(what + " workspace")
+    return {k: v.take(f"{what} {k}") for k, v in o.items()}
+
+
+def _identical(a, b, what, rows=None):
+    for k in a:
+        x, y = (a[k], b[k]) if rows is None else (a[k][rows], b[k][rows])
+        assert np.array_equal(x, y, equal_nan=True), f"{what}: {k}"
+
+
+def _held_to_plan_twin(got, twin, B, case, what):
+    import rrt_cases as rc
+
+    ref = {k: v[:B] for k, v in twin.items()}
+    ref["gap"] = np.full(B, np.inf)
+    err = rc.check_against_oracle(got, ref, what, show=False)
+    solved = got["status"] == rc.SOLVED
+    assert np.array_equal(got["waypoints"][solved][:, 0], case["qs"][:B][solved]), what
+    assert np.array_equal(got["waypoints"][solved][:, -1], case["qg"][:B][solved]), what
+    return err
+
+
+@pytest.mark.parametrize("n", ch.NS)
+def test_rrt_connect(ctx, n):
+    import rrt_cases as rc
+
+    case, twin = ch.plan_case(n), ch.plan_twin(n)
+    qs, qg = case["qs"], case["qg"]
+    worst = 0.0
+    for B in PLAN_COUNTS:
+        full = _rrt(ctx, n, qs[:B], qg[:B])
+        worst = max(worst, _held_to_plan_twin(full, twin, B, case, f"rrt n={n} kernel against the twin, {B} problems"))
+    _identical(_rrt(ctx, n, qs, qg, max_blocks=1), full, f"rrt n={n} max_blocks 1")          # 67 problems on 64 lanes: workspaces reused
+    _identical(_rrt(ctx, n, qs, qg, blocks=1), full, f"rrt n={n} workspace of one block")
+    if n in ORACLE_NS:
+        worst = max(worst, rc.check_against_oracle(full, ch.plan_oracle(n), f"rrt n={n} kernel against the oracle", show=False))
+    for over in ({"max_nodes": 4}, {"max_nodes": 2}, {"max_waypoints": 3}, {"max_waypoints": 2}, {"max_iters": 0}):
+        got = _rrt(ctx, n, qs, qg, **over)
+        _held_to_plan_twin(got, ch.plan_twin(n, **over), len(qs), case, f"rrt n={n} {over} kernel against the twin")
+    bad_s, bad_g = qs.copy(), qg.copy()
+    bad_s[BAD[0], 0], bad_g[BAD[1], (n - 1) // 2], bad_s[BAD[2], n - 1] = np.nan, np.inf, -np.inf
+    dirty = _rrt(ctx, n, bad_s, bad_g)
+    assert (dirty["status"][BAD] == rc.INVALID).all() and np.isnan(dirty["waypoints"][BAD]).all()
+    for k in ("count", "iterations", "nodes", "evaluations"):
+        assert (dirty[k][BAD] == 0).all(), k
+    _identical(dirty, full, f"rrt n={n} beside non-finite problems", np.setdiff1d(np.arange(len(qs)), BAD))
+    print(f"\nrrt n={n}: kernel against twin{' and oracle' if n in ORACLE_NS else ''}: waypoints {worst:.3g} (bound {rc.WAYPOINT_BOUND:.3g})")
+
+
+# ------------------------------------------------------------------------------------------------ mp_path_shortcut_f64
+SHORTCUT_COUNTS = (1, 64, 65, ch.SHORTCUT_PROBLEMS)
+_SC_REAL = ("waypoints", "length_in", "length_out")
+
+
+@pytest.fixture(scope="module")
+def planner():
+    import manipulapy_amd as mp
+
+    sm, dyn, lim = mp.load_robot("ur5")  # (batch_validate_path takes the joint count from the collision model)
+    return mp.OptimizedTrajectoryPlanning(sm, None, dyn, lim, use_cuda=False)
+
+
+def _shortcut(ctx, n, wp, cnt, max_blocks=0, blocks=None, **over):
+    import shortcut_cases as sc
+
+    cm, p = ch.shortcut_case(n)["cm"], ch.shortcut_params(n, **over)
+    wp, cnt = np.ascontiguousarray(wp, dtype=np.float64), np.ascontiguousarray(cnt, dtype=np.int32)
+    B, w_in, _ = wp.shape
+    W = p["max_waypoints"]
+    ws_bytes = _hip.path_shortcut_workspace_bytes(n, W, (B + 63) // 64 if blocks is None else blocks)
+    x = Inputs(ctx, wp, cnt)
+    ws = Out(ctx, (ws_bytes,), np.uint8)
+    o = {k: Out(ctx, (B, W, n) if k == "waypoints" else (B,), np.float64 if k in _SC_REAL else np.int32) for k in sc.KEYS}
+    cm.sync_world(ctx)
+    ctx.path_shortcut(cm.model, cm.handle, x.bufs[0], x.bufs[1], B, w_in, sc.MARGIN, sc.TOL, d_workspace=ws.buf, workspace_bytes=ws_bytes,
+                      max_blocks=max_blocks, **p, **{"d_" + k: v.buf for k, v in o.items()})
+    ctx.synchronize()
+    x.free()
+    what = f"shortcut n={n} problems={B} {over}"
+    ws.take(what + " workspace")
+    return {k: v.take(f"{what} {k}") for k, v in o.items()}
+
+
+def _held_to_shortcut_twin(got, twin, B, what):
+    import shortcut_cases as sc
+
+    ref = {k: v[:B] for k, v in twin.items()}
+    ref["gap"] = np.full(B, np.inf)
+    return sc.check_against_oracle(got, ref, what, show=False)
+
+
+@pytest.mark.parametrize("n", ch.NS)
+def test_path_shortcut(ctx, planner, n):
+    import shortcut_cases as sc
+
+    case = ch.shortcut_case(n)
+    wp, cnt, P = case["waypoints"], case["count"], ch.SHORTCUT_PROBLEMS
+    worst = {}
+
+    def note(fig):
+        for k, v in fig.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+
+    for tight in (False, True):
+        over = {"max_waypoints": case["tight"]} if tight else {}
+        twin = ch.shortcut_twin(n, tight)
+        what = f"shortcut n={n}{' tight' if tight else ''}"
+        for B in SHORTCUT_COUNTS if not tight else (P,):
+            full = _shortcut(ctx, n, wp[:B], cnt[:B], **over)
+            note(_held_to_shortcut_twin(full, twin, B, f"{what} kernel against the twin, {B} problems"))
+        assert full["waypoints"].shape[1] == (case["tight"] if tight else sc.MAX_WAYPOINTS)
+        sc.check_sound(planner, case, full, f"{what} kernel")
+        _identical(_shortcut(ctx, n, wp, cnt, max_blocks=1, **over), full, f"{what} max_blocks 1")   # 73 problems on 64 lanes
+        _identical(_shortcut(ctx, n, wp, cnt, blocks=1, **over), full, f"{what} workspace of one block")
+        if n in ORACLE_NS:
+            note(sc.check_against_oracle(full, ch.shortcut_oracle(n, tight=tight), f"{what} kernel against the oracle", show=False))
+        if tight:
+            assert (full["skipped_full"].sum() > 0) == (n >= 2)
+        else:
+            clean = full
+    cm = case["cm"]
+    narrow = np.ascontiguousarray(wp[:, :sc.MAX_WAYPOINTS])                 # w_in = max_waypoints: no input row to spare
+    want = _hip.cpu_path_shortcut(cm.model, cm.handle, narrow, cnt, sc.MARGIN, sc.TOL, **ch.shortcut_params(n))
+    note(_held_to_shortcut_twin(_shortcut(ctx, n, narrow, cnt), want, P, f"shortcut n={n} w_in = max_waypoints"))
+    none = _shortcut(ctx, n, wp, cnt, max_iters=0)
+    _held_to_shortcut_twin(none, ch.shortcut_twin(n, max_iters=0), P, f"shortcut n={n} max_iters 0")
+    assert none["evaluations"].max() == 0 and none["iterations"].max() == 0
+    src = int(np.argmax(cnt[:ch.PLAN_PROBLEMS]))          # the longest solved path stands on the three poisoned rows
+    base, bad = wp.copy(), cnt.copy()
+    base[BAD], bad[BAD] = wp[src], cnt[src]
+    ok = _shortcut(ctx, n, base, bad)
+    assert (ok["status"][BAD] == clean["status"][src]).all() and (ok["count"][BAD] == clean["count"][src]).all()
+    base[BAD[0], 0, 0], base[BAD[1], 1, (n - 1) // 2], base[BAD[2], cnt[src] - 1, n - 1] = np.nan, np.inf, -np.inf
+    dirty = _shortcut(ctx, n, base, bad)
+    assert (dirty["status"][BAD] == sc.INVALID).all()
+    for k in sc.KEYS:
+        assert np.isnan(dirty[k][BAD]).all() if k in _SC_REAL else k == "status" or (dirty[k][BAD] == 0).all(), k
+    _identical(dirty, ok, f"shortcut n={n} beside non-finite problems", np.setdiff1d(np.arange(P), BAD))
+    _identical(ok, clean, f"shortcut n={n} beside replaced problems", np.setdiff1d(np.arange(P), BAD))
+    print(f"\nshortcut n={n}: kernel against twin{' and oracle' if n in ORACLE_NS else ''}: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items())
+          + f" (bounds {sc.WAYPOINT_BOUND:.3g}, {sc.LENGTH_BOUND:.3g})")

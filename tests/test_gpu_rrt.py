@@ -1,7 +1,9 @@
 """GPU: k_rrt_connect (csrc/mp_rrt.h) against its CPU twin and the NumPy oracle under the rule of rrt_cases.py; the work queue turned
 over (capped grids that make every lane reuse its workspace, reversed order, repeated launches, a captured graph), the device and host
-forms, output subsets, a workspace for one block, a replaced world, empty tables and the planner on the "hip" backend.  Problem
-counts: 131 (two waves and three lanes), 1 and 67."""
+forms, output subsets, a workspace for one block, a replaced world, empty tables and the planner on the "hip" backend; the paths only
+the kernel has - lanes trapped on the spot (d == 0) beside working ones in one wave, TREE_FULL, PATH_TOO_LONG and max_iters = 0 on
+the device.  Every output and the workspace are followed by a guard band that must come back untouched.  Problem counts: 131 (two
+waves and three lanes), 1 and 67."""
 import numpy as np
 import pytest
 
@@ -13,6 +15,7 @@ from manipulapy_amd.collision import SphereCollisionModel
 
 pytestmark = pytest.mark.gpu
 ALL = rc.PLAN_KEYS
+GUARD = 4096      # bytes of 0xA5 behind every output and behind the workspace: they must come back untouched
 _refs = {}
 
 
@@ -39,31 +42,34 @@ def _shape(k, B, W, n):
 
 
 def device_run(ctx, case, qs=None, qg=None, want=ALL, max_blocks=0, blocks=None, launch=None, cm=None, **over):
-    """The device form on fresh buffers filled with 0xFF and a workspace of `blocks` blocks (default: one a wave of problems):
-    {output: array}.  `launch(run)` may wrap the launch (a capture, a repeat)."""
+    """The device form on fresh buffers filled with 0xFF and a workspace of `blocks` blocks (default: one a wave of problems), each
+    followed by a guard band: {output: array}.  `launch(run)` may wrap the launch (a capture, a repeat); `lo` / `hi` replace the box."""
     cm = case["cm"] if cm is None else cm
+    lo, hi = over.pop("lo", case["lo"]), over.pop("hi", case["hi"])
     qs = np.ascontiguousarray(case["qs"] if qs is None else qs, dtype=np.float64)
     qg = np.ascontiguousarray(case["qg"] if qg is None else qg, dtype=np.float64)
     B, n = qs.shape
     p = rc.params_of(case["name"], **over)
     ws_bytes = _hip.rrt_connect_workspace_bytes(n, p["max_nodes"], (B + 63) // 64 if blocks is None else blocks)
-    ds, dg, ws = ctx.to_device(qs), ctx.to_device(qg), ctx.alloc(ws_bytes)
+    ds, dg, ws = ctx.to_device(qs), ctx.to_device(qg), ctx.alloc(ws_bytes + GUARD)
     dtype = {k: np.float64 if k == "waypoints" else np.int32 for k in want}
     shape = {k: _shape(k, B, p["max_waypoints"], n) for k in want}
     size = {k: int(np.prod(shape[k])) * np.dtype(dtype[k]).itemsize for k in want}
-    bufs = {k: ctx.alloc(size[k]) for k in want}
+    bufs = {k: ctx.alloc(size[k] + GUARD) for k in want}
     try:
-        for k, b in bufs.items():
-            ctx.memset(b, 0xFF, size[k])
-        ctx.memset(ws, 0xFF, ws_bytes)  # stale nodes everywhere: a lane must never read past its own counts
+        for b, nbytes in [(bufs[k], size[k]) for k in want] + [(ws, ws_bytes)]:
+            ctx.memset(b, 0xA5, nbytes + GUARD)
+            ctx.memset(b, 0xFF, nbytes)  # (the workspace: stale nodes everywhere, a lane must never read past its own counts)
         cm.sync_world(ctx)
-        run = lambda: ctx.rrt_connect(cm.model, cm.handle, ds, dg, B, case["lo"], case["hi"], rc.MARGIN, rc.TOL, d_workspace=ws,  # noqa: E731
+        run = lambda: ctx.rrt_connect(cm.model, cm.handle, ds, dg, B, lo, hi, rc.MARGIN, rc.TOL, d_workspace=ws,  # noqa: E731
                                       workspace_bytes=ws_bytes, max_blocks=max_blocks, **p, **{"d_" + k: b for k, b in bufs.items()})
         if launch is None:
             run()
         else:
             launch(run)
         ctx.synchronize()
+        for k, b, nbytes in [(k, bufs[k], size[k]) for k in want] + [("workspace", ws, ws_bytes)]:
+            assert (b.download((nbytes + GUARD,), np.uint8)[nbytes:] == 0xA5).all(), f"{k}: bytes written past the end"
         return {k: b.download(shape[k], dtype[k]) for k, b in bufs.items()}
     finally:
         for b in (ds, dg, ws, *bufs.values()):
@@ -163,6 +169,42 @@ def test_device_form_host_form_subsets_and_a_small_workspace(ctx):
     finally:
         for b in (ds, dg, ws, st):
             b.free()
+
+
+def test_degenerate_box_traps_lanes_beside_working_ones(ctx):
+    """lo == hi: every sample is the same point, so once it has joined a tree d == 0 and the extension is trapped on the spot - the
+    re-entry of mp_rrt_trip under wave_any, which is the identity on the host.  The six problems of
+    test_rrt_host.py::test_degenerate_box_traps_every_extension (the first six that need an iteration: the twin's iterations are the
+    oracle's, test_rrt_host.py holds it to them) lead 61 ordinary ones, so trapped, extending and finished lanes share a wave; at
+    max_blocks = 1 three problems more than lanes."""
+    case, twin = _case("ur5")
+    mid = 0.5 * (case["lo"] + case["hi"])
+    six = np.flatnonzero(twin["iterations"] >= 1)[:6]
+    rows = np.concatenate([six, np.setdiff1d(np.arange(rc.PROBLEMS), six)[:61]])
+    qs, qg = np.ascontiguousarray(case["qs"][rows]), np.ascontiguousarray(case["qg"][rows])
+    cm = case["cm"]
+    want = _hip.cpu_rrt_connect(cm.model, cm.handle, qs, qg, mid, mid, rc.MARGIN, rc.TOL, **rc.params_of("ur5", max_iters=12))
+    assert (want["status"][:6] == rc.EXHAUSTED).any() and want["nodes"][:6].max() <= 12 and (want["iterations"] == 0).any()
+    want["gap"] = np.full(len(rows), np.inf)
+    for blocks in (0, 1):
+        got = device_run(ctx, case, qs, qg, max_blocks=blocks, max_iters=12, lo=mid, hi=mid)
+        rc.check_against_oracle(got, want, f"degenerate box, max_blocks {blocks}", show=False)
+
+
+def test_tree_full_path_too_long_and_no_iterations_on_the_device(ctx):
+    """The device form of test_rrt_host.py::test_tree_full_path_too_long_and_no_iterations: a node written at index max_nodes - 1 of a
+    workspace sized for exactly that max_nodes, a waypoint row of exactly 2, and max_iters = 0 - every problem equals the twin's and
+    no guard band is touched."""
+    case, _ = _case("ur5")
+    cm = case["cm"]
+    for over, code in (({"max_nodes": 4}, rc.TREE_FULL), ({"max_waypoints": 2}, rc.PATH_TOO_LONG), ({"max_iters": 0}, rc.EXHAUSTED)):
+        want = _hip.cpu_rrt_connect(cm.model, cm.handle, case["qs"], case["qg"], case["lo"], case["hi"], rc.MARGIN, rc.TOL,
+                                    **rc.params_of("ur5", **over))
+        assert (want["status"] == code).sum() >= 8, over
+        want["gap"] = np.full(rc.PROBLEMS, np.inf)
+        got = device_run(ctx, case, **over)
+        rc.check_against_oracle(got, want, f"ur5 {over} kernel against the twin", show=False)
+        assert got["waypoints"].shape[1] == rc.params_of("ur5", **over)["max_waypoints"]
 
 
 def test_non_finite_problems_leave_their_neighbours_alone(ctx):

@@ -1,8 +1,9 @@
 """GPU: k_path_shortcut (csrc/mp_shortcut.h) against its CPU twin on every discrete output of every problem and against the NumPy
 oracle under the rule of shortcut_cases.py; soundness and usefulness of the kernel's paths; the work queue turned over (a grid of one
 block over a workspace filled with 0xFF, so that every lane is reused, reversed order, repeated launches, a captured graph replayed
-twice); the host form against the device form, output subsets, a workspace smaller than one block, and the planner on the "hip"
-backend.  Problem count: 135 a robot (two waves and seven lanes)."""
+twice); the host form against the device form, output subsets, a workspace smaller than one block, the planner on the "hip"
+backend, and the planner's and the shortcutter's launches in one captured graph on one collision handle.  Every output and the
+workspace are followed by a guard band that must come back untouched.  Problem count: 135 a robot (two waves and seven lanes)."""
 import numpy as np
 import pytest
 
@@ -13,6 +14,7 @@ from manipulapy_amd import _hip, registry
 pytestmark = pytest.mark.gpu
 ALL = sc.KEYS
 REAL = ("waypoints", "length_in", "length_out")
+GUARD = 4096      # bytes of 0xA5 behind every output and behind the workspace: they must come back untouched
 
 
 @pytest.fixture(scope="module")
@@ -38,15 +40,15 @@ def device_run(ctx, case, waypoints=None, count=None, want=ALL, max_blocks=0, bl
     p = sc.params_of(**over)
     W = p["max_waypoints"]
     ws_bytes = _hip.path_shortcut_workspace_bytes(n, W, (B + 63) // 64 if blocks is None else blocks)
-    dw, dc, ws = ctx.to_device(wp), ctx.to_device(cnt), ctx.alloc(ws_bytes)
+    dw, dc, ws = ctx.to_device(wp), ctx.to_device(cnt), ctx.alloc(ws_bytes + GUARD)
     dtype = {k: np.float64 if k in REAL else np.int32 for k in want}
     shape = {k: (B, W, n) if k == "waypoints" else (B,) for k in want}
     size = {k: int(np.prod(shape[k])) * np.dtype(dtype[k]).itemsize for k in want}
-    bufs = {k: ctx.alloc(size[k]) for k in want}
+    bufs = {k: ctx.alloc(size[k] + GUARD) for k in want}
     try:
-        for k, b in bufs.items():
-            ctx.memset(b, 0xFF, size[k])
-        ctx.memset(ws, 0xFF, ws_bytes)  # stale paths everywhere: a lane must never read past its own count
+        for b, nbytes in [(bufs[k], size[k]) for k in want] + [(ws, ws_bytes)]:
+            ctx.memset(b, 0xA5, nbytes + GUARD)
+            ctx.memset(b, 0xFF, nbytes)  # (the workspace: stale paths everywhere, a lane must never read past its own count)
         cm.sync_world(ctx)
         run = lambda: ctx.path_shortcut(cm.model, cm.handle, dw, dc, B, w_in, sc.MARGIN, sc.TOL, d_workspace=ws,  # noqa: E731
                                         workspace_bytes=ws_bytes, max_blocks=max_blocks, **p, **{"d_" + k: b for k, b in bufs.items()})
@@ -55,6 +57,8 @@ def device_run(ctx, case, waypoints=None, count=None, want=ALL, max_blocks=0, bl
         else:
             launch(run)
         ctx.synchronize()
+        for k, b, nbytes in [(k, bufs[k], size[k]) for k in want] + [("workspace", ws, ws_bytes)]:
+            assert (b.download((nbytes + GUARD,), np.uint8)[nbytes:] == 0xA5).all(), f"{k}: bytes written past the end"
         return {k: b.download(shape[k], dtype[k]) for k, b in bufs.items()}
     finally:
         for b in (dw, dc, ws, *bufs.values()):
@@ -122,6 +126,76 @@ def test_queue_turned_over(ctx):
     finally:
         for g in graphs:
             g.destroy()
+
+
+def test_planner_and_shortcutter_share_a_handle_in_one_graph(ctx):
+    """rrt_connect then path_shortcut on one collision handle take their problems from the same queue counter (zeroed on the stream
+    before each kernel).  Captured into one graph - the shortcutter reads the planner's waypoints and counts where the planner left
+    them - and replayed twice, they give bit for bit what the two separate launches give."""
+    import rrt_cases as rc
+
+    B = 67
+    plan_case = rc.make_plan_case("ur5")
+    cm, n = plan_case["cm"], plan_case["cm"].n
+    pp, sp = rc.params_of("ur5"), sc.params_of()
+    W = pp["max_waypoints"]
+    assert sp["max_waypoints"] == W
+    ds, dg = ctx.to_device(plan_case["qs"][:B]), ctx.to_device(plan_case["qg"][:B])
+    pw_bytes, sw_bytes = _hip.rrt_connect_workspace_bytes(n, pp["max_nodes"], 2), _hip.path_shortcut_workspace_bytes(n, W, 2)
+    pws, sws = ctx.alloc(pw_bytes), ctx.alloc(sw_bytes)
+    spec = {"plan_status": ((B,), np.int32), "plan_count": ((B,), np.int32), "plan_waypoints": ((B, W, n), np.float64)}
+    spec.update({k: ((B, W, n) if k == "waypoints" else (B,), np.float64 if k in REAL else np.int32) for k in ALL})
+    size = {k: int(np.prod(s)) * np.dtype(t).itemsize for k, (s, t) in spec.items()}
+    bufs = {k: ctx.alloc(size[k] + GUARD) for k in spec}
+
+    def reset():
+        for k, b in bufs.items():
+            ctx.memset(b, 0xA5, size[k] + GUARD)
+            ctx.memset(b, 0xFF, size[k])
+        ctx.memset(pws, 0xFF, pw_bytes)
+        ctx.memset(sws, 0xFF, sw_bytes)
+
+    def plan():
+        ctx.rrt_connect(cm.model, cm.handle, ds, dg, B, plan_case["lo"], plan_case["hi"], rc.MARGIN, rc.TOL, d_workspace=pws,
+                        workspace_bytes=pw_bytes, d_status=bufs["plan_status"], d_count=bufs["plan_count"],
+                        d_waypoints=bufs["plan_waypoints"], **pp)
+
+    def shorten():
+        ctx.path_shortcut(cm.model, cm.handle, bufs["plan_waypoints"], bufs["plan_count"], B, W, sc.MARGIN, sc.TOL, d_workspace=sws,
+                          workspace_bytes=sw_bytes, **sp, **{"d_" + k: bufs[k] for k in ALL})
+
+    def take():
+        ctx.synchronize()
+        for k, b in bufs.items():
+            assert (b.download((size[k] + GUARD,), np.uint8)[size[k]:] == 0xA5).all(), f"{k}: bytes written past the end"
+        return {k: bufs[k].download(*spec[k]) for k in spec}
+
+    graph = None
+    try:
+        cm.sync_world(ctx)
+        reset()
+        plan()
+        ctx.synchronize()      # two separate launches
+        shorten()
+        apart = take()
+        assert (apart["plan_status"] == rc.SOLVED).sum() >= 16 and (apart["accepted"] > 0).sum() >= 8
+        reset()
+        with ctx.capture() as cap:
+            plan()
+            shorten()
+        graph = cap.graph
+        for replay in range(2):
+            graph.launch()
+            _same(take(), apart, tuple(spec))
+            if replay == 0:
+                reset()
+    finally:
+        if graph is not None:
+            graph.destroy()
+        for b in (ds, dg, pws, sws, *bufs.values()):
+            b.free()
+    twin = _hip.cpu_path_shortcut(cm.model, cm.handle, apart["plan_waypoints"], apart["plan_count"], sc.MARGIN, sc.TOL, **sp)
+    sc.check_against_oracle({k: apart[k] for k in ALL}, dict(twin, gap=np.full(B, np.inf)), "shortcut behind the planner", show=False)
 
 
 def test_device_form_host_form_subsets_and_a_small_workspace(ctx):
