@@ -3109,13 +3109,36 @@ static int collision_resident(const char* fn, mp_ctx* ctx, mp_collision* h, mp_c
   *out = &K;
   return MP_OK;
 }
+// what every sphere-model entry checks first (`fn`: the entry's name, a const char*)
+#define CHECK_SPHERE_ENTRY(fn)                                                                                          \
+  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);                                        \
+  CTX_ENTER(ctx);                                                                                                       \
+  REQUIRE_SMALL(fn);                                                                                                    \
+  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n)
+
+static MpColDevice collision_device(const mp_collision* h, const mp_collision::Resident* R) {
+  return {h->sph.S, static_cast<const MpColSpheres*>(R->sph),
+          reinterpret_cast<const MpColPair*>(static_cast<const char*>(R->sph) + sizeof(MpColSpheres)),
+          static_cast<const MpColWorld*>(R->world), static_cast<unsigned long long*>(R->counter)};
+}
+// The grid of a work-queue launch (mpk_queue_plan): the resident blocks, ceil(B / 64), max_blocks if that is positive and the blocks
+// the workspace holds, whichever is smallest.
+static long queue_grid(const MpQueuePlan& plan, int64_t B, int max_blocks, size_t ws_blocks = SIZE_MAX) {
+  long grid = std::min<long>(plan.resident, (long)((B + 63) / 64));
+  if (max_blocks > 0) grid = std::min<long>(grid, max_blocks);
+  return (long)std::min<size_t>((size_t)grid, ws_blocks);
+}
+// The planners' host entries take their workspace from the pool: as many blocks as the launch can use, at most 1 GiB of them (never
+// less than one block).
+static size_t host_workspace_bytes(const MpQueuePlan& plan, int64_t B, size_t block_bytes) {
+  const long blocks = std::min<long>(queue_grid(plan, B, 0), (long)(((size_t)1 << 30) / block_bytes));
+  return (size_t)std::max<long>(1, blocks) * block_bytes;
+}
+
 static int collision_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q, int64_t rows,
                           double eps_world, double eps_self, double* d_dw, int32_t* d_aw, double* d_ds, int32_t* d_as, double* d_gdw,
                           double* d_gds, double* d_cost, double* d_grad) {
-  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
-  CTX_ENTER(ctx);
-  REQUIRE_SMALL(fn);
-  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  CHECK_SPHERE_ENTRY(fn);
   REQUIRE(eps_world > 0.0 && eps_self > 0.0 && std::isfinite(eps_world) && std::isfinite(eps_self),
           "%s: eps_world and eps_self must be positive and finite", fn);
   REQUIRE(rows >= 0, "%s: negative row count", fn);
@@ -3129,20 +3152,15 @@ static int collision_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp
   mp_collision::Resident* R = nullptr;
   if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
   PROFILE_SCOPE(ctx, fn);
-  HIP_TRY(mpk_collision(ctx->compute, model->d, h->sph.S, static_cast<const MpColSpheres*>(R->sph),
-                        reinterpret_cast<const MpColPair*>(static_cast<const char*>(R->sph) + sizeof(MpColSpheres)),
-                        static_cast<const MpColWorld*>(R->world), d_q, (long)rows, eps_world, eps_self, d_dw, d_aw, d_ds, d_as, d_gdw,
-                        d_gds, d_cost, d_grad));
+  HIP_TRY(mpk_collision(ctx->compute, model->d, collision_device(h, R), d_q, (long)rows, eps_world, eps_self, d_dw, d_aw, d_ds, d_as,
+                        d_gdw, d_gds, d_cost, d_grad));
   return MP_OK;
 }
 
 static int collision_edges_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_qa,
                                 const double* d_qb, int64_t edges, double margin, double tol, int max_steps, int max_blocks,
                                 int32_t* d_status, double* d_t, int32_t* d_steps, double* d_clear, int32_t* d_witness) {
-  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
-  CTX_ENTER(ctx);
-  REQUIRE_SMALL(fn);
-  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  CHECK_SPHERE_ENTRY(fn);
   if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
   REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
   REQUIRE(edges >= 0, "%s: negative edge count", fn);
@@ -3157,10 +3175,10 @@ static int collision_edges_impl(const char* fn, mp_ctx* ctx, const mp_model* mod
   if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
   PROFILE_SCOPE(ctx, fn);
   const MpColEdgeParams P = {margin, tol, max_steps, 0};
-  HIP_TRY(mpk_collision_edges(ctx->compute, model->d, h->sph.S, static_cast<const MpColSpheres*>(R->sph),
-                              reinterpret_cast<const MpColPair*>(static_cast<const char*>(R->sph) + sizeof(MpColSpheres)),
-                              static_cast<const MpColWorld*>(R->world), d_qa, d_qb, (long)edges, P, d_status, d_t, d_steps, d_clear,
-                              d_witness, static_cast<unsigned long long*>(R->counter), ctx->compute_units, max_blocks));
+  MpQueuePlan plan;
+  HIP_TRY(mpk_queue_plan(MP_QUEUE_EDGES, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_collision_edges(ctx->compute, model->d, collision_device(h, R), d_qa, d_qb, (long)edges, P, d_status, d_t, d_steps, d_clear,
+                              d_witness, queue_grid(plan, edges, max_blocks), plan.lds));
   return MP_OK;
 }
 
@@ -3177,9 +3195,7 @@ int mp_collision_edges_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision
                                 double margin, double tol, int max_steps, int32_t* status, double* t, int32_t* steps, double* clearance,
                                 int32_t* witness) {
   const char* fn = "mp_collision_edges_host_f64";
-  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
-  CTX_ENTER(ctx);
-  REQUIRE_SMALL(fn);
+  CHECK_SPHERE_ENTRY(fn);
   REQUIRE(edges >= 0, "%s: negative edge count", fn);
   if (edges == 0) return mp_collision_edges_check(fn, margin, tol, max_steps);
   REQUIRE(q_from && q_to, "%s: null host pointer", fn);
@@ -3198,11 +3214,11 @@ int mp_collision_edges_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision
 
 }  // extern "C"
 
-// ---- batched RRT-Connect over the sphere model (mp_rrt.h).  The grid: the resident blocks, ceil(B / 64), max_blocks and what the
-// workspace holds, whichever is smallest.
+// ---- batched RRT-Connect over the sphere model (mp_rrt.h).  `made`: the launch plan where the entry has made it already (the host
+// entry sizes its workspace by it); every entry call makes one.
 static int rrt_connect_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_qs, const double* d_qg,
-                            int64_t B, const MpRrtParams& P, void* d_ws, size_t ws_bytes, int max_blocks, int32_t* d_status,
-                            int32_t* d_count, double* d_wp, int32_t* d_iters, int32_t* d_nodes, int32_t* d_evals) {
+                            int64_t B, const MpRrtParams& P, void* d_ws, size_t ws_bytes, int max_blocks, const MpQueuePlan* made,
+                            int32_t* d_status, int32_t* d_count, double* d_wp, int32_t* d_iters, int32_t* d_nodes, int32_t* d_evals) {
   REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
@@ -3218,15 +3234,11 @@ static int rrt_connect_impl(const char* fn, mp_ctx* ctx, const mp_model* model, 
   mp_collision::Resident* R = nullptr;
   if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
   PROFILE_SCOPE(ctx, fn);
-  long grid = 0;
-  HIP_TRY(mpk_rrt_connect_resident(model->d.n, h->sph.S, ctx->compute_units, &grid));
-  grid = std::min<long>(grid, (long)((B + 63) / 64));
-  if (max_blocks > 0) grid = std::min<long>(grid, max_blocks);
-  grid = std::min<long>(grid, (long)(ws_bytes / block_bytes));
-  HIP_TRY(mpk_rrt_connect(ctx->compute, model->d, h->sph.S, static_cast<const MpColSpheres*>(R->sph),
-                          reinterpret_cast<const MpColPair*>(static_cast<const char*>(R->sph) + sizeof(MpColSpheres)),
-                          static_cast<const MpColWorld*>(R->world), d_qs, d_qg, (long)B, P, d_status, d_count, d_wp, d_iters, d_nodes,
-                          d_evals, static_cast<double*>(d_ws), static_cast<unsigned long long*>(R->counter), ctx->compute_units, grid));
+  MpQueuePlan plan;
+  if (made) plan = *made;
+  else HIP_TRY(mpk_queue_plan(MP_QUEUE_RRT, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_rrt_connect(ctx->compute, model->d, collision_device(h, R), d_qs, d_qg, (long)B, P, d_status, d_count, d_wp, d_iters,
+                          d_nodes, d_evals, static_cast<double*>(d_ws), queue_grid(plan, B, max_blocks, ws_bytes / block_bytes), plan.lds));
   return MP_OK;
 }
 
@@ -3238,28 +3250,21 @@ int mp_rrt_connect_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, cons
                        int max_blocks, int32_t* d_status, int32_t* d_count, double* d_waypoints, int32_t* d_iterations, int32_t* d_nodes,
                        int32_t* d_evaluations) {
   const char* fn = "mp_rrt_connect_f64";
-  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
-  CTX_ENTER(ctx);
-  REQUIRE_SMALL(fn);
-  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  CHECK_SPHERE_ENTRY(fn);
   MpRrtParams P;
   if (int rc = mp_rrt_connect_check(fn, model->d.n, lo, hi, seed, step, min_advance, max_iters, max_nodes, max_waypoints, margin, tol,
                                     max_steps, &P))
     return rc;
-  return rrt_connect_impl(fn, ctx, model, h, d_q_start, d_q_goal, B, P, d_workspace, workspace_bytes, max_blocks, d_status, d_count,
-                          d_waypoints, d_iterations, d_nodes, d_evaluations);
+  return rrt_connect_impl(fn, ctx, model, h, d_q_start, d_q_goal, B, P, d_workspace, workspace_bytes, max_blocks, nullptr, d_status,
+                          d_count, d_waypoints, d_iterations, d_nodes, d_evaluations);
 }
 
-// the workspace comes from the pool: as many blocks as the launch can use, at most 1 GiB of them (never less than one block)
 int mp_rrt_connect_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q_start, const double* q_goal, int64_t B,
                             const double* lo, const double* hi, uint32_t seed, double step, double min_advance, int max_iters,
                             int max_nodes, int max_waypoints, double margin, double tol, int max_steps, int32_t* status, int32_t* count,
                             double* waypoints, int32_t* iterations, int32_t* nodes, int32_t* evaluations) {
   const char* fn = "mp_rrt_connect_host_f64";
-  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
-  CTX_ENTER(ctx);
-  REQUIRE_SMALL(fn);
-  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  CHECK_SPHERE_ENTRY(fn);
   MpRrtParams P;
   if (int rc = mp_rrt_connect_check(fn, model->d.n, lo, hi, seed, step, min_advance, max_iters, max_nodes, max_waypoints, margin, tol,
                                     max_steps, &P))
@@ -3267,13 +3272,10 @@ int mp_rrt_connect_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h,
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
   REQUIRE(q_start && q_goal, "%s: null host pointer", fn);
-  long blocks = 0;
-  HIP_TRY(mpk_rrt_connect_resident(model->d.n, h->sph.S, ctx->compute_units, &blocks));
+  MpQueuePlan plan;
+  HIP_TRY(mpk_queue_plan(MP_QUEUE_RRT, model->d.n, h->sph.S, ctx->compute_units, &plan));
   const size_t n = (size_t)model->d.n, qb = (size_t)B * n * sizeof(double), ib = (size_t)B * sizeof(int32_t);
-  const size_t block_bytes = (size_t)mp_rrt_connect_workspace_bytes(model->d.n, max_nodes, 1);
-  blocks = std::min<long>(blocks, (long)((B + 63) / 64));
-  blocks = std::max<long>(1, std::min<long>(blocks, (long)(((size_t)1 << 30) / block_bytes)));
-  const size_t ws_bytes = (size_t)blocks * block_bytes;
+  const size_t ws_bytes = host_workspace_bytes(plan, B, (size_t)mp_rrt_connect_workspace_bytes(model->d.n, max_nodes, 1));
   HostCall hc(ctx);  // (h is the collision handle)
   const double *ds = hc.in(q_start, qb), *dg = hc.in(q_goal, qb);
   int32_t *dstatus = hc.out(status, ib), *dcount = hc.out(count, ib);
@@ -3281,18 +3283,18 @@ int mp_rrt_connect_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h,
   int32_t *dit = hc.out(iterations, ib), *dnodes = hc.out(nodes, 2 * ib), *dev = hc.out(evaluations, ib);
   void* dws = hc.work(ws_bytes);
   return hc.run([&] {
-    return rrt_connect_impl(fn, ctx, model, h, ds, dg, B, P, dws, ws_bytes, 0, dstatus, dcount, dwp, dit, dnodes, dev);
+    return rrt_connect_impl(fn, ctx, model, h, ds, dg, B, P, dws, ws_bytes, 0, &plan, dstatus, dcount, dwp, dit, dnodes, dev);
   });
 }
 
 }  // extern "C"
 
-// ---- batched path shortcutting over the sphere model (mp_shortcut.h).  The grid: the resident blocks, ceil(B / 64), max_blocks and
-// what the workspace holds, whichever is smallest.
+// ---- batched path shortcutting over the sphere model (mp_shortcut.h).  `made`: as in rrt_connect_impl.
 static int path_shortcut_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_in,
                               const int32_t* d_count_in, int64_t B, const MpShortcutParams& P, void* d_ws, size_t ws_bytes,
-                              int max_blocks, int32_t* d_status, int32_t* d_count, double* d_wp, double* d_len_in, double* d_len_out,
-                              int32_t* d_iters, int32_t* d_accepted, int32_t* d_full, int32_t* d_evals) {
+                              int max_blocks, const MpQueuePlan* made, int32_t* d_status, int32_t* d_count, double* d_wp,
+                              double* d_len_in, double* d_len_out, int32_t* d_iters, int32_t* d_accepted, int32_t* d_full,
+                              int32_t* d_evals) {
   REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
@@ -3310,17 +3312,12 @@ static int path_shortcut_impl(const char* fn, mp_ctx* ctx, const mp_model* model
   mp_collision::Resident* R = nullptr;
   if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
   PROFILE_SCOPE(ctx, fn);
-  long grid = 0;
-  unsigned lds = 0;
-  HIP_TRY(mpk_path_shortcut_resident(model->d.n, h->sph.S, ctx->compute_units, &grid, &lds));
-  grid = std::min<long>(grid, (long)((B + 63) / 64));
-  if (max_blocks > 0) grid = std::min<long>(grid, max_blocks);
-  grid = std::min<long>(grid, (long)(ws_bytes / block_bytes));
-  HIP_TRY(mpk_path_shortcut(ctx->compute, model->d, h->sph.S, static_cast<const MpColSpheres*>(R->sph),
-                            reinterpret_cast<const MpColPair*>(static_cast<const char*>(R->sph) + sizeof(MpColSpheres)),
-                            static_cast<const MpColWorld*>(R->world), d_in, d_count_in, (long)B, P, d_status, d_count, d_wp, d_len_in,
-                            d_len_out, d_iters, d_accepted, d_full, d_evals, static_cast<double*>(d_ws),
-                            static_cast<unsigned long long*>(R->counter), grid, lds));
+  MpQueuePlan plan;
+  if (made) plan = *made;
+  else HIP_TRY(mpk_queue_plan(MP_QUEUE_SHORTCUT, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_path_shortcut(ctx->compute, model->d, collision_device(h, R), d_in, d_count_in, (long)B, P, d_status, d_count, d_wp,
+                            d_len_in, d_len_out, d_iters, d_accepted, d_full, d_evals, static_cast<double*>(d_ws),
+                            queue_grid(plan, B, max_blocks, ws_bytes / block_bytes), plan.lds));
   return MP_OK;
 }
 
@@ -3332,39 +3329,29 @@ int mp_path_shortcut_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, co
                          int32_t* d_count, double* d_waypoints, double* d_length_in, double* d_length_out, int32_t* d_iterations,
                          int32_t* d_accepted, int32_t* d_skipped_full, int32_t* d_evaluations) {
   const char* fn = "mp_path_shortcut_f64";
-  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
-  CTX_ENTER(ctx);
-  REQUIRE_SMALL(fn);
-  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  CHECK_SPHERE_ENTRY(fn);
   MpShortcutParams P;
   if (int rc = mp_path_shortcut_check(fn, W_in, seed, max_iters, min_gain, max_waypoints, margin, tol, max_steps, &P)) return rc;
-  return path_shortcut_impl(fn, ctx, model, h, d_waypoints_in, d_count_in, B, P, d_workspace, workspace_bytes, max_blocks, d_status,
-                            d_count, d_waypoints, d_length_in, d_length_out, d_iterations, d_accepted, d_skipped_full, d_evaluations);
+  return path_shortcut_impl(fn, ctx, model, h, d_waypoints_in, d_count_in, B, P, d_workspace, workspace_bytes, max_blocks, nullptr,
+                            d_status, d_count, d_waypoints, d_length_in, d_length_out, d_iterations, d_accepted, d_skipped_full,
+                            d_evaluations);
 }
 
-// the workspace comes from the pool: as many blocks as the launch can use, at most 1 GiB of them (never less than one block)
 int mp_path_shortcut_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* waypoints_in, const int32_t* count_in,
                               int64_t B, int64_t W_in, uint32_t seed, int max_iters, double min_gain, int max_waypoints, double margin,
                               double tol, int max_steps, int32_t* status, int32_t* count, double* waypoints, double* length_in,
                               double* length_out, int32_t* iterations, int32_t* accepted, int32_t* skipped_full, int32_t* evaluations) {
   const char* fn = "mp_path_shortcut_host_f64";
-  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
-  CTX_ENTER(ctx);
-  REQUIRE_SMALL(fn);
-  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n);
+  CHECK_SPHERE_ENTRY(fn);
   MpShortcutParams P;
   if (int rc = mp_path_shortcut_check(fn, W_in, seed, max_iters, min_gain, max_waypoints, margin, tol, max_steps, &P)) return rc;
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
   REQUIRE(waypoints_in && count_in, "%s: null host pointer", fn);
-  long blocks = 0;
-  unsigned lds = 0;  // (the launch asks again: path_shortcut_impl)
-  HIP_TRY(mpk_path_shortcut_resident(model->d.n, h->sph.S, ctx->compute_units, &blocks, &lds));
+  MpQueuePlan plan;
+  HIP_TRY(mpk_queue_plan(MP_QUEUE_SHORTCUT, model->d.n, h->sph.S, ctx->compute_units, &plan));
   const size_t n = (size_t)model->d.n, ib = (size_t)B * sizeof(int32_t), db = (size_t)B * sizeof(double);
-  const size_t block_bytes = (size_t)mp_path_shortcut_workspace_bytes(model->d.n, max_waypoints, 1);
-  blocks = std::min<long>(blocks, (long)((B + 63) / 64));
-  blocks = std::max<long>(1, std::min<long>(blocks, (long)(((size_t)1 << 30) / block_bytes)));
-  const size_t ws_bytes = (size_t)blocks * block_bytes;
+  const size_t ws_bytes = host_workspace_bytes(plan, B, (size_t)mp_path_shortcut_workspace_bytes(model->d.n, max_waypoints, 1));
   HostCall hc(ctx);  // (h is the collision handle)
   const double* din = hc.in(waypoints_in, (size_t)B * (size_t)W_in * n * sizeof(double));
   const int32_t* dcin = hc.in(count_in, ib);
@@ -3374,7 +3361,8 @@ int mp_path_shortcut_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* 
   int32_t *dit = hc.out(iterations, ib), *dacc = hc.out(accepted, ib), *dfull = hc.out(skipped_full, ib), *dev = hc.out(evaluations, ib);
   void* dws = hc.work(ws_bytes);
   return hc.run([&] {
-    return path_shortcut_impl(fn, ctx, model, h, din, dcin, B, P, dws, ws_bytes, 0, dstatus, dcount, dwp, dli, dlo, dit, dacc, dfull, dev);
+    return path_shortcut_impl(fn, ctx, model, h, din, dcin, B, P, dws, ws_bytes, 0, &plan, dstatus, dcount, dwp, dli, dlo, dit, dacc,
+                              dfull, dev);
   });
 }
 
@@ -3409,9 +3397,7 @@ int mp_collision_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, c
                           double eps_self, double* dist_world, int32_t* arg_world, double* dist_self, int32_t* arg_self,
                           double* grad_dist_world, double* grad_dist_self, double* cost, double* grad) {
   const char* fn = "mp_collision_host_f64";
-  REQUIRE(ctx && model && h, "%s: null context, model or collision handle", fn);
-  CTX_ENTER(ctx);
-  REQUIRE_SMALL(fn);
+  CHECK_SPHERE_ENTRY(fn);
   REQUIRE(rows >= 0, "%s: negative row count", fn);
   if (rows == 0) return MP_OK;
   REQUIRE(q, "%s: null host pointer", fn);

@@ -363,6 +363,18 @@ struct MpColBoundsLanes {  // [entry][lane]
   MP_HD void put(int i, double x) { base[i * 64] = x; }
   MP_HD double get(int i) const { return base[i * 64]; }
 };
+// The dynamic LDS of the one-wave work-queue kernels built on the edge check (k_collision_edges, k_rrt_connect, k_path_shortcut): the
+// park of S centres [sphere][xyz][lane], then the speed bounds [entry][lane] at mp_col_queue_bounds_offset doubles.
+MP_HD constexpr int mp_col_queue_bounds_offset(int S) { return 3 * 64 * S; }
+MP_HD constexpr unsigned mp_col_queue_lds_bytes(int n, int S) {
+  return (unsigned)(mp_col_queue_bounds_offset(S) + 64 * (n * (n + 1) / 2)) * (unsigned)sizeof(double);
+}
+// The wave-wide steps of a state machine (mp_rrt.h, mp_shortcut.h) where one problem runs at a time, as in the CPU twins: the identity.
+// The kernels' version over the 64 lanes is MpWaveOpsLanes (mp_kernels.hip).
+struct MpWaveOpsSerial {
+  MP_HD int wave_max(int v) const { return v; }
+  MP_HD bool wave_any(bool b) const { return b; }
+};
 
 struct MpColEdgeParams {
   double margin, tol;

@@ -1196,19 +1196,35 @@ int mp_collision_pack_world(const char* fn, int O, const int32_t* kind, const do
   return MP_OK;
 }
 
+// ---- what the four twins below share: the first checks, and the handle's host tables as the per-row code reads them
+static int col_too_many(const char* fn, int n) {
+  char msg[192];
+  std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, n);
+  return mp_set_error(MP_ERR_UNSUPPORTED, msg);
+}
+static int col_twin_enter(const char* fn, const mp_model* model, const mp_collision* h) {
+  if (!model || !h) return col_fail("%s: null model or collision handle", fn);
+  if (model->big) return col_too_many(fn, model->d.n);
+  if (h->n != model->d.n) return col_fail("%s: the collision handle was made for a model of %ld joints", fn, h->n);
+  return MP_OK;
+}
+static int col_joint_count(const char* fn, int n) {  // the n of the two workspace sizes
+  if (n < 1) return col_fail("%s: joint count %ld below 1", fn, n);
+  return n > MP_MAX_DOF ? col_too_many(fn, n) : MP_OK;
+}
+typedef MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*> MpColTablesHost;
+static MpColTablesHost col_host_tables(const mp_collision* h, MpColWorld& hdr) {  // hdr: the caller's, the tables point at it
+  hdr = {(int)h->world.size(), {0, 0, 0}};
+  return {&h->sph, h->pairs.data(), &hdr, h->world.data()};
+}
+
 extern "C" {
 
 int mp_collision_cpu_f64(const mp_model* model, const mp_collision* h, const double* q, int64_t rows, double eps_world, double eps_self,
                          double* dist_world, int32_t* arg_world, double* dist_self, int32_t* arg_self, double* grad_dist_world,
                          double* grad_dist_self, double* cost, double* grad, int nthreads) {
   const char* fn = "mp_collision_cpu_f64";
-  if (!model || !h) return col_fail("%s: null model or collision handle", fn);
-  if (model->big) {
-    char msg[192];
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (h->n != model->d.n) return col_fail("%s: the collision handle was made for a model of %ld joints", fn, h->n);
+  if (int rc = col_twin_enter(fn, model, h)) return rc;
   if (!(eps_world > 0.0) || !(eps_self > 0.0) || !std::isfinite(eps_world) || !std::isfinite(eps_self))
     return col_fail("%s: eps_world and eps_self must be positive and finite", fn);
   if (rows < 0) return col_fail("%s: negative row count", fn);
@@ -1217,9 +1233,8 @@ int mp_collision_cpu_f64(const mp_model* model, const mp_collision* h, const dou
   if (!dist_world && !arg_world && !dist_self && !arg_self && !grad_dist_world && !grad_dist_self && !cost && !grad)
     return col_fail("%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
-  const MpColWorld hdr = {(int)h->world.size(), {0, 0, 0}};
-  const MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*> tb = {&h->sph, h->pairs.data(), &hdr,
-                                                                                                          h->world.data()};
+  MpColWorld hdr;
+  const MpColTablesHost tb = col_host_tables(h, hdr);
   const bool want_grad = grad_dist_world || grad_dist_self || grad;
   MP_CPU_DISPATCH(M.n, {
     parallel_for(rows, 64, nthreads, [&](int64_t lo, int64_t hi) {
@@ -1258,22 +1273,15 @@ int mp_collision_edges_cpu_f64(const mp_model* model, const mp_collision* h, con
                                double margin, double tol, int max_steps, int32_t* status, double* t, int32_t* steps, double* clearance,
                                int32_t* witness, int nthreads) {
   const char* fn = "mp_collision_edges_cpu_f64";
-  if (!model || !h) return col_fail("%s: null model or collision handle", fn);
-  if (model->big) {
-    char msg[192];
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (h->n != model->d.n) return col_fail("%s: the collision handle was made for a model of %ld joints", fn, h->n);
+  if (int rc = col_twin_enter(fn, model, h)) return rc;
   if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
   if (edges < 0) return col_fail("%s: negative edge count", fn);
   if (edges == 0) return MP_OK;
   if (!q_from || !q_to) return col_fail("%s: null pointer", fn);
   if (!status && !t && !steps && !clearance && !witness) return col_fail("%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
-  const MpColWorld hdr = {(int)h->world.size(), {0, 0, 0}};
-  const MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*> tb = {&h->sph, h->pairs.data(), &hdr,
-                                                                                                          h->world.data()};
+  MpColWorld hdr;
+  const MpColTablesHost tb = col_host_tables(h, hdr);
   const MpColEdgeParams P = {margin, tol, max_steps, 0};
   MP_CPU_DISPATCH(M.n, {
     parallel_for(edges, 16, nthreads, [&](int64_t lo, int64_t hi) {
@@ -1314,12 +1322,7 @@ extern "C" {
 
 int64_t mp_rrt_connect_workspace_bytes(int n, int max_nodes, int blocks) {
   const char* fn = "mp_rrt_connect_workspace_bytes";
-  if (n < 1) return -(int64_t)col_fail("%s: joint count %ld below 1", fn, n);
-  if (n > MP_MAX_DOF) {
-    char msg[160];
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, n);
-    return -(int64_t)mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
+  if (int rc = col_joint_count(fn, n)) return -(int64_t)rc;
   if (max_nodes < 2 || max_nodes > MP_RRT_MAX_NODES) return -(int64_t)col_fail("%s: max_nodes %ld outside 2..65536", fn, max_nodes);
   if (blocks < 1) return -(int64_t)col_fail("%s: block count %ld below 1", fn, blocks);
   return (int64_t)blocks * 64 * 2 * (int64_t)max_nodes * (8 * (int64_t)n + 4);
@@ -1330,13 +1333,7 @@ int mp_rrt_connect_cpu_f64(const mp_model* model, const mp_collision* h, const d
                            int max_nodes, int max_waypoints, double margin, double tol, int max_steps, int32_t* status, int32_t* count,
                            double* waypoints, int32_t* iterations, int32_t* nodes, int32_t* evaluations, int nthreads) {
   const char* fn = "mp_rrt_connect_cpu_f64";
-  if (!model || !h) return col_fail("%s: null model or collision handle", fn);
-  if (model->big) {
-    char msg[192];
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (h->n != model->d.n) return col_fail("%s: the collision handle was made for a model of %ld joints", fn, h->n);
+  if (int rc = col_twin_enter(fn, model, h)) return rc;
   MpRrtParams P;
   if (int rc = mp_rrt_connect_check(fn, model->d.n, lo, hi, seed, step, min_advance, max_iters, max_nodes, max_waypoints, margin, tol,
                                     max_steps, &P))
@@ -1346,9 +1343,8 @@ int mp_rrt_connect_cpu_f64(const mp_model* model, const mp_collision* h, const d
   if (!q_start || !q_goal) return col_fail("%s: null pointer", fn);
   if (!status && !count && !waypoints && !iterations && !nodes && !evaluations) return col_fail("%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
-  const MpColWorld hdr = {(int)h->world.size(), {0, 0, 0}};
-  const MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*> tb = {&h->sph, h->pairs.data(), &hdr,
-                                                                                                          h->world.data()};
+  MpColWorld hdr;
+  const MpColTablesHost tb = col_host_tables(h, hdr);
   MP_CPU_DISPATCH(M.n, {
     parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
       std::vector<double> tree((size_t)2 * (size_t)max_nodes * N);  // the thread's trees, reused like a lane's
@@ -1384,12 +1380,7 @@ extern "C" {
 
 int64_t mp_path_shortcut_workspace_bytes(int n, int max_waypoints, int blocks) {
   const char* fn = "mp_path_shortcut_workspace_bytes";
-  if (n < 1) return -(int64_t)col_fail("%s: joint count %ld below 1", fn, n);
-  if (n > MP_MAX_DOF) {
-    char msg[160];
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, n);
-    return -(int64_t)mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
+  if (int rc = col_joint_count(fn, n)) return -(int64_t)rc;
   if (max_waypoints < 2 || max_waypoints > MP_SC_MAX_WAYPOINTS)
     return -(int64_t)col_fail("%s: max_waypoints %ld outside 2..65536", fn, max_waypoints);
   if (blocks < 1) return -(int64_t)col_fail("%s: block count %ld below 1", fn, blocks);
@@ -1401,13 +1392,7 @@ int mp_path_shortcut_cpu_f64(const mp_model* model, const mp_collision* h, const
                              int max_steps, int32_t* status, int32_t* count, double* waypoints, double* length_in, double* length_out,
                              int32_t* iterations, int32_t* accepted, int32_t* skipped_full, int32_t* evaluations, int nthreads) {
   const char* fn = "mp_path_shortcut_cpu_f64";
-  if (!model || !h) return col_fail("%s: null model or collision handle", fn);
-  if (model->big) {
-    char msg[192];
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (h->n != model->d.n) return col_fail("%s: the collision handle was made for a model of %ld joints", fn, h->n);
+  if (int rc = col_twin_enter(fn, model, h)) return rc;
   MpShortcutParams P;
   if (int rc = mp_path_shortcut_check(fn, W_in, seed, max_iters, min_gain, max_waypoints, margin, tol, max_steps, &P)) return rc;
   if (B < 0) return col_fail("%s: negative problem count", fn);
@@ -1416,9 +1401,8 @@ int mp_path_shortcut_cpu_f64(const mp_model* model, const mp_collision* h, const
   if (!status && !count && !waypoints && !length_in && !length_out && !iterations && !accepted && !skipped_full && !evaluations)
     return col_fail("%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
-  const MpColWorld hdr = {(int)h->world.size(), {0, 0, 0}};
-  const MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*> tb = {&h->sph, h->pairs.data(), &hdr,
-                                                                                                          h->world.data()};
+  MpColWorld hdr;
+  const MpColTablesHost tb = col_host_tables(h, hdr);
   MP_CPU_DISPATCH(M.n, {
     parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
       std::vector<double> pts((size_t)max_waypoints * N), cum((size_t)max_waypoints);  // the thread's path, reused like a lane's

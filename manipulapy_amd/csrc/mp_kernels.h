@@ -174,41 +174,43 @@ hipError_t mpk_traj_id_hard(hipStream_t s, const MpModel<float>* d_model, int n,
 hipError_t mpk_traj_id_tab(hipStream_t s, const MpModel<float>& M, const MpCall<float>& C, bool ftip, const float* start,
                            const float* end, long B, long Nt, const double* tab, float* tau);
 
-// sphere-model collision distances, cost and gradients (csrc/mp_collision.h), float64, 1..MP_MAX_DOF joints; S sizes the dynamic LDS;
-// the tables are device-resident; every output may be null
+// sphere-model collision distances, cost and gradients (csrc/mp_collision.h), float64, 1..MP_MAX_DOF joints; D.S sizes the dynamic
+// LDS; every output may be null
 struct MpColSpheres;
 struct MpColPair;
 struct MpColWorld;
-hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
-                         const MpColWorld* d_world, const double* q, long rows, double eps_world, double eps_self, double* dist_world,
-                         int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world, double* grad_dist_self, double* cost,
-                         double* grad);
-// continuous collision checking of joint-space edges (csrc/mp_collision.h): a work queue over `edges`, one evaluated configuration a
-// trip; queue_counter (8 bytes of device memory) is zeroed on the stream first.  The grid is the resident blocks of the device
-// (occupancy x compute_units), at most ceil(edges / 64) and at most max_blocks if that is positive.
+struct MpColDevice {  // a collision handle's tables on one device, and the 8-byte head of the work queue beside them
+  int S;
+  const MpColSpheres* sph;
+  const MpColPair* pairs;
+  const MpColWorld* world;
+  unsigned long long* counter;
+};
+hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q, long rows, double eps_world,
+                         double eps_self, double* dist_world, int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world,
+                         double* grad_dist_self, double* cost, double* grad);
+// The one-wave work-queue kernels on the sphere model: continuous collision checking of joint-space edges (csrc/mp_collision.h),
+// batched RRT-Connect (csrc/mp_rrt.h, the trees in `workspace`: blocks x 64 x 2 max_nodes (8 n + 4) bytes) and batched path
+// shortcutting (csrc/mp_shortcut.h, the working paths in `workspace`: blocks x 64 x max_waypoints (8 n + 8) bytes).  A work queue
+// over the edges / problems, one evaluated configuration a trip.  mpk_queue_plan gives a kernel's dynamic LDS and the blocks of it the
+// device keeps resident (occupancy x compute_units); the caller settles the grid (`blocks`) from that, the count, its cap and the
+// workspace, and hands grid and LDS to the launch, which zeroes D.counter on the stream first and makes no runtime query.
+enum MpQueueKernel { MP_QUEUE_EDGES, MP_QUEUE_RRT, MP_QUEUE_SHORTCUT };
+struct MpQueuePlan {
+  unsigned lds;
+  long resident;
+};
+hipError_t mpk_queue_plan(MpQueueKernel kernel, int n, int S, int compute_units, MpQueuePlan* plan);
 struct MpColEdgeParams;
-hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
-                               const MpColWorld* d_world, const double* q_from, const double* q_to, long edges, const MpColEdgeParams& P,
-                               int* status, double* t, int* steps, double* clearance, int* witness, unsigned long long* queue_counter,
-                               int compute_units, int max_blocks);
-// batched RRT-Connect over the sphere model (csrc/mp_rrt.h): a work queue over `problems`, one evaluated configuration a trip, the
-// trees in `workspace` (blocks x 64 x 2 max_nodes (8 n + 4) bytes); queue_counter is zeroed on the stream first.
-// mpk_rrt_connect_resident gives the one-wave blocks the device keeps resident; the caller settles the grid (`blocks`) from it, the
-// problem count, its cap and the workspace.
+hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q_from, const double* q_to,
+                               long edges, const MpColEdgeParams& P, int* status, double* t, int* steps, double* clearance, int* witness,
+                               long blocks, unsigned lds);
 struct MpRrtParams;
-hipError_t mpk_rrt_connect_resident(int n, int S, int compute_units, long* blocks);
-hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
-                           const MpColWorld* d_world, const double* q_start, const double* q_goal, long problems, const MpRrtParams& P,
-                           int* status, int* count, double* waypoints, int* iterations, int* nodes, int* evaluations, double* workspace,
-                           unsigned long long* queue_counter, int compute_units, long blocks);
-// batched path shortcutting over the sphere model (csrc/mp_shortcut.h): the same queue, one evaluated configuration a trip, the
-// working paths in `workspace` (blocks x 64 x max_waypoints (8 n + 8) bytes); queue_counter is zeroed on the stream first.  The
-// caller settles the grid (`blocks`) from mpk_path_shortcut_resident, the problem count, its cap and the workspace, and hands the
-// dynamic LDS size it got there (`lds`) on to the launch.
+hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q_start, const double* q_goal,
+                           long problems, const MpRrtParams& P, int* status, int* count, double* waypoints, int* iterations, int* nodes,
+                           int* evaluations, double* workspace, long blocks, unsigned lds);
 struct MpShortcutParams;
-hipError_t mpk_path_shortcut_resident(int n, int S, int compute_units, long* blocks, unsigned* lds);
-hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
-                             const MpColWorld* d_world, const double* waypoints_in, const int* count_in, long problems,
-                             const MpShortcutParams& P, int* status, int* count, double* waypoints, double* length_in,
-                             double* length_out, int* iterations, int* accepted, int* skipped_full, int* evaluations,
-                             double* workspace, unsigned long long* queue_counter, long blocks, unsigned lds);
+hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
+                             long problems, const MpShortcutParams& P, int* status, int* count, double* waypoints, double* length_in,
+                             double* length_out, int* iterations, int* accepted, int* skipped_full, int* evaluations, double* workspace,
+                             long blocks, unsigned lds);

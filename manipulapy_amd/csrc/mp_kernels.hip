@@ -426,6 +426,33 @@ typedef const __attribute__((address_space(4))) MpColSpheres MpColSpheresConst;
 typedef const __attribute__((address_space(4))) MpColPair MpColPairConst;
 typedef const __attribute__((address_space(4))) MpColWorld MpColWorldConst;
 typedef const __attribute__((address_space(4))) MpColObstacle MpColObstacleConst;
+typedef MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*> MpColTablesConst;
+__device__ __forceinline__ MpColTablesConst mp_col_tables_const(const MpColSpheres* sph, const MpColPair* pairs, const MpColWorld* world) {
+  return {(MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
+}
+// The scaffold of the one-wave work-queue kernels on the sphere model (k_collision_edges, k_rrt_connect, k_path_shortcut; DESIGN
+// §4.10).  Their dynamic LDS, sized by mp_col_queue_lds_bytes (mp_collision.h): the park of S centres, then the edge's n (n + 1) / 2
+// speed bounds [entry][lane] - per lane, but read at wave-uniform link numbers.  Each lane reads and writes only its own column of
+// both, so no barrier is needed.
+struct MpColQueueLanes {
+  MpColParkLanes park;
+  MpColBoundsLanes L;
+};
+__device__ __forceinline__ MpColQueueLanes mp_col_queue_lanes(double* lds, int lane, int S) {
+  return {{lds + lane}, {lds + mp_col_queue_bounds_offset(S) + lane}};
+}
+// the wave-wide steps of the state machines of mp_rrt.h and mp_shortcut.h over the 64 lanes (the twins': MpWaveOpsSerial)
+struct MpWaveOpsLanes {
+  __device__ __forceinline__ int wave_max(int v) const {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int w = __shfl_xor(v, o);
+      v = w > v ? w : v;
+    }
+    return v;
+  }
+  __device__ __forceinline__ bool wave_any(bool b) const { return __any(b ? 1 : 0) != 0; }
+};
 
 template <int N, bool WANT_GRAD>
 __global__ __launch_bounds__(64) void k_collision(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
@@ -458,8 +485,7 @@ __global__ __launch_bounds__(64) void k_collision(const MpModel<double> M, const
   }
   MpBad<double> bad;
   bad.add(a);
-  const MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*> tb = {
-      (MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
+  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
   MpColParkLanes park{mp_col_park + lane};
   MpColRow<N> o;
   mp_collision_row<N, WANT_GRAD>(M, tb, a, eps_world, eps_self, park, o);
@@ -482,9 +508,8 @@ __global__ __launch_bounds__(64) void k_collision(const MpModel<double> M, const
 // One wave per block (the park is [sphere][xyz][lane]), tables through constant-address-space pointers as in k_collision.  Work queue
 // as in k_ik: a lane without an edge takes the next index from the device counter, every trip of the loop evaluates ONE configuration
 // of the lane's own edge, and a finished lane writes its row and fetches another - iteration counts run from 1 to a few hundred between
-// neighbouring edges.  The loop ends because the counter only grows and every edge ends within max_steps.  Dynamic LDS: the park of
-// S centres, then the edge's n (n + 1) / 2 speed bounds [entry][lane] - per lane, but read at wave-uniform link numbers.  Each lane
-// reads and writes only its own column of both, so no barrier is needed.  The 2 n inputs of an edge are plain per-lane loads.
+// neighbouring edges.  The loop ends because the counter only grows and every edge ends within max_steps.  Dynamic LDS: the park and
+// the speed bounds (mp_col_queue_lanes).  The 2 n inputs of an edge are plain per-lane loads.
 template <int N>
 __global__ __launch_bounds__(64) void k_collision_edges(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                         const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
@@ -494,10 +519,8 @@ __global__ __launch_bounds__(64) void k_collision_edges(const MpModel<double> M,
                                                         int* __restrict__ witness, unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_col_edge_lds[];
   const int lane = (int)threadIdx.x;
-  const MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*> tb = {
-      (MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
-  MpColParkLanes park{mp_col_edge_lds + lane};
-  MpColBoundsLanes L{mp_col_edge_lds + 3 * 64 * tb.sph->S + lane};
+  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  MpColQueueLanes Q = mp_col_queue_lanes(mp_col_edge_lds, lane, tb.sph->S);
   MpColEdgeState<N> S;
   bool have = false;
   long row = 0;
@@ -508,10 +531,10 @@ __global__ __launch_bounds__(64) void k_collision_edges(const MpModel<double> M,
       double a[N], b[N];
       RunIO<double, N>::load(q_from, row, a);
       RunIO<double, N>::load(q_to, row, b);
-      mp_col_edge_begin<N>(M, tb.sph, a, b, S, L);
+      mp_col_edge_begin<N>(M, tb.sph, a, b, S, Q.L);
       have = true;
     }
-    if (const int done = mp_col_edge_iterate<N>(M, tb, P, S, park, L)) {
+    if (const int done = mp_col_edge_iterate<N>(M, tb, P, S, Q.park, Q.L)) {
       int st, sp, w[3];
       double tt, cl;
       mp_col_edge_result<N>(S, done, st, tt, sp, cl, w);
@@ -528,13 +551,13 @@ __global__ __launch_bounds__(64) void k_collision_edges(const MpModel<double> M,
 // ------------------------------------------------------- batched RRT-Connect over the sphere model (float64, mp_rrt.h)
 // One wave per block and a work queue as in k_collision_edges: a lane without a problem takes the next index from the device counter,
 // every trip of the loop does the selection work the lane's problem is waiting for and evaluates ONE configuration of its running
-// edge, and a finished lane writes its row and fetches another.  Dynamic LDS: the park and the speed bounds, laid out exactly as in
-// k_collision_edges.  The trees live in the caller's workspace and belong to the resident lane, not to the problem: per block the
+// edge, and a finished lane writes its row and fetches another.  Dynamic LDS: the park and the speed bounds (mp_col_queue_lanes).
+// The trees live in the caller's workspace and belong to the resident lane, not to the problem: per block the
 // nodes [tree][node][dim][lane] (doubles), then the parents [tree][node][lane] (int32); a new problem resets the lane's counts
 // only.  Each lane reads and writes only its own column, in program order, so no barrier or fence is needed.  The nearest search
 // (mp_rrt_nearest) is entered by all 64 lanes on every trip and runs to the wave's largest count, so the wave reads whole 512-byte
 // lines; the loop of the kernel ends for the whole wave at once, when no lane holds a problem and the queue is empty.
-struct MpRrtTreeLanes {
+struct MpRrtTreeLanes : MpWaveOpsLanes {
   double* nodes;  // already offset by the block and the lane
   int* parents;
   int max_nodes, n;
@@ -542,15 +565,6 @@ struct MpRrtTreeLanes {
   __device__ __forceinline__ void put(int tree, int v, int j, double x) { nodes[(((long)tree * max_nodes + v) * n + j) * 64] = x; }
   __device__ __forceinline__ int parent(int tree, int v) const { return parents[((long)tree * max_nodes + v) * 64]; }
   __device__ __forceinline__ void set_parent(int tree, int v, int p) { parents[((long)tree * max_nodes + v) * 64] = p; }
-  __device__ __forceinline__ int wave_max(int v) const {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int w = __shfl_xor(v, o);
-      v = w > v ? w : v;
-    }
-    return v;
-  }
-  __device__ __forceinline__ bool wave_any(bool b) const { return __any(b ? 1 : 0) != 0; }
 };
 
 template <int N>
@@ -563,14 +577,12 @@ __global__ __launch_bounds__(64) void k_rrt_connect(const MpModel<double> M, con
                                                     unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_rrt_lds[];
   const int lane = (int)threadIdx.x;
-  const MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*> tb = {
-      (MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
-  MpColParkLanes park{mp_rrt_lds + lane};
-  MpColBoundsLanes L{mp_rrt_lds + 3 * 64 * tb.sph->S + lane};
+  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  MpColQueueLanes Q = mp_col_queue_lanes(mp_rrt_lds, lane, tb.sph->S);
   const size_t node_words = (size_t)2 * (size_t)P.max_nodes * N * 64;                  // doubles a block
   const size_t block_words = node_words + (size_t)P.max_nodes * 64;                   // + 2 max_nodes 64 int32
   double* const mine = workspace + (size_t)blockIdx.x * block_words;
-  MpRrtTreeLanes T{mine + lane, reinterpret_cast<int*>(mine + node_words) + lane, P.max_nodes, N};
+  MpRrtTreeLanes T{{}, mine + lane, reinterpret_cast<int*>(mine + node_words) + lane, P.max_nodes, N};
   MpRrtState<N> S;
   S.phase = MP_RRT_IDLE;
   S.done = 0;
@@ -585,13 +597,13 @@ __global__ __launch_bounds__(64) void k_rrt_connect(const MpModel<double> M, con
         double a[N], b[N];
         RunIO<double, N>::load(q_start, row, a);
         RunIO<double, N>::load(q_goal, row, b);
-        mp_rrt_begin<N>(M, tb, P, a, b, S, T, L, waypoints != nullptr ? waypoints + row * (long)P.max_waypoints * N : nullptr);
+        mp_rrt_begin<N>(M, tb, P, a, b, S, T, Q.L, waypoints != nullptr ? waypoints + row * (long)P.max_waypoints * N : nullptr);
         have = true;
       }
     }
     if (!T.wave_any(have)) break;
     double* wp = (have && waypoints != nullptr) ? waypoints + row * (long)P.max_waypoints * N : nullptr;
-    if (mp_rrt_trip<N>(M, tb, P, S, T, park, L, wp)) {
+    if (mp_rrt_trip<N>(M, tb, P, S, T, Q.park, Q.L, wp)) {
       if (status != nullptr) status[row] = S.status;
       if (count != nullptr) count[row] = S.count;
       if (iterations != nullptr) iterations[row] = S.k;
@@ -606,14 +618,14 @@ __global__ __launch_bounds__(64) void k_rrt_connect(const MpModel<double> M, con
 // ------------------------------------------------------- batched path shortcutting over the sphere model (float64, mp_shortcut.h)
 // One wave per block and the work queue of k_collision_edges / k_rrt_connect: a lane without a problem takes the next index from the
 // device counter, every trip of the loop does the selection work the lane's problem is waiting for and evaluates ONE configuration
-// of its running edge, and a finished lane writes its row and fetches another.  Dynamic LDS: the park and the speed bounds, laid out
-// exactly as in k_collision_edges.  The working path lives in the caller's workspace and belongs to the resident lane, not to the
+// of its running edge, and a finished lane writes its row and fetches another.  Dynamic LDS: the park and the speed bounds
+// (mp_col_queue_lanes).  The working path lives in the caller's workspace and belongs to the resident lane, not to the
 // problem: per block the waypoints [waypoint][dim][lane] (doubles), then the cumulative lengths [waypoint][lane]; a lane that takes
 // a new problem copies its count_in rows in.  Each lane reads and writes only its own column, in program order, so no barrier or
 // fence is needed.  The locate scan (mp_shortcut_locate) is entered by all 64 lanes on every pass and runs to the wave's largest m,
 // so the wave reads whole 512-byte lines; the splice and the recomputation of the lengths after an accepted shortcut are per lane.
 // The loop of the kernel ends for the whole wave at once, when no lane holds a problem and the queue is empty.
-struct MpShortcutPathLanes {
+struct MpShortcutPathLanes : MpWaveOpsLanes {
   double* pts;  // already offset by the block and the lane
   double* cum;
   int n;
@@ -621,15 +633,6 @@ struct MpShortcutPathLanes {
   __device__ __forceinline__ void put(int w, int j, double x) { pts[((long)w * n + j) * 64] = x; }
   __device__ __forceinline__ double len(int w) const { return cum[(long)w * 64]; }
   __device__ __forceinline__ void set_len(int w, double x) { cum[(long)w * 64] = x; }
-  __device__ __forceinline__ int wave_max(int v) const {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int w = __shfl_xor(v, o);
-      v = w > v ? w : v;
-    }
-    return v;
-  }
-  __device__ __forceinline__ bool wave_any(bool b) const { return __any(b ? 1 : 0) != 0; }
 };
 
 template <int N>
@@ -644,14 +647,12 @@ __global__ __launch_bounds__(64) void k_path_shortcut(const MpModel<double> M, c
                                                       double* __restrict__ workspace, unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_shortcut_lds[];
   const int lane = (int)threadIdx.x;
-  const MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*> tb = {
-      (MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
-  MpColParkLanes park{mp_shortcut_lds + lane};
-  MpColBoundsLanes L{mp_shortcut_lds + 3 * 64 * tb.sph->S + lane};
+  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  MpColQueueLanes Q = mp_col_queue_lanes(mp_shortcut_lds, lane, tb.sph->S);
   const size_t point_words = (size_t)P.max_waypoints * N * 64;           // doubles a block
   const size_t block_words = point_words + (size_t)P.max_waypoints * 64;  // + the lengths
   double* const mine = workspace + (size_t)blockIdx.x * block_words;
-  MpShortcutPathLanes T{mine + lane, mine + point_words + lane, N};
+  MpShortcutPathLanes T{{}, mine + lane, mine + point_words + lane, N};
   MpShortcutState<N> S;
   S.phase = MP_SC_IDLE;
   S.done = 0;
@@ -671,7 +672,7 @@ __global__ __launch_bounds__(64) void k_path_shortcut(const MpModel<double> M, c
     }
     if (!T.wave_any(have)) break;
     double* wp = (have && waypoints != nullptr) ? waypoints + row * (long)P.max_waypoints * N : nullptr;
-    if (mp_shortcut_trip<N>(M, tb, P, S, T, park, L, wp)) {
+    if (mp_shortcut_trip<N>(M, tb, P, S, T, Q.park, Q.L, wp)) {
       if (status != nullptr) status[row] = S.status;
       if (count != nullptr) count[row] = S.m;
       if (length_in != nullptr) length_in[row] = S.lam_in;
@@ -1517,14 +1518,13 @@ hipError_t mpk_fk_jac_vjp(hipStream_t s, const MpModel<double>& M, int frame, co
 }
 
 // dynamic LDS: the park of S world centres for 64 lanes; beyond the default limit the function's own limit is raised first
-hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
-                         const MpColWorld* d_world, const double* q, long rows, double eps_world, double eps_self, double* dist_world,
-                         int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world, double* grad_dist_self, double* cost,
-                         double* grad) {
+hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q, long rows, double eps_world,
+                         double eps_self, double* dist_world, int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world,
+                         double* grad_dist_self, double* cost, double* grad) {
   if (rows <= 0) return hipSuccess;
-  if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
+  if (D.S < 1 || D.S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
   const unsigned gb = (unsigned)((rows + 63) / 64);
-  const unsigned park = (unsigned)S * 3u * 64u * (unsigned)sizeof(double);
+  const unsigned park = (unsigned)D.S * 3u * 64u * (unsigned)sizeof(double);
   const bool want_grad = grad_dist_world != nullptr || grad_dist_self != nullptr || grad != nullptr;
 #define MP_COL_LAUNCH(WG)                                                                                                              \
   do {                                                                                                                                 \
@@ -1533,7 +1533,7 @@ hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, int S, const M
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)park);                                 \
       if (e != hipSuccess) return e;                                                                                                   \
     }                                                                                                                                  \
-    hipLaunchKernelGGL((k_collision<N, WG>), dim3(gb), dim3(64), park, s, M, d_sph, d_pairs, d_world, q, rows, eps_world, eps_self,    \
+    hipLaunchKernelGGL((k_collision<N, WG>), dim3(gb), dim3(64), park, s, M, D.sph, D.pairs, D.world, q, rows, eps_world, eps_self,    \
                        dist_world, arg_world, dist_self, arg_self, grad_dist_world, grad_dist_self, cost, grad);                       \
   } while (0)
   MP_DISPATCH_N(M.n, {
@@ -1544,118 +1544,80 @@ hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, int S, const M
   return hipGetLastError();
 }
 
-// dynamic LDS: the park and the speed bounds of 64 lanes.  The grid holds the blocks the device keeps resident; the queue feeds them.
-hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
-                               const MpColWorld* d_world, const double* q_from, const double* q_to, long edges, const MpColEdgeParams& P,
-                               int* status, double* t, int* steps, double* clearance, int* witness, unsigned long long* queue_counter,
-                               int compute_units, int max_blocks) {
-  if (edges <= 0) return hipSuccess;
-  if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(queue_counter, 0, sizeof(unsigned long long), s);
+// The launch plan of a one-wave work-queue kernel on the sphere model: its dynamic LDS (beyond the default limit the kernel's own
+// limit is raised first) and the blocks of it the device keeps resident.  The only runtime queries of these kernels; the launchers
+// below are handed what the caller made of the plan.
+template <typename K>
+static hipError_t queue_plan(K kernel, int n, int S, int compute_units, MpQueuePlan* plan) {
+  const unsigned lds = mp_col_queue_lds_bytes(n, S);
+  const void* fn = reinterpret_cast<const void*>(kernel);
+  if (lds > 64u * 1024u) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  int per_cu = 0;
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds);
   if (e != hipSuccess) return e;
-  const long want = (edges + 63) / 64;
-  MP_DISPATCH_N(M.n, {
-    const unsigned lds = (unsigned)(3 * S + N * (N + 1) / 2) * 64u * (unsigned)sizeof(double);
-    const void* fn = reinterpret_cast<const void*>(&k_collision_edges<N>);
-    if (lds > 64u * 1024u) {
-      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
+  *plan = {lds, (long)(per_cu > 0 ? per_cu : 1) * (compute_units > 0 ? compute_units : 256)};
+  return hipSuccess;
+}
+
+hipError_t mpk_queue_plan(MpQueueKernel kernel, int n, int S, int compute_units, MpQueuePlan* plan) {
+  if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
+  MP_DISPATCH_N(n, {
+    switch (kernel) {
+      case MP_QUEUE_EDGES: return queue_plan(&k_collision_edges<N>, N, S, compute_units, plan);
+      case MP_QUEUE_RRT: return queue_plan(&k_rrt_connect<N>, N, S, compute_units, plan);
+      case MP_QUEUE_SHORTCUT: return queue_plan(&k_path_shortcut<N>, N, S, compute_units, plan);
     }
-    int per_cu = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds);
-    if (e != hipSuccess) return e;
-    long grid = (long)(per_cu > 0 ? per_cu : 1) * (compute_units > 0 ? compute_units : 256);
-    grid = grid < want ? grid : want;
-    if (max_blocks > 0 && grid > max_blocks) grid = max_blocks;
-    hipLaunchKernelGGL((k_collision_edges<N>), dim3((unsigned)grid), dim3(64), lds, s, M, d_sph, d_pairs, d_world, q_from, q_to, edges, P,
-                       status, t, steps, clearance, witness, queue_counter);
+  })
+  return hipErrorInvalidValue;
+}
+
+// The three queue launches: `blocks` is the grid the caller has settled on (the plan's resident blocks, the count, its cap and the
+// workspace), `lds` the plan's dynamic LDS.  They zero the queue counter on the stream and launch; no runtime query.
+static hipError_t queue_reset(hipStream_t s, const MpColDevice& D, long blocks) {
+  if (D.S < 1 || D.S > MP_COL_MAX_SPHERES || blocks < 1) return hipErrorInvalidValue;
+  return hipMemsetAsync(D.counter, 0, sizeof(unsigned long long), s);
+}
+
+hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q_from, const double* q_to,
+                               long edges, const MpColEdgeParams& P, int* status, double* t, int* steps, double* clearance, int* witness,
+                               long blocks, unsigned lds) {
+  if (edges <= 0) return hipSuccess;
+  const hipError_t e = queue_reset(s, D, blocks);
+  if (e != hipSuccess) return e;
+  MP_DISPATCH_N(M.n, {
+    hipLaunchKernelGGL((k_collision_edges<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, q_from, q_to, edges,
+                       P, status, t, steps, clearance, witness, D.counter);
   })
   return hipGetLastError();
 }
 
-// the one-wave blocks of k_rrt_connect the device keeps resident (LDS as for the edge kernel)
-template <int N>
-static hipError_t rrt_resident(int S, int compute_units, unsigned* lds_out, long* blocks) {
-  const unsigned lds = (unsigned)(3 * S + N * (N + 1) / 2) * 64u * (unsigned)sizeof(double);
-  const void* fn = reinterpret_cast<const void*>(&k_rrt_connect<N>);
-  if (lds > 64u * 1024u) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  int per_cu = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds);
-  if (e != hipSuccess) return e;
-  *lds_out = lds;
-  *blocks = (long)(per_cu > 0 ? per_cu : 1) * (compute_units > 0 ? compute_units : 256);
-  return hipSuccess;
-}
-
-hipError_t mpk_rrt_connect_resident(int n, int S, int compute_units, long* blocks) {
-  if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
-  unsigned lds = 0;
-  MP_DISPATCH_N(n, { return rrt_resident<N>(S, compute_units, &lds, blocks); })
-  return hipErrorInvalidValue;
-}
-
-// `blocks`: the grid the caller has settled on (mpk_rrt_connect_resident, the problem count, max_blocks and the workspace)
-hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
-                           const MpColWorld* d_world, const double* q_start, const double* q_goal, long problems, const MpRrtParams& P,
-                           int* status, int* count, double* waypoints, int* iterations, int* nodes, int* evaluations, double* workspace,
-                           unsigned long long* queue_counter, int compute_units, long blocks) {
+hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q_start, const double* q_goal,
+                           long problems, const MpRrtParams& P, int* status, int* count, double* waypoints, int* iterations, int* nodes,
+                           int* evaluations, double* workspace, long blocks, unsigned lds) {
   if (problems <= 0) return hipSuccess;
-  if (S < 1 || S > MP_COL_MAX_SPHERES || blocks < 1) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(queue_counter, 0, sizeof(unsigned long long), s);
+  const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
   MP_DISPATCH_N(M.n, {
-    unsigned lds = 0;
-    long resident = 0;
-    e = rrt_resident<N>(S, compute_units, &lds, &resident);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_rrt_connect<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, d_sph, d_pairs, d_world, q_start, q_goal, problems,
-                       P, status, count, waypoints, iterations, nodes, evaluations, workspace, queue_counter);
+    hipLaunchKernelGGL((k_rrt_connect<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, q_start, q_goal, problems,
+                       P, status, count, waypoints, iterations, nodes, evaluations, workspace, D.counter);
   })
   return hipGetLastError();
 }
 
-// the one-wave blocks of k_path_shortcut the device keeps resident (LDS as for the edge kernel)
-template <int N>
-static hipError_t shortcut_resident(int S, int compute_units, unsigned* lds_out, long* blocks) {
-  const unsigned lds = (unsigned)(3 * S + N * (N + 1) / 2) * 64u * (unsigned)sizeof(double);
-  const void* fn = reinterpret_cast<const void*>(&k_path_shortcut<N>);
-  if (lds > 64u * 1024u) {
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  int per_cu = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds);
-  if (e != hipSuccess) return e;
-  *lds_out = lds;
-  *blocks = (long)(per_cu > 0 ? per_cu : 1) * (compute_units > 0 ? compute_units : 256);
-  return hipSuccess;
-}
-
-hipError_t mpk_path_shortcut_resident(int n, int S, int compute_units, long* blocks, unsigned* lds) {
-  if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
-  MP_DISPATCH_N(n, { return shortcut_resident<N>(S, compute_units, lds, blocks); })
-  return hipErrorInvalidValue;
-}
-
-// `blocks`: the grid the caller has settled on (mpk_path_shortcut_resident, the problem count, max_blocks and the workspace); `lds`:
-// the dynamic LDS mpk_path_shortcut_resident gave (it has raised the kernel's limit where that is needed), so the launch itself
-// makes no further runtime query
-hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, int S, const MpColSpheres* d_sph, const MpColPair* d_pairs,
-                             const MpColWorld* d_world, const double* waypoints_in, const int* count_in, long problems,
-                             const MpShortcutParams& P, int* status, int* count, double* waypoints, double* length_in,
-                             double* length_out, int* iterations, int* accepted, int* skipped_full, int* evaluations,
-                             double* workspace, unsigned long long* queue_counter, long blocks, unsigned lds) {
+hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
+                             long problems, const MpShortcutParams& P, int* status, int* count, double* waypoints, double* length_in,
+                             double* length_out, int* iterations, int* accepted, int* skipped_full, int* evaluations, double* workspace,
+                             long blocks, unsigned lds) {
   if (problems <= 0) return hipSuccess;
-  if (S < 1 || S > MP_COL_MAX_SPHERES || blocks < 1) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(queue_counter, 0, sizeof(unsigned long long), s);
+  const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
   MP_DISPATCH_N(M.n, {
-    hipLaunchKernelGGL((k_path_shortcut<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, d_sph, d_pairs, d_world, waypoints_in, count_in,
+    hipLaunchKernelGGL((k_path_shortcut<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
                        problems, P, status, count, waypoints, length_in, length_out, iterations, accepted, skipped_full, evaluations,
-                       workspace, queue_counter);
+                       workspace, D.counter);
   })
   return hipGetLastError();
 }

@@ -32,7 +32,7 @@ struct MpRrtParams {
 };
 
 // the twin's trees: nodes [tree][node][dim], parents [tree][node]
-struct MpRrtTreeLocal {
+struct MpRrtTreeLocal : MpWaveOpsSerial {
   double* nodes;
   int* parents;
   int max_nodes, n;
@@ -40,8 +40,6 @@ struct MpRrtTreeLocal {
   MP_HD void put(int tree, int v, int j, double x) { nodes[((long)tree * max_nodes + v) * n + j] = x; }
   MP_HD int parent(int tree, int v) const { return parents[(long)tree * max_nodes + v]; }
   MP_HD void set_parent(int tree, int v, int p) { parents[(long)tree * max_nodes + v] = p; }
-  MP_HD int wave_max(int v) const { return v; }
-  MP_HD bool wave_any(bool b) const { return b; }
 };
 
 constexpr int MP_RRT_IDLE = 0, MP_RRT_START = 1, MP_RRT_GOAL = 2, MP_RRT_EXTEND = 3, MP_RRT_CONNECT = 4, MP_RRT_TOP = 5,
@@ -298,7 +296,7 @@ void mp_rrt_cpu(const MT& M, const TB& tb, const MpRrtParams& P, const double* q
   for (int j = 0; j < N; ++j) { qs[j] = q_start[b * N + j]; qg[j] = q_goal[b * N + j]; }
   MpColParkLocal park;
   MpColBoundsLocal<N> L;
-  MpRrtTreeLocal T{nodes, parents, P.max_nodes, N};
+  MpRrtTreeLocal T{{}, nodes, parents, P.max_nodes, N};
   MpRrtState<N> S;
   double* wp = waypoints ? waypoints + b * (long)P.max_waypoints * N : nullptr;
   mp_rrt_begin<N>(M, tb, P, qs, qg, S, T, L, wp);

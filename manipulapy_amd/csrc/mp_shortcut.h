@@ -30,7 +30,7 @@ struct MpShortcutParams {
 };
 
 // the twin's path: waypoints [waypoint][dim], lengths [waypoint]
-struct MpShortcutPathLocal {
+struct MpShortcutPathLocal : MpWaveOpsSerial {
   double* pts;
   double* cum;
   int n;
@@ -38,8 +38,6 @@ struct MpShortcutPathLocal {
   MP_HD void put(int w, int j, double x) { pts[(long)w * n + j] = x; }
   MP_HD double len(int w) const { return cum[w]; }
   MP_HD void set_len(int w, double x) { cum[w] = x; }
-  MP_HD int wave_max(int v) const { return v; }
-  MP_HD bool wave_any(bool b) const { return b; }
 };
 
 constexpr int MP_SC_IDLE = 0, MP_SC_EDGE = 1, MP_SC_TOP = 2, MP_SC_SCAN = 3, MP_SC_FINISHED = 4;
@@ -278,7 +276,7 @@ void mp_shortcut_cpu(const MT& M, const TB& tb, const MpShortcutParams& P, const
                      int* iterations, int* accepted, int* skipped_full, int* evaluations) {
   MpColParkLocal park;
   MpColBoundsLocal<N> L;
-  MpShortcutPathLocal T{pts, cum, N};
+  MpShortcutPathLocal T{{}, pts, cum, N};
   MpShortcutState<N> S;
   double* wp = waypoints ? waypoints + b * (long)P.max_waypoints * N : nullptr;
   mp_shortcut_begin<N>(P, waypoints_in + b * (long)P.w_in * N, count_in[b], S, T, wp);
