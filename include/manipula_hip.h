@@ -928,6 +928,73 @@ int mp_path_shortcut_cpu_f64(const mp_model* model, const mp_collision* h, const
                              int max_steps, int32_t* status, int32_t* count, double* waypoints, double* length_in, double* length_out,
                              int32_t* iterations, int32_t* accepted, int32_t* skipped_full, int32_t* evaluations, int nthreads);
 
+/* ---- collision-free goal configurations for pose goals over the sphere model above (float64, models of 1..8 joints -
+ * MP_ERR_UNSUPPORTED above that; generic kernels only, no run-time specialisation; csrc/mp_goal.h).  For B independent end-effector
+ * poses in one world: a joint configuration inside a box that reaches the pose and that the planner accepts as a goal.  Damped
+ * Newton attempts from the caller's seed and then from random points of the box; every attempt that reaches the pose gets the
+ * zero-edge decision mp_rrt_connect_* makes for its q_goal, and the first FREE one is the answer.  This is not
+ * mp_inverse_kinematics_*: no best-point restarts, no adaptive damping, and the step is taken on the hybrid Jacobian.  The kernel,
+ * the CPU twin and the tests' NumPy oracle implement exactly the contract below.
+ * Per problem: T_goal, 16 doubles row-major of which only entries 0..11 are read (as mp_inverse_kinematics_* reads a pose), and
+ *   q_seed (n).  Per launch: the box lo, hi (n each, HOST arrays, finite, lo <= hi), seed (uint32), eomg, ev, damping, step_cap (all
+ *   finite and > 0), max_iters >= 0, max_attempts in 1..65536, and margin, tol with the meaning they have for the edges.  Anything
+ *   else is MP_ERR_INVALID with a message.
+ * Random numbers: u(k, j) of mp_rrt_connect_*, with key = the FNV-1a hash (the same offset and prime) over the 64-bit patterns of
+ *   T_goal[0..12) then q_seed[0..n), and k the attempt number.  A problem's result depends on its own content and the seed only -
+ *   not on its row, its lane or the launch.
+ * Procedure:
+ *   A non-finite value among T_goal[0..12) or q_seed: INVALID, nothing is evaluated.
+ *   For attempt a = 0 .. max_attempts - 1:
+ *     theta_j = clamp(q_seed_j, lo_j, hi_j) for a = 0; theta_j = lo_j + u(a, j) (hi_j - lo_j) for a >= 1.
+ *     For k = 0 .. max_iters:
+ *       T_c and the space Jacobian J_s at theta (the FK and Jacobian of mp_fk_jac_id_*); e = [angular error in space axes;
+ *         p_goal - p_c], rot = the rotation angle and tr = |p_goal - p_c|, exactly as mp_inverse_kinematics_* measures them.
+ *       rot < eomg and tr < ev: the attempt has converged; leave the loop.
+ *       k == max_iters: the attempt has failed; leave the loop.
+ *       Otherwise one damped Newton step on the HYBRID Jacobian J_h, the proper pair of e: rows 0..2 are those of J_s, column i of
+ *         rows 3..5 is v_i + w_i x p_c (p_c the translation of T_c).  A = J_h J_h^T + damping^2 1 (each entry summed over the joints
+ *         ascending, the diagonal starting from damping^2), y = A^-1 e by Cholesky, d = J_h^T y; if |d| > step_cap then
+ *         d <- d (step_cap / |d|); theta_j <- clamp(theta_j + d_j, lo_j, hi_j); iterations += 1.
+ *     A converged attempt: converged += 1, and ONE evaluation of the zero edge theta -> theta by the edge check of the section
+ *       above with the launch's margin and tol (a zero edge is FREE or BLOCKED at its first evaluation).  FREE: FOUND, q = theta,
+ *       stop.  Otherwise, if its clearance is strictly larger than the best so far (or it is the first), theta becomes the best.
+ *   After the last attempt: a best exists: IN_COLLISION, q = best.  Otherwise UNREACHED.
+ * Per problem (every output may be NULL; at least one is needed; a bad row leaves the others untouched):
+ *     status (B) int32                   MP_GOAL_FOUND 0, _IN_COLLISION 1, _UNREACHED 2, _INVALID -1
+ *     q (B, n)                           the configuration; NaN for UNREACHED and INVALID
+ *     attempts (B) int32                 attempts started (0 for INVALID)
+ *     iterations (B) int32               steps taken, all attempts together
+ *     converged (B) int32                attempts that reached the pose
+ *     pose_error (B, 2)                  rot, tr at q; NaN without one
+ *     clearance (B), witness (B, 3)      at q, as the zero edge reports them; NaN and -1 without one
+ *   q goes straight into mp_rrt_connect_* as q_goal: under the same margin and tol a FOUND row is never GOAL_BLOCKED there (it is
+ *   the same decision on the same configuration), an IN_COLLISION row is GOAL_BLOCKED, UNREACHED and INVALID rows are MP_PLAN_INVALID.
+ * mp_goal_ik_f64: d_T_goal (B,16), d_q_seed (B,n) device rows, 16-byte aligned like every output.  One launch: a lane serves one
+ *   problem at a time and takes problems from a queue; a trip of the wave is one pose evaluation with its step and, only when a lane
+ *   has just converged, one collision evaluation.  No workspace: a problem's state lives in registers.  The grid is the smallest of
+ *   the one-wave blocks the device keeps resident, ceil(B / 64) and max_blocks (if positive).  Asynchronous; it allocates nothing once
+ *   the handle is resident on the context and may then be captured into a launch graph (the queue head's reset is part of it).
+ *   Launches that share a collision handle share its queue head: they are serialised by the handle's lock and the compute stream.
+ *   mp_goal_ik_host_f64: host arrays, device memory from the context's pool.  mp_goal_ik_cpu_f64: the kernel's per-problem code on
+ *   the host, no context. */
+#define MP_GOAL_FOUND 0
+#define MP_GOAL_IN_COLLISION 1
+#define MP_GOAL_UNREACHED 2
+#define MP_GOAL_INVALID (-1)
+int mp_goal_ik_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_T_goal, const double* d_q_seed, int64_t B,
+                   const double* lo, const double* hi, uint32_t seed, double eomg, double ev, double damping, double step_cap,
+                   int max_iters, int max_attempts, double margin, double tol, int max_blocks, int32_t* d_status, double* d_q,
+                   int32_t* d_attempts, int32_t* d_iterations, int32_t* d_converged, double* d_pose_error, double* d_clearance,
+                   int32_t* d_witness);
+int mp_goal_ik_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* T_goal, const double* q_seed, int64_t B,
+                        const double* lo, const double* hi, uint32_t seed, double eomg, double ev, double damping, double step_cap,
+                        int max_iters, int max_attempts, double margin, double tol, int32_t* status, double* q, int32_t* attempts,
+                        int32_t* iterations, int32_t* converged, double* pose_error, double* clearance, int32_t* witness);
+int mp_goal_ik_cpu_f64(const mp_model* model, const mp_collision* h, const double* T_goal, const double* q_seed, int64_t B,
+                       const double* lo, const double* hi, uint32_t seed, double eomg, double ev, double damping, double step_cap,
+                       int max_iters, int max_attempts, double margin, double tol, int32_t* status, double* q, int32_t* attempts,
+                       int32_t* iterations, int32_t* converged, double* pose_error, double* clearance, int32_t* witness, int nthreads);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new; the reference is single-device) ------
  * Trajectory batches are sharded over ranks with no exchange during compute; the only collective is
  * the all-gather that reassembles the torque history.  Rank 0 creates the id, the launcher

@@ -191,6 +191,9 @@ SIGNATURES = {
     "mp_path_shortcut_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_path_shortcut_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _vp, _i64, _i64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _c_dp, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
     "mp_path_shortcut_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _vp, _i64, _i64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _c_dp, _c_dp, _c_dp, _vp, _vp, _vp, _vp, ctypes.c_int]),
+    "mp_goal_ik_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "mp_goal_ik_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _c_dp, _vp, _vp, _vp, _c_dp, _c_dp, _vp]),
+    "mp_goal_ik_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _c_dp, _vp, _vp, _vp, _c_dp, _c_dp, _vp, ctypes.c_int]),
     "mp_comm_unique_id": (ctypes.c_int, [ctypes.POINTER(ctypes.c_uint8)]),
     "mp_comm_create": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, ctypes.c_int, ctypes.POINTER(_vp)]),
     "mp_comm_destroy": (ctypes.c_int, [_vp]),
@@ -762,6 +765,29 @@ class HipContext:
         with its device form is held by tests/test_gpu_shortcut.py.)"""
         return _path_shortcut((self.handle,), self.lib.mp_path_shortcut_host_f64, model, collision, waypoints, count, margin, tol,
                               max_iters, min_gain, max_waypoints, max_steps, seed, want)
+
+    def goal_ik(self, model, collision, d_T_goal, d_q_seed, problems, lo, hi, margin, tol, *, eomg, ev, damping, step_cap, max_iters,
+                max_attempts, seed, max_blocks: int = 0, d_status=None, d_q=None, d_attempts=None, d_iterations=None, d_converged=None,
+                d_pose_error=None, d_clearance=None, d_witness=None):
+        """Collision-free goal configurations for pose goals on device buffers (float64; csrc/mp_goal.h): d_T_goal (problems,16),
+        d_q_seed (problems,n); lo, hi (n) host arrays; outputs status / attempts / iterations / converged (problems) int32, q
+        (problems,n), pose_error (problems,2), clearance (problems), witness (problems,3) int32, each may be None (at least one
+        given).  No workspace.  `max_blocks` > 0 caps the grid.  Asynchronous (capturable once the handle has been used or given a
+        world on this context)."""
+        lo, hi = _as_c(lo, np.float64, (model.n,), "lo"), _as_c(hi, np.float64, (model.n,), "hi")
+        _check(self.lib.mp_goal_ik_f64(self.handle, model.handle, collision.handle, _p(d_T_goal), _p(d_q_seed), int(problems), _dptr(lo),
+                                       _dptr(hi), int(seed), float(eomg), float(ev), float(damping), float(step_cap), int(max_iters),
+                                       int(max_attempts), float(margin), float(tol), int(max_blocks), _p(d_status), _p(d_q),
+                                       _p(d_attempts), _p(d_iterations), _p(d_converged), _p(d_pose_error), _p(d_clearance),
+                                       _p(d_witness)))
+
+    def goal_ik_arrays(self, model, collision, T_goal, q_seed, lo, hi, margin, tol, *, eomg, ev, damping, step_cap, max_iters,
+                       max_attempts, seed, want=None):
+        """The same on host arrays (mp_goal_ik_host_f64) through the context's pool: a dict of the outputs named in `want` (default:
+        all of GOAL_OUTPUTS).  (Not named `*_host`, as rrt_connect_arrays is not; this entry's equality with its device form is held
+        by tests/test_gpu_goal.py.)"""
+        return _goal_ik((self.handle,), self.lib.mp_goal_ik_host_f64, model, collision, T_goal, q_seed, lo, hi, margin, tol, eomg, ev,
+                        damping, step_cap, max_iters, max_attempts, seed, want)
 
     def collision_set_world(self, collision, kinds, params):
         """Replaces the obstacle table of `collision` on this context's device, behind the launches already on its stream."""
@@ -1632,6 +1658,48 @@ def cpu_path_shortcut(model: "HipModel", collision: "HipCollision", waypoints, c
     """CPU twin of HipContext.path_shortcut_arrays."""
     return _path_shortcut((), load_library().mp_path_shortcut_cpu_f64, model, collision, waypoints, count, margin, tol, max_iters,
                           min_gain, max_waypoints, max_steps, seed, want, nthreads)
+
+
+GOAL_OUTPUTS = ("status", "q", "attempts", "iterations", "converged", "pose_error", "clearance", "witness")
+GOAL_FOUND, GOAL_IN_COLLISION, GOAL_UNREACHED, GOAL_INVALID = 0, 1, 2, -1
+
+
+def _goal_ik(lead, fn, model, collision, T_goal, q_seed, lo, hi, margin, tol, eomg, ev, damping, step_cap, max_iters, max_attempts, seed,
+             want, nthreads=None):
+    want = GOAL_OUTPUTS if want is None else tuple(want)
+    for w in want:
+        if w not in GOAL_OUTPUTS:
+            raise ValueError(f"unknown goal output {w!r}; choose from {GOAL_OUTPUTS}")
+    q0 = _as_c(q_seed, np.float64, name="q_seed")
+    if q0.ndim != 2 or q0.shape[1] != model.n:
+        raise ValueError(f"q_seed must be (problems, {model.n}); got {q0.shape}")
+    B, n = q0.shape
+    Tg = np.asarray(T_goal, dtype=np.float64)
+    if Tg.shape != (B, 4, 4) and Tg.shape != (B, 16):
+        raise ValueError(f"T_goal must be ({B}, 4, 4) or ({B}, 16); got {Tg.shape}")
+    Tg = _as_c(Tg.reshape(B, 16), np.float64, (B, 16), "T_goal")
+    lo, hi = _as_c(lo, np.float64, (n,), "lo"), _as_c(hi, np.float64, (n,), "hi")
+    shapes = {"status": (B,), "q": (B, n), "attempts": (B,), "iterations": (B,), "converged": (B,), "pose_error": (B, 2),
+              "clearance": (B,), "witness": (B, 3)}
+    real = ("q", "pose_error", "clearance")
+    out = {w: np.empty(shapes[w], dtype=np.float64 if w in real else np.int32) for w in want}
+    ptrs = []
+    for w in GOAL_OUTPUTS:
+        a = out.get(w)
+        ptrs.append(None if a is None else (_dptr(a) if w in real else a.ctypes.data_as(_vp)))
+    args = list(lead) + [model.handle, collision.handle, _dptr(Tg), _dptr(q0), B, _dptr(lo), _dptr(hi), int(seed), float(eomg), float(ev),
+                         float(damping), float(step_cap), int(max_iters), int(max_attempts), float(margin), float(tol)] + ptrs
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return out
+
+
+def cpu_goal_ik(model: "HipModel", collision: "HipCollision", T_goal, q_seed, lo, hi, margin, tol, *, eomg, ev, damping, step_cap,
+                max_iters, max_attempts, seed, want=None, nthreads: int = 0) -> dict:
+    """CPU twin of HipContext.goal_ik_arrays."""
+    return _goal_ik((), load_library().mp_goal_ik_cpu_f64, model, collision, T_goal, q_seed, lo, hi, margin, tol, eomg, ev, damping,
+                    step_cap, max_iters, max_attempts, seed, want, nthreads)
 
 
 def _pd_regulation_args(model, theta0, theta_des, Kp, Kd, g, steps):

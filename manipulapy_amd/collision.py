@@ -14,7 +14,7 @@ import numpy as np
 from . import _hip
 from .registry import execute_registered_kernel
 
-__all__ = ["SphereCollisionModel", "COLLISION_OP", "EDGES_OP", "PLAN_OP", "SHORTCUT_OP"]
+__all__ = ["SphereCollisionModel", "COLLISION_OP", "EDGES_OP", "PLAN_OP", "SHORTCUT_OP", "GOAL_OP"]
 
 # The registry's sorted name list starts with "control.pd_regulation" (the unknown-name message is pinned by a test), so the operation
 # lives in the "planning" family rather than in one of its own that would sort ahead of it.
@@ -22,6 +22,7 @@ COLLISION_OP = "planning.collision_spheres"
 EDGES_OP = "planning.collision_edges"
 PLAN_OP = "planning.rrt_connect"
 SHORTCUT_OP = "planning.shortcut_paths"
+GOAL_OP = "planning.goal_configurations"
 
 
 def _hip_model_of(obj) -> _hip.HipModel:
@@ -230,4 +231,27 @@ class SphereCollisionModel:
         out = execute_registered_kernel(SHORTCUT_OP, self, np.ascontiguousarray(wp.reshape((-1,) + wp.shape[-2:])),
                                         cnt.reshape(-1), margin, tol, max_iters=max_iters,
                                         min_gain=min_gain, max_waypoints=max_waypoints, max_steps=max_steps, seed=seed, want=want)
+        return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}
+
+    # ------------------------------------------------------------------ pose goals
+    def goal_configurations(self, T_goal, q_seed, lo, hi, margin: float = 0.0, tol: float = 1e-3, *, eomg: float, ev: float,
+                            damping: float, step_cap: float, max_iters: int, max_attempts: int, seed: int = 0, want=None) -> dict:
+        """Collision-free joint configurations for B end-effector poses T_goal ((B, 4, 4) with seeds q_seed (B, n), or any common
+        leading shape) inside the box lo, hi (n): {"status" (0 found, 1 in collision, 2 unreached, -1 invalid), "q" (.., n),
+        "attempts", "iterations", "converged", "pose_error" (.., 2: rotation angle, distance), "clearance", "witness" (.., 3)} or the
+        subset named in `want`.  Up to `max_attempts` damped Newton attempts of at most `max_iters` steps each on the hybrid Jacobian
+        (damping `damping`, steps capped at `step_cap`, clamped into the box), the first from the clamped seed and the later ones
+        from random points of the box; an attempt converges when the rotation error is below `eomg` and the position error below
+        `ev`.  Every converged attempt gets the zero-edge decision of `check_edges(q, q)` with this margin and tol - the decision
+        `plan_paths` makes for its q_goal: the first FREE one is returned as found; if none is free, the converged configuration of
+        the largest clearance comes back as in collision; if none converged, NaN as unreached.  "q" goes straight into `plan_paths`
+        as q_goal: a found row is never goal-blocked there under the same margin and tol.  A problem's result depends on its content
+        and `seed` only."""
+        Tg, q0 = np.asarray(T_goal, dtype=np.float64), np.asarray(q_seed, dtype=np.float64)
+        if Tg.ndim < 2 or Tg.shape[-2:] != (4, 4) or q0.ndim < 1 or q0.shape[-1] != self.n or Tg.shape[:-2] != q0.shape[:-1]:
+            raise ValueError(f"T_goal must be (..., 4, 4) and q_seed (..., {self.n}) with one leading shape; got {Tg.shape} and {q0.shape}")
+        lead = q0.shape[:-1]
+        out = execute_registered_kernel(GOAL_OP, self, np.ascontiguousarray(Tg.reshape(-1, 16)), np.ascontiguousarray(q0.reshape(-1, self.n)),
+                                        lo, hi, margin, tol, eomg=eomg, ev=ev, damping=damping, step_cap=step_cap, max_iters=max_iters,
+                                        max_attempts=max_attempts, seed=seed, want=want)
         return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}

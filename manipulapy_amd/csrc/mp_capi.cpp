@@ -3366,6 +3366,72 @@ int mp_path_shortcut_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* 
   });
 }
 
+}  // extern "C"
+
+// ---- goal configurations for pose goals over the sphere model (mp_goal.h): no workspace, so one plan per call, made here
+static int goal_ik_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_Tg, const double* d_q0,
+                        int64_t B, const MpGoalParams& P, int max_blocks, int32_t* d_status, double* d_q, int32_t* d_attempts,
+                        int32_t* d_iters, int32_t* d_conv, double* d_pose, double* d_clear, int32_t* d_witness) {
+  REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  REQUIRE(d_Tg && d_q0, "%s: null device pointer", fn);
+  REQUIRE(d_status || d_q || d_attempts || d_iters || d_conv || d_pose || d_clear || d_witness, "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_Tg) && aligned16(d_q0) && aligned16(d_status) && aligned16(d_q) && aligned16(d_attempts) && aligned16(d_iters) &&
+              aligned16(d_conv) && aligned16(d_pose) && aligned16(d_clear) && aligned16(d_witness),
+          "%s: device pointers must be 16-byte aligned", fn);
+  std::lock_guard<std::mutex> hl(h->mu);
+  mp_collision::Resident* R = nullptr;
+  if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
+  PROFILE_SCOPE(ctx, fn);
+  MpQueuePlan plan;
+  HIP_TRY(mpk_queue_plan(MP_QUEUE_GOAL, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_goal_ik(ctx->compute, model->d, collision_device(h, R), d_Tg, d_q0, (long)B, P, d_status, d_q, d_attempts, d_iters, d_conv,
+                      d_pose, d_clear, d_witness, queue_grid(plan, B, max_blocks), plan.lds));
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_goal_ik_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_T_goal, const double* d_q_seed, int64_t B,
+                   const double* lo, const double* hi, uint32_t seed, double eomg, double ev, double damping, double step_cap,
+                   int max_iters, int max_attempts, double margin, double tol, int max_blocks, int32_t* d_status, double* d_q,
+                   int32_t* d_attempts, int32_t* d_iterations, int32_t* d_converged, double* d_pose_error, double* d_clearance,
+                   int32_t* d_witness) {
+  const char* fn = "mp_goal_ik_f64";
+  CHECK_SPHERE_ENTRY(fn);
+  MpGoalParams P;
+  if (int rc = mp_goal_ik_check(fn, model->d.n, lo, hi, seed, eomg, ev, damping, step_cap, max_iters, max_attempts, margin, tol, &P))
+    return rc;
+  return goal_ik_impl(fn, ctx, model, h, d_T_goal, d_q_seed, B, P, max_blocks, d_status, d_q, d_attempts, d_iterations, d_converged,
+                      d_pose_error, d_clearance, d_witness);
+}
+
+int mp_goal_ik_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* T_goal, const double* q_seed, int64_t B,
+                        const double* lo, const double* hi, uint32_t seed, double eomg, double ev, double damping, double step_cap,
+                        int max_iters, int max_attempts, double margin, double tol, int32_t* status, double* q, int32_t* attempts,
+                        int32_t* iterations, int32_t* converged, double* pose_error, double* clearance, int32_t* witness) {
+  const char* fn = "mp_goal_ik_host_f64";
+  CHECK_SPHERE_ENTRY(fn);
+  MpGoalParams P;
+  if (int rc = mp_goal_ik_check(fn, model->d.n, lo, hi, seed, eomg, ev, damping, step_cap, max_iters, max_attempts, margin, tol, &P))
+    return rc;
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  REQUIRE(T_goal && q_seed, "%s: null host pointer", fn);
+  const size_t n = (size_t)model->d.n, ib = (size_t)B * sizeof(int32_t), db = (size_t)B * sizeof(double);
+  HostCall hc(ctx);  // (h is the collision handle)
+  const double *dtg = hc.in(T_goal, 16 * db), *dq0 = hc.in(q_seed, n * db);
+  int32_t* dstatus = hc.out(status, ib);
+  double* dq = hc.out(q, n * db);
+  int32_t *datt = hc.out(attempts, ib), *dit = hc.out(iterations, ib), *dconv = hc.out(converged, ib);
+  double *dpose = hc.out(pose_error, 2 * db), *dclear = hc.out(clearance, db);
+  int32_t* dwit = hc.out(witness, 3 * ib);
+  return hc.run([&] {
+    return goal_ik_impl(fn, ctx, model, h, dtg, dq0, B, P, 0, dstatus, dq, datt, dit, dconv, dpose, dclear, dwit);
+  });
+}
+
 int mp_collision_set_world(mp_ctx* ctx, mp_collision* h, int O, const int32_t* kind, const double* params) {
   const char* fn = "mp_collision_set_world";
   REQUIRE(h, "%s: null collision handle", fn);

@@ -1415,3 +1415,58 @@ int mp_path_shortcut_cpu_f64(const mp_model* model, const mp_collision* h, const
 }
 
 }  // extern "C"
+
+// ---- goal configurations for pose goals over the sphere model (mp_goal.h)
+int mp_goal_ik_check(const char* fn, int n, const double* lo, const double* hi, uint32_t seed, double eomg, double ev, double damping,
+                     double step_cap, int max_iters, int max_attempts, double margin, double tol, MpGoalParams* out) {
+  if (int rc = mp_collision_edges_check(fn, margin, tol, 1)) return rc;
+  if (!lo || !hi) return col_fail("%s: null joint box", fn);
+  MpGoalParams P;
+  std::memset(&P, 0, sizeof P);
+  for (int j = 0; j < n; ++j) {
+    if (!std::isfinite(lo[j]) || !std::isfinite(hi[j]) || !(lo[j] <= hi[j]))
+      return col_fail("%s: joint %ld: the box must be finite with lo <= hi", fn, j);
+    P.lo[j] = lo[j];
+    P.hi[j] = hi[j];
+  }
+  if (!(eomg > 0.0) || !std::isfinite(eomg) || !(ev > 0.0) || !std::isfinite(ev)) return col_fail("%s: eomg and ev must be positive and finite", fn);
+  if (!(damping > 0.0) || !std::isfinite(damping)) return col_fail("%s: damping must be positive and finite", fn);
+  if (!(step_cap > 0.0) || !std::isfinite(step_cap)) return col_fail("%s: step_cap must be positive and finite", fn);
+  if (max_iters < 0) return col_fail("%s: negative max_iters", fn);
+  if (max_attempts < 1 || max_attempts > MP_GOAL_MAX_ATTEMPTS) return col_fail("%s: max_attempts %ld outside 1..65536", fn, max_attempts);
+  P.eomg = eomg; P.ev = ev; P.damping = damping; P.step_cap = step_cap;
+  P.edge = {margin, tol, 1, 0};
+  P.seed = seed; P.max_iters = max_iters; P.max_attempts = max_attempts;
+  *out = P;
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_goal_ik_cpu_f64(const mp_model* model, const mp_collision* h, const double* T_goal, const double* q_seed, int64_t B,
+                       const double* lo, const double* hi, uint32_t seed, double eomg, double ev, double damping, double step_cap,
+                       int max_iters, int max_attempts, double margin, double tol, int32_t* status, double* q, int32_t* attempts,
+                       int32_t* iterations, int32_t* converged, double* pose_error, double* clearance, int32_t* witness, int nthreads) {
+  const char* fn = "mp_goal_ik_cpu_f64";
+  if (int rc = col_twin_enter(fn, model, h)) return rc;
+  MpGoalParams P;
+  if (int rc = mp_goal_ik_check(fn, model->d.n, lo, hi, seed, eomg, ev, damping, step_cap, max_iters, max_attempts, margin, tol, &P))
+    return rc;
+  if (B < 0) return col_fail("%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  if (!T_goal || !q_seed) return col_fail("%s: null pointer", fn);
+  if (!status && !q && !attempts && !iterations && !converged && !pose_error && !clearance && !witness)
+    return col_fail("%s: at least one output is required", fn);
+  const MpModel<double>& M = model->d;
+  MpColWorld hdr;
+  const MpColTablesHost tb = col_host_tables(h, hdr);
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
+      for (int64_t b = b0; b < b1; ++b)
+        mp_goal_cpu<N>(M, tb, P, T_goal, q_seed, (long)b, status, q, attempts, iterations, converged, pose_error, clearance, witness);
+    });
+  })
+  return MP_OK;
+}
+
+}  // extern "C"

@@ -8,6 +8,7 @@
 #include "mp_collision.h"
 #include "mp_rrt.h"
 #include "mp_shortcut.h"
+#include "mp_goal.h"
 #include "mp_model.h"
 
 struct mp_model {
@@ -49,5 +50,9 @@ int mp_rrt_connect_check(const char* fn, int n, const double* lo, const double* 
 // the shortcutter's parameters (the edge check's among them), packed into `out`; 0, or MP_ERR_INVALID with the message set (mp_cpu.cpp)
 int mp_path_shortcut_check(const char* fn, int64_t w_in, uint32_t seed, int max_iters, double min_gain, int max_waypoints, double margin,
                            double tol, int max_steps, MpShortcutParams* out);
+// the goal-configuration parameters (margin and tol of the edge check among them), packed into `out`; 0, or MP_ERR_INVALID with the
+// message set (mp_cpu.cpp)
+int mp_goal_ik_check(const char* fn, int n, const double* lo, const double* hi, uint32_t seed, double eomg, double ev, double damping,
+                     double step_cap, int max_iters, int max_attempts, double margin, double tol, MpGoalParams* out);
 
 int mp_set_error(int code, const char* msg);  // thread-local message of mp_last_error (mp_capi.cpp; C++ linkage)

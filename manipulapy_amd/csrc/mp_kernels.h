@@ -190,12 +190,13 @@ hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, const MpColDev
                          double eps_self, double* dist_world, int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world,
                          double* grad_dist_self, double* cost, double* grad);
 // The one-wave work-queue kernels on the sphere model: continuous collision checking of joint-space edges (csrc/mp_collision.h),
-// batched RRT-Connect (csrc/mp_rrt.h, the trees in `workspace`: blocks x 64 x 2 max_nodes (8 n + 4) bytes) and batched path
-// shortcutting (csrc/mp_shortcut.h, the working paths in `workspace`: blocks x 64 x max_waypoints (8 n + 8) bytes).  A work queue
+// batched RRT-Connect (csrc/mp_rrt.h, the trees in `workspace`: blocks x 64 x 2 max_nodes (8 n + 4) bytes), batched path
+// shortcutting (csrc/mp_shortcut.h, the working paths in `workspace`: blocks x 64 x max_waypoints (8 n + 8) bytes) and goal
+// configurations for pose goals (csrc/mp_goal.h, no workspace: one pose or collision evaluation a trip).  A work queue
 // over the edges / problems, one evaluated configuration a trip.  mpk_queue_plan gives a kernel's dynamic LDS and the blocks of it the
 // device keeps resident (occupancy x compute_units); the caller settles the grid (`blocks`) from that, the count, its cap and the
 // workspace, and hands grid and LDS to the launch, which zeroes D.counter on the stream first and makes no runtime query.
-enum MpQueueKernel { MP_QUEUE_EDGES, MP_QUEUE_RRT, MP_QUEUE_SHORTCUT };
+enum MpQueueKernel { MP_QUEUE_EDGES, MP_QUEUE_RRT, MP_QUEUE_SHORTCUT, MP_QUEUE_GOAL };
 struct MpQueuePlan {
   unsigned lds;
   long resident;
@@ -214,3 +215,7 @@ hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, const MpCo
                              long problems, const MpShortcutParams& P, int* status, int* count, double* waypoints, double* length_in,
                              double* length_out, int* iterations, int* accepted, int* skipped_full, int* evaluations, double* workspace,
                              long blocks, unsigned lds);
+struct MpGoalParams;
+hipError_t mpk_goal_ik(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* T_goal, const double* q_seed,
+                       long problems, const MpGoalParams& P, int* status, double* q, int* attempts, int* iterations, int* converged,
+                       double* pose_error, double* clearance, int* witness, long blocks, unsigned lds);

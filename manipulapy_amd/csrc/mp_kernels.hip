@@ -25,6 +25,7 @@
 #include "mp_collision.h"
 #include "mp_rrt.h"
 #include "mp_shortcut.h"
+#include "mp_goal.h"
 
 namespace {
 
@@ -430,7 +431,7 @@ typedef MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpCol
 __device__ __forceinline__ MpColTablesConst mp_col_tables_const(const MpColSpheres* sph, const MpColPair* pairs, const MpColWorld* world) {
   return {(MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
 }
-// The scaffold of the one-wave work-queue kernels on the sphere model (k_collision_edges, k_rrt_connect, k_path_shortcut; DESIGN
+// The scaffold of the one-wave work-queue kernels on the sphere model (k_collision_edges, k_rrt_connect, k_path_shortcut, k_goal_ik; DESIGN
 // §4.10).  Their dynamic LDS, sized by mp_col_queue_lds_bytes (mp_collision.h): the park of S centres, then the edge's n (n + 1) / 2
 // speed bounds [entry][lane] - per lane, but read at wave-uniform link numbers.  Each lane reads and writes only its own column of
 // both, so no barrier is needed.
@@ -684,6 +685,57 @@ __global__ __launch_bounds__(64) void k_path_shortcut(const MpModel<double> M, c
       have = false;
       S.phase = MP_SC_IDLE;
       S.m = 0;
+    }
+  }
+}
+
+// ------------------------------------------------------- goal configurations for pose goals over the sphere model (float64, mp_goal.h)
+// One wave per block and the work queue of k_collision_edges / k_rrt_connect: a lane without a problem takes the next index from the
+// device counter, every trip of the loop does at most one pose evaluation with its step for a lane that is iterating and - only if
+// some lane of the wave has just converged - the one collision evaluation of such a lane, and a finished lane writes its row and
+// fetches another.  Dynamic LDS: the park and the speed bounds (mp_col_queue_lanes), which only the collision evaluation touches.
+// All of a problem's state is in registers: no workspace.  The loop of the kernel ends for the whole wave at once, when no lane holds
+// a problem and the queue is empty; it ends because the counter only grows and every problem ends within
+// max_attempts (max_iters + 2) trips.
+template <int N>
+__global__ __launch_bounds__(64) void k_goal_ik(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
+                                                const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
+                                                const double* __restrict__ T_goal, const double* __restrict__ q_seed, long problems,
+                                                const MpGoalParams P, int* __restrict__ status, double* __restrict__ q,
+                                                int* __restrict__ attempts, int* __restrict__ iterations, int* __restrict__ converged,
+                                                double* __restrict__ pose_error, double* __restrict__ clearance,
+                                                int* __restrict__ witness, unsigned long long* __restrict__ next) {
+  extern __shared__ __attribute__((aligned(16))) double mp_goal_lds[];
+  const int lane = (int)threadIdx.x;
+  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  MpColQueueLanes Q = mp_col_queue_lanes(mp_goal_lds, lane, tb.sph->S);
+  const MpWaveOpsLanes W{};
+  MpGoalState<N> S;
+  S.phase = MP_GOAL_IDLE;
+  bool have = false, dry = false;
+  long row = 0;
+  for (;;) {
+    if (!have && !dry) {
+      row = (long)atomicAdd(next, 1ull);
+      if (row >= problems) {
+        dry = true;
+      } else {
+        mp_goal_begin<N>(P, T_goal + 16 * row, q_seed + row * N, S);
+        have = true;
+      }
+    }
+    if (!W.wave_any(have)) break;
+    if (mp_goal_trip<N>(M, tb, P, S, W, Q.park, Q.L, T_goal + 16 * (have ? row : 0))) {
+      if (status != nullptr) status[row] = S.status;
+      if (q != nullptr) RunIO<double, N>::store(q, row, S.best);
+      if (attempts != nullptr) attempts[row] = S.attempt + 1;
+      if (iterations != nullptr) iterations[row] = S.iterations;
+      if (converged != nullptr) converged[row] = S.converged;
+      if (pose_error != nullptr) { pose_error[2 * row] = S.rot; pose_error[2 * row + 1] = S.tr; }
+      if (clearance != nullptr) clearance[row] = S.clearance;
+      if (witness != nullptr) { witness[3 * row] = S.witness[0]; witness[3 * row + 1] = S.witness[1]; witness[3 * row + 2] = S.witness[2]; }
+      have = false;
+      S.phase = MP_GOAL_IDLE;
     }
   }
 }
@@ -1569,12 +1621,13 @@ hipError_t mpk_queue_plan(MpQueueKernel kernel, int n, int S, int compute_units,
       case MP_QUEUE_EDGES: return queue_plan(&k_collision_edges<N>, N, S, compute_units, plan);
       case MP_QUEUE_RRT: return queue_plan(&k_rrt_connect<N>, N, S, compute_units, plan);
       case MP_QUEUE_SHORTCUT: return queue_plan(&k_path_shortcut<N>, N, S, compute_units, plan);
+      case MP_QUEUE_GOAL: return queue_plan(&k_goal_ik<N>, N, S, compute_units, plan);
     }
   })
   return hipErrorInvalidValue;
 }
 
-// The three queue launches: `blocks` is the grid the caller has settled on (the plan's resident blocks, the count, its cap and the
+// The four queue launches: `blocks` is the grid the caller has settled on (the plan's resident blocks, the count, its cap and the
 // workspace), `lds` the plan's dynamic LDS.  They zero the queue counter on the stream and launch; no runtime query.
 static hipError_t queue_reset(hipStream_t s, const MpColDevice& D, long blocks) {
   if (D.S < 1 || D.S > MP_COL_MAX_SPHERES || blocks < 1) return hipErrorInvalidValue;
@@ -1618,6 +1671,19 @@ hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, const MpCo
     hipLaunchKernelGGL((k_path_shortcut<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
                        problems, P, status, count, waypoints, length_in, length_out, iterations, accepted, skipped_full, evaluations,
                        workspace, D.counter);
+  })
+  return hipGetLastError();
+}
+
+hipError_t mpk_goal_ik(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* T_goal, const double* q_seed,
+                       long problems, const MpGoalParams& P, int* status, double* q, int* attempts, int* iterations, int* converged,
+                       double* pose_error, double* clearance, int* witness, long blocks, unsigned lds) {
+  if (problems <= 0) return hipSuccess;
+  const hipError_t e = queue_reset(s, D, blocks);
+  if (e != hipSuccess) return e;
+  MP_DISPATCH_N(M.n, {
+    hipLaunchKernelGGL((k_goal_ik<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, T_goal, q_seed, problems, P,
+                       status, q, attempts, iterations, converged, pose_error, clearance, witness, D.counter);
   })
   return hipGetLastError();
 }

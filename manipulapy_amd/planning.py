@@ -587,8 +587,7 @@ class OptimizedTrajectoryPlanning:
         n = collision_model.n
         if sb.ndim != 2 or sb.shape != gb.shape or sb.shape[1] != n:
             raise ValueError(f"start and goal must both be (B, {n}); got {sb.shape} and {gb.shape}")
-        lim = np.nan_to_num(np.asarray(self.joint_limits, dtype=np.float64), nan=0.0, posinf=finite_limit, neginf=-finite_limit)
-        lo, hi = np.clip(lim[:, 0], -finite_limit, finite_limit), np.clip(lim[:, 1], -finite_limit, finite_limit)
+        lo, hi = self._planning_box(finite_limit)
         return self._dispatch("planning.rrt_connect", collision_model, np.ascontiguousarray(sb), np.ascontiguousarray(gb), lo, hi, margin,
                               tol, step=step, min_advance=min_advance, max_iters=max_iters, max_nodes=max_nodes,
                               max_waypoints=max_waypoints, max_steps=max_steps, seed=seed)
@@ -608,6 +607,47 @@ class OptimizedTrajectoryPlanning:
         return self._dispatch("planning.shortcut_paths", collision_model, np.ascontiguousarray(wp),
                               cnt, margin, tol, max_iters=max_iters, min_gain=min_gain,
                               max_waypoints=max_waypoints, max_steps=max_steps, seed=seed)
+
+    def _planning_box(self, finite_limit: float):
+        """This planner's joint limits as a finite box: an open or non-finite limit clipped to +-`finite_limit` (batch_plan_path's rule)."""
+        lim = np.nan_to_num(np.asarray(self.joint_limits, dtype=np.float64), nan=0.0, posinf=finite_limit, neginf=-finite_limit)
+        return np.clip(lim[:, 0], -finite_limit, finite_limit), np.clip(lim[:, 1], -finite_limit, finite_limit)
+
+    def batch_goal_configurations(self, T_goal, q_seed, collision_model, margin: float = 0.0, tol: float = 1e-3, *, eomg: float = 1e-6,
+                                  ev: float = 1e-6, damping: float = 0.02, step_cap: float = 0.5, max_iters: int = 50,
+                                  max_attempts: int = 8, seed: int = 0, finite_limit: float = 2 * np.pi) -> Dict[str, np.ndarray]:
+        """Collision-free joint configurations for B end-effector poses T_goal (B, 4, 4), seeded by q_seed (B, n), under a
+        collision.SphereCollisionModel (SphereCollisionModel.goal_configurations), all B problems in one launch.  The box is this
+        planner's joint limits, clipped as `batch_plan_path` clips its sampling box.  {"status" (0 found, 1 in collision, 2
+        unreached, -1 invalid), "q" (B, n), "attempts", "iterations", "converged", "pose_error" (B, 2), "clearance", "witness"
+        (B, 3)}: "q" can go straight into `batch_plan_path` as the goal."""
+        Tg, q0 = np.asarray(T_goal, dtype=np.float64), np.asarray(q_seed, dtype=np.float64)
+        n = collision_model.n
+        if q0.ndim != 2 or q0.shape[1] != n or Tg.shape != (q0.shape[0], 4, 4):
+            raise ValueError(f"T_goal must be (B, 4, 4) and q_seed (B, {n}); got {Tg.shape} and {q0.shape}")
+        lo, hi = self._planning_box(finite_limit)
+        return self._dispatch("planning.goal_configurations", collision_model, np.ascontiguousarray(Tg.reshape(-1, 16)),
+                              np.ascontiguousarray(q0), lo, hi, margin, tol, eomg=eomg, ev=ev, damping=damping, step_cap=step_cap,
+                              max_iters=max_iters, max_attempts=max_attempts, seed=seed)
+
+    def batch_plan_path_to_pose(self, start, T_goal, collision_model, margin: float = 0.0, tol: float = 1e-3, *, eomg: float = 1e-6,
+                                ev: float = 1e-6, damping: float = 0.02, step_cap: float = 0.5, goal_max_iters: int = 50,
+                                max_attempts: int = 8, step: float = 1.0, min_advance=None, max_iters: int = 200, max_nodes: int = 256,
+                                max_waypoints: int = 64, max_steps: int = 64, seed: int = 0,
+                                finite_limit: float = 2 * np.pi) -> Dict[str, np.ndarray]:
+        """Collision-free paths from B start configurations (B, n) to B end-effector poses T_goal (B, 4, 4): `batch_goal_configurations`
+        seeded by `start`, then `batch_plan_path` to its "q", both with this margin, tol, seed and `finite_limit`.  Returns
+        `batch_plan_path`'s dict and "goal_status", "q_goal", "goal_attempts".  No masking between the two: under one margin and tol
+        a found goal is never goal-blocked, a goal in collision comes back goal-blocked, and an unreached or invalid one (NaN) comes
+        back invalid."""
+        goal = self.batch_goal_configurations(T_goal, start, collision_model, margin, tol, eomg=eomg, ev=ev, damping=damping,
+                                              step_cap=step_cap, max_iters=goal_max_iters, max_attempts=max_attempts, seed=seed,
+                                              finite_limit=finite_limit)
+        out = dict(self.batch_plan_path(start, goal["q"], collision_model, margin, tol, step=step, min_advance=min_advance,
+                                        max_iters=max_iters, max_nodes=max_nodes, max_waypoints=max_waypoints, max_steps=max_steps,
+                                        seed=seed, finite_limit=finite_limit))
+        out["goal_status"], out["q_goal"], out["goal_attempts"] = goal["status"], goal["q"], goal["attempts"]
+        return out
 
     # ------------------------------------------------------------------ legacy dynamics objects (Mlist_per_link=None)
     # The reference's approximation for such objects is not rigid-body dynamics (dynamics/mass_matrix.py:101-132), so there

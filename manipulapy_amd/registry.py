@@ -327,6 +327,10 @@ def _launch_path_shortcut_cpu(cm, waypoints, count, margin, tol, **kw):
     return _hip.cpu_path_shortcut(cm.model, cm.handle, waypoints, count, margin, tol, **kw)
 
 
+def _launch_goal_ik_cpu(cm, T_goal, q_seed, lo, hi, margin, tol, **kw):
+    return _hip.cpu_goal_ik(cm.model, cm.handle, T_goal, q_seed, lo, hi, margin, tol, **kw)
+
+
 def _launch_opspace_cpu(model, q, qd, g=None, frame="hybrid", task="full", damping=0.0, want=_hip.OPSPACE_OUTPUTS):
     return _hip.cpu_opspace(model, q, qd, g, frame, task, damping, want)
 
@@ -508,6 +512,12 @@ def _launch_path_shortcut_gpu(cm, waypoints, count, margin, tol, **kw):
     return ctx.path_shortcut_arrays(cm.model, cm.handle, waypoints, count, margin, tol, **kw)
 
 
+def _launch_goal_ik_gpu(cm, T_goal, q_seed, lo, hi, margin, tol, **kw):
+    ctx = get_context()
+    cm.sync_world(ctx)
+    return ctx.goal_ik_arrays(cm.model, cm.handle, T_goal, q_seed, lo, hi, margin, tol, **kw)
+
+
 def _launch_fk_jac_vjp_gpu(model, q, gT=None, gJ=None, frame="space", want_T=False, want_J=False, want_gq=True):
     return get_context().fk_jac_vjp_host(model, q, gT, gJ, frame, want_T, want_J, want_gq)
 
@@ -650,6 +660,9 @@ def _build_kernel_registry() -> KernelRegistry:
         # batched shortcutting of the planner's paths, every new segment proven by the edge check (csrc/mp_shortcut.h); the name sorts
         # after the pinned head of the name list
         ("planning.shortcut_paths", "mp_path_shortcut_host_f64", _launch_path_shortcut_gpu, _launch_path_shortcut_cpu),
+        # collision-free goal configurations for pose goals, each decided by the planner's own zero-edge check (csrc/mp_goal.h); the
+        # name sorts after the pinned head of the name list
+        ("planning.goal_configurations", "mp_goal_ik_host_f64", _launch_goal_ik_gpu, _launch_goal_ik_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):
