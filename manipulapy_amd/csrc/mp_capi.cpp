@@ -9,7 +9,6 @@
 #include <atomic>
 #include <set>
 #include <cmath>
-#include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -126,37 +125,18 @@ struct mp_graph {
 };
 
 namespace {
-thread_local char g_err[512] = "";
+thread_local char g_err[512] = "";  // what mp_set_error keeps for mp_last_error; every refusal goes through mp_fail (mp_handles.h)
 
-int set_err(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  std::vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
 int hip_err(hipError_t e, const char* what) {
-  return set_err(MP_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+  return mp_fail(MP_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
 }
 #define HIP_TRY(expr)                                   \
   do {                                                  \
     hipError_t e_ = (expr);                             \
     if (e_ != hipSuccess) return hip_err(e_, #expr);    \
   } while (0)
-#define REQUIRE(cond, ...)                                        \
-  do {                                                            \
-    if (!(cond)) return set_err(MP_ERR_INVALID, __VA_ARGS__);     \
-  } while (0)
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-const double kG[3] = {0.0, 0.0, -9.81};  // reference planning/trajectory_dynamics.py:54
-
-bool any_nonzero(const double* F) {
-  if (!F) return false;
-  for (int k = 0; k < 6; ++k)
-    if (F[k] != 0.0) return true;
-  return false;
-}
 int bind(mp_ctx* ctx) {
   HIP_TRY(hipSetDevice(ctx->device));
   return MP_OK;
@@ -241,10 +221,6 @@ struct KernelScope {
   }
 };
 #define PROFILE_SCOPE(ctx, name) KernelScope kernel_scope_((ctx), (name))
-
-template <typename T> const MpModel<T>& pick(const mp_model* m);
-template <> const MpModel<float>& pick<float>(const mp_model* m) { return m->f; }
-template <> const MpModel<double>& pick<double>(const mp_model* m) { return m->d; }
 
 template <typename T>
 void make_call(const mp_model* m, const double* g, const double* Ftip, MpCall<T>* c) {
@@ -563,9 +539,6 @@ template <> void make_call_ctx<double>(mp_ctx*, const mp_model* model, const dou
 }
 
 // MpBigModel<T> of a 9..32-joint model resident in device memory (read by the looped k_dyn_* kernels through scalar loads)
-template <typename T> const MpBigModel<T>& pick_big(const mp_model* m);
-template <> const MpBigModel<float>& pick_big<float>(const mp_model* m) { return m->bf; }
-template <> const MpBigModel<double>& pick_big<double>(const mp_model* m) { return m->bd; }
 template <typename T>
 int device_big_model(mp_ctx* ctx, const mp_model* model, const MpBigModel<T>** out) {
   auto& table = ctx->dev_big[sizeof(T) == 8 ? 1 : 0];
@@ -581,13 +554,6 @@ int device_big_model(mp_ctx* ctx, const mp_model* model, const MpBigModel<T>** o
   *out = static_cast<const MpBigModel<T>*>(it->second);
   return MP_OK;
 }
-#define REQUIRE_SMALL(fn)                                                                                              \
-  do {                                                                                                                 \
-    if (model->big)                                                                                                    \
-      return set_err(MP_ERR_UNSUPPORTED, "%s: not available for models with more than %d joints (this one has %d)", fn, \
-                     MP_MAX_DOF, model->d.n);                                                                          \
-  } while (0)
-
 // float32 calls on a 9..32-joint model: where the kernels find the float64 model for their ill-conditioned rows (mp_dyn.h,
 // mp_dyn_row_id_f64); float64 calls need nothing
 int big_cold_model(mp_ctx* ctx, const mp_model* model, MpCall<float>* c) {
@@ -1050,8 +1016,7 @@ static int kin_vjp_impl(const char* fn, mp_ctx* ctx, const mp_model* model, int 
   REQUIRE(ctx && model, "%s: null context or model", fn);
   CTX_ENTER(ctx);
   REQUIRE_SMALL(fn);
-  REQUIRE(frame == 0 || frame == 1, "%s: frame must be 0 (space) or 1 (body), got %d", fn, frame);
-  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (int rc = mp_kin_vjp_check(fn, frame, rows)) return rc;
   if (rows == 0) return MP_OK;
   REQUIRE(d_q, "%s: null device pointer", fn);
   REQUIRE(d_T || d_J || d_gq, "%s: at least one output is required", fn);
@@ -1064,20 +1029,13 @@ static int kin_vjp_impl(const char* fn, mp_ctx* ctx, const mp_model* model, int 
 
 // operational-space dynamics and task-space torque (mp_opspace.h): float64, unrolled models only; frame 0 = space, 1 = body,
 // 2 = hybrid; task 0 = full, 1 = linear, 2 = angular
-static int opspace_args(const char* fn, int frame, int task, double damping, int64_t rows) {
-  REQUIRE(frame >= 0 && frame <= 2, "%s: frame must be 0 (space), 1 (body) or 2 (hybrid), got %d", fn, frame);
-  REQUIRE(task >= 0 && task <= 2, "%s: task must be 0 (full), 1 (linear) or 2 (angular), got %d", fn, task);
-  REQUIRE(std::isfinite(damping) && damping >= 0.0, "%s: damping must be finite and >= 0", fn);
-  REQUIRE(rows >= 0, "%s: negative row count", fn);
-  return MP_OK;
-}
 static int opspace_impl(const char* fn, mp_ctx* ctx, const mp_model* model, int frame, int task, double damping, const double* d_q,
                         const double* d_qd, int64_t rows, const double* g, double* d_T, double* d_J, double* d_Jdqd, double* d_Lambda,
                         double* d_Jbar, double* d_mu, double* d_p) {
   REQUIRE(ctx && model, "%s: null context or model", fn);
   CTX_ENTER(ctx);
   REQUIRE_SMALL(fn);
-  if (int rc = opspace_args(fn, frame, task, damping, rows)) return rc;
+  if (int rc = mp_opspace_check(fn, frame, task, damping, rows)) return rc;
   if (rows == 0) return MP_OK;
   REQUIRE(d_q && d_qd, "%s: null device pointer", fn);
   REQUIRE(d_T || d_J || d_Jdqd || d_Lambda || d_Jbar || d_mu || d_p, "%s: at least one output is required", fn);
@@ -1097,7 +1055,7 @@ static int opspace_torque_impl(const char* fn, mp_ctx* ctx, const mp_model* mode
   REQUIRE(ctx && model, "%s: null context or model", fn);
   CTX_ENTER(ctx);
   REQUIRE_SMALL(fn);
-  if (int rc = opspace_args(fn, frame, task, damping, rows)) return rc;
+  if (int rc = mp_opspace_check(fn, frame, task, damping, rows)) return rc;
   if (rows == 0) return MP_OK;
   REQUIRE(d_q && d_qd && d_acc && d_tau, "%s: null device pointer", fn);
   REQUIRE(aligned16(d_q) && aligned16(d_qd) && aligned16(d_acc) && aligned16(d_tau0) && aligned16(d_tau),
@@ -1117,7 +1075,7 @@ static int regressor_impl(const char* fn, mp_ctx* ctx, const mp_model* model, co
   REQUIRE(ctx && model, "%s: null context or model", fn);
   CTX_ENTER(ctx);
   REQUIRE_SMALL(fn);
-  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (int rc = mp_regressor_check(fn, rows)) return rc;
   if (rows == 0) return MP_OK;
   REQUIRE(d_q && d_qd && d_qdd && d_Y, "%s: null device pointer", fn);
   REQUIRE(aligned16(d_q) && aligned16(d_qd) && aligned16(d_qdd) && aligned16(d_Y) && aligned16(d_tau_ext),
@@ -1137,7 +1095,7 @@ static int regressor_normal_impl(const char* fn, mp_ctx* ctx, const mp_model* mo
   REQUIRE(ctx && model, "%s: null context or model", fn);
   CTX_ENTER(ctx);
   REQUIRE_SMALL(fn);
-  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (int rc = mp_regressor_check(fn, rows)) return rc;
   REQUIRE(d_b && d_rr, "%s: null device pointer", fn);
   REQUIRE(aligned16(d_A) && aligned16(d_b) && aligned16(d_rr), "%s: device pointers must be 16-byte aligned", fn);
   const size_t w = (size_t)MP_REG_P * (size_t)model->d.n;
@@ -1243,17 +1201,11 @@ static int fdtraj_vjp_host_impl(const char* fn, mp_ctx* ctx, const mp_model* mod
 // batched iLQR (mp_ilqr.h): float64, unrolled models only, intRes = 1.  The weights are host vectors (2n, n, 2n) and travel as kernel
 // arguments.  k_batch_major: K / k are (B, N, ...) instead of (N, B, ...) - what the host forms hand back.
 static int ilqr_weights(const char* fn, int n, const double* wq, const double* wr, const double* wf, MpIlqrWeights* W) {
-  REQUIRE(wq && wr && wf, "%s: null weight vector", fn);
+  if (int rc = mp_ilqr_weights_check(fn, n, wq, wr, wf)) return rc;
   std::memset(W, 0, sizeof *W);
-  for (int j = 0; j < 2 * n; ++j) {
-    REQUIRE(std::isfinite(wq[j]) && std::isfinite(wf[j]), "%s: non-finite weight", fn);
-    W->wq[j] = wq[j];
-    W->wf[j] = wf[j];
-  }
-  for (int j = 0; j < n; ++j) {
-    REQUIRE(std::isfinite(wr[j]), "%s: non-finite weight", fn);
-    W->wr[j] = wr[j];
-  }
+  std::copy(wq, wq + 2 * n, W->wq);
+  std::copy(wr, wr + n, W->wr);
+  std::copy(wf, wf + 2 * n, W->wf);
   return MP_OK;
 }
 // MANIPULAPY_HIP_ILQR_BACKWARD=lane (read at every call): the one-lane-per-trajectory kernel and its global workspace instead of the
@@ -1383,27 +1335,6 @@ static int ilqr_rollout_host_impl(const char* fn, mp_ctx* ctx, const mp_model* m
 
 // time-optimal path parameterisation (mp_toppra.h): float64, unrolled models only.  The limits are host vectors and travel as kernel
 // arguments: velocity (n, finite and positive), torque (n, 2) or null (none), acceleration (n) or null (none).
-static int toppra_vmax(const char* fn, int n, const double* vlim, MpToppraVmax* V) {
-  REQUIRE(vlim, "%s: null velocity limits", fn);
-  std::memset(V, 0, sizeof *V);
-  for (int j = 0; j < n; ++j) {
-    REQUIRE(std::isfinite(vlim[j]) && vlim[j] > 0.0, "%s: velocity limits must be finite and positive", fn);
-    V->v[j] = vlim[j];
-  }
-  return MP_OK;
-}
-static int toppra_limits(const char* fn, int n, const double* tlim, const double* alim, MpToppraLimits* L) {
-  std::memset(L, 0, sizeof *L);
-  for (int j = 0; j < n; ++j) {
-    L->tau_lo[j] = tlim ? tlim[2 * j] : -INFINITY;
-    L->tau_hi[j] = tlim ? tlim[2 * j + 1] : INFINITY;
-    L->amax[j] = alim ? alim[j] : INFINITY;
-    REQUIRE(!std::isnan(L->tau_lo[j]) && !std::isnan(L->tau_hi[j]) && L->tau_lo[j] <= L->tau_hi[j],
-            "%s: torque limits must be ordered pairs (lo <= hi, either may be infinite)", fn);
-    REQUIRE(L->amax[j] > 0.0, "%s: acceleration limits must be positive", fn);
-  }
-  return MP_OK;
-}
 // The row outputs are written by the sweep's forward pass: measured 0.85 (xArm6) and 0.90 (Panda) of the time of the sweep followed
 // by the row-parallel launch k_path_rows.  MANIPULAPY_HIP_TOPPRA_EPILOGUE=separate (read at every call, so a captured
 // graph keeps the variant it was captured with) selects that launch instead; it exists for tools/toppra_bench.py to time the loser.
@@ -1419,7 +1350,7 @@ static int path_dynamics_impl(const char* fn, mp_ctx* ctx, const mp_model* model
   REQUIRE_SMALL(fn);
   REQUIRE(rows >= 0, "%s: negative row count", fn);
   MpToppraVmax V;
-  if (int rc = toppra_vmax(fn, model->d.n, vlim, &V)) return rc;
+  if (int rc = mp_toppra_vmax_check(fn, model->d.n, vlim, &V)) return rc;
   if (rows == 0) return MP_OK;
   REQUIRE(d_q && d_dq && d_ddq && d_a && d_b && d_c && d_xbar, "%s: null device pointer", fn);
   REQUIRE(aligned16(d_q) && aligned16(d_dq) && aligned16(d_ddq) && aligned16(d_a) && aligned16(d_b) && aligned16(d_c) && aligned16(d_xbar),
@@ -1440,7 +1371,7 @@ static int toppra_tm_impl(const char* fn, mp_ctx* ctx, const mp_model* model, co
   REQUIRE(B >= 0, "%s: negative B (%lld)", fn, (long long)B);
   REQUIRE(N >= 3, "%s: N must be >= 3 (got %lld)", fn, (long long)N);
   MpToppraLimits L;
-  if (int rc = toppra_limits(fn, model->d.n, tlim, alim, &L)) return rc;
+  if (int rc = mp_toppra_limits_check(fn, model->d.n, tlim, alim, &L)) return rc;
   if (B == 0) return MP_OK;
   REQUIRE(d_a && d_b && d_c && d_xbar && d_sd_start && d_sd_end && d_K && d_x && d_u && d_t && d_dur && d_status,
           "%s: null device pointer", fn);
@@ -1472,8 +1403,8 @@ static int toppra_host_impl(const char* fn, mp_ctx* ctx, const mp_model* model, 
   REQUIRE(N >= 3, "%s: N must be >= 3 (got %lld)", fn, (long long)N);
   MpToppraVmax V;
   MpToppraLimits L;
-  if (int rc = toppra_vmax(fn, model->d.n, vlim, &V)) return rc;
-  if (int rc = toppra_limits(fn, model->d.n, tlim, alim, &L)) return rc;
+  if (int rc = mp_toppra_vmax_check(fn, model->d.n, vlim, &V)) return rc;
+  if (int rc = mp_toppra_limits_check(fn, model->d.n, tlim, alim, &L)) return rc;
   if (B == 0) return MP_OK;
   REQUIRE(q && dq && ddq && sd_start && sd_end && K && x && u && t && dur && status, "%s: null host pointer", fn);
   REQUIRE((qd != nullptr) == (qdd != nullptr) && (qd != nullptr) == (tau != nullptr),
@@ -1737,7 +1668,7 @@ int mp_selftest(mp_ctx* ctx) {
   HIP_TRY(hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, ctx->compute));
   HIP_TRY(hipStreamSynchronize(ctx->compute));
   for (int i = 0; i < 64; ++i)
-    if (h[i] != i) return set_err(MP_ERR_HIP, "mp_selftest: lane %d wrote %d", i, h[i]);
+    if (h[i] != i) return mp_fail(MP_ERR_HIP, "mp_selftest: lane %d wrote %d", i, h[i]);
   return MP_OK;
 }
 
@@ -1760,7 +1691,7 @@ int mp_stream_bandwidth(mp_ctx* ctx, size_t bytes_per_array, int reads, int reps
   for (int w = 0; w < 3; ++w) HIP_TRY(mpk_stream(ctx->compute, reads, nt, a, buf[1], buf[2], d, n4));
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIP_TRY(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return set_err(MP_ERR_HIP, "mp_stream_bandwidth: hipEventCreate failed"); }
+  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return mp_fail(MP_ERR_HIP, "mp_stream_bandwidth: hipEventCreate failed"); }
   hipError_t e = hipEventRecord(e0, ctx->compute);
   for (int r = 0; r < reps && e == hipSuccess; ++r) e = mpk_stream(ctx->compute, reads, nt, a, buf[1], buf[2], d, n4);
   if (e == hipSuccess) e = hipEventRecord(e1, ctx->compute);
@@ -1768,7 +1699,7 @@ int mp_stream_bandwidth(mp_ctx* ctx, size_t bytes_per_array, int reads, int reps
   float ms = 0.f;
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  if (e != hipSuccess) return set_err(MP_ERR_HIP, "mp_stream_bandwidth: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return mp_fail(MP_ERR_HIP, "mp_stream_bandwidth: %s", hipGetErrorString(e));
   *gb_per_s = (double)(reads + 1) * (double)nb * (double)reps / ((double)ms * 1e-3) / 1e9;
   return MP_OK;
 }
@@ -1787,11 +1718,11 @@ int mp_stream_bandwidth_mix(mp_ctx* ctx, size_t bytes_per_array, int reads, int 
   const long n4 = (long)(nb / 16);
   hipError_t e = hipSuccess;
   for (int w = 0; w < 2 && e == hipSuccess; ++w) e = mpk_stream_mix(ctx->compute, reads, writes, nontemporal != 0, a, d, n4);
-  if (e == hipErrorInvalidValue) return set_err(MP_ERR_INVALID, "mp_stream_bandwidth_mix: no probe kernel for %d reads : %d writes", reads, writes);
+  if (e == hipErrorInvalidValue) return mp_fail(MP_ERR_INVALID, "mp_stream_bandwidth_mix: no probe kernel for %d reads : %d writes", reads, writes);
   if (e != hipSuccess) return hip_err(e, "mp_stream_bandwidth_mix");
   hipEvent_t e0 = nullptr, e1 = nullptr;
   HIP_TRY(hipEventCreate(&e0));
-  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return set_err(MP_ERR_HIP, "mp_stream_bandwidth_mix: hipEventCreate failed"); }
+  if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return mp_fail(MP_ERR_HIP, "mp_stream_bandwidth_mix: hipEventCreate failed"); }
   e = hipEventRecord(e0, ctx->compute);
   for (int r = 0; r < reps && e == hipSuccess; ++r) e = mpk_stream_mix(ctx->compute, reads, writes, nontemporal != 0, a, d, n4);
   if (e == hipSuccess) e = hipEventRecord(e1, ctx->compute);
@@ -1799,7 +1730,7 @@ int mp_stream_bandwidth_mix(mp_ctx* ctx, size_t bytes_per_array, int reads, int 
   float ms = 0.f;
   if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
   (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  if (e != hipSuccess) return set_err(MP_ERR_HIP, "mp_stream_bandwidth_mix: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return mp_fail(MP_ERR_HIP, "mp_stream_bandwidth_mix: %s", hipGetErrorString(e));
   *gb_per_s = (double)(reads + writes) * (double)nb * (double)reps / ((double)ms * 1e-3) / 1e9;
   return MP_OK;
 }
@@ -2100,7 +2031,7 @@ int mp_model_create(int n, const double* S, const double* Mcom, const double* G,
   }
   if (rc) {
     delete m;
-    return set_err(MP_ERR_MODEL, "mp_model_create: %s", msg);
+    return mp_fail(MP_ERR_MODEL, "mp_model_create: %s", msg);
   }
   static std::atomic<uint64_t> next_uid{1};
   m->uid = next_uid.fetch_add(1);
@@ -2186,11 +2117,11 @@ int mp_model_specialize_compile(const mp_model* model, size_t* code_bytes, int* 
   std::vector<char> code;
   std::string err;
   bool cached = false;
-  if (mp_jit_compile(model->f, model->d, &code, &cached, &err)) return set_err(MP_ERR_UNSUPPORTED, "mp_model_specialize_compile: %s", err.c_str());
+  if (mp_jit_compile(model->f, model->d, &code, &cached, &err)) return mp_fail(MP_ERR_UNSUPPORTED, "mp_model_specialize_compile: %s", err.c_str());
   {  // the second program (the one-row float32 inverse dynamics under the max-ILP scheduling strategy): both are needed
     std::vector<char> code2;
     bool cached2 = false;
-    if (mp_jit_compile(model->f, model->d, &code2, &cached2, &err, 1)) return set_err(MP_ERR_UNSUPPORTED, "mp_model_specialize_compile: %s", err.c_str());
+    if (mp_jit_compile(model->f, model->d, &code2, &cached2, &err, 1)) return mp_fail(MP_ERR_UNSUPPORTED, "mp_model_specialize_compile: %s", err.c_str());
     code.insert(code.end(), code2.begin(), code2.end());   // (the size reported is both programs')
     cached = cached && cached2;
   }
@@ -2211,7 +2142,7 @@ int mp_model_specialize(mp_ctx* ctx, const mp_model* model) {
   if (ctx->specs.count(model->uid)) return MP_OK;
   std::vector<char> code;
   std::string err;
-  if (mp_jit_compile(model->f, model->d, &code, nullptr, &err)) return set_err(MP_ERR_UNSUPPORTED, "mp_model_specialize: %s", err.c_str());
+  if (mp_jit_compile(model->f, model->d, &code, nullptr, &err)) return mp_fail(MP_ERR_UNSUPPORTED, "mp_model_specialize: %s", err.c_str());
   MpSpec sp;
   HIP_TRY(hipModuleLoadData(&sp.mod, code.data()));
   // every kernel of the two programs is required: a program that lacks one is refused and the generic kernels serve
@@ -2238,7 +2169,7 @@ int mp_model_specialize(mp_ctx* ctx, const mp_model* model) {
     hipModule_t m2 = nullptr;
     if (mp_jit_compile(model->f, model->d, &code2, nullptr, &err, 1)) {
       (void)hipModuleUnload(sp.mod);
-      return set_err(MP_ERR_UNSUPPORTED, "mp_model_specialize: %s", err.c_str());
+      return mp_fail(MP_ERR_UNSUPPORTED, "mp_model_specialize: %s", err.c_str());
     }
     hipError_t e = hipModuleLoadData(&m2, code2.data());
     if (e != hipSuccess) { (void)hipModuleUnload(sp.mod); return hip_err(e, "hipModuleLoadData (second program)"); }
@@ -2313,7 +2244,7 @@ int mp_model_specialize(mp_ctx* ctx, const mp_model* model) {
     }
     if (!ok) {
       unload();
-      return set_err(MP_ERR_UNSUPPORTED, "mp_model_specialize: the specialised kernels of this toolchain do not keep the non-finite row "
+      return mp_fail(MP_ERR_UNSUPPORTED, "mp_model_specialize: the specialised kernels of this toolchain do not keep the non-finite row "
                                          "contract (self-check failed); the generic kernels are used instead");
     }
   }
@@ -2578,11 +2509,9 @@ int mp_id_regressor_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, c
   return regressor_impl("mp_id_regressor_f64", ctx, model, d_q, d_qd, d_qdd, rows, g, Ftip, d_Y, d_tau_ext);
 }
 int64_t mp_id_regressor_normal_workspace_bytes(const mp_model* model, int64_t rows) {
-  if (!model) return -set_err(MP_ERR_INVALID, "mp_id_regressor_normal_workspace_bytes: null model");
-  if (rows < 0) return -set_err(MP_ERR_INVALID, "mp_id_regressor_normal_workspace_bytes: negative row count");
-  if (model->big)
-    return -set_err(MP_ERR_UNSUPPORTED, "mp_id_regressor_normal_workspace_bytes: not available for models with more than %d joints "
-                    "(this one has %d)", MP_MAX_DOF, model->d.n);
+  if (!model) return -mp_fail(MP_ERR_INVALID, "mp_id_regressor_normal_workspace_bytes: null model");
+  if (rows < 0) return -mp_fail(MP_ERR_INVALID, "mp_id_regressor_normal_workspace_bytes: negative row count");
+  if (model->big) return -mp_too_many_joints("mp_id_regressor_normal_workspace_bytes", model->d.n);
   return regressor_normal_work_bytes(model->d.n, rows);
 }
 int mp_id_regressor_normal_f64(mp_ctx* ctx, const mp_model* model, const double* d_q, const double* d_qd, const double* d_qdd,
@@ -2591,9 +2520,9 @@ int mp_id_regressor_normal_f64(mp_ctx* ctx, const mp_model* model, const double*
   return regressor_normal_impl("mp_id_regressor_normal_f64", ctx, model, d_q, d_qd, d_qdd, d_rhs, rows, g, Ftip, d_work, d_A, d_b, d_rr);
 }
 int64_t mp_fd_trajectory_vjp_workspace_bytes(const mp_model* model, int64_t B, int64_t N, int intRes) {
-  if (!model) return -set_err(MP_ERR_INVALID, "mp_fd_trajectory_vjp_workspace_bytes: null model");
+  if (!model) return -mp_fail(MP_ERR_INVALID, "mp_fd_trajectory_vjp_workspace_bytes: null model");
   if (B < 0 || N < 0 || intRes < 1)
-    return -set_err(MP_ERR_INVALID, "mp_fd_trajectory_vjp_workspace_bytes: negative B or N, or intRes < 1");
+    return -mp_fail(MP_ERR_INVALID, "mp_fd_trajectory_vjp_workspace_bytes: negative B or N, or intRes < 1");
   return vjp_work_doubles(model->d.n, B, N, intRes) * (int64_t)sizeof(double);
 }
 int mp_fd_trajectory_vjp_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_theta0, const double* d_dtheta0,
@@ -2611,11 +2540,9 @@ int mp_fd_trajectory_vjp_host_f64(mp_ctx* ctx, const mp_model* model, const doub
                               gvel, gacc, gtheta0, gdtheta0, gtaumat);
 }
 int64_t mp_ilqr_backward_workspace_bytes(const mp_model* model, int64_t B, int64_t N) {
-  if (!model) return -set_err(MP_ERR_INVALID, "mp_ilqr_backward_workspace_bytes: null model");
-  if (B < 0 || N < 2) return -set_err(MP_ERR_INVALID, "mp_ilqr_backward_workspace_bytes: negative B, or N < 2");
-  if (model->big)
-    return -set_err(MP_ERR_UNSUPPORTED, "mp_ilqr_backward_workspace_bytes: not available for models with more than %d joints "
-                    "(this one has %d)", MP_MAX_DOF, model->d.n);
+  if (!model) return -mp_fail(MP_ERR_INVALID, "mp_ilqr_backward_workspace_bytes: null model");
+  if (B < 0 || N < 2) return -mp_fail(MP_ERR_INVALID, "mp_ilqr_backward_workspace_bytes: negative B, or N < 2");
+  if (model->big) return -mp_too_many_joints("mp_ilqr_backward_workspace_bytes", model->d.n);
   return ilqr_lane_variant() ? B * (int64_t)mp_ilqr_work_doubles(model->d.n) * (int64_t)sizeof(double) : 0;
 }
 int mp_ilqr_backward_tm_f64(mp_ctx* ctx, const mp_model* model, const double* d_pos, const double* d_vel, const double* d_taumat,
@@ -2793,8 +2720,7 @@ int mp_fk_jac_vjp_host_f64(mp_ctx* ctx, const mp_model* model, int frame, const 
   REQUIRE(ctx && model, "%s: null context or model", fn);
   CTX_ENTER(ctx);
   REQUIRE_SMALL(fn);
-  REQUIRE(frame == 0 || frame == 1, "%s: frame must be 0 (space) or 1 (body), got %d", fn, frame);
-  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (int rc = mp_kin_vjp_check(fn, frame, rows)) return rc;
   if (rows == 0) return MP_OK;
   REQUIRE(q, "%s: null host pointer", fn);
   REQUIRE(T || J || gq, "%s: at least one output is required", fn);
@@ -2812,7 +2738,7 @@ int mp_opspace_host_f64(mp_ctx* ctx, const mp_model* model, int frame, int task,
   REQUIRE(ctx && model, "%s: null context or model", fn);
   CTX_ENTER(ctx);
   REQUIRE_SMALL(fn);
-  if (int rc = opspace_args(fn, frame, task, damping, rows)) return rc;
+  if (int rc = mp_opspace_check(fn, frame, task, damping, rows)) return rc;
   if (rows == 0) return MP_OK;
   REQUIRE(q && qd, "%s: null host pointer", fn);
   REQUIRE(T || J || Jdqd || Lambda || Jbar || mu || p, "%s: at least one output is required", fn);
@@ -2830,7 +2756,7 @@ int mp_opspace_torque_host_f64(mp_ctx* ctx, const mp_model* model, int frame, in
   REQUIRE(ctx && model, "%s: null context or model", fn);
   CTX_ENTER(ctx);
   REQUIRE_SMALL(fn);
-  if (int rc = opspace_args(fn, frame, task, damping, rows)) return rc;
+  if (int rc = mp_opspace_check(fn, frame, task, damping, rows)) return rc;
   if (rows == 0) return MP_OK;
   REQUIRE(q && qd && acc && tau, "%s: null host pointer", fn);
   const size_t vb = (size_t)rows * (size_t)model->d.n * sizeof(double), ab = (size_t)rows * (task == 0 ? 6 : 3) * sizeof(double);
@@ -2846,7 +2772,7 @@ int mp_id_regressor_host_f64(mp_ctx* ctx, const mp_model* model, const double* q
   REQUIRE(ctx && model, "%s: null context or model", fn);
   CTX_ENTER(ctx);
   REQUIRE_SMALL(fn);
-  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (int rc = mp_regressor_check(fn, rows)) return rc;
   if (rows == 0) return MP_OK;
   REQUIRE(q && qd && qdd && Y, "%s: null host pointer", fn);
   const size_t n = (size_t)model->d.n, vb = (size_t)rows * n * sizeof(double), yb = vb * n * MP_REG_P;
@@ -2862,7 +2788,7 @@ int mp_id_regressor_normal_host_f64(mp_ctx* ctx, const mp_model* model, const do
   REQUIRE(ctx && model, "%s: null context or model", fn);
   CTX_ENTER(ctx);
   REQUIRE_SMALL(fn);
-  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  if (int rc = mp_regressor_check(fn, rows)) return rc;
   REQUIRE(b && rr && (rows == 0 || (q && qd && qdd && rhs)), "%s: null host pointer", fn);
   const size_t n = (size_t)model->d.n, vb = (size_t)rows * n * sizeof(double), w = n * MP_REG_P;
   HostCall h(ctx);
@@ -2955,22 +2881,15 @@ int mp_potential_field_host_f32(mp_ctx* ctx, const float* positions, const float
 }
 
 }  // extern "C"
-template <typename PT, int CAP>
+// the settings of the IK entries, packed by mp_ik_pack (mp_handles.h); these entries' words say which joint's limits are crossed
+template <int CAP>
 static int ik_params(const char* fn, const mp_model* model, const double* joint_limits, double eomg, double ev, int max_iterations,
                      double damping, double step_cap, double w_o, double w_p, int adaptive, int backtracking, uint32_t seed,
-                     PT* P) {
+                     MpIkParamsT<CAP>* P) {
   REQUIRE(max_iterations >= 1, "%s: max_iterations must be at least 1 (got %d)", fn, max_iterations);
-  REQUIRE(eomg > 0 && ev > 0 && damping >= 0 && step_cap > 0, "%s: eomg, ev, step_cap must be positive and damping non-negative", fn);
-  P->eomg = eomg; P->ev = ev; P->damping = damping; P->step_cap = step_cap; P->w_o = w_o; P->w_p = w_p;
-  P->max_iterations = max_iterations; P->seed = seed;
-  P->adaptive_tuning = adaptive ? 1 : 0; P->backtracking = backtracking ? 1 : 0;
-  const int n = model->d.n;
-  for (int j = 0; j < CAP; ++j) {
-    P->lo[j] = (j < n && joint_limits) ? joint_limits[2 * j] : -HUGE_VAL;
-    P->hi[j] = (j < n && joint_limits) ? joint_limits[2 * j + 1] : HUGE_VAL;
-    REQUIRE(!(P->lo[j] > P->hi[j]), "%s: joint %d has lower limit above upper limit", fn, j);
-  }
-  return MP_OK;
+  const int rc = mp_ik_pack(fn, model->d.n, joint_limits, eomg, ev, max_iterations, damping, step_cap, w_o, w_p, adaptive, backtracking, seed, P);
+  REQUIRE(rc >= 0, "%s: joint %d has lower limit above upper limit", fn, -rc - 1);
+  return rc;
 }
 extern "C" {
 
@@ -2990,7 +2909,7 @@ int mp_inverse_kinematics_f64(mp_ctx* ctx, const mp_model* model, const double* 
   }
   if (model->big) {  // 9..32 joints: the same iteration on the run-time-n kinematics (csrc/mp_dyn.h)
     MpIkBigParams PB;
-    if (int rc = ik_params<MpIkBigParams, MP_BIG_DOF>("mp_inverse_kinematics_f64", model, joint_limits, eomg, ev, max_iterations, damping,
+    if (int rc = ik_params("mp_inverse_kinematics_f64", model, joint_limits, eomg, ev, max_iterations, damping,
                                                       step_cap, weight_orientation, weight_position, adaptive_tuning, backtracking, seed, &PB))
       return rc;
     const MpBigModel<double>* dm = nullptr;
@@ -3000,7 +2919,7 @@ int mp_inverse_kinematics_f64(mp_ctx* ctx, const mp_model* model, const double* 
     return MP_OK;
   }
   MpIkParams P;
-  if (int rc = ik_params<MpIkParams, MP_MAX_DOF>("mp_inverse_kinematics_f64", model, joint_limits, eomg, ev, max_iterations, damping, step_cap,
+  if (int rc = ik_params("mp_inverse_kinematics_f64", model, joint_limits, eomg, ev, max_iterations, damping, step_cap,
                                                  weight_orientation, weight_position, adaptive_tuning, backtracking, seed, &P))
     return rc;
   if (const MpSpec* sp = find_spec(ctx, model)) {  // this robot's constants baked in (mp_model_specialize)
@@ -3099,7 +3018,7 @@ static int collision_resident(const char* fn, mp_ctx* ctx, mp_collision* h, mp_c
   HIP_TRY(hipMalloc(&R.sph, sizeof(MpColSpheres) + (pb ? pb : sizeof(MpColPair))));
   if (hipMalloc(&R.counter, 256) != hipSuccess) {
     (void)hipFree(R.sph);
-    return set_err(MP_ERR_HIP, "%s: out of device memory", fn);
+    return mp_fail(MP_ERR_HIP, "%s: out of device memory", fn);
   }
   h->release = collision_release;
   mp_collision::Resident& K = h->resident[ctx->uid] = R;
@@ -3480,4 +3399,7 @@ int mp_collision_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, c
 
 }  // extern "C"
 
-int mp_set_error(int code, const char* msg) { return set_err(code, "%s", msg); }
+int mp_set_error(int code, const char* msg) {
+  std::snprintf(g_err, sizeof g_err, "%s", msg);
+  return code;
+}

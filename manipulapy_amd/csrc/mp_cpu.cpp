@@ -34,10 +34,6 @@
 #include "mp_collision.h"
 
 namespace {
-const double kG[3] = {0.0, 0.0, -9.81};
-
-int fail(const char* msg) { return mp_set_error(MP_ERR_INVALID, msg); }
-
 // Threads a launcher takes when the caller names none: every core this process may run on (its affinity mask) - but a container is
 // often SHOWN more cores than it is granted time on (the MI355X boxes of this project: 256 visible, a cgroup quota of 16 CPUs), and
 // one thread per visible core then loses to a fraction of them (the CPU baseline of bench.py: 256 threads 0.27 M rows/s, 64: 0.68): at
@@ -104,21 +100,6 @@ int parallel_for(int64_t items, int64_t grain, int nthreads, F fn) {
   return started;
 }
 
-bool any_nonzero(const double* F) {
-  if (!F) return false;
-  for (int k = 0; k < 6; ++k)
-    if (F[k] != 0.0) return true;
-  return false;
-}
-
-template <typename T> const MpModel<T>& pick(const mp_model* m);
-template <> const MpModel<float>& pick<float>(const mp_model* m) { return m->f; }
-template <> const MpModel<double>& pick<double>(const mp_model* m) { return m->d; }
-
-template <typename T> const MpBigModel<T>& pick_big(const mp_model* m);
-template <> const MpBigModel<float>& pick_big<float>(const mp_model* m) { return m->bf; }
-template <> const MpBigModel<double>& pick_big<double>(const mp_model* m) { return m->bd; }
-
 template <typename T>
 MpCall<T> make_call(const mp_model* m, const double* g, const double* Ftip) {
   MpCall<double> cd;
@@ -141,7 +122,7 @@ MpCall<T> make_call(const mp_model* m, const double* g, const double* Ftip) {
     case 6: { constexpr int N = 6; __VA_ARGS__; } break;         \
     case 7: { constexpr int N = 7; __VA_ARGS__; } break;         \
     case 8: { constexpr int N = 8; __VA_ARGS__; } break;         \
-    default: return fail("dof outside 1..8 (larger models take the looped path before this dispatch)");                    \
+    default: return mp_fail(MP_ERR_INVALID, "dof outside 1..8 (larger models take the looped path before this dispatch)"); \
   }
 
 // ---- one row of FK / Jacobian / inverse dynamics: the body of k_fk_jac_id / k_id on the host
@@ -178,10 +159,10 @@ void rows_fk_jac_id(const MpModel<T>& M, const MpCall<T>& C, const T* q, const T
 template <typename T>
 int fk_jac_id_cpu(const char* fn, const mp_model* model, const T* q, const T* qd, const T* qdd, int64_t rows, const double* g,
                   const double* Ftip, T* Tout, T* Jout, T* tau, int nthreads) {
-  if (!model) return fail("null model");
-  if (rows < 0) return fail("negative row count");
+  REQUIRE(model, "null model");
+  REQUIRE(rows >= 0, "negative row count");
   if (rows == 0) return MP_OK;
-  if (!q || !(Tout || Jout || tau) || (tau && !(qd && qdd))) return fail(fn);
+  REQUIRE(q && (Tout || Jout || tau) && (!tau || (qd && qdd)), "%s", fn);
   const MpModel<T>& M = pick<T>(model);
   const MpCall<T> C = make_call<T>(model, g, Ftip);
   const bool ftip = any_nonzero(Ftip);
@@ -284,11 +265,11 @@ void rollouts(const MpModel<T>& M, const MpCall<T>& C, const T* theta0, const T*
 template <typename T>
 int fd_trajectory_cpu(const mp_model* model, const T* theta0, const T* dtheta0, const T* taumat, const T* Ftipmat, int64_t B,
                       int64_t Nt, const double* g, double dt, int intRes, float* pos, float* vel, float* acc, int nthreads) {
-  if (!model) return fail("null model");
-  if (B < 0 || Nt < 0) return fail("negative trajectory / step count");
+  REQUIRE(model, "null model");
+  REQUIRE(B >= 0 && Nt >= 0, "negative trajectory / step count");
   if (B == 0 || Nt == 0) return MP_OK;
-  if (intRes < 1) return fail("intRes must be >= 1");
-  if (!theta0 || !dtheta0 || !taumat || !pos || !vel || !acc) return fail("null pointer");
+  REQUIRE(intRes >= 1, "intRes must be >= 1");
+  REQUIRE(theta0 && dtheta0 && taumat && pos && vel && acc, "null pointer");
   const MpModel<T>& M = pick<T>(model);
   const MpCall<T> C = make_call<T>(model, g, nullptr);
   const T h = (T)(dt / intRes);
@@ -312,27 +293,72 @@ int fd_trajectory_cpu(const mp_model* model, const T* theta0, const T* dtheta0, 
 }
 }  // namespace
 
+// ---- the argument checks that the twins below share with the entries of a context (mp_handles.h); the sphere-model families'
+// stand further down, beside their twins
+int mp_opspace_check(const char* fn, int frame, int task, double damping, int64_t rows) {
+  REQUIRE(frame >= 0 && frame <= 2, "%s: frame must be 0 (space), 1 (body) or 2 (hybrid), got %d", fn, frame);
+  REQUIRE(task >= 0 && task <= 2, "%s: task must be 0 (full), 1 (linear) or 2 (angular), got %d", fn, task);
+  REQUIRE(std::isfinite(damping) && damping >= 0.0, "%s: damping must be finite and >= 0", fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  return MP_OK;
+}
+int mp_kin_vjp_check(const char* fn, int frame, int64_t rows) {
+  REQUIRE(frame == 0 || frame == 1, "%s: frame must be 0 (space) or 1 (body), got %d", fn, frame);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  return MP_OK;
+}
+int mp_regressor_check(const char* fn, int64_t rows) {
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
+  return MP_OK;
+}
+int mp_ilqr_weights_check(const char* fn, int n, const double* wq, const double* wr, const double* wf) {
+  REQUIRE(wq && wr && wf, "%s: null weight vector", fn);
+  for (int j = 0; j < 2 * n; ++j) REQUIRE(std::isfinite(wq[j]) && std::isfinite(wf[j]) && std::isfinite(wr[j / 2]), "%s: non-finite weight", fn);
+  return MP_OK;
+}
+int mp_toppra_vmax_check(const char* fn, int n, const double* vlim, MpToppraVmax* out) {
+  REQUIRE(vlim, "%s: null velocity limits", fn);
+  std::memset(out, 0, sizeof *out);
+  for (int j = 0; j < n; ++j) {
+    REQUIRE(std::isfinite(vlim[j]) && vlim[j] > 0.0, "%s: velocity limits must be finite and positive", fn);
+    out->v[j] = vlim[j];
+  }
+  return MP_OK;
+}
+int mp_toppra_limits_check(const char* fn, int n, const double* tlim, const double* alim, MpToppraLimits* out) {
+  std::memset(out, 0, sizeof *out);
+  for (int j = 0; j < n; ++j) {
+    out->tau_lo[j] = tlim ? tlim[2 * j] : -INFINITY;
+    out->tau_hi[j] = tlim ? tlim[2 * j + 1] : INFINITY;
+    out->amax[j] = alim ? alim[j] : INFINITY;
+    REQUIRE(!std::isnan(out->tau_lo[j]) && !std::isnan(out->tau_hi[j]) && out->tau_lo[j] <= out->tau_hi[j],
+            "%s: torque limits must be ordered pairs (lo <= hi, either may be infinite)", fn);
+    REQUIRE(out->amax[j] > 0.0, "%s: acceleration limits must be positive", fn);
+  }
+  return MP_OK;
+}
+
 extern "C" {
 
 int mp_cpu_threads(int64_t items) { return thread_count(items, 1, 0); }
 
 int mp_id_trajectory_cpu_f32(const mp_model* model, const float* q, const float* qd, const float* qdd, int64_t rows,
                              const double* g, const double* Ftip, float* tau, int nthreads) {
-  if (rows > 0 && !tau) return fail("mp_id_trajectory_cpu_f32: null tau");
+  REQUIRE(rows <= 0 || tau, "mp_id_trajectory_cpu_f32: null tau");
   return fk_jac_id_cpu<float>("mp_id_trajectory_cpu_f32: null pointer", model, q, qd, qdd, rows, g, Ftip, nullptr, nullptr, tau, nthreads);
 }
 int mp_id_trajectory_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, int64_t rows,
                              const double* g, const double* Ftip, double* tau, int nthreads) {
-  if (rows > 0 && !tau) return fail("mp_id_trajectory_cpu_f64: null tau");
+  REQUIRE(rows <= 0 || tau, "mp_id_trajectory_cpu_f64: null tau");
   return fk_jac_id_cpu<double>("mp_id_trajectory_cpu_f64: null pointer", model, q, qd, qdd, rows, g, Ftip, nullptr, nullptr, tau, nthreads);
 }
 // which rows the float32 inverse-dynamics kernels evaluate in float64 (mp_core.h, mp_id_row_is_hard): 1 per such row
 int mp_id_row_precision_cpu_f32(const mp_model* model, const float* q, const float* qd, const float* qdd, int64_t rows,
                                 const double* g, const double* Ftip, uint8_t* in_f64, int nthreads) {
-  if (!model) return fail("mp_id_row_precision_cpu_f32: null model");
-  if (rows < 0) return fail("mp_id_row_precision_cpu_f32: negative row count");
+  REQUIRE(model, "mp_id_row_precision_cpu_f32: null model");
+  REQUIRE(rows >= 0, "mp_id_row_precision_cpu_f32: negative row count");
   if (rows == 0) return MP_OK;
-  if (!q || !qd || !qdd || !in_f64) return fail("mp_id_row_precision_cpu_f32: null pointer");
+  REQUIRE(q && qd && qdd && in_f64, "mp_id_row_precision_cpu_f32: null pointer");
   const MpModel<float>& M = model->f;
   const MpCall<float> C = make_call<float>(model, g, Ftip);
   const bool ftip = any_nonzero(Ftip);
@@ -375,10 +401,10 @@ int mp_fk_jac_id_cpu_f64(const mp_model* model, const double* q, const double* q
 }
 
 int mp_mass_matrix_cpu_f64(const mp_model* model, const double* q, int64_t rows, double* Mout, int nthreads) {
-  if (!model) return fail("mp_mass_matrix_cpu_f64: null model");
-  if (rows < 0) return fail("mp_mass_matrix_cpu_f64: negative row count");
+  REQUIRE(model, "mp_mass_matrix_cpu_f64: null model");
+  REQUIRE(rows >= 0, "mp_mass_matrix_cpu_f64: negative row count");
   if (rows == 0) return MP_OK;
-  if (!q || !Mout) return fail("mp_mass_matrix_cpu_f64: null pointer");
+  REQUIRE(q && Mout, "mp_mass_matrix_cpu_f64: null pointer");
   const MpModel<double>& M = model->d;
   if (model->big) {
     parallel_for(rows, 128, nthreads, [&](int64_t lo, int64_t hi) {
@@ -392,10 +418,10 @@ int mp_mass_matrix_cpu_f64(const mp_model* model, const double* q, int64_t rows,
 
 int mp_forward_dynamics_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* tau, int64_t rows,
                                 const double* g, const double* Ftip, double* qdd, int nthreads) {
-  if (!model) return fail("mp_forward_dynamics_cpu_f64: null model");
-  if (rows < 0) return fail("mp_forward_dynamics_cpu_f64: negative row count");
+  REQUIRE(model, "mp_forward_dynamics_cpu_f64: null model");
+  REQUIRE(rows >= 0, "mp_forward_dynamics_cpu_f64: negative row count");
   if (rows == 0) return MP_OK;
-  if (!q || !qd || !tau || !qdd) return fail("mp_forward_dynamics_cpu_f64: null pointer");
+  REQUIRE(q && qd && tau && qdd, "mp_forward_dynamics_cpu_f64: null pointer");
   const MpModel<double>& M = model->d;
   const MpCall<double> C = make_call<double>(model, g, Ftip);
   const bool ftip = any_nonzero(Ftip);
@@ -420,15 +446,10 @@ int mp_forward_dynamics_cpu_f64(const mp_model* model, const double* q, const do
 // analytical derivatives (mp_deriv.h): the kernels' per-row code over host rows
 static int deriv_cpu(const char* fn, bool fd, const mp_model* model, const double* q, const double* qd, const double* x, int64_t rows,
                      const double* g, const double* Ftip, double* y, double* dq, double* dqd, double* mat, int nthreads) {
-  char msg[192];
-  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
-  if (model->big) {
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (rows < 0) { std::snprintf(msg, sizeof msg, "%s: negative row count", fn); return fail(msg); }
+  if (int rc = mp_small_model(fn, model)) return rc;
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
   if (rows == 0) return MP_OK;
-  if (!q || !qd || !x || !dq || !dqd) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
+  REQUIRE(q && qd && x && dq && dqd, "%s: null pointer", fn);
   const MpModel<double>& M = model->d;
   const MpCall<double> C = make_call<double>(model, g, Ftip);
   const bool ftip = any_nonzero(Ftip);
@@ -461,15 +482,10 @@ int mp_fd_derivatives_cpu_f64(const mp_model* model, const double* q, const doub
 // ID: o1 = gq, o2 = gqd, o3 = gqdd (may be null), y unused;  FD: y = qdd (may be null), o1 = gq, o2 = gqd, o3 = gtau (may be null)
 static int vjp_cpu(const char* fn, bool fd, const mp_model* model, const double* q, const double* qd, const double* x, const double* cot,
                    int64_t rows, const double* g, const double* Ftip, double* y, double* o1, double* o2, double* o3, int nthreads) {
-  char msg[192];
-  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
-  if (model->big) {
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (rows < 0) { std::snprintf(msg, sizeof msg, "%s: negative row count", fn); return fail(msg); }
+  if (int rc = mp_small_model(fn, model)) return rc;
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
   if (rows == 0) return MP_OK;
-  if (!q || !qd || !x || !cot || !o1 || !o2) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
+  REQUIRE(q && qd && x && cot && o1 && o2, "%s: null pointer", fn);
   const MpModel<double>& M = model->d;
   const MpCall<double> C = make_call<double>(model, g, Ftip);
   const bool ftip = any_nonzero(Ftip);
@@ -500,20 +516,11 @@ int mp_fd_vjp_cpu_f64(const mp_model* model, const double* q, const double* qd, 
 int mp_fk_jac_vjp_cpu_f64(const mp_model* model, int frame, const double* q, const double* gT, const double* gJ, int64_t rows,
                           double* T, double* J, double* gq, int nthreads) {
   const char* fn = "mp_fk_jac_vjp_cpu_f64";
-  char msg[192];
-  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
-  if (model->big) {
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (frame != 0 && frame != 1) {
-    std::snprintf(msg, sizeof msg, "%s: frame must be 0 (space) or 1 (body), got %d", fn, frame);
-    return fail(msg);
-  }
-  if (rows < 0) { std::snprintf(msg, sizeof msg, "%s: negative row count", fn); return fail(msg); }
+  if (int rc = mp_small_model(fn, model)) return rc;
+  if (int rc = mp_kin_vjp_check(fn, frame, rows)) return rc;
   if (rows == 0) return MP_OK;
-  if (!q) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
-  if (!T && !J && !gq) { std::snprintf(msg, sizeof msg, "%s: at least one output is required", fn); return fail(msg); }
+  REQUIRE(q, "%s: null pointer", fn);
+  REQUIRE(T || J || gq, "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MP_CPU_DISPATCH(M.n, {
     parallel_for(rows, 256, nthreads, [&](int64_t lo, int64_t hi) {
@@ -526,34 +533,15 @@ int mp_fk_jac_vjp_cpu_f64(const mp_model* model, int frame, const double* q, con
   return MP_OK;
 }
 // operational-space dynamics and task-space torque (mp_opspace.h): the kernels' per-row code over host rows
-static int opspace_cpu_check(const char* fn, const mp_model* model, int frame, int task, double damping, int64_t rows) {
-  char msg[192];
-  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
-  if (model->big) {
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (frame < 0 || frame > 2) {
-    std::snprintf(msg, sizeof msg, "%s: frame must be 0 (space), 1 (body) or 2 (hybrid), got %d", fn, frame);
-    return fail(msg);
-  }
-  if (task < 0 || task > 2) {
-    std::snprintf(msg, sizeof msg, "%s: task must be 0 (full), 1 (linear) or 2 (angular), got %d", fn, task);
-    return fail(msg);
-  }
-  if (!(std::isfinite(damping) && damping >= 0.0)) { std::snprintf(msg, sizeof msg, "%s: damping must be finite and >= 0", fn); return fail(msg); }
-  if (rows < 0) { std::snprintf(msg, sizeof msg, "%s: negative row count", fn); return fail(msg); }
-  return MP_OK;
-}
 int mp_opspace_cpu_f64(const mp_model* model, int frame, int task, double damping, const double* q, const double* qd, int64_t rows,
                        const double* g, double* T, double* J, double* Jdqd, double* Lambda, double* Jbar, double* mu, double* p,
                        int nthreads) {
   const char* fn = "mp_opspace_cpu_f64";
-  char msg[192];
-  if (int rc = opspace_cpu_check(fn, model, frame, task, damping, rows)) return rc;
+  if (int rc = mp_small_model(fn, model)) return rc;
+  if (int rc = mp_opspace_check(fn, frame, task, damping, rows)) return rc;
   if (rows == 0) return MP_OK;
-  if (!q || !qd) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
-  if (!T && !J && !Jdqd && !Lambda && !Jbar && !mu && !p) { std::snprintf(msg, sizeof msg, "%s: at least one output is required", fn); return fail(msg); }
+  REQUIRE(q && qd, "%s: null pointer", fn);
+  REQUIRE(T || J || Jdqd || Lambda || Jbar || mu || p, "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   const MpCall<double> C = make_call<double>(model, g, nullptr);
   const double lam2 = damping * damping;
@@ -567,10 +555,10 @@ int mp_opspace_cpu_f64(const mp_model* model, int frame, int task, double dampin
 int mp_opspace_torque_cpu_f64(const mp_model* model, int frame, int task, double damping, const double* q, const double* qd,
                               const double* acc, const double* tau0, int64_t rows, const double* g, double* tau, int nthreads) {
   const char* fn = "mp_opspace_torque_cpu_f64";
-  char msg[192];
-  if (int rc = opspace_cpu_check(fn, model, frame, task, damping, rows)) return rc;
+  if (int rc = mp_small_model(fn, model)) return rc;
+  if (int rc = mp_opspace_check(fn, frame, task, damping, rows)) return rc;
   if (rows == 0) return MP_OK;
-  if (!q || !qd || !acc || !tau) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
+  REQUIRE(q && qd && acc && tau, "%s: null pointer", fn);
   const MpModel<double>& M = model->d;
   const MpCall<double> C = make_call<double>(model, g, nullptr);
   const double lam2 = damping * damping;
@@ -582,22 +570,13 @@ int mp_opspace_torque_cpu_f64(const mp_model* model, int frame, int task, double
   return MP_OK;
 }
 // dynamics regressor (mp_regressor.h): the kernels' per-row code over host rows
-static int regressor_cpu_check(const char* fn, const mp_model* model, int64_t rows) {
-  char msg[192];
-  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
-  if (model->big) {
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (rows < 0) { std::snprintf(msg, sizeof msg, "%s: negative row count", fn); return fail(msg); }
-  return MP_OK;
-}
 int mp_id_regressor_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, int64_t rows, const double* g,
                             const double* Ftip, double* Y, double* tau_ext, int nthreads) {
   const char* fn = "mp_id_regressor_cpu_f64";
-  if (int rc = regressor_cpu_check(fn, model, rows)) return rc;
+  if (int rc = mp_small_model(fn, model)) return rc;
+  if (int rc = mp_regressor_check(fn, rows)) return rc;
   if (rows == 0) return MP_OK;
-  if (!q || !qd || !qdd || !Y) { char msg[96]; std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
+  REQUIRE(q && qd && qdd && Y, "%s: null pointer", fn);
   const MpModel<double>& M = model->d;
   const MpCall<double> C = make_call<double>(model, g, Ftip);
   const bool ftip = any_nonzero(Ftip);
@@ -617,12 +596,9 @@ int mp_id_regressor_cpu_f64(const mp_model* model, const double* q, const double
 int mp_id_regressor_normal_cpu_f64(const mp_model* model, const double* q, const double* qd, const double* qdd, const double* rhs,
                                    int64_t rows, const double* g, const double* Ftip, double* A, double* b, double* rr, int nthreads) {
   const char* fn = "mp_id_regressor_normal_cpu_f64";
-  if (int rc = regressor_cpu_check(fn, model, rows)) return rc;
-  if (!b || !rr || (rows > 0 && (!q || !qd || !qdd || !rhs))) {
-    char msg[96];
-    std::snprintf(msg, sizeof msg, "%s: null pointer", fn);
-    return fail(msg);
-  }
+  if (int rc = mp_small_model(fn, model)) return rc;
+  if (int rc = mp_regressor_check(fn, rows)) return rc;
+  REQUIRE(b && rr && (rows == 0 || (q && qd && qdd && rhs)), "%s: null pointer", fn);
   const MpModel<double>& M = model->d;
   const int W = MP_REG_P * M.n;
   const int64_t chunks = std::min<int64_t>(256, (rows + 63) / 64), per = chunks ? (rows + chunks - 1) / chunks : 0;
@@ -672,19 +648,11 @@ int mp_fd_trajectory_vjp_cpu_f64(const mp_model* model, const double* theta0, co
                                  const double* gvel, const double* gacc, double* gtheta0, double* gdtheta0, double* gtaumat,
                                  int nthreads) {
   const char* fn = "mp_fd_trajectory_vjp_cpu_f64";
-  char msg[192];
-  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
-  if (model->big) {
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (B < 0 || Nt < 0) { std::snprintf(msg, sizeof msg, "%s: negative B or N", fn); return fail(msg); }
-  if (intRes < 1) { std::snprintf(msg, sizeof msg, "%s: intRes must be >= 1 (got %d)", fn, intRes); return fail(msg); }
+  if (int rc = mp_small_model(fn, model)) return rc;
+  REQUIRE(B >= 0 && Nt >= 0, "%s: negative B or N", fn);
+  REQUIRE(intRes >= 1, "%s: intRes must be >= 1 (got %d)", fn, intRes);
   if (B == 0 || Nt == 0) return MP_OK;
-  if (!theta0 || !dtheta0 || !taumat || !gtheta0 || !gdtheta0 || !gtaumat) {
-    std::snprintf(msg, sizeof msg, "%s: null pointer", fn);
-    return fail(msg);
-  }
+  REQUIRE(theta0 && dtheta0 && taumat && gtheta0 && gdtheta0 && gtaumat, "%s: null pointer", fn);
   const MpModel<double>& M = model->d;
   const MpCall<double> C = make_call<double>(model, g, nullptr);
   const double h = dt / intRes;
@@ -709,21 +677,10 @@ int mp_fd_trajectory_vjp_cpu_f64(const mp_model* model, const double* theta0, co
 // blocks of its trajectory itself (mp_fd_deriv_row over rows (pos[0:N-1], vel[0:N-1], tau[1:N])), each thread with its own workspace.
 static int ilqr_cpu_check(const char* fn, const mp_model* model, int64_t B, int64_t Nt, const double* wq, const double* wr,
                           const double* wf) {
-  char msg[192];
-  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
-  if (model->big) {
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (B < 0) { std::snprintf(msg, sizeof msg, "%s: negative B", fn); return fail(msg); }
-  if (Nt < 2) { std::snprintf(msg, sizeof msg, "%s: N must be >= 2 (got %lld)", fn, (long long)Nt); return fail(msg); }
-  if (!wq || !wr || !wf) { std::snprintf(msg, sizeof msg, "%s: null weight vector", fn); return fail(msg); }
-  for (int j = 0; j < 2 * model->d.n; ++j)
-    if (!std::isfinite(wq[j]) || !std::isfinite(wf[j]) || !std::isfinite(wr[j / 2])) {
-      std::snprintf(msg, sizeof msg, "%s: non-finite weight", fn);
-      return fail(msg);
-    }
-  return MP_OK;
+  if (int rc = mp_small_model(fn, model)) return rc;
+  REQUIRE(B >= 0, "%s: negative B", fn);
+  REQUIRE(Nt >= 2, "%s: N must be >= 2 (got %lld)", fn, (long long)Nt);
+  return mp_ilqr_weights_check(fn, model->d.n, wq, wr, wf);
 }
 int mp_ilqr_backward_cpu_f64(const mp_model* model, const double* pos, const double* vel, const double* taumat, const double* xref,
                              const double* wq, const double* wr, const double* wf, const double* reg, int64_t B, int64_t Nt,
@@ -731,11 +688,7 @@ int mp_ilqr_backward_cpu_f64(const mp_model* model, const double* pos, const dou
   const char* fn = "mp_ilqr_backward_cpu_f64";
   if (int rc = ilqr_cpu_check(fn, model, B, Nt, wq, wr, wf)) return rc;
   if (B == 0) return MP_OK;
-  if (!pos || !vel || !taumat || !xref || !reg || !K || !k || !dV || !status) {
-    char msg[96];
-    std::snprintf(msg, sizeof msg, "%s: null pointer", fn);
-    return fail(msg);
-  }
+  REQUIRE(pos && vel && taumat && xref && reg && K && k && dV && status, "%s: null pointer", fn);
   const MpModel<double>& M = model->d;
   const MpCall<double> C = make_call<double>(model, g, nullptr);
   // MANIPULAPY_ILQR_CPU_FORM=coop (read at every call): the cooperative form of the device kernel, lane by lane, instead of the
@@ -772,18 +725,13 @@ int mp_ilqr_rollout_cpu_f64(const mp_model* model, const double* theta0, const d
                             double dt, double* cost, double* opos, double* ovel, double* otau, int nthreads) {
   const char* fn = "mp_ilqr_rollout_cpu_f64";
   if (int rc = ilqr_cpu_check(fn, model, B, Nt, wq, wr, wf)) return rc;
-  char msg[160];
-  if (A < 0) { std::snprintf(msg, sizeof msg, "%s: negative A", fn); return fail(msg); }
+  REQUIRE(A >= 0, "%s: negative A", fn);
   if (A == 0 || B == 0) return MP_OK;
-  if (!theta0 || !dtheta0 || !taumat || !alpha || !xref || !cost) { std::snprintf(msg, sizeof msg, "%s: null pointer", fn); return fail(msg); }
-  if ((K != nullptr) != (k != nullptr) || (K && (!pos || !vel))) {
-    std::snprintf(msg, sizeof msg, "%s: K and k must both be given, with the nominal pos and vel, or both be null", fn);
-    return fail(msg);
-  }
-  if ((opos != nullptr) != (ovel != nullptr) || (opos != nullptr) != (otau != nullptr)) {
-    std::snprintf(msg, sizeof msg, "%s: the three row outputs must all be given or all be null", fn);
-    return fail(msg);
-  }
+  REQUIRE(theta0 && dtheta0 && taumat && alpha && xref && cost, "%s: null pointer", fn);
+  REQUIRE((K != nullptr) == (k != nullptr) && (!K || (pos && vel)),
+          "%s: K and k must both be given, with the nominal pos and vel, or both be null", fn);
+  REQUIRE((opos != nullptr) == (ovel != nullptr) && (opos != nullptr) == (otau != nullptr),
+          "%s: the three row outputs must all be given or all be null", fn);
   const MpModel<double>& M = model->d;
   const MpCall<double> C = make_call<double>(model, g, nullptr);
   MP_CPU_DISPATCH(M.n, {
@@ -799,51 +747,16 @@ int mp_ilqr_rollout_cpu_f64(const mp_model* model, const double* theta0, const d
   return MP_OK;
 }
 // time-optimal path parameterisation (mp_toppra.h): the kernels' per-row and per-path code over batch-major host arrays
-static int toppra_cpu_limits(const char* fn, int n, const double* vlim, const double* tlim, const double* alim, MpToppraVmax* V,
-                             MpToppraLimits* L) {
-  char msg[192];
-  if (V) std::memset(V, 0, sizeof *V);
-  std::memset(L, 0, sizeof *L);
-  for (int j = 0; j < n; ++j) {
-    if (V) {
-      if (!vlim) { std::snprintf(msg, sizeof msg, "%s: null velocity limits", fn); return fail(msg); }
-      if (!(std::isfinite(vlim[j]) && vlim[j] > 0.0)) {
-        std::snprintf(msg, sizeof msg, "%s: velocity limits must be finite and positive", fn);
-        return fail(msg);
-      }
-      V->v[j] = vlim[j];
-    }
-    L->tau_lo[j] = tlim ? tlim[2 * j] : -INFINITY;
-    L->tau_hi[j] = tlim ? tlim[2 * j + 1] : INFINITY;
-    L->amax[j] = alim ? alim[j] : INFINITY;
-    if (std::isnan(L->tau_lo[j]) || std::isnan(L->tau_hi[j]) || !(L->tau_lo[j] <= L->tau_hi[j])) {
-      std::snprintf(msg, sizeof msg, "%s: torque limits must be ordered pairs (lo <= hi, either may be infinite)", fn);
-      return fail(msg);
-    }
-    if (!(L->amax[j] > 0.0)) { std::snprintf(msg, sizeof msg, "%s: acceleration limits must be positive", fn); return fail(msg); }
-  }
-  return MP_OK;
-}
-static int toppra_cpu_model(const char* fn, const mp_model* model) {
-  char msg[192];
-  if (!model) { std::snprintf(msg, sizeof msg, "%s: null model", fn); return fail(msg); }
-  if (model->big) {
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  return MP_OK;
-}
 int mp_path_dynamics_cpu_f64(const mp_model* model, const double* q, const double* dq, const double* ddq, int64_t rows,
                              const double* velocity_limits, const double* g, const double* Ftip, double* a, double* b, double* c,
                              double* xbar, int nthreads) {
   const char* fn = "mp_path_dynamics_cpu_f64";
-  if (int rc = toppra_cpu_model(fn, model)) return rc;
-  if (rows < 0) return fail("mp_path_dynamics_cpu_f64: negative row count");
+  if (int rc = mp_small_model(fn, model)) return rc;
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
   MpToppraVmax V;
-  MpToppraLimits L;
-  if (int rc = toppra_cpu_limits(fn, model->d.n, velocity_limits, nullptr, nullptr, &V, &L)) return rc;
+  if (int rc = mp_toppra_vmax_check(fn, model->d.n, velocity_limits, &V)) return rc;
   if (rows == 0) return MP_OK;
-  if (!q || !dq || !ddq || !a || !b || !c || !xbar) return fail("mp_path_dynamics_cpu_f64: null pointer");
+  REQUIRE(q && dq && ddq && a && b && c && xbar, "%s: null pointer", fn);
   const MpModel<double>& M = model->d;
   const MpCall<double> C = make_call<double>(model, g, Ftip);
   const bool ftip = any_nonzero(Ftip);
@@ -863,25 +776,16 @@ int mp_toppra_sweep_cpu_f64(int n, const double* a, const double* b, const doubl
                             const double* sd_end, int64_t B, int64_t Nt, double* K, double* x, double* u, double* t, double* duration,
                             int32_t* status, double* qd, double* qdd, double* tau, int nthreads) {
   const char* fn = "mp_toppra_sweep_cpu_f64";
-  char msg[160];
-  if (n < 1 || n > MP_MAX_DOF) { std::snprintf(msg, sizeof msg, "%s: n must be 1..%d", fn, MP_MAX_DOF); return mp_set_error(MP_ERR_UNSUPPORTED, msg); }
-  if (B < 0) { std::snprintf(msg, sizeof msg, "%s: negative B", fn); return fail(msg); }
-  if (Nt < 3) { std::snprintf(msg, sizeof msg, "%s: N must be >= 3 (got %lld)", fn, (long long)Nt); return fail(msg); }
+  if (n < 1 || n > MP_MAX_DOF) return mp_fail(MP_ERR_UNSUPPORTED, "%s: n must be 1..%d", fn, MP_MAX_DOF);
+  REQUIRE(B >= 0, "%s: negative B", fn);
+  REQUIRE(Nt >= 3, "%s: N must be >= 3 (got %lld)", fn, (long long)Nt);
   MpToppraLimits L;
-  if (int rc = toppra_cpu_limits(fn, n, nullptr, torque_limits, acceleration_limits, nullptr, &L)) return rc;
+  if (int rc = mp_toppra_limits_check(fn, n, torque_limits, acceleration_limits, &L)) return rc;
   if (B == 0) return MP_OK;
-  if (!a || !b || !c || !xbar || !sd_start || !sd_end || !K || !x || !u || !t || !duration || !status) {
-    std::snprintf(msg, sizeof msg, "%s: null pointer", fn);
-    return fail(msg);
-  }
-  if ((qd != nullptr) != (qdd != nullptr) || (qd != nullptr) != (tau != nullptr)) {
-    std::snprintf(msg, sizeof msg, "%s: the three row outputs must all be given or all be null", fn);
-    return fail(msg);
-  }
-  if ((acceleration_limits || tau) && (!dq || !ddq)) {
-    std::snprintf(msg, sizeof msg, "%s: acceleration limits and the row outputs need the path derivatives dq and ddq", fn);
-    return fail(msg);
-  }
+  REQUIRE(a && b && c && xbar && sd_start && sd_end && K && x && u && t && duration && status, "%s: null pointer", fn);
+  REQUIRE((qd != nullptr) == (qdd != nullptr) && (qd != nullptr) == (tau != nullptr),
+          "%s: the three row outputs must all be given or all be null", fn);
+  REQUIRE(!(acceleration_limits || tau) || (dq && ddq), "%s: acceleration limits and the row outputs need the path derivatives dq and ddq", fn);
   const bool acc = acceleration_limits != nullptr;
   MP_CPU_DISPATCH(n, {
     parallel_for(B, 1, nthreads, [&](int64_t lo, int64_t hi) {
@@ -906,15 +810,15 @@ int mp_toppra_cpu_f64(const mp_model* model, const double* q, const double* dq, 
                       int64_t B, int64_t Nt, const double* g, const double* Ftip, double* K, double* x, double* u, double* t,
                       double* duration, int32_t* status, double* qd, double* qdd, double* tau, int nthreads) {
   const char* fn = "mp_toppra_cpu_f64";
-  if (int rc = toppra_cpu_model(fn, model)) return rc;
-  if (B < 0) return fail("mp_toppra_cpu_f64: negative B");
-  if (Nt < 3) { char msg[96]; std::snprintf(msg, sizeof msg, "%s: N must be >= 3 (got %lld)", fn, (long long)Nt); return fail(msg); }
+  if (int rc = mp_small_model(fn, model)) return rc;
+  REQUIRE(B >= 0, "%s: negative B", fn);
+  REQUIRE(Nt >= 3, "%s: N must be >= 3 (got %lld)", fn, (long long)Nt);
   const int n = model->d.n;
   std::vector<double> co;
   try {
     co.resize((size_t)B * Nt * (3 * n + 1));
   } catch (...) {
-    return mp_set_error(MP_ERR_INVALID, "mp_toppra_cpu_f64: out of memory for the coefficients");
+    return mp_fail(MP_ERR_INVALID, "%s: out of memory for the coefficients", fn);
   }
   const size_t blk = (size_t)B * Nt * n;
   double *a = co.data(), *b = a + blk, *c = b + blk, *xb = c + blk;
@@ -938,27 +842,20 @@ int mp_inverse_kinematics_cpu_f64(const mp_model* model, const double* T_desired
                                   double step_cap, double weight_orientation, double weight_position, int adaptive_tuning,
                                   int backtracking, uint32_t seed, double* theta, int32_t* success, int32_t* iterations,
                                   int32_t* restarts, int nthreads) {
-  if (!model) return fail("mp_inverse_kinematics_cpu_f64: null model");
-  if (B < 0) return fail("mp_inverse_kinematics_cpu_f64: negative problem count");
+  const char* fn = "mp_inverse_kinematics_cpu_f64";
+  REQUIRE(model, "%s: null model", fn);
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
-  if (!T_desired || !theta0 || !theta || !success || !iterations || !restarts) return fail("mp_inverse_kinematics_cpu_f64: null pointer");
-  if (max_iterations < 1) return fail("mp_inverse_kinematics_cpu_f64: max_iterations must be at least 1");
-  if (!(eomg > 0 && ev > 0 && damping >= 0 && step_cap > 0))
-    return fail("mp_inverse_kinematics_cpu_f64: eomg, ev, step_cap must be positive and damping non-negative");
-  auto fill = [&](auto& P, int cap) -> bool {
-    P.eomg = eomg; P.ev = ev; P.damping = damping; P.step_cap = step_cap; P.w_o = weight_orientation; P.w_p = weight_position;
-    P.max_iterations = max_iterations; P.seed = seed;
-    P.adaptive_tuning = adaptive_tuning ? 1 : 0; P.backtracking = backtracking ? 1 : 0;
-    for (int j = 0; j < cap; ++j) {
-      P.lo[j] = (j < model->d.n && joint_limits) ? joint_limits[2 * j] : -HUGE_VAL;
-      P.hi[j] = (j < model->d.n && joint_limits) ? joint_limits[2 * j + 1] : HUGE_VAL;
-      if (P.lo[j] > P.hi[j]) return false;
-    }
-    return true;
+  REQUIRE(T_desired && theta0 && theta && success && iterations && restarts, "%s: null pointer", fn);
+  REQUIRE(max_iterations >= 1, "%s: max_iterations must be at least 1", fn);
+  auto pack = [&](auto* P) {  // (the twin's words for crossed limits name no joint)
+    const int rc = mp_ik_pack(fn, model->d.n, joint_limits, eomg, ev, max_iterations, damping, step_cap, weight_orientation, weight_position,
+                              adaptive_tuning, backtracking, seed, P);
+    return rc < 0 ? mp_fail(MP_ERR_INVALID, "%s: a joint has its lower limit above its upper limit", fn) : rc;
   };
   if (model->big) {  // 9..32 joints: the body of k_dyn_ik (run-time-n kinematics of csrc/mp_dyn.h under the same iteration)
     MpIkBigParams PB;
-    if (!fill(PB, MP_BIG_DOF)) return fail("mp_inverse_kinematics_cpu_f64: a joint has its lower limit above its upper limit");
+    if (int rc = pack(&PB)) return rc;
     const MpBigModel<double>& MB = model->bd;
     const int n = MB.n;
     auto rows_of = [&](auto cap_tag) {   // per-problem arrays of 16 entries for 9..16 joints, 32 beyond (as the kernels: MP_DISPATCH_CAP)
@@ -982,7 +879,7 @@ int mp_inverse_kinematics_cpu_f64(const mp_model* model, const double* T_desired
     return MP_OK;
   }
   MpIkParams P;
-  if (!fill(P, MP_MAX_DOF)) return fail("mp_inverse_kinematics_cpu_f64: a joint has its lower limit above its upper limit");
+  if (int rc = pack(&P)) return rc;
   const MpModel<double>& M = model->d;
   // the body of k_ik (csrc/mp_kernels.hip) per problem: begin, iterate until the iteration reports done
   MP_CPU_DISPATCH(M.n, {
@@ -1005,10 +902,10 @@ int mp_inverse_kinematics_cpu_f64(const mp_model* model, const double* T_desired
 
 int mp_pd_regulation_cpu_f64(const mp_model* model, const double* theta0, const double* theta_des, const double* Kp, const double* Kd,
                              int64_t K, const double* g, double dt, int steps, double* errors, int32_t* count, int nthreads) {
-  if (!model) return fail("mp_pd_regulation_cpu_f64: null model");
-  if (K < 0 || steps < 0) return fail("mp_pd_regulation_cpu_f64: negative run or step count");
+  REQUIRE(model, "mp_pd_regulation_cpu_f64: null model");
+  REQUIRE(K >= 0 && steps >= 0, "mp_pd_regulation_cpu_f64: negative run or step count");
   if (K == 0) return MP_OK;
-  if (!theta0 || !theta_des || !Kp || !Kd || !count || (!errors && steps > 0)) return fail("mp_pd_regulation_cpu_f64: null pointer");
+  REQUIRE(theta0 && theta_des && Kp && Kd && count && (errors || steps == 0), "mp_pd_regulation_cpu_f64: null pointer");
   const MpCall<double> C = make_call<double>(model, g, nullptr);
   const int n = model->d.n;
   if (model->big) {  // the body of k_dyn_pd_regulation
@@ -1034,10 +931,10 @@ int mp_pd_regulation_cpu_f64(const mp_model* model, const double* theta0, const 
 
 int mp_cartesian_trajectory_cpu_f32(const double* Xstart, const double* Xend, int64_t B, int64_t N, double Tf, int method,
                                     float* pos, float* vel, float* acc, float* orient, int nthreads) {
-  if (B < 0 || N < 0) return fail("mp_cartesian_trajectory_cpu_f32: negative count");
+  REQUIRE(B >= 0 && N >= 0, "mp_cartesian_trajectory_cpu_f32: negative count");
   if (B == 0 || N == 0) return MP_OK;
-  if (N < 2) return fail("mp_cartesian_trajectory_cpu_f32: N must be >= 2");
-  if (!Xstart || !Xend || !pos || !vel || !acc || !orient) return fail("mp_cartesian_trajectory_cpu_f32: null pointer");
+  REQUIRE(N >= 2, "mp_cartesian_trajectory_cpu_f32: N must be >= 2");
+  REQUIRE(Xstart && Xend && pos && vel && acc && orient, "mp_cartesian_trajectory_cpu_f32: null pointer");
   parallel_for(B * N, 512, nthreads, [&](int64_t lo, int64_t hi) {
     for (int64_t r = lo; r < hi; ++r) {
       const int64_t b = r / N, i = r - b * N;
@@ -1054,41 +951,29 @@ int mp_cartesian_trajectory_cpu_f32(const double* Xstart, const double* Xend, in
 }
 
 // ---- sphere-model collision (mp_collision.h): the tables' checks, the handle, and the kernel's per-row code over host rows
-static int col_fail(const char* fmt, const char* fn, long a = 0, double b = 0.0) {
-  char msg[256];
-  std::snprintf(msg, sizeof msg, fmt, fn, a, b);
-  return fail(msg);
-}
-
 int mp_collision_create(const mp_model* model, int S, const int32_t* link, const double* centre, const double* radius, int P,
                         const int32_t* pairs, mp_collision** out) {
   const char* fn = "mp_collision_create";
-  if (!out) return col_fail("%s: null output", fn);
+  REQUIRE(out, "%s: null output", fn);
   *out = nullptr;
-  if (!model) return col_fail("%s: null model", fn);
-  if (model->big) {
-    char msg[192];
-    std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, model->d.n);
-    return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-  }
-  if (S < 1 || S > MP_COL_MAX_SPHERES) return col_fail("%s: %ld spheres, outside 1..64", fn, S);
-  if (P < 0) return col_fail("%s: negative pair count", fn);
-  if (!link || !centre || !radius || (P > 0 && !pairs)) return col_fail("%s: null table", fn);
+  if (int rc = mp_small_model(fn, model)) return rc;
+  REQUIRE(S >= 1 && S <= MP_COL_MAX_SPHERES, "%s: %d spheres, outside 1..64", fn, S);
+  REQUIRE(P >= 0, "%s: negative pair count", fn);
+  REQUIRE(link && centre && radius && (P == 0 || pairs), "%s: null table", fn);
   const MpModel<double>& M = model->d;
   const int n = M.n;
   for (int s = 0; s < S; ++s) {
-    if (link[s] < 0 || link[s] > n) return col_fail("%s: sphere %ld: link outside 0..n", fn, s);
-    if (!(radius[s] > 0.0) || !std::isfinite(radius[s])) return col_fail("%s: sphere %ld: radius %g is not positive and finite", fn, s, radius[s]);
-    for (int k = 0; k < 3; ++k)
-      if (!std::isfinite(centre[3 * s + k])) return col_fail("%s: sphere %ld: non-finite centre", fn, s);
+    REQUIRE(link[s] >= 0 && link[s] <= n, "%s: sphere %d: link outside 0..n", fn, s);
+    REQUIRE(radius[s] > 0.0 && std::isfinite(radius[s]), "%s: sphere %d: radius %g is not positive and finite", fn, s, radius[s]);
+    for (int k = 0; k < 3; ++k) REQUIRE(std::isfinite(centre[3 * s + k]), "%s: sphere %d: non-finite centre", fn, s);
   }
   for (int k = 0; k < P; ++k) {
     const int a = pairs[2 * k], b = pairs[2 * k + 1];
-    if (a < 0 || a >= S || b < 0 || b >= S) return col_fail("%s: pair %ld: sphere index outside 0..S-1", fn, k);
-    if (a == b) return col_fail("%s: pair %ld: a sphere paired with itself", fn, k);
+    REQUIRE(a >= 0 && a < S && b >= 0 && b < S, "%s: pair %d: sphere index outside 0..S-1", fn, k);
+    REQUIRE(a != b, "%s: pair %d: a sphere paired with itself", fn, k);
   }
   mp_collision* h = new (std::nothrow) mp_collision;
-  if (!h) return col_fail("%s: out of host memory", fn);
+  REQUIRE(h, "%s: out of host memory", fn);
   h->n = n;
   // the link frames at the home configuration
   double R[MP_MAX_DOF][9], p[MP_MAX_DOF][3];
@@ -1101,7 +986,7 @@ int mp_collision_create(const mp_model* model, int S, const int32_t* link, const
     } break;
     MP_COL_HOME(1) MP_COL_HOME(2) MP_COL_HOME(3) MP_COL_HOME(4) MP_COL_HOME(5) MP_COL_HOME(6) MP_COL_HOME(7) MP_COL_HOME(8)
 #undef MP_COL_HOME
-    default: delete h; return col_fail("%s: dof outside 1..8", fn);
+    default: delete h; return mp_fail(MP_ERR_INVALID, "%s: dof outside 1..8", fn);
   }
   MpColSpheres& T = h->sph;
   std::memset(&T, 0, sizeof T);
@@ -1163,28 +1048,23 @@ int mp_collision_destroy(mp_collision* h) {
 }  // extern "C"
 
 int mp_collision_pack_world(const char* fn, int O, const int32_t* kind, const double* params, std::vector<MpColObstacle>* out) {
-  if (O < 0) return col_fail("%s: negative obstacle count", fn);
-  if (O > 0 && (!kind || !params)) return col_fail("%s: null obstacle table", fn);
+  REQUIRE(O >= 0, "%s: negative obstacle count", fn);
+  REQUIRE(O == 0 || (kind && params), "%s: null obstacle table", fn);
   std::vector<MpColObstacle> w((size_t)O);
   for (int o = 0; o < O; ++o) {
     const double* p = params + 16 * (size_t)o;
-    int used = 0;
-    if (kind[o] == MP_OBSTACLE_SPHERE) used = 4;
-    else if (kind[o] == MP_OBSTACLE_CAPSULE) used = 7;
-    else if (kind[o] == MP_OBSTACLE_BOX) used = 15;
-    else return col_fail("%s: obstacle %ld: unknown kind", fn, o);
-    for (int k = 0; k < used; ++k)
-      if (!std::isfinite(p[k])) return col_fail("%s: obstacle %ld: non-finite parameter", fn, o);
-    if (kind[o] == MP_OBSTACLE_SPHERE && p[3] < 0.0) return col_fail("%s: obstacle %ld: negative radius", fn, o);
-    if (kind[o] == MP_OBSTACLE_CAPSULE && p[6] < 0.0) return col_fail("%s: obstacle %ld: negative radius", fn, o);
+    const int used = kind[o] == MP_OBSTACLE_SPHERE ? 4 : kind[o] == MP_OBSTACLE_CAPSULE ? 7 : kind[o] == MP_OBSTACLE_BOX ? 15 : 0;
+    REQUIRE(used, "%s: obstacle %d: unknown kind", fn, o);
+    for (int k = 0; k < used; ++k) REQUIRE(std::isfinite(p[k]), "%s: obstacle %d: non-finite parameter", fn, o);
+    REQUIRE(kind[o] != MP_OBSTACLE_SPHERE || !(p[3] < 0.0), "%s: obstacle %d: negative radius", fn, o);
+    REQUIRE(kind[o] != MP_OBSTACLE_CAPSULE || !(p[6] < 0.0), "%s: obstacle %d: negative radius", fn, o);
     if (kind[o] == MP_OBSTACLE_BOX) {
-      for (int k = 12; k < 15; ++k)
-        if (p[k] < 0.0) return col_fail("%s: obstacle %ld: negative half-extent", fn, o);
+      for (int k = 12; k < 15; ++k) REQUIRE(!(p[k] < 0.0), "%s: obstacle %d: negative half-extent", fn, o);
       for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 3; ++b) {
           double dot = 0.0;
           for (int k = 0; k < 3; ++k) dot += p[3 + 3 * k + a] * p[3 + 3 * k + b];
-          if (std::fabs(dot - (a == b ? 1.0 : 0.0)) > 1e-9) return col_fail("%s: obstacle %ld: box rotation is not orthonormal to 1e-9", fn, o);
+          REQUIRE(!(std::fabs(dot - (a == b ? 1.0 : 0.0)) > 1e-9), "%s: obstacle %d: box rotation is not orthonormal to 1e-9", fn, o);
         }
     }
     MpColObstacle& ob = w[(size_t)o];
@@ -1197,20 +1077,15 @@ int mp_collision_pack_world(const char* fn, int O, const int32_t* kind, const do
 }
 
 // ---- what the four twins below share: the first checks, and the handle's host tables as the per-row code reads them
-static int col_too_many(const char* fn, int n) {
-  char msg[192];
-  std::snprintf(msg, sizeof msg, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, n);
-  return mp_set_error(MP_ERR_UNSUPPORTED, msg);
-}
 static int col_twin_enter(const char* fn, const mp_model* model, const mp_collision* h) {
-  if (!model || !h) return col_fail("%s: null model or collision handle", fn);
-  if (model->big) return col_too_many(fn, model->d.n);
-  if (h->n != model->d.n) return col_fail("%s: the collision handle was made for a model of %ld joints", fn, h->n);
+  REQUIRE(model && h, "%s: null model or collision handle", fn);
+  REQUIRE_SMALL(fn);
+  REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints", fn, h->n);
   return MP_OK;
 }
 static int col_joint_count(const char* fn, int n) {  // the n of the two workspace sizes
-  if (n < 1) return col_fail("%s: joint count %ld below 1", fn, n);
-  return n > MP_MAX_DOF ? col_too_many(fn, n) : MP_OK;
+  REQUIRE(n >= 1, "%s: joint count %d below 1", fn, n);
+  return n > MP_MAX_DOF ? mp_too_many_joints(fn, n) : MP_OK;
 }
 typedef MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*> MpColTablesHost;
 static MpColTablesHost col_host_tables(const mp_collision* h, MpColWorld& hdr) {  // hdr: the caller's, the tables point at it
@@ -1225,13 +1100,13 @@ int mp_collision_cpu_f64(const mp_model* model, const mp_collision* h, const dou
                          double* grad_dist_self, double* cost, double* grad, int nthreads) {
   const char* fn = "mp_collision_cpu_f64";
   if (int rc = col_twin_enter(fn, model, h)) return rc;
-  if (!(eps_world > 0.0) || !(eps_self > 0.0) || !std::isfinite(eps_world) || !std::isfinite(eps_self))
-    return col_fail("%s: eps_world and eps_self must be positive and finite", fn);
-  if (rows < 0) return col_fail("%s: negative row count", fn);
+  REQUIRE(eps_world > 0.0 && eps_self > 0.0 && std::isfinite(eps_world) && std::isfinite(eps_self),
+          "%s: eps_world and eps_self must be positive and finite", fn);
+  REQUIRE(rows >= 0, "%s: negative row count", fn);
   if (rows == 0) return MP_OK;
-  if (!q) return col_fail("%s: null pointer", fn);
-  if (!dist_world && !arg_world && !dist_self && !arg_self && !grad_dist_world && !grad_dist_self && !cost && !grad)
-    return col_fail("%s: at least one output is required", fn);
+  REQUIRE(q, "%s: null pointer", fn);
+  REQUIRE(dist_world || arg_world || dist_self || arg_self || grad_dist_world || grad_dist_self || cost || grad,
+          "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);
@@ -1253,9 +1128,9 @@ int mp_collision_cpu_f64(const mp_model* model, const mp_collision* h, const dou
 
 // ---- continuous collision checking of joint-space edges (mp_collision.h, mp_collision_edge_*)
 int mp_collision_edges_check(const char* fn, double margin, double tol, int max_steps) {
-  if (!std::isfinite(margin)) return col_fail("%s: margin must be finite", fn);
-  if (!(tol > 0.0) || !std::isfinite(tol)) return col_fail("%s: tol must be positive and finite", fn);
-  if (max_steps < 1 || max_steps > MP_COL_EDGE_MAX_STEPS) return col_fail("%s: max_steps %ld outside 1..65536", fn, max_steps);
+  REQUIRE(std::isfinite(margin), "%s: margin must be finite", fn);
+  REQUIRE(tol > 0.0 && std::isfinite(tol), "%s: tol must be positive and finite", fn);
+  REQUIRE(max_steps >= 1 && max_steps <= MP_COL_EDGE_MAX_STEPS, "%s: max_steps %d outside 1..65536", fn, max_steps);
   return MP_OK;
 }
 
@@ -1263,7 +1138,7 @@ extern "C" {
 
 int mp_collision_motion_bounds(const mp_collision* h, double* rho) {
   const char* fn = "mp_collision_motion_bounds";
-  if (!h || !rho) return col_fail("%s: null pointer", fn);
+  REQUIRE(h && rho, "%s: null pointer", fn);
   for (int j = 0; j < h->n; ++j)
     for (int k = 0; k <= h->n; ++k) rho[j * (h->n + 1) + k] = h->sph.rho[j][k];
   return MP_OK;
@@ -1275,10 +1150,10 @@ int mp_collision_edges_cpu_f64(const mp_model* model, const mp_collision* h, con
   const char* fn = "mp_collision_edges_cpu_f64";
   if (int rc = col_twin_enter(fn, model, h)) return rc;
   if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
-  if (edges < 0) return col_fail("%s: negative edge count", fn);
+  REQUIRE(edges >= 0, "%s: negative edge count", fn);
   if (edges == 0) return MP_OK;
-  if (!q_from || !q_to) return col_fail("%s: null pointer", fn);
-  if (!status && !t && !steps && !clearance && !witness) return col_fail("%s: at least one output is required", fn);
+  REQUIRE(q_from && q_to, "%s: null pointer", fn);
+  REQUIRE(status || t || steps || clearance || witness, "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);
@@ -1297,20 +1172,19 @@ int mp_collision_edges_cpu_f64(const mp_model* model, const mp_collision* h, con
 int mp_rrt_connect_check(const char* fn, int n, const double* lo, const double* hi, uint32_t seed, double step, double min_advance,
                          int max_iters, int max_nodes, int max_waypoints, double margin, double tol, int max_steps, MpRrtParams* out) {
   if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
-  if (!lo || !hi) return col_fail("%s: null sampling box", fn);
+  REQUIRE(lo && hi, "%s: null sampling box", fn);
   MpRrtParams P;
   std::memset(&P, 0, sizeof P);
   for (int j = 0; j < n; ++j) {
-    if (!std::isfinite(lo[j]) || !std::isfinite(hi[j]) || !(lo[j] <= hi[j]))
-      return col_fail("%s: joint %ld: the sampling box must be finite with lo <= hi", fn, j);
+    REQUIRE(std::isfinite(lo[j]) && std::isfinite(hi[j]) && lo[j] <= hi[j], "%s: joint %d: the sampling box must be finite with lo <= hi", fn, j);
     P.lo[j] = lo[j];
     P.hi[j] = hi[j];
   }
-  if (!(step > 0.0) || !std::isfinite(step)) return col_fail("%s: step must be positive and finite", fn);
-  if (!(min_advance >= 0.0) || !std::isfinite(min_advance)) return col_fail("%s: min_advance must be non-negative and finite", fn);
-  if (max_iters < 0) return col_fail("%s: negative max_iters", fn);
-  if (max_nodes < 2 || max_nodes > MP_RRT_MAX_NODES) return col_fail("%s: max_nodes %ld outside 2..65536", fn, max_nodes);
-  if (max_waypoints < 2) return col_fail("%s: max_waypoints %ld below 2", fn, max_waypoints);
+  REQUIRE(step > 0.0 && std::isfinite(step), "%s: step must be positive and finite", fn);
+  REQUIRE(min_advance >= 0.0 && std::isfinite(min_advance), "%s: min_advance must be non-negative and finite", fn);
+  REQUIRE(max_iters >= 0, "%s: negative max_iters", fn);
+  REQUIRE(max_nodes >= 2 && max_nodes <= MP_RRT_MAX_NODES, "%s: max_nodes %d outside 2..65536", fn, max_nodes);
+  REQUIRE(max_waypoints >= 2, "%s: max_waypoints %d below 2", fn, max_waypoints);
   P.step = step; P.min_advance = min_advance;
   P.edge = {margin, tol, max_steps, 0};
   P.seed = seed; P.max_iters = max_iters; P.max_nodes = max_nodes; P.max_waypoints = max_waypoints;
@@ -1323,8 +1197,8 @@ extern "C" {
 int64_t mp_rrt_connect_workspace_bytes(int n, int max_nodes, int blocks) {
   const char* fn = "mp_rrt_connect_workspace_bytes";
   if (int rc = col_joint_count(fn, n)) return -(int64_t)rc;
-  if (max_nodes < 2 || max_nodes > MP_RRT_MAX_NODES) return -(int64_t)col_fail("%s: max_nodes %ld outside 2..65536", fn, max_nodes);
-  if (blocks < 1) return -(int64_t)col_fail("%s: block count %ld below 1", fn, blocks);
+  if (max_nodes < 2 || max_nodes > MP_RRT_MAX_NODES) return -(int64_t)mp_fail(MP_ERR_INVALID, "%s: max_nodes %d outside 2..65536", fn, max_nodes);
+  if (blocks < 1) return -(int64_t)mp_fail(MP_ERR_INVALID, "%s: block count %d below 1", fn, blocks);
   return (int64_t)blocks * 64 * 2 * (int64_t)max_nodes * (8 * (int64_t)n + 4);
 }
 
@@ -1338,10 +1212,10 @@ int mp_rrt_connect_cpu_f64(const mp_model* model, const mp_collision* h, const d
   if (int rc = mp_rrt_connect_check(fn, model->d.n, lo, hi, seed, step, min_advance, max_iters, max_nodes, max_waypoints, margin, tol,
                                     max_steps, &P))
     return rc;
-  if (B < 0) return col_fail("%s: negative problem count", fn);
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
-  if (!q_start || !q_goal) return col_fail("%s: null pointer", fn);
-  if (!status && !count && !waypoints && !iterations && !nodes && !evaluations) return col_fail("%s: at least one output is required", fn);
+  REQUIRE(q_start && q_goal, "%s: null pointer", fn);
+  REQUIRE(status || count || waypoints || iterations || nodes || evaluations, "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);
@@ -1363,10 +1237,10 @@ int mp_rrt_connect_cpu_f64(const mp_model* model, const mp_collision* h, const d
 int mp_path_shortcut_check(const char* fn, int64_t w_in, uint32_t seed, int max_iters, double min_gain, int max_waypoints, double margin,
                            double tol, int max_steps, MpShortcutParams* out) {
   if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
-  if (w_in < 1 || w_in > MP_SC_MAX_WAYPOINTS) return col_fail("%s: %ld input rows a path, outside 1..65536", fn, (long)w_in);
-  if (max_iters < 0) return col_fail("%s: negative max_iters", fn);
-  if (!(min_gain >= 0.0) || !std::isfinite(min_gain)) return col_fail("%s: min_gain must be non-negative and finite", fn);
-  if (max_waypoints < 2 || max_waypoints > MP_SC_MAX_WAYPOINTS) return col_fail("%s: max_waypoints %ld outside 2..65536", fn, max_waypoints);
+  REQUIRE(w_in >= 1 && w_in <= MP_SC_MAX_WAYPOINTS, "%s: %lld input rows a path, outside 1..65536", fn, (long long)w_in);
+  REQUIRE(max_iters >= 0, "%s: negative max_iters", fn);
+  REQUIRE(min_gain >= 0.0 && std::isfinite(min_gain), "%s: min_gain must be non-negative and finite", fn);
+  REQUIRE(max_waypoints >= 2 && max_waypoints <= MP_SC_MAX_WAYPOINTS, "%s: max_waypoints %d outside 2..65536", fn, max_waypoints);
   MpShortcutParams P;
   std::memset(&P, 0, sizeof P);
   P.edge = {margin, tol, max_steps, 0};
@@ -1382,8 +1256,8 @@ int64_t mp_path_shortcut_workspace_bytes(int n, int max_waypoints, int blocks) {
   const char* fn = "mp_path_shortcut_workspace_bytes";
   if (int rc = col_joint_count(fn, n)) return -(int64_t)rc;
   if (max_waypoints < 2 || max_waypoints > MP_SC_MAX_WAYPOINTS)
-    return -(int64_t)col_fail("%s: max_waypoints %ld outside 2..65536", fn, max_waypoints);
-  if (blocks < 1) return -(int64_t)col_fail("%s: block count %ld below 1", fn, blocks);
+    return -(int64_t)mp_fail(MP_ERR_INVALID, "%s: max_waypoints %d outside 2..65536", fn, max_waypoints);
+  if (blocks < 1) return -(int64_t)mp_fail(MP_ERR_INVALID, "%s: block count %d below 1", fn, blocks);
   return (int64_t)blocks * 64 * (int64_t)max_waypoints * (8 * (int64_t)n + 8);
 }
 
@@ -1395,11 +1269,11 @@ int mp_path_shortcut_cpu_f64(const mp_model* model, const mp_collision* h, const
   if (int rc = col_twin_enter(fn, model, h)) return rc;
   MpShortcutParams P;
   if (int rc = mp_path_shortcut_check(fn, W_in, seed, max_iters, min_gain, max_waypoints, margin, tol, max_steps, &P)) return rc;
-  if (B < 0) return col_fail("%s: negative problem count", fn);
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
-  if (!waypoints_in || !count_in) return col_fail("%s: null pointer", fn);
-  if (!status && !count && !waypoints && !length_in && !length_out && !iterations && !accepted && !skipped_full && !evaluations)
-    return col_fail("%s: at least one output is required", fn);
+  REQUIRE(waypoints_in && count_in, "%s: null pointer", fn);
+  REQUIRE(status || count || waypoints || length_in || length_out || iterations || accepted || skipped_full || evaluations,
+          "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);
@@ -1420,20 +1294,19 @@ int mp_path_shortcut_cpu_f64(const mp_model* model, const mp_collision* h, const
 int mp_goal_ik_check(const char* fn, int n, const double* lo, const double* hi, uint32_t seed, double eomg, double ev, double damping,
                      double step_cap, int max_iters, int max_attempts, double margin, double tol, MpGoalParams* out) {
   if (int rc = mp_collision_edges_check(fn, margin, tol, 1)) return rc;
-  if (!lo || !hi) return col_fail("%s: null joint box", fn);
+  REQUIRE(lo && hi, "%s: null joint box", fn);
   MpGoalParams P;
   std::memset(&P, 0, sizeof P);
   for (int j = 0; j < n; ++j) {
-    if (!std::isfinite(lo[j]) || !std::isfinite(hi[j]) || !(lo[j] <= hi[j]))
-      return col_fail("%s: joint %ld: the box must be finite with lo <= hi", fn, j);
+    REQUIRE(std::isfinite(lo[j]) && std::isfinite(hi[j]) && lo[j] <= hi[j], "%s: joint %d: the box must be finite with lo <= hi", fn, j);
     P.lo[j] = lo[j];
     P.hi[j] = hi[j];
   }
-  if (!(eomg > 0.0) || !std::isfinite(eomg) || !(ev > 0.0) || !std::isfinite(ev)) return col_fail("%s: eomg and ev must be positive and finite", fn);
-  if (!(damping > 0.0) || !std::isfinite(damping)) return col_fail("%s: damping must be positive and finite", fn);
-  if (!(step_cap > 0.0) || !std::isfinite(step_cap)) return col_fail("%s: step_cap must be positive and finite", fn);
-  if (max_iters < 0) return col_fail("%s: negative max_iters", fn);
-  if (max_attempts < 1 || max_attempts > MP_GOAL_MAX_ATTEMPTS) return col_fail("%s: max_attempts %ld outside 1..65536", fn, max_attempts);
+  REQUIRE(eomg > 0.0 && std::isfinite(eomg) && ev > 0.0 && std::isfinite(ev), "%s: eomg and ev must be positive and finite", fn);
+  REQUIRE(damping > 0.0 && std::isfinite(damping), "%s: damping must be positive and finite", fn);
+  REQUIRE(step_cap > 0.0 && std::isfinite(step_cap), "%s: step_cap must be positive and finite", fn);
+  REQUIRE(max_iters >= 0, "%s: negative max_iters", fn);
+  REQUIRE(max_attempts >= 1 && max_attempts <= MP_GOAL_MAX_ATTEMPTS, "%s: max_attempts %d outside 1..65536", fn, max_attempts);
   P.eomg = eomg; P.ev = ev; P.damping = damping; P.step_cap = step_cap;
   P.edge = {margin, tol, 1, 0};
   P.seed = seed; P.max_iters = max_iters; P.max_attempts = max_attempts;
@@ -1452,11 +1325,11 @@ int mp_goal_ik_cpu_f64(const mp_model* model, const mp_collision* h, const doubl
   MpGoalParams P;
   if (int rc = mp_goal_ik_check(fn, model->d.n, lo, hi, seed, eomg, ev, damping, step_cap, max_iters, max_attempts, margin, tol, &P))
     return rc;
-  if (B < 0) return col_fail("%s: negative problem count", fn);
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
-  if (!T_goal || !q_seed) return col_fail("%s: null pointer", fn);
-  if (!status && !q && !attempts && !iterations && !converged && !pose_error && !clearance && !witness)
-    return col_fail("%s: at least one output is required", fn);
+  REQUIRE(T_goal && q_seed, "%s: null pointer", fn);
+  REQUIRE(status || q || attempts || iterations || converged || pose_error || clearance || witness,
+          "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);

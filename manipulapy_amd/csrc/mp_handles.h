@@ -1,15 +1,38 @@
-// Handle layouts shared by the translation units that implement the C ABI (mp_capi.cpp, mp_cpu.cpp).
+// What the translation units that implement the C ABI share (mp_capi.cpp: the entries of a context; mp_cpu.cpp: their CPU twins):
+// the handle layouts, the one way to refuse a call (mp_fail / REQUIRE), the model gate, and per family the check of an entry's
+// arguments (mp_*_check, defined in mp_cpu.cpp) that all three entries of an operation call.  DESIGN.md, section 3, has the rules.
 #pragma once
+#include <cmath>
+#include <cstdarg>
 #include <cstdint>
+#include <cstdio>
 #include <map>
 #include <mutex>
 #include <vector>
 
+#include "../../include/manipula_hip.h"
 #include "mp_collision.h"
 #include "mp_rrt.h"
 #include "mp_shortcut.h"
 #include "mp_goal.h"
+#include "mp_ik.h"
+#include "mp_toppra.h"
 #include "mp_model.h"
+
+// ---- refusing a call: the message of mp_last_error, formatted; REQUIRE(cond, fmt, ...) returns MP_ERR_INVALID unless cond holds
+int mp_set_error(int code, const char* msg);  // thread-local message of mp_last_error (mp_capi.cpp; C++ linkage)
+__attribute__((format(printf, 2, 3))) inline int mp_fail(int code, const char* fmt, ...) {
+  char msg[512];  // the size of the message mp_last_error keeps
+  va_list ap;
+  va_start(ap, fmt);
+  std::vsnprintf(msg, sizeof msg, fmt, ap);
+  va_end(ap);
+  return mp_set_error(code, msg);
+}
+#define REQUIRE(cond, ...)                                        \
+  do {                                                            \
+    if (!(cond)) return mp_fail(MP_ERR_INVALID, __VA_ARGS__);     \
+  } while (0)
 
 struct mp_model {
   MpModel<double> d;   // n <= MP_MAX_DOF: the unrolled kernels take these by value.  d.n is ALWAYS the joint count.
@@ -20,6 +43,67 @@ struct mp_model {
   double pmap[MP_MAX_DOF * 100];  // n <= MP_MAX_DOF: per link the 10 x 10 inertial-parameter map D (mp_inertial_map, mp_regressor.h)
   uint64_t uid;  // never reused, so a context's device copies cannot alias a destroyed model
 };
+
+// ---- the model gate of the entries that exist for the unrolled kernels only.  `n`: the joint count refused
+inline int mp_too_many_joints(const char* fn, int n) {
+  return mp_fail(MP_ERR_UNSUPPORTED, "%s: not available for models with more than %d joints (this one has %d)", fn, MP_MAX_DOF, n);
+}
+#define REQUIRE_SMALL(fn)                                              \
+  do {                                                                 \
+    if (model->big) return mp_too_many_joints(fn, model->d.n);         \
+  } while (0)
+// the twins' form: a model, and a small one (the entries of a context word the null case with their context)
+inline int mp_small_model(const char* fn, const mp_model* model) {
+  REQUIRE(model, "%s: null model", fn);
+  REQUIRE_SMALL(fn);
+  return MP_OK;
+}
+
+const double kG[3] = {0.0, 0.0, -9.81};  // reference planning/trajectory_dynamics.py:54
+inline bool any_nonzero(const double* F) {
+  if (!F) return false;
+  for (int k = 0; k < 6; ++k)
+    if (F[k] != 0.0) return true;
+  return false;
+}
+template <typename T> const MpModel<T>& pick(const mp_model* m);
+template <> inline const MpModel<float>& pick<float>(const mp_model* m) { return m->f; }
+template <> inline const MpModel<double>& pick<double>(const mp_model* m) { return m->d; }
+template <typename T> const MpBigModel<T>& pick_big(const mp_model* m);
+template <> inline const MpBigModel<float>& pick_big<float>(const mp_model* m) { return m->bf; }
+template <> inline const MpBigModel<double>& pick_big<double>(const mp_model* m) { return m->bd; }
+
+// ---- per family the check of an entry's arguments: 0, or an MP_ERR_* code with the message set, `fn` the entry's name in front
+// (mp_cpu.cpp).  A check packs the kernel's parameter struct where this header can see it.
+// operational space: frame 0..2, task 0..2, damping finite and >= 0, rows >= 0
+int mp_opspace_check(const char* fn, int frame, int task, double damping, int64_t rows);
+// kinematics VJP: frame 0 or 1, rows >= 0
+int mp_kin_vjp_check(const char* fn, int frame, int64_t rows);
+// the regressor and its normal form: rows >= 0
+int mp_regressor_check(const char* fn, int64_t rows);
+// iLQR: three weight vectors (2n, n, 2n), finite.  (MpIlqrWeights is declared with the launchers, which the twins do not see: the
+// entries of a context pack it themselves)
+int mp_ilqr_weights_check(const char* fn, int n, const double* wq, const double* wr, const double* wf);
+// TOPP-RA: the velocity limits (n, finite and positive) and the torque (n, 2) / acceleration (n) limits, either may be null (none)
+int mp_toppra_vmax_check(const char* fn, int n, const double* vlim, MpToppraVmax* out);
+int mp_toppra_limits_check(const char* fn, int n, const double* tlim, const double* alim, MpToppraLimits* out);
+// inverse kinematics: the tolerances, then the settings packed into MpIkParams / MpIkBigParams.  0; MP_ERR_INVALID with the message
+// set; or -(1 + j) with no message for a joint j whose lower limit lies above its upper one, which the twin and the entries of a
+// context word differently
+template <int CAP>
+int mp_ik_pack(const char* fn, int n, const double* joint_limits, double eomg, double ev, int max_iterations, double damping,
+               double step_cap, double w_o, double w_p, int adaptive, int backtracking, uint32_t seed, MpIkParamsT<CAP>* P) {
+  REQUIRE(eomg > 0 && ev > 0 && damping >= 0 && step_cap > 0, "%s: eomg, ev, step_cap must be positive and damping non-negative", fn);
+  P->eomg = eomg; P->ev = ev; P->damping = damping; P->step_cap = step_cap; P->w_o = w_o; P->w_p = w_p;
+  P->max_iterations = max_iterations; P->seed = seed;
+  P->adaptive_tuning = adaptive ? 1 : 0; P->backtracking = backtracking ? 1 : 0;
+  for (int j = 0; j < CAP; ++j) {
+    P->lo[j] = (j < n && joint_limits) ? joint_limits[2 * j] : -HUGE_VAL;
+    P->hi[j] = (j < n && joint_limits) ? joint_limits[2 * j + 1] : HUGE_VAL;
+    if (P->lo[j] > P->hi[j]) return -(1 + j);
+  }
+  return MP_OK;
+}
 
 // Sphere collision model (mp_collision.h): the host tables, and per context that has used it the device copies.  The device side is
 // mp_capi.cpp's: it registers `release` when it makes the first copy, mp_collision_destroy (mp_cpu.cpp) calls it.
@@ -54,5 +138,3 @@ int mp_path_shortcut_check(const char* fn, int64_t w_in, uint32_t seed, int max_
 // message set (mp_cpu.cpp)
 int mp_goal_ik_check(const char* fn, int n, const double* lo, const double* hi, uint32_t seed, double eomg, double ev, double damping,
                      double step_cap, int max_iters, int max_attempts, double margin, double tol, MpGoalParams* out);
-
-int mp_set_error(int code, const char* msg);  // thread-local message of mp_last_error (mp_capi.cpp; C++ linkage)

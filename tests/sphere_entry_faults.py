@@ -1,5 +1,5 @@
 """Shared by test_sphere_entry_faults_host.py and test_gpu_sphere_entry_faults.py: the single-fault calls of the sphere-model entries
-(collision, collision edges, RRT-Connect, path shortcutting) in their three flavours - the CPU twins (`cpu`), the host-array entries
+(collision, collision edges, RRT-Connect, path shortcutting, goal configurations) in their three flavours - the CPU twins (`cpu`), the host-array entries
 of a context (`host`) and the device-pointer entries (`device`) - with the code and the exact text each must answer.
 
 Every call is made through the C ABI with the argument list of _hip.SIGNATURES, on one problem of the 3-joint chain of chain_cases.py:
@@ -31,10 +31,14 @@ FAMILIES = {
     "path_shortcut": (("waypoints_in", "count_in"), "B", ("W_in", "seed", "max_iters", "min_gain", "max_waypoints", "margin", "tol",
                                                           "max_steps"), ("workspace", "workspace_bytes", "max_blocks"),
                       ("status", "count", "waypoints", "length_in", "length_out", "iterations", "accepted", "skipped_full", "evaluations")),
+    "goal_ik": (("T_goal", "q_seed"), "B", ("lo", "hi", "seed", "eomg", "ev", "damping", "step_cap", "max_iters", "max_attempts", "margin",
+                                            "tol"), ("max_blocks",),
+                ("status", "q", "attempts", "iterations", "converged", "pose_error", "clearance", "witness")),
 }
 SETTINGS = {"eps_world": 0.05, "eps_self": 0.05, "margin": 0.01, "tol": 0.01, "max_steps": 64, "seed": 7, "step": 0.3, "min_advance": 0.04,
-            "max_iters": 2, "max_nodes": MAX_NODES, "max_waypoints": MAX_WAYPOINTS, "W_in": W_IN, "min_gain": 0.0, "max_blocks": 0}
-COUNT_WORD = {"collision": "row", "collision_edges": "edge", "rrt_connect": "problem", "path_shortcut": "problem"}
+            "max_iters": 2, "max_nodes": MAX_NODES, "max_waypoints": MAX_WAYPOINTS, "W_in": W_IN, "min_gain": 0.0, "max_blocks": 0,
+            "eomg": 0.01, "ev": 0.001, "damping": 0.01, "step_cap": 0.5, "max_attempts": 2}
+COUNT_WORD = {"collision": "row", "collision_edges": "edge", "rrt_connect": "problem", "path_shortcut": "problem", "goal_ik": "problem"}
 _EDGE = (("margin nan", {"margin": float("nan")}, "margin must be finite"),
          ("tol 0", {"tol": 0.0}, "tol must be positive and finite"),
          ("max_steps 0", {"max_steps": 0}, "max_steps 0 outside 1..65536"))
@@ -54,6 +58,14 @@ BAD_SETTINGS = {
                               ("max_iters -1", {"max_iters": -1}, "negative max_iters"),
                               ("min_gain -1", {"min_gain": -1.0}, "min_gain must be non-negative and finite"),
                               ("max_waypoints 1", {"max_waypoints": 1}, "max_waypoints 1 outside 2..65536")),
+    "goal_ik": _EDGE[:2] + (("null box", {"hi": None}, "null joint box"),
+                            ("empty box", {"hi": "below"}, "joint 0: the box must be finite with lo <= hi"),
+                            ("eomg 0", {"eomg": 0.0}, "eomg and ev must be positive and finite"),
+                            ("ev inf", {"ev": float("inf")}, "eomg and ev must be positive and finite"),
+                            ("damping 0", {"damping": 0.0}, "damping must be positive and finite"),
+                            ("step_cap nan", {"step_cap": float("nan")}, "step_cap must be positive and finite"),
+                            ("max_iters -1", {"max_iters": -1}, "negative max_iters"),
+                            ("max_attempts 0", {"max_attempts": 0}, "max_attempts 0 outside 1..65536")),
 }
 BIG = "not available for models with more than 8 joints (this one has 9)"
 

@@ -1,5 +1,5 @@
-"""GPU: the eight sphere-model entries of a context (collision, collision edges, RRT-Connect and path shortcutting, on device
-pointers and on host arrays): a call with exactly one thing wrong answers the code and the text recorded in sphere_entry_faults.py,
+"""GPU: the ten sphere-model entries of a context (collision, collision edges, RRT-Connect, path shortcutting and goal
+configurations, on device pointers and on host arrays): a call with exactly one thing wrong answers the code and the text recorded in sphere_entry_faults.py,
 byte for byte, with the entry's own name in front - the faults of the CPU twins and, on device pointers, a misaligned pointer, a
 short or missing workspace and a negative max_blocks.  Every call is refused before anything is launched.
 

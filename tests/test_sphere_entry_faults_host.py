@@ -1,5 +1,5 @@
 """The CPU twins of the sphere-model entries (mp_collision_cpu_f64, mp_collision_edges_cpu_f64, mp_rrt_connect_cpu_f64,
-mp_path_shortcut_cpu_f64) and the two workspace sizes: a call with exactly one thing wrong answers the code and the text recorded in
+mp_path_shortcut_cpu_f64, mp_goal_ik_cpu_f64) and the two workspace sizes: a call with exactly one thing wrong answers the code and the text recorded in
 sphere_entry_faults.py, byte for byte, with the entry's own name in front - a null model or handle, a 9-joint model, a handle made for
 another joint count, one bad value per check of the settings, a negative count, null inputs, no output."""
 import pytest
