@@ -4,8 +4,8 @@ mass matrix and float32 FK + Jacobian + ID have none and fall back to the generi
 17..32 joints).  Every model runs as a generic model, specialised (up to 8 joints), and with a tip wrench (the HAS_FTIP = true
 instantiations) and a non-default g.
 
-The checker is a float64 reference that shares no code with the kernels: oracle/oracle.c up to 8 joints, oracle/ref_numpy.py past
-that (on a sample of rows: its velocity term is a central difference of mass matrices).  The bounds are those of
+The checker is a float64 reference that shares no code with the kernels: oracle/oracle.c up to 8 joints, the exact Newton-Euler
+oracle oracle/newton_euler.py past that, on every row.  The bounds are those of
 tests/test_row_dynamics_host.py (forward bound on the suite arms, backward bound on random chains); every launch's outputs have a
 guard band behind them that must come back untouched.  Float32 inputs are rounded to float32 before the reference sees them."""
 import numpy as np
@@ -23,7 +23,7 @@ pytestmark = pytest.mark.gpu
 
 ROWS = 1031                      # odd, past four 256-thread blocks
 CHAINS = [f"n{n}" for n in range(1, 9)]
-BIG = ["n9", "n12", "n16", "n17", "n32"]
+BIG = ["n9", "n12", "n14", "n16", "n17", "n32"]   # n14, n17, n32: prismatic joints (7, 12, 16) in both run-time-n instantiations
 SPEC_CHAINS = (1, 5, 8)          # random chains also run specialised (hiprtc compiles each in 2-9 s; build() warms the suite arms only)
 MODELS = ROBOTS + CHAINS + BIG
 GUARD, PATTERN = 4096, 0xA5
@@ -71,9 +71,7 @@ class Case:
             assert ctx.is_specialized(self.spec) and not ctx.is_specialized(self.model)
         self.q, self.qd, self.tau = fd_rows(rng, tab, ROWS, suite)
         self.qdd = rng.uniform(-3.0, 3.0, (ROWS, self.n)).astype(np.float32).astype(np.float64)
-        # past 8 joints: rows on both sides of the block boundaries, and the last one
-        sample = None if self.n <= 8 else ([0, 255, 256, 777, ROWS - 1] if self.n <= 16 else [0, 256, ROWS - 1])
-        self.ref = Reference(tab, self.q, self.qd, sample)
+        self.ref = Reference(tab, self.q, self.qd)     # every row, at every joint count
 
     def variants(self):
         """(label, model, g, Ftip): generic, specialised (if it is), and both with a tip wrench + a non-default g."""
@@ -190,10 +188,12 @@ def test_forward_dynamics_f64_device_form(name, ctx, cases):
         if c.n <= 8:
             r = record("fd_f64 rule", f64_ratio(qdd[idx], want))
             assert r <= 1.0, f"{name} {label}: {r:.3g} x the float64 rule"
-        else:   # ref_numpy's central-difference velocity term: the backward form, at the float64 rule's 1e-7
+        else:   # the backward form at the float64 rule's 1e-7, as before, and (the oracle is exact past 8 joints too) the forward rule
             bias = R.bias(g, F)
             r = record("fd_f64 backward (9..32)", backward_ratio(R.M, qdd[idx], c.tau[idx] - bias, bias, c.tau[idx], 1e-7))
             assert r <= 1.0, f"{name} {label}: backward error {r:.3g} x 1e-7"
+            r = record("fd_f64 rule (9..32)", f64_ratio(qdd[idx], want))
+            assert r <= 1.0, f"{name} {label}: {r:.3g} x the float64 rule"
         host = ctx.forward_dynamics_host(m, c.q, c.qd, c.tau, g, F)
         np.testing.assert_array_equal(qdd, host, err_msg=f"{name} {label}: device form != host form")
     for plain, special in (("generic", "spec"), ("wrench", "spec+wrench")) if c.spec is not None else ():
@@ -289,7 +289,7 @@ def test_mass_matrix_f32_against_the_reference(name, ctx, cases):
 @pytest.mark.parametrize("name", BIG)
 def test_mass_matrix_f32_run_time_n(name, ctx, cases):
     """The run-time-n float32 mass matrix (9..16 and 17..32 joints): the store-path test's row counts with a guard band, against the
-    float64 CPU launcher; the reference's rows against ref_numpy."""
+    float64 CPU launcher; every row against the Newton-Euler oracle."""
     from manipulapy_amd import _hip
 
     c = cases(name)
@@ -297,7 +297,7 @@ def test_mass_matrix_f32_run_time_n(name, ctx, cases):
     full = run(ctx, "mm", c.model, (c.q,), [(ROWS, n, n)], np.float32)[0].astype(np.float64)
     for i, r in enumerate(c.ref.idx):
         want = c.ref.M[i]
-        rr = record("mm_f32 run-time n (ref_numpy)", np.abs(full[r] - want).max() / (3e-5 * np.abs(want).max()))
+        rr = record("mm_f32 run-time n (oracle)", np.abs(full[r] - want).max() / (3e-5 * np.abs(want).max()))
         assert rr <= 1.0, f"{name} row {r}: {rr:.3g} x the bound"
     want = _hip.cpu_mass_matrix(c.model, c.q[:333])
     for rows in (1, 15, 16, 17, 31, 33, 63, 64, 65, 130, 333):
@@ -321,13 +321,14 @@ def test_mass_matrix_f32_nonfinite_rows(name, ctx, cases):
 
 # ------------------------------------------------------------------------------------------------ FK + Jacobian + ID, float32
 def _tau_ref(c, g, F):
-    """Reference torques of the case's rows (q, qd, qdd): the C oracle on every row up to 8 joints, else the sampled rows."""
+    """Reference torques of the case's rows (q, qd, qdd): the C oracle up to 8 joints, else M_ref qdd + bias_ref of the Newton-Euler
+    oracle; every row."""
     if c.n <= 8:
         return c_oracle.inverse_dynamics_rows(c.tab, c.q, c.qd, c.qdd, ref.G_DEFAULT if g is None else g, F)[0]
     return np.einsum("rij,rj->ri", c.ref.M, c.qdd[c.ref.idx]) + c.ref.bias(g, F)
 
 
-@pytest.mark.parametrize("name", ROBOTS + CHAINS + ["n9", "n16", "n17", "n32"])
+@pytest.mark.parametrize("name", ROBOTS + CHAINS + ["n9", "n14", "n16", "n17", "n32"])
 def test_fk_jac_id_f32_against_the_reference(name, ctx, cases):
     """mp_fk_jac_id_f32 at ordinary sizes: T and J within 2e-5 (x max(1, max|J|) on random chains) of ref_numpy, tau under the
     suite's element-wise float32 rule against the reference; every output subset gives the bits of the full launch, each with its
@@ -336,7 +337,7 @@ def test_fk_jac_id_f32_against_the_reference(name, ctx, cases):
     n = c.n
     shapes = [(ROWS, 4, 4), (ROWS, 6, n), (ROWS, n)]
     ins = (c.q, c.qd, c.qdd)
-    sample = c.ref.idx if n > 8 else range(0, ROWS, 7)
+    sample = range(0, ROWS, 7)
     full = {}
     for label, m, g, F in c.variants():
         T, J, tau = full[label] = run(ctx, "fkjid", m, ins, shapes, np.float32, g, F)

@@ -1,5 +1,5 @@
 """The float32 forward-dynamics template (csrc/mp_core.h mp_forward_dynamics: bias recursion + CRBA + float32 Cholesky) built for
-the host, against a float64 reference that shares none of its code (oracle/oracle.c, and oracle/ref_numpy.py past 8 joints).
+the host, against a float64 reference that shares none of its code (oracle/oracle.c, and oracle/newton_euler.py past 8 joints).
 
 Two bounds, the same ones tests/test_gpu_row_dynamics.py holds the kernels to (include/manipula_hip.h, mp_forward_dynamics_f32):
   forward   max|qdd - qdd_ref| <= 1e-4 * max|qdd_ref|  per row, on the four suite arms (M's condition number reaches ~3e4 there);
@@ -11,6 +11,7 @@ import pytest
 
 from conftest import ROBOTS
 from oracle import c_oracle
+from oracle import newton_euler as ne
 from oracle import ref_numpy as ref
 from test_host_logic import hostsim  # noqa: F401  (fixture: clang++ build of the device templates)
 from test_random_robots import FLAVOURS, random_robot
@@ -40,9 +41,11 @@ def fd_rows(rng, tab, rows, suite):
 
 
 class Reference:
-    """M_ref and bias_ref = ID(q, qd, 0, g, F) of float64 rows, and qdd_ref = solve(M_ref, tau - bias_ref).  Up to 8 joints the
-    C oracle evaluates every row; past that ref_numpy evaluates the rows listed in `sample` (its velocity term costs 2n mass
-    matrices of a row, ~1.6 s at 32 joints), and keeps that term, so other g / Ftip cost only the gravity and wrench terms."""
+    """M_ref and bias_ref = ID(q, qd, 0, g, F) of float64 rows, and qdd_ref = solve(M_ref, tau - bias_ref), on every row (or on the
+    rows listed in `sample`).  Up to 8 joints the C oracle evaluates them; past that the exact Newton-Euler oracle
+    (oracle/newton_euler.py, pinned by tests/test_newton_euler_oracle.py; its float64 differs from its longdouble by 4e-14 at most in
+    forward dynamics on these chains), in blocks of rows so that the n recursions of a block's mass matrices stay small."""
+    BLOCK = 64
 
     def __init__(self, tab, q, qd, sample=None):
         self.tab, self.n = tab, tab.n
@@ -50,17 +53,15 @@ class Reference:
         self.q, self.qd = q[self.idx], qd[self.idx]
         if self.n <= 8:
             self.M = c_oracle.mass_matrix_rows(tab, self.q)
-            self.c = None
         else:
-            self.M = np.stack([ref.mass_matrix(tab, x) for x in self.q])
-            self.c = np.stack([ref.velocity_quadratic_forces(tab, x, v) for x, v in zip(self.q, self.qd)])
+            self.M = np.concatenate([ne.mass_matrix(tab, self.q[i:i + self.BLOCK]) for i in range(0, len(self.q), self.BLOCK)])
 
     def bias(self, g=None, F=None):
         g = ref.G_DEFAULT if g is None else np.asarray(g, dtype=np.float64)
         F = np.zeros(6) if F is None else np.asarray(F, dtype=np.float64)
-        if self.c is None:
+        if self.n <= 8:
             return c_oracle.inverse_dynamics_rows(self.tab, self.q, self.qd, np.zeros_like(self.q), g, F)[0]
-        return self.c + np.stack([ref.gravity_forces(self.tab, x, g) + ref.jacobian_space(self.tab, x).T @ F for x in self.q])
+        return ne.inverse_dynamics(self.tab, self.q, self.qd, np.zeros_like(self.q), g, F)
 
     def qdd(self, tau, g=None, F=None):
         return np.linalg.solve(self.M, (tau[self.idx] - self.bias(g, F))[..., None])[..., 0]
