@@ -995,6 +995,80 @@ int mp_goal_ik_cpu_f64(const mp_model* model, const mp_collision* h, const doubl
                        int max_iters, int max_attempts, double margin, double tol, int32_t* status, double* q, int32_t* attempts,
                        int32_t* iterations, int32_t* converged, double* pose_error, double* clearance, int32_t* witness, int nthreads);
 
+/* ---- batched C2 corner blending of waypoint paths over the sphere model above (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED
+ * above that; generic kernels only, no run-time specialisation; csrc/mp_blend.h).  For B piecewise-linear joint-space paths in one
+ * world: every interior corner is replaced by a quintic blend that is proven free by the conservative advancement of
+ * mp_collision_edges_*, and the resulting twice-differentiable curve is sampled on the uniform grid s_i = i / (N - 1) as q, dq/ds,
+ * d2q/ds2 - what mp_toppra_* reads.  No random numbers.  The kernels, the CPU twin and the tests' NumPy oracle implement exactly the
+ * contract below; every sum is taken in the order written, j ascending.
+ * Per problem: waypoints_in (W_in, n) and count_in, exactly as mp_path_shortcut_* reads them.  Per launch: W_in in 1..65536, N in
+ *   3..65536, blend > 0 and finite (the largest cut distance, in the joint-space norm of the shortcutter's lengths), max_halvings in
+ *   0..32, and margin, tol, max_steps as for the edges.  Anything else is MP_ERR_INVALID with a message.
+ * 1 Screen: count_in < 2: SKIPPED.  count_in > W_in, or a non-finite value in the first count_in rows: INVALID.
+ * 2 Compact: r_0 = p_0; p_i is kept iff some component differs, compared as doubles, from the last kept point: m points.
+ *   m == 1: POINT - q = r_0 on the whole grid, dq = ddq = 0, length 0.
+ * 3 Segments: for i = 1..m-1, D_i = r_i - r_{i-1}, l_i = sqrt(sum_j D_ij^2), u_i = D_i / l_i.  m == 2: STRAIGHT.  Corners are
+ *   k = 1..m-2 with u_in = u_k, u_out = u_{k+1}.  The first k with sum_j u_in,j u_out,j < -1 + 1e-9: REVERSAL, corner = k, nothing is
+ *   evaluated (a path that doubles back has no C2 blend of non-zero speed).
+ * 4 Corners, in ascending order: d = min(blend, l_k / 2, l_{k+1} / 2); up to max_halvings + 1 attempts; an attempt that is not FREE
+ *   halves d and adds 1 to `halvings`.  The first FREE attempt sets cut[k] = d.  None: BLOCKED, corner = k, the problem stops.
+ *   An attempt is the iteration of mp_collision_edges_* over u in [0, 1], u_0 = 0, on the curve
+ *       q(u) = r_k - d u_in (1 - u)^4 (1 + 1.5 u) + d u_out u^4 (2.5 - 1.5 u)
+ *   - the quintic Bezier on a, (a + r) / 2, r, r, (r + b) / 2, b with a = r_k - d u_in, b = r_k + d u_out, whose second derivative
+ *   vanishes at both ends - with the speed bounds L[ka][kb] of the edges, in which |D_j| is replaced by v_j = 2.5 d max(|u_in,j|,
+ *   |u_out,j|) and the reach max(|q_a,j|, |q_b,j|) of a prismatic joint by max(|a_j|, |r_k,j|, |b_j|): both bound the whole curve
+ *   (the hodograph's control differences are (r - a) / 2 twice, 0, (b - r) / 2 twice, and the curve lies in the hull of a, r, b).
+ *   The decisions are the edge's: c <= tol: BLOCKED; otherwise u + tau >= 1: FREE; max_steps evaluations of one attempt without a
+ *   decision: a failed attempt.  The linear pieces are pieces of input segments and ARE NOT CHECKED, as in mp_path_shortcut_*.
+ * 5 Parameter sigma: unit speed on linear pieces, and a blend of cut d takes 2.5 d of it (so that dq/dsigma is continuous).  With
+ *   cut[0] = cut[m-1] = 0: knot[0] = 0, knot[k] = (knot[k-1] + 2.5 cut[k-1]) + ((l_k - cut[k-1]) - cut[k]) for k = 1..m-1;
+ *   knot[m-1] = Sigma, the length.
+ * 6 Grid: sigma = (i / (N - 1)) Sigma.  i = 0: r_0, Sigma u_1, 0.  i = N - 1: r_{m-1}, Sigma u_{m-1}, 0.  Otherwise k = the
+ *   largest index in 0..m-2 with knot[k] <= sigma.  If k >= 1 and sigma - knot[k] < 2.5 cut[k]: blend k at u = (sigma - knot[k]) /
+ *   (2.5 cut[k]): q(u) as above with d = cut[k], dq/ds = Sigma [u_in (1 - u)^3 (1 + 3 u) + u_out u^3 (4 - 3 u)], d2q/ds2 = Sigma^2
+ *   4.8 u (1 - u) [u u_out - (1 - u) u_in] / cut[k].  Else the linear piece of segment k + 1: q = r_k + (((cut[k] + sigma) -
+ *   knot[k]) - 2.5 cut[k]) u_{k+1}, dq/ds = Sigma u_{k+1}, d2q/ds2 = 0.  All three are continuous across a knot.
+ * Per problem (every output may be NULL; at least one is needed):
+ *     status (B) int32                   MP_BLEND_DONE 0, _STRAIGHT 1, _SKIPPED 2, _POINT 3, _BLOCKED 4, _REVERSAL 5, _INVALID -1
+ *     corner (B) int32                   the first offending corner of the compacted path (BLOCKED, REVERSAL), else -1
+ *     count (B) int32                    m
+ *     points (B, W_in, n)                the compacted points, padded by repeating the last
+ *     cut (B, W_in), knot (B, W_in)      padded with 0 and with Sigma
+ *     length (B)                         Sigma
+ *     halvings, evaluations (B) int32    failed attempts, configurations evaluated
+ *     clearance (B)                      the smallest min(dist_world, dist_self) met in the attempts, +inf without any
+ *     q, dq, ddq (B, N, n)               the grid, batch-major
+ *   A problem that is not DONE, STRAIGHT or POINT has NaN in every real output and 0 in count; status, corner and the two counters
+ *   stay meaningful.  A problem's result depends on its own content only.  points and the grid arrays must not overlap waypoints_in.
+ * mp_path_blend_f64: device arrays, 16-byte aligned.  Two launches on the compute stream: the corners - a lane serves one problem at a
+ *   time and takes problems from a queue, one collision evaluation a trip, no workspace (a lane reads its own input rows) - and,
+ *   if any of q, dq, ddq is given, the grid, one lane a grid point.  The grid reads status, count, points, cut, knot and length
+ *   back: all six are then required.  max_blocks > 0 caps the first grid.  Asynchronous; it allocates nothing once the handle is
+ *   resident on the context and may then be captured into a launch graph (the queue head's reset is part of it).  Launches that share
+ *   a collision handle share its queue head: they are serialised by the handle's lock and the compute stream.
+ *   mp_path_blend_host_f64: host arrays, device memory from the context's pool.  mp_path_blend_cpu_f64: the kernels' per-problem and
+ *   per-grid-point code on the host, no context. */
+#define MP_BLEND_DONE 0
+#define MP_BLEND_STRAIGHT 1
+#define MP_BLEND_SKIPPED 2
+#define MP_BLEND_POINT 3
+#define MP_BLEND_BLOCKED 4
+#define MP_BLEND_REVERSAL 5
+#define MP_BLEND_INVALID (-1)
+int mp_path_blend_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_waypoints_in, const int32_t* d_count_in,
+                      int64_t B, int64_t W_in, int64_t N, double blend, int max_halvings, double margin, double tol, int max_steps,
+                      int max_blocks, int32_t* d_status, int32_t* d_corner, int32_t* d_count, double* d_points, double* d_cut,
+                      double* d_knot, double* d_length, int32_t* d_halvings, int32_t* d_evaluations, double* d_clearance, double* d_q,
+                      double* d_dq, double* d_ddq);
+int mp_path_blend_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* waypoints_in, const int32_t* count_in,
+                           int64_t B, int64_t W_in, int64_t N, double blend, int max_halvings, double margin, double tol, int max_steps,
+                           int32_t* status, int32_t* corner, int32_t* count, double* points, double* cut, double* knot, double* length,
+                           int32_t* halvings, int32_t* evaluations, double* clearance, double* q, double* dq, double* ddq);
+int mp_path_blend_cpu_f64(const mp_model* model, const mp_collision* h, const double* waypoints_in, const int32_t* count_in, int64_t B,
+                          int64_t W_in, int64_t N, double blend, int max_halvings, double margin, double tol, int max_steps,
+                          int32_t* status, int32_t* corner, int32_t* count, double* points, double* cut, double* knot, double* length,
+                          int32_t* halvings, int32_t* evaluations, double* clearance, double* q, double* dq, double* ddq, int nthreads);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new; the reference is single-device) ------
  * Trajectory batches are sharded over ranks with no exchange during compute; the only collective is
  * the all-gather that reassembles the torque history.  Rank 0 creates the id, the launcher

@@ -191,6 +191,9 @@ SIGNATURES = {
     "mp_path_shortcut_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_path_shortcut_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _vp, _i64, _i64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _c_dp, _c_dp, _c_dp, _vp, _vp, _vp, _vp]),
     "mp_path_shortcut_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _vp, _i64, _i64, ctypes.c_uint32, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _c_dp, _c_dp, _c_dp, _vp, _vp, _vp, _vp, ctypes.c_int]),
+    "mp_path_blend_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int] + [_vp] * 13),
+    "mp_path_blend_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _vp, _i64, _i64, _i64, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp]),
+    "mp_path_blend_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _vp, _i64, _i64, _i64, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
     "mp_goal_ik_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_goal_ik_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _c_dp, _vp, _vp, _vp, _c_dp, _c_dp, _vp]),
     "mp_goal_ik_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _c_dp, _vp, _vp, _vp, _c_dp, _c_dp, _vp, ctypes.c_int]),
@@ -765,6 +768,27 @@ class HipContext:
         with its device form is held by tests/test_gpu_shortcut.py.)"""
         return _path_shortcut((self.handle,), self.lib.mp_path_shortcut_host_f64, model, collision, waypoints, count, margin, tol,
                               max_iters, min_gain, max_waypoints, max_steps, seed, want)
+
+    def path_blend(self, model, collision, d_waypoints_in, d_count_in, problems, w_in, N, margin, tol, *, blend=0.5, max_halvings=6,
+                   max_steps=64, max_blocks: int = 0, d_status=None, d_corner=None, d_count=None, d_points=None, d_cut=None, d_knot=None,
+                   d_length=None, d_halvings=None, d_evaluations=None, d_clearance=None, d_q=None, d_dq=None, d_ddq=None):
+        """C2 corner blending of waypoint paths on device buffers (float64; csrc/mp_blend.h): d_waypoints_in (problems,w_in,n),
+        d_count_in (problems) int32; outputs status / corner / count / halvings / evaluations (problems) int32, length / clearance
+        (problems), points (problems,w_in,n), cut / knot (problems,w_in), q / dq / ddq (problems,N,n), each may be None (at least one
+        given; status, count, points, cut, knot and length are required with any of q, dq, ddq).  No workspace.  `max_blocks` > 0
+        caps the grid of the corner launch.  Asynchronous (capturable once the handle has been used or given a world on this
+        context)."""
+        _check(self.lib.mp_path_blend_f64(self.handle, model.handle, collision.handle, _p(d_waypoints_in), _p(d_count_in), int(problems),
+                                          int(w_in), int(N), float(blend), int(max_halvings), float(margin), float(tol), int(max_steps),
+                                          int(max_blocks), _p(d_status), _p(d_corner), _p(d_count), _p(d_points), _p(d_cut), _p(d_knot),
+                                          _p(d_length), _p(d_halvings), _p(d_evaluations), _p(d_clearance), _p(d_q), _p(d_dq), _p(d_ddq)))
+
+    def path_blend_arrays(self, model, collision, waypoints, count, N, margin, tol, *, blend=0.5, max_halvings=6, max_steps=64, want=None):
+        """The same on host arrays (mp_path_blend_host_f64) through the context's pool: a dict of the outputs named in `want` (default:
+        all of BLEND_OUTPUTS).  (Not named `*_host`, as rrt_connect_arrays is not; this entry's equality with its device form is held
+        by tests/test_gpu_blend.py.)"""
+        return _path_blend((self.handle,), self.lib.mp_path_blend_host_f64, model, collision, waypoints, count, N, margin, tol, blend,
+                           max_halvings, max_steps, want)
 
     def goal_ik(self, model, collision, d_T_goal, d_q_seed, problems, lo, hi, margin, tol, *, eomg, ev, damping, step_cap, max_iters,
                 max_attempts, seed, max_blocks: int = 0, d_status=None, d_q=None, d_attempts=None, d_iterations=None, d_converged=None,
@@ -1658,6 +1682,48 @@ def cpu_path_shortcut(model: "HipModel", collision: "HipCollision", waypoints, c
     """CPU twin of HipContext.path_shortcut_arrays."""
     return _path_shortcut((), load_library().mp_path_shortcut_cpu_f64, model, collision, waypoints, count, margin, tol, max_iters,
                           min_gain, max_waypoints, max_steps, seed, want, nthreads)
+
+
+BLEND_OUTPUTS = ("status", "corner", "count", "points", "cut", "knot", "length", "halvings", "evaluations", "clearance", "q", "dq", "ddq")
+BLEND_DONE, BLEND_STRAIGHT, BLEND_SKIPPED, BLEND_POINT, BLEND_BLOCKED, BLEND_REVERSAL, BLEND_INVALID = 0, 1, 2, 3, 4, 5, -1
+
+
+def _path_blend(lead, fn, model, collision, waypoints, count, N, margin, tol, blend, max_halvings, max_steps, want, nthreads=None):
+    want = BLEND_OUTPUTS if want is None else tuple(want)
+    for w in want:
+        if w not in BLEND_OUTPUTS:
+            raise ValueError(f"unknown blend output {w!r}; choose from {BLEND_OUTPUTS}")
+    wp = _as_c(waypoints, np.float64, name="waypoints")
+    if wp.ndim != 3 or wp.shape[2] != model.n:
+        raise ValueError(f"waypoints must be (problems, W, {model.n}); got {wp.shape}")
+    B, w_in, n = wp.shape
+    cnt = np.asarray(count)
+    if cnt.dtype.kind not in "iu":  # (a silent cast would turn 2.9 into 2)
+        raise TypeError(f"count must be an integer array; got {cnt.dtype}")
+    if cnt.size and (cnt.min() < np.iinfo(np.int32).min or cnt.max() > np.iinfo(np.int32).max):
+        raise ValueError("count does not fit 32 bits")
+    cnt = _as_c(cnt.astype(np.int32), np.int32, (B,), "count")
+    grid = max(int(N), 0)  # (a value below 3 is the entry's to refuse)
+    shapes = {"points": (B, w_in, n), "cut": (B, w_in), "knot": (B, w_in), "q": (B, grid, n), "dq": (B, grid, n), "ddq": (B, grid, n)}
+    whole = ("status", "corner", "count", "halvings", "evaluations")
+    out = {w: np.empty(shapes.get(w, (B,)), dtype=np.int32 if w in whole else np.float64) for w in want}
+    ptrs = []
+    for w in BLEND_OUTPUTS:
+        a = out.get(w)
+        ptrs.append(None if a is None else (a.ctypes.data_as(_vp) if w in whole else _dptr(a)))
+    args = list(lead) + [model.handle, collision.handle, _dptr(wp), cnt.ctypes.data_as(_vp), B, w_in, int(N), float(blend),
+                         int(max_halvings), float(margin), float(tol), int(max_steps)] + ptrs
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return out
+
+
+def cpu_path_blend(model: "HipModel", collision: "HipCollision", waypoints, count, N, margin, tol, *, blend=0.5, max_halvings=6,
+                   max_steps=64, want=None, nthreads: int = 0) -> dict:
+    """CPU twin of HipContext.path_blend_arrays."""
+    return _path_blend((), load_library().mp_path_blend_cpu_f64, model, collision, waypoints, count, N, margin, tol, blend, max_halvings,
+                       max_steps, want, nthreads)
 
 
 GOAL_OUTPUTS = ("status", "q", "attempts", "iterations", "converged", "pose_error", "clearance", "witness")

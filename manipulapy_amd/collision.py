@@ -14,7 +14,7 @@ import numpy as np
 from . import _hip
 from .registry import execute_registered_kernel
 
-__all__ = ["SphereCollisionModel", "COLLISION_OP", "EDGES_OP", "PLAN_OP", "SHORTCUT_OP", "GOAL_OP"]
+__all__ = ["SphereCollisionModel", "COLLISION_OP", "EDGES_OP", "PLAN_OP", "SHORTCUT_OP", "GOAL_OP", "BLEND_OP"]
 
 # The registry's sorted name list starts with "control.pd_regulation" (the unknown-name message is pinned by a test), so the operation
 # lives in the "planning" family rather than in one of its own that would sort ahead of it.
@@ -23,6 +23,7 @@ EDGES_OP = "planning.collision_edges"
 PLAN_OP = "planning.rrt_connect"
 SHORTCUT_OP = "planning.shortcut_paths"
 GOAL_OP = "planning.goal_configurations"
+BLEND_OP = "planning.blend_paths"
 
 
 def _hip_model_of(obj) -> _hip.HipModel:
@@ -231,6 +232,28 @@ class SphereCollisionModel:
         out = execute_registered_kernel(SHORTCUT_OP, self, np.ascontiguousarray(wp.reshape((-1,) + wp.shape[-2:])),
                                         cnt.reshape(-1), margin, tol, max_iters=max_iters,
                                         min_gain=min_gain, max_waypoints=max_waypoints, max_steps=max_steps, seed=seed, want=want)
+        return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}
+
+    def blend_paths(self, waypoints, count, N: int, margin: float = 0.0, tol: float = 1e-3, *, blend: float = 0.5, max_halvings: int = 6,
+                    max_steps: int = 64, want=None) -> dict:
+        """C2 corner blending of B piecewise-linear paths, waypoints (B, W, n) with count (B,) real rows each (any common leading
+        shape; `plan_paths`' or `shortcut_paths`' "waypoints" and "count" go straight in), sampled on the N grid points s_i = i / (N -
+        1): {"status" (0 done, 1 straight, 2 skipped: fewer than two waypoints, 3 point, 4 blocked, 5 reversal, -1 invalid), "corner",
+        "count", "points" (.., W, n), "cut", "knot" (.., W), "length", "halvings", "evaluations", "clearance", "q", "dq", "ddq" (.., N,
+        n)} or the subset named in `want`.  Repeated waypoints are dropped; every interior corner is then replaced by a quintic blend
+        that leaves the two segments at most `blend` (joint-space length) from the corner and is proven free by `check_edges`'
+        conservative advancement with this margin, tol and max_steps; a blend that is not proven is tried again at half the cut, up
+        to `max_halvings` times, and a corner that is never proven makes the path blocked ("corner": its index in "points").  A
+        path that doubles back on itself is a reversal.  "q", "dq", "ddq" are the curve and its first two derivatives in s, the
+        arguments of OptimizedTrajectoryPlanning.batch_time_optimal_parameterization; rows without a curve are NaN.  The linear
+        pieces are pieces of input segments and ARE NOT CHECKED (OptimizedTrajectoryPlanning.batch_validate_path does that).  A
+        problem's result depends on its content only."""
+        wp, cnt = np.asarray(waypoints, dtype=np.float64), np.asarray(count)
+        if wp.ndim < 3 or wp.shape[-1] != self.n or cnt.shape != wp.shape[:-2]:
+            raise ValueError(f"waypoints must be (..., W, {self.n}) and count its leading shape; got {wp.shape} and {cnt.shape}")
+        lead = wp.shape[:-2]
+        out = execute_registered_kernel(BLEND_OP, self, np.ascontiguousarray(wp.reshape((-1,) + wp.shape[-2:])), cnt.reshape(-1), N,
+                                        margin, tol, blend=blend, max_halvings=max_halvings, max_steps=max_steps, want=want)
         return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}
 
     # ------------------------------------------------------------------ pose goals

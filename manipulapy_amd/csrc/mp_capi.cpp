@@ -3351,6 +3351,90 @@ int mp_goal_ik_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, con
   });
 }
 
+}  // extern "C"
+
+// ---- C2 corner blending of waypoint paths over the sphere model (mp_blend.h): the corners on the work queue, then the grid.  No
+// workspace, so one plan per call, made here
+static int path_blend_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_in, const int32_t* d_count_in,
+                           int64_t B, const MpBlendParams& P, int max_blocks, int32_t* d_status, int32_t* d_corner, int32_t* d_count,
+                           double* d_points, double* d_cut, double* d_knot, double* d_length, int32_t* d_halvings, int32_t* d_evals,
+                           double* d_clear, double* d_q, double* d_dq, double* d_ddq) {
+  REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  REQUIRE(d_in && d_count_in, "%s: null device pointer", fn);
+  const bool grid = d_q || d_dq || d_ddq;
+  REQUIRE(d_status || d_corner || d_count || d_points || d_cut || d_knot || d_length || d_halvings || d_evals || d_clear || grid,
+          "%s: at least one output is required", fn);
+  REQUIRE(!grid || (d_status && d_count && d_points && d_cut && d_knot && d_length),
+          "%s: q, dq and ddq are sampled from status, count, points, cut, knot and length: all six are required with them", fn);
+  REQUIRE(aligned16(d_in) && aligned16(d_count_in) && aligned16(d_status) && aligned16(d_corner) && aligned16(d_count) &&
+              aligned16(d_points) && aligned16(d_cut) && aligned16(d_knot) && aligned16(d_length) && aligned16(d_halvings) &&
+              aligned16(d_evals) && aligned16(d_clear) && aligned16(d_q) && aligned16(d_dq) && aligned16(d_ddq),
+          "%s: device pointers must be 16-byte aligned", fn);
+  std::lock_guard<std::mutex> hl(h->mu);
+  mp_collision::Resident* R = nullptr;
+  if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
+  PROFILE_SCOPE(ctx, fn);
+  MpQueuePlan plan;
+  HIP_TRY(mpk_queue_plan(MP_QUEUE_BLEND, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_path_blend(ctx->compute, model->d, collision_device(h, R), d_in, d_count_in, (long)B, P, d_status, d_corner, d_count, d_points,
+                         d_cut, d_knot, d_length, d_halvings, d_evals, d_clear, queue_grid(plan, B, max_blocks), plan.lds));
+  if (grid)
+    HIP_TRY(mpk_path_blend_sample(ctx->compute, model->d.n, (long)B, P, d_status, d_count, d_points, d_cut, d_knot, d_length, d_q, d_dq,
+                                  d_ddq));
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_path_blend_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_waypoints_in, const int32_t* d_count_in,
+                      int64_t B, int64_t W_in, int64_t N, double blend, int max_halvings, double margin, double tol, int max_steps,
+                      int max_blocks, int32_t* d_status, int32_t* d_corner, int32_t* d_count, double* d_points, double* d_cut,
+                      double* d_knot, double* d_length, int32_t* d_halvings, int32_t* d_evaluations, double* d_clearance, double* d_q,
+                      double* d_dq, double* d_ddq) {
+  const char* fn = "mp_path_blend_f64";
+  CHECK_SPHERE_ENTRY(fn);
+  MpBlendParams P;
+  if (int rc = mp_path_blend_check(fn, W_in, N, blend, max_halvings, margin, tol, max_steps, &P)) return rc;
+  return path_blend_impl(fn, ctx, model, h, d_waypoints_in, d_count_in, B, P, max_blocks, d_status, d_corner, d_count, d_points, d_cut,
+                         d_knot, d_length, d_halvings, d_evaluations, d_clearance, d_q, d_dq, d_ddq);
+}
+
+int mp_path_blend_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* waypoints_in, const int32_t* count_in,
+                           int64_t B, int64_t W_in, int64_t N, double blend, int max_halvings, double margin, double tol, int max_steps,
+                           int32_t* status, int32_t* corner, int32_t* count, double* points, double* cut, double* knot, double* length,
+                           int32_t* halvings, int32_t* evaluations, double* clearance, double* q, double* dq, double* ddq) {
+  const char* fn = "mp_path_blend_host_f64";
+  CHECK_SPHERE_ENTRY(fn);
+  MpBlendParams P;
+  if (int rc = mp_path_blend_check(fn, W_in, N, blend, max_halvings, margin, tol, max_steps, &P)) return rc;
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  REQUIRE(waypoints_in && count_in, "%s: null host pointer", fn);
+  REQUIRE(status || corner || count || points || cut || knot || length || halvings || evaluations || clearance || q || dq || ddq,
+          "%s: at least one output is required", fn);
+  const size_t n = (size_t)model->d.n, ib = (size_t)B * sizeof(int32_t), db = (size_t)B * sizeof(double);
+  const size_t wb = (size_t)W_in * db, gb = (size_t)N * n * db;
+  const bool grid = q || dq || ddq;
+  HostCall hc(ctx);  // (h is the collision handle)
+  const double* din = hc.in(waypoints_in, wb * n);
+  const int32_t* dcin = hc.in(count_in, ib);
+  // the tables the grid reads back stay on the device where the caller did not ask for them
+  auto table_i = [&](int32_t* host, size_t bytes) { return host ? hc.out(host, bytes) : (grid ? hc.work<int32_t>(bytes) : nullptr); };
+  auto table_d = [&](double* host, size_t bytes) { return host ? hc.out(host, bytes) : (grid ? hc.work<double>(bytes) : nullptr); };
+  int32_t* dstatus = table_i(status, ib);
+  int32_t* dcorner = hc.out(corner, ib);
+  int32_t* dcount = table_i(count, ib);
+  double *dpoints = table_d(points, wb * n), *dcut = table_d(cut, wb), *dknot = table_d(knot, wb), *dlength = table_d(length, db);
+  int32_t *dhalv = hc.out(halvings, ib), *dev = hc.out(evaluations, ib);
+  double *dclear = hc.out(clearance, db), *dq_ = hc.out(q, gb), *ddq_ = hc.out(dq, gb), *dddq_ = hc.out(ddq, gb);
+  return hc.run([&] {
+    return path_blend_impl(fn, ctx, model, h, din, dcin, B, P, 0, dstatus, dcorner, dcount, dpoints, dcut, dknot, dlength, dhalv, dev,
+                           dclear, dq_, ddq_, dddq_);
+  });
+}
+
 int mp_collision_set_world(mp_ctx* ctx, mp_collision* h, int O, const int32_t* kind, const double* params) {
   const char* fn = "mp_collision_set_world";
   REQUIRE(h, "%s: null collision handle", fn);

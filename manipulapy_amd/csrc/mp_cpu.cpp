@@ -1343,3 +1343,78 @@ int mp_goal_ik_cpu_f64(const mp_model* model, const mp_collision* h, const doubl
 }
 
 }  // extern "C"
+
+// ---- C2 corner blending of waypoint paths over the sphere model (mp_blend.h)
+int mp_path_blend_check(const char* fn, int64_t w_in, int64_t grid, double blend, int max_halvings, double margin, double tol,
+                        int max_steps, MpBlendParams* out) {
+  if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
+  REQUIRE(w_in >= 1 && w_in <= MP_BL_MAX_WAYPOINTS, "%s: %lld input rows a path, outside 1..65536", fn, (long long)w_in);
+  REQUIRE(grid >= 3 && grid <= MP_BL_MAX_GRID, "%s: %lld grid points, outside 3..65536", fn, (long long)grid);
+  REQUIRE(blend > 0.0 && std::isfinite(blend), "%s: blend must be positive and finite", fn);
+  REQUIRE(max_halvings >= 0 && max_halvings <= MP_BL_MAX_HALVINGS, "%s: max_halvings %d outside 0..32", fn, max_halvings);
+  MpBlendParams P;
+  std::memset(&P, 0, sizeof P);
+  P.edge = {margin, tol, max_steps, 0};
+  P.blend = blend;
+  P.max_halvings = max_halvings; P.w_in = (int)w_in; P.grid = (int)grid;
+  *out = P;
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_path_blend_cpu_f64(const mp_model* model, const mp_collision* h, const double* waypoints_in, const int32_t* count_in, int64_t B,
+                          int64_t W_in, int64_t N_grid, double blend, int max_halvings, double margin, double tol, int max_steps,
+                          int32_t* status, int32_t* corner, int32_t* count, double* points, double* cut, double* knot, double* length,
+                          int32_t* halvings, int32_t* evaluations, double* clearance, double* q, double* dq, double* ddq, int nthreads) {
+  const char* fn = "mp_path_blend_cpu_f64";
+  if (int rc = col_twin_enter(fn, model, h)) return rc;
+  MpBlendParams P;
+  if (int rc = mp_path_blend_check(fn, W_in, N_grid, blend, max_halvings, margin, tol, max_steps, &P)) return rc;
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
+  if (B == 0) return MP_OK;
+  REQUIRE(waypoints_in && count_in, "%s: null pointer", fn);
+  REQUIRE(status || corner || count || points || cut || knot || length || halvings || evaluations || clearance || q || dq || ddq,
+          "%s: at least one output is required", fn);
+  const MpModel<double>& M = model->d;
+  MpColWorld hdr;
+  const MpColTablesHost tb = col_host_tables(h, hdr);
+  const bool grid = q || dq || ddq;
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
+      // the tables the grid reads back, where the caller did not ask for them: the thread's own, reused like a lane's registers
+      std::vector<double> own_points(grid && !points ? (size_t)W_in * N : 0), own_cut(grid && !cut ? (size_t)W_in : 0),
+          own_knot(grid && !knot ? (size_t)W_in : 0);
+      for (int64_t b = b0; b < b1; ++b) {
+        const MpBlendRows o = {points ? points + b * W_in * N : (grid ? own_points.data() : nullptr),
+                               cut ? cut + b * W_in : (grid ? own_cut.data() : nullptr),
+                               knot ? knot + b * W_in : (grid ? own_knot.data() : nullptr)};
+        MpBlendState<N> S;
+        mp_blend_cpu<N>(M, tb, P, waypoints_in + b * W_in * N, count_in[b], o, S);
+        const int st = S.status, m = S.m;
+        const double len = S.length;
+        if (status) status[b] = st;
+        if (corner) corner[b] = S.corner;
+        if (count) count[b] = m;
+        if (length) length[b] = len;
+        if (halvings) halvings[b] = S.halvings;
+        if (evaluations) evaluations[b] = S.evals;
+        if (clearance) clearance[b] = S.clearance;
+        if (!grid) continue;
+        for (int i = 0; i < P.grid; ++i) {
+          double x[N], dx[N], ddx[N];
+          mp_blend_sample<N>(st, m, len, o.points, o.cut, o.knot, i, P.grid, x, dx, ddx);
+          const int64_t at = (b * P.grid + i) * N;
+          for (int j = 0; j < N; ++j) {
+            if (q) q[at + j] = x[j];
+            if (dq) dq[at + j] = dx[j];
+            if (ddq) ddq[at + j] = ddx[j];
+          }
+        }
+      }
+    });
+  })
+  return MP_OK;
+}
+
+}  // extern "C"

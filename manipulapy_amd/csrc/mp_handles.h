@@ -15,6 +15,7 @@
 #include "mp_rrt.h"
 #include "mp_shortcut.h"
 #include "mp_goal.h"
+#include "mp_blend.h"
 #include "mp_ik.h"
 #include "mp_toppra.h"
 #include "mp_model.h"
@@ -138,3 +139,7 @@ int mp_path_shortcut_check(const char* fn, int64_t w_in, uint32_t seed, int max_
 // message set (mp_cpu.cpp)
 int mp_goal_ik_check(const char* fn, int n, const double* lo, const double* hi, uint32_t seed, double eomg, double ev, double damping,
                      double step_cap, int max_iters, int max_attempts, double margin, double tol, MpGoalParams* out);
+// the corner blender's parameters (the edge check's among them), packed into `out`; 0, or MP_ERR_INVALID with the message set
+// (mp_cpu.cpp)
+int mp_path_blend_check(const char* fn, int64_t w_in, int64_t grid, double blend, int max_halvings, double margin, double tol,
+                        int max_steps, MpBlendParams* out);

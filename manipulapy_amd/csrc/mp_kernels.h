@@ -196,7 +196,7 @@ hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, const MpColDev
 // over the edges / problems, one evaluated configuration a trip.  mpk_queue_plan gives a kernel's dynamic LDS and the blocks of it the
 // device keeps resident (occupancy x compute_units); the caller settles the grid (`blocks`) from that, the count, its cap and the
 // workspace, and hands grid and LDS to the launch, which zeroes D.counter on the stream first and makes no runtime query.
-enum MpQueueKernel { MP_QUEUE_EDGES, MP_QUEUE_RRT, MP_QUEUE_SHORTCUT, MP_QUEUE_GOAL };
+enum MpQueueKernel { MP_QUEUE_EDGES, MP_QUEUE_RRT, MP_QUEUE_SHORTCUT, MP_QUEUE_GOAL, MP_QUEUE_BLEND };
 struct MpQueuePlan {
   unsigned lds;
   long resident;
@@ -219,3 +219,13 @@ struct MpGoalParams;
 hipError_t mpk_goal_ik(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* T_goal, const double* q_seed,
                        long problems, const MpGoalParams& P, int* status, double* q, int* attempts, int* iterations, int* converged,
                        double* pose_error, double* clearance, int* witness, long blocks, unsigned lds);
+// C2 corner blending of waypoint paths (csrc/mp_blend.h): the corners on the work queue (no workspace: one collision evaluation a
+// trip, a lane reads its own input rows), then mpk_path_blend_sample, one lane a grid point over problems x P.grid rows, which reads
+// status, count, points, cut, knot and length back (q, dq, ddq: any may be null).
+struct MpBlendParams;
+hipError_t mpk_path_blend(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
+                          long problems, const MpBlendParams& P, int* status, int* corner, int* count, double* points, double* cut,
+                          double* knot, double* length, int* halvings, int* evaluations, double* clearance, long blocks, unsigned lds);
+hipError_t mpk_path_blend_sample(hipStream_t s, int n, long problems, const MpBlendParams& P, const int* status, const int* count,
+                                 const double* points, const double* cut, const double* knot, const double* length, double* q, double* dq,
+                                 double* ddq);

@@ -26,6 +26,7 @@
 #include "mp_rrt.h"
 #include "mp_shortcut.h"
 #include "mp_goal.h"
+#include "mp_blend.h"
 
 namespace {
 
@@ -431,7 +432,7 @@ typedef MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpCol
 __device__ __forceinline__ MpColTablesConst mp_col_tables_const(const MpColSpheres* sph, const MpColPair* pairs, const MpColWorld* world) {
   return {(MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
 }
-// The scaffold of the one-wave work-queue kernels on the sphere model (k_collision_edges, k_rrt_connect, k_path_shortcut, k_goal_ik; DESIGN
+// The scaffold of the one-wave work-queue kernels on the sphere model (k_collision_edges, k_rrt_connect, k_path_shortcut, k_goal_ik, k_path_blend; DESIGN
 // §4.10).  Their dynamic LDS, sized by mp_col_queue_lds_bytes (mp_collision.h): the park of S centres, then the edge's n (n + 1) / 2
 // speed bounds [entry][lane] - per lane, but read at wave-uniform link numbers.  Each lane reads and writes only its own column of
 // both, so no barrier is needed.
@@ -738,6 +739,90 @@ __global__ __launch_bounds__(64) void k_goal_ik(const MpModel<double> M, const M
       S.phase = MP_GOAL_IDLE;
     }
   }
+}
+
+// ------------------------------------------------------- C2 corner blending of waypoint paths (float64, mp_blend.h)
+// One wave per block and the work queue of k_collision_edges / k_goal_ik: a lane without a problem takes the next index from the
+// device counter and screens, compacts and sets it up (mp_blend_begin), every trip of the loop makes ONE collision evaluation of the
+// lane's running attempt, and a finished lane writes its row and fetches another.  Dynamic LDS: the park and the speed bounds
+// (mp_col_queue_lanes).  A problem's state is its corner, in registers; the next corner is read from the lane's own input rows: no
+// workspace.  The loop of the kernel ends for the whole wave at once, when no lane holds a problem and the queue is empty; it ends
+// because the counter only grows and every problem ends within (count_in - 2) (max_halvings + 1) max_steps trips.
+template <int N>
+__global__ __launch_bounds__(64) void k_path_blend(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
+                                                   const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
+                                                   const double* __restrict__ waypoints_in, const int* __restrict__ count_in,
+                                                   long problems, const MpBlendParams P, int* __restrict__ status,
+                                                   int* __restrict__ corner, int* __restrict__ count, double* __restrict__ points,
+                                                   double* __restrict__ cut, double* __restrict__ knot, double* __restrict__ length,
+                                                   int* __restrict__ halvings, int* __restrict__ evaluations,
+                                                   double* __restrict__ clearance, unsigned long long* __restrict__ next) {
+  extern __shared__ __attribute__((aligned(16))) double mp_blend_lds[];
+  const int lane = (int)threadIdx.x;
+  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  MpColQueueLanes Q = mp_col_queue_lanes(mp_blend_lds, lane, tb.sph->S);
+  const MpWaveOpsLanes W{};
+  MpBlendState<N> S;
+  S.phase = MP_BL_IDLE;
+  bool have = false, dry = false;
+  long row = 0;
+  int cin = 0;
+  MpBlendRows o = {nullptr, nullptr, nullptr};
+  for (;;) {
+    if (!have && !dry) {
+      row = (long)atomicAdd(next, 1ull);
+      if (row >= problems) {
+        dry = true;
+        row = 0;
+      } else {
+        cin = count_in[row];
+        o = {points != nullptr ? points + row * (long)P.w_in * N : nullptr, cut != nullptr ? cut + row * (long)P.w_in : nullptr,
+             knot != nullptr ? knot + row * (long)P.w_in : nullptr};
+        mp_blend_begin<N>(M, tb.sph, P, waypoints_in + row * (long)P.w_in * N, cin, S, Q.L, o);
+        have = true;
+      }
+    }
+    if (!W.wave_any(have)) break;
+    if (mp_blend_trip<N>(M, tb, P, waypoints_in + row * (long)P.w_in * N, cin, S, Q.park, Q.L, o)) {
+      if (status != nullptr) status[row] = S.status;
+      if (corner != nullptr) corner[row] = S.corner;
+      if (count != nullptr) count[row] = S.m;
+      if (length != nullptr) length[row] = S.length;
+      if (halvings != nullptr) halvings[row] = S.halvings;
+      if (evaluations != nullptr) evaluations[row] = S.evals;
+      if (clearance != nullptr) clearance[row] = S.clearance;
+      have = false;
+      S.phase = MP_BL_IDLE;
+    }
+  }
+}
+
+// The grid of the blended curves: one lane a grid point over problems x grid rows, one wave per block.  A lane finds its piece by a
+// binary search of the problem's knots, evaluates the closed forms (mp_blend_sample) and the wave stores its 64 rows of q, dq/ds,
+// d2q/ds2 as whole lines (mp_wave_store_auto): 24 n bytes a row written, a few table entries read.  The lanes of the last, partial
+// wave that have no row recompute the last one and store nothing.
+template <int N>
+__global__ __launch_bounds__(64) void k_path_blend_sample(long problems, int grid, int w_in, const int* __restrict__ status,
+                                                          const int* __restrict__ count, const double* __restrict__ points,
+                                                          const double* __restrict__ cut, const double* __restrict__ knot,
+                                                          const double* __restrict__ length, double* __restrict__ q,
+                                                          double* __restrict__ dq, double* __restrict__ ddq) {
+  __shared__ __attribute__((aligned(16))) char lds[MP_WAVE_LDS_BYTES];
+  const int lane = (int)threadIdx.x;
+  const long rows = problems * grid;
+  const long row0 = (long)blockIdx.x * 64;
+  if (row0 >= rows) return;
+  const long left = rows - row0;
+  const int nvalid = left < 64 ? (int)left : 64;
+  const long rr = lane < nvalid ? row0 + lane : rows - 1;
+  const long b = rr / grid;
+  const int i = (int)(rr - b * grid);
+  double x[N], dx[N], ddx[N];
+  mp_blend_sample<N>(status[b], count[b], length[b], points + b * (long)w_in * N, cut + b * (long)w_in, knot + b * (long)w_in, i, grid, x, dx,
+                     ddx);
+  if (q != nullptr) mp_wave_store_auto<double, N>(q, row0, lane, nvalid, x, lds);
+  if (dq != nullptr) mp_wave_store_auto<double, N>(dq, row0, lane, nvalid, dx, lds);
+  if (ddq != nullptr) mp_wave_store_auto<double, N>(ddq, row0, lane, nvalid, ddx, lds);
 }
 
 // ------------------------------------------------------- operational-space dynamics and torque (float64, mp_opspace.h)
@@ -1622,12 +1707,13 @@ hipError_t mpk_queue_plan(MpQueueKernel kernel, int n, int S, int compute_units,
       case MP_QUEUE_RRT: return queue_plan(&k_rrt_connect<N>, N, S, compute_units, plan);
       case MP_QUEUE_SHORTCUT: return queue_plan(&k_path_shortcut<N>, N, S, compute_units, plan);
       case MP_QUEUE_GOAL: return queue_plan(&k_goal_ik<N>, N, S, compute_units, plan);
+      case MP_QUEUE_BLEND: return queue_plan(&k_path_blend<N>, N, S, compute_units, plan);
     }
   })
   return hipErrorInvalidValue;
 }
 
-// The four queue launches: `blocks` is the grid the caller has settled on (the plan's resident blocks, the count, its cap and the
+// The five queue launches: `blocks` is the grid the caller has settled on (the plan's resident blocks, the count, its cap and the
 // workspace), `lds` the plan's dynamic LDS.  They zero the queue counter on the stream and launch; no runtime query.
 static hipError_t queue_reset(hipStream_t s, const MpColDevice& D, long blocks) {
   if (D.S < 1 || D.S > MP_COL_MAX_SPHERES || blocks < 1) return hipErrorInvalidValue;
@@ -1684,6 +1770,31 @@ hipError_t mpk_goal_ik(hipStream_t s, const MpModel<double>& M, const MpColDevic
   MP_DISPATCH_N(M.n, {
     hipLaunchKernelGGL((k_goal_ik<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, T_goal, q_seed, problems, P,
                        status, q, attempts, iterations, converged, pose_error, clearance, witness, D.counter);
+  })
+  return hipGetLastError();
+}
+
+hipError_t mpk_path_blend(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
+                          long problems, const MpBlendParams& P, int* status, int* corner, int* count, double* points, double* cut,
+                          double* knot, double* length, int* halvings, int* evaluations, double* clearance, long blocks, unsigned lds) {
+  if (problems <= 0) return hipSuccess;
+  const hipError_t e = queue_reset(s, D, blocks);
+  if (e != hipSuccess) return e;
+  MP_DISPATCH_N(M.n, {
+    hipLaunchKernelGGL((k_path_blend<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
+                       problems, P, status, corner, count, points, cut, knot, length, halvings, evaluations, clearance, D.counter);
+  })
+  return hipGetLastError();
+}
+
+hipError_t mpk_path_blend_sample(hipStream_t s, int n, long problems, const MpBlendParams& P, const int* status, const int* count,
+                                 const double* points, const double* cut, const double* knot, const double* length, double* q, double* dq,
+                                 double* ddq) {
+  if (problems <= 0) return hipSuccess;
+  const unsigned gb = (unsigned)((problems * P.grid + 63) / 64);
+  MP_DISPATCH_N(n, {
+    hipLaunchKernelGGL((k_path_blend_sample<N>), dim3(gb), dim3(64), 0, s, problems, P.grid, P.w_in, status, count, points, cut, knot,
+                       length, q, dq, ddq);
   })
   return hipGetLastError();
 }

@@ -608,6 +608,47 @@ class OptimizedTrajectoryPlanning:
                               cnt, margin, tol, max_iters=max_iters, min_gain=min_gain,
                               max_waypoints=max_waypoints, max_steps=max_steps, seed=seed)
 
+    def batch_blend_path(self, waypoints, count, collision_model, N: int, margin: float = 0.0, tol: float = 1e-3, *, blend: float = 0.5,
+                         max_halvings: int = 6, max_steps: int = 64) -> Dict[str, np.ndarray]:
+        """Turns B piecewise-linear joint-space paths (B, W, n) with `count` (B,) real waypoints each - `batch_plan_path`'s or
+        `batch_shortcut_path`'s "waypoints" and "count" - into twice-differentiable curves under a collision.SphereCollisionModel
+        (SphereCollisionModel.blend_paths) and samples them on N grid points, all B paths in one call.  {"status", "corner", "count",
+        "points", "cut", "knot", "length", "halvings", "evaluations", "clearance", "q", "dq", "ddq" (B, N, n)}: rows that were not
+        solved come back skipped, and "q", "dq", "ddq" go straight into `batch_time_optimal_parameterization`.  The input paths
+        themselves are not checked."""
+        wp = np.asarray(waypoints, dtype=np.float64)
+        cnt = np.asarray(count)
+        n = collision_model.n
+        if wp.ndim != 3 or wp.shape[2] != n or cnt.shape != (wp.shape[0],):
+            raise ValueError(f"waypoints must be (B, W, {n}) and count (B,); got {wp.shape} and {cnt.shape}")
+        return self._dispatch("planning.blend_paths", collision_model, np.ascontiguousarray(wp), cnt, N, margin, tol, blend=blend,
+                              max_halvings=max_halvings, max_steps=max_steps)
+
+    def batch_time_optimal_path(self, waypoints, count, collision_model, N: int, velocity_limits, torque_limits=None,
+                                acceleration_limits=None, margin: float = 0.0, tol: float = 1e-3, *, blend: float = 0.5,
+                                max_halvings: int = 6, max_steps: int = 64, sd_start=0.0, sd_end=0.0, g=None,
+                                Ftip=None) -> Dict[str, Dict[str, np.ndarray]]:
+        """`batch_blend_path`, then `batch_time_optimal_parameterization` of the curves it made: {"blend": its dict, "timing": the
+        parameterisation's dict over all B rows}.  Only the rows whose blend status is 0 (done) or 1 (straight) are timed; every
+        other row - skipped, a point, blocked, a reversal, invalid - keeps its blend status and comes back with NaN in every real
+        timing output and -1 in the timing status.  sd_start / sd_end: scalars or (B,)."""
+        bl = self.batch_blend_path(waypoints, count, collision_model, N, margin, tol, blend=blend, max_halvings=max_halvings,
+                                   max_steps=max_steps)
+        B = bl["status"].shape[0]
+        rows = np.flatnonzero((bl["status"] == 0) | (bl["status"] == 1))
+        pick = lambda v: v if np.ndim(v) == 0 else np.asarray(v, dtype=np.float64)[rows]  # noqa: E731
+        n, G = bl["q"].shape[2], bl["q"].shape[1]
+        shapes = {"sd2": (G,), "sdd": (G,), "time": (G,), "duration": (), "velocities": (G, n), "accelerations": (G, n),
+                  "torques": (G, n), "controllable": (G, 2)}
+        timing = {k: np.full((B,) + shape, np.nan) for k, shape in shapes.items()}
+        timing["status"] = np.full(B, -1, dtype=np.int32)
+        if len(rows):
+            part = self.batch_time_optimal_parameterization(bl["q"][rows], bl["dq"][rows], bl["ddq"][rows], velocity_limits,
+                                                            torque_limits, acceleration_limits, pick(sd_start), pick(sd_end), g, Ftip)
+            for k, v in part.items():
+                timing[k][rows] = v
+        return {"blend": bl, "timing": timing}
+
     def _planning_box(self, finite_limit: float):
         """This planner's joint limits as a finite box: an open or non-finite limit clipped to +-`finite_limit` (batch_plan_path's rule)."""
         lim = np.nan_to_num(np.asarray(self.joint_limits, dtype=np.float64), nan=0.0, posinf=finite_limit, neginf=-finite_limit)

@@ -327,6 +327,10 @@ def _launch_path_shortcut_cpu(cm, waypoints, count, margin, tol, **kw):
     return _hip.cpu_path_shortcut(cm.model, cm.handle, waypoints, count, margin, tol, **kw)
 
 
+def _launch_path_blend_cpu(cm, waypoints, count, N, margin, tol, **kw):
+    return _hip.cpu_path_blend(cm.model, cm.handle, waypoints, count, N, margin, tol, **kw)
+
+
 def _launch_goal_ik_cpu(cm, T_goal, q_seed, lo, hi, margin, tol, **kw):
     return _hip.cpu_goal_ik(cm.model, cm.handle, T_goal, q_seed, lo, hi, margin, tol, **kw)
 
@@ -512,6 +516,12 @@ def _launch_path_shortcut_gpu(cm, waypoints, count, margin, tol, **kw):
     return ctx.path_shortcut_arrays(cm.model, cm.handle, waypoints, count, margin, tol, **kw)
 
 
+def _launch_path_blend_gpu(cm, waypoints, count, N, margin, tol, **kw):
+    ctx = get_context()
+    cm.sync_world(ctx)
+    return ctx.path_blend_arrays(cm.model, cm.handle, waypoints, count, N, margin, tol, **kw)
+
+
 def _launch_goal_ik_gpu(cm, T_goal, q_seed, lo, hi, margin, tol, **kw):
     ctx = get_context()
     cm.sync_world(ctx)
@@ -663,6 +673,9 @@ def _build_kernel_registry() -> KernelRegistry:
         # collision-free goal configurations for pose goals, each decided by the planner's own zero-edge check (csrc/mp_goal.h); the
         # name sorts after the pinned head of the name list
         ("planning.goal_configurations", "mp_goal_ik_host_f64", _launch_goal_ik_gpu, _launch_goal_ik_cpu),
+        # C2 corner blending of waypoint paths, every blend proven by the edge check, sampled for the time-optimal parameterisation
+        # (csrc/mp_blend.h); the name sorts after the pinned head of the name list
+        ("planning.blend_paths", "mp_path_blend_host_f64", _launch_path_blend_gpu, _launch_path_blend_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):
