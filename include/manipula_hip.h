@@ -1069,6 +1069,78 @@ int mp_path_blend_cpu_f64(const mp_model* model, const mp_collision* h, const do
                           int32_t* status, int32_t* corner, int32_t* count, double* points, double* cut, double* knot, double* length,
                           int32_t* halvings, int32_t* evaluations, double* clearance, double* q, double* dq, double* ddq, int nthreads);
 
+/* ---- batched fixed-rate sampling of time-optimal trajectories (float64, models of 1..8 joints - MP_ERR_UNSUPPORTED above that;
+ * generic kernels only, no run-time specialisation; csrc/mp_sample.h).  B timed paths in, B trajectories out whose row k is the
+ * time k dt: s, sd, sdd, q, qd, qdd and the full inverse dynamics of the row, on at most M rows a path.  The kernel, the CPU twin
+ * and the tests' NumPy oracle implement exactly the contract below.
+ * Per path: t (B, N) and x = sd^2 (B, N), batch-major, as mp_toppra_* returns them (t, x) on the grid s_i = i / (N - 1),
+ *   D = 1 / (N - 1).  Per launch: N in 3..2^31-1, dt > 0 and finite, M in 1..2^31-1, B M n and B N n below 2^60.  Anything else is
+ *   MP_ERR_INVALID with a message.
+ * The geometry comes from one of two sources, chosen by which group of pointers is given (both groups, neither, or a group that is
+ *   given in part: MP_ERR_INVALID):
+ *   grid:  q, dq, ddq (B, N, n), the arrays the parameterisation read.  Between grid points i and i + 1 the path is the quintic
+ *     Hermite interpolant in s - the one quintic that matches q, q' and q'' at both ends; it is C2 across grid points and exact for
+ *     a path that is a polynomial of degree <= 5 in s on the interval.  At the left end of an interval it is q_i bit for bit.
+ *   curve: blend_status, blend_count (B) int32, points (B, W_in, n), cut, knot (B, W_in), length (B): the tables of
+ *     mp_path_blend_* (W_in in 1..65536).  The path is that contract's closed-form curve, evaluated at the real parameter
+ *     sigma = s Sigma by the formulas of its step 6 with s in the place of i / (N - 1); s <= 0 and s >= 1 are r_0 and r_{m-1} bit for
+ *     bit.  The samples lie on the curve whose blends were proven free, not on an interpolant of its grid.
+ * 1 Screen, in this order.  NaN anywhere in the path's t or x (a parameterisation status != 0), or (curve) a blend status other than
+ *   DONE, STRAIGHT, POINT or a count outside 1..W_in: UNTIMED.  +inf in t (the interior stop the parameterisation allows): STOPS.
+ *   t_0 != 0, a t_{i+1} < t_i, a negative or infinite x, (grid) a non-finite value in q, dq, ddq, (curve) a non-finite length, or
+ *   T / dt >= 2^31 - 2 (the count would not fit): INVALID.  Such a path has NaN in every real output and 0 in count and needed.
+ * 2 T = t_{N-1}.  k_end = the smallest integer k >= 0 with (double)k * dt >= T, computed as k = ceil(T / dt); if k > 0 and
+ *   (double)(k - 1) * dt >= T then k - 1, else if (double)k * dt < T then k + 1: a function of the IEEE products alone.
+ *   needed = k_end + 1, count = min(needed, M), status OK, or TRUNCATED when needed > M.  needed is always reported.
+ * 3 Row k < M, tau_k = (double)k * dt.  tau_k >= T: the HOLD row - s = 1, sd = sdd = 0, q = the path's end point (q_{N-1} / r_{m-1},
+ *   bit for bit), qd = qdd = 0: the robot at rest at the end, whatever sd_end the parameterisation was given (a path timed to
+ *   arrive with speed still stops here: a controller that runs past the last sample must find a configuration it can hold).
+ *   Rows count..M-1 of an OK path are hold rows, as the planner pads a path by repeating its goal.  Otherwise the MOVING row:
+ *   i = the largest index in 0..N-2 with t_i <= tau_k (binary search), delta = tau_k - t_i, r = sqrt(x_i),
+ *   ubar = (x_{i+1} - x_i) / (2 D), sigma = clamp((r + 0.5 ubar delta) delta, 0, D), s = i / (N - 1) + sigma,
+ *   sd = max(r + ubar delta, 0), sdd = ubar; then qd = q'(s) sd, qdd = q'(s) ubar + q''(s) sd^2.  ubar comes from the two x values
+ *   and not from the stored u: the forward pass clips x_{i+1}, and only ubar reproduces the stored time stamps
+ *   (r + ubar (t_{i+1} - t_i) = sqrt(x_{i+1})).
+ * 4 torques = the inverse dynamics of the row at (q, qd, qdd) with the call's g and Ftip (either may be NULL: -9.81 z, no wrench):
+ *   one Newton-Euler recursion over the link frames from the row's own sin / cos - not an interpolation of the grid's torques, so
+ *   that a limit missed between grid points shows.  Without torques the recursion is not compiled in.
+ * Per path (every output may be NULL; at least one is needed):
+ *     status (B) int32                   MP_SAMPLE_OK 0, _TRUNCATED 1, _STOPS 2, _UNTIMED 3, _INVALID -1
+ *     count, needed (B) int32
+ *     s, sd, sdd (B, M)
+ *     positions, velocities, accelerations, torques (B, M, n), batch-major
+ *   A path's result depends on its own content only.  No output may overlap an input.
+ * mp_trajectory_sample_f64: device arrays, 16-byte aligned.  One launch on the compute stream, one lane a row, a path's screen shared
+ *   by the lanes of a wave; max_blocks > 0 caps the grid.  Models of 7 and 8 joints, where the fused recursion was measured slower:
+ *   when positions, velocities, accelerations and torques are all given, the torques come from a second launch, the inverse-dynamics
+ *   kernel over the rows just written (same contract: the inverse dynamics of the row).  Asynchronous, allocates nothing, may be
+ *   captured into a launch graph.
+ *   mp_trajectory_sample_host_f64: host arrays, device memory from the context's pool.  mp_trajectory_sample_cpu_f64: the kernel's
+ *   per-path and per-row code on the host, no context. */
+#define MP_SAMPLE_OK 0
+#define MP_SAMPLE_TRUNCATED 1
+#define MP_SAMPLE_STOPS 2
+#define MP_SAMPLE_UNTIMED 3
+#define MP_SAMPLE_INVALID (-1)
+int mp_trajectory_sample_f64(mp_ctx* ctx, const mp_model* model, const double* d_t, const double* d_x, int64_t B, int64_t N, const double* d_q,
+                             const double* d_dq, const double* d_ddq, const int32_t* d_blend_status, const int32_t* d_blend_count,
+                             const double* d_points, const double* d_cut, const double* d_knot, const double* d_length, int64_t W_in,
+                             double dt, int64_t M, const double* g, const double* Ftip, int max_blocks, int32_t* d_status,
+                             int32_t* d_count, int32_t* d_needed, double* d_s, double* d_sd, double* d_sdd, double* d_positions,
+                             double* d_velocities, double* d_accelerations, double* d_torques);
+int mp_trajectory_sample_host_f64(mp_ctx* ctx, const mp_model* model, const double* t, const double* x, int64_t B, int64_t N, const double* q,
+                                  const double* dq, const double* ddq, const int32_t* blend_status, const int32_t* blend_count,
+                                  const double* points, const double* cut, const double* knot, const double* length, int64_t W_in,
+                                  double dt, int64_t M, const double* g, const double* Ftip, int32_t* status, int32_t* count,
+                                  int32_t* needed, double* s, double* sd, double* sdd, double* positions, double* velocities,
+                                  double* accelerations, double* torques);
+int mp_trajectory_sample_cpu_f64(const mp_model* model, const double* t, const double* x, int64_t B, int64_t N, const double* q,
+                                 const double* dq, const double* ddq, const int32_t* blend_status, const int32_t* blend_count,
+                                 const double* points, const double* cut, const double* knot, const double* length, int64_t W_in, double dt,
+                                 int64_t M, const double* g, const double* Ftip, int32_t* status, int32_t* count, int32_t* needed,
+                                 double* s, double* sd, double* sdd, double* positions, double* velocities, double* accelerations,
+                                 double* torques, int nthreads);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new; the reference is single-device) ------
  * Trajectory batches are sharded over ranks with no exchange during compute; the only collective is
  * the all-gather that reassembles the torque history.  Rank 0 creates the id, the launcher

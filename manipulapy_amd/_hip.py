@@ -194,6 +194,9 @@ SIGNATURES = {
     "mp_path_blend_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int] + [_vp] * 13),
     "mp_path_blend_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _vp, _i64, _i64, _i64, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "mp_path_blend_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _vp, _i64, _i64, _i64, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
+    "mp_trajectory_sample_f64": (ctypes.c_int, [_vp] * 4 + [_i64, _i64] + [_vp] * 9 + [_i64, ctypes.c_double, _i64, _c_dp, _c_dp, ctypes.c_int] + [_vp] * 10),
+    "mp_trajectory_sample_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _i64, _i64, _c_dp, _c_dp, _c_dp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, ctypes.c_double, _i64, _c_dp, _c_dp, _vp, _vp, _vp] + [_c_dp] * 7),
+    "mp_trajectory_sample_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _i64, _i64, _c_dp, _c_dp, _c_dp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, ctypes.c_double, _i64, _c_dp, _c_dp, _vp, _vp, _vp] + [_c_dp] * 7 + [ctypes.c_int]),
     "mp_goal_ik_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_goal_ik_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _c_dp, _vp, _vp, _vp, _c_dp, _c_dp, _vp]),
     "mp_goal_ik_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _c_dp, _vp, _vp, _vp, _c_dp, _c_dp, _vp, ctypes.c_int]),
@@ -789,6 +792,28 @@ class HipContext:
         by tests/test_gpu_blend.py.)"""
         return _path_blend((self.handle,), self.lib.mp_path_blend_host_f64, model, collision, waypoints, count, N, margin, tol, blend,
                            max_halvings, max_steps, want)
+
+    def trajectory_sample(self, model, d_t, d_x, paths, N, dt, M, *, d_q=None, d_dq=None, d_ddq=None, d_blend_status=None,
+                          d_blend_count=None, d_points=None, d_cut=None, d_knot=None, d_length=None, w_in: int = 0, g=None, Ftip=None,
+                          max_blocks: int = 0, d_status=None, d_count=None, d_needed=None, d_s=None, d_sd=None, d_sdd=None,
+                          d_positions=None, d_velocities=None, d_accelerations=None, d_torques=None):
+        """Fixed-rate sampling of timed paths on device buffers (float64; csrc/mp_sample.h, contract in include/manipula_hip.h):
+        d_t, d_x (paths, N) as the parameterisation returns "time" and "sd2"; the geometry is EITHER d_q / d_dq / d_ddq (paths, N, n)
+        OR the blend's tables d_blend_status / d_blend_count (paths) int32, d_points (paths, w_in, n), d_cut / d_knot (paths, w_in),
+        d_length (paths).  Outputs status / count / needed (paths) int32, s / sd / sdd (paths, M), positions / velocities /
+        accelerations / torques (paths, M, n), each may be None (at least one given).  `max_blocks` > 0 caps the grid.  Asynchronous,
+        allocates nothing, capturable."""
+        _check(self.lib.mp_trajectory_sample_f64(self.handle, model.handle, _p(d_t), _p(d_x), int(paths), int(N), _p(d_q), _p(d_dq), _p(d_ddq),
+                                                 _p(d_blend_status), _p(d_blend_count), _p(d_points), _p(d_cut), _p(d_knot), _p(d_length),
+                                                 int(w_in), float(dt), int(M), _dptr(_vec_or_none(g, 3, "g")),
+                                                 _dptr(_vec_or_none(Ftip, 6, "Ftip")), int(max_blocks), _p(d_status), _p(d_count),
+                                                 _p(d_needed), _p(d_s), _p(d_sd), _p(d_sdd), _p(d_positions), _p(d_velocities),
+                                                 _p(d_accelerations), _p(d_torques)))
+
+    def trajectory_sample_arrays(self, model, t, x, dt, M, *, path=None, curve=None, g=None, Ftip=None, want=None):
+        """The same on host arrays (mp_trajectory_sample_host_f64) through the context's pool: a dict of the outputs named in `want`
+        (default: all of SAMPLE_OUTPUTS).  Its equality with the device form is held by tests/test_gpu_sample.py."""
+        return _trajectory_sample((self.handle,), self.lib.mp_trajectory_sample_host_f64, model, t, x, dt, M, path, curve, g, Ftip, want)
 
     def goal_ik(self, model, collision, d_T_goal, d_q_seed, problems, lo, hi, margin, tol, *, eomg, ev, damping, step_cap, max_iters,
                 max_attempts, seed, max_blocks: int = 0, d_status=None, d_q=None, d_attempts=None, d_iterations=None, d_converged=None,
@@ -1724,6 +1749,81 @@ def cpu_path_blend(model: "HipModel", collision: "HipCollision", waypoints, coun
     """CPU twin of HipContext.path_blend_arrays."""
     return _path_blend((), load_library().mp_path_blend_cpu_f64, model, collision, waypoints, count, N, margin, tol, blend, max_halvings,
                        max_steps, want, nthreads)
+
+
+SAMPLE_OUTPUTS = ("status", "count", "needed", "s", "sd", "sdd", "positions", "velocities", "accelerations", "torques")
+SAMPLE_OK, SAMPLE_TRUNCATED, SAMPLE_STOPS, SAMPLE_UNTIMED, SAMPLE_INVALID = 0, 1, 2, 3, -1
+SAMPLE_CURVE_TABLES = ("status", "count", "points", "cut", "knot", "length")
+
+
+def sample_rows_needed(duration, dt) -> np.ndarray:
+    """`needed` of the sampler's contract for durations T (any shape) at period dt, by the entry's own rule: k_end + 1 with k_end the
+    smallest k >= 0 whose float64 product k * dt reaches T; 0 where T is not finite (or negative)."""
+    T = np.asarray(duration, dtype=np.float64)
+    dt = float(dt)
+    ok = np.isfinite(T) & (T >= 0)
+    Ts = np.where(ok, T, 0.0)
+    k = np.ceil(Ts / dt)
+    down = (k > 0) & ((k - 1.0) * dt >= Ts)
+    up = ~down & (k * dt < Ts)
+    k = k - down + up
+    return np.where(ok, k + 1, 0).astype(np.int64)
+
+
+def _trajectory_sample(lead, fn, model, t, x, dt, M, path, curve, g, Ftip, want, nthreads=None):
+    want = SAMPLE_OUTPUTS if want is None else tuple(want)
+    for w in want:
+        if w not in SAMPLE_OUTPUTS:
+            raise ValueError(f"unknown sample output {w!r}; choose from {SAMPLE_OUTPUTS}")
+    n = model.n
+    t = _as_c(t, np.float64, name="time")
+    if t.ndim != 2:
+        raise ValueError(f"time must be (paths, N); got {t.shape}")
+    B, N = t.shape
+    x = _as_c(x, np.float64, (B, N), "sd2")
+    geo = [None, None, None]
+    if path is not None:
+        if len(path) != 3:
+            raise ValueError("path must be the three arrays (q, dq, ddq)")
+        geo = [None if a is None else _as_c(a, np.float64, (B, N, n), name) for a, name in zip(path, ("q", "dq", "ddq"))]
+    tab, w_in = [None] * 6, 0
+    if curve is not None:
+        pts = curve.get("points")
+        if pts is not None:
+            pts = _as_c(pts, np.float64, name="points")
+            if pts.ndim != 3 or pts.shape[0] != B or pts.shape[2] != n:
+                raise ValueError(f"curve points must be ({B}, W, {n}); got {pts.shape}")
+            w_in = pts.shape[1]
+        else:
+            w_in = 0 if curve.get("cut") is None else np.shape(curve["cut"])[-1]
+        shapes = {"status": (B,), "count": (B,), "points": (B, w_in, n), "cut": (B, w_in), "knot": (B, w_in), "length": (B,)}
+        for i, k in enumerate(SAMPLE_CURVE_TABLES):
+            a = curve.get(k)
+            if a is not None:
+                tab[i] = _as_c(a, np.int32 if k in ("status", "count") else np.float64, shapes[k], "curve " + k)
+    rows = max(int(M), 0)  # (a value below 1 is the entry's to refuse)
+    whole = ("status", "count", "needed")
+    shapes = {"s": (B, rows), "sd": (B, rows), "sdd": (B, rows), "positions": (B, rows, n), "velocities": (B, rows, n),
+              "accelerations": (B, rows, n), "torques": (B, rows, n)}
+    out = {w: np.empty(shapes.get(w, (B,)), dtype=np.int32 if w in whole else np.float64) for w in want}
+    ptrs = []
+    for w in SAMPLE_OUTPUTS:
+        a = out.get(w)
+        ptrs.append(None if a is None else (a.ctypes.data_as(_vp) if w in whole else _dptr(a)))
+    iptr = lambda a: None if a is None else a.ctypes.data_as(_vp)  # noqa: E731
+    args = list(lead) + [model.handle, _dptr(t), _dptr(x), B, N, _dptr(geo[0]), _dptr(geo[1]), _dptr(geo[2]), iptr(tab[0]), iptr(tab[1]),
+                         _dptr(tab[2]), _dptr(tab[3]), _dptr(tab[4]), _dptr(tab[5]), int(w_in), float(dt), int(M),
+                         _dptr(_vec_or_none(g, 3, "g")), _dptr(_vec_or_none(Ftip, 6, "Ftip"))] + ptrs
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return out
+
+
+def cpu_trajectory_sample(model: "HipModel", t, x, dt, M, *, path=None, curve=None, g=None, Ftip=None, want=None,
+                          nthreads: int = 0) -> dict:
+    """CPU twin of HipContext.trajectory_sample_arrays."""
+    return _trajectory_sample((), load_library().mp_trajectory_sample_cpu_f64, model, t, x, dt, M, path, curve, g, Ftip, want, nthreads)
 
 
 GOAL_OUTPUTS = ("status", "q", "attempts", "iterations", "converged", "pose_error", "clearance", "witness")

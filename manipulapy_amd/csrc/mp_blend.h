@@ -405,3 +405,71 @@ MP_HD void mp_blend_sample(int status, int m, double length, const double* point
     }
   }
 }
+
+// a b + c d with the rounding pinned: one product, then one fused multiply-add.  Left as a sum of two products the compiler fuses
+// either of them, as the code around the sum suggests, and the kernel variants of the trajectory sampler (with and without the
+// torques) must round the geometry alike.
+MP_HD double mp_two_products(double a, double b, double c, double d) { return __builtin_fma(a, b, c * d); }
+
+// The same curve at a real parameter s in [0, 1] (sigma = s * length) of a problem that has one (m >= 1): the formulas of
+// mp_blend_sample, step 6 of the contract, with s in the place of i / (grid - 1).  s <= 0 and s >= 1 are the end points themselves,
+// bit for bit.  For the trajectory sampler (mp_sample.h); mp_blend_sample is not touched.  Sums of two products go through mp_two_products.
+template <int N>
+MP_HD void mp_blend_sample_at(int m, double length, const double* points, const double* cut, const double* knot, double s, double (&q)[N],
+                              double (&dq)[N], double (&ddq)[N]) {
+#pragma unroll
+  for (int j = 0; j < N; ++j) ddq[j] = 0.0;
+  if (m == 1) {
+    mp_blend_row<N>(points, 0, q);
+#pragma unroll
+    for (int j = 0; j < N; ++j) dq[j] = 0.0;
+    return;
+  }
+  const bool first = !(s > 0.0), last = !first && s >= 1.0;
+  const double sigma = s * length;
+  int k;
+  if (first) {
+    k = 0;
+  } else if (last) {
+    k = m - 2;
+  } else {
+    int lo = 0, hi = m - 2;
+    while (lo < hi) {  // the largest k in 0..m-2 with knot[k] <= sigma
+      const int mid = (lo + hi + 1) >> 1;
+      if (knot[mid] <= sigma) lo = mid;
+      else hi = mid - 1;
+    }
+    k = lo;
+  }
+  double rk[N], rn[N], un[N], ln;
+  mp_blend_row<N>(points, k, rk);
+  mp_blend_row<N>(points, k + 1, rn);
+  mp_blend_segment<N>(rk, rn, un, ln);  // u_{k+1}
+  if (first || last) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) { q[j] = first ? rk[j] : rn[j]; dq[j] = length * un[j]; }
+    return;
+  }
+  const double ck = cut[k], at = sigma - knot[k];
+  if (k >= 1 && at < 2.5 * ck) {
+    double rp[N], up[N], lp;
+    mp_blend_row<N>(points, k - 1, rp);
+    mp_blend_segment<N>(rp, rk, up, lp);  // u_k
+    const double u = at / (2.5 * ck), w = 1.0 - u;
+    mp_blend_curve_point<N>(rk, up, un, ck, u, q);
+    const double fa = (w * w * w) * (1.0 + 3.0 * u), fb = (u * u * u) * (4.0 - 3.0 * u);
+    const double g = (length * length) * 4.8 * (u * w);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      dq[j] = length * mp_two_products(up[j], fa, un[j], fb);
+      ddq[j] = g * mp_two_products(u, un[j], -w, up[j]) / ck;
+    }
+  } else {
+    const double t = ((ck + sigma) - knot[k]) - 2.5 * ck;
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      q[j] = rk[j] + t * un[j];
+      dq[j] = length * un[j];
+    }
+  }
+}

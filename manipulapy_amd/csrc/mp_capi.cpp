@@ -3435,6 +3435,101 @@ int mp_path_blend_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, 
   });
 }
 
+}  // extern "C"
+
+// ---- fixed-rate sampling of timed paths (mp_sample.h): one launch, no workspace.  I: checked and packed by
+// mp_trajectory_sample_check, its pointers filled in by the caller.  The torques: up to 6 joints the same launch writes them (the
+// fused form: measured 0.75 - 0.82 of the time of the launch without them followed by the inverse-dynamics kernel over the same rows,
+// xArm6).  From 7 joints on the fused recursion needs more than 256 registers and was measured 1.6 - 1.9 times SLOWER than that
+// split form (Panda, 8 joints), so the entry runs the split form - k_traj_sample without torques, then k_id over the rows
+// it wrote - whenever the caller gave positions, velocities and accelerations for it to read; without one of them there is nowhere
+// to put the rows (the entry allocates nothing) and the fused kernel runs.  MANIPULAPY_HIP_SAMPLE_TORQUES=fused (read at every
+// call, so a captured graph keeps the variant it was captured with) selects the fused kernel throughout; it exists for
+// tools/sample_bench.py to time the loser.
+static bool sample_force_fused() {
+  const char* e = getenv("MANIPULAPY_HIP_SAMPLE_TORQUES");
+  return e && std::strcmp(e, "fused") == 0;
+}
+static int trajectory_sample_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const MpSampleIn& I, const double* g, const double* Ftip,
+                                  int max_blocks, const MpSampleOut& O) {
+  REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
+  if (I.B == 0) return MP_OK;
+  REQUIRE(I.t && I.x, "%s: null device pointer", fn);
+  REQUIRE(O.status || O.count || O.needed || O.s || O.sd || O.sdd || O.pos || O.vel || O.acc || O.tau, "%s: at least one output is required",
+          fn);
+  REQUIRE(aligned16(I.t) && aligned16(I.x) && aligned16(I.q) && aligned16(I.dq) && aligned16(I.ddq) && aligned16(I.bstatus) &&
+              aligned16(I.bcount) && aligned16(I.points) && aligned16(I.cut) && aligned16(I.knot) && aligned16(I.length) &&
+              aligned16(O.status) && aligned16(O.count) && aligned16(O.needed) && aligned16(O.s) && aligned16(O.sd) && aligned16(O.sdd) &&
+              aligned16(O.pos) && aligned16(O.vel) && aligned16(O.acc) && aligned16(O.tau),
+          "%s: device pointers must be 16-byte aligned", fn);
+  MpCall<double> c;
+  make_call<double>(model, g, Ftip, &c);
+  PROFILE_SCOPE(ctx, fn);
+  const bool split = O.tau && model->d.n >= 7 && O.pos && O.vel && O.acc && !sample_force_fused();
+  MpSampleOut W = O;
+  if (split) W.tau = nullptr;
+  HIP_TRY(mpk_traj_sample(ctx->compute, model->d, c, any_nonzero(Ftip), I.points != nullptr, I, W, (long)max_blocks));
+  if (split) HIP_TRY(mpk_id<double>(ctx->compute, model->d, c, any_nonzero(Ftip), O.pos, O.vel, O.acc, O.tau, (long)(I.B * I.M)));
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_trajectory_sample_f64(mp_ctx* ctx, const mp_model* model, const double* d_t, const double* d_x, int64_t B, int64_t N, const double* d_q,
+                             const double* d_dq, const double* d_ddq, const int32_t* d_blend_status, const int32_t* d_blend_count,
+                             const double* d_points, const double* d_cut, const double* d_knot, const double* d_length, int64_t W_in,
+                             double dt, int64_t M, const double* g, const double* Ftip, int max_blocks, int32_t* d_status,
+                             int32_t* d_count, int32_t* d_needed, double* d_s, double* d_sd, double* d_sdd, double* d_positions,
+                             double* d_velocities, double* d_accelerations, double* d_torques) {
+  const char* fn = "mp_trajectory_sample_f64";
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  MpSampleIn I;
+  if (int rc = mp_trajectory_sample_check(fn, B, N, W_in, dt, M, model->d.n, (d_q != nullptr) + (d_dq != nullptr) + (d_ddq != nullptr),
+                                          (d_blend_status != nullptr) + (d_blend_count != nullptr) + (d_points != nullptr) +
+                                              (d_cut != nullptr) + (d_knot != nullptr) + (d_length != nullptr), &I))
+    return rc;
+  I.t = d_t; I.x = d_x; I.q = d_q; I.dq = d_dq; I.ddq = d_ddq;
+  I.bstatus = d_blend_status; I.bcount = d_blend_count; I.points = d_points; I.cut = d_cut; I.knot = d_knot; I.length = d_length;
+  const MpSampleOut O = {d_status, d_count, d_needed, d_s, d_sd, d_sdd, d_positions, d_velocities, d_accelerations, d_torques};
+  return trajectory_sample_impl(fn, ctx, model, I, g, Ftip, max_blocks, O);
+}
+
+int mp_trajectory_sample_host_f64(mp_ctx* ctx, const mp_model* model, const double* t, const double* x, int64_t B, int64_t N, const double* q,
+                                  const double* dq, const double* ddq, const int32_t* blend_status, const int32_t* blend_count,
+                                  const double* points, const double* cut, const double* knot, const double* length, int64_t W_in,
+                                  double dt, int64_t M, const double* g, const double* Ftip, int32_t* status, int32_t* count,
+                                  int32_t* needed, double* s, double* sd, double* sdd, double* positions, double* velocities,
+                                  double* accelerations, double* torques) {
+  const char* fn = "mp_trajectory_sample_host_f64";
+  REQUIRE(ctx && model, "%s: null context or model", fn);
+  CTX_ENTER(ctx);
+  REQUIRE_SMALL(fn);
+  MpSampleIn I;
+  if (int rc = mp_trajectory_sample_check(fn, B, N, W_in, dt, M, model->d.n, (q != nullptr) + (dq != nullptr) + (ddq != nullptr),
+                                          (blend_status != nullptr) + (blend_count != nullptr) + (points != nullptr) + (cut != nullptr) +
+                                              (knot != nullptr) + (length != nullptr), &I))
+    return rc;
+  if (B == 0) return MP_OK;
+  REQUIRE(t && x, "%s: null host pointer", fn);
+  REQUIRE(status || count || needed || s || sd || sdd || positions || velocities || accelerations || torques,
+          "%s: at least one output is required", fn);
+  const size_t n = (size_t)model->d.n, ib = (size_t)B * sizeof(int32_t), db = (size_t)B * sizeof(double);
+  const size_t gb = (size_t)N * db, wb = (size_t)W_in * db, mb = (size_t)M * db;
+  HostCall hc(ctx);
+  I.t = hc.in(t, gb); I.x = hc.in(x, gb);
+  I.q = hc.in(q, gb * n); I.dq = hc.in(dq, gb * n); I.ddq = hc.in(ddq, gb * n);
+  I.bstatus = hc.in(blend_status, ib); I.bcount = hc.in(blend_count, ib);
+  I.points = hc.in(points, wb * n); I.cut = hc.in(cut, wb); I.knot = hc.in(knot, wb); I.length = hc.in(length, db);
+  MpSampleOut O;
+  O.status = hc.out(status, ib); O.count = hc.out(count, ib); O.needed = hc.out(needed, ib);
+  O.s = hc.out(s, mb); O.sd = hc.out(sd, mb); O.sdd = hc.out(sdd, mb);
+  O.pos = hc.out(positions, mb * n); O.vel = hc.out(velocities, mb * n); O.acc = hc.out(accelerations, mb * n);
+  O.tau = hc.out(torques, mb * n);
+  return hc.run([&] { return trajectory_sample_impl(fn, ctx, model, I, g, Ftip, 0, O); });
+}
+
 int mp_collision_set_world(mp_ctx* ctx, mp_collision* h, int O, const int32_t* kind, const double* params) {
   const char* fn = "mp_collision_set_world";
   REQUIRE(h, "%s: null collision handle", fn);

@@ -1418,3 +1418,72 @@ int mp_path_blend_cpu_f64(const mp_model* model, const mp_collision* h, const do
 }
 
 }  // extern "C"
+
+// ---- fixed-rate sampling of timed paths (mp_sample.h)
+int mp_trajectory_sample_check(const char* fn, int64_t B, int64_t grid, int64_t w_in, double dt, int64_t M, int n, int grid_given,
+                               int curve_given, MpSampleIn* out) {
+  REQUIRE(B >= 0, "%s: negative path count", fn);
+  REQUIRE(grid >= 3 && grid <= 2147483647LL, "%s: %lld grid points, outside 3..2^31-1", fn, (long long)grid);
+  REQUIRE(dt > 0.0 && std::isfinite(dt), "%s: dt must be positive and finite", fn);
+  REQUIRE(M >= 1 && M <= 2147483647LL, "%s: %lld sample rows a path, outside 1..2^31-1", fn, (long long)M);
+  const int64_t cap = (int64_t)1 << 60;
+  REQUIRE(B == 0 || (M <= cap / B / n && grid <= cap / B / n), "%s: %lld paths of %lld rows and %lld grid points are not addressable", fn,
+          (long long)B, (long long)M, (long long)grid);
+  REQUIRE(grid_given == 0 || grid_given == 3, "%s: the grid source needs q, dq and ddq, all three", fn);
+  REQUIRE(curve_given == 0 || curve_given == 6, "%s: the curve source needs status, count, points, cut, knot and length, all six", fn);
+  REQUIRE((grid_given != 0) != (curve_given != 0), "%s: exactly one source of the geometry must be given, the grid or the curve", fn);
+  REQUIRE(curve_given == 0 || (w_in >= 1 && w_in <= MP_BL_MAX_WAYPOINTS), "%s: %lld rows a path in the curve's tables, outside 1..65536", fn,
+          (long long)w_in);
+  MpSampleIn I;
+  std::memset(&I, 0, sizeof I);
+  I.dt = dt;
+  I.B = (long)B; I.M = (int)M; I.grid = (int)grid; I.w_in = curve_given ? (int)w_in : 0;
+  *out = I;
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_trajectory_sample_cpu_f64(const mp_model* model, const double* t, const double* x, int64_t B, int64_t N_grid, const double* q,
+                                 const double* dq, const double* ddq, const int32_t* blend_status, const int32_t* blend_count,
+                                 const double* points, const double* cut, const double* knot, const double* length, int64_t W_in, double dt,
+                                 int64_t M_rows, const double* g, const double* Ftip, int32_t* status, int32_t* count, int32_t* needed,
+                                 double* s, double* sd, double* sdd, double* positions, double* velocities, double* accelerations,
+                                 double* torques, int nthreads) {
+  const char* fn = "mp_trajectory_sample_cpu_f64";
+  if (int rc = mp_small_model(fn, model)) return rc;
+  MpSampleIn I;
+  if (int rc = mp_trajectory_sample_check(fn, B, N_grid, W_in, dt, M_rows, model->d.n, (q != nullptr) + (dq != nullptr) + (ddq != nullptr),
+                                          (blend_status != nullptr) + (blend_count != nullptr) + (points != nullptr) + (cut != nullptr) +
+                                              (knot != nullptr) + (length != nullptr), &I))
+    return rc;
+  if (B == 0) return MP_OK;
+  REQUIRE(t && x, "%s: null pointer", fn);
+  REQUIRE(status || count || needed || s || sd || sdd || positions || velocities || accelerations || torques,
+          "%s: at least one output is required", fn);
+  I.t = t; I.x = x; I.q = q; I.dq = dq; I.ddq = ddq;
+  I.bstatus = blend_status; I.bcount = blend_count; I.points = points; I.cut = cut; I.knot = knot; I.length = length;
+  const MpSampleOut O = {status, count, needed, s, sd, sdd, positions, velocities, accelerations, torques};
+  const MpModel<double>& M = model->d;
+  const MpCall<double> C = make_call<double>(model, g, Ftip);
+  const int tau = !torques ? MP_TS_NO_TAU : (any_nonzero(Ftip) ? MP_TS_TAU_FTIP : MP_TS_TAU);
+  const bool curve = points != nullptr;
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
+      for (int64_t b = b0; b < b1; ++b) {
+        if (curve) {
+          if (tau == MP_TS_NO_TAU) mp_ts_path_cpu<N, MP_TS_CURVE, MP_TS_NO_TAU>(M, C, I, O, (long)b);
+          else if (tau == MP_TS_TAU) mp_ts_path_cpu<N, MP_TS_CURVE, MP_TS_TAU>(M, C, I, O, (long)b);
+          else mp_ts_path_cpu<N, MP_TS_CURVE, MP_TS_TAU_FTIP>(M, C, I, O, (long)b);
+        } else {
+          if (tau == MP_TS_NO_TAU) mp_ts_path_cpu<N, MP_TS_GRID, MP_TS_NO_TAU>(M, C, I, O, (long)b);
+          else if (tau == MP_TS_TAU) mp_ts_path_cpu<N, MP_TS_GRID, MP_TS_TAU>(M, C, I, O, (long)b);
+          else mp_ts_path_cpu<N, MP_TS_GRID, MP_TS_TAU_FTIP>(M, C, I, O, (long)b);
+        }
+      }
+    });
+  })
+  return MP_OK;
+}
+
+}  // extern "C"

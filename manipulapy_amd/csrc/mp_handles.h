@@ -16,6 +16,7 @@
 #include "mp_shortcut.h"
 #include "mp_goal.h"
 #include "mp_blend.h"
+#include "mp_sample.h"
 #include "mp_ik.h"
 #include "mp_toppra.h"
 #include "mp_model.h"
@@ -143,3 +144,8 @@ int mp_goal_ik_check(const char* fn, int n, const double* lo, const double* hi, 
 // (mp_cpu.cpp)
 int mp_path_blend_check(const char* fn, int64_t w_in, int64_t grid, double blend, int max_halvings, double margin, double tol,
                         int max_steps, MpBlendParams* out);
+// the trajectory sampler's arguments, packed into `out` (the pointers are the caller's to fill in): the source is chosen by which group of
+// pointers is given - grid_given of the 3 grid arrays, curve_given of the 6 blend tables; 0, or MP_ERR_INVALID with the message set
+// (mp_cpu.cpp)
+int mp_trajectory_sample_check(const char* fn, int64_t B, int64_t grid, int64_t w_in, double dt, int64_t M, int n, int grid_given,
+                               int curve_given, MpSampleIn* out);

@@ -229,3 +229,9 @@ hipError_t mpk_path_blend(hipStream_t s, const MpModel<double>& M, const MpColDe
 hipError_t mpk_path_blend_sample(hipStream_t s, int n, long problems, const MpBlendParams& P, const int* status, const int* count,
                                  const double* points, const double* cut, const double* knot, const double* length, double* q, double* dq,
                                  double* ddq);
+// fixed-rate sampling of timed paths (csrc/mp_sample.h): one lane a (path, sample) row over I.B x I.M rows, the tiles of 64 rows
+// spread over at most `max_blocks` blocks (0: one block a tile).  curve: the geometry is the blend's tables, else the grid arrays.
+struct MpSampleIn;
+struct MpSampleOut;
+hipError_t mpk_traj_sample(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, bool curve, const MpSampleIn& I,
+                           const MpSampleOut& O, long max_blocks);

@@ -27,6 +27,7 @@
 #include "mp_shortcut.h"
 #include "mp_goal.h"
 #include "mp_blend.h"
+#include "mp_sample.h"
 
 namespace {
 
@@ -823,6 +824,52 @@ __global__ __launch_bounds__(64) void k_path_blend_sample(long problems, int gri
   if (q != nullptr) mp_wave_store_auto<double, N>(q, row0, lane, nvalid, x, lds);
   if (dq != nullptr) mp_wave_store_auto<double, N>(dq, row0, lane, nvalid, dx, lds);
   if (ddq != nullptr) mp_wave_store_auto<double, N>(ddq, row0, lane, nvalid, ddx, lds);
+}
+
+// ------------------------------------------------------- fixed-rate sampling of timed paths (float64, mp_sample.h)
+// One lane a (path, sample) row over B x M rows, one wave per block, a block takes the tiles of 64 rows blockIdx.x, + gridDim.x, ...
+// The 64 rows of a tile belong to paths bf..bl; the wave screens each of them once, its lanes sharing the scan of the path's tables
+// (flags OR-ed over the wave: the same bits as the twin's walk), and a lane keeps the flags of its own path.  Neighbouring lanes are
+// neighbouring samples of one path: their searches of the time stamps and their reads of the interval's rows hit the same lines.  The
+// rows go out as whole lines (mp_wave_store_auto), s / sd / sdd per lane (a tile's 64 values are one run), status / count / needed
+// by the lane that holds a path's row 0.  The lanes of the last, partial tile that have no row recompute the last one and store nothing.
+template <int N, int SOURCE, int TAU>
+__global__ __launch_bounds__(64) void k_traj_sample(const MpModel<double> M, const MpCall<double> C, const MpSampleIn I, const MpSampleOut O,
+                                                    long tiles) {
+  __shared__ __attribute__((aligned(16))) char lds[MP_WAVE_LDS_BYTES];
+  const int lane = (int)threadIdx.x;
+  const long rows = I.B * I.M;
+  for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long row0 = tile * 64, left = rows - row0;
+    const int nvalid = left < 64 ? (int)left : 64;
+    const long rr = lane < nvalid ? row0 + lane : rows - 1;
+    const long b = rr / I.M, k = rr - b * I.M;
+    const long bf = row0 / I.M, bl = (row0 + nvalid - 1) / I.M;
+    int flags = 0;
+    for (long p = bf; p <= bl; ++p) {
+      const int f = mp_ts_scan<SOURCE>(I, N, p, lane, 64);
+      const int all = (__any(f & MP_TS_F_NAN) ? MP_TS_F_NAN : 0) | (__any(f & MP_TS_F_STOP) ? MP_TS_F_STOP : 0) |
+                      (__any(f & MP_TS_F_BAD) ? MP_TS_F_BAD : 0);
+      if (p == b) flags = all;
+    }
+    const MpSampleHead H = mp_ts_head<SOURCE>(I, b, flags);
+    MpSampleRow<N> o;
+    mp_ts_row<N, SOURCE, TAU>(M, C, I, b, H, k, o);
+    if (k == 0 && lane < nvalid) {
+      if (O.status != nullptr) O.status[b] = H.status;
+      if (O.count != nullptr) O.count[b] = H.count;
+      if (O.needed != nullptr) O.needed[b] = H.needed;
+    }
+    if (lane < nvalid) {
+      if (O.s != nullptr) O.s[rr] = o.s;
+      if (O.sd != nullptr) O.sd[rr] = o.sd;
+      if (O.sdd != nullptr) O.sdd[rr] = o.sdd;
+    }
+    if (O.pos != nullptr) mp_wave_store_auto<double, N>(O.pos, row0, lane, nvalid, o.q, lds);
+    if (O.vel != nullptr) mp_wave_store_auto<double, N>(O.vel, row0, lane, nvalid, o.qd, lds);
+    if (O.acc != nullptr) mp_wave_store_auto<double, N>(O.acc, row0, lane, nvalid, o.qdd, lds);
+    if (TAU != MP_TS_NO_TAU) mp_wave_store_auto<double, N>(O.tau, row0, lane, nvalid, o.tau, lds);
+  }
 }
 
 // ------------------------------------------------------- operational-space dynamics and torque (float64, mp_opspace.h)
@@ -1795,6 +1842,27 @@ hipError_t mpk_path_blend_sample(hipStream_t s, int n, long problems, const MpBl
   MP_DISPATCH_N(n, {
     hipLaunchKernelGGL((k_path_blend_sample<N>), dim3(gb), dim3(64), 0, s, problems, P.grid, P.w_in, status, count, points, cut, knot,
                        length, q, dq, ddq);
+  })
+  return hipGetLastError();
+}
+
+// `ftip`: the call's wrench is not zero.  blocks: the grid the caller has settled on (the tiles of 64 rows, capped).
+template <int N, int SOURCE>
+static void launch_traj_sample(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const MpSampleIn& I,
+                               const MpSampleOut& O, long tiles, unsigned blocks) {
+  if (O.tau == nullptr) hipLaunchKernelGGL((k_traj_sample<N, SOURCE, MP_TS_NO_TAU>), dim3(blocks), dim3(64), 0, s, M, C, I, O, tiles);
+  else if (!ftip) hipLaunchKernelGGL((k_traj_sample<N, SOURCE, MP_TS_TAU>), dim3(blocks), dim3(64), 0, s, M, C, I, O, tiles);
+  else hipLaunchKernelGGL((k_traj_sample<N, SOURCE, MP_TS_TAU_FTIP>), dim3(blocks), dim3(64), 0, s, M, C, I, O, tiles);
+}
+hipError_t mpk_traj_sample(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, bool curve, const MpSampleIn& I,
+                           const MpSampleOut& O, long max_blocks) {
+  if (I.B <= 0) return hipSuccess;
+  const long tiles = (I.B * I.M + 63) / 64;
+  long blocks = tiles < 0x7fffffffL ? tiles : 0x7fffffffL;
+  if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
+  MP_DISPATCH_N(M.n, {
+    if (curve) launch_traj_sample<N, MP_TS_CURVE>(s, M, C, ftip, I, O, tiles, (unsigned)blocks);
+    else launch_traj_sample<N, MP_TS_GRID>(s, M, C, ftip, I, O, tiles, (unsigned)blocks);
   })
   return hipGetLastError();
 }

@@ -649,6 +649,68 @@ class OptimizedTrajectoryPlanning:
                 timing[k][rows] = v
         return {"blend": bl, "timing": timing}
 
+    def batch_sample_time_optimal(self, timing, dt: float, *, path=None, curve=None, max_samples: Optional[int] = None,
+                                  velocity_limits=None, g=None, Ftip=None) -> Dict[str, np.ndarray]:
+        """Turns B timed paths into B trajectories at the fixed period dt: row k is the time k dt (conventions in
+        include/manipula_hip.h, mp_trajectory_sample_*).  `timing`: the dict of `batch_time_optimal_parameterization` ("time", "sd2",
+        "duration" are read).  The geometry is either `path` = (q, dq, ddq), the (B, N, n) arrays that were timed - the samples lie
+        on their quintic Hermite interpolant - or `curve` = the dict of `batch_blend_path` - the samples lie on the blended curve
+        itself.  max_samples: the rows M a path gets; None takes the largest "needed" over the paths with a finite duration (1 if
+        there is none), so that no path is truncated.  Returns {"status" (0 ok, 1 truncated: more than M rows were needed, 2 stops:
+        the timing has an interior stop, 3 untimed: no timing or no curve, -1 invalid), "count", "needed" (B,) int32, "s", "sd",
+        "sdd" (B, M), "positions", "velocities", "accelerations", "torques" (B, M, n), "peak_torque_ratio" (B,)} and, with
+        `velocity_limits` (n), "peak_velocity_ratio" (B,).  Rows from "count" on repeat the path's end point at rest; a path without
+        samples is NaN.  "torques" is the inverse dynamics at every sample (g, Ftip as elsewhere), not an interpolation of the grid's
+        torques: "peak_torque_ratio" - the largest |torque_j| / limit_j over a path's samples against this planner's torque limits,
+        an infinite limit counting 0, NaN for a path without samples - above 1 says that the grid was too coarse for the path (raise
+        N).  "peak_velocity_ratio" is the same for |velocity_j| / velocity_limits_j."""
+        model = self._vjp_model("batch_sample_time_optimal")
+        t, x = np.asarray(timing["time"], dtype=np.float64), np.asarray(timing["sd2"], dtype=np.float64)
+        if t.ndim != 2 or x.shape != t.shape:
+            raise ValueError(f"timing['time'] and timing['sd2'] must both be (B, N); got {t.shape} and {x.shape}")
+        if (path is None) == (curve is None):
+            raise ValueError("batch_sample_time_optimal: give exactly one of path=(q, dq, ddq) and curve=<the dict of batch_blend_path>")
+        if not (np.isfinite(dt) and dt > 0):
+            raise ValueError("batch_sample_time_optimal: dt must be positive and finite")
+        if max_samples is None:
+            need = _hip.sample_rows_needed(np.asarray(timing["duration"], dtype=np.float64), dt)
+            max_samples = max(int(need.max()) if need.size else 0, 1)
+        if curve is not None:
+            curve = {k: curve[k] for k in _hip.SAMPLE_CURVE_TABLES}
+        out = self._dispatch("planning.time_optimal_samples", model, np.ascontiguousarray(t), np.ascontiguousarray(x), float(dt),
+                             int(max_samples), path=path, curve=curve, g=g, Ftip=Ftip)
+        tl = self._torque_limits_f64
+        out["peak_torque_ratio"] = self._peak_ratio(out["torques"], out["count"], tl[:, 1], tl[:, 0])
+        if velocity_limits is not None:
+            out["peak_velocity_ratio"] = self._peak_ratio(out["velocities"], out["count"], np.asarray(velocity_limits, dtype=np.float64))
+        return out
+
+    @staticmethod
+    def _peak_ratio(values, count, hi, lo=None) -> np.ndarray:
+        """max over a path's first `count` rows and the joints of value_j / hi_j (value_j >= 0) or value_j / lo_j (value_j < 0; lo =
+        -hi by default), 0 for an infinite limit; NaN for a path without rows."""
+        B, M, n = values.shape
+        hi = np.asarray(hi, dtype=np.float64)
+        lim = np.where(values >= 0, hi, -hi if lo is None else np.asarray(lo, dtype=np.float64))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ratio = np.where(np.isinf(lim), 0.0, values / lim)
+        live = np.arange(M)[None, :] < np.asarray(count)[:, None]
+        peak = np.where(live[:, :, None], ratio, -np.inf).reshape(B, -1).max(axis=1)
+        return np.where(np.asarray(count) > 0, peak, np.nan)
+
+    def batch_time_optimal_trajectory(self, waypoints, count, collision_model, N: int, dt: float, velocity_limits, torque_limits=None,
+                                      acceleration_limits=None, margin: float = 0.0, tol: float = 1e-3, *, blend: float = 0.5,
+                                      max_halvings: int = 6, max_steps: int = 64, max_samples: Optional[int] = None, g=None,
+                                      Ftip=None) -> Dict[str, Dict[str, np.ndarray]]:
+        """`batch_time_optimal_path` (blend, then time from rest to rest), then `batch_sample_time_optimal` of its result on the
+        blended curves at the period dt: {"blend", "timing", "samples"}, the three dicts over all B rows.  A row without a curve or
+        without a timing keeps its earlier status and comes back untimed (3) with NaN samples."""
+        both = self.batch_time_optimal_path(waypoints, count, collision_model, N, velocity_limits, torque_limits, acceleration_limits,
+                                            margin, tol, blend=blend, max_halvings=max_halvings, max_steps=max_steps, g=g, Ftip=Ftip)
+        both["samples"] = self.batch_sample_time_optimal(both["timing"], dt, curve=both["blend"], max_samples=max_samples,
+                                                         velocity_limits=velocity_limits, g=g, Ftip=Ftip)
+        return both
+
     def _planning_box(self, finite_limit: float):
         """This planner's joint limits as a finite box: an open or non-finite limit clipped to +-`finite_limit` (batch_plan_path's rule)."""
         lim = np.nan_to_num(np.asarray(self.joint_limits, dtype=np.float64), nan=0.0, posinf=finite_limit, neginf=-finite_limit)

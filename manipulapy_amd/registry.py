@@ -331,6 +331,10 @@ def _launch_path_blend_cpu(cm, waypoints, count, N, margin, tol, **kw):
     return _hip.cpu_path_blend(cm.model, cm.handle, waypoints, count, N, margin, tol, **kw)
 
 
+def _launch_trajectory_sample_cpu(model, t, x, dt, M, **kw):
+    return _hip.cpu_trajectory_sample(model, t, x, dt, M, **kw)
+
+
 def _launch_goal_ik_cpu(cm, T_goal, q_seed, lo, hi, margin, tol, **kw):
     return _hip.cpu_goal_ik(cm.model, cm.handle, T_goal, q_seed, lo, hi, margin, tol, **kw)
 
@@ -522,6 +526,10 @@ def _launch_path_blend_gpu(cm, waypoints, count, N, margin, tol, **kw):
     return ctx.path_blend_arrays(cm.model, cm.handle, waypoints, count, N, margin, tol, **kw)
 
 
+def _launch_trajectory_sample_gpu(model, t, x, dt, M, **kw):
+    return get_context().trajectory_sample_arrays(model, t, x, dt, M, **kw)
+
+
 def _launch_goal_ik_gpu(cm, T_goal, q_seed, lo, hi, margin, tol, **kw):
     ctx = get_context()
     cm.sync_world(ctx)
@@ -676,6 +684,9 @@ def _build_kernel_registry() -> KernelRegistry:
         # C2 corner blending of waypoint paths, every blend proven by the edge check, sampled for the time-optimal parameterisation
         # (csrc/mp_blend.h); the name sorts after the pinned head of the name list
         ("planning.blend_paths", "mp_path_blend_host_f64", _launch_path_blend_gpu, _launch_path_blend_cpu),
+        # fixed-rate sampling of the parameterisation's result: s, sd, sdd, q, qd, qdd and the row's own inverse dynamics at t = k dt
+        # (csrc/mp_sample.h; first argument: a HipModel); the name sorts after the pinned head of the name list
+        ("planning.time_optimal_samples", "mp_trajectory_sample_host_f64", _launch_trajectory_sample_gpu, _launch_trajectory_sample_cpu),
         ("trajectory.cartesian", "mp_cartesian_trajectory_host_f32", _launch_cartesian_gpu, _launch_cartesian_cpu),
         ("control.pd_regulation", "mp_pd_regulation_host_f64", _launch_pd_regulation_gpu, _launch_pd_regulation_cpu),
     ):
