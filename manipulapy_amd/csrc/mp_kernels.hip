@@ -1423,8 +1423,46 @@ __global__ __launch_bounds__(kBlock) void k_dyn_traj(const MpBigModel<float>* __
   mp_dyn_row_traj<CAP, HAS_FTIP>(*(MpBigConst<float>*)Mdev, C, start, end, b, r - b * Nt, Nt, Tf, method, pos, vel, acc, tau);
 }
 
-inline unsigned grid_for(long rows) { return (unsigned)((rows + kBlock - 1) / kBlock); }
+// ---------------------------------------------------------------------------------- launching
+constexpr int kWave = 64;  // the block of the kernels declared __launch_bounds__(64): one wave
 
+// The one grid rule: the blocks for `items` at `per_block` lanes or rows a block, rounded up (`y`: the grid's second dimension).
+// A grid holds at most 2^31 - 1 blocks along x; beyond that `ok` is false and launch() refuses.
+struct MpGrid { unsigned x, y; bool ok; };
+constexpr long kMaxGrid = 0x7fffffffL;
+constexpr long mp_blocks(long items, long per_block) { return items > 0 ? (items - 1) / per_block + 1 : 0; }
+constexpr MpGrid mp_grid(long items, long per_block, long y = 1) {
+  return {(unsigned)mp_blocks(items, per_block), (unsigned)y, mp_blocks(items, per_block) <= kMaxGrid};
+}
+// ... and a grid of a x b blocks along x (blocks per trajectory x trajectories, tiles x tiles): the product is checked
+constexpr MpGrid mp_grid2(long a, long b) {
+  return a < 0 || b < 0 || a > kMaxGrid || b > kMaxGrid ? MpGrid{0, 1, false} : mp_grid(a * b, 1);
+}
+static_assert(mp_grid(0, 64).x == 0 && mp_grid(0, 64).ok && mp_grid(1, 64).x == 1 && mp_grid(64, 64).x == 1 && mp_grid(65, 64).x == 2 &&
+              mp_grid(256, 256).x == 1 && mp_grid(257, 256).x == 2 && mp_grid(65, 64).y == 1 && mp_grid(65, 64).ok, "rounds up");
+static_assert(mp_grid(kMaxGrid * 64, 64).ok && mp_grid(kMaxGrid * 64, 64).x == 0x7fffffffu && !mp_grid(kMaxGrid * 64 + 1, 64).ok &&
+              mp_grid(kMaxGrid * 256, 256).ok && !mp_grid(kMaxGrid * 256 + 1, 256).ok, "2^31 - 1 blocks are the most");
+static_assert(mp_grid2(3, 5).x == 15 && mp_grid2(3, 5).ok && mp_grid2(0, 5).x == 0 && mp_grid2(kMaxGrid, 1).ok && !mp_grid2(kMaxGrid, 2).ok &&
+              mp_grid2(46340, 46340).ok && !mp_grid2(46341, 46341).ok && !mp_grid2(kMaxGrid + 1, 1).ok, "the product is what is bounded");
+
+// The one launch - the only place that spells it.  Typed on the kernel's own parameters P..., the arguments bound as const P& outside
+// template deduction: they convert to the kernel's types here exactly as at a launch written out (bool -> int, long -> unsigned, a
+// const T* const -> const T* __restrict__), a by-value struct such as the model is bound, not copied a second time, and a list that
+// does not fit does not compile.  No runtime query, no allocation.
+template <typename P> struct MpArg { typedef P type; };  // (keeps the arguments out of template deduction)
+template <typename... P>
+hipError_t launch(void (*kernel)(P...), MpGrid grid, int block, size_t lds, hipStream_t s, const typename MpArg<P>::type&... args) {
+  if (!grid.ok) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(kernel, dim3(grid.x, grid.y), dim3(block), lds, s, args...);
+  return hipGetLastError();
+}
+
+// A launcher names its kernel's arguments ONCE: MP_DISPATCH_N / MP_DISPATCH_CAP bind the run-time joint count to the constant N / CAP,
+// MP_FLAG binds a run-time bool to a constexpr bool NAME, and each expands its body once per value - so the body,
+// `return launch(k_x<N, NAME>, grid, block, lds, s, <arguments>)`, is written one time whatever the number of instances.  MP_FLAG nests.
+#define MP_FLAG(flag, NAME, ...)                      \
+  if (flag) { constexpr bool NAME = true; __VA_ARGS__; } \
+  else { constexpr bool NAME = false; __VA_ARGS__; }
 #define MP_DISPATCH_N(n, ...)                                   \
   switch (n) {                                                  \
     case 1: { constexpr int N = 1; __VA_ARGS__; } break;        \
@@ -1458,12 +1496,8 @@ __global__ __launch_bounds__(256) void k_stream(const mp_f4v* __restrict__ a, co
   else d[i] = v;
 }
 hipError_t mpk_stream(hipStream_t s, int reads, bool nontemporal, const void* a, const void* b, const void* c, void* d, long n4) {
-  const unsigned grid = (unsigned)((n4 + 255) / 256);
-#define MP_STREAM_LAUNCH(R, NT) hipLaunchKernelGGL((k_stream<R, NT>), dim3(grid), dim3(256), 0, s, (const mp_f4v*)a, (const mp_f4v*)b, (const mp_f4v*)c, (mp_f4v*)d, n4)
-  if (reads == 3) { if (nontemporal) MP_STREAM_LAUNCH(3, true); else MP_STREAM_LAUNCH(3, false); }
-  else { if (nontemporal) MP_STREAM_LAUNCH(1, true); else MP_STREAM_LAUNCH(1, false); }
-#undef MP_STREAM_LAUNCH
-  return hipGetLastError();
+  MP_FLAG(reads == 3, THREE, MP_FLAG(nontemporal, NT, return launch(k_stream<THREE ? 3 : 1, NT>, mp_grid(n4, kBlock), kBlock, 0, s,
+      (const mp_f4v*)a, (const mp_f4v*)b, (const mp_f4v*)c, (mp_f4v*)d, n4)))
 }
 
 // the same with any byte mix: every lane reads R 16-byte chunks (one from each of R arrays laid back to back in `a`) and writes W
@@ -1482,12 +1516,10 @@ __global__ __launch_bounds__(256) void k_stream_mix(const mp_f4v* __restrict__ a
   }
 }
 hipError_t mpk_stream_mix(hipStream_t s, int reads, int writes, bool nontemporal, const void* a, void* d, long n4) {
-  const unsigned grid = (unsigned)((n4 + 255) / 256);
-#define MP_MIX(R, W)                                                                                                              \
-  if (reads == R && writes == W) {                                                                                                \
-    if (nontemporal) hipLaunchKernelGGL((k_stream_mix<R, W, true>), dim3(grid), dim3(256), 0, s, (const mp_f4v*)a, (mp_f4v*)d, n4); \
-    else hipLaunchKernelGGL((k_stream_mix<R, W, false>), dim3(grid), dim3(256), 0, s, (const mp_f4v*)a, (mp_f4v*)d, n4);          \
-    return hipGetLastError();                                                                                                     \
+  // (the mixes that exist: what is particular here is this list)
+#define MP_MIX(R, W)              \
+  if (reads == R && writes == W) { \
+    MP_FLAG(nontemporal, NT, return launch(k_stream_mix<R, W, NT>, mp_grid(n4, kBlock), kBlock, 0, s, (const mp_f4v*)a, (mp_f4v*)d, n4)) \
   }
   MP_MIX(0, 1) MP_MIX(1, 1) MP_MIX(3, 1) MP_MIX(1, 3) MP_MIX(2, 3) MP_MIX(1, 2) MP_MIX(2, 1)
   MP_MIX(9, 1) MP_MIX(10, 1)   // the read-heavy mixes of k_fk_jac_vjp (q + gT + gJ in, gq out: 9.7 : 1 at n = 6, 9 : 1 at n = 8)
@@ -1509,115 +1541,74 @@ __global__ __launch_bounds__(64) void k_clock_sampler(unsigned long long* __rest
   }
 }
 hipError_t mpk_clock_sampler(hipStream_t s, unsigned long long* out, unsigned blocks, unsigned samples, unsigned naps) {
-  hipLaunchKernelGGL(k_clock_sampler, dim3(blocks), dim3(64), 0, s, out, samples, naps);
-  return hipGetLastError();
+  return launch(k_clock_sampler, mp_grid(blocks, 1), kWave, 0, s, out, samples, naps);
 }
 
-hipError_t mpk_selftest(hipStream_t s, int* d_out) {
-  hipLaunchKernelGGL(k_selftest, dim3(1), dim3(64), 0, s, d_out);
-  return hipGetLastError();
-}
+hipError_t mpk_selftest(hipStream_t s, int* d_out) { return launch(k_selftest, mp_grid(1, 1), kWave, 0, s, d_out); }
 
 // one row per lane, model through a device pointer (k_id_dm)
 hipError_t mpk_id_dm(hipStream_t s, const MpModel<float>* d_model, int n, const MpCall<float>& C, bool ftip, const float* q,
                      const float* qd, const float* qdd, float* tau, long rows, const MpLead& L, bool all_revolute) {
   if (rows <= 0) return hipSuccess;
-  using T = float;
-  const dim3 grid(grid_for(rows) + L.blocks), block(kBlock);
-  MP_DISPATCH_N(n, {
-    if (all_revolute) {
-      if (ftip) hipLaunchKernelGGL((k_id_dm<T, N, true, true>), grid, block, 0, s, d_model, C, q, qd, qdd, tau, rows, L);
-      else hipLaunchKernelGGL((k_id_dm<T, N, false, true>), grid, block, 0, s, d_model, C, q, qd, qdd, tau, rows, L);
-    } else {
-      if (ftip) hipLaunchKernelGGL((k_id_dm<T, N, true, false>), grid, block, 0, s, d_model, C, q, qd, qdd, tau, rows, L);
-      else hipLaunchKernelGGL((k_id_dm<T, N, false, false>), grid, block, 0, s, d_model, C, q, qd, qdd, tau, rows, L);
-    }
-  })
-  return hipGetLastError();
+  const MpGrid grid = mp_grid(rows + (long)L.blocks * kBlock, kBlock);  // the lead's blocks, then the rows' (ceil(rows / kBlock) + L.blocks)
+  MP_DISPATCH_N(n, MP_FLAG(all_revolute, REV, MP_FLAG(ftip, F,
+      return launch(k_id_dm<float, N, F, REV>, grid, kBlock, 0, s, d_model, C, q, qd, qdd, tau, rows, L))))
 }
 
 hipError_t mpk_id_hard(hipStream_t s, const MpModel<float>* d_model, int n, const MpCall<float>& C, bool ftip, const float* q,
                        const float* qd, const float* qdd, float* tau, unsigned rows, unsigned blocks) {
   if (blocks == 0 || !C.hard_rows || !C.cold_model) return hipSuccess;
-  MP_DISPATCH_N(n, {
-    if (ftip) hipLaunchKernelGGL((k_id_hard<N, true>), dim3(blocks), dim3(64), 0, s, d_model, C, q, qd, qdd, tau, rows);
-    else hipLaunchKernelGGL((k_id_hard<N, false>), dim3(blocks), dim3(64), 0, s, d_model, C, q, qd, qdd, tau, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(n, MP_FLAG(ftip, F, return launch(k_id_hard<N, F>, mp_grid(blocks, 1), kWave, 0, s, d_model, C, q, qd, qdd, tau, rows)))
 }
 
 hipError_t mpk_id_hard_batch(hipStream_t s, const MpModel<float>* d_model, int n, bool ftip, const MpHardBatch& B, int entries, unsigned blocks) {
   if (blocks == 0 || entries <= 0) return hipSuccess;
-  MP_DISPATCH_N(n, {
-    if (ftip) hipLaunchKernelGGL((k_id_hard_batch<N, true>), dim3(blocks, (unsigned)entries), dim3(64), 0, s, d_model, B);
-    else hipLaunchKernelGGL((k_id_hard_batch<N, false>), dim3(blocks, (unsigned)entries), dim3(64), 0, s, d_model, B);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(n, MP_FLAG(ftip, F, return launch(k_id_hard_batch<N, F>, mp_grid(blocks, 1, entries), kWave, 0, s, d_model, B)))
 }
 
 template <>
 hipError_t mpk_id<double>(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q,
                           const double* qd, const double* qdd, double* tau, long rows) {
-  using T = double;
   if (rows <= 0) return hipSuccess;
-  MP_DISPATCH_N(M.n, {
-    if (ftip) hipLaunchKernelGGL((k_id<T, N, true>), dim3(grid_for(rows)), dim3(kBlock), 0, s, M, C, q, qd, qdd, tau, rows);
-    else hipLaunchKernelGGL((k_id<T, N, false>), dim3(grid_for(rows)), dim3(kBlock), 0, s, M, C, q, qd, qdd, tau, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(ftip, F, return launch(k_id<double, N, F>, mp_grid(rows, kBlock), kBlock, 0, s, M, C, q, qd, qdd, tau, rows)))
 }
 
 hipError_t mpk_batch_traj(hipStream_t s, const MpModel<float>& M, const float* start, const float* end, long B,
                           long Nt, double Tf, int method, float* pos, float* vel, float* acc) {
   const long rows = B * Nt;
   if (rows <= 0) return hipSuccess;
-  MP_DISPATCH_N(M.n, {
-    hipLaunchKernelGGL((k_batch_traj<N>), dim3(grid_for(rows)), dim3(kBlock), 0, s, M, start, end, B, Nt, Tf, method, pos, vel, acc);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_batch_traj<N>, mp_grid(rows, kBlock), kBlock, 0, s, M, start, end, B, Nt, Tf, method, pos, vel, acc))
 }
 
 hipError_t mpk_time_table(hipStream_t s, double* tab, long Nt, double Tf, int method) {
   if (Nt <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_time_table, dim3(grid_for(Nt)), dim3(kBlock), 0, s, tab, Nt, Tf, method);
-  return hipGetLastError();
+  return launch(k_time_table, mp_grid(Nt, kBlock), kBlock, 0, s, tab, Nt, Tf, method);
 }
 
 // blocks per trajectory of the table-driven fused kernels (block = 256 lanes, ceil(Nt / 2) lanes per trajectory)
-unsigned mpk_traj_blocks_per_trajectory(long Nt) { return (unsigned)(((Nt + 1) / 2 + kBlock - 1) / kBlock); }
+unsigned mpk_traj_blocks_per_trajectory(long Nt) { return mp_grid((Nt + 1) / 2, kBlock).x; }
 
 hipError_t mpk_traj_id_tab(hipStream_t s, const MpModel<float>& M, const MpCall<float>& C, bool ftip, const float* start,
                            const float* end, long B, long Nt, const double* tab, float* tau) {
   if (B <= 0 || Nt <= 0) return hipSuccess;
   const unsigned bpt = mpk_traj_blocks_per_trajectory(Nt);
-  const unsigned grid = (unsigned)(B * bpt);
-  MP_DISPATCH_N(M.n, {
-    if (ftip) hipLaunchKernelGGL((k_traj_id_pk_tab<N, true>), dim3(grid), dim3(kBlock), 0, s, M, C, start, end, Nt, bpt, tab, tau);
-    else hipLaunchKernelGGL((k_traj_id_pk_tab<N, false>), dim3(grid), dim3(kBlock), 0, s, M, C, start, end, Nt, bpt, tab, tau);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(ftip, F,
+      return launch(k_traj_id_pk_tab<N, F>, mp_grid2(B, bpt), kBlock, 0, s, M, C, start, end, Nt, bpt, tab, tau)))
 }
 
 hipError_t mpk_traj_id_hard(hipStream_t s, const MpModel<float>* d_model, int n, const MpCall<float>& C, bool ftip, const float* start,
                             const float* end, unsigned Nt, const double* tab, float* tau, unsigned rows, unsigned blocks) {
   if (blocks == 0 || !C.hard_rows || !C.cold_model) return hipSuccess;
-  MP_DISPATCH_N(n, {
-    if (ftip) hipLaunchKernelGGL((k_traj_id_hard<N, true>), dim3(blocks), dim3(64), 0, s, d_model, C, start, end, Nt, tab, tau, rows);
-    else hipLaunchKernelGGL((k_traj_id_hard<N, false>), dim3(blocks), dim3(64), 0, s, d_model, C, start, end, Nt, tab, tau, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(n, MP_FLAG(ftip, F,
+      return launch(k_traj_id_hard<N, F>, mp_grid(blocks, 1), kWave, 0, s, d_model, C, start, end, Nt, tab, tau, rows)))
 }
 
 template <typename T>
 hipError_t mpk_fk_jac_id(hipStream_t s, const MpModel<T>& M, const MpCall<T>& C, bool ftip, const T* q, const T* qd,
                          const T* qdd, T* Tout, T* Jout, T* tau, long rows) {
   if (rows <= 0) return hipSuccess;
-  MP_DISPATCH_N(M.n, {
-    const unsigned gb = (unsigned)((rows + kFkBlock - 1) / kFkBlock);
-    if (ftip) hipLaunchKernelGGL((k_fk_jac_id<T, N, true>), dim3(gb), dim3(kFkBlock), 0, s, M, C, q, qd, qdd, Tout, Jout, tau, rows);
-    else hipLaunchKernelGGL((k_fk_jac_id<T, N, false>), dim3(gb), dim3(kFkBlock), 0, s, M, C, q, qd, qdd, Tout, Jout, tau, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(ftip, F,
+      return launch(k_fk_jac_id<T, N, F>, mp_grid(rows, kFkBlock), kFkBlock, 0, s, M, C, q, qd, qdd, Tout, Jout, tau, rows)))
 }
 template hipError_t mpk_fk_jac_id<float>(hipStream_t, const MpModel<float>&, const MpCall<float>&, bool, const float*,
                                          const float*, const float*, float*, float*, float*, long);
@@ -1627,8 +1618,7 @@ template hipError_t mpk_fk_jac_id<double>(hipStream_t, const MpModel<double>&, c
 template <typename T>
 hipError_t mpk_mass_matrix(hipStream_t s, const MpModel<T>& M, const T* q, T* Mout, long rows) {
   if (rows <= 0) return hipSuccess;
-  MP_DISPATCH_N(M.n, { hipLaunchKernelGGL((k_mass_matrix<T, N>), dim3((unsigned)((rows + kFkBlock - 1) / kFkBlock)), dim3(kFkBlock), 0, s, M, q, Mout, rows); })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_mass_matrix<T, N>, mp_grid(rows, kFkBlock), kFkBlock, 0, s, M, q, Mout, rows))
 }
 template hipError_t mpk_mass_matrix<float>(hipStream_t, const MpModel<float>&, const float*, float*, long);
 template hipError_t mpk_mass_matrix<double>(hipStream_t, const MpModel<double>&, const double*, double*, long);
@@ -1637,11 +1627,8 @@ template <typename T>
 hipError_t mpk_forward_dynamics(hipStream_t s, const MpModel<T>& M, const MpCall<T>& C, bool ftip, const T* q, const T* qd,
                                 const T* tau, T* qdd, long rows) {
   if (rows <= 0) return hipSuccess;
-  MP_DISPATCH_N(M.n, {
-    if (ftip) hipLaunchKernelGGL((k_forward_dynamics<T, N, true>), dim3(grid_for(rows)), dim3(kBlock), 0, s, M, C, q, qd, tau, qdd, rows);
-    else hipLaunchKernelGGL((k_forward_dynamics<T, N, false>), dim3(grid_for(rows)), dim3(kBlock), 0, s, M, C, q, qd, tau, qdd, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(ftip, F,
+      return launch(k_forward_dynamics<T, N, F>, mp_grid(rows, kBlock), kBlock, 0, s, M, C, q, qd, tau, qdd, rows)))
 }
 template hipError_t mpk_forward_dynamics<float>(hipStream_t, const MpModel<float>&, const MpCall<float>&, bool, const float*,
                                                 const float*, const float*, float*, long);
@@ -1651,54 +1638,34 @@ template hipError_t mpk_forward_dynamics<double>(hipStream_t, const MpModel<doub
 hipError_t mpk_id_deriv(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
                         const double* qdd, double* tau, double* dq, double* dqd, double* Mout, long rows) {
   if (rows <= 0) return hipSuccess;
-  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(M.n, {
-    if (ftip) hipLaunchKernelGGL((k_id_deriv<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, qdd, tau, dq, dqd, Mout, rows);
-    else hipLaunchKernelGGL((k_id_deriv<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, qdd, tau, dq, dqd, Mout, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(ftip, F,
+      return launch(k_id_deriv<N, F>, mp_grid(rows, kDerivBlock), kDerivBlock, 0, s, M, C, q, qd, qdd, tau, dq, dqd, Mout, rows)))
 }
 hipError_t mpk_fd_deriv(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
                         const double* tau, double* qdd, double* dq, double* dqd, double* Minv, long rows) {
   if (rows <= 0) return hipSuccess;
-  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(M.n, {
-    if (ftip) hipLaunchKernelGGL((k_fd_deriv<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, qdd, dq, dqd, Minv, rows);
-    else hipLaunchKernelGGL((k_fd_deriv<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, qdd, dq, dqd, Minv, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(ftip, F,
+      return launch(k_fd_deriv<N, F>, mp_grid(rows, kDerivBlock), kDerivBlock, 0, s, M, C, q, qd, tau, qdd, dq, dqd, Minv, rows)))
 }
 
 hipError_t mpk_id_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
                       const double* qdd, const double* gtau, double* gq, double* gqd, double* gqdd, long rows) {
   if (rows <= 0) return hipSuccess;
-  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(M.n, {
-    if (ftip) hipLaunchKernelGGL((k_id_vjp<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, qdd, gtau, gq, gqd, gqdd, rows);
-    else hipLaunchKernelGGL((k_id_vjp<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, qdd, gtau, gq, gqd, gqdd, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(ftip, F,
+      return launch(k_id_vjp<N, F>, mp_grid(rows, kDerivBlock), kDerivBlock, 0, s, M, C, q, qd, qdd, gtau, gq, gqd, gqdd, rows)))
 }
 hipError_t mpk_fd_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const double* q, const double* qd,
                       const double* tau, const double* gqdd, double* qdd, double* gq, double* gqd, double* gtau, long rows) {
   if (rows <= 0) return hipSuccess;
-  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(M.n, {
-    if (ftip) hipLaunchKernelGGL((k_fd_vjp<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, gqdd, qdd, gq, gqd, gtau, rows);
-    else hipLaunchKernelGGL((k_fd_vjp<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, q, qd, tau, gqdd, qdd, gq, gqd, gtau, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(ftip, F,
+      return launch(k_fd_vjp<N, F>, mp_grid(rows, kDerivBlock), kDerivBlock, 0, s, M, C, q, qd, tau, gqdd, qdd, gq, gqd, gtau, rows)))
 }
 
 hipError_t mpk_fk_jac_vjp(hipStream_t s, const MpModel<double>& M, int frame, const double* q, const double* gT, const double* gJ,
                          double* Tout, double* Jout, double* gq, long rows) {
   if (rows <= 0) return hipSuccess;
-  const unsigned gb = (unsigned)((rows + kFkBlock - 1) / kFkBlock);
-  MP_DISPATCH_N(M.n, {
-    if (frame == 0) hipLaunchKernelGGL((k_fk_jac_vjp<N, 0>), dim3(gb), dim3(kFkBlock), 0, s, M, q, gT, gJ, Tout, Jout, gq, rows);
-    else hipLaunchKernelGGL((k_fk_jac_vjp<N, 1>), dim3(gb), dim3(kFkBlock), 0, s, M, q, gT, gJ, Tout, Jout, gq, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(frame != 0, BODY,
+      return launch(k_fk_jac_vjp<N, BODY ? 1 : 0>, mp_grid(rows, kFkBlock), kFkBlock, 0, s, M, q, gT, gJ, Tout, Jout, gq, rows)))
 }
 
 // dynamic LDS: the park of S world centres for 64 lanes; beyond the default limit the function's own limit is raised first
@@ -1707,25 +1674,17 @@ hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, const MpColDev
                          double* grad_dist_self, double* cost, double* grad) {
   if (rows <= 0) return hipSuccess;
   if (D.S < 1 || D.S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
-  const unsigned gb = (unsigned)((rows + 63) / 64);
-  const unsigned park = (unsigned)D.S * 3u * 64u * (unsigned)sizeof(double);
+  const unsigned park = (unsigned)D.S * 3u * kWave * (unsigned)sizeof(double);
   const bool want_grad = grad_dist_world != nullptr || grad_dist_self != nullptr || grad != nullptr;
-#define MP_COL_LAUNCH(WG)                                                                                                              \
-  do {                                                                                                                                 \
-    if (park + MP_WAVE_LDS_BYTES > 64u * 1024u) {                                                                                      \
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_collision<N, WG>),                                     \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)park);                                 \
-      if (e != hipSuccess) return e;                                                                                                   \
-    }                                                                                                                                  \
-    hipLaunchKernelGGL((k_collision<N, WG>), dim3(gb), dim3(64), park, s, M, D.sph, D.pairs, D.world, q, rows, eps_world, eps_self,    \
-                       dist_world, arg_world, dist_self, arg_self, grad_dist_world, grad_dist_self, cost, grad);                       \
-  } while (0)
-  MP_DISPATCH_N(M.n, {
-    if (want_grad) MP_COL_LAUNCH(true);
-    else MP_COL_LAUNCH(false);
-  })
-#undef MP_COL_LAUNCH
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(want_grad, WG, {
+    if (park + MP_WAVE_LDS_BYTES > 64u * 1024u) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_collision<N, WG>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)park);
+      if (e != hipSuccess) return e;
+    }
+    return launch(k_collision<N, WG>, mp_grid(rows, kWave), kWave, park, s, M, D.sph, D.pairs, D.world, q, rows, eps_world, eps_self,
+                  dist_world, arg_world, dist_self, arg_self, grad_dist_world, grad_dist_self, cost, grad);
+  }))
 }
 
 // The launch plan of a one-wave work-queue kernel on the sphere model: its dynamic LDS (beyond the default limit the kernel's own
@@ -1740,7 +1699,7 @@ static hipError_t queue_plan(K kernel, int n, int S, int compute_units, MpQueueP
     if (e != hipSuccess) return e;
   }
   int per_cu = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds);
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kWave, lds);
   if (e != hipSuccess) return e;
   *plan = {lds, (long)(per_cu > 0 ? per_cu : 1) * (compute_units > 0 ? compute_units : 256)};
   return hipSuccess;
@@ -1773,11 +1732,8 @@ hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, const Mp
   if (edges <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
-  MP_DISPATCH_N(M.n, {
-    hipLaunchKernelGGL((k_collision_edges<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, q_from, q_to, edges,
-                       P, status, t, steps, clearance, witness, D.counter);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_collision_edges<N>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, q_from, q_to, edges,
+                                   P, status, t, steps, clearance, witness, D.counter))
 }
 
 hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q_start, const double* q_goal,
@@ -1786,11 +1742,8 @@ hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, const MpColD
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
-  MP_DISPATCH_N(M.n, {
-    hipLaunchKernelGGL((k_rrt_connect<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, q_start, q_goal, problems,
-                       P, status, count, waypoints, iterations, nodes, evaluations, workspace, D.counter);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_rrt_connect<N>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, q_start, q_goal, problems,
+                                   P, status, count, waypoints, iterations, nodes, evaluations, workspace, D.counter))
 }
 
 hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
@@ -1800,12 +1753,9 @@ hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, const MpCo
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
-  MP_DISPATCH_N(M.n, {
-    hipLaunchKernelGGL((k_path_shortcut<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
-                       problems, P, status, count, waypoints, length_in, length_out, iterations, accepted, skipped_full, evaluations,
-                       workspace, D.counter);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_path_shortcut<N>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
+                                   problems, P, status, count, waypoints, length_in, length_out, iterations, accepted, skipped_full,
+                                   evaluations, workspace, D.counter))
 }
 
 hipError_t mpk_goal_ik(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* T_goal, const double* q_seed,
@@ -1814,11 +1764,8 @@ hipError_t mpk_goal_ik(hipStream_t s, const MpModel<double>& M, const MpColDevic
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
-  MP_DISPATCH_N(M.n, {
-    hipLaunchKernelGGL((k_goal_ik<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, T_goal, q_seed, problems, P,
-                       status, q, attempts, iterations, converged, pose_error, clearance, witness, D.counter);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_goal_ik<N>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, T_goal, q_seed, problems, P,
+                                   status, q, attempts, iterations, converged, pose_error, clearance, witness, D.counter))
 }
 
 hipError_t mpk_path_blend(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
@@ -1827,80 +1774,55 @@ hipError_t mpk_path_blend(hipStream_t s, const MpModel<double>& M, const MpColDe
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
-  MP_DISPATCH_N(M.n, {
-    hipLaunchKernelGGL((k_path_blend<N>), dim3((unsigned)blocks), dim3(64), lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
-                       problems, P, status, corner, count, points, cut, knot, length, halvings, evaluations, clearance, D.counter);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_path_blend<N>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
+                                   problems, P, status, corner, count, points, cut, knot, length, halvings, evaluations, clearance,
+                                   D.counter))
 }
 
 hipError_t mpk_path_blend_sample(hipStream_t s, int n, long problems, const MpBlendParams& P, const int* status, const int* count,
                                  const double* points, const double* cut, const double* knot, const double* length, double* q, double* dq,
                                  double* ddq) {
   if (problems <= 0) return hipSuccess;
-  const unsigned gb = (unsigned)((problems * P.grid + 63) / 64);
-  MP_DISPATCH_N(n, {
-    hipLaunchKernelGGL((k_path_blend_sample<N>), dim3(gb), dim3(64), 0, s, problems, P.grid, P.w_in, status, count, points, cut, knot,
-                       length, q, dq, ddq);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(n, return launch(k_path_blend_sample<N>, mp_grid(problems * P.grid, kWave), kWave, 0, s, problems, P.grid, P.w_in, status,
+                                 count, points, cut, knot, length, q, dq, ddq))
 }
 
-// `ftip`: the call's wrench is not zero.  blocks: the grid the caller has settled on (the tiles of 64 rows, capped).
-template <int N, int SOURCE>
-static void launch_traj_sample(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const MpSampleIn& I,
-                               const MpSampleOut& O, long tiles, unsigned blocks) {
-  if (O.tau == nullptr) hipLaunchKernelGGL((k_traj_sample<N, SOURCE, MP_TS_NO_TAU>), dim3(blocks), dim3(64), 0, s, M, C, I, O, tiles);
-  else if (!ftip) hipLaunchKernelGGL((k_traj_sample<N, SOURCE, MP_TS_TAU>), dim3(blocks), dim3(64), 0, s, M, C, I, O, tiles);
-  else hipLaunchKernelGGL((k_traj_sample<N, SOURCE, MP_TS_TAU_FTIP>), dim3(blocks), dim3(64), 0, s, M, C, I, O, tiles);
-}
+// `ftip`: the call's wrench is not zero.  The grid: the tiles of 64 rows, clamped to what a grid holds and to the caller's cap - the
+// kernel strides over the tiles.  The torque variant: none without O.tau, else with or without the wrench (three instances, not four).
 hipError_t mpk_traj_sample(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, bool curve, const MpSampleIn& I,
                            const MpSampleOut& O, long max_blocks) {
   if (I.B <= 0) return hipSuccess;
-  const long tiles = (I.B * I.M + 63) / 64;
-  long blocks = tiles < 0x7fffffffL ? tiles : 0x7fffffffL;
+  const long tiles = (I.B * I.M + kWave - 1) / kWave;
+  long blocks = tiles < kMaxGrid ? tiles : kMaxGrid;
   if (max_blocks > 0 && blocks > max_blocks) blocks = max_blocks;
-  MP_DISPATCH_N(M.n, {
-    if (curve) launch_traj_sample<N, MP_TS_CURVE>(s, M, C, ftip, I, O, tiles, (unsigned)blocks);
-    else launch_traj_sample<N, MP_TS_GRID>(s, M, C, ftip, I, O, tiles, (unsigned)blocks);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(curve, CURVE, MP_FLAG(O.tau != nullptr, WITH_TAU, MP_FLAG(ftip, F, {
+    constexpr int TAU = !WITH_TAU ? MP_TS_NO_TAU : F ? MP_TS_TAU_FTIP : MP_TS_TAU;
+    return launch(k_traj_sample<N, CURVE ? MP_TS_CURVE : MP_TS_GRID, TAU>, mp_grid(blocks, 1), kWave, 0, s, M, C, I, O, tiles);
+  }))))
 }
 
 hipError_t mpk_opspace(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, int frame, int task, double lam2, const double* q,
                        const double* qd, double* Tout, double* Jout, double* Jdqd, double* Lam, double* Jbar, double* mu, double* p,
                        long rows) {
   if (rows <= 0) return hipSuccess;
-  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(M.n, {
-    hipLaunchKernelGGL((k_opspace<N>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, frame, task, lam2, q, qd, Tout, Jout, Jdqd, Lam, Jbar, mu, p,
-                       rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_opspace<N>, mp_grid(rows, kDerivBlock), kDerivBlock, 0, s, M, C, frame, task, lam2, q, qd, Tout, Jout,
+                                   Jdqd, Lam, Jbar, mu, p, rows))
 }
 
 hipError_t mpk_opspace_torque(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, int frame, int task, double lam2,
                               const double* q, const double* qd, const double* acc, const double* tau0, double* tau, long rows) {
   if (rows <= 0) return hipSuccess;
-  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(M.n, {
-    hipLaunchKernelGGL((k_opspace_torque<N>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, frame, task, lam2, q, qd, acc, tau0, tau, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_opspace_torque<N>, mp_grid(rows, kDerivBlock), kDerivBlock, 0, s, M, C, frame, task, lam2, q, qd, acc,
+                                   tau0, tau, rows))
 }
 
 hipError_t mpk_fd_traj_vjp(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, const double* theta0, const double* dtheta0,
                            const double* taumat, const double* Ftipmat, long B, long Nt, double h, int intRes, const double* gp,
                            const double* gv, const double* ga, double* work, double* gth0, double* gdth0, double* gtau) {
   if (B <= 0 || Nt <= 0) return hipSuccess;
-  const unsigned gb = (unsigned)((B + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(M.n, {
-    if (Ftipmat) hipLaunchKernelGGL((k_fd_traj_vjp<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt,
-                                    h, intRes, gp, gv, ga, work, gth0, gdth0, gtau);
-    else hipLaunchKernelGGL((k_fd_traj_vjp<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt,
-                            h, intRes, gp, gv, ga, work, gth0, gdth0, gtau);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(Ftipmat != nullptr, F,
+      return launch(k_fd_traj_vjp<N, F>, mp_grid(B, kDerivBlock), kDerivBlock, 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt, h, intRes,
+                    gp, gv, ga, work, gth0, gdth0, gtau)))
 }
 
 hipError_t mpk_ilqr_backward(hipStream_t s, const MpModel<double>& M, const MpIlqrWeights& Wt, const double* pos, const double* vel,
@@ -1908,105 +1830,71 @@ hipError_t mpk_ilqr_backward(hipStream_t s, const MpModel<double>& M, const MpIl
                              const double* reg, long B, long Nt, double h, bool k_batch_major, double* work, double* K, double* k,
                              double* dV, int* status) {
   if (B <= 0 || Nt <= 0) return hipSuccess;
-  if (!work) {   // no workspace: the cooperative form
-    if ((B + 3) / 4 > 0x7fffffffL) return hipErrorInvalidValue;
-    MP_DISPATCH_N(M.n, {
-      hipLaunchKernelGGL((k_ilqr_backward_coop<N>), dim3((unsigned)((B + 3) / 4)), dim3(64), 0, s, M, Wt, pos, vel, tau, dq, dqd, Minv, xref,
-                         reg, B, Nt, h, (int)k_batch_major, K, k, dV, status);
-    })
-    return hipGetLastError();
+  if (!work) {   // no workspace: the cooperative form, kWave / MP_ILQR_LANES trajectories a block
+    MP_DISPATCH_N(M.n, return launch(k_ilqr_backward_coop<N>, mp_grid(B, kWave / MP_ILQR_LANES), kWave, 0, s, M, Wt, pos, vel, tau, dq, dqd,
+                                     Minv, xref, reg, B, Nt, h, k_batch_major, K, k, dV, status))
   }
-  const unsigned gb = (unsigned)((B + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(M.n, {
-    hipLaunchKernelGGL((k_ilqr_backward<N>), dim3(gb), dim3(kDerivBlock), 0, s, M, Wt, pos, vel, tau, dq, dqd, Minv, xref, reg, B, Nt, h,
-                       (int)k_batch_major, work, K, k, dV, status);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_ilqr_backward<N>, mp_grid(B, kDerivBlock), kDerivBlock, 0, s, M, Wt, pos, vel, tau, dq, dqd, Minv, xref,
+                                   reg, B, Nt, h, k_batch_major, work, K, k, dV, status))
 }
 hipError_t mpk_ilqr_rollout(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, const MpIlqrWeights& Wt, const double* th0,
                             const double* dth0, const double* tau, const double* pos, const double* vel, const double* K, const double* k,
                             const double* alpha, const double* xref, long A, long B, long Nt, double h, bool k_batch_major, double* cost,
                             double* opos, double* ovel, double* otau) {
   if (A <= 0 || B <= 0 || Nt <= 0) return hipSuccess;
-  const unsigned gb = (unsigned)((A * B + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(M.n, {
-    hipLaunchKernelGGL((k_ilqr_rollout<N>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, Wt, th0, dth0, tau, pos, vel, K, k, alpha, xref, A, B,
-                       Nt, h, (int)k_batch_major, cost, opos, ovel, otau);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_ilqr_rollout<N>, mp_grid(A * B, kDerivBlock), kDerivBlock, 0, s, M, C, Wt, th0, dth0, tau, pos, vel, K, k,
+                                   alpha, xref, A, B, Nt, h, k_batch_major, cost, opos, ovel, otau))
 }
 
 hipError_t mpk_path_coeffs(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, bool ftip, const MpToppraVmax& V,
                            const double* q, const double* dq, const double* ddq, double* a, double* b, double* c, double* xbar, long rows) {
   if (rows <= 0) return hipSuccess;
-  if ((rows + kDerivBlock - 1) / kDerivBlock > 0x7fffffffL) return hipErrorInvalidValue;
-  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(M.n, {
-    if (ftip) hipLaunchKernelGGL((k_path_coeffs<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, V, q, dq, ddq, a, b, c, xbar, rows);
-    else hipLaunchKernelGGL((k_path_coeffs<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, C, V, q, dq, ddq, a, b, c, xbar, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(ftip, F,
+      return launch(k_path_coeffs<N, F>, mp_grid(rows, kDerivBlock), kDerivBlock, 0, s, M, C, V, q, dq, ddq, a, b, c, xbar, rows)))
 }
 hipError_t mpk_toppra_sweep(hipStream_t s, int n, const MpToppraLimits& lim, bool acc, const double* a, const double* b, const double* c,
                             const double* xbar, const double* dq, const double* ddq, const double* sd_start, const double* sd_end, long B,
                             long Nt, double* K, double* x, double* u, double* t, double* dur, int* status, double* oqd, double* oqdd,
                             double* otau) {
   if (B <= 0) return hipSuccess;
-  if (Nt < 3 || (B + kDerivBlock - 1) / kDerivBlock > 0x7fffffffL) return hipErrorInvalidValue;
-  const unsigned gb = (unsigned)((B + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(n, {
-    if (acc) hipLaunchKernelGGL((k_toppra_sweep<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, lim, a, b, c, xbar, dq, ddq, sd_start, sd_end,
-                                B, Nt, K, x, u, t, dur, status, oqd, oqdd, otau);
-    else hipLaunchKernelGGL((k_toppra_sweep<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, lim, a, b, c, xbar, dq, ddq, sd_start, sd_end, B,
-                            Nt, K, x, u, t, dur, status, oqd, oqdd, otau);
-  })
-  return hipGetLastError();
+  if (Nt < 3) return hipErrorInvalidValue;
+  MP_DISPATCH_N(n, MP_FLAG(acc, ACC,
+      return launch(k_toppra_sweep<N, ACC>, mp_grid(B, kDerivBlock), kDerivBlock, 0, s, lim, a, b, c, xbar, dq, ddq, sd_start, sd_end, B, Nt,
+                    K, x, u, t, dur, status, oqd, oqdd, otau)))
 }
 hipError_t mpk_path_rows(hipStream_t s, int n, const double* a, const double* b, const double* c, const double* dq, const double* ddq,
                          const double* x, const double* u, double* oqd, double* oqdd, double* otau, long rows) {
   if (rows <= 0) return hipSuccess;
-  if ((rows + kDerivBlock - 1) / kDerivBlock > 0x7fffffffL) return hipErrorInvalidValue;
-  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(n, { hipLaunchKernelGGL((k_path_rows<N>), dim3(gb), dim3(kDerivBlock), 0, s, a, b, c, dq, ddq, x, u, oqd, oqdd, otau, rows); })
-  return hipGetLastError();
+  MP_DISPATCH_N(n, return launch(k_path_rows<N>, mp_grid(rows, kDerivBlock), kDerivBlock, 0, s, a, b, c, dq, ddq, x, u, oqd, oqdd, otau, rows))
 }
 
 hipError_t mpk_id_regressor(hipStream_t s, const MpModel<double>& M, const double* Dmap, const MpCall<double>& C, bool ftip,
                             const double* q, const double* qd, const double* qdd, double* Y, double* tau_ext, long rows) {
   if (rows <= 0) return hipSuccess;
-  const unsigned gb = (unsigned)((rows + kDerivBlock - 1) / kDerivBlock);
-  MP_DISPATCH_N(M.n, {
-    if (ftip) hipLaunchKernelGGL((k_id_regressor<N, true>), dim3(gb), dim3(kDerivBlock), 0, s, M, Dmap, C, q, qd, qdd, Y, tau_ext, rows);
-    else hipLaunchKernelGGL((k_id_regressor<N, false>), dim3(gb), dim3(kDerivBlock), 0, s, M, Dmap, C, q, qd, qdd, Y, tau_ext, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(ftip, F,
+      return launch(k_id_regressor<N, F>, mp_grid(rows, kDerivBlock), kDerivBlock, 0, s, M, Dmap, C, q, qd, qdd, Y, tau_ext, rows)))
 }
 hipError_t mpk_id_regressor_normal(hipStream_t s, const MpModel<double>& M, const double* Dmap, const MpCall<double>& C, bool ftip,
                                    const double* q, const double* qd, const double* qdd, const double* rhs, long rows, double* work,
                                    double* A, double* b, double* rr) {
   if (rows <= 0) return hipSuccess;
-  const unsigned G = (unsigned)mp_reg_normal_groups(rows);
+  const long groups = mp_reg_normal_groups(rows);
   const bool with_a = A != nullptr;
-  MP_DISPATCH_N(M.n, {
-    if (ftip && with_a) hipLaunchKernelGGL((k_id_regressor_normal<N, true, true>), dim3(G), dim3(64), 0, s, M, Dmap, C, q, qd, qdd, rhs, rows, work);
-    else if (ftip) hipLaunchKernelGGL((k_id_regressor_normal<N, true, false>), dim3(G), dim3(64), 0, s, M, Dmap, C, q, qd, qdd, rhs, rows, work);
-    else if (with_a) hipLaunchKernelGGL((k_id_regressor_normal<N, false, true>), dim3(G), dim3(64), 0, s, M, Dmap, C, q, qd, qdd, rhs, rows, work);
-    else hipLaunchKernelGGL((k_id_regressor_normal<N, false, false>), dim3(G), dim3(64), 0, s, M, Dmap, C, q, qd, qdd, rhs, rows, work);
-    const int W = MP_REG_P * N, outs = (with_a ? W * W : 0) + W + 1;
-    hipLaunchKernelGGL((k_id_regressor_normal_reduce<N>), dim3((outs + 255) / 256), dim3(256), 0, s, work, (int)G, with_a, A, b, rr);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(ftip, F, MP_FLAG(with_a, WITH_A, {
+    const hipError_t e = launch(k_id_regressor_normal<N, F, WITH_A>, mp_grid(groups, 1), kWave, 0, s, M, Dmap, C, q, qd, qdd, rhs, rows, work);
+    if (e != hipSuccess) return e;
+    constexpr int W = MP_REG_P * N, outs = (WITH_A ? W * W : 0) + W + 1;
+    return launch(k_id_regressor_normal_reduce<N>, mp_grid(outs, kBlock), kBlock, 0, s, work, groups, with_a, A, b, rr);
+  })))
 }
 
 template <typename T>
 hipError_t mpk_fd_traj(hipStream_t s, const MpModel<T>& M, const MpCall<T>& C, const T* theta0, const T* dtheta0,
                        const T* taumat, const T* Ftipmat, long B, long Nt, T h, int intRes, float* pos, float* vel, float* acc) {
   if (B <= 0 || Nt <= 0) return hipSuccess;
-  MP_DISPATCH_N(M.n, {
-    if (Ftipmat) hipLaunchKernelGGL((k_fd_traj<T, N, true>), dim3((unsigned)((B + kFdBlock - 1) / kFdBlock)), dim3(kFdBlock), 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt, h, intRes, pos, vel, acc);
-    else hipLaunchKernelGGL((k_fd_traj<T, N, false>), dim3((unsigned)((B + kFdBlock - 1) / kFdBlock)), dim3(kFdBlock), 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt, h, intRes, pos, vel, acc);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(Ftipmat != nullptr, F,
+      return launch(k_fd_traj<T, N, F>, mp_grid(B, kFdBlock), kFdBlock, 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt, h, intRes, pos, vel,
+                    acc)))
 }
 template hipError_t mpk_fd_traj<float>(hipStream_t, const MpModel<float>&, const MpCall<float>&, const float*, const float*,
                                        const float*, const float*, long, long, float, int, float*, float*, float*);
@@ -2018,12 +1906,9 @@ template <typename T>
 hipError_t mpk_fd_traj_tm(hipStream_t s, const MpModel<T>& M, const MpCall<T>& C, const T* theta0, const T* dtheta0,
                           const T* taumat, const T* Ftipmat, long B, long Nt, T h, int intRes, float* pos, float* vel, float* acc) {
   if (B <= 0 || Nt <= 0) return hipSuccess;
-  const dim3 grid((unsigned)((B + kFdBlock - 1) / kFdBlock));
-  MP_DISPATCH_N(M.n, {
-    if (Ftipmat) hipLaunchKernelGGL((k_fd_traj_tm<T, N, true>), grid, dim3(kFdBlock), 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt, h, intRes, pos, vel, acc);
-    else hipLaunchKernelGGL((k_fd_traj_tm<T, N, false>), grid, dim3(kFdBlock), 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt, h, intRes, pos, vel, acc);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, MP_FLAG(Ftipmat != nullptr, F,
+      return launch(k_fd_traj_tm<T, N, F>, mp_grid(B, kFdBlock), kFdBlock, 0, s, M, C, theta0, dtheta0, taumat, Ftipmat, B, Nt, h, intRes, pos,
+                    vel, acc)))
 }
 template hipError_t mpk_fd_traj_tm<float>(hipStream_t, const MpModel<float>&, const MpCall<float>&, const float*, const float*,
                                           const float*, const float*, long, long, float, int, float*, float*, float*);
@@ -2036,11 +1921,8 @@ template <typename T>
 hipError_t mpk_dyn_fk_jac_id(hipStream_t s, int n, const MpBigModel<T>* d_model, const MpCall<T>& C, bool ftip, const T* q, const T* qd,
                              const T* qdd, T* Tout, T* Jout, T* tau, long rows) {
   if (rows <= 0) return hipSuccess;
-  MP_DISPATCH_CAP(n, {
-    if (ftip) hipLaunchKernelGGL((k_dyn_fk_jac_id<CAP, T, true>), dim3(grid_for(rows)), dim3(kBlock), 0, s, d_model, C, q, qd, qdd, Tout, Jout, tau, rows);
-    else hipLaunchKernelGGL((k_dyn_fk_jac_id<CAP, T, false>), dim3(grid_for(rows)), dim3(kBlock), 0, s, d_model, C, q, qd, qdd, Tout, Jout, tau, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_CAP(n, MP_FLAG(ftip, F,
+      return launch(k_dyn_fk_jac_id<CAP, T, F>, mp_grid(rows, kBlock), kBlock, 0, s, d_model, C, q, qd, qdd, Tout, Jout, tau, rows)))
 }
 template hipError_t mpk_dyn_fk_jac_id<float>(hipStream_t, int, const MpBigModel<float>*, const MpCall<float>&, bool, const float*,
                                              const float*, const float*, float*, float*, float*, long);
@@ -2049,8 +1931,7 @@ template hipError_t mpk_dyn_fk_jac_id<double>(hipStream_t, int, const MpBigModel
 template <typename T>
 hipError_t mpk_dyn_mass_matrix(hipStream_t s, int n, const MpBigModel<T>* d_model, const T* q, T* Mout, long rows) {
   if (rows <= 0) return hipSuccess;
-  MP_DISPATCH_CAP(n, { hipLaunchKernelGGL((k_dyn_mass_matrix<CAP, T>), dim3(grid_for(rows)), dim3(kBlock), 0, s, d_model, q, Mout, rows); })
-  return hipGetLastError();
+  MP_DISPATCH_CAP(n, return launch(k_dyn_mass_matrix<CAP, T>, mp_grid(rows, kBlock), kBlock, 0, s, d_model, q, Mout, rows))
 }
 template hipError_t mpk_dyn_mass_matrix<float>(hipStream_t, int, const MpBigModel<float>*, const float*, float*, long);
 template hipError_t mpk_dyn_mass_matrix<double>(hipStream_t, int, const MpBigModel<double>*, const double*, double*, long);
@@ -2058,11 +1939,8 @@ template <typename T>
 hipError_t mpk_dyn_forward_dynamics(hipStream_t s, int n, const MpBigModel<T>* d_model, const MpCall<T>& C, bool ftip, const T* q,
                                     const T* qd, const T* tau, T* qdd, long rows) {
   if (rows <= 0) return hipSuccess;
-  MP_DISPATCH_CAP(n, {
-    if (ftip) hipLaunchKernelGGL((k_dyn_forward_dynamics<CAP, T, true>), dim3(grid_for(rows)), dim3(kBlock), 0, s, d_model, C, q, qd, tau, qdd, rows);
-    else hipLaunchKernelGGL((k_dyn_forward_dynamics<CAP, T, false>), dim3(grid_for(rows)), dim3(kBlock), 0, s, d_model, C, q, qd, tau, qdd, rows);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_CAP(n, MP_FLAG(ftip, F,
+      return launch(k_dyn_forward_dynamics<CAP, T, F>, mp_grid(rows, kBlock), kBlock, 0, s, d_model, C, q, qd, tau, qdd, rows)))
 }
 template hipError_t mpk_dyn_forward_dynamics<float>(hipStream_t, int, const MpBigModel<float>*, const MpCall<float>&, bool, const float*,
                                                     const float*, const float*, float*, long);
@@ -2073,13 +1951,9 @@ hipError_t mpk_dyn_fd_traj(hipStream_t s, int n, const MpBigModel<T>* d_model, c
                            const T* taumat, const T* Ftipmat, long B, long Nt, T h, int intRes, float* pos, float* vel, float* acc,
                            bool time_major) {
   if (B <= 0 || Nt <= 0) return hipSuccess;
-  const dim3 grid((unsigned)((B + 63) / 64));
-  const int tm = time_major ? 1 : 0;
-  MP_DISPATCH_CAP(n, {
-    if (Ftipmat) hipLaunchKernelGGL((k_dyn_fd_traj<CAP, T, true>), grid, dim3(64), 0, s, d_model, C, theta0, dtheta0, taumat, Ftipmat, B, Nt, h, intRes, pos, vel, acc, tm);
-    else hipLaunchKernelGGL((k_dyn_fd_traj<CAP, T, false>), grid, dim3(64), 0, s, d_model, C, theta0, dtheta0, taumat, Ftipmat, B, Nt, h, intRes, pos, vel, acc, tm);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_CAP(n, MP_FLAG(Ftipmat != nullptr, F,
+      return launch(k_dyn_fd_traj<CAP, T, F>, mp_grid(B, kWave), kWave, 0, s, d_model, C, theta0, dtheta0, taumat, Ftipmat, B, Nt, h, intRes, pos,
+                    vel, acc, time_major)))
 }
 template hipError_t mpk_dyn_fd_traj<float>(hipStream_t, int, const MpBigModel<float>*, const MpCall<float>&, const float*, const float*,
                                            const float*, const float*, long, long, float, int, float*, float*, float*, bool);
@@ -2089,22 +1963,16 @@ template hipError_t mpk_dyn_fd_traj<double>(hipStream_t, int, const MpBigModel<d
 hipError_t mpk_dyn_traj(hipStream_t s, int n, const MpBigModel<float>* d_model, const MpCall<float>& C, bool ftip, const float* start,
                         const float* end, long B, long Nt, double Tf, int method, float* pos, float* vel, float* acc, float* tau) {
   if (B <= 0 || Nt <= 0) return hipSuccess;
-  MP_DISPATCH_CAP(n, {
-    if (ftip) hipLaunchKernelGGL((k_dyn_traj<CAP, true>), dim3(grid_for(B * Nt)), dim3(kBlock), 0, s, d_model, C, start, end, B, Nt, Tf, method, pos, vel, acc, tau);
-    else hipLaunchKernelGGL((k_dyn_traj<CAP, false>), dim3(grid_for(B * Nt)), dim3(kBlock), 0, s, d_model, C, start, end, B, Nt, Tf, method, pos, vel, acc, tau);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_CAP(n, MP_FLAG(ftip, F,
+      return launch(k_dyn_traj<CAP, F>, mp_grid(B * Nt, kBlock), kBlock, 0, s, d_model, C, start, end, B, Nt, Tf, method, pos, vel, acc, tau)))
 }
 
 hipError_t mpk_transpose_rows(hipStream_t s, const void* src, void* dst, long outer, long inner, int row_dwords) {
   if (outer <= 0 || inner <= 0 || row_dwords <= 0) return hipSuccess;
   const int TI = mp_tr_ti(row_dwords);
-  const long gx = (inner + TI - 1) / TI, gy = (outer + MP_TR_TO - 1) / MP_TR_TO;
-  if (gx * gy > 0x7fffffffL) return hipErrorInvalidValue;
   const size_t lds = (size_t)MP_TR_TO * (TI * row_dwords + 1) * sizeof(unsigned);
-  hipLaunchKernelGGL(k_transpose_rows, dim3((unsigned)(gx * gy)), dim3(kBlock), lds, s, (const unsigned*)src, (unsigned*)dst, outer,
-                     inner, row_dwords);
-  return hipGetLastError();
+  return launch(k_transpose_rows, mp_grid2(mp_blocks(inner, TI), mp_blocks(outer, MP_TR_TO)), kBlock, lds, s, (const unsigned*)src,
+                (unsigned*)dst, outer, inner, row_dwords);
 }
 
 // K closed-loop regulation runs (mp_pd_regulation_run), one lane each: rows of theta0 / des (K, n), gains per run, errors (K, steps)
@@ -2163,9 +2031,14 @@ __global__ __launch_bounds__(kBlock) void k_dyn_ik(const MpBigModel<double>* __r
 hipError_t mpk_cartesian_traj(hipStream_t s, const double* Xstart, const double* Xend, long B, long Nt, double Tf, int method,
                               float* pos, float* vel, float* acc, float* ori) {
   if (B <= 0 || Nt <= 0) return hipSuccess;
-  const unsigned bpt = (unsigned)((Nt + kBlock - 1) / kBlock);
-  hipLaunchKernelGGL(k_cartesian_traj, dim3((unsigned)(B * bpt)), dim3(kBlock), 0, s, Xstart, Xend, Nt, bpt, Tf, method, pos, vel, acc, ori);
-  return hipGetLastError();
+  const unsigned bpt = mp_grid(Nt, kBlock).x;
+  return launch(k_cartesian_traj, mp_grid2(B, bpt), kBlock, 0, s, Xstart, Xend, Nt, bpt, Tf, method, pos, vel, acc, ori);
+}
+
+// the grid of the IK work queues: resident lanes only (two 256-thread blocks per CU; fp64 IK needs > 128 VGPRs): the queue feeds them
+static MpGrid ik_grid(long B, int compute_units) {
+  const long want = mp_blocks(B, kBlock), cap = 2L * (compute_units > 0 ? compute_units : 256);
+  return mp_grid(want < cap ? want : cap, 1);
 }
 
 hipError_t mpk_ik(hipStream_t s, const MpModel<double>& M, const MpIkParams& P, const double* Tdes, const double* theta0, long B,
@@ -2173,24 +2046,20 @@ hipError_t mpk_ik(hipStream_t s, const MpModel<double>& M, const MpIkParams& P, 
   if (B <= 0) return hipSuccess;
   hipError_t e = hipMemsetAsync(queue_counter, 0, sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;
-  // resident lanes only (two 256-thread blocks per CU; fp64 IK needs > 128 VGPRs): the queue feeds them
-  const long want = (B + kBlock - 1) / kBlock, cap = 2L * (compute_units > 0 ? compute_units : 256);
-  const unsigned grid = (unsigned)(want < cap ? want : cap);
-  MP_DISPATCH_N(M.n, { hipLaunchKernelGGL((k_ik<N>), dim3(grid), dim3(kBlock), 0, s, M, P, Tdes, theta0, B, theta, success, iterations, restarts, queue_counter); })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_ik<N>, ik_grid(B, compute_units), kBlock, 0, s, M, P, Tdes, theta0, B, theta, success, iterations,
+                                   restarts, queue_counter))
 }
 
 hipError_t mpk_pd_regulation(hipStream_t s, const MpModel<double>& M, const MpCall<double>& C, const double* theta0, const double* des,
                              const double* Kp, const double* Kd, long K, double dt, int steps, double* err, int* count) {
   if (K <= 0) return hipSuccess;  // (steps == 0 still launches: every run reports a count of 0)
-  MP_DISPATCH_N(M.n, { hipLaunchKernelGGL((k_pd_regulation<N>), dim3((unsigned)((K + 63) / 64)), dim3(64), 0, s, M, C, theta0, des, Kp, Kd, K, dt, steps, err, count); })
-  return hipGetLastError();
+  MP_DISPATCH_N(M.n, return launch(k_pd_regulation<N>, mp_grid(K, kWave), kWave, 0, s, M, C, theta0, des, Kp, Kd, K, dt, steps, err, count))
 }
 hipError_t mpk_dyn_pd_regulation(hipStream_t s, int n, const MpBigModel<double>* d_model, const MpCall<double>& C, const double* theta0,
                                  const double* des, const double* Kp, const double* Kd, long K, double dt, int steps, double* err, int* count) {
   if (K <= 0) return hipSuccess;  // (steps == 0 still launches: every run reports a count of 0)
-  MP_DISPATCH_CAP(n, { hipLaunchKernelGGL((k_dyn_pd_regulation<CAP>), dim3((unsigned)((K + 63) / 64)), dim3(64), 0, s, d_model, C, theta0, des, Kp, Kd, K, dt, steps, err, count); })
-  return hipGetLastError();
+  MP_DISPATCH_CAP(n, return launch(k_dyn_pd_regulation<CAP>, mp_grid(K, kWave), kWave, 0, s, d_model, C, theta0, des, Kp, Kd, K, dt, steps, err,
+                                   count))
 }
 
 template <int CAP>
@@ -2207,20 +2076,14 @@ hipError_t mpk_dyn_ik(hipStream_t s, int n, const MpBigModel<double>* d_model, c
   if (B <= 0) return hipSuccess;
   hipError_t e = hipMemsetAsync(queue_counter, 0, sizeof(unsigned long long), s);
   if (e != hipSuccess) return e;
-  const long want = (B + kBlock - 1) / kBlock, cap = 2L * (compute_units > 0 ? compute_units : 256);
-  MP_DISPATCH_CAP(n, {
-    const MpIkParamsT<CAP> Q = ik_params_for<CAP>(P);
-    hipLaunchKernelGGL((k_dyn_ik<CAP>), dim3((unsigned)(want < cap ? want : cap)), dim3(kBlock), 0, s, d_model, Q, Tdes, theta0, B, theta, success,
-                       iterations, restarts, queue_counter);
-  })
-  return hipGetLastError();
+  MP_DISPATCH_CAP(n, return launch(k_dyn_ik<CAP>, ik_grid(B, compute_units), kBlock, 0, s, d_model, ik_params_for<CAP>(P), Tdes, theta0, B,
+                                   theta, success, iterations, restarts, queue_counter))
 }
 
 hipError_t mpk_potential_field(hipStream_t s, const float* pos, const float* goal3_host, const float* obs, long P, long O,
                                float influence, float* pot, float* grad) {
   if (P <= 0) return hipSuccess;
   const float inv = influence > 0.0f ? (float)(1.0 / (double)influence) : 0.0f;
-  hipLaunchKernelGGL(k_potential_field, dim3(grid_for(P)), dim3(kBlock), 0, s, pos, goal3_host[0], goal3_host[1], goal3_host[2], obs,
-                     P, O, inv, influence * influence, pot, grad);
-  return hipGetLastError();
+  return launch(k_potential_field, mp_grid(P, kBlock), kBlock, 0, s, pos, goal3_host[0], goal3_host[1], goal3_host[2], obs, P, O, inv,
+                influence * influence, pot, grad);
 }

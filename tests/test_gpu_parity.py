@@ -224,6 +224,51 @@ def test_fused_equals_two_step_pipeline(ctx, models):
         assert (np.abs(f2 - two) <= 4e-6 * np.abs(two).max(axis=1, keepdims=True)).all()
 
 
+@pytest.mark.parametrize("n", (1, 8, "ur5 upright"))
+def test_fused_with_a_wrench_on_the_generic_kernels(n, ctx, tables):
+    """k_traj_id_pk_tab<N, true> on a model that is not specialised, at the two ends of the joint-count switch: 3 trajectories of 515
+    timesteps = 258 lanes each, a full 256-lane block and a two-lane one.  Against the two-step pipeline with the same wrench under the
+    bound of the test above, and against the float64 twin on the same float32 rows under the suite's float32 rule.  "ur5 upright": the arm
+    balanced on its base with a small wrench, where every row is handed to the float64 pass (k_traj_id_hard<6, true> behind the fused
+    kernel, k_id_hard<6, true> behind the two-step one), which has to carry the wrench too."""
+    from manipulapy_amd import _hip
+    from test_random_robots import random_robot
+
+    rng = np.random.default_rng(4100 + (n if isinstance(n, int) else 0))
+    B, N = 3, 515
+    if isinstance(n, int):
+        tab = random_robot(rng, n, ("general",))
+        lo, hi = np.asarray(tab.joint_limits, dtype=float).T
+        s, e = (rng.uniform(lo, hi, (B, n)).astype(np.float32) for _ in range(2))
+        F = np.array([1.0, -2.0, 0.5, 3.0, -1.5, 0.75])
+    else:
+        tab = tables["ur5"]
+        up = np.array([0.0, -np.pi / 2, 0.0, -np.pi / 2, 0.0, 0.0])
+        s, e = ((up + rng.uniform(-2e-3, 2e-3, (B, 6))).astype(np.float32) for _ in range(2))
+        F = np.array([0.01, -0.02, 0.005, 0.03, -0.015, 0.0075])
+    m = _hip.HipModel(tab.S, tab.Mcom, tab.G, tab.M_ee, tab.joint_limits)
+    try:
+        p, v, a = (x.reshape(-1, m.n) for x in ctx.batch_trajectory_host(m, s, e, 2.0, N, 5))
+        if not isinstance(n, int):
+            assert _hip.cpu_id_row_precision(m, p, v, a, None, F).mean() > 0.9
+        fused = ctx.traj_id_fused_host(m, s, e, 2.0, N, 5, None, F).reshape(-1, m.n)
+        two = ctx.id_trajectory_host(m, p, v, a, None, F)
+        bare = ctx.traj_id_fused_host(m, s, e, 2.0, N, 5).reshape(-1, m.n)
+        want = _hip.cpu_id_trajectory(m, p, v, a, None, F, dtype=np.float64)
+        assert (np.abs(fused - two) <= 4e-6 * np.abs(two).max(axis=1, keepdims=True)).all()
+        assert_f32(fused, want)
+        assert_f32(two, want)
+        d = [ctx.to_device(np.ascontiguousarray(x)) for x in (p, v, a)]   # the device form parks its float64 pass: k_id_hard_batch<N, true>
+        d_tau = ctx.alloc(two.nbytes)
+        ctx.id_trajectory(m, *d, len(p), d_tau, None, F)
+        np.testing.assert_array_equal(d_tau.download(two.shape, np.float32), two)
+        for b in (*d, d_tau):
+            b.free()
+        assert (np.abs(bare - want) > 1e-3 * np.abs(want).max(axis=1, keepdims=True)).any()   # the wrench is not a detail of these rows
+    finally:
+        m.destroy()
+
+
 @pytest.mark.parametrize("robot,dtype", [("ur5", np.float32), ("iiwa14", np.float64), ("panda", np.float32), ("xarm6", np.float64)])
 def test_random_rows_against_oracle(robot, dtype, ctx, models, tables):
     """Seeded random rows (positions inside the joint limits) vs the CPU oracle, incl. a wrench."""

@@ -90,6 +90,27 @@ def test_kernel_matches_twin_random_chains(ctx, seed):
     assert abs(rr - rrc) <= 1e-12 * rrc
 
 
+@pytest.mark.parametrize("n", (1, 8))
+def test_normal_kernel_every_instance_at_both_ends_of_the_switch(ctx, n):
+    """k_id_regressor_normal<N, wrench, with A> at n = 1 and n = 8, all four instances on 65 rows (six tiles of 12 rows, the last one
+    partial), each against the twin under the bounds of the random-chain test; without A, b and rr are those of the call with A."""
+    rng = np.random.default_rng(700 + n)
+    tb = random_robot(rng, n, ("general",))
+    m = _hip.HipModel(tb.S, tb.Mcom, tb.G, tb.M_ee, tb.joint_limits)
+    q, qd, qdd = _rows(rng, n, 65)
+    tau = rng.uniform(-10, 10, q.shape)
+    for F in (None, rng.uniform(-3, 3, 6)):
+        A, b, rr = ctx.id_regressor_normal_host(m, q, qd, qdd, tau, None, F)
+        Ac, bc, rrc = _hip.cpu_id_regressor_normal(m, q, qd, qdd, tau, None, F)
+        _close_A(A, Ac, f"n={n} wrench {F is not None} A")
+        A0, b0, rr0 = ctx.id_regressor_normal_host(m, q, qd, qdd, tau, None, F, want_A=False)
+        assert A0 is None
+        for got, what in (((b, rr), "with A"), ((b0, rr0), "without A")):
+            np.testing.assert_allclose(got[0], bc, rtol=1e-11, atol=1e-11 * np.abs(bc).max(), err_msg=f"n={n} wrench {F is not None} b {what}")
+            assert abs(got[1] - rrc) <= 1e-12 * rrc, (n, F is not None, what)
+        assert np.array_equal(b0, b) and rr0 == rr
+
+
 @pytest.mark.parametrize("robot", ("ur5", "panda"))
 def test_normal_kernel_million_rows_and_bit_identical(ctx, robot):
     m = _model(robot)

@@ -212,6 +212,23 @@ def test_device_form_host_form_subsets_and_torques(ctx):
     assert not np.array_equal(wrench["torques"], dev["torques"], equal_nan=True)
 
 
+def test_grid_source_with_a_wrench(ctx):
+    """k_traj_sample<N, grid, torques with a wrench>, the one instance the curve case above does not reach: xarm6 (6 joints, the full
+    call) and panda (8 joints, the last of the joint-count switch: the torques alone, which there come from the fused recursion), five
+    paths of 33 rows = two waves and a partial one.  The torques follow the inverse-dynamics twin WITH the wrench at the returned rows
+    and differ from the call without it; every other output is that call's, bit for bit."""
+    F = np.array([0.3, -0.2, 0.1, 4.0, -3.0, 2.0])
+    for key, want in ((("grid", "xarm6", 33, True), ALL), (("grid", "panda", 33, True), ("torques",))):
+        case = _case(key)
+        five = _rows(case, [b % case["planted"] for b in range(5)])   # (the sound paths come first)
+        bare, full = device_run(ctx, five, 33), device_run(ctx, five, 33, Ftip=F)
+        got = device_run(ctx, five, 33, want=want, Ftip=F)
+        assert np.isin(full["status"], (sc.OK, sc.TRUNCATED)).all()
+        sc.check_torques(five, dict(full, torques=got["torques"]), f"grid {key[1]} with a wrench", Ftip=F)
+        _same(full, bare, tuple(k for k in ALL if k != "torques"))
+        assert not np.array_equal(got["torques"], bare["torques"], equal_nan=True)
+
+
 def test_planner_hip_against_numpy(ctx):
     """batch_time_optimal_trajectory on both backends: the samples agree under the rule, and on "hip" every DONE / STRAIGHT row of the
     base run comes back OK (acceleration limits 40: none of the 98 rows has an interior stop on N = 33)."""

@@ -122,6 +122,27 @@ def test_kernels_match_cpu_twins(ctx, case):
         d.free()
 
 
+@pytest.mark.parametrize("n", (1, 8))
+def test_coefficients_with_a_tip_wrench(ctx, n):
+    """k_path_coeffs<N, true> at the two ends of the joint-count switch: 5 paths of 13 grid points = 65 rows (one full wave and one
+    lane), a tip wrench in c, against the twin under the float64 row rule.  The wrench moves c (a launch of the instance without
+    one would give the coefficients of the call without one), and leaves a and b alone."""
+    model, lim, vlim, _ = tc.chain_case(n)
+    paths = tc.make_paths(lim, 5, 13)
+    q, dq, ddq = (x.reshape(-1, n) for x in paths)
+    F = np.array([0.3, -0.2, 0.1, 4.0, -3.0, 2.0])
+    want, bare = (_hip.cpu_path_dynamics(model, q, dq, ddq, vlim, tc.G9, Fw) for Fw in (F, None))
+    assert not np.allclose(want[2], bare[2], rtol=1e-3, atol=0) and np.array_equal(want[0], bare[0])
+    d = _Device(ctx, model, paths)
+    try:
+        for Fw, ref in ((F, want), (None, bare)):
+            d.coeffs(vlim, Fw)
+            for got, co, what in zip(d.coefficients(), ref, ("a", "b", "c", "xbar")):
+                tc.f64_rule(got.reshape(co.shape), co, f"n {n} wrench {Fw is not None} {what}")
+    finally:
+        d.free()
+
+
 def test_failing_paths_leave_their_neighbours_alone(ctx):
     """Failing paths at lanes 0, 63 and 64 - the ends of the first wave and the start of the second - with one status each."""
     model, vlim, tlim, alim, (q, dq, ddq), _, _, _ = _setup("ur5")
