@@ -1141,6 +1141,94 @@ int mp_trajectory_sample_cpu_f64(const mp_model* model, const double* t, const d
                                  double* s, double* sd, double* sdd, double* positions, double* velocities, double* accelerations,
                                  double* torques, int nthreads);
 
+/* ---- batched Cartesian straight-line paths over the sphere model above, proven free (float64, models of 3..8 joints; generic
+ * kernels only, no run-time specialisation; csrc/mp_cartesian.h).  For B independent problems: from a start configuration the tool
+ * travels on a straight line to a goal pose; the joint-space curve that does it comes back as the (q, dq/ds, d2q/ds2) grid that
+ * mp_toppra_* reads, and conservative advancement proves the curve the trajectory sampler executes collision-free.  The kernels,
+ * the CPU twin and the tests' NumPy oracle implement exactly the contract below.
+ * Per problem: q_start (n), T_goal (16, row-major; the last row is not read).  Per launch: the box lo, hi (n, finite, lo <= hi),
+ *   the grid size N in 2..65536, task MP_TASK_FULL (6 rows: needs n >= 6) or MP_TASK_POSITION (3 rows, orientation free: needs
+ *   n >= 3) - fewer joints than rows is MP_ERR_UNSUPPORTED, as is n > 8 - eomg, ev, damping, max_joint_step positive and finite,
+ *   max_iters in 0..65536, and margin, tol, max_steps as for the edges.  Anything else is MP_ERR_INVALID with a message.
+ * 1 The line.  T_start = FK(q_start).  V = [omega; v] = the error vector of the goal step (mp_goal_ik_*) between T_start and T_goal:
+ *   the rotation vector of R_start^T R_goal in space axes and p_goal - p_start.  The target at s_i = i / (N - 1) is
+ *   R(s) = exp([omega] s) R_start (Rodrigues with angle |omega| s about omega / |omega|; the identity when |omega| = 0),
+ *   p(s) = p_start + s v.  POSITION uses p(s) and v alone.  A non-finite value in q_start or T_goal, or (FULL) a rotation angle of
+ *   R_start^T R_goal at or above pi - 1e-6 (no unique geodesic): INVALID.
+ * 2 Tracking, grid point by grid point; J_h = the task's rows of the hybrid Jacobian (angular rows first), h = 1 / (N - 1).
+ *   Row 0 is q_start bit for bit, with no Newton step.  Point i >= 1 starts from the predictor q_{i-1} + h dq_{i-1} and makes at most
+ *   max_iters steps q <- q + J_h^T (J_h J_h^T + damping^2 1)^-1 e, e = the same error vector between FK(q) and the target, not clamped
+ *   into the box; it has converged when rot < eomg && tr < ev (POSITION: tr < ev), tested before every step.  At every accepted
+ *   point, row 0 included: dq = J_h^T (J_h J_h^T)^-1 V and ddq = -J_h^T (J_h J_h^T)^-1 (Jdot_h dq), undamped and minimum-norm, so
+ *   that J_h dq = V along the whole line.  The first failing decision ends the problem, in this order at each point:
+ *     not converged after max_iters steps                                  STALLED
+ *     the converged q outside [lo, hi]                                     LIMIT (at index 0 when q_start itself is outside)
+ *     max_j |q_i - q_{i-1}| > max_joint_step                               JUMP (a branch flip near a singularity)
+ *     a pivot d of the Cholesky factor of J_h J_h^T with d <= 2^-46 A_jj   SINGULAR
+ *   reached = the number of accepted grid points; rows reached..N-1 of q, dq, ddq are NaN.
+ * 3 Proof.  The curve is the quintic Hermite interpolant of the grid rows, the one mp_trajectory_sample_* evaluates for a grid
+ *   source, through the same function.  Span i (s_i..s_{i+1}, u in [0, 1]) is the quintic Bezier curve on
+ *     P0 = q_i, P1 = P0 + h dq_i / 5, P2 = P0 + 2 h dq_i / 5 + h^2 ddq_i / 20,
+ *     P5 = q_{i+1}, P4 = P5 - h dq_{i+1} / 5, P3 = P5 - 2 h dq_{i+1} / 5 + h^2 ddq_{i+1} / 20,
+ *   so |dq_j/du| <= 5 max_k |P_{k+1,j} - P_{k,j}| and |q_j(u)| <= max_k |P_{k,j}|.  These take the places of the blend's speed and
+ *   reach in the sums of mp_path_blend_*; the advance from u = 0, its three decisions (BLOCKED: d - margin <= tol; FREE:
+ *   u + tau >= 1; UNDECIDED: max_steps evaluations) and their order are that contract's.  Every span of a fully tracked problem is
+ *   checked on its own.  The problem is DONE if all its spans are FREE, else BLOCKED or UNDECIDED as the FIRST span that is not
+ *   free says; span = that span, t = the u at which its advance stopped.  DONE: span -1, t 1.
+ * 4 Deviation.  Each span evaluates the curve at u = 1/2, takes its FK and compares it with the line's pose at (i + 1/2) / (N - 1):
+ *   deviation_pos / deviation_rot = the largest position distance / rotation angle (POSITION: 0) over the problem's spans.
+ * Per problem (every output may be NULL, at least one is needed; the device form needs q, dq and ddq, which its span launch reads):
+ *     status (B) int32                   MP_CARTESIAN_DONE 0, _STALLED 1, _SINGULAR 2, _LIMIT 3, _JUMP 4, _BLOCKED 5, _UNDECIDED 6,
+ *                                        _INVALID -1
+ *     reached, span (B) int32
+ *     t, clearance (B)                   clearance: the smallest distance any evaluation of any span saw
+ *     deviation_pos, deviation_rot (B)
+ *     pose_error (B)                     the largest converged error over the grid points 1..reached-1: max(rot, tr), POSITION: tr
+ *     iterations, evaluations (B) int32  Newton steps; collision evaluations over all spans
+ *     q, dq, ddq (B, N, n)               the grid, batch-major
+ *     span_status (B, N - 1) int32       MP_EDGE_FREE / _BLOCKED / _UNDECIDED, -1 for the spans of a problem not tracked to its end
+ *     span_clearance (B, N - 1)
+ *   A problem that was not tracked to its end has span -1, NaN in t, clearance and the deviations and 0 evaluations; INVALID also has
+ *   a NaN pose_error.  No random numbers; a problem's result depends on its own content only.  No output may overlap an input.
+ * mp_cartesian_path_f64: device arrays, 16-byte aligned.  Three launches on the compute stream: the tracking, one lane a problem;
+ *   the spans, one lane a span, taken from a queue, one collision evaluation a trip; the reduction, one lane a problem.  The spans'
+ *   records pass through d_workspace, mp_cartesian_path_workspace_bytes(B, N) bytes (or minus an MP_ERR_* code); max_blocks > 0 caps
+ *   the grid of the span launch.  Asynchronous; it allocates nothing once the handle is resident on the context and may then be
+ *   captured into a launch graph (the queue head's reset is part of it).  Launches that share a collision handle share its queue
+ *   head: they are serialised by the handle's lock and the compute stream.
+ *   mp_cartesian_path_host_f64: host arrays, device memory (workspace and unrequested grid arrays included) from the context's pool.
+ *   mp_cartesian_path_cpu_f64: the kernels' per-problem and per-span code on the host, no context. */
+#define MP_CARTESIAN_DONE 0
+#define MP_CARTESIAN_STALLED 1
+#define MP_CARTESIAN_SINGULAR 2
+#define MP_CARTESIAN_LIMIT 3
+#define MP_CARTESIAN_JUMP 4
+#define MP_CARTESIAN_BLOCKED 5
+#define MP_CARTESIAN_UNDECIDED 6
+#define MP_CARTESIAN_INVALID (-1)
+#define MP_TASK_FULL 0
+#define MP_TASK_POSITION 1
+int64_t mp_cartesian_path_workspace_bytes(int64_t B, int64_t N);
+int mp_cartesian_path_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q_start, const double* d_T_goal, int64_t B,
+                          const double* lo, const double* hi, int64_t N, int task, double eomg, double ev, double damping, int max_iters,
+                          double max_joint_step, double margin, double tol, int max_steps, void* d_workspace, size_t workspace_bytes,
+                          int max_blocks, int32_t* d_status, int32_t* d_reached, int32_t* d_span, double* d_t, double* d_clearance,
+                          double* d_deviation_pos, double* d_deviation_rot, double* d_pose_error, int32_t* d_iterations,
+                          int32_t* d_evaluations, double* d_q, double* d_dq, double* d_ddq, int32_t* d_span_status,
+                          double* d_span_clearance);
+int mp_cartesian_path_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q_start, const double* T_goal, int64_t B,
+                               const double* lo, const double* hi, int64_t N, int task, double eomg, double ev, double damping,
+                               int max_iters, double max_joint_step, double margin, double tol, int max_steps, int32_t* status,
+                               int32_t* reached, int32_t* span, double* t, double* clearance, double* deviation_pos,
+                               double* deviation_rot, double* pose_error, int32_t* iterations, int32_t* evaluations, double* q, double* dq,
+                               double* ddq, int32_t* span_status, double* span_clearance);
+int mp_cartesian_path_cpu_f64(const mp_model* model, const mp_collision* h, const double* q_start, const double* T_goal, int64_t B,
+                              const double* lo, const double* hi, int64_t N, int task, double eomg, double ev, double damping,
+                              int max_iters, double max_joint_step, double margin, double tol, int max_steps, int32_t* status,
+                              int32_t* reached, int32_t* span, double* t, double* clearance, double* deviation_pos,
+                              double* deviation_rot, double* pose_error, int32_t* iterations, int32_t* evaluations, double* q, double* dq,
+                              double* ddq, int32_t* span_status, double* span_clearance, int nthreads);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (new; the reference is single-device) ------
  * Trajectory batches are sharded over ranks with no exchange during compute; the only collective is
  * the all-gather that reassembles the torque history.  Rank 0 creates the id, the launcher

@@ -197,6 +197,10 @@ SIGNATURES = {
     "mp_trajectory_sample_f64": (ctypes.c_int, [_vp] * 4 + [_i64, _i64] + [_vp] * 9 + [_i64, ctypes.c_double, _i64, _c_dp, _c_dp, ctypes.c_int] + [_vp] * 10),
     "mp_trajectory_sample_host_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _i64, _i64, _c_dp, _c_dp, _c_dp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, ctypes.c_double, _i64, _c_dp, _c_dp, _vp, _vp, _vp] + [_c_dp] * 7),
     "mp_trajectory_sample_cpu_f64": (ctypes.c_int, [_vp, _c_dp, _c_dp, _i64, _i64, _c_dp, _c_dp, _c_dp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _i64, ctypes.c_double, _i64, _c_dp, _c_dp, _vp, _vp, _vp] + [_c_dp] * 7 + [ctypes.c_int]),
+    "mp_cartesian_path_workspace_bytes": (_i64, [_i64, _i64]),
+    "mp_cartesian_path_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, _i64, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, ctypes.c_size_t, ctypes.c_int] + [_vp] * 15),
+    "mp_cartesian_path_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _i64, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _vp, _vp, _c_dp, _c_dp, _c_dp, _vp, _c_dp]),
+    "mp_cartesian_path_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, _i64, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, _c_dp, _vp, _vp, _c_dp, _c_dp, _c_dp, _vp, _c_dp, ctypes.c_int]),
     "mp_goal_ik_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_goal_ik_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _c_dp, _vp, _vp, _vp, _c_dp, _c_dp, _vp]),
     "mp_goal_ik_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _c_dp, _i64, _c_dp, _c_dp, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, _vp, _c_dp, _vp, _vp, _vp, _c_dp, _c_dp, _vp, ctypes.c_int]),
@@ -837,6 +841,34 @@ class HipContext:
         by tests/test_gpu_goal.py.)"""
         return _goal_ik((self.handle,), self.lib.mp_goal_ik_host_f64, model, collision, T_goal, q_seed, lo, hi, margin, tol, eomg, ev,
                         damping, step_cap, max_iters, max_attempts, seed, want)
+
+    def cartesian_path(self, model, collision, d_q_start, d_T_goal, problems, lo, hi, N, margin, tol, *, task="full", eomg=1e-6,
+                       ev=1e-6, damping=0.01, max_iters=20, max_joint_step=0.5, max_steps=64, d_workspace, workspace_bytes,
+                       max_blocks: int = 0, d_status=None, d_reached=None, d_span=None, d_t=None, d_clearance=None,
+                       d_deviation_pos=None, d_deviation_rot=None, d_pose_error=None, d_iterations=None, d_evaluations=None, d_q,
+                       d_dq, d_ddq, d_span_status=None, d_span_clearance=None):
+        """Cartesian straight-line paths on device buffers (float64; csrc/mp_cartesian.h, contract in include/manipula_hip.h):
+        d_q_start (problems,n), d_T_goal (problems,16); lo, hi (n) host arrays; d_q / d_dq / d_ddq (problems,N,n) are required, the
+        other outputs - status / reached / span / iterations / evaluations (problems) int32, t / clearance / deviation_pos /
+        deviation_rot / pose_error (problems), span_status (problems,N-1) int32, span_clearance (problems,N-1) - may be None.
+        d_workspace holds the spans' records: cartesian_path_workspace_bytes(problems, N).  `max_blocks` > 0 caps the grid of the
+        span launch.  Asynchronous (capturable once the handle has been used or given a world on this context)."""
+        lo, hi = _as_c(lo, np.float64, (model.n,), "lo"), _as_c(hi, np.float64, (model.n,), "hi")
+        _check(self.lib.mp_cartesian_path_f64(self.handle, model.handle, collision.handle, _p(d_q_start), _p(d_T_goal), int(problems),
+                                              _dptr(lo), _dptr(hi), int(N), _cartesian_task(task), float(eomg), float(ev), float(damping),
+                                              int(max_iters), float(max_joint_step), float(margin), float(tol), int(max_steps),
+                                              _p(d_workspace), ctypes.c_size_t(int(workspace_bytes)), int(max_blocks), _p(d_status),
+                                              _p(d_reached), _p(d_span), _p(d_t), _p(d_clearance), _p(d_deviation_pos),
+                                              _p(d_deviation_rot), _p(d_pose_error), _p(d_iterations), _p(d_evaluations), _p(d_q),
+                                              _p(d_dq), _p(d_ddq), _p(d_span_status), _p(d_span_clearance)))
+
+    def cartesian_path_arrays(self, model, collision, q_start, T_goal, lo, hi, N, margin, tol, *, task="full", eomg=1e-6, ev=1e-6,
+                              damping=0.01, max_iters=20, max_joint_step=0.5, max_steps=64, want=None):
+        """The same on host arrays (mp_cartesian_path_host_f64) through the context's pool, workspace included: a dict of the outputs
+        named in `want` (default: all of CARTESIAN_OUTPUTS).  Its equality with the device form is held by
+        tests/test_gpu_cartesian.py."""
+        return _cartesian_path((self.handle,), self.lib.mp_cartesian_path_host_f64, model, collision, q_start, T_goal, lo, hi, N, margin,
+                               tol, task, eomg, ev, damping, max_iters, max_joint_step, max_steps, want)
 
     def collision_set_world(self, collision, kinds, params):
         """Replaces the obstacle table of `collision` on this context's device, behind the launches already on its stream."""
@@ -1866,6 +1898,68 @@ def cpu_goal_ik(model: "HipModel", collision: "HipCollision", T_goal, q_seed, lo
     """CPU twin of HipContext.goal_ik_arrays."""
     return _goal_ik((), load_library().mp_goal_ik_cpu_f64, model, collision, T_goal, q_seed, lo, hi, margin, tol, eomg, ev, damping,
                     step_cap, max_iters, max_attempts, seed, want, nthreads)
+
+
+CARTESIAN_OUTPUTS = ("status", "reached", "span", "t", "clearance", "deviation_pos", "deviation_rot", "pose_error", "iterations",
+                     "evaluations", "q", "dq", "ddq", "span_status", "span_clearance")
+(CARTESIAN_DONE, CARTESIAN_STALLED, CARTESIAN_SINGULAR, CARTESIAN_LIMIT, CARTESIAN_JUMP, CARTESIAN_BLOCKED, CARTESIAN_UNDECIDED,
+ CARTESIAN_INVALID) = 0, 1, 2, 3, 4, 5, 6, -1
+CARTESIAN_TASKS = ("full", "position")
+
+
+def _cartesian_task(task) -> int:
+    if task in CARTESIAN_TASKS:
+        return CARTESIAN_TASKS.index(task)
+    if isinstance(task, (int, np.integer)) and not isinstance(task, bool):
+        return int(task)  # (a value outside 0..1 is the entry's to refuse)
+    raise ValueError(f"unknown task {task!r}; choose from {CARTESIAN_TASKS}")
+
+
+def cartesian_path_workspace_bytes(problems: int, N: int) -> int:
+    """Bytes of workspace for HipContext.cartesian_path over `problems` problems of N grid points."""
+    r = int(load_library().mp_cartesian_path_workspace_bytes(int(problems), int(N)))
+    if r < 0:
+        _check(-r)
+    return r
+
+
+def _cartesian_path(lead, fn, model, collision, q_start, T_goal, lo, hi, N, margin, tol, task, eomg, ev, damping, max_iters,
+                    max_joint_step, max_steps, want, nthreads=None):
+    want = CARTESIAN_OUTPUTS if want is None else tuple(want)
+    for w in want:
+        if w not in CARTESIAN_OUTPUTS:
+            raise ValueError(f"unknown cartesian output {w!r}; choose from {CARTESIAN_OUTPUTS}")
+    q0 = _as_c(q_start, np.float64, name="q_start")
+    if q0.ndim != 2 or q0.shape[1] != model.n:
+        raise ValueError(f"q_start must be (problems, {model.n}); got {q0.shape}")
+    B, n = q0.shape
+    Tg = np.asarray(T_goal, dtype=np.float64)
+    if Tg.shape != (B, 4, 4) and Tg.shape != (B, 16):
+        raise ValueError(f"T_goal must be ({B}, 4, 4) or ({B}, 16); got {Tg.shape}")
+    Tg = _as_c(Tg.reshape(B, 16), np.float64, (B, 16), "T_goal")
+    lo, hi = _as_c(lo, np.float64, (n,), "lo"), _as_c(hi, np.float64, (n,), "hi")
+    grid = max(int(N), 1)  # (a value below 2 is the entry's to refuse)
+    shapes = {"q": (B, grid, n), "dq": (B, grid, n), "ddq": (B, grid, n), "span_status": (B, grid - 1), "span_clearance": (B, grid - 1)}
+    whole = ("status", "reached", "span", "iterations", "evaluations", "span_status")
+    out = {w: np.empty(shapes.get(w, (B,)), dtype=np.int32 if w in whole else np.float64) for w in want}
+    ptrs = []
+    for w in CARTESIAN_OUTPUTS:
+        a = out.get(w)
+        ptrs.append(None if a is None else (a.ctypes.data_as(_vp) if w in whole else _dptr(a)))
+    args = list(lead) + [model.handle, collision.handle, _dptr(q0), _dptr(Tg), B, _dptr(lo), _dptr(hi), int(N), _cartesian_task(task),
+                         float(eomg), float(ev), float(damping), int(max_iters), float(max_joint_step), float(margin), float(tol),
+                         int(max_steps)] + ptrs
+    if nthreads is not None:
+        args.append(int(nthreads))
+    _check(fn(*args))
+    return out
+
+
+def cpu_cartesian_path(model: "HipModel", collision: "HipCollision", q_start, T_goal, lo, hi, N, margin, tol, *, task="full", eomg=1e-6,
+                       ev=1e-6, damping=0.01, max_iters=20, max_joint_step=0.5, max_steps=64, want=None, nthreads: int = 0) -> dict:
+    """CPU twin of HipContext.cartesian_path_arrays."""
+    return _cartesian_path((), load_library().mp_cartesian_path_cpu_f64, model, collision, q_start, T_goal, lo, hi, N, margin, tol, task,
+                           eomg, ev, damping, max_iters, max_joint_step, max_steps, want, nthreads)
 
 
 def _pd_regulation_args(model, theta0, theta_des, Kp, Kd, g, steps):

@@ -24,6 +24,7 @@ PLAN_OP = "planning.rrt_connect"
 SHORTCUT_OP = "planning.shortcut_paths"
 GOAL_OP = "planning.goal_configurations"
 BLEND_OP = "planning.blend_paths"
+CARTESIAN_OP = "planning.cartesian_paths"
 
 
 def _hip_model_of(obj) -> _hip.HipModel:
@@ -254,6 +255,33 @@ class SphereCollisionModel:
         lead = wp.shape[:-2]
         out = execute_registered_kernel(BLEND_OP, self, np.ascontiguousarray(wp.reshape((-1,) + wp.shape[-2:])), cnt.reshape(-1), N,
                                         margin, tol, blend=blend, max_halvings=max_halvings, max_steps=max_steps, want=want)
+        return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}
+
+    # ------------------------------------------------------------------ Cartesian lines
+    def cartesian_paths(self, q_start, T_goal, lo, hi, N: int, margin: float = 0.0, tol: float = 1e-3, *, task: str = "full",
+                        eomg: float = 1e-6, ev: float = 1e-6, damping: float = 0.01, max_iters: int = 20, max_joint_step: float = 0.5,
+                        max_steps: int = 64, want=None) -> dict:
+        """Straight tool lines from B start configurations q_start (B, n) to B poses T_goal ((B, 4, 4), or any common leading shape)
+        inside the box lo, hi (n), on the N grid points s_i = i / (N - 1): {"status" (0 done, 1 stalled, 2 singular, 3 limit, 4 jump,
+        5 blocked, 6 undecided, -1 invalid), "reached", "span", "t", "clearance", "deviation_pos", "deviation_rot", "pose_error",
+        "iterations", "evaluations", "q", "dq", "ddq" (.., N, n), "span_status", "span_clearance" (.., N - 1)} or the subset named in
+        `want`.  The tool origin moves on the segment from its start to the goal's while (task "full") the orientation turns about
+        one axis at a constant rate; task "position" leaves the orientation free.  Every grid point is tracked from its predecessor
+        by at most `max_iters` damped Newton steps to within `eomg` / `ev`; a point that does not converge (stalled), leaves the box
+        (limit), moves a joint by more than `max_joint_step` (jump) or is singular ends the problem, "reached" points in.  "q", "dq",
+        "ddq" are the joint curve and its derivatives in s, the arguments of
+        OptimizedTrajectoryPlanning.batch_time_optimal_parameterization and of batch_sample_time_optimal(path=...); every span of
+        their quintic Hermite interpolant - the curve that sampler executes - is proven free by `check_edges`' conservative
+        advancement with this margin, tol and max_steps, or the problem is blocked / undecided at "span", "t".  "deviation_pos" /
+        "deviation_rot": how far the interpolant leaves the line at the spans' midpoints (raise N when it is too much).  A problem's
+        result depends on its content only."""
+        Tg, q0 = np.asarray(T_goal, dtype=np.float64), np.asarray(q_start, dtype=np.float64)
+        if Tg.ndim < 2 or Tg.shape[-2:] != (4, 4) or q0.ndim < 1 or q0.shape[-1] != self.n or Tg.shape[:-2] != q0.shape[:-1]:
+            raise ValueError(f"T_goal must be (..., 4, 4) and q_start (..., {self.n}) with one leading shape; got {Tg.shape} and {q0.shape}")
+        lead = q0.shape[:-1]
+        out = execute_registered_kernel(CARTESIAN_OP, self, np.ascontiguousarray(q0.reshape(-1, self.n)),
+                                        np.ascontiguousarray(Tg.reshape(-1, 16)), lo, hi, N, margin, tol, task=task, eomg=eomg, ev=ev,
+                                        damping=damping, max_iters=max_iters, max_joint_step=max_joint_step, max_steps=max_steps, want=want)
         return {k: v.reshape(lead + v.shape[1:]) for k, v in out.items()}
 
     # ------------------------------------------------------------------ pose goals

@@ -3437,6 +3437,88 @@ int mp_path_blend_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, 
 
 }  // extern "C"
 
+// ---- Cartesian straight-line paths over the sphere model (mp_cartesian.h): tracking, the spans on the work queue, the reduction.
+// The spans' records pass through the caller's workspace; one plan per call, made here.
+static int cartesian_path_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q0, const double* d_Tg,
+                               int64_t B, const MpCartParams& P, void* d_ws, size_t ws_bytes, int max_blocks, const MpCartOut& O,
+                               double* d_q, double* d_dq, double* d_ddq) {
+  REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
+  if (B == 0) return MP_OK;
+  REQUIRE(d_q0 && d_Tg, "%s: null device pointer", fn);
+  REQUIRE(d_q && d_dq && d_ddq, "%s: q, dq and ddq are what the spans are read from: all three are required", fn);
+  REQUIRE(aligned16(d_q0) && aligned16(d_Tg) && aligned16(O.status) && aligned16(O.reached) && aligned16(O.span) && aligned16(O.t) &&
+              aligned16(O.clearance) && aligned16(O.deviation_pos) && aligned16(O.deviation_rot) && aligned16(O.pose_error) &&
+              aligned16(O.iterations) && aligned16(O.evaluations) && aligned16(d_q) && aligned16(d_dq) && aligned16(d_ddq) &&
+              aligned16(O.span_status) && aligned16(O.span_clearance) && aligned16(d_ws),
+          "%s: device pointers must be 16-byte aligned", fn);
+  const size_t need = mp_cart_work_bytes((long)B, P.grid);
+  REQUIRE(d_ws && ws_bytes >= need, "%s: the workspace holds %zu bytes, the call needs %zu (mp_cartesian_path_workspace_bytes)", fn,
+          d_ws ? ws_bytes : (size_t)0, need);
+  std::lock_guard<std::mutex> hl(h->mu);
+  mp_collision::Resident* R = nullptr;
+  if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
+  PROFILE_SCOPE(ctx, fn);
+  MpQueuePlan plan;
+  HIP_TRY(mpk_cart_plan(model->d.n, P.task, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_cartesian_path(ctx->compute, model->d, collision_device(h, R), P, d_q0, d_Tg, (long)B, mp_cart_work(d_ws, (long)B, P.grid), d_q,
+                             d_dq, d_ddq, O, queue_grid(plan, B * (P.grid - 1), max_blocks), plan.lds));
+  return MP_OK;
+}
+
+extern "C" {
+
+int mp_cartesian_path_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q_start, const double* d_T_goal, int64_t B,
+                          const double* lo, const double* hi, int64_t N, int task, double eomg, double ev, double damping, int max_iters,
+                          double max_joint_step, double margin, double tol, int max_steps, void* d_workspace, size_t workspace_bytes,
+                          int max_blocks, int32_t* d_status, int32_t* d_reached, int32_t* d_span, double* d_t, double* d_clearance,
+                          double* d_deviation_pos, double* d_deviation_rot, double* d_pose_error, int32_t* d_iterations,
+                          int32_t* d_evaluations, double* d_q, double* d_dq, double* d_ddq, int32_t* d_span_status,
+                          double* d_span_clearance) {
+  const char* fn = "mp_cartesian_path_f64";
+  CHECK_SPHERE_ENTRY(fn);
+  MpCartParams P;
+  if (int rc = mp_cartesian_path_check(fn, model->d.n, B, lo, hi, N, task, eomg, ev, damping, max_iters, max_joint_step, margin, tol,
+                                       max_steps, &P))
+    return rc;
+  const MpCartOut O = {d_status, d_reached, d_span, d_t, d_clearance, d_deviation_pos, d_deviation_rot, d_pose_error, d_iterations,
+                       d_evaluations, d_span_status, d_span_clearance};
+  return cartesian_path_impl(fn, ctx, model, h, d_q_start, d_T_goal, B, P, d_workspace, workspace_bytes, max_blocks, O, d_q, d_dq, d_ddq);
+}
+
+int mp_cartesian_path_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q_start, const double* T_goal, int64_t B,
+                               const double* lo, const double* hi, int64_t N, int task, double eomg, double ev, double damping,
+                               int max_iters, double max_joint_step, double margin, double tol, int max_steps, int32_t* status,
+                               int32_t* reached, int32_t* span, double* t, double* clearance, double* deviation_pos,
+                               double* deviation_rot, double* pose_error, int32_t* iterations, int32_t* evaluations, double* q, double* dq,
+                               double* ddq, int32_t* span_status, double* span_clearance) {
+  const char* fn = "mp_cartesian_path_host_f64";
+  CHECK_SPHERE_ENTRY(fn);
+  MpCartParams P;
+  if (int rc = mp_cartesian_path_check(fn, model->d.n, B, lo, hi, N, task, eomg, ev, damping, max_iters, max_joint_step, margin, tol,
+                                       max_steps, &P))
+    return rc;
+  if (B == 0) return MP_OK;
+  REQUIRE(q_start && T_goal, "%s: null host pointer", fn);
+  REQUIRE(status || reached || span || t || clearance || deviation_pos || deviation_rot || pose_error || iterations || evaluations || q ||
+              dq || ddq || span_status || span_clearance,
+          "%s: at least one output is required", fn);
+  const size_t n = (size_t)model->d.n, ib = (size_t)B * sizeof(int32_t), db = (size_t)B * sizeof(double);
+  const size_t gb = (size_t)N * n * db, sp = (size_t)(N - 1);
+  const size_t ws_bytes = mp_cart_work_bytes((long)B, (long)N);
+  HostCall hc(ctx);  // (h is the collision handle)
+  const double *dq0 = hc.in(q_start, n * db), *dtg = hc.in(T_goal, 16 * db);
+  // the grid arrays the spans read stay on the device where the caller did not ask for them
+  auto grid = [&](double* host) { return host ? hc.out(host, gb) : hc.work<double>(gb); };
+  const MpCartOut O = {hc.out(status, ib), hc.out(reached, ib), hc.out(span, ib), hc.out(t, db), hc.out(clearance, db),
+                       hc.out(deviation_pos, db), hc.out(deviation_rot, db), hc.out(pose_error, db), hc.out(iterations, ib),
+                       hc.out(evaluations, ib), hc.out(span_status, sp * ib), hc.out(span_clearance, sp * db)};
+  double *dq_ = grid(q), *ddq_ = grid(dq), *dddq_ = grid(ddq);
+  void* dws = hc.work(ws_bytes);
+  return hc.run([&] { return cartesian_path_impl(fn, ctx, model, h, dq0, dtg, B, P, dws, ws_bytes, 0, O, dq_, ddq_, dddq_); });
+}
+
+}  // extern "C"
+
 // ---- fixed-rate sampling of timed paths (mp_sample.h): one launch, no workspace.  I: checked and packed by
 // mp_trajectory_sample_check, its pointers filled in by the caller.  The torques: up to 6 joints the same launch writes them (the
 // fused form: measured 0.75 - 0.82 of the time of the launch without them followed by the inverse-dynamics kernel over the same rows,

@@ -1419,6 +1419,110 @@ int mp_path_blend_cpu_f64(const mp_model* model, const mp_collision* h, const do
 
 }  // extern "C"
 
+// ---- Cartesian straight-line paths over the sphere model (mp_cartesian.h)
+int mp_cartesian_path_check(const char* fn, int n, int64_t B, const double* lo, const double* hi, int64_t grid, int task, double eomg,
+                            double ev, double damping, int max_iters, double max_joint_step, double margin, double tol, int max_steps,
+                            MpCartParams* out) {
+  if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
+  REQUIRE(task == MP_CP_FULL || task == MP_CP_POSITION, "%s: task %d is neither MP_TASK_FULL (0) nor MP_TASK_POSITION (1)", fn, task);
+  const int rows = task == MP_CP_FULL ? 6 : 3;
+  if (n < rows)
+    return mp_fail(MP_ERR_UNSUPPORTED, "%s: a task of %d rows needs at least %d joints (this model has %d)", fn, rows, rows, n);
+  REQUIRE(B >= 0, "%s: negative problem count", fn);
+  REQUIRE(grid >= 2 && grid <= MP_CP_MAX_GRID, "%s: %lld grid points, outside 2..65536", fn, (long long)grid);
+  REQUIRE(B == 0 || grid <= ((int64_t)1 << 56) / B / n, "%s: %lld problems of %lld grid points are not addressable", fn, (long long)B,
+          (long long)grid);
+  REQUIRE(lo && hi, "%s: null joint box", fn);
+  MpCartParams P;
+  std::memset(&P, 0, sizeof P);
+  for (int j = 0; j < n; ++j) {
+    REQUIRE(std::isfinite(lo[j]) && std::isfinite(hi[j]) && lo[j] <= hi[j], "%s: joint %d: the box must be finite with lo <= hi", fn, j);
+    P.lo[j] = lo[j];
+    P.hi[j] = hi[j];
+  }
+  REQUIRE(eomg > 0.0 && std::isfinite(eomg) && ev > 0.0 && std::isfinite(ev), "%s: eomg and ev must be positive and finite", fn);
+  REQUIRE(damping > 0.0 && std::isfinite(damping), "%s: damping must be positive and finite", fn);
+  REQUIRE(max_joint_step > 0.0 && std::isfinite(max_joint_step), "%s: max_joint_step must be positive and finite", fn);
+  REQUIRE(max_iters >= 0 && max_iters <= MP_CP_MAX_ITERS, "%s: max_iters %d outside 0..65536", fn, max_iters);
+  P.eomg = eomg; P.ev = ev; P.damping = damping; P.max_joint_step = max_joint_step;
+  P.edge = {margin, tol, max_steps, 0};
+  P.grid = (int)grid; P.task = task; P.max_iters = max_iters;
+  *out = P;
+  return MP_OK;
+}
+
+// the twin's instance for a chain of N joints and a task of MR rows; none where the chain is too short (the check has refused it)
+template <int N, int MR, bool FITS = (N >= MR)>
+struct CartesianTwin {
+  template <typename... A> static void run(A&&... a) { mp_cart_problem_cpu<N, MR>(a...); }
+};
+template <int N, int MR>
+struct CartesianTwin<N, MR, false> {
+  template <typename... A> static void run(A&&...) {}
+};
+
+extern "C" {
+
+int64_t mp_cartesian_path_workspace_bytes(int64_t B, int64_t N) {
+  if (B < 0 || N < 2 || N > MP_CP_MAX_GRID || (B > 0 && N > ((int64_t)1 << 56) / B)) {
+    mp_fail(MP_ERR_INVALID, "mp_cartesian_path_workspace_bytes: %lld problems of %lld grid points (N in 2..65536)", (long long)B, (long long)N);
+    return -MP_ERR_INVALID;
+  }
+  return (int64_t)mp_cart_work_bytes((long)B, (long)N);
+}
+
+int mp_cartesian_path_cpu_f64(const mp_model* model, const mp_collision* h, const double* q_start, const double* T_goal, int64_t B,
+                              const double* lo, const double* hi, int64_t N_grid, int task, double eomg, double ev, double damping,
+                              int max_iters, double max_joint_step, double margin, double tol, int max_steps, int32_t* status,
+                              int32_t* reached, int32_t* span, double* t, double* clearance, double* deviation_pos,
+                              double* deviation_rot, double* pose_error, int32_t* iterations, int32_t* evaluations, double* q, double* dq,
+                              double* ddq, int32_t* span_status, double* span_clearance, int nthreads) {
+  const char* fn = "mp_cartesian_path_cpu_f64";
+  if (int rc = col_twin_enter(fn, model, h)) return rc;
+  MpCartParams P;
+  if (int rc = mp_cartesian_path_check(fn, model->d.n, B, lo, hi, N_grid, task, eomg, ev, damping, max_iters, max_joint_step, margin, tol,
+                                       max_steps, &P))
+    return rc;
+  if (B == 0) return MP_OK;
+  REQUIRE(q_start && T_goal, "%s: null pointer", fn);
+  REQUIRE(status || reached || span || t || clearance || deviation_pos || deviation_rot || pose_error || iterations || evaluations || q ||
+              dq || ddq || span_status || span_clearance,
+          "%s: at least one output is required", fn);
+  const MpModel<double>& M = model->d;
+  MpColWorld hdr;
+  const MpColTablesHost tb = col_host_tables(h, hdr);
+  const MpCartOut O = {status, reached, span, t, clearance, deviation_pos, deviation_rot, pose_error, iterations, evaluations, span_status,
+                       span_clearance};
+  MP_CPU_DISPATCH(M.n, {
+    parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
+      // One problem at a time: its workspace and the grid arrays the caller did not ask for are the thread's own, addressed as
+      // problem 0 of a batch of one - so are the outputs, through pointers moved to the problem.
+      const size_t rows = (size_t)P.grid * N;
+      std::vector<char> work(mp_cart_work_bytes(1, P.grid) + 16);
+      std::vector<double> own_q(q ? 0 : rows), own_dq(dq ? 0 : rows), own_ddq(ddq ? 0 : rows);
+      void* base = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(work.data()) + 15) & ~(uintptr_t)15);
+      const MpCartWork W = mp_cart_work(base, 1, P.grid);
+      for (int64_t b = b0; b < b1; ++b) {
+        const int64_t e = b * (P.grid - 1);
+        const MpCartOut Ob = {O.status ? O.status + b : nullptr, O.reached ? O.reached + b : nullptr, O.span ? O.span + b : nullptr,
+                              O.t ? O.t + b : nullptr, O.clearance ? O.clearance + b : nullptr,
+                              O.deviation_pos ? O.deviation_pos + b : nullptr, O.deviation_rot ? O.deviation_rot + b : nullptr,
+                              O.pose_error ? O.pose_error + b : nullptr, O.iterations ? O.iterations + b : nullptr,
+                              O.evaluations ? O.evaluations + b : nullptr, O.span_status ? O.span_status + e : nullptr,
+                              O.span_clearance ? O.span_clearance + e : nullptr};
+        double* qb = q ? q + b * rows : own_q.data();
+        double* dqb = dq ? dq + b * rows : own_dq.data();
+        double* ddqb = ddq ? ddq + b * rows : own_ddq.data();
+        if (P.task == MP_CP_FULL) CartesianTwin<N, 6>::run(M, tb, P, q_start + b * N, T_goal + 16 * b, 0L, W, qb, dqb, ddqb, Ob);
+        else CartesianTwin<N, 3>::run(M, tb, P, q_start + b * N, T_goal + 16 * b, 0L, W, qb, dqb, ddqb, Ob);
+      }
+    });
+  })
+  return MP_OK;
+}
+
+}  // extern "C"
+
 // ---- fixed-rate sampling of timed paths (mp_sample.h)
 int mp_trajectory_sample_check(const char* fn, int64_t B, int64_t grid, int64_t w_in, double dt, int64_t M, int n, int grid_given,
                                int curve_given, MpSampleIn* out) {

@@ -17,6 +17,7 @@
 #include "mp_goal.h"
 #include "mp_blend.h"
 #include "mp_sample.h"
+#include "mp_cartesian.h"
 #include "mp_ik.h"
 #include "mp_toppra.h"
 #include "mp_model.h"
@@ -144,6 +145,11 @@ int mp_goal_ik_check(const char* fn, int n, const double* lo, const double* hi, 
 // (mp_cpu.cpp)
 int mp_path_blend_check(const char* fn, int64_t w_in, int64_t grid, double blend, int max_halvings, double margin, double tol,
                         int max_steps, MpBlendParams* out);
+// the Cartesian path's parameters (the edge check's among them), packed into `out`; 0, MP_ERR_UNSUPPORTED for a chain with fewer
+// joints than the task has rows, or MP_ERR_INVALID, with the message set (mp_cpu.cpp)
+int mp_cartesian_path_check(const char* fn, int n, int64_t B, const double* lo, const double* hi, int64_t grid, int task, double eomg,
+                            double ev, double damping, int max_iters, double max_joint_step, double margin, double tol, int max_steps,
+                            MpCartParams* out);
 // the trajectory sampler's arguments, packed into `out` (the pointers are the caller's to fill in): the source is chosen by which group of
 // pointers is given - grid_given of the 3 grid arrays, curve_given of the 6 blend tables; 0, or MP_ERR_INVALID with the message set
 // (mp_cpu.cpp)

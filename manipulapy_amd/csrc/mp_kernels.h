@@ -229,6 +229,16 @@ hipError_t mpk_path_blend(hipStream_t s, const MpModel<double>& M, const MpColDe
 hipError_t mpk_path_blend_sample(hipStream_t s, int n, long problems, const MpBlendParams& P, const int* status, const int* count,
                                  const double* points, const double* cut, const double* knot, const double* length, double* q, double* dq,
                                  double* ddq);
+// Cartesian straight-line paths (csrc/mp_cartesian.h): k_cart_track, one lane a problem; k_cart_span, the work queue over problems x
+// (P.grid - 1) spans, one lane a span (its plan from mpk_cart_plan: the instance depends on the task's rows too); k_cart_reduce, one
+// lane a problem.  W: the call's workspace (mp_cart_work); q, dq, ddq are required, the outputs of O may be null.
+struct MpCartParams;
+struct MpCartWork;
+struct MpCartOut;
+hipError_t mpk_cart_plan(int n, int task, int S, int compute_units, MpQueuePlan* plan);
+hipError_t mpk_cartesian_path(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const MpCartParams& P, const double* q_start,
+                              const double* T_goal, long problems, const MpCartWork& W, double* q, double* dq, double* ddq,
+                              const MpCartOut& O, long blocks, unsigned lds);
 // fixed-rate sampling of timed paths (csrc/mp_sample.h): one lane a (path, sample) row over I.B x I.M rows, the tiles of 64 rows
 // spread over at most `max_blocks` blocks (0: one block a tile).  curve: the geometry is the blend's tables, else the grid arrays.
 struct MpSampleIn;

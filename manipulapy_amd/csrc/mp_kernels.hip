@@ -27,6 +27,7 @@
 #include "mp_shortcut.h"
 #include "mp_goal.h"
 #include "mp_blend.h"
+#include "mp_cartesian.h"
 #include "mp_sample.h"
 
 namespace {
@@ -824,6 +825,75 @@ __global__ __launch_bounds__(64) void k_path_blend_sample(long problems, int gri
   if (q != nullptr) mp_wave_store_auto<double, N>(q, row0, lane, nvalid, x, lds);
   if (dq != nullptr) mp_wave_store_auto<double, N>(dq, row0, lane, nvalid, dx, lds);
   if (ddq != nullptr) mp_wave_store_auto<double, N>(ddq, row0, lane, nvalid, ddx, lds);
+}
+
+// ------------------------------------------------------- Cartesian straight-line paths, proven free (float64, mp_cartesian.h)
+// Tracking: one lane per problem, sequential over its grid, a plain grid and no LDS - a problem's state (q, dq, the line's V and start
+// pose) is in registers, the targets are recomputed from s.  A lane stores its own rows as it accepts them (RunIO-style plain per-lane
+// stores, as k_goal_ik stores its q) and its head into the workspace.
+template <int N, int MR>
+__global__ __launch_bounds__(64) void k_cart_track(const MpModel<double> M, const MpCartParams P, const double* __restrict__ q_start,
+                                                   const double* __restrict__ T_goal, long problems, const MpCartWork W,
+                                                   double* __restrict__ q, double* __restrict__ dq, double* __restrict__ ddq) {
+  const long b = (long)blockIdx.x * 64 + (long)threadIdx.x;
+  if (b >= problems) return;
+  const long at = b * (long)P.grid * N;
+  MpCartHead H;
+  mp_cart_track<N, MR>(M, P, q_start + b * N, T_goal + 16 * b, q + at, dq + at, ddq + at, H);
+  mp_cart_head_store(W, b, H);
+}
+
+// The spans: one wave per block and the work queue of k_collision_edges over problems x (grid - 1) spans, ONE LANE PER SPAN - the
+// spans of a problem are independent once its rows stand, so they spread over the lanes instead of being walked by the problem's
+// own.  A lane without a span takes the next index from the device counter; the span of a problem that was not tracked to its end is
+// recorded SKIPPED at once; otherwise mp_cart_span_begin (bounds, midpoint deviation) and then one collision evaluation a trip.  The
+// span's two grid rows are re-read from memory every trip (mp_ts_hermite reads them in place): the state in registers is u, the
+// clearance and two counters.  Dynamic LDS: the park and the speed bounds (mp_col_queue_lanes).  No wave-wide step: a lane leaves when
+// the queue is dry.  The loop ends because the counter only grows and every span ends within max_steps trips.
+template <int N, int MR>
+__global__ __launch_bounds__(64) void k_cart_span(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
+                                                  const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
+                                                  const MpCartParams P, const double* __restrict__ T_goal, long problems,
+                                                  const MpCartWork W, const double* __restrict__ q, const double* __restrict__ dq,
+                                                  const double* __restrict__ ddq, unsigned long long* __restrict__ next) {
+  extern __shared__ __attribute__((aligned(16))) double mp_cart_lds[];
+  const int lane = (int)threadIdx.x;
+  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  MpColQueueLanes Q = mp_col_queue_lanes(mp_cart_lds, lane, tb.sph->S);
+  const long per = (long)(P.grid - 1), spans = problems * per;
+  const double nm1 = (double)(P.grid - 1);
+  MpCartSpan S;
+  bool have = false;
+  long e = 0, r = 0;
+  for (;;) {
+    if (!have) {
+      e = (long)atomicAdd(next, 1ull);
+      if (e >= spans) break;
+      const long b = e / per;
+      const int i = (int)(e - b * per);
+      if (W.track[b] != MP_CP_DONE) {
+        mp_cart_span_skip(W, e);
+        continue;
+      }
+      const long at = b * (long)P.grid * N;
+      r = at + (long)i * N;
+      mp_cart_span_begin<N, MR>(M, tb.sph, q + r, dq + r, ddq + r, q + at, T_goal + 16 * b, nm1, ((double)i + 0.5) / nm1, S, Q.L);
+      have = true;
+    }
+    if (const int done = mp_cart_span_iterate<N>(M, tb, P.edge, q + r, dq + r, ddq + r, nm1, S, Q.park, Q.L)) {
+      S.status = done - 1;
+      mp_cart_span_store(W, e, S);
+      have = false;
+    }
+  }
+}
+
+// The reduction: one lane per problem walks its spans' records in order (mp_cart_reduce) - what a problem reports is a function of
+// the records, whichever lanes wrote them.
+__global__ __launch_bounds__(64) void k_cart_reduce(long problems, int grid, const MpCartWork W, const MpCartOut O) {
+  const long b = (long)blockIdx.x * 64 + (long)threadIdx.x;
+  if (b >= problems) return;
+  mp_cart_reduce(W, b, grid, O);
 }
 
 // ------------------------------------------------------- fixed-rate sampling of timed paths (float64, mp_sample.h)
@@ -1785,6 +1855,49 @@ hipError_t mpk_path_blend_sample(hipStream_t s, int n, long problems, const MpBl
   if (problems <= 0) return hipSuccess;
   MP_DISPATCH_N(n, return launch(k_path_blend_sample<N>, mp_grid(problems * P.grid, kWave), kWave, 0, s, problems, P.grid, P.w_in, status,
                                  count, points, cut, knot, length, q, dq, ddq))
+}
+
+// Cartesian paths: the joint count and the task's rows bound to constants - POSITION (3 rows) from 3 joints, FULL (6 rows) from 6.
+// The body is written once, as a generic lambda over the two constants.
+template <int V> struct MpConst { static constexpr int value = V; };
+template <typename F>
+static hipError_t cart_dispatch(int n, int task, F f) {
+  const bool pos = task == MP_CP_POSITION;
+  switch (n) {
+    case 3: return pos ? f(MpConst<3>{}, MpConst<3>{}) : hipErrorInvalidValue;
+    case 4: return pos ? f(MpConst<4>{}, MpConst<3>{}) : hipErrorInvalidValue;
+    case 5: return pos ? f(MpConst<5>{}, MpConst<3>{}) : hipErrorInvalidValue;
+    case 6: return pos ? f(MpConst<6>{}, MpConst<3>{}) : f(MpConst<6>{}, MpConst<6>{});
+    case 7: return pos ? f(MpConst<7>{}, MpConst<3>{}) : f(MpConst<7>{}, MpConst<6>{});
+    case 8: return pos ? f(MpConst<8>{}, MpConst<3>{}) : f(MpConst<8>{}, MpConst<6>{});
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t mpk_cart_plan(int n, int task, int S, int compute_units, MpQueuePlan* plan) {
+  if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
+  return cart_dispatch(n, task, [&](auto cn, auto cm) {
+    return queue_plan(&k_cart_span<decltype(cn)::value, decltype(cm)::value>, decltype(cn)::value, S, compute_units, plan);
+  });
+}
+
+// Tracking, the spans on the work queue (`blocks` and `lds` from mpk_cart_plan, the queue head zeroed on the stream first), the
+// reduction: three launches on one stream, no runtime query.
+hipError_t mpk_cartesian_path(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const MpCartParams& P, const double* q_start,
+                              const double* T_goal, long problems, const MpCartWork& W, double* q, double* dq, double* ddq,
+                              const MpCartOut& O, long blocks, unsigned lds) {
+  if (problems <= 0) return hipSuccess;
+  hipError_t e = queue_reset(s, D, blocks);
+  if (e != hipSuccess) return e;
+  e = cart_dispatch(M.n, P.task, [&](auto cn, auto cm) {
+    constexpr int N = decltype(cn)::value, MR = decltype(cm)::value;
+    const hipError_t t = launch(k_cart_track<N, MR>, mp_grid(problems, kWave), kWave, 0, s, M, P, q_start, T_goal, problems, W, q, dq, ddq);
+    if (t != hipSuccess) return t;
+    return launch(k_cart_span<N, MR>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, P, T_goal, problems, W, q, dq, ddq,
+                  D.counter);
+  });
+  if (e != hipSuccess) return e;
+  return launch(k_cart_reduce, mp_grid(problems, kWave), kWave, 0, s, problems, P.grid, W, O);
 }
 
 // `ftip`: the call's wrench is not zero.  The grid: the tiles of 64 rows, clamped to what a grid holds and to the caller's cap - the

@@ -711,6 +711,72 @@ class OptimizedTrajectoryPlanning:
                                                          velocity_limits=velocity_limits, g=g, Ftip=Ftip)
         return both
 
+    def batch_cartesian_path(self, q_start, T_goal, collision_model, N: int, margin: float = 0.0, tol: float = 1e-3, *,
+                             task: str = "full", eomg: float = 1e-6, ev: float = 1e-6, damping: float = 0.01, max_iters: int = 20,
+                             max_joint_step: float = 0.5, max_steps: int = 64, finite_limit: float = 2 * np.pi) -> Dict[str, np.ndarray]:
+        """Straight tool lines from B start configurations q_start (B, n) to B poses T_goal (B, 4, 4) under a
+        collision.SphereCollisionModel (SphereCollisionModel.cartesian_paths), all B problems in one call.  The box is this planner's
+        joint limits, clipped as `batch_plan_path` clips its sampling box.  {"status" (0 done, 1 stalled, 2 singular, 3 limit, 4
+        jump, 5 blocked, 6 undecided, -1 invalid), "reached", "span", "t", "clearance", "deviation_pos", "deviation_rot",
+        "pose_error", "iterations", "evaluations", "q", "dq", "ddq" (B, N, n), "span_status", "span_clearance" (B, N - 1)}: "q",
+        "dq", "ddq" of a done row go straight into `batch_time_optimal_parameterization` and `batch_sample_time_optimal(path=...)`,
+        whose samples lie on the curve that was proven free."""
+        q0, Tg = np.asarray(q_start, dtype=np.float64), np.asarray(T_goal, dtype=np.float64)
+        n = collision_model.n
+        if q0.ndim != 2 or q0.shape[1] != n or Tg.shape != (q0.shape[0], 4, 4):
+            raise ValueError(f"q_start must be (B, {n}) and T_goal (B, 4, 4); got {q0.shape} and {Tg.shape}")
+        lo, hi = self._planning_box(finite_limit)
+        return self._dispatch("planning.cartesian_paths", collision_model, np.ascontiguousarray(q0),
+                              np.ascontiguousarray(Tg.reshape(-1, 16)), lo, hi, N, margin, tol, task=task, eomg=eomg, ev=ev,
+                              damping=damping, max_iters=max_iters, max_joint_step=max_joint_step, max_steps=max_steps)
+
+    def batch_time_optimal_cartesian_path(self, q_start, T_goal, collision_model, N: int, velocity_limits, torque_limits=None,
+                                          acceleration_limits=None, margin: float = 0.0, tol: float = 1e-3, *, task: str = "full",
+                                          eomg: float = 1e-6, ev: float = 1e-6, damping: float = 0.01, max_iters: int = 20,
+                                          max_joint_step: float = 0.5, max_steps: int = 64, sd_start=0.0, sd_end=0.0, g=None, Ftip=None,
+                                          finite_limit: float = 2 * np.pi) -> Dict[str, Dict[str, np.ndarray]]:
+        """`batch_cartesian_path`, then `batch_time_optimal_parameterization` of the lines it made: {"line": its dict, "timing": the
+        parameterisation's dict over all B rows}.  Only the rows whose line status is 0 (done) are timed; every other row keeps its
+        line status and comes back with NaN in every real timing output and -1 in the timing status, as `batch_time_optimal_path`
+        returns the rows without a curve.  sd_start / sd_end: scalars or (B,).  N >= 3 (the parameterisation's grid)."""
+        ln = self.batch_cartesian_path(q_start, T_goal, collision_model, N, margin, tol, task=task, eomg=eomg, ev=ev, damping=damping,
+                                       max_iters=max_iters, max_joint_step=max_joint_step, max_steps=max_steps,
+                                       finite_limit=finite_limit)
+        B = ln["status"].shape[0]
+        rows = np.flatnonzero(ln["status"] == 0)
+        pick = lambda v: v if np.ndim(v) == 0 else np.asarray(v, dtype=np.float64)[rows]  # noqa: E731
+        n, G = ln["q"].shape[2], ln["q"].shape[1]
+        shapes = {"sd2": (G,), "sdd": (G,), "time": (G,), "duration": (), "velocities": (G, n), "accelerations": (G, n),
+                  "torques": (G, n), "controllable": (G, 2)}
+        timing = {k: np.full((B,) + shape, np.nan) for k, shape in shapes.items()}
+        timing["status"] = np.full(B, -1, dtype=np.int32)
+        if len(rows):
+            part = self.batch_time_optimal_parameterization(ln["q"][rows], ln["dq"][rows], ln["ddq"][rows], velocity_limits,
+                                                            torque_limits, acceleration_limits, pick(sd_start), pick(sd_end), g, Ftip)
+            for k, v in part.items():
+                timing[k][rows] = v
+        return {"line": ln, "timing": timing}
+
+    def batch_time_optimal_cartesian_trajectory(self, q_start, T_goal, collision_model, N: int, dt: float, velocity_limits,
+                                                torque_limits=None, acceleration_limits=None, margin: float = 0.0, tol: float = 1e-3, *,
+                                                task: str = "full", eomg: float = 1e-6, ev: float = 1e-6, damping: float = 0.01,
+                                                max_iters: int = 20, max_joint_step: float = 0.5, max_steps: int = 64,
+                                                max_samples: Optional[int] = None, g=None, Ftip=None,
+                                                finite_limit: float = 2 * np.pi) -> Dict[str, Dict[str, np.ndarray]]:
+        """`batch_time_optimal_cartesian_path` (line, then time from rest to rest), then `batch_sample_time_optimal` of its result at
+        the period dt on the grid rows themselves (path=(q, dq, ddq)): {"line", "timing", "samples"}, the three dicts over all B
+        rows.  The samples lie on the quintic Hermite interpolant whose spans the line proved free.  A row that is not done keeps
+        its line status and comes back untimed (3) with NaN samples."""
+        both = self.batch_time_optimal_cartesian_path(q_start, T_goal, collision_model, N, velocity_limits, torque_limits,
+                                                      acceleration_limits, margin, tol, task=task, eomg=eomg, ev=ev, damping=damping,
+                                                      max_iters=max_iters, max_joint_step=max_joint_step, max_steps=max_steps, g=g,
+                                                      Ftip=Ftip, finite_limit=finite_limit)
+        ln = both["line"]
+        # (a row that is not done has NaN timing, which the sampler screens - untimed - before it looks at the grid rows)
+        both["samples"] = self.batch_sample_time_optimal(both["timing"], dt, path=(ln["q"], ln["dq"], ln["ddq"]), max_samples=max_samples,
+                                                         velocity_limits=velocity_limits, g=g, Ftip=Ftip)
+        return both
+
     def _planning_box(self, finite_limit: float):
         """This planner's joint limits as a finite box: an open or non-finite limit clipped to +-`finite_limit` (batch_plan_path's rule)."""
         lim = np.nan_to_num(np.asarray(self.joint_limits, dtype=np.float64), nan=0.0, posinf=finite_limit, neginf=-finite_limit)

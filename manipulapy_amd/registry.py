@@ -327,6 +327,10 @@ def _launch_path_shortcut_cpu(cm, waypoints, count, margin, tol, **kw):
     return _hip.cpu_path_shortcut(cm.model, cm.handle, waypoints, count, margin, tol, **kw)
 
 
+def _launch_cartesian_path_cpu(cm, q_start, T_goal, lo, hi, N, margin, tol, **kw):
+    return _hip.cpu_cartesian_path(cm.model, cm.handle, q_start, T_goal, lo, hi, N, margin, tol, **kw)
+
+
 def _launch_path_blend_cpu(cm, waypoints, count, N, margin, tol, **kw):
     return _hip.cpu_path_blend(cm.model, cm.handle, waypoints, count, N, margin, tol, **kw)
 
@@ -526,6 +530,12 @@ def _launch_path_blend_gpu(cm, waypoints, count, N, margin, tol, **kw):
     return ctx.path_blend_arrays(cm.model, cm.handle, waypoints, count, N, margin, tol, **kw)
 
 
+def _launch_cartesian_path_gpu(cm, q_start, T_goal, lo, hi, N, margin, tol, **kw):
+    ctx = get_context()
+    cm.sync_world(ctx)
+    return ctx.cartesian_path_arrays(cm.model, cm.handle, q_start, T_goal, lo, hi, N, margin, tol, **kw)
+
+
 def _launch_trajectory_sample_gpu(model, t, x, dt, M, **kw):
     return get_context().trajectory_sample_arrays(model, t, x, dt, M, **kw)
 
@@ -684,6 +694,9 @@ def _build_kernel_registry() -> KernelRegistry:
         # C2 corner blending of waypoint paths, every blend proven by the edge check, sampled for the time-optimal parameterisation
         # (csrc/mp_blend.h); the name sorts after the pinned head of the name list
         ("planning.blend_paths", "mp_path_blend_host_f64", _launch_path_blend_gpu, _launch_path_blend_cpu),
+        # Cartesian straight lines tracked in joint space, every span of the curve the sampler executes proven by the edge check
+        # (csrc/mp_cartesian.h); the name sorts after the pinned head of the name list
+        ("planning.cartesian_paths", "mp_cartesian_path_host_f64", _launch_cartesian_path_gpu, _launch_cartesian_path_cpu),
         # fixed-rate sampling of the parameterisation's result: s, sd, sdd, q, qd, qdd and the row's own inverse dynamics at t = k dt
         # (csrc/mp_sample.h; first argument: a HipModel); the name sorts after the pinned head of the name list
         ("planning.time_optimal_samples", "mp_trajectory_sample_host_f64", _launch_trajectory_sample_gpu, _launch_trajectory_sample_cpu),
