@@ -1112,9 +1112,10 @@ int mp_path_blend_cpu_f64(const mp_model* model, const mp_collision* h, const do
  *   A path's result depends on its own content only.  No output may overlap an input.
  * mp_trajectory_sample_f64: device arrays, 16-byte aligned.  One launch on the compute stream, one lane a row, a path's screen shared
  *   by the lanes of a wave; max_blocks > 0 caps the grid.  Models of 7 and 8 joints, where the fused recursion was measured slower:
- *   when positions, velocities, accelerations and torques are all given, the torques come from a second launch, the inverse-dynamics
- *   kernel over the rows just written (same contract: the inverse dynamics of the row).  Asynchronous, allocates nothing, may be
- *   captured into a launch graph.
+ *   the torques come from a second launch, the inverse-dynamics kernel over the rows just written (same contract: the inverse
+ *   dynamics of the row).  Asynchronous; allocates nothing and may be captured into a launch graph - except a call for the torques of
+ *   a 7- or 8-joint model without all of positions, velocities and accelerations, which takes the missing rows from the context's
+ *   pool for the length of the call and is refused inside a capture.
  *   mp_trajectory_sample_host_f64: host arrays, device memory from the context's pool.  mp_trajectory_sample_cpu_f64: the kernel's
  *   per-path and per-row code on the host, no context. */
 #define MP_SAMPLE_OK 0

@@ -806,7 +806,8 @@ class HipContext:
         OR the blend's tables d_blend_status / d_blend_count (paths) int32, d_points (paths, w_in, n), d_cut / d_knot (paths, w_in),
         d_length (paths).  Outputs status / count / needed (paths) int32, s / sd / sdd (paths, M), positions / velocities /
         accelerations / torques (paths, M, n), each may be None (at least one given).  `max_blocks` > 0 caps the grid.  Asynchronous,
-        allocates nothing, capturable."""
+        allocates nothing, capturable - except torques of a 7- or 8-joint model without all of positions, velocities and
+        accelerations: the missing rows come from the context's pool and the call is refused inside a capture."""
         _check(self.lib.mp_trajectory_sample_f64(self.handle, model.handle, _p(d_t), _p(d_x), int(paths), int(N), _p(d_q), _p(d_dq), _p(d_ddq),
                                                  _p(d_blend_status), _p(d_blend_count), _p(d_points), _p(d_cut), _p(d_knot), _p(d_length),
                                                  int(w_in), float(dt), int(M), _dptr(_vec_or_none(g, 3, "g")),

@@ -3519,19 +3519,15 @@ int mp_cartesian_path_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision*
 
 }  // extern "C"
 
-// ---- fixed-rate sampling of timed paths (mp_sample.h): one launch, no workspace.  I: checked and packed by
-// mp_trajectory_sample_check, its pointers filled in by the caller.  The torques: up to 6 joints the same launch writes them (the
-// fused form: measured 0.75 - 0.82 of the time of the launch without them followed by the inverse-dynamics kernel over the same rows,
-// xArm6).  From 7 joints on the fused recursion needs more than 256 registers and was measured 1.6 - 1.9 times SLOWER than that
-// split form (Panda, 8 joints), so the entry runs the split form - k_traj_sample without torques, then k_id over the rows
-// it wrote - whenever the caller gave positions, velocities and accelerations for it to read; without one of them there is nowhere
-// to put the rows (the entry allocates nothing) and the fused kernel runs.  MANIPULAPY_HIP_SAMPLE_TORQUES=fused (read at every
-// call, so a captured graph keeps the variant it was captured with) selects the fused kernel throughout; it exists for
-// tools/sample_bench.py to time the loser.
-static bool sample_force_fused() {
-  const char* e = getenv("MANIPULAPY_HIP_SAMPLE_TORQUES");
-  return e && std::strcmp(e, "fused") == 0;
-}
+// ---- fixed-rate sampling of timed paths (mp_sample.h).  I: checked and packed by mp_trajectory_sample_check, its pointers
+// filled in by the caller.  The torques: up to 6 joints the same launch writes them (the fused form: measured 0.75 - 0.82 of the time
+// of the launch without them followed by the inverse-dynamics kernel over the same rows, xArm6).  From 7 joints on the entry ALWAYS
+// runs the split form - k_traj_sample without torques, then k_id over the rows it wrote - and never dispatches a torque instance of
+// k_traj_sample: those take more than 256 registers, were measured 1.6 - 1.9 times slower than the split form (Panda, 8 joints;
+// DESIGN 4.15), and k_traj_sample<8, grid, torques with a wrench> has written behind its output arrays (the cause is not
+// known).  Where the caller gave no positions, velocities or accelerations for the rows, the missing arrays come from the context's
+// pool for the length of the call (its reuse is ordered on the compute stream) - so such a call cannot be captured into a launch
+// graph, and mp_malloc says so.
 static int trajectory_sample_impl(const char* fn, mp_ctx* ctx, const mp_model* model, const MpSampleIn& I, const double* g, const double* Ftip,
                                   int max_blocks, const MpSampleOut& O) {
   REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
@@ -3547,11 +3543,22 @@ static int trajectory_sample_impl(const char* fn, mp_ctx* ctx, const mp_model* m
   MpCall<double> c;
   make_call<double>(model, g, Ftip, &c);
   PROFILE_SCOPE(ctx, fn);
-  const bool split = O.tau && model->d.n >= 7 && O.pos && O.vel && O.acc && !sample_force_fused();
+  const bool split = O.tau && model->d.n >= 7;
   MpSampleOut W = O;
-  if (split) W.tau = nullptr;
+  Scratch sc(ctx);
+  if (split) {
+    W.tau = nullptr;
+    const size_t bytes = (size_t)(I.B * I.M) * (size_t)model->d.n * sizeof(double);
+    for (double** rows : {&W.pos, &W.vel, &W.acc}) {
+      void* p = nullptr;
+      if (*rows == nullptr) {
+        if (int rc = sc.get(bytes, &p)) return rc;
+        *rows = static_cast<double*>(p);
+      }
+    }
+  }
   HIP_TRY(mpk_traj_sample(ctx->compute, model->d, c, any_nonzero(Ftip), I.points != nullptr, I, W, (long)max_blocks));
-  if (split) HIP_TRY(mpk_id<double>(ctx->compute, model->d, c, any_nonzero(Ftip), O.pos, O.vel, O.acc, O.tau, (long)(I.B * I.M)));
+  if (split) HIP_TRY(mpk_id<double>(ctx->compute, model->d, c, any_nonzero(Ftip), W.pos, W.vel, W.acc, O.tau, (long)(I.B * I.M)));
   return MP_OK;
 }
 

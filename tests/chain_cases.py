@@ -565,3 +565,153 @@ def _shortcut_twin(n, tight, over, seed, world_seed):
 def shortcut_twin(n, tight=False, seed=None, world_seed=None, **over):
     """The CPU twin on the whole case (computed once and shared: treat as read-only)."""
     return _shortcut_twin(n, tight, _frozen(over), seed, world_seed)
+
+
+# ------------------------------------------------------------------------------------------------ corner blending
+# blend_cases' oracle, rule and settings (blend 0.5, max_halvings 6, max_steps 64, N = 33, the runs "base" at margin 0.02 and "raised"
+# at 0.03) on plan_model(n).  The inputs: the 73 rows of shortcut_twin(n), then the 67 rows of plan_twin(n) - the planner's raw paths
+# carry more corners, and corners that need more halvings, than the shortcutter leaves; rows without a path come as they are (count 0,
+# NaN rows) and must come back SKIPPED - then five planted rows, made of the longest input path without a repeated waypoint:
+#     BLEND_PLANTED_REVERSAL   a, b, a with a that path's first waypoint and b = a moved by 0.25 in joint 0 alone: REVERSAL at corner 1
+#     BLEND_PLANTED_POINT      count 3, all rows equal: POINT
+#     BLEND_PLANTED_DUP        that path's rows 0 1 1 2 2 2 3 4 ..: the compaction gives the path back.  On n = 1 the longest path has two
+#                              waypoints (every path of a one-joint planner has); a row index past the end stands for the last waypoint,
+#                              so the row is p0 p1 p1 p1 p1 with count 5 and comes back STRAIGHT
+#     BLEND_PLANTED_NAN        that path with a NaN in its second waypoint: INVALID
+#     BLEND_PLANTED_COLLINEAR  a, (a + b) / 2, b with a -> b the first input row of two distinct waypoints: a corner whose two unit
+#                              vectors are equal (u_in . u_out = 1), DONE with count 3, the full cut and no halving.  On n = 1 it is the
+#                              only DONE row: in one dimension a corner is exactly straight or an exact reversal
+# 145 problems: two waves and 17 lanes.
+# Measured (float64 oracle, base / raised run; identical discrete outputs in longdouble and in the twin, no problem below blend_cases.GAP)
+# - the table is printed again by test_chain_cases_host.py::test_blend_case_conditions:
+#     n  done     straight  skipped  blocked  corners on DONE rows  largest halvings  evaluations max
+#     1  1 / 1    98        42       0 / 0    1 / 1                 0 / 0             1
+#     2  14 / 9   69        58       0 / 5    85 / 50               2 / 9             183 / 289
+#     3  68 / 50  59        14       0 / 18   395 / 269             2 / 9             228 / 364
+#     4  26 / 21  27        88       0 / 5    133 / 110             1 / 10            272 / 366
+#     5  20 / 12  11        110      0 / 8    137 / 72              0 / 9             210 / 188
+#     6  18 / 15  25        98       0 / 3    117 / 93              0 / 7             179 / 242
+#     7  30 / 23  19        92       0 / 7    196 / 122             3 / 7             608 / 384
+#     8  18 / 17  15        108      0 / 1    93 / 86               1 / 8             144 / 242
+# (every chain also has 2 POINT rows, one REVERSAL and one INVALID.)  The oracle's float64-against-longdouble figures stay within
+# twice blend_cases.MEASURED on every chain (at most: cut 5.0e-17, knot and length 3.3e-16, clearance 2.8e-16, q 8.6e-16 on n = 3 and
+# dq 3.9e-14 on n = 5 - both 3 % over their constants -, ddq 8.9e-13), so the module's bounds apply unchanged and no chain has a
+# constant of its own.
+# Planted in a scratch copy of mp_blend_curve_begin: without `e += reach[j - 1]` the twin fails the rule on n = 5, 6, 8; with `e =` in
+# the place of `e +=` (the lever arm not accumulated over two prismatic joints) on n = 5 and 8 only, and on none of blend_cases' robots.
+BLEND_INPUTS = SHORTCUT_PROBLEMS + PLAN_PROBLEMS
+BLEND_PLANTED_REVERSAL, BLEND_PLANTED_POINT, BLEND_PLANTED_DUP, BLEND_PLANTED_NAN, BLEND_PLANTED_COLLINEAR = (
+    BLEND_INPUTS + k for k in range(5))
+BLEND_PROBLEMS = BLEND_INPUTS + 5
+
+
+@functools.lru_cache(maxsize=None)
+def blend_case(n):
+    """{"cm", "model": the oracle's Model, "n", "waypoints" (BLEND_PROBLEMS, W_IN, n), "count" int32, "longest", "straight": the rows the
+    planted ones are made of} by the recipe above (computed once and shared: treat as read-only)."""
+    import blend_cases as bc
+
+    cm, _, model = plan_model(n)
+    short, plan = shortcut_twin(n), plan_twin(n)
+    W = bc.W_IN
+    assert short["waypoints"].shape[1:] == (W, n) and plan["waypoints"].shape[1:] == (W, n)
+    wp = np.concatenate([short["waypoints"], plan["waypoints"]])
+    count = np.concatenate([short["count"], plan["count"]]).astype(np.int32)
+    assert len(wp) == BLEND_INPUTS
+    distinct = np.array([all((wp[b, i] != wp[b, i + 1]).any() for i in range(count[b] - 1)) for b in range(len(wp))])
+    longest = int(np.argmax(np.where(distinct, count, 0)))
+    L = int(count[longest])
+    assert 4 <= L <= W - 3 if n >= 2 else L == 2
+    straight = int(np.flatnonzero((count == 2) & (wp[:, 0] != wp[:, 1]).any(axis=1))[0])
+    planted = np.repeat(wp[longest][None], 5, axis=0)
+    a, b = wp[longest, 0], wp[longest, 0].copy()
+    b[0] += 0.25
+    planted[0, :] = a
+    planted[0, 1] = b
+    planted[1, :] = a
+    planted[2] = wp[longest, np.minimum(np.concatenate([[0, 1, 1, 2, 2, 2], np.arange(3, W - 3)]), L - 1)]
+    planted[3, 1, n // 2] = np.nan
+    a, b = wp[straight, 0], wp[straight, 1]
+    planted[4, :] = b
+    planted[4, 0], planted[4, 1] = a, (a + b) / 2
+    pc = np.array([3, 3, L + 3, L, 3], dtype=np.int32)
+    return {"cm": cm, "model": model, "n": n, "waypoints": np.ascontiguousarray(np.concatenate([wp, planted])),
+            "count": np.concatenate([count, pc]), "longest": longest, "straight": straight}
+
+
+@functools.lru_cache(maxsize=None)
+def blend_oracle(n, run="base", long=False):
+    """blend_cases.blend on the whole case (computed once and shared: treat as read-only)."""
+    import blend_cases as bc
+
+    case = blend_case(n)
+    return bc.blend(case["model"], case["waypoints"], case["count"], N=bc.GRID, margin=bc.RUNS[run], tol=bc.TOL,
+                    dt=np.longdouble if long else np.float64, **bc.params_of())
+
+
+@functools.lru_cache(maxsize=None)
+def blend_twin(n, run="base"):
+    """The CPU twin on the whole case (computed once and shared: treat as read-only)."""
+    import blend_cases as bc
+
+    case = blend_case(n)
+    cm = case["cm"]
+    return _hip.cpu_path_blend(cm.model, cm.handle, case["waypoints"], case["count"], bc.GRID, bc.RUNS[run], bc.TOL, **bc.params_of())
+
+
+# ------------------------------------------------------------------------------------------------ fixed-rate sampling
+# sample_cases' two recipes (grid_case_of, curve_case_of), oracle and rule on chain(n).
+# Grid source: the paths, model and limits of toppra_case(n, B = 4, N) for N = 33 and 3, timed by the TOPP-RA twin with and without
+# acceleration limits (a third of the largest |qdd| of the unlimited N = 33 run), the six planted rows made of path 0.
+# Curve source: the base run of blend_case(n), its DONE / STRAIGHT rows timed with velocity limits 2, acceleration limits 10 and
+# infinite torque limits, near-stops made stops, the four planted timings on DONE rows - on n = 1, where BLEND_PLANTED_COLLINEAR is the
+# only DONE row, on STRAIGHT rows.  dt by sample_cases._pick_dt; every case is sampled at M = the largest `needed` and at M_SMALL.
+# Measured: dt 2^-6 to 2^-2, M 29 to 55; the oracle's float64-against-longdouble figures at most s 1.9e-16, sd 1.7e-16, sdd 1.1e-16,
+# positions 4.2e-15, velocities 4.7e-13 (n = 1, N = 33), accelerations 1.2e-11, torques 1.4e-11 (n = 7, N = 33) - within twice
+# sample_cases.MEASURED, so the module's bounds apply unchanged and no chain has a constant of its own.  Planted in a scratch copy of
+# mp_sample.h: H1 and H4 exchanged in mp_ts_hermite fails the twin on every chain's N = 33 grid cases (at N = 3 make_paths' dq/ds is the
+# same at all three grid points, so the exchange changes nothing); the hold row read one point early fails it on every curve case.
+SAMPLE_GRIDS = tuple((N, acc) for N in (33, 3) for acc in (False, True))
+
+
+def sample_keys(n):
+    """the five cases of a chain: ("curve", n) and ("grid", n, N, acc)"""
+    return (("curve", n),) + tuple(("grid", n, N, acc) for N, acc in SAMPLE_GRIDS)
+
+
+@functools.lru_cache(maxsize=None)
+def sample_grid_case(n, N, acc):
+    import sample_cases as sp
+
+    model, vlim, tlim, paths = toppra_case(n, 4, N)
+    alim = sp.acc_limits_of(*toppra_case(n, 4, 33)) if acc else None
+    return sp.grid_case_of(model, vlim, tlim, paths, alim, f"chain {n} N {N} acc {acc}")
+
+
+@functools.lru_cache(maxsize=None)
+def sample_curve_case(n):
+    import blend_cases as bc
+    import sample_cases as sp
+
+    return sp.curve_case_of(blend_case(n)["cm"], blend_twin(n), f"chain {n} curve", plant_on=bc.STRAIGHT if n == 1 else bc.DONE)
+
+
+def sample_case(key):
+    return sample_curve_case(key[1]) if key[0] == "curve" else sample_grid_case(*key[1:])
+
+
+@functools.lru_cache(maxsize=None)
+def sample_twin(key, small=False):
+    """The CPU twin on a whole case of sample_keys (computed once and shared: treat as read-only)."""
+    import sample_cases as sp
+
+    return sp.twin(sample_case(key), sp.M_SMALL if small else None)
+
+
+@functools.lru_cache(maxsize=None)
+def sample_oracle(key, small=False, long=False):
+    """sample_cases.sample on a whole case of sample_keys (computed once and shared: treat as read-only)."""
+    import sample_cases as sp
+
+    case = sample_case(key)
+    return sp.sample(case, sp.M_SMALL if small else case["M"], long)

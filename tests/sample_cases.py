@@ -27,6 +27,8 @@ grid point inside a tight blend can admit next to no speed: panda has one such r
 dt is chosen from paths that move.
 dt is a power of two, chosen per case so that the longest finite duration needs about 40 rows (28..57).  Every case is sampled at
 M = the largest `needed` (nothing truncated) and at M_SMALL = 12 rows (P_SHORT and P_EXACT fit, the case's own paths do not all).
+grid_case_of and curve_case_of are the two recipes on their ingredients (a model, limits and paths; a collision model and a blend
+result): chain_cases.py runs them on chain(n), n = 1..8.
 
 Conditions (test_sample_host.py::test_case_conditions): every status occurs in the default run of a grid case and in its small
 run; TRUNCATED covers some rows and not all; except on P_EXACT no k dt lies within 1e-9 T of T, so that no discrete output hangs on
@@ -91,13 +93,18 @@ def _robot(name):
     return tc.chain_case(3) if name == "chain3" else tc.robot_case(name)
 
 
-@functools.lru_cache(maxsize=None)
-def _acc_limits(name):
-    model, lim, vlim, tlim = _robot(name)
-    q, dq, ddq = tc.make_paths(lim, GRID_ROBOTS[name], 33)
+def acc_limits_of(model, vlim, tlim, paths):
+    """the acceleration limits of a grid case: a third of the largest |qdd| of the unlimited run on `paths` (the N = 33 ones)"""
+    q, dq, ddq = paths
     free = _hip.cpu_toppra(model, q, dq, ddq, vlim, tlim, None, g=tc.G9)
     assert not free["status"].any()
     return np.maximum(np.abs(free["accelerations"][:, :-1]).max(axis=(0, 1)) / 3.0, 1e-3)
+
+
+@functools.lru_cache(maxsize=None)
+def _acc_limits(name):
+    model, lim, vlim, tlim = _robot(name)
+    return acc_limits_of(model, vlim, tlim, tc.make_paths(lim, GRID_ROBOTS[name], 33))
 
 
 @functools.lru_cache(maxsize=None)
@@ -105,12 +112,17 @@ def make_grid_case(name, N, acc):
     """{"model", "source": "grid", "t", "x" (B, N), "path": (q, dq, ddq) (B, N, n), "dt", "M", "planted": the first planted row, "g"}
     by the recipe of the module's docstring (computed once and shared: treat as read-only)."""
     model, lim, vlim, tlim = _robot(name)
-    P = GRID_ROBOTS[name]
-    q, dq, ddq = tc.make_paths(lim, P, N)
+    return grid_case_of(model, vlim, tlim, tc.make_paths(lim, GRID_ROBOTS[name], N), _acc_limits(name) if acc else None,
+                        f"{name} N {N} acc {acc}")
+
+
+def grid_case_of(model, vlim, tlim, paths, alim, name):
+    """The grid-source recipe on its ingredients: paths = (q, dq, ddq) (P, N, n), left untouched; alim: the acceleration limits or
+    None."""
+    P, N = paths[0].shape[:2]
     pick = lambda a: np.concatenate([a, np.repeat(a[:1], 6, axis=0)])  # noqa: E731
-    q, dq, ddq = pick(q), pick(dq), pick(ddq)
+    q, dq, ddq = (pick(a) for a in paths)
     dq[P + P_UNTIMED, N // 2] = 0.0
-    alim = _acc_limits(name) if acc else None
     timing = _hip.cpu_toppra(model, q, dq, ddq, vlim, tlim, alim, g=tc.G9)
     assert not timing["status"][:P].any() and timing["status"][P + P_UNTIMED] != 0
     t, x = timing["time"].copy(), timing["sd2"].copy()
@@ -126,16 +138,20 @@ def make_grid_case(name, N, acc):
     t[P + P_EXACT], x[P + P_EXACT] = _rescale(t[0], x[0], EXACT_ROWS * dt)
     need = _hip.sample_rows_needed(t[:, -1], dt)
     return {"model": model, "source": "grid", "t": t, "x": x, "path": (q, dq, ddq), "curve": None, "dt": dt, "M": int(need.max()),
-            "planted": P, "g": tc.G9, "name": f"{name} N {N} acc {acc}"}
+            "planted": P, "g": tc.G9, "name": name}
 
 
 @functools.lru_cache(maxsize=None)
 def make_curve_case(name):
     """the same for the curve source: "curve" = the blend twin's tables, "path" None, "planted" = {P_...: row}, and "cm" (the collision
     model) and "blend" (the twin's whole result) for the clearance check"""
-    case, bl = bc.make_blend_case(name), bc.twin_of(name)
-    cm = case["cm"]
-    n, B, N = cm.n, bc.PROBLEMS, bc.GRID
+    return curve_case_of(bc.make_blend_case(name)["cm"], bc.twin_of(name), f"{name} curve")
+
+
+def curve_case_of(cm, bl, name, plant_on=bc.DONE):
+    """The curve-source recipe on its ingredients: bl = the blend twin's whole base-run result under the collision model cm.  The
+    planted timings go on rows of blend status `plant_on` that move: "movers" lists them, the planted ones included."""
+    n, (B, N) = cm.n, bl["q"].shape[:2]
     rows = np.flatnonzero((bl["status"] == bc.DONE) | (bl["status"] == bc.STRAIGHT))
     part = _hip.cpu_toppra(cm.model, bl["q"][rows], bl["dq"][rows], bl["ddq"][rows], np.full(n, 2.0), np.tile([-np.inf, np.inf], (n, 1)),
                            np.full(n, 10.0), g=tc.G9)
@@ -148,7 +164,7 @@ def make_curve_case(name):
         x[b, N // 2 - 1:N // 2 + 1] = 0.0
         t[b, N // 2:] = np.inf
     finite = np.setdiff1d(finite, slow)
-    done = [b for b in finite if bl["status"][b] == bc.DONE]
+    done = [b for b in finite if bl["status"][b] == plant_on]
     assert len(done) >= 8
     dt = _pick_dt(t[finite, -1])
     planted = {P_DECREASING: done[1], P_SHORT: done[2], P_EXACT: done[3], P_STOPS: done[4]}
@@ -163,7 +179,7 @@ def make_curve_case(name):
     need = _hip.sample_rows_needed(t[:, -1], dt)
     curve = {k: bl[k] for k in _hip.SAMPLE_CURVE_TABLES}
     return {"model": cm.model, "source": "curve", "t": t, "x": x, "path": None, "curve": curve, "dt": dt, "M": int(need.max()),
-            "planted": planted, "g": tc.G9, "name": f"{name} curve", "cm": cm, "blend": bl}
+            "planted": planted, "g": tc.G9, "name": name, "cm": cm, "blend": bl, "movers": done}
 
 
 def twin(case, M=None, **kw):

@@ -5,7 +5,9 @@ Each test first re-measures the oracle's own float64-against-longdouble differen
 the family's bound was sized from (as test_oracle_float64_error_is_what_the_bound_was_sized_from does), then applies the family's
 existing rule with its existing bound.  The planner and the shortcutter (chain_cases.plan_case / shortcut_case) are also held to the
 oracle at the limits - max_nodes 4 and 2, max_waypoints 3 and 2, max_iters 0, the tight shortcut run - and their paths to the edge
-checker; the slowest of these tests takes 18 s (the planner's float64 and longdouble oracles on n = 5)."""
+checker; the slowest of these tests takes 18 s (the planner's float64 and longdouble oracles on n = 5).  Corner blending
+(chain_cases.blend_case) and fixed-rate sampling (sample_curve_case / sample_grid_case) add the conditions their cases must meet and
+the same two steps; their 104 tests take under half a minute together."""
 import numpy as np
 import pytest
 
@@ -393,3 +395,201 @@ def test_path_shortcut_twin_matches_the_oracle(chain_planner, n, tight):
     fig = sc.check_against_oracle(twin, ref, f"shortcut n={n} twin", show=False)
     print(f"shortcut n={n}: twin against oracle: " + ", ".join(f"{k} {v:.3g}" for k, v in fig.items()))
     sc.check_sound(chain_planner, case, twin, f"shortcut n={n} twin")
+
+
+# ------------------------------------------------------------------------------------------------ corner blending
+def _blend_own(n, run):
+    """the oracle's float64-against-longdouble difference of every real output, held to twice blend_cases.MEASURED"""
+    import blend_cases as bc
+
+    o, ol = ch.blend_oracle(n, run), ch.blend_oracle(n, run, long=True)
+    own = {k: float(bc.relative_difference(o[k], ol[k]).max()) for k in bc.REAL}
+    for k, v in own.items():
+        assert v <= 2 * bc.MEASURED[k], f"blend n={n} {run}: the oracle's own {k} differs by {v:.3g} (constant {bc.MEASURED[k]:.3g})"
+    return own
+
+
+@pytest.mark.parametrize("n", ch.NS)
+def test_blend_case_conditions(n):
+    """The conditions a chain's blending case must meet, on the float64 and the longdouble oracle (conditions, not measurements)."""
+    import blend_cases as bc
+
+    case = ch.blend_case(n)
+    B, cin = ch.BLEND_PROBLEMS, case["count"]
+    assert len(cin) == B == 145 and case["waypoints"].shape == (B, bc.W_IN, n)
+    planted = np.arange(ch.BLEND_INPUTS, B)
+    for run in bc.RUNS:
+        o, ol = ch.blend_oracle(n, run), ch.blend_oracle(n, run, long=True)
+        own = _blend_own(n, run)
+        st, done = o["status"], o["status"] == bc.DONE
+        mix = {k: int((st == v).sum()) for k, v in (("done", bc.DONE), ("straight", bc.STRAIGHT), ("skipped", bc.SKIPPED), ("point", bc.POINT),
+                                                    ("blocked", bc.BLOCKED), ("reversal", bc.REVERSAL), ("invalid", bc.INVALID))}
+        corners = int((o["count"][done] - 2).sum())
+        print(f"\nblend n={n} {run}: {mix}; {corners} corners on DONE rows; halvings max {o['halvings'].max()}; evaluations max "
+              f"{o['evaluations'].max()}; smallest gap {np.delete(o['gap'], ch.BLEND_PLANTED_REVERSAL).min():.3g} (the planted reversal's "
+              f"is 1e-9 by construction); oracle float64 against longdouble: "
+              + ", ".join(f"{k} {v:.2g}" for k, v in own.items()))
+        for k in bc.DISCRETE:
+            assert np.array_equal(o[k], ol[k]), (n, run, k)
+        assert (o["gap"] >= bc.GAP).all() and (ol["gap"] >= bc.GAP).all(), "the oracle alone excuses nobody"
+        assert o["evaluations"].max() <= 700
+        skipped = cin < 2
+        assert skipped.any() and (st[skipped] == bc.SKIPPED).all() and (st[~skipped] != bc.SKIPPED).all()
+        assert st[ch.BLEND_PLANTED_REVERSAL] == bc.REVERSAL and o["corner"][ch.BLEND_PLANTED_REVERSAL] == 1
+        assert o["evaluations"][ch.BLEND_PLANTED_REVERSAL] == 0
+        assert st[ch.BLEND_PLANTED_POINT] == bc.POINT and st[ch.BLEND_PLANTED_NAN] == bc.INVALID
+        col = ch.BLEND_PLANTED_COLLINEAR
+        assert st[col] == bc.DONE and o["count"][col] == 3 and o["halvings"][col] == 0 and o["cut"][col, 1] > 0
+        assert st[ch.BLEND_PLANTED_DUP] == st[case["longest"]] and o["count"][ch.BLEND_PLANTED_DUP] == o["count"][case["longest"]]
+        if n == 1:      # one joint: a corner is exactly straight or an exact reversal
+            assert np.array_equal(np.flatnonzero(done), [col])
+            assert {bc.STRAIGHT, bc.SKIPPED} <= set(st[:ch.BLEND_INPUTS].tolist()) <= {bc.STRAIGHT, bc.SKIPPED, bc.POINT}
+            assert st[ch.BLEND_PLANTED_DUP] == bc.STRAIGHT
+            continue
+        assert {bc.DONE, bc.STRAIGHT, bc.SKIPPED, bc.POINT, bc.REVERSAL, bc.INVALID} <= set(st.tolist())
+        if run == "base":
+            assert mix["done"] >= 12 and corners >= 75 and st[ch.BLEND_PLANTED_DUP] == bc.DONE
+        else:
+            assert mix["blocked"] >= 1 and o["halvings"].max() >= 7
+    assert planted[-1] == ch.BLEND_PLANTED_COLLINEAR
+
+
+@pytest.mark.parametrize("run", ("base", "raised"))
+@pytest.mark.parametrize("n", ch.NS)
+def test_blend_twin_matches_the_oracle(n, run):
+    """The oracle's own float64-against-longdouble differences against the constants blend_cases' bounds were sized from, the module's
+    rule with its bounds unchanged, then what test_blend_host.py::test_soundness checks without the oracle: the end rows of the grid are
+    the input's end points, every grid configuration of a DONE row clears the planner's margin and every evaluated one of a row without a halving the run's,
+    and the repeated points change nothing."""
+    import blend_cases as bc
+    import manipulapy_amd as mp
+
+    case, ref, got = ch.blend_case(n), ch.blend_oracle(n, run), ch.blend_twin(n, run)
+    _blend_own(n, run)
+    assert set(got) == set(bc.KEYS)
+    fig = bc.check_against_oracle(got, ref, f"blend n={n} {run} twin", show=False)
+    print(f"\nblend n={n} {run}: twin against oracle, share of the bound: "
+          + ", ".join(f"{k} {v / bc.BOUND[k] if bc.BOUND[k] else 0.0:.2g}" for k, v in fig.items()))
+    st, m, wp, cin = got["status"], got["count"], case["waypoints"], case["count"]
+    path = np.isin(st, (bc.DONE, bc.STRAIGHT, bc.POINT))
+    for k in bc.REAL:
+        assert np.isnan(got[k][~path]).all(), k
+    assert (m[~path] == 0).all() and (m[path] >= 1).all() and np.isinf(got["clearance"][st == bc.STRAIGHT]).all()
+    curve = np.flatnonzero((st == bc.DONE) | (st == bc.STRAIGHT))
+    done = np.flatnonzero(st == bc.DONE)
+    assert len(done) and len(curve) > len(done)
+    assert np.array_equal(got["q"][curve, 0], wp[curve, 0]) and np.array_equal(got["q"][curve, -1], wp[curve, cin[curve] - 1])
+    assert not got["ddq"][st == bc.STRAIGHT].any() and not got["ddq"][curve][:, [0, -1]].any()
+    # (the blends are proven at the run's margin; the linear pieces between them are the input's, proven at the planner's - the base one)
+    with mp.use_backend("numpy"):
+        d = case["cm"].distances(got["q"][done])
+    assert (d["dist_world"] > bc.RUNS["base"]).all() and (d["dist_self"] > bc.RUNS["base"]).all()
+    first = done[got["halvings"][done] == 0]     # `clearance` counts failed attempts in; without one, every evaluation cleared the run's margin
+    assert len(first) and got["clearance"][first].min() > bc.RUNS[run] + bc.TOL
+    for k in bc.KEYS:   # the repeated points change nothing
+        assert np.array_equal(got[k][ch.BLEND_PLANTED_DUP], got[k][case["longest"]], equal_nan=True), k
+
+
+# ------------------------------------------------------------------------------------------------ fixed-rate sampling
+SAMPLE_KEYS = tuple(k[:1] + k[2:] for k in ch.sample_keys(0))      # the five cases of a chain, without the chain
+SAMPLE_IDS = [" ".join(str(x) for x in k) for k in SAMPLE_KEYS]
+
+
+def _sample_key(n, key):
+    return key[:1] + (n,) + key[1:]
+
+
+def _sample_own(key, small):
+    """the oracle's float64-against-longdouble difference of every real output, held to twice sample_cases.MEASURED"""
+    import blend_cases as bc
+    import sample_cases as sp
+
+    o, ol = ch.sample_oracle(key, small), ch.sample_oracle(key, small, long=True)
+    for k in sp.DISCRETE:
+        assert np.array_equal(o[k], ol[k]), (key, small, k)
+    own = {k: float(bc.relative_difference(o[k], ol[k]).max()) for k in sp.REAL}
+    for k, v in own.items():
+        assert v <= 2 * sp.MEASURED[k], f"sampling {key} small {small}: the oracle's own {k} differs by {v:.3g} (constant {sp.MEASURED[k]:.3g})"
+    return own
+
+
+@pytest.mark.parametrize("key", SAMPLE_KEYS, ids=SAMPLE_IDS)
+@pytest.mark.parametrize("n", ch.NS)
+def test_sample_case_conditions(n, key):
+    """The conditions of sample_cases.py on a chain's case (conditions, not measurements)."""
+    import blend_cases as bc
+    import sample_cases as sp
+
+    key = _sample_key(n, key)
+    case = ch.sample_case(key)
+    t, dt = case["t"], case["dt"]
+    o, os_ = ch.sample_oracle(key), ch.sample_oracle(key, small=True)
+    own = {k: max(a, b) for (k, a), b in zip(_sample_own(key, False).items(), _sample_own(key, True).values())}
+    print(f"\nsampling {case['name']}: {len(t)} paths, dt {dt:g}, M {case['M']}; oracle float64 against longdouble: "
+          + ", ".join(f"{k} {v:.2g}" for k, v in own.items()))
+    planted = case["planted"]
+    row = (lambda p: planted + p) if key[0] == "grid" else planted.get
+    assert o["status"][row(sp.P_STOPS)] == sp.STOPS and o["status"][row(sp.P_DECREASING)] == sp.INVALID
+    assert o["status"][row(sp.P_SHORT)] == sp.OK and o["needed"][row(sp.P_SHORT)] == 2
+    assert o["status"][row(sp.P_EXACT)] == sp.OK and o["needed"][row(sp.P_EXACT)] == sp.EXACT_ROWS + 1
+    assert os_["status"][row(sp.P_SHORT)] == sp.OK and os_["status"][row(sp.P_EXACT)] == sp.OK
+    if key[0] == "grid":
+        assert o["status"][row(sp.P_UNTIMED)] == sp.UNTIMED and o["status"][row(sp.P_NAN_Q)] == sp.INVALID
+    else:
+        bl = case["blend"]
+        assert len(bl["status"]) == ch.BLEND_PROBLEMS and len(case["movers"]) >= 12
+        assert (bl["status"][case["movers"]] == (bc.STRAIGHT if n == 1 else bc.DONE)).all()
+        timed = np.isin(bl["status"], (bc.DONE, bc.STRAIGHT))       # (the timing twin answered 0 on each: curve_case_of asserts it)
+        assert not np.isnan(t[timed]).any() and np.isnan(t[~timed]).all() and (o["status"][~timed] == sp.UNTIMED).all()
+    assert set(o["status"].tolist()) == {sp.OK, sp.STOPS, sp.UNTIMED, sp.INVALID}, "the default M truncates nobody"
+    assert set(os_["status"].tolist()) == {sp.OK, sp.TRUNCATED, sp.STOPS, sp.UNTIMED, sp.INVALID}, "every status occurs"
+    timed = np.isin(os_["status"], (sp.OK, sp.TRUNCATED))
+    cut = os_["status"] == sp.TRUNCATED
+    assert 0 < cut.sum() < timed.sum()
+    need = o["needed"]
+    assert 28 <= need.max() <= 57 and need.max() == case["M"]
+    for b in np.flatnonzero(timed):
+        if b == row(sp.P_EXACT):
+            assert t[b, -1] == sp.EXACT_ROWS * dt
+            continue
+        T = t[b, -1]
+        k = np.arange(need[b] + 2)
+        assert (np.abs(k * dt - T) > sp.NEAR * T).all(), f"path {b}: a sample time within {sp.NEAR:g} T of T"
+
+
+@pytest.mark.parametrize("key", SAMPLE_KEYS, ids=SAMPLE_IDS)
+@pytest.mark.parametrize("n", ch.NS)
+def test_sample_twin_matches_the_oracle(n, key):
+    """The oracle's own float64-against-longdouble differences against the constants sample_cases' bounds were sized from, then the
+    module's rule with its bounds unchanged and the torques against the existing inverse dynamics, at M and at M_SMALL; row 0 is the
+    path's start and the hold rows are its end, bit for bit."""
+    import sample_cases as sp
+
+    key = _sample_key(n, key)
+    case = ch.sample_case(key)
+    worst = dict.fromkeys(sp.REAL, 0.0)
+    for small in (False, True):
+        _sample_own(key, small)
+        got = ch.sample_twin(key, small)
+        assert set(got) == set(sp.KEYS)
+        label = f"{case['name']} M {got['s'].shape[1]} twin against the oracle"
+        for k, v in sp.check(got, ch.sample_oracle(key, small), label, show=False).items():
+            worst[k] = max(worst[k], v / sp.BOUND[k])
+        sp.check_torques(case, got, label)
+        dead = ~np.isin(got["status"], (sp.OK, sp.TRUNCATED))
+        for k in sp.REAL:
+            assert np.isnan(got[k][dead]).all() and np.isfinite(got[k][~dead]).all(), k
+        assert not got["count"][dead].any() and not got["needed"][dead].any() and (got["count"][~dead] >= 1).all()
+    print(f"\nsampling {case['name']}: twin against oracle, share of the bound: " + ", ".join(f"{k} {v:.2g}" for k, v in worst.items()))
+    got = ch.sample_twin(key)
+    ok = np.flatnonzero(got["status"] == sp.OK)
+    assert len(ok) >= 3
+    for b in ok:
+        c = got["count"][b]
+        if case["source"] == "grid":
+            start, end = case["path"][0][b, 0], case["path"][0][b, -1]
+        else:
+            start, end = case["curve"]["points"][b, 0], case["curve"]["points"][b, case["curve"]["count"][b] - 1]
+        assert np.array_equal(got["positions"][b, 0], start) and got["s"][b, 0] == 0
+        assert (got["positions"][b, c - 1:] == end).all() and (got["s"][b, c - 1:] == 1).all()
+        assert not got["velocities"][b, c - 1:].any() and not got["accelerations"][b, c - 1:].any()

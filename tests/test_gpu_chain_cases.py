@@ -1,4 +1,4 @@
-"""GPU: every joint count 1..8 of the ten later kernel families on chain_cases.chain(n) - prismatic joints included - through the
+"""GPU: every joint count 1..8 of the twelve later kernel families on chain_cases.chain(n) - prismatic joints included - through the
 DEVICE forms, each output buffer filled with 0xFF (a row the kernel skipped reads as NaN) and followed by a 4096-byte guard of 0xA5
 that must come back untouched (a store past the last valid row).  Kernels are held to their CPU twins under each family's existing
 kernel-against-twin rule and, where test_chain_cases_host.py has one, to the independent oracle.
@@ -13,15 +13,23 @@ and guarded like the outputs.  Measured on an MI355X, seconds a test (the oracle
     n              1     2     3     4     5     6     7     8
     rrt_connect    0.6   3.5   0.8   3.2   7.5   4.5   3.9   6.9
     path_shortcut  0.1   2.1   1.0   <2.2  5.3   3.4   2.5   5.1
-(at max_iters 48 / 50 on every chain the same tests took 7 to 16 s on n = 4..8, which is why chain_cases cuts those chains' max_iters.)"""
+(at max_iters 48 / 50 on every chain the same tests took 7 to 16 s on n = 4..8, which is why chain_cases cuts those chains' max_iters.)
+
+Corner blending and fixed-rate sampling (test_path_blend, test_trajectory_sample, test_trajectory_sample_torque_variants,
+test_blend_time_sample_chain) run chain_cases.blend_case / sample_curve_case / sample_grid_case through the device runs of
+test_gpu_blend.py and test_gpu_sample.py, guard bands included: 40 tests, under a second each, 8 s together."""
 import numpy as np
 import pytest
 
+import blend_cases as bc
 import chain_cases as ch
 import collision_cases as cc
 import collision_edge_cases as ec
 import ilqr_cases as ic
 import opspace_cases as oc
+import sample_cases as sp
+import test_gpu_blend as gb
+import test_gpu_sample as gs
 import toppra_cases as tc
 from manipulapy_amd import _hip, registry
 
@@ -707,3 +715,159 @@ def test_path_shortcut(ctx, planner, n):
     _identical(ok, clean, f"shortcut n={n} beside replaced problems", np.setdiff1d(np.arange(P), BAD))
     print(f"\nshortcut n={n}: kernel against twin{' and oracle' if n in ORACLE_NS else ''}: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items())
           + f" (bounds {sc.WAYPOINT_BOUND:.3g}, {sc.LENGTH_BOUND:.3g})")
+
+
+# ------------------------------------------------------------------------------------------------ mp_path_blend_f64
+# k_path_blend<n> and k_path_blend_sample<n> on chain_cases.blend_case(n): 145 problems (two waves and 17 lanes), 145 x 33 grid rows of
+# 8 n bytes each - for n = 1, 3, 5, 7 no multiple of 16 bytes - stored whole tiles at a time.  The device runs are test_gpu_blend.py's
+# (fresh 0xFF buffers, a guard band behind every output).
+def _shares(figures, bound):
+    return ", ".join(f"{k} {v / bound[k] if bound[k] else 0.0:.2g}" for k, v in figures.items())
+
+
+@pytest.mark.parametrize("run", ("base", "raised"))
+@pytest.mark.parametrize("n", ch.NS)
+def test_path_blend(ctx, n, run):
+    """Every discrete output of every problem equals the twin's (gap = inf: nobody is excused) and the float64 oracle's, the real ones
+    lie within blend_cases.BOUND of both; NaN outside DONE / STRAIGHT / POINT; the end rows of the grid are the input's end waypoints
+    bit for bit; 64 lanes serving all 145 problems give the full launch's bits."""
+    case, B = ch.blend_case(n), ch.BLEND_PROBLEMS
+    got = gb.device_run(ctx, case, run=run)
+    what = f"blend n={n} {run} kernel against the"
+    tw = bc.check_against_oracle(got, dict(ch.blend_twin(n, run), gap=np.full(B, np.inf)), f"{what} twin", show=False)
+    ora = bc.check_against_oracle(got, ch.blend_oracle(n, run), f"{what} oracle", show=False)
+    print(f"\nblend n={n} {run}: share of the bound: against the twin {_shares(tw, bc.BOUND)}; against the oracle {_shares(ora, bc.BOUND)}")
+    st = got["status"]
+    assert st[ch.BLEND_PLANTED_COLLINEAR] == bc.DONE and (n == 1 or {bc.DONE, bc.STRAIGHT, bc.SKIPPED, bc.POINT, bc.REVERSAL, bc.INVALID}
+                                                           <= set(st.tolist()))
+    assert n == 1 or (run == "raised") == bool((st == bc.BLOCKED).any())
+    path = np.isin(st, (bc.DONE, bc.STRAIGHT, bc.POINT))
+    for k in bc.REAL:
+        assert np.isnan(got[k][~path]).all(), k
+    curve = np.flatnonzero((st == bc.DONE) | (st == bc.STRAIGHT))
+    assert np.array_equal(got["q"][curve, 0], case["waypoints"][curve, 0])
+    assert np.array_equal(got["q"][curve, -1], case["waypoints"][curve, case["count"][curve] - 1])
+    gb._same(gb.device_run(ctx, case, run=run, max_blocks=1), got)
+
+
+# ------------------------------------------------------------------------------------------------ mp_trajectory_sample_f64
+# k_traj_sample<n, source, torques> on chain_cases.sample_curve_case / sample_grid_case through test_gpu_sample.py's device run.
+SAMPLE_GPU_KEYS = (("curve",), ("grid", 33, True), ("grid", 3, False))
+WRENCH = np.array([0.3, -0.2, 0.1, 4.0, -3.0, 2.0])
+
+
+@pytest.mark.parametrize("n", ch.NS)
+def test_trajectory_sample(ctx, n):
+    """Both sources at M and at M_SMALL: status, count and needed equal the twin's and the oracle's on every path, the real outputs lie
+    within sample_cases.BOUND of both, the torques follow the existing inverse dynamics at the returned rows, dead paths are NaN and
+    live ones finite; one block walking all the tiles gives the full launch's bits."""
+    worst = {}
+    for short in SAMPLE_GPU_KEYS:
+        key = short[:1] + (n,) + short[1:]
+        case = ch.sample_case(key)
+        for small in (False, True):
+            got = gs.device_run(ctx, case, sp.M_SMALL if small else None)
+            label = f"{case['name']} M {got['s'].shape[1]} kernel"
+            figs = (sp.check(got, ch.sample_twin(key, small), label + " against the twin", show=False),
+                    sp.check(got, ch.sample_oracle(key, small), label + " against the oracle", show=False))
+            for k in sp.REAL:
+                worst[k] = max(worst.get(k, 0.0), figs[0][k], figs[1][k])
+            sp.check_torques(case, got, label)
+            dead = ~np.isin(got["status"], (sp.OK, sp.TRUNCATED))
+            assert dead.any() and not dead.all()
+            for k in sp.REAL:
+                assert np.isnan(got[k][dead]).all() and np.isfinite(got[k][~dead]).all(), k
+            if not small:
+                gs._same(gs.device_run(ctx, case, max_blocks=1), got)
+    print(f"\nsampling n={n}: kernel against twin and oracle, share of the bound: {_shares(worst, sp.BOUND)}")
+
+
+# The torques: up to 6 joints k_traj_sample's torque instances write them in the same launch; from 7 joints on the entry runs
+# k_traj_sample without torques and k_id over its rows, whatever outputs the caller asks for (rows it did not ask for live in the
+# context's pool for the call), and dispatches no torque instance: k_traj_sample<8, grid, torques with a wrench> wrote behind its
+# arrays, and MANIPULAPY_HIP_SAMPLE_TORQUES, which used to force such an instance, is no longer read (DESIGN section 7).
+@pytest.mark.parametrize("n", ch.NS)
+def test_trajectory_sample_torque_variants(ctx, n, monkeypatch):
+    """Three ways to the torques on the N = 33 grid case, without and with a tip wrench: the full call, a torques-only call, and the
+    full call with MANIPULAPY_HIP_SAMPLE_TORQUES=fused in the environment.  Up to 6 joints the three torque arrays agree bit for bit.
+    From 7 joints on the last two agree bit for bit, follow the inverse-dynamics twin at the returned rows and lie within the rule's
+    bound of the full call.  s, sd, sdd and the rows are the same bits in every variant, the launch without torques, a call for the
+    positions and the torques alone and the call with the wrench included."""
+    case = ch.sample_grid_case(n, 33, True)
+    rest = tuple(k for k in sp.KEYS if k != "torques")
+    bare = None
+    for F in (None, WRENCH):
+        what = f"sampling n={n} wrench {F is not None}"
+        full = gs.device_run(ctx, case, Ftip=F)
+        alone = gs.device_run(ctx, case, want=("torques",), Ftip=F)
+        monkeypatch.setenv("MANIPULAPY_HIP_SAMPLE_TORQUES", "fused")
+        forced = gs.device_run(ctx, case, Ftip=F)
+        monkeypatch.delenv("MANIPULAPY_HIP_SAMPLE_TORQUES")
+        gs._same(forced, full, rest)
+        gs._same(gs.device_run(ctx, case, want=rest, Ftip=F), full, rest)
+        gs._same(gs.device_run(ctx, case, want=("positions", "torques"), Ftip=F), forced, ("positions", "torques"))
+        gs._same(alone, forced, ("torques",))
+        sp.check_torques(case, full, what + " full call", Ftip=F)
+        if n <= 6:
+            gs._same(forced, full, ("torques",))
+        else:
+            for got, how in ((forced, "with the variable set"), (dict(full, torques=alone["torques"]), "torques alone")):
+                sp.check_torques(case, got, f"{what} {how}", Ftip=F)
+                sp.check({"torques": got["torques"]}, full, f"{what} {how} against the full call", show=False, keys=("torques",))
+        if F is None:
+            bare = full
+    gs._same(full, bare, rest)
+    assert not np.array_equal(full["torques"], bare["torques"], equal_nan=True)
+    curve = ch.sample_curve_case(n)     # the curve source with the wrench
+    full = gs.device_run(ctx, curve, Ftip=WRENCH)
+    sp.check_torques(curve, full, f"sampling n={n} curve with the wrench", Ftip=WRENCH)
+    gs._same(gs.device_run(ctx, curve, want=("torques",), Ftip=WRENCH), full, ("torques",))
+
+
+# ------------------------------------------------------------------------------------------------ blend -> time -> sample
+def _chain_planner(n, backend):
+    import manipulapy_amd as mp
+
+    tb, _, lim, _ = ch.chain(n)
+    dyn = mp.ManipulatorDynamics(M_list=tb.M_ee, omega_list=None, r_list=None, b_list=None, S_list=tb.S, B_list=tb.S.copy(), Glist=tb.G,
+                                 Mlist_per_link=tb.Mcom)
+    return mp.OptimizedTrajectoryPlanning(dyn, None, dyn, lim, use_cuda=None if backend == "hip" else False)
+
+
+@pytest.mark.parametrize("n", ch.NS)
+def test_blend_time_sample_chain(ctx, n, monkeypatch):
+    """batch_time_optimal_trajectory - batch_blend_path, the TOPP-RA parameterisation of its DONE / STRAIGHT rows, then
+    batch_sample_time_optimal on the blended curves - on the first 16 inputs of blend_case(n), "hip" backend against "numpy": the blend
+    under blend_cases' rule with nobody excused, the timing's status and sd2, and the sampler on "hip" on the NumPy backend's blend and
+    timing under sample_cases' rule (the two timings differ by rounding, which the sampler's rule does not cover)."""
+    import manipulapy_amd as mp
+
+    monkeypatch.setenv("MANIPULAPY_HIP_SPECIALIZE", "0")       # (the float32 specialisation has no part in these float64 families)
+    case, B = ch.blend_case(n), 16
+    wp, cnt, cm = case["waypoints"][:B], case["count"][:B], case["cm"]
+    dt, vl, inf = ch.sample_curve_case(n)["dt"], np.full(n, 2.0), np.tile([-np.inf, np.inf], (n, 1))
+    runs = {}
+    for backend in ("numpy", "hip"):
+        with mp.use_backend(backend):
+            pl = _chain_planner(n, backend)
+            before = pl.performance_stats["gpu_calls"]
+            runs[backend] = pl.batch_time_optimal_trajectory(wp, cnt, cm, bc.GRID, dt, vl, torque_limits=inf, acceleration_limits=np.full(n, 10.0),
+                                                             margin=bc.RUNS["base"], tol=bc.TOL, g=ch.G9, **bc.params_of())
+            assert (pl.performance_stats["gpu_calls"] - before >= 3) == (backend == "hip")      # three launches, none on the host
+    cpu, gpu = runs["numpy"], runs["hip"]
+    gb._same(cpu["blend"], {k: v[:B] for k, v in ch.blend_twin(n).items()})
+    bc.check_against_oracle(gpu["blend"], dict(cpu["blend"], gap=np.full(B, np.inf)), f"n={n} planner blend on hip against numpy", show=False)
+    st = gpu["blend"]["status"]
+    curve = (st == bc.DONE) | (st == bc.STRAIGHT)
+    assert curve.any() and (~curve).any()        # (12, 5, 14, 7, 2, 5, 6, 1 of the 16 rows have a curve, n = 1..8)
+    assert np.array_equal(gpu["timing"]["status"], cpu["timing"]["status"]) and (gpu["timing"]["status"][curve] == 0).all()
+    assert (gpu["timing"]["status"][~curve] == -1).all()
+    tc.f64_rule(gpu["timing"]["sd2"][curve], cpu["timing"]["sd2"][curve], f"n={n} planner sd2 on hip against numpy")
+    moving = np.isfinite(cpu["timing"]["duration"])
+    assert np.array_equal(moving, np.isfinite(gpu["timing"]["duration"])) and moving.any()
+    sam = gpu["samples"]["status"]
+    assert (sam[moving] == sp.OK).all() and (sam[curve & ~moving] == sp.STOPS).all() and (sam[~curve] == sp.UNTIMED).all()
+    with mp.use_backend("hip"):
+        again = pl.batch_sample_time_optimal(cpu["timing"], dt, curve=cpu["blend"], velocity_limits=vl, g=ch.G9)
+    sp.check({k: again[k] for k in sp.KEYS}, {k: cpu["samples"][k] for k in sp.KEYS}, f"n={n} planner samples on hip against numpy", show=False)
+    sp.check_torques(dict(ch.sample_curve_case(n), model=pl._hip_model()), again, f"n={n} planner samples on hip")

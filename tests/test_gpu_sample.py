@@ -192,8 +192,8 @@ def test_device_form_host_form_subsets_and_torques(ctx):
         _same(device_run(ctx, case, want=rest), dev, rest)
         for want in (("status",), ("needed", "s"), ("positions", "count"), ("sd", "sdd", "velocities", "accelerations")):
             _same(device_run(ctx, case, want=want), dev, want)
-        # the torques without the rows: from 7 joints on the full call takes them from the inverse-dynamics kernel over the rows it
-        # wrote, a call without the rows from the fused recursion - the same contract, the rule's bound between the two
+        # the torques without the rows: from 7 joints on every call takes them from the inverse-dynamics kernel over the rows the
+        # sampler wrote - the caller's, or the context's pool where the caller gave none - and the rule's bound is all that is asked
         alone = device_run(ctx, case, want=("torques",))
         sub = ctx.trajectory_sample_arrays(case["model"], case["t"], case["x"], case["dt"], case["M"], path=case["path"], curve=case["curve"],
                                            g=case["g"], want=("torques", "count"))
@@ -214,7 +214,7 @@ def test_device_form_host_form_subsets_and_torques(ctx):
 
 def test_grid_source_with_a_wrench(ctx):
     """k_traj_sample<N, grid, torques with a wrench>, the one instance the curve case above does not reach: xarm6 (6 joints, the full
-    call) and panda (8 joints, the last of the joint-count switch: the torques alone, which there come from the fused recursion), five
+    call) and panda (8 joints, beyond the joint-count switch: the torques alone, from k_id over rows kept in the context's pool), five
     paths of 33 rows = two waves and a partial one.  The torques follow the inverse-dynamics twin WITH the wrench at the returned rows
     and differ from the call without it; every other output is that call's, bit for bit."""
     F = np.array([0.3, -0.2, 0.1, 4.0, -3.0, 2.0])

@@ -9,8 +9,8 @@ Grid source: the paths of tools/toppra_bench.py (DESIGN 4.8's case) - 2048 disti
 velocity and effort limits, repeated to --B paths (a path's result depends on its content only) - at a dt that gives the longest path
 each of --rows rows (M = that many).  Curve source: the 139 problems of tests/blend_cases.py (base run) blended at N = --grid, timed
 with velocity limits 2 and acceleration limits 40, --copies copies, 100 rows.  Per configuration:
-  fused_ms      mp_trajectory_sample_f64 with every output, the torques among them, forced into one launch
-                (MANIPULAPY_HIP_SAMPLE_TORQUES=fused);
+  fused_ms      mp_trajectory_sample_f64 with every output, the torques among them, in one launch - up to 6 joints, where the entry
+                has that form; from 7 joints on it no longer dispatches the torque instances (DESIGN 7) and this is entry_ms again;
   plain_ms      the same without the torques;
   id_ms         mp_id_trajectory_f64 over the B M rows the plain launch wrote;
   split_ms      the plain launch and the inverse-dynamics launch, timed together: the split form;
@@ -89,12 +89,8 @@ def _measure(ctx, model, t, x, dt, M, reps, path=None, curve=None):
             ident()
 
         r = {"paths": B, "grid": N, "rows": M, "n": n, "dt": dt}
-        def fused():   # the fused kernel whatever the entry would choose (it reads the variable at every call)
-            os.environ["MANIPULAPY_HIP_SAMPLE_TORQUES"] = "fused"
-            try:
-                sample(_hip.SAMPLE_OUTPUTS)
-            finally:
-                del os.environ["MANIPULAPY_HIP_SAMPLE_TORQUES"]
+        def fused():   # every output in one call: the fused kernel up to 6 joints, the entry's split form beyond
+            sample(_hip.SAMPLE_OUTPUTS)
 
         for key, fn in (("fused", fused), ("plain", plain), ("id", ident), ("split", split), ("entry", lambda: sample(_hip.SAMPLE_OUTPUTS))):
             r[f"{key}_ms"], r[f"{key}_min_ms"], r[f"{key}_max_ms"], r[f"{key}_launches"] = _time(ctx, fn, reps)
