@@ -706,6 +706,32 @@ int mp_pd_regulation_cpu_f64(const mp_model* model, const double* theta0, const 
  *   (it grows in steps of 64 obstacles; a replaced table stays allocated until the handle is destroyed) - see the new world.  The robot's
  *   tables are not rebuilt.  ctx = NULL sets the world of the _cpu twin only; a handle that no call has given a world has O = 0.  Not
  *   allowed during a capture.
+ * Point cloud (csrc/mp_cloud.h): M points x_i with one common radius r_c >= 0 and a truncation distance d_max > 0.  It counts as ONE
+ *   obstacle, appended after the O primitives, for every entry that takes the handle (the edge check and the planners included):
+ *     sd_cloud(p) = min( d_max , min_i |p - x_i| - r_c )
+ *   the exact signed distance to the union of the M balls, cut off at d_max.  It is >= -r_c and 1-Lipschitz, so it never overstates the
+ *   true distance and conservative advancement stays sound with it; far from the cloud a step is limited by d_max, the knob.
+ *   The direction n is the unit vector from the nearest point to p; it is 0 where the value is the truncated one or the two coincide
+ *   (length below 1e-300).  Witness: the obstacle member of arg_world (and of the edge check's witness) is O + i for the caller's point
+ *   i, O + M where the cloud's value is the truncated one; -1 keeps meaning that there is no candidate at all.  Of equal minima the first
+ *   in (link, caller sphere index), then obstacle order stays: the cloud's points come after the primitives in the caller's index order
+ *   (of equally near points the lowest index, whatever the grid stores or visits), the truncated value last (|p - x_i| - r_c = d_max is
+ *   point i; a point within an ulp or so of that distance may be reported either way - the value is d_max in both cases).  Cost: ONE hinge term per (sphere on a link >= 1, cloud), phi(sd_cloud(p_s) - r_s; eps_world), not one per point, with the
+ *   gradient phi' n (zero where truncated); it is the exact cost of the union of balls whenever d_max >= eps_world + max_s r_s.  Edge
+ *   check: the cloud's d enters its link's smallest distance and the witness exactly as a primitive's does.  The base's spheres do not
+ *   meet the cloud.
+ * mp_collision_set_cloud(ctx, h, M, points, radius, d_max, cell): points (M,3) host array; M = 0 removes the cloud; cell <= 0 selects
+ *   the default d_max + radius.  The points are sorted into a uniform grid of edge `cell` over their bounding box (float64 positions,
+ *   the caller's index beside each); a query visits the (2 R + 1)^3 cells around p, R = ceil((d_max + radius) / cell), which must be
+ *   1..4.  A non-finite point, a negative or non-finite radius, d_max not positive and finite, R outside 1..4, M above 2^24 or a grid of
+ *   more than 2^22 cells ("raise cell") is MP_ERR_INVALID with a message and leaves the previous cloud in place.  Otherwise as
+ *   mp_collision_set_world: the image is copied behind the launches already on the compute stream, the call returns when the copy is
+ *   done, a replaced device buffer stays allocated until the handle is destroyed, ctx = NULL sets the _cpu twin's copy only, not allowed
+ *   during a capture; the two calls never disturb each other.  Launches on a handle with a cloud run kernel instances of their own
+ *   (without one, the code is what it was before clouds existed): a graph captured while a cloud was set sees every later cloud when
+ *   replayed, one captured without a cloud keeps running without.
+ * mp_collision_cloud_info(h, &M, &radius, &d_max, &cell, dims): the cloud's count (0: none), parameters and grid dimensions (3 int32);
+ *   any output may be NULL.
  * mp_collision_f64: d_q (rows,n) device rows, 16-byte aligned like every output.  Asynchronous, no synchronisation; it allocates nothing
  *   once the handle is resident on the context (its first mp_collision_set_world, mp_collision_f64 or _host_f64 there makes it so),
  *   and may then be captured into a launch graph.  mp_collision_host_f64: host arrays, device memory from the context's pool.
@@ -719,6 +745,8 @@ int mp_collision_create(const mp_model* model, int S, const int32_t* link, const
                         const int32_t* pairs, mp_collision** out);
 int mp_collision_destroy(mp_collision* h);
 int mp_collision_set_world(mp_ctx* ctx, mp_collision* h, int O, const int32_t* kind, const double* params);
+int mp_collision_set_cloud(mp_ctx* ctx, mp_collision* h, int64_t M, const double* points, double radius, double d_max, double cell);
+int mp_collision_cloud_info(const mp_collision* h, int64_t* M, double* radius, double* d_max, double* cell, int32_t* dims);
 int mp_collision_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q, int64_t rows, double eps_world,
                      double eps_self, double* d_dist_world, int32_t* d_arg_world, double* d_dist_self, int32_t* d_arg_self,
                      double* d_grad_dist_world, double* d_grad_dist_self, double* d_cost, double* d_grad);

@@ -176,6 +176,8 @@ SIGNATURES = {
     "mp_collision_create": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _c_dp, _c_dp, ctypes.c_int, _vp, ctypes.POINTER(_vp)]),
     "mp_collision_destroy": (ctypes.c_int, [_vp]),
     "mp_collision_set_world": (ctypes.c_int, [_vp, _vp, ctypes.c_int, _vp, _c_dp]),
+    "mp_collision_set_cloud": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _c_dp, ctypes.c_double, ctypes.c_double, ctypes.c_double]),
+    "mp_collision_cloud_info": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_collision_f64": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "mp_collision_host_f64": (ctypes.c_int, [_vp, _vp, _vp, _c_dp, _i64, ctypes.c_double, ctypes.c_double, _c_dp, _vp, _c_dp, _vp, _c_dp, _c_dp, _c_dp, _c_dp]),
     "mp_collision_cpu_f64": (ctypes.c_int, [_vp, _vp, _c_dp, _i64, ctypes.c_double, ctypes.c_double, _c_dp, _vp, _c_dp, _vp, _c_dp, _c_dp, _c_dp, _c_dp, ctypes.c_int]),
@@ -1558,6 +1560,21 @@ class HipCollision:
         pm = _as_c(np.zeros((0, 16)) if O == 0 else params, np.float64, (O, 16), "params")
         _check(self.lib.mp_collision_set_world(None if ctx is None else ctx.handle, self.handle, O, kd.ctypes.data_as(_vp) if O else None,
                                                _dptr(pm) if O else None))
+
+    def set_cloud(self, points, radius: float, d_max: float, cell: float = 0.0, ctx: Optional["HipContext"] = None) -> None:
+        """points (M,3) with one radius and the truncation distance d_max; M = 0 removes the cloud; cell <= 0: d_max + radius.  ctx=None
+        sets the cloud the CPU twin reads; with a context its grid is also copied to the device."""
+        pts = np.ascontiguousarray(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+        M = pts.shape[0]
+        _check(self.lib.mp_collision_set_cloud(None if ctx is None else ctx.handle, self.handle, M, _dptr(pts) if M else None,
+                                               float(radius), float(d_max), float(cell)))
+
+    def cloud_info(self) -> dict:
+        """{"M", "radius", "d_max", "cell", "dims"} of the cloud the CPU twin reads (M = 0: none)."""
+        M, r, d, c = ctypes.c_int64(0), ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        dims = (ctypes.c_int32 * 3)()
+        _check(self.lib.mp_collision_cloud_info(self.handle, ctypes.byref(M), ctypes.byref(r), ctypes.byref(d), ctypes.byref(c), dims))
+        return {"M": int(M.value), "radius": r.value, "d_max": d.value, "cell": c.value, "dims": tuple(int(v) for v in dims)}
 
     def motion_bounds(self) -> np.ndarray:
         """rho (n, n + 1): row j - 1, column k = the largest distance of a sphere centre of link k from the axis of revolute joint j."""

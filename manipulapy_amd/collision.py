@@ -2,8 +2,10 @@
 own spheres, the CHOMP hinge cost and its gradient (csrc/mp_collision.h; the conventions are those of include/manipula_hip.h).
 
 The robot is S spheres, each fixed to a link (0 = the base .. n) and given by its centre in the space frame at q = 0; the world is a
-table of spheres, capsules and oriented boxes that can be replaced at any time.  No meshes: `potential_field.CollisionChecker` keeps
-mirroring the reference's mesh-less checker and is not touched by this module.
+table of spheres, capsules and oriented boxes that can be replaced at any time, and optionally a point cloud - a sensed scene as
+points or occupied voxels with one radius, one more obstacle after the table's (`set_cloud`, `set_cloud_from_voxels`;
+csrc/mp_cloud.h).  Every query and planner of the model sees both.  No meshes: `potential_field.CollisionChecker` keeps mirroring
+the reference's mesh-less checker and is not touched by this module.
 """
 from __future__ import annotations
 
@@ -51,8 +53,10 @@ class SphereCollisionModel:
         self.handle = _hip.HipCollision(self.model, self.links, self.centres, self.radii, self.pairs)
         self.kinds = np.zeros(0, dtype=np.int32)
         self.params = np.zeros((0, 16))
+        self._cloud = None  # (points (M, 3), radius, d_max, cell) as given, or None
         self._version = 0
-        self._uploaded = {}  # id(context) -> world version on its device
+        self._cloud_version = 0
+        self._uploaded = {}  # id(context) -> (world version, cloud version) on its device
 
     # ------------------------------------------------------------------ construction from a kinematic chain
     @classmethod
@@ -144,11 +148,63 @@ class SphereCollisionModel:
         self.kinds, self.params = kinds.copy(), params.copy()
         self._version += 1
 
+    def set_cloud(self, points, radius: float, d_max: float, cell: Optional[float] = None) -> None:
+        """A point cloud as one more obstacle after the table's: points (M, 3), every one a ball of `radius` (>= 0), the distance cut
+        off at `d_max` (> 0): sd(p) = min(d_max, min_i |p - x_i| - radius), exact for the union of the balls below d_max and never
+        above the true distance.  `arg_world`'s obstacle index is O + i for point i, O + M where the value is the cut-off one.  The
+        cost has one hinge term per (robot sphere, cloud), exact whenever d_max >= eps_world + the largest sphere radius; the edge
+        check and every planner treat the cloud like any obstacle, and far from it a step of theirs is limited by d_max.  `cell`
+        (None: d_max + radius) is the edge of the grid the points are sorted into; it may be as small as a quarter of the default
+        (fewer points per cell, up to 729 cells a query instead of 27).  Replaces the previous cloud; the primitive table stays.
+        CAPTURED GRAPHS: a launch picks the kernels that look at the cloud only when the model has one at that moment.  A graph
+        captured while a cloud was set sees every later cloud (and a cleared one) when replayed; a graph captured BEFORE the first
+        `set_cloud` keeps running without the cloud and ignores it silently - capture again after setting one."""
+        pts = np.array(points, dtype=np.float64).reshape(-1, 3)
+        if pts.shape[0] == 0:
+            return self.clear_cloud()
+        self.handle.set_cloud(pts, radius, d_max, 0.0 if cell is None else cell)   # validates; the CPU twin reads this copy
+        self._cloud = (pts, float(radius), float(d_max), self.handle.cloud_info()["cell"])
+        self._cloud_version += 1
+
+    def clear_cloud(self) -> None:
+        """Removes the point cloud: the world is the primitive table alone again."""
+        self.handle.set_cloud(np.zeros((0, 3)), 0.0, 1.0)
+        self._cloud = None
+        self._cloud_version += 1
+
+    def set_cloud_from_voxels(self, occupancy, origin, pitch: float, d_max: float, cell: Optional[float] = None) -> None:
+        """The occupied voxels of a (nx, ny, nz) bool grid as a cloud: voxel (i, j, k) is the cube of edge `pitch` whose lowest corner
+        is origin + pitch (i, j, k); its centre becomes a point and radius = pitch sqrt(3) / 2, so the balls cover the cubes."""
+        occ = np.asarray(occupancy, dtype=bool)
+        if occ.ndim != 3:
+            raise ValueError(f"occupancy must be (nx, ny, nz); got {occ.shape}")
+        pitch = float(pitch)
+        if not (pitch > 0 and np.isfinite(pitch)):
+            raise ValueError("pitch must be positive and finite")
+        centres = np.asarray(origin, dtype=np.float64).reshape(3) + pitch * (np.argwhere(occ) + 0.5)
+        self.set_cloud(centres, pitch * np.sqrt(3.0) / 2.0, d_max, cell)
+
+    @property
+    def cloud(self) -> Optional[dict]:
+        """{"points" (M, 3), "radius", "d_max", "cell"} of the current cloud, or None."""
+        if self._cloud is None:
+            return None
+        pts, radius, d_max, cell = self._cloud
+        return {"points": pts.copy(), "radius": radius, "d_max": d_max, "cell": cell}
+
     def sync_world(self, ctx) -> None:
-        """Makes the world on `ctx`'s device the current one (a copy behind the launches already on its stream; no-op when it is)."""
-        if self._uploaded.get(id(ctx)) != self._version:
+        """Makes the world on `ctx`'s device the current one, table and cloud (copies behind the launches already on its stream;
+        no-op when it is)."""
+        have = self._uploaded.get(id(ctx), (None, 0))
+        if have[0] != self._version:
             self.handle.set_world(self.kinds, self.params, ctx=ctx)
-            self._uploaded[id(ctx)] = self._version
+        if have[1] != self._cloud_version:
+            if self._cloud is None:
+                self.handle.set_cloud(np.zeros((0, 3)), 0.0, 1.0, ctx=ctx)
+            else:
+                pts, radius, d_max, cell = self._cloud
+                self.handle.set_cloud(pts, radius, d_max, cell, ctx=ctx)
+        self._uploaded[id(ctx)] = (self._version, self._cloud_version)
 
     # ------------------------------------------------------------------ queries
     def _run(self, q, eps_world, eps_self, want):
@@ -161,12 +217,14 @@ class SphereCollisionModel:
 
     def distances(self, q, want_grad: bool = False) -> dict:
         """dist_world, arg_world, dist_self, arg_self of every row of q ((rows, n) or (B, N, n)); with `want_grad` also
-        grad_dist_world and grad_dist_self."""
+        grad_dist_world and grad_dist_self.
+        The world is the obstacle table of `set_world` and the point cloud of `set_cloud`, if one is set."""
         want = ("dist_world", "arg_world", "dist_self", "arg_self") + (("grad_dist_world", "grad_dist_self") if want_grad else ())
         return self._run(q, 1.0, 1.0, want)
 
     def cost(self, q, eps_world, eps_self, want_grad: bool = True):
-        """The hinge cost of every row, and its gradient with `want_grad`: cost, or (cost, grad)."""
+        """The hinge cost of every row, and its gradient with `want_grad`: cost, or (cost, grad).
+        The world is the obstacle table of `set_world` and the point cloud of `set_cloud`, if one is set."""
         r = self._run(q, eps_world, eps_self, ("cost", "grad") if want_grad else ("cost",))
         return (r["cost"], r["grad"]) if want_grad else r["cost"]
 
@@ -185,7 +243,8 @@ class SphereCollisionModel:
         """Continuous check of the straight joint-space motions q_from -> q_to ((E, n) or any common leading shape) by conservative
         advancement: {"status" (0 free, 1 blocked, 2 undecided, -1 invalid), "t", "steps", "clearance", "witness" (.., 3)} or the
         subset named in `want`.  FREE proves clearance > margin on the whole edge; BLOCKED stops at the first evaluated t whose
-        clearance is <= margin + tol, with [0, t) proven; UNDECIDED (max_steps evaluations) proves [0, t)."""
+        clearance is <= margin + tol, with [0, t) proven; UNDECIDED (max_steps evaluations) proves [0, t).
+        The world is the obstacle table of `set_world` and the point cloud of `set_cloud`, if one is set."""
         qa, qb = np.asarray(q_from, dtype=np.float64), np.asarray(q_to, dtype=np.float64)
         if qa.shape != qb.shape or qa.ndim < 1 or qa.shape[-1] != self.n:
             raise ValueError(f"q_from and q_to must have one shape (..., {self.n}); got {qa.shape} and {qb.shape}")
@@ -203,7 +262,8 @@ class SphereCollisionModel:
         in `want`.  Every tree edge, and so every segment of a returned path, is proven free by `check_edges`' conservative
         advancement with this margin, tol and max_steps; a path is padded by repeating its last waypoint.  `min_advance` defaults
         to step / 8.  A problem's result depends on its content and `seed` only.  The launch lasts as long as its slowest problem:
-        `max_iters` is the latency knob."""
+        `max_iters` is the latency knob.
+        The world is the obstacle table of `set_world` and the point cloud of `set_cloud`, if one is set."""
         qs, qg = np.asarray(q_start, dtype=np.float64), np.asarray(q_goal, dtype=np.float64)
         if qs.shape != qg.shape or qs.ndim < 1 or qs.shape[-1] != self.n:
             raise ValueError(f"q_start and q_goal must have one shape (..., {self.n}); got {qs.shape} and {qg.shape}")
@@ -225,7 +285,8 @@ class SphereCollisionModel:
         is the room of an output path: a shortcut inside one segment pair can add a waypoint, and one that would not fit is counted
         in "skipped_full".  Every new segment is proven free and pieces of input segments are kept, so the output is as free as the
         input; THE INPUT IS NOT CHECKED (OptimizedTrajectoryPlanning.batch_validate_path does that).  A path is padded by repeating
-        its last waypoint.  A problem's result depends on its content and `seed` only."""
+        its last waypoint.  A problem's result depends on its content and `seed` only.
+        The world is the obstacle table of `set_world` and the point cloud of `set_cloud`, if one is set."""
         wp, cnt = np.asarray(waypoints, dtype=np.float64), np.asarray(count)
         if wp.ndim < 3 or wp.shape[-1] != self.n or cnt.shape != wp.shape[:-2]:
             raise ValueError(f"waypoints must be (..., W, {self.n}) and count its leading shape; got {wp.shape} and {cnt.shape}")
@@ -248,7 +309,8 @@ class SphereCollisionModel:
         path that doubles back on itself is a reversal.  "q", "dq", "ddq" are the curve and its first two derivatives in s, the
         arguments of OptimizedTrajectoryPlanning.batch_time_optimal_parameterization; rows without a curve are NaN.  The linear
         pieces are pieces of input segments and ARE NOT CHECKED (OptimizedTrajectoryPlanning.batch_validate_path does that).  A
-        problem's result depends on its content only."""
+        problem's result depends on its content only.
+        The world is the obstacle table of `set_world` and the point cloud of `set_cloud`, if one is set."""
         wp, cnt = np.asarray(waypoints, dtype=np.float64), np.asarray(count)
         if wp.ndim < 3 or wp.shape[-1] != self.n or cnt.shape != wp.shape[:-2]:
             raise ValueError(f"waypoints must be (..., W, {self.n}) and count its leading shape; got {wp.shape} and {cnt.shape}")
@@ -274,7 +336,8 @@ class SphereCollisionModel:
         their quintic Hermite interpolant - the curve that sampler executes - is proven free by `check_edges`' conservative
         advancement with this margin, tol and max_steps, or the problem is blocked / undecided at "span", "t".  "deviation_pos" /
         "deviation_rot": how far the interpolant leaves the line at the spans' midpoints (raise N when it is too much).  A problem's
-        result depends on its content only."""
+        result depends on its content only.
+        The world is the obstacle table of `set_world` and the point cloud of `set_cloud`, if one is set."""
         Tg, q0 = np.asarray(T_goal, dtype=np.float64), np.asarray(q_start, dtype=np.float64)
         if Tg.ndim < 2 or Tg.shape[-2:] != (4, 4) or q0.ndim < 1 or q0.shape[-1] != self.n or Tg.shape[:-2] != q0.shape[:-1]:
             raise ValueError(f"T_goal must be (..., 4, 4) and q_start (..., {self.n}) with one leading shape; got {Tg.shape} and {q0.shape}")
@@ -297,7 +360,8 @@ class SphereCollisionModel:
         `plan_paths` makes for its q_goal: the first FREE one is returned as found; if none is free, the converged configuration of
         the largest clearance comes back as in collision; if none converged, NaN as unreached.  "q" goes straight into `plan_paths`
         as q_goal: a found row is never goal-blocked there under the same margin and tol.  A problem's result depends on its content
-        and `seed` only."""
+        and `seed` only.
+        The world is the obstacle table of `set_world` and the point cloud of `set_cloud`, if one is set."""
         Tg, q0 = np.asarray(T_goal, dtype=np.float64), np.asarray(q_seed, dtype=np.float64)
         if Tg.ndim < 2 or Tg.shape[-2:] != (4, 4) or q0.ndim < 1 or q0.shape[-1] != self.n or Tg.shape[:-2] != q0.shape[:-1]:
             raise ValueError(f"T_goal must be (..., 4, 4) and q_seed (..., {self.n}) with one leading shape; got {Tg.shape} and {q0.shape}")

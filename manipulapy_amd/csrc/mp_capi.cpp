@@ -2983,13 +2983,15 @@ static void collision_release(mp_collision* h) {
     (void)hipSetDevice(R.device);
     if (R.sph) (void)hipFree(R.sph);
     if (R.world) (void)hipFree(R.world);
+    if (R.cloud) (void)hipFree(R.cloud);
     if (R.counter) (void)hipFree(R.counter);
     for (void* p : R.retired) (void)hipFree(p);
   }
   h->resident.clear();
   if (prev >= 0) (void)hipSetDevice(prev);
 }
-// header + obstacles to the context's table, growing it in steps of 64 obstacles; returns when the copy is done
+// header + obstacles to the context's table, growing it in steps of 64 obstacles; the header keeps the address of the context's
+// cloud; returns when the copy is done
 static int collision_upload_world(mp_ctx* ctx, mp_collision::Resident& R, const std::vector<MpColObstacle>& w) {
   const int O = (int)w.size();
   if (!R.world || O > R.cap) {
@@ -3001,12 +3003,39 @@ static int collision_upload_world(mp_ctx* ctx, mp_collision::Resident& R, const 
     R.cap = cap;
   }
   std::vector<char> img(sizeof(MpColWorld) + (size_t)O * sizeof(MpColObstacle));
-  const MpColWorld hdr = {O, {0, 0, 0}};
+  const MpColWorld hdr = {O, 0, static_cast<const MpColCloud*>(R.cloud)};
   std::memcpy(img.data(), &hdr, sizeof hdr);
   if (O) std::memcpy(img.data() + sizeof hdr, w.data(), (size_t)O * sizeof(MpColObstacle));
   H2D(R.world, img.data(), img.size());
   HIP_TRY(hipStreamSynchronize(ctx->compute));
   return MP_OK;
+}
+// The cloud's image to a device buffer of its own (the old one is retired: a captured graph's kernels may still be reading it), then
+// the world table's header with its address - the kernels find the cloud through the header, so a replayed graph sees the new one.
+// An empty image removes the cloud.  Both copies go behind the launches already on the compute stream; returns when they are done.
+static int collision_upload_cloud(mp_ctx* ctx, mp_collision::Resident& R, const std::vector<MpCloudPoint>& img) {
+  void* p = nullptr;
+  if (!img.empty()) {
+    HIP_TRY(hipMalloc(&p, img.size() * sizeof(MpCloudPoint)));
+    if (hipMemcpyAsync(p, img.data(), img.size() * sizeof(MpCloudPoint), hipMemcpyHostToDevice, ctx->compute) != hipSuccess ||
+        hipStreamSynchronize(ctx->compute) != hipSuccess) {
+      (void)hipFree(p);
+      return mp_fail(MP_ERR_HIP, "mp_collision_set_cloud: the copy of the cloud failed");
+    }
+  }
+  if (R.cloud) R.retired.push_back(R.cloud);
+  R.cloud = p;
+  if (!R.world) return MP_OK;  // (the first upload of the world follows and writes the header)
+  const MpColCloud* at = static_cast<const MpColCloud*>(p);
+  H2D(static_cast<char*>(R.world) + offsetof(MpColWorld, cloud), &at, sizeof at);
+  HIP_TRY(hipStreamSynchronize(ctx->compute));
+  return MP_OK;
+}
+// whether a launch of `h` on this context takes the kernels' cloud instances
+// (the caller holds h->mu, as every *_impl does: mp_collision_set_cloud changes both under it)
+static bool collision_has_cloud(mp_ctx* ctx, mp_collision* h) {
+  auto it = h->resident.find(ctx->uid);
+  return it != h->resident.end() ? it->second.cloud != nullptr : !h->cloud.empty();
 }
 static int collision_resident(const char* fn, mp_ctx* ctx, mp_collision* h, mp_collision::Resident** out) {
   auto it = h->resident.find(ctx->uid);
@@ -3024,6 +3053,7 @@ static int collision_resident(const char* fn, mp_ctx* ctx, mp_collision* h, mp_c
   mp_collision::Resident& K = h->resident[ctx->uid] = R;
   H2D(K.sph, &h->sph, sizeof(MpColSpheres));
   if (pb) H2D(static_cast<char*>(K.sph) + sizeof(MpColSpheres), h->pairs.data(), pb);
+  if (int rc = collision_upload_cloud(ctx, K, h->cloud)) return rc;
   if (int rc = collision_upload_world(ctx, K, h->world)) return rc;
   *out = &K;
   return MP_OK;
@@ -3035,10 +3065,15 @@ static int collision_resident(const char* fn, mp_ctx* ctx, mp_collision* h, mp_c
   REQUIRE_SMALL(fn);                                                                                                    \
   REQUIRE(h->n == model->d.n, "%s: the collision handle was made for a model of %d joints, this one has %d", fn, h->n, model->d.n)
 
+// ... for an entry that holds no lock yet (the host forms size their workspace before they enter the impl)
+static bool collision_has_cloud_locked(mp_ctx* ctx, mp_collision* h) {
+  std::lock_guard<std::mutex> hl(h->mu);
+  return collision_has_cloud(ctx, h);
+}
 static MpColDevice collision_device(const mp_collision* h, const mp_collision::Resident* R) {
   return {h->sph.S, static_cast<const MpColSpheres*>(R->sph),
           reinterpret_cast<const MpColPair*>(static_cast<const char*>(R->sph) + sizeof(MpColSpheres)),
-          static_cast<const MpColWorld*>(R->world), static_cast<unsigned long long*>(R->counter)};
+          static_cast<const MpColWorld*>(R->world), static_cast<unsigned long long*>(R->counter), R->cloud != nullptr};
 }
 // The grid of a work-queue launch (mpk_queue_plan): the resident blocks, ceil(B / 64), max_blocks if that is positive and the blocks
 // the workspace holds, whichever is smallest.
@@ -3095,7 +3130,7 @@ static int collision_edges_impl(const char* fn, mp_ctx* ctx, const mp_model* mod
   PROFILE_SCOPE(ctx, fn);
   const MpColEdgeParams P = {margin, tol, max_steps, 0};
   MpQueuePlan plan;
-  HIP_TRY(mpk_queue_plan(MP_QUEUE_EDGES, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_queue_plan(MP_QUEUE_EDGES, model->d.n, h->sph.S, collision_has_cloud(ctx, h), ctx->compute_units, &plan));
   HIP_TRY(mpk_collision_edges(ctx->compute, model->d, collision_device(h, R), d_qa, d_qb, (long)edges, P, d_status, d_t, d_steps, d_clear,
                               d_witness, queue_grid(plan, edges, max_blocks), plan.lds));
   return MP_OK;
@@ -3155,7 +3190,7 @@ static int rrt_connect_impl(const char* fn, mp_ctx* ctx, const mp_model* model, 
   PROFILE_SCOPE(ctx, fn);
   MpQueuePlan plan;
   if (made) plan = *made;
-  else HIP_TRY(mpk_queue_plan(MP_QUEUE_RRT, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  else HIP_TRY(mpk_queue_plan(MP_QUEUE_RRT, model->d.n, h->sph.S, collision_has_cloud(ctx, h), ctx->compute_units, &plan));
   HIP_TRY(mpk_rrt_connect(ctx->compute, model->d, collision_device(h, R), d_qs, d_qg, (long)B, P, d_status, d_count, d_wp, d_iters,
                           d_nodes, d_evals, static_cast<double*>(d_ws), queue_grid(plan, B, max_blocks, ws_bytes / block_bytes), plan.lds));
   return MP_OK;
@@ -3192,7 +3227,7 @@ int mp_rrt_connect_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h,
   if (B == 0) return MP_OK;
   REQUIRE(q_start && q_goal, "%s: null host pointer", fn);
   MpQueuePlan plan;
-  HIP_TRY(mpk_queue_plan(MP_QUEUE_RRT, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_queue_plan(MP_QUEUE_RRT, model->d.n, h->sph.S, collision_has_cloud_locked(ctx, h), ctx->compute_units, &plan));
   const size_t n = (size_t)model->d.n, qb = (size_t)B * n * sizeof(double), ib = (size_t)B * sizeof(int32_t);
   const size_t ws_bytes = host_workspace_bytes(plan, B, (size_t)mp_rrt_connect_workspace_bytes(model->d.n, max_nodes, 1));
   HostCall hc(ctx);  // (h is the collision handle)
@@ -3233,7 +3268,7 @@ static int path_shortcut_impl(const char* fn, mp_ctx* ctx, const mp_model* model
   PROFILE_SCOPE(ctx, fn);
   MpQueuePlan plan;
   if (made) plan = *made;
-  else HIP_TRY(mpk_queue_plan(MP_QUEUE_SHORTCUT, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  else HIP_TRY(mpk_queue_plan(MP_QUEUE_SHORTCUT, model->d.n, h->sph.S, collision_has_cloud(ctx, h), ctx->compute_units, &plan));
   HIP_TRY(mpk_path_shortcut(ctx->compute, model->d, collision_device(h, R), d_in, d_count_in, (long)B, P, d_status, d_count, d_wp,
                             d_len_in, d_len_out, d_iters, d_accepted, d_full, d_evals, static_cast<double*>(d_ws),
                             queue_grid(plan, B, max_blocks, ws_bytes / block_bytes), plan.lds));
@@ -3268,7 +3303,7 @@ int mp_path_shortcut_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* 
   if (B == 0) return MP_OK;
   REQUIRE(waypoints_in && count_in, "%s: null host pointer", fn);
   MpQueuePlan plan;
-  HIP_TRY(mpk_queue_plan(MP_QUEUE_SHORTCUT, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_queue_plan(MP_QUEUE_SHORTCUT, model->d.n, h->sph.S, collision_has_cloud_locked(ctx, h), ctx->compute_units, &plan));
   const size_t n = (size_t)model->d.n, ib = (size_t)B * sizeof(int32_t), db = (size_t)B * sizeof(double);
   const size_t ws_bytes = host_workspace_bytes(plan, B, (size_t)mp_path_shortcut_workspace_bytes(model->d.n, max_waypoints, 1));
   HostCall hc(ctx);  // (h is the collision handle)
@@ -3304,7 +3339,7 @@ static int goal_ik_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_c
   if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
   PROFILE_SCOPE(ctx, fn);
   MpQueuePlan plan;
-  HIP_TRY(mpk_queue_plan(MP_QUEUE_GOAL, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_queue_plan(MP_QUEUE_GOAL, model->d.n, h->sph.S, collision_has_cloud(ctx, h), ctx->compute_units, &plan));
   HIP_TRY(mpk_goal_ik(ctx->compute, model->d, collision_device(h, R), d_Tg, d_q0, (long)B, P, d_status, d_q, d_attempts, d_iters, d_conv,
                       d_pose, d_clear, d_witness, queue_grid(plan, B, max_blocks), plan.lds));
   return MP_OK;
@@ -3377,7 +3412,7 @@ static int path_blend_impl(const char* fn, mp_ctx* ctx, const mp_model* model, m
   if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
   PROFILE_SCOPE(ctx, fn);
   MpQueuePlan plan;
-  HIP_TRY(mpk_queue_plan(MP_QUEUE_BLEND, model->d.n, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_queue_plan(MP_QUEUE_BLEND, model->d.n, h->sph.S, collision_has_cloud(ctx, h), ctx->compute_units, &plan));
   HIP_TRY(mpk_path_blend(ctx->compute, model->d, collision_device(h, R), d_in, d_count_in, (long)B, P, d_status, d_corner, d_count, d_points,
                          d_cut, d_knot, d_length, d_halvings, d_evals, d_clear, queue_grid(plan, B, max_blocks), plan.lds));
   if (grid)
@@ -3459,7 +3494,7 @@ static int cartesian_path_impl(const char* fn, mp_ctx* ctx, const mp_model* mode
   if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
   PROFILE_SCOPE(ctx, fn);
   MpQueuePlan plan;
-  HIP_TRY(mpk_cart_plan(model->d.n, P.task, h->sph.S, ctx->compute_units, &plan));
+  HIP_TRY(mpk_cart_plan(model->d.n, P.task, h->sph.S, collision_has_cloud(ctx, h), ctx->compute_units, &plan));
   HIP_TRY(mpk_cartesian_path(ctx->compute, model->d, collision_device(h, R), P, d_q0, d_Tg, (long)B, mp_cart_work(d_ws, (long)B, P.grid), d_q,
                              d_dq, d_ddq, O, queue_grid(plan, B * (P.grid - 1), max_blocks), plan.lds));
   return MP_OK;
@@ -3637,6 +3672,28 @@ int mp_collision_set_world(mp_ctx* ctx, mp_collision* h, int O, const int32_t* k
   if (it != h->resident.end()) return collision_upload_world(ctx, it->second, h->world);
   mp_collision::Resident* R = nullptr;
   return collision_resident(fn, ctx, h, &R);  // (uploads the world with the rest)
+}
+
+int mp_collision_set_cloud(mp_ctx* ctx, mp_collision* h, int64_t M, const double* points, double radius, double d_max, double cell) {
+  const char* fn = "mp_collision_set_cloud";
+  REQUIRE(h, "%s: null collision handle", fn);
+  std::vector<MpCloudPoint> img;
+  if (int rc = mp_cloud_build(fn, M, points, radius, d_max, cell, &img)) return rc;
+  if (!ctx) {
+    std::lock_guard<std::mutex> hl(h->mu);
+    h->cloud.swap(img);
+    return MP_OK;
+  }
+  CTX_ENTER(ctx);
+  REQUIRE(!ctx->capturing, "%s: not allowed while a launch graph is being captured (mp_graph_begin)", fn);
+  std::lock_guard<std::mutex> hl(h->mu);
+  h->cloud.swap(img);
+  auto it = h->resident.find(ctx->uid);
+  mp_collision::Resident* R = nullptr;
+  const int rc = it != h->resident.end() ? collision_upload_cloud(ctx, it->second, h->cloud)
+                                         : collision_resident(fn, ctx, h, &R);  // (uploads the cloud with the rest)
+  if (rc) h->cloud.swap(img);  // the device kept its cloud: so does the twin
+  return rc;
 }
 
 int mp_collision_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q, int64_t rows, double eps_world,

@@ -6,7 +6,10 @@
 //   MpColSpheres   the robot's spheres SORTED BY LINK, centres in link-local coordinates of the compiled frames (mp_model.h), the
 //                  caller's index of each, and first[k] .. first[k + 1] = the run of link k (0 = the fixed base .. n)
 //   MpColPair      the self pairs as SORTED indices (the parked centres are addressed by them), in the caller's order
-//   MpColWorld     the obstacle count, followed by the obstacles (kind + 16 doubles each)
+//   MpColWorld     the obstacle count and the point cloud's address (null: none), followed by the obstacles (kind + 16 doubles each)
+// The point cloud (mp_cloud.h) is one more obstacle after the O primitives: its header is wave-uniform too, its cells and records are
+// per-lane gathers.  Only tables whose CL parameter names the cloud's pointer types carry the query (MpColTables::has_cloud): the
+// kernels have an instance with and one without, and a launch on a handle without a cloud runs the code it ran before there were clouds.
 //
 // Per row: the FK sweep of mp_fk_jac, unrolled over the links.  At link k the Jacobian column of joint k is kept, and every sphere of
 // the link's run gets its world centre c = p_k + R_k c_local, is parked (PARK: LDS [sphere][xyz][lane] in the kernel, a local array
@@ -22,6 +25,8 @@
 constexpr int MP_COL_MAX_SPHERES = 64;
 constexpr int MP_COL_SPHERE = 0, MP_COL_CAPSULE = 1, MP_COL_BOX = 2;  // = MP_OBSTACLE_* of the public header
 #define MP_COL_TINY 1e-300  // a direction shorter than this is n = 0 (coincident centres, a point on a capsule's axis)
+
+#include "mp_cloud.h"
 
 struct MpColSpheres {
   int S, P;
@@ -41,17 +46,30 @@ struct MpColObstacle {
   int kind, pad;
 };
 struct MpColWorld {  // the header of the obstacle table; MpColObstacle[O] follows at +16 bytes
-  int O, pad[3];
+  int O, pad;
+  const MpColCloud* cloud;  // the point cloud's image (mp_cloud.h), null: none
 };
+static_assert(sizeof(MpColWorld) == 16, "the obstacles follow at +16 bytes");
 
-// views of the tables: SP / PP / WP / OP are pointers, plain on the host and constant-address-space in the kernel
-template <typename SP, typename PP, typename WP, typename OP>
+// views of the tables: SP / PP / WP / OP are pointers, plain on the host and constant-address-space in the kernel; CL: the pointer
+// types of the cloud's image (MpCloudPtrHost, the kernels' own), void for tables that never look for a cloud
+template <typename CL> struct MpColHasCloud { static constexpr bool value = true; };
+template <> struct MpColHasCloud<void> { static constexpr bool value = false; };
+template <typename SP, typename PP, typename WP, typename OP, typename CL = void>
 struct MpColTables {
+  typedef CL Cloud;
+  static constexpr bool has_cloud = MpColHasCloud<CL>::value;
   SP sph;
   PP pairs;
   WP world;
   OP obs;
 };
+// the cloud of tables that can have one (null: none set); wave-uniform
+template <typename TB>
+MP_HD const MpColCloud* mp_col_cloud_of(const TB& tb) {
+  if constexpr (TB::has_cloud) return tb.world->cloud;
+  else return nullptr;
+}
 
 // the park of the world centres
 struct MpColParkLocal {
@@ -199,6 +217,7 @@ MP_HD void mp_collision_row(const MT& M, const TB& tb, const double (&q)[N], dou
   MpJointState<double, N> js;
   mp_joint_state<double, N>(M, q, js);
   const int O = tb.world->O, P = tb.sph->P;
+  const MpColCloud* const cloud = mp_col_cloud_of(tb);
   double Jc[G], W[G];  // per joint [w; v] / per link [moment; force]
 #pragma unroll
   for (int k = 0; k < G; ++k) { Jc[k] = 0.0; W[k] = 0.0; }
@@ -244,6 +263,22 @@ MP_HD void mp_collision_row(const MT& M, const TB& tb, const double (&q)[N], dou
         mp_col_hinge(d, eps_world, phi, dphi);
         cost += phi;
         if (WANT_GRAD) { fx += dphi * nx; fy += dphi * ny; fz += dphi * nz; }
+      }
+      if constexpr (TB::has_cloud) {
+        if (cloud != nullptr) {  // the cloud: obstacle O + its point's index, O + M where truncated; one hinge term
+          double sd, nx, ny, nz;
+          int pt;
+          mp_cloud_distance<typename TB::Cloud>(cloud, cx, cy, cz, MP_COL_TINY, sd, nx, ny, nz, pt);
+          const double d = sd - rs;
+          if (d < dw) {
+            dw = d; aws = who; awo = O + pt;
+            if (WANT_GRAD) { wnx = nx; wny = ny; wnz = nz; wcx = cx; wcy = cy; wcz = cz; wlink = i + 1; }
+          }
+          double phi, dphi;
+          mp_col_hinge(d, eps_world, phi, dphi);
+          cost += phi;
+          if (WANT_GRAD) { fx += dphi * nx; fy += dphi * ny; fz += dphi * nz; }
+        }
       }
       if constexpr (WANT_GRAD) {
         W[6 * i] += cy * fz - cz * fy; W[6 * i + 1] += cz * fx - cx * fz; W[6 * i + 2] += cx * fy - cy * fx;
@@ -393,6 +428,7 @@ MP_HD void mp_collision_edge_eval(const MT& M, const TB& tb, const double (&q)[N
   MpJointState<double, N> js;
   mp_joint_state<double, N>(M, q, js);
   const int O = tb.world->O, P = tb.sph->P;
+  const MpColCloud* const cloud = mp_col_cloud_of(tb);
   double dw = inf, tau = inf;
   int aws = -1, awo = -1;
   {
@@ -422,8 +458,18 @@ MP_HD void mp_collision_edge_eval(const MT& M, const TB& tb, const double (&q)[N
         if (d < dw) { dw = d; aws = who; awo = o; }
         dl = d < dl ? d : dl;
       }
+      if constexpr (TB::has_cloud) {
+        if (cloud != nullptr) {
+          double sd, nx, ny, nz;
+          int pt;
+          mp_cloud_distance<typename TB::Cloud>(cloud, cx, cy, cz, MP_COL_TINY, sd, nx, ny, nz, pt);
+          const double d = sd - rs;
+          if (d < dw) { dw = d; aws = who; awo = O + pt; }
+          dl = d < dl ? d : dl;
+        }
+      }
     }
-    if (s1 > s0 && O > 0) {
+    if (s1 > s0 && (O > 0 || cloud != nullptr)) {
       const double Lw = L.get(mp_col_bound_index(0, i + 1));
       const double c = dl - margin;
       if (Lw > 0.0 && c < tau * Lw) tau = c / Lw;

@@ -1087,9 +1087,10 @@ static int col_joint_count(const char* fn, int n) {  // the n of the two workspa
   REQUIRE(n >= 1, "%s: joint count %d below 1", fn, n);
   return n > MP_MAX_DOF ? mp_too_many_joints(fn, n) : MP_OK;
 }
-typedef MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*> MpColTablesHost;
+// (the twins always carry the cloud's query: a null address in the header skips it, and the arithmetic of the rest is the same)
+typedef MpColTables<const MpColSpheres*, const MpColPair*, const MpColWorld*, const MpColObstacle*, MpCloudPtrHost> MpColTablesHost;
 static MpColTablesHost col_host_tables(const mp_collision* h, MpColWorld& hdr) {  // hdr: the caller's, the tables point at it
-  hdr = {(int)h->world.size(), {0, 0, 0}};
+  hdr = {(int)h->world.size(), 0, h->cloud.empty() ? nullptr : reinterpret_cast<const MpColCloud*>(h->cloud.data())};
   return {&h->sph, h->pairs.data(), &hdr, h->world.data()};
 }
 

@@ -115,10 +115,12 @@ struct mp_collision {
   MpColSpheres sph;
   std::vector<MpColPair> pairs;
   std::vector<MpColObstacle> world;   // the _cpu twin's world (and the last one set on any context)
+  std::vector<MpCloudPoint> cloud;    // the point cloud's image (mp_cloud.h: header, cell starts, records), empty: none; as `world`
   struct Resident {
     int device = -1;
     void* sph = nullptr;              // MpColSpheres, then the pairs
     void* world = nullptr;            // MpColWorld, then `cap` obstacles
+    void* cloud = nullptr;            // the cloud's image, null: none (the world table's header holds this address)
     int cap = 0;
     void* counter = nullptr;          // the 8-byte work-queue head of k_collision_edges
     std::vector<void*> retired;       // outgrown world tables that captured graphs may still read
@@ -129,6 +131,10 @@ struct mp_collision {
 };
 // checks an obstacle table and packs it; 0 or an MP_ERR_* code with the message set (mp_cpu.cpp)
 int mp_collision_pack_world(const char* fn, int O, const int32_t* kind, const double* params, std::vector<MpColObstacle>* out);
+// checks a point cloud and builds its image with a counting sort; M = 0 gives the empty image (no cloud); cell <= 0: the default,
+// d_max + radius; 0, or MP_ERR_INVALID with the message set and `image` untouched (mp_cloud_build.cpp)
+int mp_cloud_build(const char* fn, int64_t M, const double* points, double radius, double d_max, double cell,
+                   std::vector<MpCloudPoint>* image);
 // the edge check's parameters: margin finite, tol positive and finite, max_steps in 1..65536; 0 or MP_ERR_INVALID (mp_cpu.cpp)
 int mp_collision_edges_check(const char* fn, double margin, double tol, int max_steps);
 // the planner's parameters (the edge check's among them), packed into `out`; 0, or MP_ERR_INVALID with the message set (mp_cpu.cpp)

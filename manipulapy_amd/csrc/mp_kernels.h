@@ -185,6 +185,7 @@ struct MpColDevice {  // a collision handle's tables on one device, and the 8-by
   const MpColPair* pairs;
   const MpColWorld* world;
   unsigned long long* counter;
+  bool cloud;  // the handle has a point cloud (csrc/mp_cloud.h): the launchers take the kernels' instance that queries it
 };
 hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q, long rows, double eps_world,
                          double eps_self, double* dist_world, int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world,
@@ -201,7 +202,7 @@ struct MpQueuePlan {
   unsigned lds;
   long resident;
 };
-hipError_t mpk_queue_plan(MpQueueKernel kernel, int n, int S, int compute_units, MpQueuePlan* plan);
+hipError_t mpk_queue_plan(MpQueueKernel kernel, int n, int S, bool cloud, int compute_units, MpQueuePlan* plan);
 struct MpColEdgeParams;
 hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q_from, const double* q_to,
                                long edges, const MpColEdgeParams& P, int* status, double* t, int* steps, double* clearance, int* witness,
@@ -235,7 +236,7 @@ hipError_t mpk_path_blend_sample(hipStream_t s, int n, long problems, const MpBl
 struct MpCartParams;
 struct MpCartWork;
 struct MpCartOut;
-hipError_t mpk_cart_plan(int n, int task, int S, int compute_units, MpQueuePlan* plan);
+hipError_t mpk_cart_plan(int n, int task, int S, bool cloud, int compute_units, MpQueuePlan* plan);
 hipError_t mpk_cartesian_path(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const MpCartParams& P, const double* q_start,
                               const double* T_goal, long problems, const MpCartWork& W, double* q, double* dq, double* ddq,
                               const MpCartOut& O, long blocks, unsigned lds);

@@ -430,8 +430,23 @@ typedef const __attribute__((address_space(4))) MpColSpheres MpColSpheresConst;
 typedef const __attribute__((address_space(4))) MpColPair MpColPairConst;
 typedef const __attribute__((address_space(4))) MpColWorld MpColWorldConst;
 typedef const __attribute__((address_space(4))) MpColObstacle MpColObstacleConst;
-typedef MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*> MpColTablesConst;
-__device__ __forceinline__ MpColTablesConst mp_col_tables_const(const MpColSpheres* sph, const MpColPair* pairs, const MpColWorld* world) {
+// The point cloud (mp_cloud.h): the header wave-uniform through the constant address space, cells and records per lane through the
+// global one.  CLOUD = false gives the tables without the query: every sphere-model kernel has both instances, and the launcher takes
+// the one without for a handle that has no cloud (MpColDevice::cloud), so such a launch runs the code it ran before there were clouds.
+struct MpCloudPtrDevice {
+  typedef const __attribute__((address_space(4))) MpColCloud* Header;
+  typedef const __attribute__((address_space(1))) int* Cells;
+  typedef const __attribute__((address_space(1))) MpCloudPoint* Points;
+};
+template <bool CLOUD> struct MpColTablesConstOf {
+  typedef MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*> type;
+};
+template <> struct MpColTablesConstOf<true> {
+  typedef MpColTables<MpColSpheresConst*, MpColPairConst*, MpColWorldConst*, MpColObstacleConst*, MpCloudPtrDevice> type;
+};
+template <bool CLOUD>
+__device__ __forceinline__ typename MpColTablesConstOf<CLOUD>::type mp_col_tables_const(const MpColSpheres* sph, const MpColPair* pairs,
+                                                                                        const MpColWorld* world) {
   return {(MpColSpheresConst*)sph, (MpColPairConst*)pairs, (MpColWorldConst*)world, (MpColObstacleConst*)(world + 1)};
 }
 // The scaffold of the one-wave work-queue kernels on the sphere model (k_collision_edges, k_rrt_connect, k_path_shortcut, k_goal_ik, k_path_blend; DESIGN
@@ -458,7 +473,7 @@ struct MpWaveOpsLanes {
   __device__ __forceinline__ bool wave_any(bool b) const { return __any(b ? 1 : 0) != 0; }
 };
 
-template <int N, bool WANT_GRAD>
+template <int N, bool WANT_GRAD, bool CLOUD>
 __global__ __launch_bounds__(64) void k_collision(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                   const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                   const double* __restrict__ q, long rows, double eps_world, double eps_self,
@@ -489,7 +504,7 @@ __global__ __launch_bounds__(64) void k_collision(const MpModel<double> M, const
   }
   MpBad<double> bad;
   bad.add(a);
-  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  const auto tb = mp_col_tables_const<CLOUD>(sph, pairs, world);
   MpColParkLanes park{mp_col_park + lane};
   MpColRow<N> o;
   mp_collision_row<N, WANT_GRAD>(M, tb, a, eps_world, eps_self, park, o);
@@ -514,7 +529,7 @@ __global__ __launch_bounds__(64) void k_collision(const MpModel<double> M, const
 // of the lane's own edge, and a finished lane writes its row and fetches another - iteration counts run from 1 to a few hundred between
 // neighbouring edges.  The loop ends because the counter only grows and every edge ends within max_steps.  Dynamic LDS: the park and
 // the speed bounds (mp_col_queue_lanes).  The 2 n inputs of an edge are plain per-lane loads.
-template <int N>
+template <int N, bool CLOUD>
 __global__ __launch_bounds__(64) void k_collision_edges(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                         const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                         const double* __restrict__ q_from, const double* __restrict__ q_to, long edges,
@@ -523,7 +538,7 @@ __global__ __launch_bounds__(64) void k_collision_edges(const MpModel<double> M,
                                                         int* __restrict__ witness, unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_col_edge_lds[];
   const int lane = (int)threadIdx.x;
-  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  const auto tb = mp_col_tables_const<CLOUD>(sph, pairs, world);
   MpColQueueLanes Q = mp_col_queue_lanes(mp_col_edge_lds, lane, tb.sph->S);
   MpColEdgeState<N> S;
   bool have = false;
@@ -571,7 +586,7 @@ struct MpRrtTreeLanes : MpWaveOpsLanes {
   __device__ __forceinline__ void set_parent(int tree, int v, int p) { parents[((long)tree * max_nodes + v) * 64] = p; }
 };
 
-template <int N>
+template <int N, bool CLOUD>
 __global__ __launch_bounds__(64) void k_rrt_connect(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                     const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                     const double* __restrict__ q_start, const double* __restrict__ q_goal, long problems,
@@ -581,7 +596,7 @@ __global__ __launch_bounds__(64) void k_rrt_connect(const MpModel<double> M, con
                                                     unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_rrt_lds[];
   const int lane = (int)threadIdx.x;
-  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  const auto tb = mp_col_tables_const<CLOUD>(sph, pairs, world);
   MpColQueueLanes Q = mp_col_queue_lanes(mp_rrt_lds, lane, tb.sph->S);
   const size_t node_words = (size_t)2 * (size_t)P.max_nodes * N * 64;                  // doubles a block
   const size_t block_words = node_words + (size_t)P.max_nodes * 64;                   // + 2 max_nodes 64 int32
@@ -639,7 +654,7 @@ struct MpShortcutPathLanes : MpWaveOpsLanes {
   __device__ __forceinline__ void set_len(int w, double x) { cum[(long)w * 64] = x; }
 };
 
-template <int N>
+template <int N, bool CLOUD>
 __global__ __launch_bounds__(64) void k_path_shortcut(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                       const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                       const double* __restrict__ waypoints_in, const int* __restrict__ count_in,
@@ -651,7 +666,7 @@ __global__ __launch_bounds__(64) void k_path_shortcut(const MpModel<double> M, c
                                                       double* __restrict__ workspace, unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_shortcut_lds[];
   const int lane = (int)threadIdx.x;
-  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  const auto tb = mp_col_tables_const<CLOUD>(sph, pairs, world);
   MpColQueueLanes Q = mp_col_queue_lanes(mp_shortcut_lds, lane, tb.sph->S);
   const size_t point_words = (size_t)P.max_waypoints * N * 64;           // doubles a block
   const size_t block_words = point_words + (size_t)P.max_waypoints * 64;  // + the lengths
@@ -700,7 +715,7 @@ __global__ __launch_bounds__(64) void k_path_shortcut(const MpModel<double> M, c
 // All of a problem's state is in registers: no workspace.  The loop of the kernel ends for the whole wave at once, when no lane holds
 // a problem and the queue is empty; it ends because the counter only grows and every problem ends within
 // max_attempts (max_iters + 2) trips.
-template <int N>
+template <int N, bool CLOUD>
 __global__ __launch_bounds__(64) void k_goal_ik(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                 const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                 const double* __restrict__ T_goal, const double* __restrict__ q_seed, long problems,
@@ -710,7 +725,7 @@ __global__ __launch_bounds__(64) void k_goal_ik(const MpModel<double> M, const M
                                                 int* __restrict__ witness, unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_goal_lds[];
   const int lane = (int)threadIdx.x;
-  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  const auto tb = mp_col_tables_const<CLOUD>(sph, pairs, world);
   MpColQueueLanes Q = mp_col_queue_lanes(mp_goal_lds, lane, tb.sph->S);
   const MpWaveOpsLanes W{};
   MpGoalState<N> S;
@@ -750,7 +765,7 @@ __global__ __launch_bounds__(64) void k_goal_ik(const MpModel<double> M, const M
 // (mp_col_queue_lanes).  A problem's state is its corner, in registers; the next corner is read from the lane's own input rows: no
 // workspace.  The loop of the kernel ends for the whole wave at once, when no lane holds a problem and the queue is empty; it ends
 // because the counter only grows and every problem ends within (count_in - 2) (max_halvings + 1) max_steps trips.
-template <int N>
+template <int N, bool CLOUD>
 __global__ __launch_bounds__(64) void k_path_blend(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                    const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                    const double* __restrict__ waypoints_in, const int* __restrict__ count_in,
@@ -761,7 +776,7 @@ __global__ __launch_bounds__(64) void k_path_blend(const MpModel<double> M, cons
                                                    double* __restrict__ clearance, unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_blend_lds[];
   const int lane = (int)threadIdx.x;
-  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  const auto tb = mp_col_tables_const<CLOUD>(sph, pairs, world);
   MpColQueueLanes Q = mp_col_queue_lanes(mp_blend_lds, lane, tb.sph->S);
   const MpWaveOpsLanes W{};
   MpBlendState<N> S;
@@ -850,7 +865,7 @@ __global__ __launch_bounds__(64) void k_cart_track(const MpModel<double> M, cons
 // span's two grid rows are re-read from memory every trip (mp_ts_hermite reads them in place): the state in registers is u, the
 // clearance and two counters.  Dynamic LDS: the park and the speed bounds (mp_col_queue_lanes).  No wave-wide step: a lane leaves when
 // the queue is dry.  The loop ends because the counter only grows and every span ends within max_steps trips.
-template <int N, int MR>
+template <int N, int MR, bool CLOUD>
 __global__ __launch_bounds__(64) void k_cart_span(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                   const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                   const MpCartParams P, const double* __restrict__ T_goal, long problems,
@@ -858,7 +873,7 @@ __global__ __launch_bounds__(64) void k_cart_span(const MpModel<double> M, const
                                                   const double* __restrict__ ddq, unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_cart_lds[];
   const int lane = (int)threadIdx.x;
-  const MpColTablesConst tb = mp_col_tables_const(sph, pairs, world);
+  const auto tb = mp_col_tables_const<CLOUD>(sph, pairs, world);
   MpColQueueLanes Q = mp_col_queue_lanes(mp_cart_lds, lane, tb.sph->S);
   const long per = (long)(P.grid - 1), spans = problems * per;
   const double nm1 = (double)(P.grid - 1);
@@ -1746,15 +1761,15 @@ hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, const MpColDev
   if (D.S < 1 || D.S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
   const unsigned park = (unsigned)D.S * 3u * kWave * (unsigned)sizeof(double);
   const bool want_grad = grad_dist_world != nullptr || grad_dist_self != nullptr || grad != nullptr;
-  MP_DISPATCH_N(M.n, MP_FLAG(want_grad, WG, {
+  MP_DISPATCH_N(M.n, MP_FLAG(want_grad, WG, MP_FLAG(D.cloud, CLOUD, {
     if (park + MP_WAVE_LDS_BYTES > 64u * 1024u) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_collision<N, WG>),
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_collision<N, WG, CLOUD>),
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)park);
       if (e != hipSuccess) return e;
     }
-    return launch(k_collision<N, WG>, mp_grid(rows, kWave), kWave, park, s, M, D.sph, D.pairs, D.world, q, rows, eps_world, eps_self,
-                  dist_world, arg_world, dist_self, arg_self, grad_dist_world, grad_dist_self, cost, grad);
-  }))
+    return launch(k_collision<N, WG, CLOUD>, mp_grid(rows, kWave), kWave, park, s, M, D.sph, D.pairs, D.world, q, rows, eps_world,
+                  eps_self, dist_world, arg_world, dist_self, arg_self, grad_dist_world, grad_dist_self, cost, grad);
+  })))
 }
 
 // The launch plan of a one-wave work-queue kernel on the sphere model: its dynamic LDS (beyond the default limit the kernel's own
@@ -1775,17 +1790,17 @@ static hipError_t queue_plan(K kernel, int n, int S, int compute_units, MpQueueP
   return hipSuccess;
 }
 
-hipError_t mpk_queue_plan(MpQueueKernel kernel, int n, int S, int compute_units, MpQueuePlan* plan) {
+hipError_t mpk_queue_plan(MpQueueKernel kernel, int n, int S, bool cloud, int compute_units, MpQueuePlan* plan) {
   if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
-  MP_DISPATCH_N(n, {
+  MP_DISPATCH_N(n, MP_FLAG(cloud, CLOUD, {
     switch (kernel) {
-      case MP_QUEUE_EDGES: return queue_plan(&k_collision_edges<N>, N, S, compute_units, plan);
-      case MP_QUEUE_RRT: return queue_plan(&k_rrt_connect<N>, N, S, compute_units, plan);
-      case MP_QUEUE_SHORTCUT: return queue_plan(&k_path_shortcut<N>, N, S, compute_units, plan);
-      case MP_QUEUE_GOAL: return queue_plan(&k_goal_ik<N>, N, S, compute_units, plan);
-      case MP_QUEUE_BLEND: return queue_plan(&k_path_blend<N>, N, S, compute_units, plan);
+      case MP_QUEUE_EDGES: return queue_plan(&k_collision_edges<N, CLOUD>, N, S, compute_units, plan);
+      case MP_QUEUE_RRT: return queue_plan(&k_rrt_connect<N, CLOUD>, N, S, compute_units, plan);
+      case MP_QUEUE_SHORTCUT: return queue_plan(&k_path_shortcut<N, CLOUD>, N, S, compute_units, plan);
+      case MP_QUEUE_GOAL: return queue_plan(&k_goal_ik<N, CLOUD>, N, S, compute_units, plan);
+      case MP_QUEUE_BLEND: return queue_plan(&k_path_blend<N, CLOUD>, N, S, compute_units, plan);
     }
-  })
+  }))
   return hipErrorInvalidValue;
 }
 
@@ -1802,8 +1817,9 @@ hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, const Mp
   if (edges <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
-  MP_DISPATCH_N(M.n, return launch(k_collision_edges<N>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, q_from, q_to, edges,
-                                   P, status, t, steps, clearance, witness, D.counter))
+  MP_DISPATCH_N(M.n, MP_FLAG(D.cloud, CLOUD,
+      return launch(k_collision_edges<N, CLOUD>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, q_from, q_to, edges, P,
+                    status, t, steps, clearance, witness, D.counter)))
 }
 
 hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q_start, const double* q_goal,
@@ -1812,8 +1828,9 @@ hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, const MpColD
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
-  MP_DISPATCH_N(M.n, return launch(k_rrt_connect<N>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, q_start, q_goal, problems,
-                                   P, status, count, waypoints, iterations, nodes, evaluations, workspace, D.counter))
+  MP_DISPATCH_N(M.n, MP_FLAG(D.cloud, CLOUD,
+      return launch(k_rrt_connect<N, CLOUD>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, q_start, q_goal, problems, P,
+                    status, count, waypoints, iterations, nodes, evaluations, workspace, D.counter)))
 }
 
 hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
@@ -1823,9 +1840,10 @@ hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, const MpCo
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
-  MP_DISPATCH_N(M.n, return launch(k_path_shortcut<N>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
-                                   problems, P, status, count, waypoints, length_in, length_out, iterations, accepted, skipped_full,
-                                   evaluations, workspace, D.counter))
+  MP_DISPATCH_N(M.n, MP_FLAG(D.cloud, CLOUD,
+      return launch(k_path_shortcut<N, CLOUD>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
+                    problems, P, status, count, waypoints, length_in, length_out, iterations, accepted, skipped_full, evaluations, workspace,
+                    D.counter)))
 }
 
 hipError_t mpk_goal_ik(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* T_goal, const double* q_seed,
@@ -1834,8 +1852,9 @@ hipError_t mpk_goal_ik(hipStream_t s, const MpModel<double>& M, const MpColDevic
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
-  MP_DISPATCH_N(M.n, return launch(k_goal_ik<N>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, T_goal, q_seed, problems, P,
-                                   status, q, attempts, iterations, converged, pose_error, clearance, witness, D.counter))
+  MP_DISPATCH_N(M.n, MP_FLAG(D.cloud, CLOUD,
+      return launch(k_goal_ik<N, CLOUD>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, T_goal, q_seed, problems, P,
+                    status, q, attempts, iterations, converged, pose_error, clearance, witness, D.counter)))
 }
 
 hipError_t mpk_path_blend(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
@@ -1844,9 +1863,9 @@ hipError_t mpk_path_blend(hipStream_t s, const MpModel<double>& M, const MpColDe
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
-  MP_DISPATCH_N(M.n, return launch(k_path_blend<N>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
-                                   problems, P, status, corner, count, points, cut, knot, length, halvings, evaluations, clearance,
-                                   D.counter))
+  MP_DISPATCH_N(M.n, MP_FLAG(D.cloud, CLOUD,
+      return launch(k_path_blend<N, CLOUD>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
+                    problems, P, status, corner, count, points, cut, knot, length, halvings, evaluations, clearance, D.counter)))
 }
 
 hipError_t mpk_path_blend_sample(hipStream_t s, int n, long problems, const MpBlendParams& P, const int* status, const int* count,
@@ -1874,10 +1893,11 @@ static hipError_t cart_dispatch(int n, int task, F f) {
   }
 }
 
-hipError_t mpk_cart_plan(int n, int task, int S, int compute_units, MpQueuePlan* plan) {
+hipError_t mpk_cart_plan(int n, int task, int S, bool cloud, int compute_units, MpQueuePlan* plan) {
   if (S < 1 || S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
   return cart_dispatch(n, task, [&](auto cn, auto cm) {
-    return queue_plan(&k_cart_span<decltype(cn)::value, decltype(cm)::value>, decltype(cn)::value, S, compute_units, plan);
+    MP_FLAG(cloud, CLOUD, return queue_plan(&k_cart_span<decltype(cn)::value, decltype(cm)::value, CLOUD>, decltype(cn)::value, S,
+                                            compute_units, plan))
   });
 }
 
@@ -1893,8 +1913,9 @@ hipError_t mpk_cartesian_path(hipStream_t s, const MpModel<double>& M, const MpC
     constexpr int N = decltype(cn)::value, MR = decltype(cm)::value;
     const hipError_t t = launch(k_cart_track<N, MR>, mp_grid(problems, kWave), kWave, 0, s, M, P, q_start, T_goal, problems, W, q, dq, ddq);
     if (t != hipSuccess) return t;
-    return launch(k_cart_span<N, MR>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, P, T_goal, problems, W, q, dq, ddq,
-                  D.counter);
+    MP_FLAG(D.cloud, CLOUD,
+        return launch(k_cart_span<N, MR, CLOUD>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, P, T_goal, problems, W, q,
+                      dq, ddq, D.counter))
   });
   if (e != hipSuccess) return e;
   return launch(k_cart_reduce, mp_grid(problems, kWave), kWave, 0, s, problems, P.grid, W, O);

@@ -527,8 +527,9 @@ class OptimizedTrajectoryPlanning:
         return {k: v[0] for k, v in r.items()}
 
     def batch_trajectory_clearance(self, positions, collision_model, margin: float = 0.0) -> Dict[str, np.ndarray]:
-        """Clearance of B trajectories (B, N, n) under a collision.SphereCollisionModel (whose world is the one last given to its
-        set_world): {"world_clearance", "self_clearance": (B,) the smallest signed distance along each trajectory (+inf where the
+        """Clearance of B trajectories (B, N, n) under a collision.SphereCollisionModel (whose world is the obstacle table last given
+        to its set_world together with the point cloud last given to its set_cloud, if any - here and in every function of this
+        planner that takes a collision model): {"world_clearance", "self_clearance": (B,) the smallest signed distance along each trajectory (+inf where the
         model has no obstacle / no pair), "world_step", "self_step": (B,) the first step at which it occurs, "first_violation": (B,)
         the first step whose world or self clearance is below `margin`, -1 if there is none}.  A trajectory with a non-finite row
         reports NaN clearances.  One row-parallel launch; the reduction over the steps is done on the host."""
@@ -557,7 +558,8 @@ class OptimizedTrajectoryPlanning:
         check_edges), all B (W - 1) segments in one launch.  {"free": (B,) every segment proven free (an UNDECIDED or INVALID segment
         counts as not free), "first_blocked_segment": (B,) the first segment that is not free, -1 if none, "blocked_at": (B,) that
         segment's index + its t (NaN for a free path or an invalid segment), "segment_status": (B, W - 1), "clearance": (B,) the
-        smallest clearance over the configurations evaluated on the path (NaN with an invalid segment)}."""
+        smallest clearance over the configurations evaluated on the path (NaN with an invalid segment)}.
+        The collision model's world is its obstacle table and its point cloud (SphereCollisionModel.set_cloud), if one is set."""
         wp = np.asarray(waypoints, dtype=np.float64)
         n = collision_model.n
         if wp.ndim != 3 or wp.shape[2] != n or wp.shape[1] < 2:
@@ -582,7 +584,8 @@ class OptimizedTrajectoryPlanning:
         """Collision-free piecewise-linear joint-space paths for B (start, goal) pairs (B, n) under a collision.SphereCollisionModel,
         by bidirectional RRT-Connect (SphereCollisionModel.plan_paths), all B problems in one launch.  The sampling box is this
         planner's joint limits, an open or non-finite limit clipped to +-`finite_limit`.  {"status", "count", "waypoints" (B,
-        max_waypoints, n), "iterations", "nodes", "evaluations"}: "waypoints" can go straight into `batch_validate_path`."""
+        max_waypoints, n), "iterations", "nodes", "evaluations"}: "waypoints" can go straight into `batch_validate_path`.
+        The collision model's world is its obstacle table and its point cloud (SphereCollisionModel.set_cloud), if one is set."""
         sb, gb = np.asarray(start, dtype=np.float64), np.asarray(goal, dtype=np.float64)
         n = collision_model.n
         if sb.ndim != 2 or sb.shape != gb.shape or sb.shape[1] != n:
@@ -598,7 +601,8 @@ class OptimizedTrajectoryPlanning:
         "waypoints" and "count" - by randomised shortcutting under a collision.SphereCollisionModel (SphereCollisionModel.
         shortcut_paths), all B paths in one launch.  {"status", "count", "waypoints" (B, max_waypoints or W, n), "length_in",
         "length_out", "iterations", "accepted", "skipped_full", "evaluations"}: rows that were not solved come back skipped, and
-        "waypoints" can go straight into `batch_validate_path`.  The input paths themselves are not checked."""
+        "waypoints" can go straight into `batch_validate_path`.  The input paths themselves are not checked.
+        The collision model's world is its obstacle table and its point cloud (SphereCollisionModel.set_cloud), if one is set."""
         wp = np.asarray(waypoints, dtype=np.float64)
         cnt = np.asarray(count)
         n = collision_model.n
@@ -615,7 +619,8 @@ class OptimizedTrajectoryPlanning:
         (SphereCollisionModel.blend_paths) and samples them on N grid points, all B paths in one call.  {"status", "corner", "count",
         "points", "cut", "knot", "length", "halvings", "evaluations", "clearance", "q", "dq", "ddq" (B, N, n)}: rows that were not
         solved come back skipped, and "q", "dq", "ddq" go straight into `batch_time_optimal_parameterization`.  The input paths
-        themselves are not checked."""
+        themselves are not checked.
+        The collision model's world is its obstacle table and its point cloud (SphereCollisionModel.set_cloud), if one is set."""
         wp = np.asarray(waypoints, dtype=np.float64)
         cnt = np.asarray(count)
         n = collision_model.n
@@ -720,7 +725,8 @@ class OptimizedTrajectoryPlanning:
         jump, 5 blocked, 6 undecided, -1 invalid), "reached", "span", "t", "clearance", "deviation_pos", "deviation_rot",
         "pose_error", "iterations", "evaluations", "q", "dq", "ddq" (B, N, n), "span_status", "span_clearance" (B, N - 1)}: "q",
         "dq", "ddq" of a done row go straight into `batch_time_optimal_parameterization` and `batch_sample_time_optimal(path=...)`,
-        whose samples lie on the curve that was proven free."""
+        whose samples lie on the curve that was proven free.
+        The collision model's world is its obstacle table and its point cloud (SphereCollisionModel.set_cloud), if one is set."""
         q0, Tg = np.asarray(q_start, dtype=np.float64), np.asarray(T_goal, dtype=np.float64)
         n = collision_model.n
         if q0.ndim != 2 or q0.shape[1] != n or Tg.shape != (q0.shape[0], 4, 4):
@@ -789,7 +795,8 @@ class OptimizedTrajectoryPlanning:
         collision.SphereCollisionModel (SphereCollisionModel.goal_configurations), all B problems in one launch.  The box is this
         planner's joint limits, clipped as `batch_plan_path` clips its sampling box.  {"status" (0 found, 1 in collision, 2
         unreached, -1 invalid), "q" (B, n), "attempts", "iterations", "converged", "pose_error" (B, 2), "clearance", "witness"
-        (B, 3)}: "q" can go straight into `batch_plan_path` as the goal."""
+        (B, 3)}: "q" can go straight into `batch_plan_path` as the goal.
+        The collision model's world is its obstacle table and its point cloud (SphereCollisionModel.set_cloud), if one is set."""
         Tg, q0 = np.asarray(T_goal, dtype=np.float64), np.asarray(q_seed, dtype=np.float64)
         n = collision_model.n
         if q0.ndim != 2 or q0.shape[1] != n or Tg.shape != (q0.shape[0], 4, 4):
