@@ -30,12 +30,25 @@ struct MpBlendParams {
   int max_halvings, w_in, grid, pad;  // w_in: the rows of an input path; grid: the grid points N
 };
 
+// the per-problem outputs of the work-queue kernel, any of them null (the grid's q, dq, ddq are sampled from them afterwards)
+struct MpBlendOut {
+  int *status, *corner, *count;
+  double* points;    // (B, w_in, n)
+  double *cut, *knot;  // (B, w_in)
+  double* length;
+  int *halvings, *evaluations;
+  double* clearance;
+};
 // the outputs a problem writes while it runs: its rows of `points`, `cut`, `knot`, any of them null
 struct MpBlendRows {
   double* points;
   double* cut;
   double* knot;
 };
+MP_HD MpBlendRows mp_blend_rows(const MpBlendOut& O, long row, int w_in, int n) {
+  return {O.points ? O.points + row * (long)w_in * n : nullptr, O.cut ? O.cut + row * (long)w_in : nullptr,
+          O.knot ? O.knot + row * (long)w_in : nullptr};
+}
 
 constexpr int MP_BL_IDLE = 0, MP_BL_RUN = 1, MP_BL_FINISHED = 2;
 
@@ -323,16 +336,29 @@ MP_HD int mp_blend_trip(const MT& M, const TB& tb, const MpBlendParams& P, const
   return S.phase == MP_BL_FINISHED ? 1 : 0;
 }
 
-// One problem over plain host rows, for the CPU twin: S is left as the last trip left it.  o: the problem's rows of points / cut /
-// knot, any of them null.
+// the row a finished problem reports beside what it wrote while it ran, stored by the kernel and the twin alike
+template <int N>
+MP_HD void mp_blend_store(const MpBlendOut& O, long row, const MpBlendState<N>& S) {
+  if (O.status) O.status[row] = S.status;
+  if (O.corner) O.corner[row] = S.corner;
+  if (O.count) O.count[row] = S.m;
+  if (O.length) O.length[row] = S.length;
+  if (O.halvings) O.halvings[row] = S.halvings;
+  if (O.evaluations) O.evaluations[row] = S.evals;
+  if (O.clearance) O.clearance[row] = S.clearance;
+}
+
+// Problem b over plain host rows, for the CPU twin: S is left as the last trip left it.  rows: its input rows; o: its rows of points /
+// cut / knot, any of them null.
 template <int N, typename MT, typename TB>
-void mp_blend_cpu(const MT& M, const TB& tb, const MpBlendParams& P, const double* rows, int count_in, const MpBlendRows& o,
-                  MpBlendState<N>& S) {
+void mp_blend_cpu(const MT& M, const TB& tb, const MpBlendParams& P, const double* rows, int count_in, long b, const MpBlendRows& o,
+                  const MpBlendOut& O, MpBlendState<N>& S) {
   MpColParkLocal park;
   MpColBoundsLocal<N> L;
   S.phase = MP_BL_IDLE;
   mp_blend_begin<N>(M, tb.sph, P, rows, count_in, S, L, o);
   while (!mp_blend_trip<N>(M, tb, P, rows, count_in, S, park, L, o)) {}
+  mp_blend_store<N>(O, b, S);
 }
 
 // Grid point i of a finished problem: q, dq/ds, d2q/ds2 at s_i = i / (grid - 1).  points / cut / knot: the problem's rows.

@@ -136,7 +136,6 @@ int hip_err(hipError_t e, const char* what) {
     if (e_ != hipSuccess) return hip_err(e_, #expr);    \
   } while (0)
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 int bind(mp_ctx* ctx) {
   HIP_TRY(hipSetDevice(ctx->device));
   return MP_OK;
@@ -3090,40 +3089,34 @@ static size_t host_workspace_bytes(const MpQueuePlan& plan, int64_t B, size_t bl
 }
 
 static int collision_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q, int64_t rows,
-                          double eps_world, double eps_self, double* d_dw, int32_t* d_aw, double* d_ds, int32_t* d_as, double* d_gdw,
-                          double* d_gds, double* d_cost, double* d_grad) {
+                          double eps_world, double eps_self, const MpColOut& O) {
   CHECK_SPHERE_ENTRY(fn);
   REQUIRE(eps_world > 0.0 && eps_self > 0.0 && std::isfinite(eps_world) && std::isfinite(eps_self),
           "%s: eps_world and eps_self must be positive and finite", fn);
   REQUIRE(rows >= 0, "%s: negative row count", fn);
   if (rows == 0) return MP_OK;
   REQUIRE(d_q, "%s: null device pointer", fn);
-  REQUIRE(d_dw || d_aw || d_ds || d_as || d_gdw || d_gds || d_cost || d_grad, "%s: at least one output is required", fn);
-  REQUIRE(aligned16(d_q) && aligned16(d_dw) && aligned16(d_aw) && aligned16(d_ds) && aligned16(d_as) && aligned16(d_gdw) &&
-              aligned16(d_gds) && aligned16(d_cost) && aligned16(d_grad),
-          "%s: device pointers must be 16-byte aligned", fn);
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_q) && mp_out_aligned16(O), "%s: device pointers must be 16-byte aligned", fn);
   std::lock_guard<std::mutex> hl(h->mu);
   mp_collision::Resident* R = nullptr;
   if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
   PROFILE_SCOPE(ctx, fn);
-  HIP_TRY(mpk_collision(ctx->compute, model->d, collision_device(h, R), d_q, (long)rows, eps_world, eps_self, d_dw, d_aw, d_ds, d_as,
-                        d_gdw, d_gds, d_cost, d_grad));
+  HIP_TRY(mpk_collision(ctx->compute, model->d, collision_device(h, R), d_q, (long)rows, eps_world, eps_self, O));
   return MP_OK;
 }
 
 static int collision_edges_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_qa,
                                 const double* d_qb, int64_t edges, double margin, double tol, int max_steps, int max_blocks,
-                                int32_t* d_status, double* d_t, int32_t* d_steps, double* d_clear, int32_t* d_witness) {
+                                const MpColEdgeOut& O) {
   CHECK_SPHERE_ENTRY(fn);
   if (int rc = mp_collision_edges_check(fn, margin, tol, max_steps)) return rc;
   REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
   REQUIRE(edges >= 0, "%s: negative edge count", fn);
   if (edges == 0) return MP_OK;
   REQUIRE(d_qa && d_qb, "%s: null device pointer", fn);
-  REQUIRE(d_status || d_t || d_steps || d_clear || d_witness, "%s: at least one output is required", fn);
-  REQUIRE(aligned16(d_qa) && aligned16(d_qb) && aligned16(d_status) && aligned16(d_t) && aligned16(d_steps) && aligned16(d_clear) &&
-              aligned16(d_witness),
-          "%s: device pointers must be 16-byte aligned", fn);
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_qa) && aligned16(d_qb) && mp_out_aligned16(O), "%s: device pointers must be 16-byte aligned", fn);
   std::lock_guard<std::mutex> hl(h->mu);
   mp_collision::Resident* R = nullptr;
   if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
@@ -3131,8 +3124,8 @@ static int collision_edges_impl(const char* fn, mp_ctx* ctx, const mp_model* mod
   const MpColEdgeParams P = {margin, tol, max_steps, 0};
   MpQueuePlan plan;
   HIP_TRY(mpk_queue_plan(MP_QUEUE_EDGES, model->d.n, h->sph.S, collision_has_cloud(ctx, h), ctx->compute_units, &plan));
-  HIP_TRY(mpk_collision_edges(ctx->compute, model->d, collision_device(h, R), d_qa, d_qb, (long)edges, P, d_status, d_t, d_steps, d_clear,
-                              d_witness, queue_grid(plan, edges, max_blocks), plan.lds));
+  HIP_TRY(mpk_collision_edges(ctx->compute, model->d, collision_device(h, R), d_qa, d_qb, (long)edges, P, O,
+                              queue_grid(plan, edges, max_blocks), plan.lds));
   return MP_OK;
 }
 
@@ -3142,7 +3135,7 @@ int mp_collision_edges_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, 
                            double margin, double tol, int max_steps, int max_blocks, int32_t* d_status, double* d_t, int32_t* d_steps,
                            double* d_clearance, int32_t* d_witness) {
   return collision_edges_impl("mp_collision_edges_f64", ctx, model, h, d_q_from, d_q_to, edges, margin, tol, max_steps, max_blocks,
-                              d_status, d_t, d_steps, d_clearance, d_witness);
+                              {d_status, d_t, d_steps, d_clearance, d_witness});
 }
 
 int mp_collision_edges_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q_from, const double* q_to, int64_t edges,
@@ -3156,14 +3149,8 @@ int mp_collision_edges_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision
   const size_t n = (size_t)model->d.n, rb = (size_t)edges * sizeof(double), ib = (size_t)edges * sizeof(int32_t);
   HostCall hc(ctx);  // (h is the collision handle)
   const double *da = hc.in(q_from, n * rb), *db = hc.in(q_to, n * rb);
-  int32_t* dstatus = hc.out(status, ib);
-  double* dt = hc.out(t, rb);
-  int32_t* dsteps = hc.out(steps, ib);
-  double* dclear = hc.out(clearance, rb);
-  int32_t* dwit = hc.out(witness, 3 * ib);
-  return hc.run([&] {
-    return collision_edges_impl(fn, ctx, model, h, da, db, edges, margin, tol, max_steps, 0, dstatus, dt, dsteps, dclear, dwit);
-  });
+  const MpColEdgeOut O = {hc.out(status, ib), hc.out(t, rb), hc.out(steps, ib), hc.out(clearance, rb), hc.out(witness, 3 * ib)};
+  return hc.run([&] { return collision_edges_impl(fn, ctx, model, h, da, db, edges, margin, tol, max_steps, 0, O); });
 }
 
 }  // extern "C"
@@ -3172,15 +3159,13 @@ int mp_collision_edges_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision
 // entry sizes its workspace by it); every entry call makes one.
 static int rrt_connect_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_qs, const double* d_qg,
                             int64_t B, const MpRrtParams& P, void* d_ws, size_t ws_bytes, int max_blocks, const MpQueuePlan* made,
-                            int32_t* d_status, int32_t* d_count, double* d_wp, int32_t* d_iters, int32_t* d_nodes, int32_t* d_evals) {
+                            const MpRrtOut& O) {
   REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
   REQUIRE(d_qs && d_qg, "%s: null device pointer", fn);
-  REQUIRE(d_status || d_count || d_wp || d_iters || d_nodes || d_evals, "%s: at least one output is required", fn);
-  REQUIRE(aligned16(d_qs) && aligned16(d_qg) && aligned16(d_status) && aligned16(d_count) && aligned16(d_wp) && aligned16(d_iters) &&
-              aligned16(d_nodes) && aligned16(d_evals) && aligned16(d_ws),
-          "%s: device pointers must be 16-byte aligned", fn);
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_qs) && aligned16(d_qg) && mp_out_aligned16(O) && aligned16(d_ws), "%s: device pointers must be 16-byte aligned", fn);
   const size_t block_bytes = (size_t)mp_rrt_connect_workspace_bytes(model->d.n, P.max_nodes, 1);
   REQUIRE(d_ws && ws_bytes >= block_bytes, "%s: the workspace holds %zu bytes, one block needs %zu (mp_rrt_connect_workspace_bytes)", fn,
           d_ws ? ws_bytes : (size_t)0, block_bytes);
@@ -3191,8 +3176,8 @@ static int rrt_connect_impl(const char* fn, mp_ctx* ctx, const mp_model* model, 
   MpQueuePlan plan;
   if (made) plan = *made;
   else HIP_TRY(mpk_queue_plan(MP_QUEUE_RRT, model->d.n, h->sph.S, collision_has_cloud(ctx, h), ctx->compute_units, &plan));
-  HIP_TRY(mpk_rrt_connect(ctx->compute, model->d, collision_device(h, R), d_qs, d_qg, (long)B, P, d_status, d_count, d_wp, d_iters,
-                          d_nodes, d_evals, static_cast<double*>(d_ws), queue_grid(plan, B, max_blocks, ws_bytes / block_bytes), plan.lds));
+  HIP_TRY(mpk_rrt_connect(ctx->compute, model->d, collision_device(h, R), d_qs, d_qg, (long)B, P, O, static_cast<double*>(d_ws),
+                          queue_grid(plan, B, max_blocks, ws_bytes / block_bytes), plan.lds));
   return MP_OK;
 }
 
@@ -3209,8 +3194,8 @@ int mp_rrt_connect_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, cons
   if (int rc = mp_rrt_connect_check(fn, model->d.n, lo, hi, seed, step, min_advance, max_iters, max_nodes, max_waypoints, margin, tol,
                                     max_steps, &P))
     return rc;
-  return rrt_connect_impl(fn, ctx, model, h, d_q_start, d_q_goal, B, P, d_workspace, workspace_bytes, max_blocks, nullptr, d_status,
-                          d_count, d_waypoints, d_iterations, d_nodes, d_evaluations);
+  return rrt_connect_impl(fn, ctx, model, h, d_q_start, d_q_goal, B, P, d_workspace, workspace_bytes, max_blocks, nullptr,
+                          {d_status, d_count, d_waypoints, d_iterations, d_nodes, d_evaluations});
 }
 
 int mp_rrt_connect_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q_start, const double* q_goal, int64_t B,
@@ -3232,13 +3217,10 @@ int mp_rrt_connect_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h,
   const size_t ws_bytes = host_workspace_bytes(plan, B, (size_t)mp_rrt_connect_workspace_bytes(model->d.n, max_nodes, 1));
   HostCall hc(ctx);  // (h is the collision handle)
   const double *ds = hc.in(q_start, qb), *dg = hc.in(q_goal, qb);
-  int32_t *dstatus = hc.out(status, ib), *dcount = hc.out(count, ib);
-  double* dwp = hc.out(waypoints, (size_t)B * (size_t)max_waypoints * n * sizeof(double));
-  int32_t *dit = hc.out(iterations, ib), *dnodes = hc.out(nodes, 2 * ib), *dev = hc.out(evaluations, ib);
+  const MpRrtOut O = {hc.out(status, ib), hc.out(count, ib), hc.out(waypoints, (size_t)B * (size_t)max_waypoints * n * sizeof(double)),
+                      hc.out(iterations, ib), hc.out(nodes, 2 * ib), hc.out(evaluations, ib)};
   void* dws = hc.work(ws_bytes);
-  return hc.run([&] {
-    return rrt_connect_impl(fn, ctx, model, h, ds, dg, B, P, dws, ws_bytes, 0, &plan, dstatus, dcount, dwp, dit, dnodes, dev);
-  });
+  return hc.run([&] { return rrt_connect_impl(fn, ctx, model, h, ds, dg, B, P, dws, ws_bytes, 0, &plan, O); });
 }
 
 }  // extern "C"
@@ -3246,19 +3228,14 @@ int mp_rrt_connect_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h,
 // ---- batched path shortcutting over the sphere model (mp_shortcut.h).  `made`: as in rrt_connect_impl.
 static int path_shortcut_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_in,
                               const int32_t* d_count_in, int64_t B, const MpShortcutParams& P, void* d_ws, size_t ws_bytes,
-                              int max_blocks, const MpQueuePlan* made, int32_t* d_status, int32_t* d_count, double* d_wp,
-                              double* d_len_in, double* d_len_out, int32_t* d_iters, int32_t* d_accepted, int32_t* d_full,
-                              int32_t* d_evals) {
+                              int max_blocks, const MpQueuePlan* made, const MpShortcutOut& O) {
   REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
   REQUIRE(d_in && d_count_in, "%s: null device pointer", fn);
-  REQUIRE(d_status || d_count || d_wp || d_len_in || d_len_out || d_iters || d_accepted || d_full || d_evals,
-          "%s: at least one output is required", fn);
-  REQUIRE(aligned16(d_in) && aligned16(d_count_in) && aligned16(d_status) && aligned16(d_count) && aligned16(d_wp) &&
-              aligned16(d_len_in) && aligned16(d_len_out) && aligned16(d_iters) && aligned16(d_accepted) && aligned16(d_full) &&
-              aligned16(d_evals) && aligned16(d_ws),
-          "%s: device pointers must be 16-byte aligned", fn);
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_in) && aligned16(d_count_in) && mp_out_aligned16(O) && aligned16(d_ws), "%s: device pointers must be 16-byte aligned",
+          fn);
   const size_t block_bytes = (size_t)mp_path_shortcut_workspace_bytes(model->d.n, P.max_waypoints, 1);
   REQUIRE(d_ws && ws_bytes >= block_bytes, "%s: the workspace holds %zu bytes, one block needs %zu (mp_path_shortcut_workspace_bytes)", fn,
           d_ws ? ws_bytes : (size_t)0, block_bytes);
@@ -3269,8 +3246,7 @@ static int path_shortcut_impl(const char* fn, mp_ctx* ctx, const mp_model* model
   MpQueuePlan plan;
   if (made) plan = *made;
   else HIP_TRY(mpk_queue_plan(MP_QUEUE_SHORTCUT, model->d.n, h->sph.S, collision_has_cloud(ctx, h), ctx->compute_units, &plan));
-  HIP_TRY(mpk_path_shortcut(ctx->compute, model->d, collision_device(h, R), d_in, d_count_in, (long)B, P, d_status, d_count, d_wp,
-                            d_len_in, d_len_out, d_iters, d_accepted, d_full, d_evals, static_cast<double*>(d_ws),
+  HIP_TRY(mpk_path_shortcut(ctx->compute, model->d, collision_device(h, R), d_in, d_count_in, (long)B, P, O, static_cast<double*>(d_ws),
                             queue_grid(plan, B, max_blocks, ws_bytes / block_bytes), plan.lds));
   return MP_OK;
 }
@@ -3287,8 +3263,8 @@ int mp_path_shortcut_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, co
   MpShortcutParams P;
   if (int rc = mp_path_shortcut_check(fn, W_in, seed, max_iters, min_gain, max_waypoints, margin, tol, max_steps, &P)) return rc;
   return path_shortcut_impl(fn, ctx, model, h, d_waypoints_in, d_count_in, B, P, d_workspace, workspace_bytes, max_blocks, nullptr,
-                            d_status, d_count, d_waypoints, d_length_in, d_length_out, d_iterations, d_accepted, d_skipped_full,
-                            d_evaluations);
+                            {d_status, d_count, d_waypoints, d_length_in, d_length_out, d_iterations, d_accepted, d_skipped_full,
+                             d_evaluations});
 }
 
 int mp_path_shortcut_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* waypoints_in, const int32_t* count_in,
@@ -3309,39 +3285,33 @@ int mp_path_shortcut_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* 
   HostCall hc(ctx);  // (h is the collision handle)
   const double* din = hc.in(waypoints_in, (size_t)B * (size_t)W_in * n * sizeof(double));
   const int32_t* dcin = hc.in(count_in, ib);
-  int32_t *dstatus = hc.out(status, ib), *dcount = hc.out(count, ib);
-  double* dwp = hc.out(waypoints, (size_t)B * (size_t)max_waypoints * n * sizeof(double));
-  double *dli = hc.out(length_in, db), *dlo = hc.out(length_out, db);
-  int32_t *dit = hc.out(iterations, ib), *dacc = hc.out(accepted, ib), *dfull = hc.out(skipped_full, ib), *dev = hc.out(evaluations, ib);
+  const MpShortcutOut O = {hc.out(status, ib), hc.out(count, ib),
+                           hc.out(waypoints, (size_t)B * (size_t)max_waypoints * n * sizeof(double)), hc.out(length_in, db),
+                           hc.out(length_out, db), hc.out(iterations, ib), hc.out(accepted, ib), hc.out(skipped_full, ib),
+                           hc.out(evaluations, ib)};
   void* dws = hc.work(ws_bytes);
-  return hc.run([&] {
-    return path_shortcut_impl(fn, ctx, model, h, din, dcin, B, P, dws, ws_bytes, 0, &plan, dstatus, dcount, dwp, dli, dlo, dit, dacc,
-                              dfull, dev);
-  });
+  return hc.run([&] { return path_shortcut_impl(fn, ctx, model, h, din, dcin, B, P, dws, ws_bytes, 0, &plan, O); });
 }
 
 }  // extern "C"
 
 // ---- goal configurations for pose goals over the sphere model (mp_goal.h): no workspace, so one plan per call, made here
 static int goal_ik_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_Tg, const double* d_q0,
-                        int64_t B, const MpGoalParams& P, int max_blocks, int32_t* d_status, double* d_q, int32_t* d_attempts,
-                        int32_t* d_iters, int32_t* d_conv, double* d_pose, double* d_clear, int32_t* d_witness) {
+                        int64_t B, const MpGoalParams& P, int max_blocks, const MpGoalOut& O) {
   REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
   REQUIRE(d_Tg && d_q0, "%s: null device pointer", fn);
-  REQUIRE(d_status || d_q || d_attempts || d_iters || d_conv || d_pose || d_clear || d_witness, "%s: at least one output is required", fn);
-  REQUIRE(aligned16(d_Tg) && aligned16(d_q0) && aligned16(d_status) && aligned16(d_q) && aligned16(d_attempts) && aligned16(d_iters) &&
-              aligned16(d_conv) && aligned16(d_pose) && aligned16(d_clear) && aligned16(d_witness),
-          "%s: device pointers must be 16-byte aligned", fn);
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
+  REQUIRE(aligned16(d_Tg) && aligned16(d_q0) && mp_out_aligned16(O), "%s: device pointers must be 16-byte aligned", fn);
   std::lock_guard<std::mutex> hl(h->mu);
   mp_collision::Resident* R = nullptr;
   if (int rc = collision_resident(fn, ctx, h, &R)) return rc;
   PROFILE_SCOPE(ctx, fn);
   MpQueuePlan plan;
   HIP_TRY(mpk_queue_plan(MP_QUEUE_GOAL, model->d.n, h->sph.S, collision_has_cloud(ctx, h), ctx->compute_units, &plan));
-  HIP_TRY(mpk_goal_ik(ctx->compute, model->d, collision_device(h, R), d_Tg, d_q0, (long)B, P, d_status, d_q, d_attempts, d_iters, d_conv,
-                      d_pose, d_clear, d_witness, queue_grid(plan, B, max_blocks), plan.lds));
+  HIP_TRY(mpk_goal_ik(ctx->compute, model->d, collision_device(h, R), d_Tg, d_q0, (long)B, P, O, queue_grid(plan, B, max_blocks),
+                      plan.lds));
   return MP_OK;
 }
 
@@ -3357,8 +3327,8 @@ int mp_goal_ik_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const do
   MpGoalParams P;
   if (int rc = mp_goal_ik_check(fn, model->d.n, lo, hi, seed, eomg, ev, damping, step_cap, max_iters, max_attempts, margin, tol, &P))
     return rc;
-  return goal_ik_impl(fn, ctx, model, h, d_T_goal, d_q_seed, B, P, max_blocks, d_status, d_q, d_attempts, d_iterations, d_converged,
-                      d_pose_error, d_clearance, d_witness);
+  return goal_ik_impl(fn, ctx, model, h, d_T_goal, d_q_seed, B, P, max_blocks,
+                      {d_status, d_q, d_attempts, d_iterations, d_converged, d_pose_error, d_clearance, d_witness});
 }
 
 int mp_goal_ik_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* T_goal, const double* q_seed, int64_t B,
@@ -3376,14 +3346,9 @@ int mp_goal_ik_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, con
   const size_t n = (size_t)model->d.n, ib = (size_t)B * sizeof(int32_t), db = (size_t)B * sizeof(double);
   HostCall hc(ctx);  // (h is the collision handle)
   const double *dtg = hc.in(T_goal, 16 * db), *dq0 = hc.in(q_seed, n * db);
-  int32_t* dstatus = hc.out(status, ib);
-  double* dq = hc.out(q, n * db);
-  int32_t *datt = hc.out(attempts, ib), *dit = hc.out(iterations, ib), *dconv = hc.out(converged, ib);
-  double *dpose = hc.out(pose_error, 2 * db), *dclear = hc.out(clearance, db);
-  int32_t* dwit = hc.out(witness, 3 * ib);
-  return hc.run([&] {
-    return goal_ik_impl(fn, ctx, model, h, dtg, dq0, B, P, 0, dstatus, dq, datt, dit, dconv, dpose, dclear, dwit);
-  });
+  const MpGoalOut O = {hc.out(status, ib), hc.out(q, n * db), hc.out(attempts, ib), hc.out(iterations, ib), hc.out(converged, ib),
+                       hc.out(pose_error, 2 * db), hc.out(clearance, db), hc.out(witness, 3 * ib)};
+  return hc.run([&] { return goal_ik_impl(fn, ctx, model, h, dtg, dq0, B, P, 0, O); });
 }
 
 }  // extern "C"
@@ -3391,21 +3356,17 @@ int mp_goal_ik_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, con
 // ---- C2 corner blending of waypoint paths over the sphere model (mp_blend.h): the corners on the work queue, then the grid.  No
 // workspace, so one plan per call, made here
 static int path_blend_impl(const char* fn, mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_in, const int32_t* d_count_in,
-                           int64_t B, const MpBlendParams& P, int max_blocks, int32_t* d_status, int32_t* d_corner, int32_t* d_count,
-                           double* d_points, double* d_cut, double* d_knot, double* d_length, int32_t* d_halvings, int32_t* d_evals,
-                           double* d_clear, double* d_q, double* d_dq, double* d_ddq) {
+                           int64_t B, const MpBlendParams& P, int max_blocks, const MpBlendOut& O, double* d_q, double* d_dq,
+                           double* d_ddq) {
   REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
   REQUIRE(d_in && d_count_in, "%s: null device pointer", fn);
   const bool grid = d_q || d_dq || d_ddq;
-  REQUIRE(d_status || d_corner || d_count || d_points || d_cut || d_knot || d_length || d_halvings || d_evals || d_clear || grid,
-          "%s: at least one output is required", fn);
-  REQUIRE(!grid || (d_status && d_count && d_points && d_cut && d_knot && d_length),
+  REQUIRE(mp_out_any(O) || grid, "%s: at least one output is required", fn);
+  REQUIRE(!grid || (O.status && O.count && O.points && O.cut && O.knot && O.length),
           "%s: q, dq and ddq are sampled from status, count, points, cut, knot and length: all six are required with them", fn);
-  REQUIRE(aligned16(d_in) && aligned16(d_count_in) && aligned16(d_status) && aligned16(d_corner) && aligned16(d_count) &&
-              aligned16(d_points) && aligned16(d_cut) && aligned16(d_knot) && aligned16(d_length) && aligned16(d_halvings) &&
-              aligned16(d_evals) && aligned16(d_clear) && aligned16(d_q) && aligned16(d_dq) && aligned16(d_ddq),
+  REQUIRE(aligned16(d_in) && aligned16(d_count_in) && mp_out_aligned16(O) && aligned16(d_q) && aligned16(d_dq) && aligned16(d_ddq),
           "%s: device pointers must be 16-byte aligned", fn);
   std::lock_guard<std::mutex> hl(h->mu);
   mp_collision::Resident* R = nullptr;
@@ -3413,10 +3374,10 @@ static int path_blend_impl(const char* fn, mp_ctx* ctx, const mp_model* model, m
   PROFILE_SCOPE(ctx, fn);
   MpQueuePlan plan;
   HIP_TRY(mpk_queue_plan(MP_QUEUE_BLEND, model->d.n, h->sph.S, collision_has_cloud(ctx, h), ctx->compute_units, &plan));
-  HIP_TRY(mpk_path_blend(ctx->compute, model->d, collision_device(h, R), d_in, d_count_in, (long)B, P, d_status, d_corner, d_count, d_points,
-                         d_cut, d_knot, d_length, d_halvings, d_evals, d_clear, queue_grid(plan, B, max_blocks), plan.lds));
+  HIP_TRY(mpk_path_blend(ctx->compute, model->d, collision_device(h, R), d_in, d_count_in, (long)B, P, O,
+                         queue_grid(plan, B, max_blocks), plan.lds));
   if (grid)
-    HIP_TRY(mpk_path_blend_sample(ctx->compute, model->d.n, (long)B, P, d_status, d_count, d_points, d_cut, d_knot, d_length, d_q, d_dq,
+    HIP_TRY(mpk_path_blend_sample(ctx->compute, model->d.n, (long)B, P, O.status, O.count, O.points, O.cut, O.knot, O.length, d_q, d_dq,
                                   d_ddq));
   return MP_OK;
 }
@@ -3432,8 +3393,9 @@ int mp_path_blend_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const
   CHECK_SPHERE_ENTRY(fn);
   MpBlendParams P;
   if (int rc = mp_path_blend_check(fn, W_in, N, blend, max_halvings, margin, tol, max_steps, &P)) return rc;
-  return path_blend_impl(fn, ctx, model, h, d_waypoints_in, d_count_in, B, P, max_blocks, d_status, d_corner, d_count, d_points, d_cut,
-                         d_knot, d_length, d_halvings, d_evaluations, d_clearance, d_q, d_dq, d_ddq);
+  return path_blend_impl(fn, ctx, model, h, d_waypoints_in, d_count_in, B, P, max_blocks,
+                         {d_status, d_corner, d_count, d_points, d_cut, d_knot, d_length, d_halvings, d_evaluations, d_clearance}, d_q,
+                         d_dq, d_ddq);
 }
 
 int mp_path_blend_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* waypoints_in, const int32_t* count_in,
@@ -3447,27 +3409,21 @@ int mp_path_blend_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, 
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
   REQUIRE(waypoints_in && count_in, "%s: null host pointer", fn);
-  REQUIRE(status || corner || count || points || cut || knot || length || halvings || evaluations || clearance || q || dq || ddq,
+  const bool grid = q || dq || ddq;
+  REQUIRE(mp_out_any(MpBlendOut{status, corner, count, points, cut, knot, length, halvings, evaluations, clearance}) || grid,
           "%s: at least one output is required", fn);
   const size_t n = (size_t)model->d.n, ib = (size_t)B * sizeof(int32_t), db = (size_t)B * sizeof(double);
   const size_t wb = (size_t)W_in * db, gb = (size_t)N * n * db;
-  const bool grid = q || dq || ddq;
   HostCall hc(ctx);  // (h is the collision handle)
   const double* din = hc.in(waypoints_in, wb * n);
   const int32_t* dcin = hc.in(count_in, ib);
   // the tables the grid reads back stay on the device where the caller did not ask for them
   auto table_i = [&](int32_t* host, size_t bytes) { return host ? hc.out(host, bytes) : (grid ? hc.work<int32_t>(bytes) : nullptr); };
   auto table_d = [&](double* host, size_t bytes) { return host ? hc.out(host, bytes) : (grid ? hc.work<double>(bytes) : nullptr); };
-  int32_t* dstatus = table_i(status, ib);
-  int32_t* dcorner = hc.out(corner, ib);
-  int32_t* dcount = table_i(count, ib);
-  double *dpoints = table_d(points, wb * n), *dcut = table_d(cut, wb), *dknot = table_d(knot, wb), *dlength = table_d(length, db);
-  int32_t *dhalv = hc.out(halvings, ib), *dev = hc.out(evaluations, ib);
-  double *dclear = hc.out(clearance, db), *dq_ = hc.out(q, gb), *ddq_ = hc.out(dq, gb), *dddq_ = hc.out(ddq, gb);
-  return hc.run([&] {
-    return path_blend_impl(fn, ctx, model, h, din, dcin, B, P, 0, dstatus, dcorner, dcount, dpoints, dcut, dknot, dlength, dhalv, dev,
-                           dclear, dq_, ddq_, dddq_);
-  });
+  const MpBlendOut O = {table_i(status, ib), hc.out(corner, ib), table_i(count, ib), table_d(points, wb * n), table_d(cut, wb),
+                        table_d(knot, wb), table_d(length, db), hc.out(halvings, ib), hc.out(evaluations, ib), hc.out(clearance, db)};
+  double *dq_ = hc.out(q, gb), *ddq_ = hc.out(dq, gb), *dddq_ = hc.out(ddq, gb);
+  return hc.run([&] { return path_blend_impl(fn, ctx, model, h, din, dcin, B, P, 0, O, dq_, ddq_, dddq_); });
 }
 
 }  // extern "C"
@@ -3481,10 +3437,8 @@ static int cartesian_path_impl(const char* fn, mp_ctx* ctx, const mp_model* mode
   if (B == 0) return MP_OK;
   REQUIRE(d_q0 && d_Tg, "%s: null device pointer", fn);
   REQUIRE(d_q && d_dq && d_ddq, "%s: q, dq and ddq are what the spans are read from: all three are required", fn);
-  REQUIRE(aligned16(d_q0) && aligned16(d_Tg) && aligned16(O.status) && aligned16(O.reached) && aligned16(O.span) && aligned16(O.t) &&
-              aligned16(O.clearance) && aligned16(O.deviation_pos) && aligned16(O.deviation_rot) && aligned16(O.pose_error) &&
-              aligned16(O.iterations) && aligned16(O.evaluations) && aligned16(d_q) && aligned16(d_dq) && aligned16(d_ddq) &&
-              aligned16(O.span_status) && aligned16(O.span_clearance) && aligned16(d_ws),
+  REQUIRE(aligned16(d_q0) && aligned16(d_Tg) && mp_out_aligned16(O) && aligned16(d_q) && aligned16(d_dq) && aligned16(d_ddq) &&
+              aligned16(d_ws),
           "%s: device pointers must be 16-byte aligned", fn);
   const size_t need = mp_cart_work_bytes((long)B, P.grid);
   REQUIRE(d_ws && ws_bytes >= need, "%s: the workspace holds %zu bytes, the call needs %zu (mp_cartesian_path_workspace_bytes)", fn,
@@ -3534,8 +3488,9 @@ int mp_cartesian_path_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision*
     return rc;
   if (B == 0) return MP_OK;
   REQUIRE(q_start && T_goal, "%s: null host pointer", fn);
-  REQUIRE(status || reached || span || t || clearance || deviation_pos || deviation_rot || pose_error || iterations || evaluations || q ||
-              dq || ddq || span_status || span_clearance,
+  REQUIRE(mp_out_any(MpCartOut{status, reached, span, t, clearance, deviation_pos, deviation_rot, pose_error, iterations, evaluations,
+                               span_status, span_clearance}) ||
+              q || dq || ddq,
           "%s: at least one output is required", fn);
   const size_t n = (size_t)model->d.n, ib = (size_t)B * sizeof(int32_t), db = (size_t)B * sizeof(double);
   const size_t gb = (size_t)N * n * db, sp = (size_t)(N - 1);
@@ -3568,12 +3523,10 @@ static int trajectory_sample_impl(const char* fn, mp_ctx* ctx, const mp_model* m
   REQUIRE(max_blocks >= 0, "%s: negative max_blocks", fn);
   if (I.B == 0) return MP_OK;
   REQUIRE(I.t && I.x, "%s: null device pointer", fn);
-  REQUIRE(O.status || O.count || O.needed || O.s || O.sd || O.sdd || O.pos || O.vel || O.acc || O.tau, "%s: at least one output is required",
-          fn);
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
   REQUIRE(aligned16(I.t) && aligned16(I.x) && aligned16(I.q) && aligned16(I.dq) && aligned16(I.ddq) && aligned16(I.bstatus) &&
               aligned16(I.bcount) && aligned16(I.points) && aligned16(I.cut) && aligned16(I.knot) && aligned16(I.length) &&
-              aligned16(O.status) && aligned16(O.count) && aligned16(O.needed) && aligned16(O.s) && aligned16(O.sd) && aligned16(O.sdd) &&
-              aligned16(O.pos) && aligned16(O.vel) && aligned16(O.acc) && aligned16(O.tau),
+              mp_out_aligned16(O),
           "%s: device pointers must be 16-byte aligned", fn);
   MpCall<double> c;
   make_call<double>(model, g, Ftip, &c);
@@ -3637,7 +3590,7 @@ int mp_trajectory_sample_host_f64(mp_ctx* ctx, const mp_model* model, const doub
     return rc;
   if (B == 0) return MP_OK;
   REQUIRE(t && x, "%s: null host pointer", fn);
-  REQUIRE(status || count || needed || s || sd || sdd || positions || velocities || accelerations || torques,
+  REQUIRE(mp_out_any(MpSampleOut{status, count, needed, s, sd, sdd, positions, velocities, accelerations, torques}),
           "%s: at least one output is required", fn);
   const size_t n = (size_t)model->d.n, ib = (size_t)B * sizeof(int32_t), db = (size_t)B * sizeof(double);
   const size_t gb = (size_t)N * db, wb = (size_t)W_in * db, mb = (size_t)M * db;
@@ -3699,8 +3652,8 @@ int mp_collision_set_cloud(mp_ctx* ctx, mp_collision* h, int64_t M, const double
 int mp_collision_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* d_q, int64_t rows, double eps_world,
                      double eps_self, double* d_dist_world, int32_t* d_arg_world, double* d_dist_self, int32_t* d_arg_self,
                      double* d_grad_dist_world, double* d_grad_dist_self, double* d_cost, double* d_grad) {
-  return collision_impl("mp_collision_f64", ctx, model, h, d_q, rows, eps_world, eps_self, d_dist_world, d_arg_world, d_dist_self,
-                        d_arg_self, d_grad_dist_world, d_grad_dist_self, d_cost, d_grad);
+  return collision_impl("mp_collision_f64", ctx, model, h, d_q, rows, eps_world, eps_self,
+                        {d_dist_world, d_arg_world, d_dist_self, d_arg_self, d_grad_dist_world, d_grad_dist_self, d_cost, d_grad});
 }
 
 int mp_collision_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, const double* q, int64_t rows, double eps_world,
@@ -3714,12 +3667,9 @@ int mp_collision_host_f64(mp_ctx* ctx, const mp_model* model, mp_collision* h, c
   const size_t n = (size_t)model->d.n, rb = (size_t)rows * sizeof(double), ib = (size_t)rows * 2 * sizeof(int32_t);
   HostCall hc(ctx);  // (h is the collision handle)
   const double* dq = hc.in(q, n * rb);
-  double* ddw = hc.out(dist_world, rb);
-  int32_t* daw = hc.out(arg_world, ib);
-  double* dds = hc.out(dist_self, rb);
-  int32_t* das = hc.out(arg_self, ib);
-  double *dgw = hc.out(grad_dist_world, n * rb), *dgs = hc.out(grad_dist_self, n * rb), *dcost = hc.out(cost, rb), *dgrad = hc.out(grad, n * rb);
-  return hc.run([&] { return collision_impl(fn, ctx, model, h, dq, rows, eps_world, eps_self, ddw, daw, dds, das, dgw, dgs, dcost, dgrad); });
+  const MpColOut O = {hc.out(dist_world, rb), hc.out(arg_world, ib), hc.out(dist_self, rb), hc.out(arg_self, ib),
+                      hc.out(grad_dist_world, n * rb), hc.out(grad_dist_self, n * rb), hc.out(cost, rb), hc.out(grad, n * rb)};
+  return hc.run([&] { return collision_impl(fn, ctx, model, h, dq, rows, eps_world, eps_self, O); });
 }
 
 }  // extern "C"

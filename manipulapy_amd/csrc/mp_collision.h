@@ -346,11 +346,19 @@ MP_HD void mp_collision_poison(bool bad, MpColRow<N>& out) {
   }
 }
 
-// One row r of the C entry over plain host rows, for the CPU twin.  Any output may be null.
+// the per-row outputs of a call, any of them null
+struct MpColOut {
+  double* dist_world;
+  int* arg_world;  // (rows, 2)
+  double* dist_self;
+  int* arg_self;   // (rows, 2)
+  double *grad_dist_world, *grad_dist_self, *cost, *grad;
+};
+
+// One row r of the C entry over plain host rows, for the CPU twin.  (k_collision stores for itself: its n-wide outputs leave through
+// the wave-cooperative stores.)
 template <int N, bool WANT_GRAD, typename MT, typename TB>
-void mp_collision_cpu_row(const MT& M, const TB& tb, const double* q, double eps_world, double eps_self, long r, double* dist_world,
-                          int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world, double* grad_dist_self, double* cost,
-                          double* grad) {
+void mp_collision_cpu_row(const MT& M, const TB& tb, const double* q, double eps_world, double eps_self, long r, const MpColOut& O) {
   double a[N];
   for (int j = 0; j < N; ++j) a[j] = q[r * N + j];
   MpBad<double> bad;
@@ -359,16 +367,16 @@ void mp_collision_cpu_row(const MT& M, const TB& tb, const double* q, double eps
   MpColRow<N> o;
   mp_collision_row<N, WANT_GRAD>(M, tb, a, eps_world, eps_self, park, o);
   mp_collision_poison<N, WANT_GRAD>(bad.any(), o);
-  if (dist_world) dist_world[r] = o.dist_world;
-  if (dist_self) dist_self[r] = o.dist_self;
-  if (cost) cost[r] = o.cost;
-  if (arg_world) { arg_world[2 * r] = o.arg_world[0]; arg_world[2 * r + 1] = o.arg_world[1]; }
-  if (arg_self) { arg_self[2 * r] = o.arg_self[0]; arg_self[2 * r + 1] = o.arg_self[1]; }
+  if (O.dist_world) O.dist_world[r] = o.dist_world;
+  if (O.dist_self) O.dist_self[r] = o.dist_self;
+  if (O.cost) O.cost[r] = o.cost;
+  if (O.arg_world) { O.arg_world[2 * r] = o.arg_world[0]; O.arg_world[2 * r + 1] = o.arg_world[1]; }
+  if (O.arg_self) { O.arg_self[2 * r] = o.arg_self[0]; O.arg_self[2 * r + 1] = o.arg_self[1]; }
   if constexpr (WANT_GRAD) {
     for (int j = 0; j < N; ++j) {
-      if (grad_dist_world) grad_dist_world[r * N + j] = o.grad_dist_world[j];
-      if (grad_dist_self) grad_dist_self[r * N + j] = o.grad_dist_self[j];
-      if (grad) grad[r * N + j] = o.grad[j];
+      if (O.grad_dist_world) O.grad_dist_world[r * N + j] = o.grad_dist_world[j];
+      if (O.grad_dist_self) O.grad_dist_self[r * N + j] = o.grad_dist_self[j];
+      if (O.grad) O.grad[r * N + j] = o.grad[j];
     }
   }
 }
@@ -414,6 +422,14 @@ struct MpWaveOpsSerial {
 struct MpColEdgeParams {
   double margin, tol;
   int max_steps, pad;
+};
+// the per-edge outputs of a call, any of them null
+struct MpColEdgeOut {
+  int* status;
+  double* t;
+  int* steps;
+  double* clearance;
+  int* witness;  // (edges, 3)
 };
 
 struct MpColEdgeEval {
@@ -562,22 +578,27 @@ MP_HD int mp_col_edge_iterate(const MT& M, const TB& tb, const MpColEdgeParams& 
   return 0;
 }
 
-// the row an edge reports: INVALID overrides whatever the zero edge gave
+// The row a finished edge reports, stored by the kernel and the twin alike (`done`: what mp_col_edge_iterate returned): INVALID
+// overrides whatever the zero edge gave.
 template <int N>
-MP_HD void mp_col_edge_result(const MpColEdgeState<N>& S, int done, int& status, double& t, int& steps, double& clearance, int (&witness)[3]) {
-  status = S.bad ? MP_COL_EDGE_INVALID : done - 1;
-  t = S.t; clearance = S.clearance;
+MP_HD void mp_col_edge_store(const MpColEdgeOut& O, long row, const MpColEdgeState<N>& S, int done) {
+  double t = S.t, clearance = S.clearance;
   mp_poison_if(S.bad, t);
   mp_poison_if(S.bad, clearance);
-  steps = S.bad ? 0 : S.steps;
+  if (O.status) O.status[row] = S.bad ? MP_COL_EDGE_INVALID : done - 1;
+  if (O.t) O.t[row] = t;
+  if (O.steps) O.steps[row] = S.bad ? 0 : S.steps;
+  if (O.clearance) O.clearance[row] = clearance;
+  if (O.witness) {
 #pragma unroll
-  for (int k = 0; k < 3; ++k) witness[k] = S.bad ? -1 : S.witness[k];
+    for (int k = 0; k < 3; ++k) O.witness[3 * row + k] = S.bad ? -1 : S.witness[k];
+  }
 }
 
-// One edge of the C entry over plain host rows, for the CPU twin.  Any output may be null.
+// One edge of the C entry over plain host rows, for the CPU twin.
 template <int N, typename MT, typename TB>
 void mp_collision_edge_cpu(const MT& M, const TB& tb, const double* q_from, const double* q_to, const MpColEdgeParams& P, long e,
-                           int* status, double* t, int* steps, double* clearance, int* witness) {
+                           const MpColEdgeOut& O) {
   double a[N], b[N];
   for (int j = 0; j < N; ++j) { a[j] = q_from[e * N + j]; b[j] = q_to[e * N + j]; }
   MpColParkLocal park;
@@ -586,12 +607,5 @@ void mp_collision_edge_cpu(const MT& M, const TB& tb, const double* q_from, cons
   mp_col_edge_begin<N>(M, tb.sph, a, b, S, L);
   int done;
   while (!(done = mp_col_edge_iterate<N>(M, tb, P, S, park, L))) {}
-  int st, sp, w[3];
-  double tt, cl;
-  mp_col_edge_result<N>(S, done, st, tt, sp, cl, w);
-  if (status) status[e] = st;
-  if (t) t[e] = tt;
-  if (steps) steps[e] = sp;
-  if (clearance) clearance[e] = cl;
-  if (witness) { witness[3 * e] = w[0]; witness[3 * e + 1] = w[1]; witness[3 * e + 2] = w[2]; }
+  mp_col_edge_store<N>(O, e, S, done);
 }

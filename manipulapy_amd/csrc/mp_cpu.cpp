@@ -1106,8 +1106,8 @@ int mp_collision_cpu_f64(const mp_model* model, const mp_collision* h, const dou
   REQUIRE(rows >= 0, "%s: negative row count", fn);
   if (rows == 0) return MP_OK;
   REQUIRE(q, "%s: null pointer", fn);
-  REQUIRE(dist_world || arg_world || dist_self || arg_self || grad_dist_world || grad_dist_self || cost || grad,
-          "%s: at least one output is required", fn);
+  const MpColOut O = {dist_world, arg_world, dist_self, arg_self, grad_dist_world, grad_dist_self, cost, grad};
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);
@@ -1115,10 +1115,8 @@ int mp_collision_cpu_f64(const mp_model* model, const mp_collision* h, const dou
   MP_CPU_DISPATCH(M.n, {
     parallel_for(rows, 64, nthreads, [&](int64_t lo, int64_t hi) {
       for (int64_t r = lo; r < hi; ++r) {
-        if (want_grad) mp_collision_cpu_row<N, true>(M, tb, q, eps_world, eps_self, (long)r, dist_world, arg_world, dist_self, arg_self,
-                                                     grad_dist_world, grad_dist_self, cost, grad);
-        else mp_collision_cpu_row<N, false>(M, tb, q, eps_world, eps_self, (long)r, dist_world, arg_world, dist_self, arg_self, nullptr,
-                                            nullptr, cost, nullptr);
+        if (want_grad) mp_collision_cpu_row<N, true>(M, tb, q, eps_world, eps_self, (long)r, O);
+        else mp_collision_cpu_row<N, false>(M, tb, q, eps_world, eps_self, (long)r, O);
       }
     });
   })
@@ -1154,14 +1152,15 @@ int mp_collision_edges_cpu_f64(const mp_model* model, const mp_collision* h, con
   REQUIRE(edges >= 0, "%s: negative edge count", fn);
   if (edges == 0) return MP_OK;
   REQUIRE(q_from && q_to, "%s: null pointer", fn);
-  REQUIRE(status || t || steps || clearance || witness, "%s: at least one output is required", fn);
+  const MpColEdgeOut O = {status, t, steps, clearance, witness};
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);
   const MpColEdgeParams P = {margin, tol, max_steps, 0};
   MP_CPU_DISPATCH(M.n, {
     parallel_for(edges, 16, nthreads, [&](int64_t lo, int64_t hi) {
-      for (int64_t e = lo; e < hi; ++e) mp_collision_edge_cpu<N>(M, tb, q_from, q_to, P, (long)e, status, t, steps, clearance, witness);
+      for (int64_t e = lo; e < hi; ++e) mp_collision_edge_cpu<N>(M, tb, q_from, q_to, P, (long)e, O);
     });
   })
   return MP_OK;
@@ -1216,7 +1215,8 @@ int mp_rrt_connect_cpu_f64(const mp_model* model, const mp_collision* h, const d
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
   REQUIRE(q_start && q_goal, "%s: null pointer", fn);
-  REQUIRE(status || count || waypoints || iterations || nodes || evaluations, "%s: at least one output is required", fn);
+  const MpRrtOut O = {status, count, waypoints, iterations, nodes, evaluations};
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);
@@ -1224,9 +1224,7 @@ int mp_rrt_connect_cpu_f64(const mp_model* model, const mp_collision* h, const d
     parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
       std::vector<double> tree((size_t)2 * (size_t)max_nodes * N);  // the thread's trees, reused like a lane's
       std::vector<int> parents((size_t)2 * (size_t)max_nodes);
-      for (int64_t b = b0; b < b1; ++b)
-        mp_rrt_cpu<N>(M, tb, P, q_start, q_goal, (long)b, tree.data(), parents.data(), status, count, waypoints, iterations, nodes,
-                      evaluations);
+      for (int64_t b = b0; b < b1; ++b) mp_rrt_cpu<N>(M, tb, P, q_start, q_goal, (long)b, tree.data(), parents.data(), O);
     });
   })
   return MP_OK;
@@ -1273,17 +1271,15 @@ int mp_path_shortcut_cpu_f64(const mp_model* model, const mp_collision* h, const
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
   REQUIRE(waypoints_in && count_in, "%s: null pointer", fn);
-  REQUIRE(status || count || waypoints || length_in || length_out || iterations || accepted || skipped_full || evaluations,
-          "%s: at least one output is required", fn);
+  const MpShortcutOut O = {status, count, waypoints, length_in, length_out, iterations, accepted, skipped_full, evaluations};
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);
   MP_CPU_DISPATCH(M.n, {
     parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
       std::vector<double> pts((size_t)max_waypoints * N), cum((size_t)max_waypoints);  // the thread's path, reused like a lane's
-      for (int64_t b = b0; b < b1; ++b)
-        mp_shortcut_cpu<N>(M, tb, P, waypoints_in, count_in, (long)b, pts.data(), cum.data(), status, count, waypoints, length_in,
-                           length_out, iterations, accepted, skipped_full, evaluations);
+      for (int64_t b = b0; b < b1; ++b) mp_shortcut_cpu<N>(M, tb, P, waypoints_in, count_in, (long)b, pts.data(), cum.data(), O);
     });
   })
   return MP_OK;
@@ -1329,15 +1325,14 @@ int mp_goal_ik_cpu_f64(const mp_model* model, const mp_collision* h, const doubl
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
   REQUIRE(T_goal && q_seed, "%s: null pointer", fn);
-  REQUIRE(status || q || attempts || iterations || converged || pose_error || clearance || witness,
-          "%s: at least one output is required", fn);
+  const MpGoalOut O = {status, q, attempts, iterations, converged, pose_error, clearance, witness};
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);
   MP_CPU_DISPATCH(M.n, {
     parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
-      for (int64_t b = b0; b < b1; ++b)
-        mp_goal_cpu<N>(M, tb, P, T_goal, q_seed, (long)b, status, q, attempts, iterations, converged, pose_error, clearance, witness);
+      for (int64_t b = b0; b < b1; ++b) mp_goal_cpu<N>(M, tb, P, T_goal, q_seed, (long)b, O);
     });
   })
   return MP_OK;
@@ -1375,36 +1370,28 @@ int mp_path_blend_cpu_f64(const mp_model* model, const mp_collision* h, const do
   REQUIRE(B >= 0, "%s: negative problem count", fn);
   if (B == 0) return MP_OK;
   REQUIRE(waypoints_in && count_in, "%s: null pointer", fn);
-  REQUIRE(status || corner || count || points || cut || knot || length || halvings || evaluations || clearance || q || dq || ddq,
-          "%s: at least one output is required", fn);
+  const MpBlendOut O = {status, corner, count, points, cut, knot, length, halvings, evaluations, clearance};
+  const bool grid = q || dq || ddq;
+  REQUIRE(mp_out_any(O) || grid, "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);
-  const bool grid = q || dq || ddq;
   MP_CPU_DISPATCH(M.n, {
     parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
       // the tables the grid reads back, where the caller did not ask for them: the thread's own, reused like a lane's registers
       std::vector<double> own_points(grid && !points ? (size_t)W_in * N : 0), own_cut(grid && !cut ? (size_t)W_in : 0),
           own_knot(grid && !knot ? (size_t)W_in : 0);
       for (int64_t b = b0; b < b1; ++b) {
-        const MpBlendRows o = {points ? points + b * W_in * N : (grid ? own_points.data() : nullptr),
-                               cut ? cut + b * W_in : (grid ? own_cut.data() : nullptr),
-                               knot ? knot + b * W_in : (grid ? own_knot.data() : nullptr)};
+        MpBlendRows o = mp_blend_rows(O, (long)b, P.w_in, N);
+        if (grid && !points) o.points = own_points.data();
+        if (grid && !cut) o.cut = own_cut.data();
+        if (grid && !knot) o.knot = own_knot.data();
         MpBlendState<N> S;
-        mp_blend_cpu<N>(M, tb, P, waypoints_in + b * W_in * N, count_in[b], o, S);
-        const int st = S.status, m = S.m;
-        const double len = S.length;
-        if (status) status[b] = st;
-        if (corner) corner[b] = S.corner;
-        if (count) count[b] = m;
-        if (length) length[b] = len;
-        if (halvings) halvings[b] = S.halvings;
-        if (evaluations) evaluations[b] = S.evals;
-        if (clearance) clearance[b] = S.clearance;
+        mp_blend_cpu<N>(M, tb, P, waypoints_in + b * W_in * N, count_in[b], (long)b, o, O, S);
         if (!grid) continue;
         for (int i = 0; i < P.grid; ++i) {
           double x[N], dx[N], ddx[N];
-          mp_blend_sample<N>(st, m, len, o.points, o.cut, o.knot, i, P.grid, x, dx, ddx);
+          mp_blend_sample<N>(S.status, S.m, S.length, o.points, o.cut, o.knot, i, P.grid, x, dx, ddx);
           const int64_t at = (b * P.grid + i) * N;
           for (int j = 0; j < N; ++j) {
             if (q) q[at + j] = x[j];
@@ -1486,14 +1473,12 @@ int mp_cartesian_path_cpu_f64(const mp_model* model, const mp_collision* h, cons
     return rc;
   if (B == 0) return MP_OK;
   REQUIRE(q_start && T_goal, "%s: null pointer", fn);
-  REQUIRE(status || reached || span || t || clearance || deviation_pos || deviation_rot || pose_error || iterations || evaluations || q ||
-              dq || ddq || span_status || span_clearance,
-          "%s: at least one output is required", fn);
+  const MpCartOut O = {status, reached, span, t, clearance, deviation_pos, deviation_rot, pose_error, iterations, evaluations, span_status,
+                       span_clearance};
+  REQUIRE(mp_out_any(O) || q || dq || ddq, "%s: at least one output is required", fn);
   const MpModel<double>& M = model->d;
   MpColWorld hdr;
   const MpColTablesHost tb = col_host_tables(h, hdr);
-  const MpCartOut O = {status, reached, span, t, clearance, deviation_pos, deviation_rot, pose_error, iterations, evaluations, span_status,
-                       span_clearance};
   MP_CPU_DISPATCH(M.n, {
     parallel_for(B, 1, nthreads, [&](int64_t b0, int64_t b1) {
       // One problem at a time: its workspace and the grid arrays the caller did not ask for are the thread's own, addressed as
@@ -1564,11 +1549,10 @@ int mp_trajectory_sample_cpu_f64(const mp_model* model, const double* t, const d
     return rc;
   if (B == 0) return MP_OK;
   REQUIRE(t && x, "%s: null pointer", fn);
-  REQUIRE(status || count || needed || s || sd || sdd || positions || velocities || accelerations || torques,
-          "%s: at least one output is required", fn);
+  const MpSampleOut O = {status, count, needed, s, sd, sdd, positions, velocities, accelerations, torques};
+  REQUIRE(mp_out_any(O), "%s: at least one output is required", fn);
   I.t = t; I.x = x; I.q = q; I.dq = dq; I.ddq = ddq;
   I.bstatus = blend_status; I.bcount = blend_count; I.points = points; I.cut = cut; I.knot = knot; I.length = length;
-  const MpSampleOut O = {status, count, needed, s, sd, sdd, positions, velocities, accelerations, torques};
   const MpModel<double>& M = model->d;
   const MpCall<double> C = make_call<double>(model, g, Ftip);
   const int tau = !torques ? MP_TS_NO_TAU : (any_nonzero(Ftip) ? MP_TS_TAU_FTIP : MP_TS_TAU);

@@ -29,6 +29,15 @@ struct MpGoalParams {
   unsigned seed;
   int max_iters, max_attempts;
 };
+// the per-problem outputs of a call, any of them null
+struct MpGoalOut {
+  int* status;
+  double* q;           // (B, n)
+  int *attempts, *iterations, *converged;
+  double* pose_error;  // (B, 2)
+  double* clearance;
+  int* witness;        // (B, 3)
+};
 
 constexpr int MP_GOAL_IDLE = 0, MP_GOAL_RUN = 1, MP_GOAL_FINISHED = 2;
 
@@ -197,22 +206,35 @@ MP_HD int mp_goal_trip(const MT& M, const TB& tb, const MpGoalParams& P, MpGoalS
   return S.phase == MP_GOAL_FINISHED ? 1 : 0;
 }
 
-// One problem of the C entry over plain host rows, for the CPU twin.  Any output may be null.
+// The row a finished problem reports, stored by the kernel and the twin alike.  q leaves as n plain stores: the twin's rows are not
+// 16-byte aligned, so the kernels' vector store (RunIO) is not for both.
+template <int N>
+MP_HD void mp_goal_store(const MpGoalOut& O, long row, const MpGoalState<N>& S) {
+  if (O.status) O.status[row] = S.status;
+  if (O.q) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) O.q[row * N + j] = S.best[j];
+  }
+  if (O.attempts) O.attempts[row] = S.attempt + 1;
+  if (O.iterations) O.iterations[row] = S.iterations;
+  if (O.converged) O.converged[row] = S.converged;
+  if (O.pose_error) { O.pose_error[2 * row] = S.rot; O.pose_error[2 * row + 1] = S.tr; }
+  if (O.clearance) O.clearance[row] = S.clearance;
+  if (O.witness) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) O.witness[3 * row + k] = S.witness[k];
+  }
+}
+
+// One problem of the C entry over plain host rows, for the CPU twin.
 template <int N, typename MT, typename TB>
-void mp_goal_cpu(const MT& M, const TB& tb, const MpGoalParams& P, const double* T_goal, const double* q_seed, long b, int* status,
-                 double* q, int* attempts, int* iterations, int* converged, double* pose_error, double* clearance, int* witness) {
+void mp_goal_cpu(const MT& M, const TB& tb, const MpGoalParams& P, const double* T_goal, const double* q_seed, long b,
+                 const MpGoalOut& O) {
   MpColParkLocal park;
   MpColBoundsLocal<N> L;
   const MpWaveOpsSerial W{};
   MpGoalState<N> S;
   mp_goal_begin<N>(P, T_goal + 16 * b, q_seed + b * N, S);
   while (!mp_goal_trip<N>(M, tb, P, S, W, park, L, T_goal + 16 * b)) {}
-  if (status) status[b] = S.status;
-  if (q) for (int j = 0; j < N; ++j) q[b * N + j] = S.best[j];
-  if (attempts) attempts[b] = S.attempt + 1;
-  if (iterations) iterations[b] = S.iterations;
-  if (converged) converged[b] = S.converged;
-  if (pose_error) { pose_error[2 * b] = S.rot; pose_error[2 * b + 1] = S.tr; }
-  if (clearance) clearance[b] = S.clearance;
-  if (witness) { witness[3 * b] = S.witness[0]; witness[3 * b + 1] = S.witness[1]; witness[3 * b + 2] = S.witness[2]; }
+  mp_goal_store<N>(O, b, S);
 }

@@ -1,13 +1,17 @@
 // What the translation units that implement the C ABI share (mp_capi.cpp: the entries of a context; mp_cpu.cpp: their CPU twins):
-// the handle layouts, the one way to refuse a call (mp_fail / REQUIRE), the model gate, and per family the check of an entry's
-// arguments (mp_*_check, defined in mp_cpu.cpp) that all three entries of an operation call.  DESIGN.md, section 3, has the rules.
+// the handle layouts, the one way to refuse a call (mp_fail / REQUIRE), the pointer checks of an output struct (mp_out_any,
+// mp_out_aligned16), the model gate, and per family the check of an entry's arguments (mp_*_check, defined in mp_cpu.cpp) that all
+// three entries of an operation call.  DESIGN.md, section 3, has the rules.
 #pragma once
+#include <array>
 #include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/manipula_hip.h"
@@ -36,6 +40,28 @@ __attribute__((format(printf, 2, 3))) inline int mp_fail(int code, const char* f
   do {                                                            \
     if (!(cond)) return mp_fail(MP_ERR_INVALID, __VA_ARGS__);     \
   } while (0)
+
+// ---- the pointer checks of an output struct (MpColOut ... MpSampleOut: pointers only, any of them null), seen as its array of pointers
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+template <typename Out>
+std::array<const void*, sizeof(Out) / sizeof(void*)> mp_out_pointers(const Out& O) {
+  static_assert(std::is_standard_layout<Out>::value && sizeof(Out) % sizeof(void*) == 0, "an output struct is a whole number of pointers");
+  std::array<const void*, sizeof(Out) / sizeof(void*)> p;
+  std::memcpy(p.data(), &O, sizeof O);
+  return p;
+}
+template <typename Out>
+bool mp_out_any(const Out& O) {  // is any output asked for
+  for (const void* p : mp_out_pointers(O))
+    if (p) return true;
+  return false;
+}
+template <typename Out>
+bool mp_out_aligned16(const Out& O) {  // (a null pointer is aligned)
+  for (const void* p : mp_out_pointers(O))
+    if (!aligned16(p)) return false;
+  return true;
+}
 
 struct mp_model {
   MpModel<double> d;   // n <= MP_MAX_DOF: the unrolled kernels take these by value.  d.n is ALWAYS the joint count.

@@ -175,10 +175,11 @@ hipError_t mpk_traj_id_tab(hipStream_t s, const MpModel<float>& M, const MpCall<
                            const float* end, long B, long Nt, const double* tab, float* tau);
 
 // sphere-model collision distances, cost and gradients (csrc/mp_collision.h), float64, 1..MP_MAX_DOF joints; D.S sizes the dynamic
-// LDS; every output may be null
+// LDS; O: the outputs, any of them null (the gradient instance is taken when one of its three gradient arrays is given)
 struct MpColSpheres;
 struct MpColPair;
 struct MpColWorld;
+struct MpColOut;
 struct MpColDevice {  // a collision handle's tables on one device, and the 8-byte head of the work queue beside them
   int S;
   const MpColSpheres* sph;
@@ -188,15 +189,15 @@ struct MpColDevice {  // a collision handle's tables on one device, and the 8-by
   bool cloud;  // the handle has a point cloud (csrc/mp_cloud.h): the launchers take the kernels' instance that queries it
 };
 hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q, long rows, double eps_world,
-                         double eps_self, double* dist_world, int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world,
-                         double* grad_dist_self, double* cost, double* grad);
+                         double eps_self, const MpColOut& O);
 // The one-wave work-queue kernels on the sphere model: continuous collision checking of joint-space edges (csrc/mp_collision.h),
 // batched RRT-Connect (csrc/mp_rrt.h, the trees in `workspace`: blocks x 64 x 2 max_nodes (8 n + 4) bytes), batched path
 // shortcutting (csrc/mp_shortcut.h, the working paths in `workspace`: blocks x 64 x max_waypoints (8 n + 8) bytes) and goal
 // configurations for pose goals (csrc/mp_goal.h, no workspace: one pose or collision evaluation a trip).  A work queue
 // over the edges / problems, one evaluated configuration a trip.  mpk_queue_plan gives a kernel's dynamic LDS and the blocks of it the
 // device keeps resident (occupancy x compute_units); the caller settles the grid (`blocks`) from that, the count, its cap and the
-// workspace, and hands grid and LDS to the launch, which zeroes D.counter on the stream first and makes no runtime query.
+// workspace, and hands grid and LDS to the launch, which zeroes D.counter on the stream first and makes no runtime query.  Each
+// family's outputs travel as one struct of pointers (Mp*Out, beside its Mp*Params), any of them null, from the entry to the kernel.
 enum MpQueueKernel { MP_QUEUE_EDGES, MP_QUEUE_RRT, MP_QUEUE_SHORTCUT, MP_QUEUE_GOAL, MP_QUEUE_BLEND };
 struct MpQueuePlan {
   unsigned lds;
@@ -204,29 +205,29 @@ struct MpQueuePlan {
 };
 hipError_t mpk_queue_plan(MpQueueKernel kernel, int n, int S, bool cloud, int compute_units, MpQueuePlan* plan);
 struct MpColEdgeParams;
+struct MpColEdgeOut;
 hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q_from, const double* q_to,
-                               long edges, const MpColEdgeParams& P, int* status, double* t, int* steps, double* clearance, int* witness,
-                               long blocks, unsigned lds);
+                               long edges, const MpColEdgeParams& P, const MpColEdgeOut& O, long blocks, unsigned lds);
 struct MpRrtParams;
+struct MpRrtOut;
 hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q_start, const double* q_goal,
-                           long problems, const MpRrtParams& P, int* status, int* count, double* waypoints, int* iterations, int* nodes,
-                           int* evaluations, double* workspace, long blocks, unsigned lds);
+                           long problems, const MpRrtParams& P, const MpRrtOut& O, double* workspace, long blocks, unsigned lds);
 struct MpShortcutParams;
+struct MpShortcutOut;
 hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
-                             long problems, const MpShortcutParams& P, int* status, int* count, double* waypoints, double* length_in,
-                             double* length_out, int* iterations, int* accepted, int* skipped_full, int* evaluations, double* workspace,
-                             long blocks, unsigned lds);
+                             long problems, const MpShortcutParams& P, const MpShortcutOut& O, double* workspace, long blocks,
+                             unsigned lds);
 struct MpGoalParams;
+struct MpGoalOut;
 hipError_t mpk_goal_ik(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* T_goal, const double* q_seed,
-                       long problems, const MpGoalParams& P, int* status, double* q, int* attempts, int* iterations, int* converged,
-                       double* pose_error, double* clearance, int* witness, long blocks, unsigned lds);
+                       long problems, const MpGoalParams& P, const MpGoalOut& O, long blocks, unsigned lds);
 // C2 corner blending of waypoint paths (csrc/mp_blend.h): the corners on the work queue (no workspace: one collision evaluation a
 // trip, a lane reads its own input rows), then mpk_path_blend_sample, one lane a grid point over problems x P.grid rows, which reads
-// status, count, points, cut, knot and length back (q, dq, ddq: any may be null).
+// O's status, count, points, cut, knot and length back (q, dq, ddq: any may be null).
 struct MpBlendParams;
+struct MpBlendOut;
 hipError_t mpk_path_blend(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
-                          long problems, const MpBlendParams& P, int* status, int* corner, int* count, double* points, double* cut,
-                          double* knot, double* length, int* halvings, int* evaluations, double* clearance, long blocks, unsigned lds);
+                          long problems, const MpBlendParams& P, const MpBlendOut& O, long blocks, unsigned lds);
 hipError_t mpk_path_blend_sample(hipStream_t s, int n, long problems, const MpBlendParams& P, const int* status, const int* count,
                                  const double* points, const double* cut, const double* knot, const double* length, double* q, double* dq,
                                  double* ddq);

@@ -477,10 +477,7 @@ template <int N, bool WANT_GRAD, bool CLOUD>
 __global__ __launch_bounds__(64) void k_collision(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                   const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                   const double* __restrict__ q, long rows, double eps_world, double eps_self,
-                                                  double* __restrict__ dist_world, int* __restrict__ arg_world,
-                                                  double* __restrict__ dist_self, int* __restrict__ arg_self,
-                                                  double* __restrict__ grad_dist_world, double* __restrict__ grad_dist_self,
-                                                  double* __restrict__ cost, double* __restrict__ grad) {
+                                                  const MpColOut O) {
   using ST = MpRowStage<double, N>;
   static_assert(ST::SPAN <= MP_WAVE_LDS_BYTES, "one array's 64 rows fit the wave's staging slice");
   __shared__ __attribute__((aligned(16))) char lds[MP_WAVE_LDS_BYTES];
@@ -510,16 +507,16 @@ __global__ __launch_bounds__(64) void k_collision(const MpModel<double> M, const
   mp_collision_row<N, WANT_GRAD>(M, tb, a, eps_world, eps_self, park, o);
   mp_collision_poison<N, WANT_GRAD>(bad.any(), o);
   if (lane < nvalid) {
-    if (dist_world != nullptr) dist_world[rr] = o.dist_world;
-    if (dist_self != nullptr) dist_self[rr] = o.dist_self;
-    if (cost != nullptr) cost[rr] = o.cost;
-    if (arg_world != nullptr) *reinterpret_cast<int2*>(arg_world + 2 * rr) = make_int2(o.arg_world[0], o.arg_world[1]);
-    if (arg_self != nullptr) *reinterpret_cast<int2*>(arg_self + 2 * rr) = make_int2(o.arg_self[0], o.arg_self[1]);
+    if (O.dist_world != nullptr) O.dist_world[rr] = o.dist_world;
+    if (O.dist_self != nullptr) O.dist_self[rr] = o.dist_self;
+    if (O.cost != nullptr) O.cost[rr] = o.cost;
+    if (O.arg_world != nullptr) *reinterpret_cast<int2*>(O.arg_world + 2 * rr) = make_int2(o.arg_world[0], o.arg_world[1]);
+    if (O.arg_self != nullptr) *reinterpret_cast<int2*>(O.arg_self + 2 * rr) = make_int2(o.arg_self[0], o.arg_self[1]);
   }
   if constexpr (WANT_GRAD) {
-    if (grad_dist_world != nullptr) mp_wave_store_auto<double, N>(grad_dist_world, row0, lane, nvalid, o.grad_dist_world, lds);
-    if (grad_dist_self != nullptr) mp_wave_store_auto<double, N>(grad_dist_self, row0, lane, nvalid, o.grad_dist_self, lds);
-    if (grad != nullptr) mp_wave_store_auto<double, N>(grad, row0, lane, nvalid, o.grad, lds);
+    if (O.grad_dist_world != nullptr) mp_wave_store_auto<double, N>(O.grad_dist_world, row0, lane, nvalid, o.grad_dist_world, lds);
+    if (O.grad_dist_self != nullptr) mp_wave_store_auto<double, N>(O.grad_dist_self, row0, lane, nvalid, o.grad_dist_self, lds);
+    if (O.grad != nullptr) mp_wave_store_auto<double, N>(O.grad, row0, lane, nvalid, o.grad, lds);
   }
 }
 
@@ -533,9 +530,8 @@ template <int N, bool CLOUD>
 __global__ __launch_bounds__(64) void k_collision_edges(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                         const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                         const double* __restrict__ q_from, const double* __restrict__ q_to, long edges,
-                                                        const MpColEdgeParams P, int* __restrict__ status, double* __restrict__ t,
-                                                        int* __restrict__ steps, double* __restrict__ clearance,
-                                                        int* __restrict__ witness, unsigned long long* __restrict__ next) {
+                                                        const MpColEdgeParams P, const MpColEdgeOut O,
+                                                        unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_col_edge_lds[];
   const int lane = (int)threadIdx.x;
   const auto tb = mp_col_tables_const<CLOUD>(sph, pairs, world);
@@ -554,14 +550,7 @@ __global__ __launch_bounds__(64) void k_collision_edges(const MpModel<double> M,
       have = true;
     }
     if (const int done = mp_col_edge_iterate<N>(M, tb, P, S, Q.park, Q.L)) {
-      int st, sp, w[3];
-      double tt, cl;
-      mp_col_edge_result<N>(S, done, st, tt, sp, cl, w);
-      if (status != nullptr) status[row] = st;
-      if (t != nullptr) t[row] = tt;
-      if (steps != nullptr) steps[row] = sp;
-      if (clearance != nullptr) clearance[row] = cl;
-      if (witness != nullptr) { witness[3 * row] = w[0]; witness[3 * row + 1] = w[1]; witness[3 * row + 2] = w[2]; }
+      mp_col_edge_store<N>(O, row, S, done);
       have = false;
     }
   }
@@ -590,9 +579,7 @@ template <int N, bool CLOUD>
 __global__ __launch_bounds__(64) void k_rrt_connect(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                     const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                     const double* __restrict__ q_start, const double* __restrict__ q_goal, long problems,
-                                                    const MpRrtParams P, int* __restrict__ status, int* __restrict__ count,
-                                                    double* __restrict__ waypoints, int* __restrict__ iterations, int* __restrict__ nodes,
-                                                    int* __restrict__ evaluations, double* __restrict__ workspace,
+                                                    const MpRrtParams P, const MpRrtOut O, double* __restrict__ workspace,
                                                     unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_rrt_lds[];
   const int lane = (int)threadIdx.x;
@@ -616,18 +603,14 @@ __global__ __launch_bounds__(64) void k_rrt_connect(const MpModel<double> M, con
         double a[N], b[N];
         RunIO<double, N>::load(q_start, row, a);
         RunIO<double, N>::load(q_goal, row, b);
-        mp_rrt_begin<N>(M, tb, P, a, b, S, T, Q.L, waypoints != nullptr ? waypoints + row * (long)P.max_waypoints * N : nullptr);
+        mp_rrt_begin<N>(M, tb, P, a, b, S, T, Q.L, O.waypoints != nullptr ? O.waypoints + row * (long)P.max_waypoints * N : nullptr);
         have = true;
       }
     }
     if (!T.wave_any(have)) break;
-    double* wp = (have && waypoints != nullptr) ? waypoints + row * (long)P.max_waypoints * N : nullptr;
+    double* wp = (have && O.waypoints != nullptr) ? O.waypoints + row * (long)P.max_waypoints * N : nullptr;
     if (mp_rrt_trip<N>(M, tb, P, S, T, Q.park, Q.L, wp)) {
-      if (status != nullptr) status[row] = S.status;
-      if (count != nullptr) count[row] = S.count;
-      if (iterations != nullptr) iterations[row] = S.k;
-      if (nodes != nullptr) { nodes[2 * row] = S.cnt0; nodes[2 * row + 1] = S.cnt1; }
-      if (evaluations != nullptr) evaluations[row] = S.evals;
+      mp_rrt_store<N>(O, row, S);
       have = false;
       S.phase = MP_RRT_IDLE;
     }
@@ -658,11 +641,7 @@ template <int N, bool CLOUD>
 __global__ __launch_bounds__(64) void k_path_shortcut(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                       const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                       const double* __restrict__ waypoints_in, const int* __restrict__ count_in,
-                                                      long problems, const MpShortcutParams P, int* __restrict__ status,
-                                                      int* __restrict__ count, double* __restrict__ waypoints,
-                                                      double* __restrict__ length_in, double* __restrict__ length_out,
-                                                      int* __restrict__ iterations, int* __restrict__ accepted,
-                                                      int* __restrict__ skipped_full, int* __restrict__ evaluations,
+                                                      long problems, const MpShortcutParams P, const MpShortcutOut O,
                                                       double* __restrict__ workspace, unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_shortcut_lds[];
   const int lane = (int)threadIdx.x;
@@ -685,21 +664,14 @@ __global__ __launch_bounds__(64) void k_path_shortcut(const MpModel<double> M, c
         dry = true;
       } else {
         mp_shortcut_begin<N>(P, waypoints_in + row * (long)P.w_in * N, count_in[row], S, T,
-                             waypoints != nullptr ? waypoints + row * (long)P.max_waypoints * N : nullptr);
+                             O.waypoints != nullptr ? O.waypoints + row * (long)P.max_waypoints * N : nullptr);
         have = true;
       }
     }
     if (!T.wave_any(have)) break;
-    double* wp = (have && waypoints != nullptr) ? waypoints + row * (long)P.max_waypoints * N : nullptr;
+    double* wp = (have && O.waypoints != nullptr) ? O.waypoints + row * (long)P.max_waypoints * N : nullptr;
     if (mp_shortcut_trip<N>(M, tb, P, S, T, Q.park, Q.L, wp)) {
-      if (status != nullptr) status[row] = S.status;
-      if (count != nullptr) count[row] = S.m;
-      if (length_in != nullptr) length_in[row] = S.lam_in;
-      if (length_out != nullptr) length_out[row] = S.m > 0 ? T.len(S.m - 1) : __builtin_nan("");
-      if (iterations != nullptr) iterations[row] = S.k;
-      if (accepted != nullptr) accepted[row] = S.accepted;
-      if (skipped_full != nullptr) skipped_full[row] = S.skipped_full;
-      if (evaluations != nullptr) evaluations[row] = S.evals;
+      mp_shortcut_store<N>(O, row, S, T);
       have = false;
       S.phase = MP_SC_IDLE;
       S.m = 0;
@@ -719,10 +691,7 @@ template <int N, bool CLOUD>
 __global__ __launch_bounds__(64) void k_goal_ik(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                 const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                 const double* __restrict__ T_goal, const double* __restrict__ q_seed, long problems,
-                                                const MpGoalParams P, int* __restrict__ status, double* __restrict__ q,
-                                                int* __restrict__ attempts, int* __restrict__ iterations, int* __restrict__ converged,
-                                                double* __restrict__ pose_error, double* __restrict__ clearance,
-                                                int* __restrict__ witness, unsigned long long* __restrict__ next) {
+                                                const MpGoalParams P, const MpGoalOut O, unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_goal_lds[];
   const int lane = (int)threadIdx.x;
   const auto tb = mp_col_tables_const<CLOUD>(sph, pairs, world);
@@ -744,14 +713,7 @@ __global__ __launch_bounds__(64) void k_goal_ik(const MpModel<double> M, const M
     }
     if (!W.wave_any(have)) break;
     if (mp_goal_trip<N>(M, tb, P, S, W, Q.park, Q.L, T_goal + 16 * (have ? row : 0))) {
-      if (status != nullptr) status[row] = S.status;
-      if (q != nullptr) RunIO<double, N>::store(q, row, S.best);
-      if (attempts != nullptr) attempts[row] = S.attempt + 1;
-      if (iterations != nullptr) iterations[row] = S.iterations;
-      if (converged != nullptr) converged[row] = S.converged;
-      if (pose_error != nullptr) { pose_error[2 * row] = S.rot; pose_error[2 * row + 1] = S.tr; }
-      if (clearance != nullptr) clearance[row] = S.clearance;
-      if (witness != nullptr) { witness[3 * row] = S.witness[0]; witness[3 * row + 1] = S.witness[1]; witness[3 * row + 2] = S.witness[2]; }
+      mp_goal_store<N>(O, row, S);
       have = false;
       S.phase = MP_GOAL_IDLE;
     }
@@ -769,11 +731,8 @@ template <int N, bool CLOUD>
 __global__ __launch_bounds__(64) void k_path_blend(const MpModel<double> M, const MpColSpheres* __restrict__ sph,
                                                    const MpColPair* __restrict__ pairs, const MpColWorld* __restrict__ world,
                                                    const double* __restrict__ waypoints_in, const int* __restrict__ count_in,
-                                                   long problems, const MpBlendParams P, int* __restrict__ status,
-                                                   int* __restrict__ corner, int* __restrict__ count, double* __restrict__ points,
-                                                   double* __restrict__ cut, double* __restrict__ knot, double* __restrict__ length,
-                                                   int* __restrict__ halvings, int* __restrict__ evaluations,
-                                                   double* __restrict__ clearance, unsigned long long* __restrict__ next) {
+                                                   long problems, const MpBlendParams P, const MpBlendOut O,
+                                                   unsigned long long* __restrict__ next) {
   extern __shared__ __attribute__((aligned(16))) double mp_blend_lds[];
   const int lane = (int)threadIdx.x;
   const auto tb = mp_col_tables_const<CLOUD>(sph, pairs, world);
@@ -793,21 +752,14 @@ __global__ __launch_bounds__(64) void k_path_blend(const MpModel<double> M, cons
         row = 0;
       } else {
         cin = count_in[row];
-        o = {points != nullptr ? points + row * (long)P.w_in * N : nullptr, cut != nullptr ? cut + row * (long)P.w_in : nullptr,
-             knot != nullptr ? knot + row * (long)P.w_in : nullptr};
+        o = mp_blend_rows(O, row, P.w_in, N);
         mp_blend_begin<N>(M, tb.sph, P, waypoints_in + row * (long)P.w_in * N, cin, S, Q.L, o);
         have = true;
       }
     }
     if (!W.wave_any(have)) break;
     if (mp_blend_trip<N>(M, tb, P, waypoints_in + row * (long)P.w_in * N, cin, S, Q.park, Q.L, o)) {
-      if (status != nullptr) status[row] = S.status;
-      if (corner != nullptr) corner[row] = S.corner;
-      if (count != nullptr) count[row] = S.m;
-      if (length != nullptr) length[row] = S.length;
-      if (halvings != nullptr) halvings[row] = S.halvings;
-      if (evaluations != nullptr) evaluations[row] = S.evals;
-      if (clearance != nullptr) clearance[row] = S.clearance;
+      mp_blend_store<N>(O, row, S);
       have = false;
       S.phase = MP_BL_IDLE;
     }
@@ -1755,12 +1707,11 @@ hipError_t mpk_fk_jac_vjp(hipStream_t s, const MpModel<double>& M, int frame, co
 
 // dynamic LDS: the park of S world centres for 64 lanes; beyond the default limit the function's own limit is raised first
 hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q, long rows, double eps_world,
-                         double eps_self, double* dist_world, int* arg_world, double* dist_self, int* arg_self, double* grad_dist_world,
-                         double* grad_dist_self, double* cost, double* grad) {
+                         double eps_self, const MpColOut& O) {
   if (rows <= 0) return hipSuccess;
   if (D.S < 1 || D.S > MP_COL_MAX_SPHERES) return hipErrorInvalidValue;
   const unsigned park = (unsigned)D.S * 3u * kWave * (unsigned)sizeof(double);
-  const bool want_grad = grad_dist_world != nullptr || grad_dist_self != nullptr || grad != nullptr;
+  const bool want_grad = O.grad_dist_world != nullptr || O.grad_dist_self != nullptr || O.grad != nullptr;
   MP_DISPATCH_N(M.n, MP_FLAG(want_grad, WG, MP_FLAG(D.cloud, CLOUD, {
     if (park + MP_WAVE_LDS_BYTES > 64u * 1024u) {
       const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_collision<N, WG, CLOUD>),
@@ -1768,7 +1719,7 @@ hipError_t mpk_collision(hipStream_t s, const MpModel<double>& M, const MpColDev
       if (e != hipSuccess) return e;
     }
     return launch(k_collision<N, WG, CLOUD>, mp_grid(rows, kWave), kWave, park, s, M, D.sph, D.pairs, D.world, q, rows, eps_world,
-                  eps_self, dist_world, arg_world, dist_self, arg_self, grad_dist_world, grad_dist_self, cost, grad);
+                  eps_self, O);
   })))
 }
 
@@ -1812,60 +1763,54 @@ static hipError_t queue_reset(hipStream_t s, const MpColDevice& D, long blocks) 
 }
 
 hipError_t mpk_collision_edges(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q_from, const double* q_to,
-                               long edges, const MpColEdgeParams& P, int* status, double* t, int* steps, double* clearance, int* witness,
-                               long blocks, unsigned lds) {
+                               long edges, const MpColEdgeParams& P, const MpColEdgeOut& O, long blocks, unsigned lds) {
   if (edges <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
   MP_DISPATCH_N(M.n, MP_FLAG(D.cloud, CLOUD,
       return launch(k_collision_edges<N, CLOUD>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, q_from, q_to, edges, P,
-                    status, t, steps, clearance, witness, D.counter)))
+                    O, D.counter)))
 }
 
 hipError_t mpk_rrt_connect(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* q_start, const double* q_goal,
-                           long problems, const MpRrtParams& P, int* status, int* count, double* waypoints, int* iterations, int* nodes,
-                           int* evaluations, double* workspace, long blocks, unsigned lds) {
+                           long problems, const MpRrtParams& P, const MpRrtOut& O, double* workspace, long blocks, unsigned lds) {
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
   MP_DISPATCH_N(M.n, MP_FLAG(D.cloud, CLOUD,
       return launch(k_rrt_connect<N, CLOUD>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, q_start, q_goal, problems, P,
-                    status, count, waypoints, iterations, nodes, evaluations, workspace, D.counter)))
+                    O, workspace, D.counter)))
 }
 
 hipError_t mpk_path_shortcut(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
-                             long problems, const MpShortcutParams& P, int* status, int* count, double* waypoints, double* length_in,
-                             double* length_out, int* iterations, int* accepted, int* skipped_full, int* evaluations, double* workspace,
-                             long blocks, unsigned lds) {
+                             long problems, const MpShortcutParams& P, const MpShortcutOut& O, double* workspace, long blocks,
+                             unsigned lds) {
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
   MP_DISPATCH_N(M.n, MP_FLAG(D.cloud, CLOUD,
       return launch(k_path_shortcut<N, CLOUD>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
-                    problems, P, status, count, waypoints, length_in, length_out, iterations, accepted, skipped_full, evaluations, workspace,
-                    D.counter)))
+                    problems, P, O, workspace, D.counter)))
 }
 
 hipError_t mpk_goal_ik(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* T_goal, const double* q_seed,
-                       long problems, const MpGoalParams& P, int* status, double* q, int* attempts, int* iterations, int* converged,
-                       double* pose_error, double* clearance, int* witness, long blocks, unsigned lds) {
+                       long problems, const MpGoalParams& P, const MpGoalOut& O, long blocks, unsigned lds) {
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
   MP_DISPATCH_N(M.n, MP_FLAG(D.cloud, CLOUD,
       return launch(k_goal_ik<N, CLOUD>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, T_goal, q_seed, problems, P,
-                    status, q, attempts, iterations, converged, pose_error, clearance, witness, D.counter)))
+                    O, D.counter)))
 }
 
 hipError_t mpk_path_blend(hipStream_t s, const MpModel<double>& M, const MpColDevice& D, const double* waypoints_in, const int* count_in,
-                          long problems, const MpBlendParams& P, int* status, int* corner, int* count, double* points, double* cut,
-                          double* knot, double* length, int* halvings, int* evaluations, double* clearance, long blocks, unsigned lds) {
+                          long problems, const MpBlendParams& P, const MpBlendOut& O, long blocks, unsigned lds) {
   if (problems <= 0) return hipSuccess;
   const hipError_t e = queue_reset(s, D, blocks);
   if (e != hipSuccess) return e;
   MP_DISPATCH_N(M.n, MP_FLAG(D.cloud, CLOUD,
       return launch(k_path_blend<N, CLOUD>, mp_grid(blocks, 1), kWave, lds, s, M, D.sph, D.pairs, D.world, waypoints_in, count_in,
-                    problems, P, status, corner, count, points, cut, knot, length, halvings, evaluations, clearance, D.counter)))
+                    problems, P, O, D.counter)))
 }
 
 hipError_t mpk_path_blend_sample(hipStream_t s, int n, long problems, const MpBlendParams& P, const int* status, const int* count,

@@ -30,6 +30,14 @@ struct MpRrtParams {
   unsigned seed;
   int max_iters, max_nodes, max_waypoints;
 };
+// the per-problem outputs of a call, any of them null
+struct MpRrtOut {
+  int *status, *count;
+  double* waypoints;  // (B, max_waypoints, n): written while the problem runs (mp_rrt_begin, mp_rrt_trip)
+  int* iterations;
+  int* nodes;         // (B, 2)
+  int* evaluations;
+};
 
 // the twin's trees: nodes [tree][node][dim], parents [tree][node]
 struct MpRrtTreeLocal : MpWaveOpsSerial {
@@ -287,23 +295,29 @@ MP_HD int mp_rrt_trip(const MT& M, const TB& tb, const MpRrtParams& P, MpRrtStat
   return S.phase == MP_RRT_FINISHED ? 1 : 0;
 }
 
+// the row a finished problem reports, stored by the kernel and the twin alike
+template <int N>
+MP_HD void mp_rrt_store(const MpRrtOut& O, long row, const MpRrtState<N>& S) {
+  if (O.status) O.status[row] = S.status;
+  if (O.count) O.count[row] = S.count;
+  if (O.iterations) O.iterations[row] = S.k;
+  if (O.nodes) { O.nodes[2 * row] = S.cnt0; O.nodes[2 * row + 1] = S.cnt1; }
+  if (O.evaluations) O.evaluations[row] = S.evals;
+}
+
 // One problem of the C entry over plain host rows, for the CPU twin.  `nodes` / `parents`: 2 max_nodes n doubles / 2 max_nodes ints
-// of the calling thread.  Any output may be null.
+// of the calling thread.
 template <int N, typename MT, typename TB>
 void mp_rrt_cpu(const MT& M, const TB& tb, const MpRrtParams& P, const double* q_start, const double* q_goal, long b, double* nodes,
-                int* parents, int* status, int* count, double* waypoints, int* iterations, int* node_counts, int* evaluations) {
+                int* parents, const MpRrtOut& O) {
   double qs[N], qg[N];
   for (int j = 0; j < N; ++j) { qs[j] = q_start[b * N + j]; qg[j] = q_goal[b * N + j]; }
   MpColParkLocal park;
   MpColBoundsLocal<N> L;
   MpRrtTreeLocal T{{}, nodes, parents, P.max_nodes, N};
   MpRrtState<N> S;
-  double* wp = waypoints ? waypoints + b * (long)P.max_waypoints * N : nullptr;
+  double* wp = O.waypoints ? O.waypoints + b * (long)P.max_waypoints * N : nullptr;
   mp_rrt_begin<N>(M, tb, P, qs, qg, S, T, L, wp);
   while (!mp_rrt_trip<N>(M, tb, P, S, T, park, L, wp)) {}
-  if (status) status[b] = S.status;
-  if (count) count[b] = S.count;
-  if (iterations) iterations[b] = S.k;
-  if (node_counts) { node_counts[2 * b] = S.cnt0; node_counts[2 * b + 1] = S.cnt1; }
-  if (evaluations) evaluations[b] = S.evals;
+  mp_rrt_store<N>(O, b, S);
 }

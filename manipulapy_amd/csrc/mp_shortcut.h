@@ -28,6 +28,13 @@ struct MpShortcutParams {
   unsigned seed;
   int max_iters, max_waypoints, w_in;  // w_in: the rows of an input path
 };
+// the per-problem outputs of a call, any of them null
+struct MpShortcutOut {
+  int *status, *count;
+  double* waypoints;  // (B, max_waypoints, n): written while the problem runs (mp_shortcut_begin, mp_shortcut_trip)
+  double *length_in, *length_out;
+  int *iterations, *accepted, *skipped_full, *evaluations;
+};
 
 // the twin's path: waypoints [waypoint][dim], lengths [waypoint]
 struct MpShortcutPathLocal : MpWaveOpsSerial {
@@ -268,25 +275,30 @@ MP_HD int mp_shortcut_trip(const MT& M, const TB& tb, const MpShortcutParams& P,
   return S.phase == MP_SC_FINISHED ? 1 : 0;
 }
 
+// the row a finished problem reports, stored by the kernel and the twin alike; T: its working path, which holds the output's length
+template <int N, typename PATH>
+MP_HD void mp_shortcut_store(const MpShortcutOut& O, long row, const MpShortcutState<N>& S, const PATH& T) {
+  if (O.status) O.status[row] = S.status;
+  if (O.count) O.count[row] = S.m;
+  if (O.length_in) O.length_in[row] = S.lam_in;
+  if (O.length_out) O.length_out[row] = S.m > 0 ? T.len(S.m - 1) : __builtin_nan("");
+  if (O.iterations) O.iterations[row] = S.k;
+  if (O.accepted) O.accepted[row] = S.accepted;
+  if (O.skipped_full) O.skipped_full[row] = S.skipped_full;
+  if (O.evaluations) O.evaluations[row] = S.evals;
+}
+
 // One problem of the C entry over plain host rows, for the CPU twin.  `pts` / `cum`: max_waypoints n / max_waypoints doubles of the
-// calling thread.  Any output may be null.
+// calling thread.
 template <int N, typename MT, typename TB>
 void mp_shortcut_cpu(const MT& M, const TB& tb, const MpShortcutParams& P, const double* waypoints_in, const int* count_in, long b,
-                     double* pts, double* cum, int* status, int* count, double* waypoints, double* length_in, double* length_out,
-                     int* iterations, int* accepted, int* skipped_full, int* evaluations) {
+                     double* pts, double* cum, const MpShortcutOut& O) {
   MpColParkLocal park;
   MpColBoundsLocal<N> L;
   MpShortcutPathLocal T{{}, pts, cum, N};
   MpShortcutState<N> S;
-  double* wp = waypoints ? waypoints + b * (long)P.max_waypoints * N : nullptr;
+  double* wp = O.waypoints ? O.waypoints + b * (long)P.max_waypoints * N : nullptr;
   mp_shortcut_begin<N>(P, waypoints_in + b * (long)P.w_in * N, count_in[b], S, T, wp);
   while (!mp_shortcut_trip<N>(M, tb, P, S, T, park, L, wp)) {}
-  if (status) status[b] = S.status;
-  if (count) count[b] = S.m;
-  if (length_in) length_in[b] = S.lam_in;
-  if (length_out) length_out[b] = S.m > 0 ? T.len(S.m - 1) : __builtin_nan("");
-  if (iterations) iterations[b] = S.k;
-  if (accepted) accepted[b] = S.accepted;
-  if (skipped_full) skipped_full[b] = S.skipped_full;
-  if (evaluations) evaluations[b] = S.evals;
+  mp_shortcut_store<N>(O, b, S, T);
 }

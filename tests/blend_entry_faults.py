@@ -74,7 +74,7 @@ def faults(flavour):
     out += [(f"null {k}", {k: None}, INVALID, pointer) for k in INPUTS]
     out.append(("no output", {k: None for k in OUTPUTS}, INVALID, "at least one output is required"))
     if flavour == "device":
-        out += [(f"misaligned {k}", {k: "misaligned"}, INVALID, "device pointers must be 16-byte aligned") for k in INPUTS + ("status", "ddq")]
+        out += [(f"misaligned {k}", {k: "misaligned"}, INVALID, "device pointers must be 16-byte aligned") for k in INPUTS + OUTPUTS]
         out.append(("negative max_blocks", {"max_blocks": -1}, INVALID, "negative max_blocks"))
         out += [(f"the grid without {k}", {k: None}, INVALID, REQUIRED) for k in TABLES]
     return out

@@ -82,7 +82,7 @@ def faults(flavour):
     if flavour == "device":
         out += [(f"without {k}", {k: None}, INVALID, REQUIRED) for k in GRID_ROWS]
         out += [(f"misaligned {k}", {k: "misaligned"}, INVALID, "device pointers must be 16-byte aligned")
-                for k in INPUTS + ("status", "ddq", "span_clearance", "workspace")]
+                for k in INPUTS + OUTPUTS + ("workspace",)]
         out.append(("negative max_blocks", {"max_blocks": -1}, INVALID, "negative max_blocks"))
         need = _hip.cartesian_path_workspace_bytes(1, GRID)
         out.append(("no workspace", {"workspace": None}, INVALID,

@@ -94,7 +94,7 @@ def faults(flavour, source, values):
     out.append(("no output", {k: None for k in OUTPUTS}, INVALID, "at least one output is required"))
     if flavour == "device":
         out += [(f"misaligned {k}", {k: "misaligned"}, INVALID, "device pointers must be 16-byte aligned")
-                for k in TIMING + (mine[0], mine[-1], "status", "s", "torques")]
+                for k in TIMING + (mine[0], mine[-1]) + OUTPUTS]
         out.append(("negative max_blocks", {"max_blocks": -1}, INVALID, "negative max_blocks"))
     return out
 

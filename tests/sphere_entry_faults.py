@@ -138,7 +138,7 @@ def faults(family, flavour):
     out.append(("no output", {k: None for k in outputs}, INVALID, "at least one output is required"))
     if flavour == "device":
         out += [(f"misaligned {k}", {k: "misaligned"}, INVALID, "device pointers must be 16-byte aligned")
-                for k in inputs + outputs[:1] + outputs[-1:] + (("workspace",) if family in ("rrt_connect", "path_shortcut") else ())]
+                for k in inputs + outputs + (("workspace",) if family in ("rrt_connect", "path_shortcut") else ())]
         out.append(("negative max_blocks", {"max_blocks": -1}, INVALID, "negative max_blocks") if family != "collision" else None)
         one = workspace_bytes(family)
         if one:

@@ -120,7 +120,8 @@ def test_output_subsets_and_threads():
     """Any subset of the outputs, the grid without its tables among them, and any thread count give the same values."""
     case, full = bc.make_blend_case("chain3"), bc.twin_of("chain3")
     cm = case["cm"]
-    for want in (("q",), ("ddq", "status"), ("cut", "knot"), ("clearance", "halvings", "evaluations", "corner"), ("points", "dq", "length")):
+    for want in (*((k,) for k in bc.KEYS), ("ddq", "status"), ("cut", "knot"), ("clearance", "halvings", "evaluations", "corner"),
+                 ("points", "dq", "length")):   # each output alone first
         got = _hip.cpu_path_blend(cm.model, cm.handle, case["waypoints"], case["count"], bc.GRID, bc.RUNS["base"], bc.TOL, want=want,
                                   nthreads=3, **bc.params_of())
         assert set(got) == set(want)

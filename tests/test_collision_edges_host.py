@@ -108,6 +108,15 @@ def test_twin_against_oracle(name):
     ec.check_against_oracle(_twin(name), ec.oracle_of(name), f"twin {name}")
 
 
+def test_each_output_alone_equals_the_full_run():
+    E = 67
+    case = ec.make_edge_case("chain3")
+    cm, full = case["cm"], _twin("chain3", edges=E)
+    for k in ec.EDGE_KEYS:
+        one = _hip.cpu_collision_edges(cm.model, cm.handle, case["qa"][:E], case["qb"][:E], ec.MARGIN, ec.TOL, ec.MAX_STEPS, want=(k,))
+        assert list(one) == [k] and np.array_equal(one[k], full[k], equal_nan=True), k
+
+
 # ------------------------------------------------------------------------------------------------ soundness
 def _sampled(name, qa, qb, samples=2001):
     """clearance (edges, samples) on the uniform grid of [0, 1], by the existing distance entry mp_collision_cpu_f64 (held to the

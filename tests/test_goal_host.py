@@ -117,7 +117,7 @@ def test_bit_equal_across_order_threads_and_subsets():
         gc.check_same(_run(case, p, nthreads=threads), full, f"{threads} threads")
     one = _run(case, p, case["Tg"][5:6], case["q0"][5:6])
     gc.check_same(one, {k: v[5:6] for k, v in full.items()}, "one problem")
-    for want in (("status",), ("q", "clearance"), ("attempts", "iterations", "converged"), ("pose_error", "witness")):
+    for want in (*((k,) for k in gc.GOAL_KEYS), ("q", "clearance"), ("attempts", "iterations", "converged"), ("pose_error", "witness")):
         sub = _run(case, p, want=want)
         assert set(sub) == set(want)
         gc.check_same(sub, full, f"subset {want}")

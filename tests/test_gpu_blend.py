@@ -130,8 +130,8 @@ def test_device_form_host_form_subsets_and_the_required_tables(ctx):
     host = ctx.path_blend_arrays(cm.model, cm.handle, wp, cnt, bc.GRID, bc.RUNS["base"], bc.TOL, **p)
     _same(dev, host)
     tables = ("status", "count", "points", "cut", "knot", "length")
-    for want in (("status",), ("corner", "halvings", "evaluations", "clearance"), ("points", "cut", "knot"), tables + ("dq",),
-                 tables + ("q", "ddq")):
+    alone = tuple((k,) if k not in ("q", "dq", "ddq") else tables + (k,) for k in ALL)   # each output alone; a grid array with the six tables
+    for want in (*alone, ("corner", "halvings", "evaluations", "clearance"), ("points", "cut", "knot"), tables + ("q", "ddq")):
         _same(device_run(ctx, case, wp, cnt, want=want), dev, want)
     for want in (("q",), ("ddq", "corner"), ("count",)):   # the host form keeps the tables the grid needs on the device
         sub = ctx.path_blend_arrays(cm.model, cm.handle, wp, cnt, bc.GRID, bc.RUNS["base"], bc.TOL, want=want, **p)

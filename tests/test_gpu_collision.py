@@ -103,6 +103,11 @@ def test_device_form_equals_host_form_and_output_subsets(ctx):
     assert np.array_equal(lean["arg_world"], dev["arg_world"]) and np.array_equal(lean["arg_self"], dev["arg_self"])
     for k in ("grad", "grad_dist_self"):                           # the gradient instance, one output at a time: the same code
         assert np.array_equal(device_run(ctx, cm, q, want=(k,))[k], dev[k]), k
+    case, _, _ = _case("chain3")                                   # each output alone: 67 rows, a staged wave and a tail of three lanes
+    cm, q = case["cm"], case["q"][:67]
+    dev = device_run(ctx, cm, q)
+    for k in ALL:
+        assert np.array_equal(device_run(ctx, cm, q, want=(k,))[k], dev[k], equal_nan=True), k
 
 
 def test_set_world_twice_without_rebuild(ctx):

@@ -125,6 +125,11 @@ def test_device_form_equals_host_form_and_output_subsets(ctx):
     und = short["status"] == ec.UNDECIDED
     assert und.any() and np.all(short["steps"][und] == 8)
     _same({k: v[~und] for k, v in short.items()}, {k: v[~und] for k, v in dev.items()})
+    case, _, _ = _case("chain3")                                   # each output alone: 67 edges, a full wave and three lanes
+    cm, qa, qb = case["cm"], case["qa"][:67], case["qb"][:67]
+    dev = device_run(ctx, cm, qa, qb)
+    for k in ALL:
+        _same(device_run(ctx, cm, qa, qb, want=(k,)), dev, (k,))
 
 
 def test_poisoned_edges_leave_their_neighbours_alone(ctx):

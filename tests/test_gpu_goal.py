@@ -112,7 +112,7 @@ def test_device_form_host_form_subsets_and_bad_rows(ctx):
     Tg[2, 0], q0[5, 0], q0[64, 1] = np.inf, -np.inf, np.nan  # bad rows beside good ones, the first and the last lanes of a wave among them
     dev = device_run(ctx, case, p, Tg, q0)
     gc.check_same(ctx.goal_ik_arrays(cm.model, cm.handle, Tg, q0, case["lo"], case["hi"], gc.MARGIN, gc.TOL, **p), dev, "host form")
-    for want in (("status",), ("q", "clearance"), ("attempts", "iterations", "converged"), ("pose_error", "witness")):
+    for want in (*((k,) for k in ALL), ("q", "clearance"), ("attempts", "iterations", "converged"), ("pose_error", "witness")):
         gc.check_same(device_run(ctx, case, p, Tg, q0, want=want), dev, f"subset {want}")
     sub = ctx.goal_ik_arrays(cm.model, cm.handle, Tg, q0, case["lo"], case["hi"], gc.MARGIN, gc.TOL, want=("q",), **p)
     assert set(sub) == {"q"} and np.array_equal(sub["q"], dev["q"], equal_nan=True)

@@ -150,7 +150,7 @@ def test_device_form_host_form_subsets_and_a_small_workspace(ctx):
     dev = device_run(ctx, case, qs, qg)
     host = ctx.rrt_connect_arrays(cm.model, cm.handle, qs, qg, case["lo"], case["hi"], rc.MARGIN, rc.TOL, **p)
     _same(dev, host)
-    for want in (("status",), ("waypoints", "nodes"), ("count", "iterations", "evaluations")):
+    for want in (*((k,) for k in ALL), ("waypoints", "nodes"), ("count", "iterations", "evaluations")):  # each output alone first
         _same(device_run(ctx, case, qs, qg, want=want), dev, want)
     sub = ctx.rrt_connect_arrays(cm.model, cm.handle, qs, qg, case["lo"], case["hi"], rc.MARGIN, rc.TOL, want=("count",), **p)
     assert set(sub) == {"count"} and np.array_equal(sub["count"], dev["count"])

@@ -205,7 +205,8 @@ def test_device_form_host_form_subsets_and_a_small_workspace(ctx):
     dev = device_run(ctx, case, wp, cnt)
     host = ctx.path_shortcut_arrays(cm.model, cm.handle, wp, cnt, sc.MARGIN, sc.TOL, **p)
     _same(dev, host)
-    for want in (("status",), ("waypoints", "length_out"), ("count", "iterations", "accepted", "skipped_full", "evaluations"), ("length_in",)):
+    for want in (*((k,) for k in ALL), ("waypoints", "length_out"),  # each output alone first
+                 ("count", "iterations", "accepted", "skipped_full", "evaluations")):
         _same(device_run(ctx, case, wp, cnt, want=want), dev, want)
     sub = ctx.path_shortcut_arrays(cm.model, cm.handle, wp, cnt, sc.MARGIN, sc.TOL, want=("count",), **p)
     assert set(sub) == {"count"} and np.array_equal(sub["count"], dev["count"])

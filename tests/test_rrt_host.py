@@ -119,6 +119,15 @@ def test_order_and_threads_do_not_matter():
     _same(_run("ur5", nthreads=3), full)
 
 
+def test_each_output_alone_equals_the_full_run():
+    B = 67
+    case, full = rc.make_plan_case("ur5"), _twin("ur5")
+    for k in rc.PLAN_KEYS:
+        one = _run("ur5", case["qs"][:B], case["qg"][:B], want=(k,))
+        assert list(one) == [k]
+        _same(one, {k: full[k][:B]}, (k,))
+
+
 def test_a_different_seed_changes_some_result():
     other = _run("ur5", seed=rc.SEED + 1)
     full = _twin("ur5")

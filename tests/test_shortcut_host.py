@@ -114,6 +114,15 @@ def test_order_and_threads_do_not_matter():
     _same(_run("ur5", nthreads=3), full)
 
 
+def test_each_output_alone_equals_the_full_run():
+    B = 67
+    case, full = sc.make_shortcut_case("ur5"), sc.twin_of("ur5")
+    for k in sc.KEYS:
+        one = _run("ur5", case["waypoints"][-B:], case["count"][-B:], want=(k,))
+        assert list(one) == [k]
+        _same(one, {k: full[k][-B:]}, (k,))
+
+
 def test_padding_rows_and_seed():
     """The rows past count_in are ignored; another seed changes some result and no STRAIGHT one."""
     case, full = sc.make_shortcut_case("ur5"), sc.twin_of("ur5")
